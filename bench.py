@@ -6,17 +6,21 @@ Workload (BASELINE.json configs[2], the one `metric` is quoted on; SURVEY.md 8d1
     Γ = 0.01 I + gridlaplacian(128,128)  (scripts/gridlaplace.jl:4-21, scripts/gaussianrandomfield.jl:15), d = 16384,
     ∇ϕ(x,i) = Γ[:,i]·x, Z = ZigZag(Γ, 0), c[i] = ‖Γ[:,i]‖₂, x0 ~ N(0,I), θ0 ∈ {±1}, t0 = 0, adapt = false,
     ONE ensemble of 4096 chains: at N GPUs rank r runs chains [r 4096/N, (r+1) 4096/N) (strong scaling, the north star's form; chains are
-    independent, no data-path collective; `--scaling weak` keeps 4096 chains PER GPU), Philox seeds 0x5EED0000 + chain.  At N = 1 the line also
-    carries `strong_proxy` -- this GPU running the 2048 / 1024 / 512 chains that a rank of a 2 / 4 / 8-GPU job runs: the per-GPU term of the curve,
-    measured -- and `pipeline`: the same steps with their trace consumed on the device (streaming mean + discretize) beside the sampler.
+    independent, no data-path collective; `--scaling weak` keeps 4096 chains PER GPU), Philox seeds 0x5EED0000 + chain.
 A "step" advances every chain by ΔT = 1.0 time units through pdmp_ensemble_run (one persistent kernel launch);
 the initial state is generated on the device, so inputs are resident in HBM when the timed region starts.
 Traces ARE written (32 B/event into a per-chain HBM segment, part of the algorithmic bytes) and recycled every step.
 
     python bench.py --gpus 1 --steps 20 --warmup 2
+    python bench.py --gpus 1 --steps 20 --warmup 2 --full
+    python bench.py --gpus 1 --steps 20 --warmup 2 --dump-outputs bench_outputs
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and, at N=1, `cpu_baseline`.
+Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline`.  A plain run sets up, warms up, times --steps steps and prints
+that line; everything measured beside the headline comes with `--full`: at N = 1 `cpu_baseline`, `exact` (the bit-identical evaluation),
+`strong_proxy` (this GPU running the 2048 / 1024 / 512 chains that a rank of a 2 / 4 / 8-GPU job runs: the per-GPU term of the curve, measured),
+`pipeline` (the same steps with their trace consumed on the device beside the sampler), `ess`, `mode` and `configs`; for C4 `late` and
+`with_path_integrals`; at N > 1 `weak`.  `--dump-outputs DIR` writes what the last timed step computed (dump_outputs) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -424,6 +428,47 @@ def measure_with_integrals(pkg, args, rank, local_rank):
             "note": "pdmp_ensemble_set_path_integrals(1): 18.7 instead of 11.9 KB of LDS per chain, 8 instead of 13 chains per CU"}
 
 
+DUMP_CHAINS = 16            # chains whose final state and last-step trace --dump-outputs writes (a fixed, seeded sample)
+DUMP_TRACE_BYTES = 32 << 20  # at most this much trace in all (C2's full-state records are 16 KB each: its per-chain traces are cut short)
+
+
+def dump_outputs(pkg, W, ens, outdir):
+    """What the timed path handed back after its last step, as float64 arrays under outdir: the counters of every chain (counters_<field>.npy), and
+    for DUMP_CHAINS chains drawn with a fixed seed (chains.npy) the final state (state_*.npy: what pdmp_ensemble_final_state /
+    pdmp_ensemble_bps_final_state return) and the events of the step's last launch (trace_*.npy, concatenated; trace_offsets.npy: where each
+    chain's run starts).  The inputs are seeded, so two builds run with the same arguments can be compared array for array."""
+    os.makedirs(outdir, exist_ok=True)
+    nch, d, cap = ens.nchains, W["d"], W["cap"]
+    cnt = ens.counters()
+    out = {"counters_" + f: cnt[f].astype(np.float64) for f in cnt.dtype.names if f != "reserved"}
+    chains = np.sort(np.random.default_rng(SEED0).choice(nch, size=min(nch, DUMP_CHAINS), replace=False))
+    out["chains"] = chains.astype(np.float64)
+    bps = W["config"] == "C2"  # (Bouncy Particle: full-state records (t, x, theta) and its own state getter)
+    states = [ens.bps_final_state(int(k), 1) if bps else ens.final_state(int(k), 1) for k in chains]
+    for f in states[0]:
+        out["state_" + f] = np.concatenate([s[f] for s in states]).astype(np.float64)
+    if cap:
+        ev_bytes = 8 * (1 + 2 * d) if bps else 8 * 4
+        per_chain = max(1, DUMP_TRACE_BYTES // (len(chains) * ev_bytes))
+        parts, offsets = [], [0]
+        for k in chains:
+            n = min(int(cnt["ntrace"][k]), per_chain)
+            if bps:
+                t, x, th = ens.bps_trace(int(k), 0, n, counters=cnt)
+                parts.append({"t": t, "x": x, "theta": th})
+            else:
+                ev = ens.trace(int(k), 0, n, counters=cnt)
+                parts.append({f: ev[f] for f in ev.dtype.names})
+            offsets.append(offsets[-1] + n)
+        for f in parts[0]:
+            out["trace_" + f] = np.concatenate([p[f] for p in parts]).astype(np.float64)
+        out["trace_offsets"] = np.asarray(offsets, dtype=np.float64)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= 64 << 20, total
+    for name, a in out.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
 def measure_ess(pkg, args, W, ens, local_rank):
     """ESS/s.  A fresh ensemble of the same shape is started IN STATIONARITY -- x0 ~ N(0, inv(Gamma)) exactly (DCT of the lattice,
     problems.gmrf_stationary_sample), theta0 uniform on {+-1} -- and run for B batches of length b on the timed kernel; after every batch
@@ -534,6 +579,12 @@ def main():
                     help="C3G: the 25^3 7-point lattice (d = 15625, |G1| = 7, |S| = 25) or a random symmetric pattern at d = 16384")
     ap.add_argument("--exact", action="store_true",
                     help="C3: the bit-identical moving evaluation (zz_local_spec8_kernel) instead of the tracked-gradient one")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what stands beside the headline (CPU baseline, exact, strong_proxy, pipeline, ESS, mode, configs, C4's late "
+                         "and with_path_integrals, N > 1's weak view); off: the run times its steps and prints the line, nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float64, < 64 MB: counters of every chain, "
+                         "final state and last-step trace of a fixed sample of chains); rank 0 only")
     args = ap.parse_args()
     if args.scaling is None:
         args.scaling = "strong" if args.config in ("C3", "C3G") and args.chains is None else "weak"
@@ -679,7 +730,8 @@ def main():
 
     launches = [0]
 
-    def step(k):
+    def step(k, keep_trace=False):
+        """keep_trace: leave the events of the step's last launch in the segments (--dump-outputs reads them after the timed region)."""
         T = (k + 1) * args.dt
         ms = 0.0
         while True:
@@ -690,7 +742,8 @@ def main():
             if cap:
                 if args.config != "C3":  # a chain whose segment filled up pauses with TRACE_FULL: drain and continue the slice
                     full = pkg._lib.needs_rerun(ens.counters()["status"])
-                ens.trace_reset()
+                if full or not keep_trace:
+                    ens.trace_reset()
             if not full:
                 return ms
 
@@ -701,7 +754,9 @@ def main():
         return {"num": int(cn["num"].sum()), "nacc": int(cn["nacc"].sum()), "nevents": int(cn["nevents"].sum()),
                 "grads": int(cn["ndraw_global"].sum()) // W.get("ksub", 1)}
 
-    placement_log = ens.debug_placement() if hasattr(ens, "debug_placement") else None  # (what set_state's placement probes saw and kept)
+    placement_log = None
+    if args.full and hasattr(ens, "debug_placement"):
+        placement_log = ens.debug_placement()  # (what set_state's placement probes saw and kept)
     for k in range(args.warmup):
         step(k)
     barrier()
@@ -710,40 +765,49 @@ def main():
     w0 = work_counters()
     launches[0] = 0
     kernel_ms = []
+    last = args.warmup + args.steps - 1
+    dump = args.dump_outputs is not None and rank == 0
     t_start = time.perf_counter()
     for k in range(args.warmup, args.warmup + args.steps):
-        kernel_ms.append(step(k))
+        kernel_ms.append(step(k, keep_trace=dump and k == last))
     barrier()
     elapsed = time.perf_counter() - t_start
     w1 = work_counters()
     cnt = ens.counters()
     bad = int(np.count_nonzero(cnt["status"] != pkg._lib.CHAIN_OK))
+    if dump:
+        dump_outputs(pkg, W, ens, args.dump_outputs)
+        if cap:
+            ens.trace_reset()
 
     work = {key: w1[key] - w0[key] for key in w0}
     num, nacc, nev = work["num"], work["nacc"], work["nevents"]
     if args.config == "C5":
         num = work["grads"]
 
-    # Beside the headline, never inside `value` (each measured in this process after the timed region)
+    # Beside the headline, never inside `value` (each measured in this process after the timed region; only with --full)
     exact = None
-    if rank == 0 and args.config == "C3" and not args.exact and args.exact_steps > 0:
+    if args.full and rank == 0 and args.config == "C3" and not args.exact and args.exact_steps > 0:
         exact = pkg.benchlib.measure_exact(pkg, args, G, c, cap, local_rank)
     strong_proxy = None
-    if rank == 0 and world == 1 and args.config == "C3" and args.lambda_ref == 0.0 and not args.no_strong_proxy and not args.gather and not args.no_trace:
+    if (args.full and rank == 0 and world == 1 and args.config == "C3" and args.lambda_ref == 0.0 and not args.no_strong_proxy and not args.gather
+            and not args.no_trace):
         v1 = nev / max(float(np.sum(kernel_ms)) * 1e-3, 1e-9)  # (this GPU's kernel-time rate at the full width: the same clock as the proxy's)
         strong_proxy = pkg.benchlib.measure_strong_proxy(pkg, args, G, c, local_rank, v1 if not args.exact else None,
                                             exact["value"] if exact else (v1 if args.exact else None))
     pipeline = None
-    if rank == 0 and world == 1 and args.config == "C3" and args.lambda_ref == 0.0 and not args.no_pipeline and not args.gather and not args.no_trace:
+    if (args.full and rank == 0 and world == 1 and args.config == "C3" and args.lambda_ref == 0.0 and not args.no_pipeline and not args.gather
+            and not args.no_trace):
         pipeline = pkg.benchlib.measure_pipeline(pkg, args, G, c, local_rank, nev / max(float(np.sum(kernel_ms)) * 1e-3, 1e-9))
     with_integrals = None
-    if rank == 0 and args.config == "C4" and not args.gather and os.environ.get("PDMP_BENCH_C4_INTEGRALS", "0") == "0" and args.exact_steps > 0:
+    if (args.full and rank == 0 and args.config == "C4" and not args.gather and os.environ.get("PDMP_BENCH_C4_INTEGRALS", "0") == "0"
+            and args.exact_steps > 0):
         with_integrals = measure_with_integrals(pkg, args, rank, local_rank)
     # C4: the timed region sits in the transient of a T = 2000 configuration -- adapt with factor 5 (scripts/logistic.jl:167) keeps raising bounds, the
     # acceptance falls from 0.8 to 0.04 over the first 200 time units and a slice gets 8 times as expensive (tools/c4_drift.py) -- so the SAME
     # ensemble is continued (untimed) to --late-T and timed again there: `late` is the figure of a long run, `value` the one of its first slices
     late = None
-    if args.config == "C4" and args.late_T > (args.warmup + args.steps) * args.dt and not args.gather:
+    if args.full and args.config == "C4" and args.late_T > (args.warmup + args.steps) * args.dt and not args.gather:
         k0 = args.warmup + args.steps
         k1 = int(round(args.late_T / args.dt))
         for k in range(k0, k1):
@@ -770,11 +834,11 @@ def main():
                     "note": "the same ensemble continued to T = %g and timed again: the bounds have adapted (the acceptance falls from 0.8 at T = 2 to "
                             "0.04 at T = 200, still falling slowly), a proposal costs what it costs in a long run" % (k1 * args.dt)}
     ess = None
-    if rank == 0 and world == 1 and args.config == "C3" and args.ess_batches >= 1 and not args.gather:
+    if args.full and rank == 0 and world == 1 and args.config == "C3" and args.ess_batches >= 1 and not args.gather:
         ess = measure_ess(pkg, args, W, ens, local_rank)
     # the default line also carries the other configurations (short runs, own processes) and the timing mode it ran in
     configs = mode = None
-    default_line = (rank == 0 and world == 1 and args.config == "C3" and not args.exact and not args.gather and not args.no_trace and not args.no_configs
+    default_line = (args.full and rank == 0 and world == 1 and args.config == "C3" and not args.exact and not args.gather and not args.no_trace and not args.no_configs
                     and args.grid == GRID and nch == CONFIG_DEFAULTS["C3"]["chains"] and strong_proxy is not None)
     if default_line:
         mode = pkg.benchlib.measure_mode(pkg, float(np.sum(kernel_ms)) / max(launches[0], 1), strong_proxy, placement_log)
@@ -857,7 +921,7 @@ def main():
     # N > 1, strong scaling: the weak-scaling view of the same job beside it (the configuration's width PER GPU: what rounds 1-4 reported),
     # so that one driver run yields both curves -- same barriers, max over ranks, never inside `value`
     weak = None
-    if world > 1 and args.scaling == "strong" and args.config == "C3" and not args.gather:
+    if args.full and world > 1 and args.scaling == "strong" and args.config == "C3" and not args.gather:
         nw = CONFIG_DEFAULTS["C3"]["chains"]
         ew = pkg.benchlib.c3_ensemble(pkg, G, c, nw, cap, SEED0 + rank * nw, not args.exact, local_rank)
         nst = max(2, min(args.steps, 6))
@@ -1015,7 +1079,7 @@ def main():
             out["mode"] = mode
         if with_integrals is not None:
             out["with_path_integrals"] = with_integrals
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(pkg, G, c) if args.config in ("C3", "C3G") else cpu_baseline_config(pkg, args.config)
             if ess is not None and "ensemble" in out["cpu_baseline"]:
                 # ESS/s of the CPU ensemble.  The CPU pool runs the reference's (moving) evaluation; the GPU ESS leg above ran the evaluation named in

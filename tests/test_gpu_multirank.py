@@ -250,7 +250,7 @@ def test_strong_scaling_two_ranks_on_one_device(gpu_pkg):
     against one rank running all 4096: `scaling` says strong, the communicator saw both ranks, every rank reports its share, the seeds continue
     across the ranks, the summed counters equal the one-rank run's, and the weak-scaling view is measured beside it."""
     steps, warm = 2, 1
-    common = ["--steps", str(steps), "--warmup", str(warm), "--no-cpu-baseline", "--ess-batches", "0", "--exact-steps", "0"]
+    common = ["--steps", str(steps), "--warmup", str(warm), "--full", "--no-cpu-baseline", "--ess-batches", "0", "--exact-steps", "0"]  # (--full: `weak`)
     two = _run_bench(2, common, {"PDMP_BENCH_SINGLE_DEVICE": "1", "PDMP_BENCH_BACKEND": "gloo"})
     assert two["scaling"] == "strong" and two["n_gpus"] == 2 and two["ranks_seen"] == 2
     assert two["config"]["total_chains"] == 4096 and two["config"]["chains_per_gpu"] == 2048

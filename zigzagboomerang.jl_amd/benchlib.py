@@ -24,7 +24,8 @@ SECONDARY = [
     # generation -- an n x n solve per Newton step on the host -- takes 90 s, more than this object's budget)
     ("C5_rows5000", ["--config", "C5", "--c5-rows", "5000", "--steps", "3", "--warmup", "1"]),
 ]
-QUIET = ["--no-cpu-baseline", "--ess-batches", "0", "--exact-steps", "0", "--no-strong-proxy", "--no-pipeline"]
+# (--full: C4's `late` is one of its side measurements; the flags after it switch the others off)
+QUIET = ["--full", "--no-cpu-baseline", "--ess-batches", "0", "--exact-steps", "0", "--no-strong-proxy", "--no-pipeline"]
 
 
 def measure_configs(bench_path, budget_s=115.0, per_run_s=60.0):
