@@ -378,6 +378,26 @@ pdmp_status pdmp_ensemble_bps_trace_copy(pdmp_ensemble* ens, int64_t chain, int6
 /* final (t, x, θ) and adapted c of chains [chain_first, chain_first+n): t, c are [n]; x, theta are [n x d] */
 pdmp_status pdmp_ensemble_bps_final_state(pdmp_ensemble* ens, int64_t chain_first, int64_t n, double* t, double* x,
                                           double* theta, double* c);
+/*
+ * Path moments of BouncyParticle / Boomerang (no counterpart in the reference; the exact time averages its trace's mean would approximate).
+ * order 1 keeps J1 = ∫_{t0}^{t} x dt, order 2 also J2 = ∫_{t0}^{t} x² dt, per chain and coordinate, in the event loop's registers: every
+ * segment adds its closed form -- linear, or the Boomerang's rotation about μ_flow.  Opt-in (default 0): order 0 runs the kernels of a
+ * plain ensemble, and with order >= 1 the events, counters and state are bit for bit those of order 0 -- only the moments are added, so a
+ * run with trace_capacity 0 gives posterior means and variances without writing a single event.  PDMP_SAMPLER_BPS only; call after
+ * set_flow_bps / set_flow_boomerang and before set_state_bps (which starts the moments at t0); PDMP_ERR_INVALID otherwise, for an order
+ * outside 0..2, or once a state exists.  set_flow_* resets the order to 0.
+ */
+pdmp_status pdmp_ensemble_set_bps_moments(pdmp_ensemble* ens, int order);
+/*
+ * j1 = ∫_{t0}^{T} x dt and j2 = ∫_{t0}^{T} x² dt of chains [chain_first, chain_first + n): host [n x d] row-major arrays; j2 may be NULL
+ * (non-NULL needs order 2).  Every chain in the range must satisfy t <= T <= its next scheduled event (refreshment or proposal) with
+ * status OK or TRACE_FULL -- what a run with PDMP_RUN_STOP_BEFORE at T leaves; otherwise PDMP_ERR_INVALID naming the chain (a
+ * reference-tail run leaves the clock past T; a TRACE_FULL pause may leave the next event before T).
+ * On a BPS ensemble with order >= 1, pdmp_ensemble_batch_means, pdmp_ensemble_ess_begin / _batch / _end, pdmp_ensemble_path_integrals and
+ * pdmp_ensemble_reduce_moments read J1 at their T under the same rule and mean what they mean for the ZigZag (with order 0 they refuse as
+ * for any BPS ensemble).
+ */
+pdmp_status pdmp_ensemble_bps_moments(pdmp_ensemble* ens, double T, int64_t chain_first, int64_t n, double* j1, double* j2);
 
 /* ------------------------------------------------------------------ trace consumers on the device (what callers do next with Ξ)
  *

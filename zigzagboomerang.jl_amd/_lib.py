@@ -43,7 +43,7 @@ EXPORTED_SYMBOLS = [
     "pdmp_ensemble_trace_dev", "pdmp_ensemble_counters_dev", 
     "pdmp_ensemble_set_flow_bps", "pdmp_ensemble_set_state_bps", "pdmp_ensemble_bps_trace_copy",
     "pdmp_ensemble_bps_final_state", "pdmp_ensemble_set_sticky", "pdmp_ensemble_set_adaptscale", "pdmp_ensemble_final_sigma", "pdmp_ensemble_set_flow_boomerang", "pdmp_ensemble_set_local_bound", "pdmp_ensemble_set_target_logistic", "pdmp_ensemble_set_flow_factboomerang",
-    "pdmp_ensemble_set_mass_cholesky", "pdmp_ensemble_set_bps_options",
+    "pdmp_ensemble_set_mass_cholesky", "pdmp_ensemble_set_bps_options", "pdmp_ensemble_set_bps_moments", "pdmp_ensemble_bps_moments",
     "pdmp_ensemble_ess_begin", "pdmp_ensemble_ess_batch", "pdmp_ensemble_ess_end", "pdmp_ensemble_set_gradient_tracking",
     "pdmp_ensemble_path_integrals", "pdmp_ensemble_set_path_integrals", "pdmp_ensemble_set_neighbourhood", "pdmp_ensemble_info",
     "pdmp_ensemble_consume_begin", "pdmp_ensemble_consume", "pdmp_ensemble_consume_async", "pdmp_ensemble_last_consume_ms", "pdmp_ensemble_consume_mean", "pdmp_ensemble_consume_inclusion", "pdmp_ensemble_consume_discretized", "pdmp_ensemble_consume_cummean", "pdmp_ensemble_consume_cummean_copy", "pdmp_ensemble_subtrace_copy", "pdmp_1d_run",
@@ -168,6 +168,8 @@ def load():
     L.pdmp_ensemble_ess_end.argtypes = [vp, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(f64), C.POINTER(f64)]
     L.pdmp_ensemble_set_mass_cholesky.argtypes = [vp, vp, vp, vp]
     L.pdmp_ensemble_set_bps_options.argtypes = [vp, C.c_int, C.c_int]
+    L.pdmp_ensemble_set_bps_moments.argtypes = [vp, C.c_int]
+    L.pdmp_ensemble_bps_moments.argtypes = [vp, f64, i64, i64, vp, vp]
     L.pdmp_ensemble_bps_trace_copy.argtypes = [vp, i64, i64, i64, vp, vp, vp]
     L.pdmp_ensemble_bps_final_state.argtypes = [vp, i64, i64, vp, vp, vp, vp]
     L.pdmp_debug_set_kernel.argtypes = [vp, C.c_int]

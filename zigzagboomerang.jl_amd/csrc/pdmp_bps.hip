@@ -94,12 +94,36 @@ __device__ __attribute__((noinline)) double bps_next_dt(uint64_t seed, uint64_t 
     return bps_poisson_time(a, b, pdmp_u01(seed, PDMP_STREAM_MAIN, n));
 }
 
+// ∫_0^τ x(s) ds (MOM >= 1) and ∫_0^τ x(s)² ds (MOM >= 2) along the free flow from (x, θ), one element: linear, x(s) = x + θs
+// (src/dynamics.jl:11-15), or the Boomerang's rotation about m, x(s) = m + A cos s + θ sin s with A = x − m (:29-36), sn = sin τ, cs = cos τ
+template <bool BOOM, int MOM>
+__device__ __forceinline__ void bps_seg_moments(double x, double th, double m, double tau, double sn, double cs, double& j1, double& j2) {
+    if constexpr (BOOM) {
+        const double A = x - m;
+        const double rot = A * sn + th * (1.0 - cs);
+        j1 += m * tau + rot;
+        if constexpr (MOM >= 2) {
+            const double h = 0.5 * tau, sc = 0.5 * (sn * cs);
+            j2 += m * m * tau + 2.0 * m * rot + A * A * (h + sc) + th * th * (h - sc) + A * th * (sn * sn);
+        }
+    } else {
+        (void)m, (void)sn, (void)cs;
+        j1 += tau * (x + th * (0.5 * tau));
+        if constexpr (MOM >= 2) j2 += tau * (x * x + x * th * tau + th * th * (tau * tau * (1.0 / 3.0)));
+    }
+}
+
 // FULL: d == 64 NS exactly, so the `element < d` guards (and their exec-mask bookkeeping) are compile-time true.
 // EXT: the extended instantiation (general Γ only) adds what the fast ones leave out -- a caller-supplied mass factor L
 // (reflect!, refresh!, Boomerang's grad_correct!: column-oriented substitution through LDS, the order oracle/pdmp_oracle.c
 // fixes), c::LocalBound with its horizon and the renew branch (src/not_fact_samplers.jl:29-31,65-71), and `subsample` (:90).
-template <int NS, bool DIAG, bool BOOM, bool IDENT, bool FULL = false, bool EXT = false>
-__global__ __launch_bounds__(64) void bps_run_kernel(BpsRunParams P) {
+// MOM (path moments, pdmp_ensemble_set_bps_moments): 0 none; 1 J1 = ∫x ds, 2 also J2 = ∫x² ds, per element from the chain's t0, kept in
+// registers beside x and θ and advanced in move() by the closed form of the segment (bps_seg_moments).  They never feed back into the
+// chain: with MOM > 0 the events, counters and state are bit for bit those of MOM = 0.
+// (Mom: one BpsMomParams where MOM > 0, nothing where MOM = 0)
+__device__ __forceinline__ BpsMomParams bps_mom_arg(BpsMomParams m) { return m; }
+template <int NS, bool DIAG, bool BOOM, bool IDENT, bool FULL = false, bool EXT = false, int MOM = 0, class... Mom>
+__global__ __launch_bounds__(64) void bps_run_kernel(BpsRunParams P, Mom... M) {
     const int lane = threadIdx.x;
     const int64_t chain = blockIdx.x;
     const int64_t d = P.d;
@@ -138,6 +162,24 @@ __global__ __launch_bounds__(64) void bps_run_kernel(BpsRunParams P) {
         }
     }
     if constexpr (IDENT) g[0] = mu[0] = dg[0] = 0.0;
+    constexpr int NJ1 = MOM >= 1 ? NS : 1, NJ2 = MOM >= 2 ? NS : 1;
+    double j1[NJ1], j2[NJ2];
+    double* gj1 = nullptr;
+    double* gj2 = nullptr;
+    if constexpr (MOM >= 1) {
+        const BpsMomParams mp = bps_mom_arg(M...);
+        gj1 = mp.J1 + chain * d;
+        if constexpr (MOM >= 2) gj2 = mp.J2 + chain * d;
+    }
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        const int64_t e = (int64_t)s * 64 + lane;
+        const bool in = FULL || e < d;
+        if constexpr (MOM >= 1) j1[s] = in ? gj1[e] : 0.0;
+        if constexpr (MOM >= 2) j2[s] = in ? gj2[e] : 0.0;
+    }
+    if constexpr (MOM < 1) j1[0] = 0.0;
+    if constexpr (MOM < 2) j2[0] = 0.0;
     const double rho = P.rho, rhobar = sqrt(1 - rho * rho);  // src/dynamics.jl:113
     const double T = P.T;
     const bool stop_before = (P.flags & PDMP_RUN_STOP_BEFORE) != 0;
@@ -293,7 +335,8 @@ __global__ __launch_bounds__(64) void bps_run_kernel(BpsRunParams P) {
         }
         nm += 1;
     };
-    // move_forward!(τ, t, x, θ, Flow): linear (src/dynamics.jl:11-15) or the rotation about μ (:29-36)
+    // move_forward!(τ, t, x, θ, Flow): linear (src/dynamics.jl:11-15) or the rotation about μ (:29-36); J += the segment's moments
+    // (from the state before the move; padding elements are 0 and stay 0)
     auto move = [&](double tau) {
         if (BOOM) {
             double sn, cs;
@@ -302,6 +345,7 @@ __global__ __launch_bounds__(64) void bps_run_kernel(BpsRunParams P) {
             for (int s = 0; s < NS; ++s) {
                 const int64_t e = (int64_t)s * 64 + lane;
                 const double m = (FULL || e < d) ? P.mu_flow[e] : 0.0;
+                if constexpr (MOM >= 1) bps_seg_moments<true, MOM>(x[s], th[s], m, tau, sn, cs, j1[s], j2[MOM >= 2 ? s : 0]);
                 const double xn = (x[s] - m) * cs + th[s] * sn + m;
                 const double tn = -(x[s] - m) * sn + th[s] * cs;
                 x[s] = xn;
@@ -309,7 +353,10 @@ __global__ __launch_bounds__(64) void bps_run_kernel(BpsRunParams P) {
             }
         } else {
 #pragma unroll
-            for (int s = 0; s < NS; ++s) x[s] += th[s] * tau;
+            for (int s = 0; s < NS; ++s) {
+                if constexpr (MOM >= 1) bps_seg_moments<false, MOM>(x[s], th[s], 0.0, tau, 0.0, 1.0, j1[s], j2[MOM >= 2 ? s : 0]);
+                x[s] += th[s] * tau;
+            }
         }
     };
     // ∇ϕx = ∇ϕ!(∇ϕx, x); grad_correct!: Boomerang subtracts L'\(L\(x − μ)) = x − μ for L = I (src/not_fact_samplers.jl:9-12)
@@ -504,6 +551,8 @@ __global__ __launch_bounds__(64) void bps_run_kernel(BpsRunParams P) {
         if (FULL || e < d) {
             gx[e] = x[s];
             gth[e] = th[s];
+            if constexpr (MOM >= 1) gj1[e] = j1[s];
+            if constexpr (MOM >= 2) gj2[e] = j2[s];
         }
     }
     if (lane == 0) {
@@ -657,61 +706,71 @@ __global__ __launch_bounds__(64) void bps_init_kernel(BpsRunParams P, const uint
     }
 }
 
+// the run kernel of one variant: the kernel of MOM = 0, or the one keeping the path moments the ensemble asked for (m.mom)
+template <int NS, bool DIAG, bool BOOM, bool IDENT, bool FULL = false, bool EXT = false>
+static void launch_run(const BpsRunParams& p, const BpsMomParams& m, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
+    if (m.mom >= 2) hipLaunchKernelGGL((bps_run_kernel<NS, DIAG, BOOM, IDENT, FULL, EXT, 2, BpsMomParams>), grid, block, lds, s, p, m);
+    else if (m.mom == 1) hipLaunchKernelGGL((bps_run_kernel<NS, DIAG, BOOM, IDENT, FULL, EXT, 1, BpsMomParams>), grid, block, lds, s, p, m);
+    else hipLaunchKernelGGL((bps_run_kernel<NS, DIAG, BOOM, IDENT, FULL, EXT, 0>), grid, block, lds, s, p);
+}
+
 template <int NS>
-static int launch_ns(const BpsRunParams& p, int64_t nchains, bool diag, bool init, const uint64_t* seeds, double t0,
+static int launch_ns(const BpsRunParams& p, const BpsMomParams& m, int64_t nchains, bool diag, bool init, const uint64_t* seeds, double t0,
                      double c0, void* stream) {
     const size_t lds = (size_t)p.d * 8;
     dim3 grid((unsigned)nchains), block(64);
     const bool boom = p.flow_kind == 1;
+    const hipStream_t s = (hipStream_t)stream;
     if (init) {
-        if (boom) hipLaunchKernelGGL((bps_init_kernel<NS, true>), grid, block, lds, (hipStream_t)stream, p, seeds, t0, c0);
-        else hipLaunchKernelGGL((bps_init_kernel<NS, false>), grid, block, lds, (hipStream_t)stream, p, seeds, t0, c0);
+        if (boom) hipLaunchKernelGGL((bps_init_kernel<NS, true>), grid, block, lds, s, p, seeds, t0, c0);
+        else hipLaunchKernelGGL((bps_init_kernel<NS, false>), grid, block, lds, s, p, seeds, t0, c0);
     } else if (p.ext) {
-        if (boom) hipLaunchKernelGGL((bps_run_kernel<NS, false, true, false, false, true>), grid, block, lds, (hipStream_t)stream, p);
-        else hipLaunchKernelGGL((bps_run_kernel<NS, false, false, false, false, true>), grid, block, lds, (hipStream_t)stream, p);
+        if (boom) launch_run<NS, false, true, false, false, true>(p, m, grid, block, lds, s);
+        else launch_run<NS, false, false, false, false, true>(p, m, grid, block, lds, s);
     } else if (boom) {
-        if (diag) hipLaunchKernelGGL((bps_run_kernel<NS, true, true, false>), grid, block, lds, (hipStream_t)stream, p);
-        else hipLaunchKernelGGL((bps_run_kernel<NS, false, true, false>), grid, block, lds, (hipStream_t)stream, p);
+        if (diag) launch_run<NS, true, true, false>(p, m, grid, block, lds, s);
+        else launch_run<NS, false, true, false>(p, m, grid, block, lds, s);
     } else if (diag && p.ident && p.d == (int64_t)NS * 64) {
-        hipLaunchKernelGGL((bps_run_kernel<NS, true, false, true, true>), grid, block, lds, (hipStream_t)stream, p);
+        launch_run<NS, true, false, true, true>(p, m, grid, block, lds, s);
     } else if (diag && p.ident) {
-        hipLaunchKernelGGL((bps_run_kernel<NS, true, false, true>), grid, block, lds, (hipStream_t)stream, p);
+        launch_run<NS, true, false, true>(p, m, grid, block, lds, s);
     } else if (diag) {
-        hipLaunchKernelGGL((bps_run_kernel<NS, true, false, false>), grid, block, lds, (hipStream_t)stream, p);
+        launch_run<NS, true, false, false>(p, m, grid, block, lds, s);
     } else {
-        hipLaunchKernelGGL((bps_run_kernel<NS, false, false, false>), grid, block, lds, (hipStream_t)stream, p);
+        launch_run<NS, false, false, false>(p, m, grid, block, lds, s);
     }
     return (int)hipGetLastError();
 }
 
 template <int NS>
-static int launch_big(const BpsRunParams& p, int64_t nchains, bool init, const uint64_t* seeds, double t0, double c0, void* stream) {
+static int launch_big(const BpsRunParams& p, const BpsMomParams& m, int64_t nchains, bool init, const uint64_t* seeds, double t0, double c0, void* stream) {
     const size_t lds = (size_t)p.d * 8;
     dim3 grid((unsigned)nchains), block(64);
     const bool boom = p.flow_kind == 1;
+    const hipStream_t s = (hipStream_t)stream;
     if (init) {
-        if (boom) hipLaunchKernelGGL((bps_init_kernel<NS, true>), grid, block, lds, (hipStream_t)stream, p, seeds, t0, c0);
-        else hipLaunchKernelGGL((bps_init_kernel<NS, false>), grid, block, lds, (hipStream_t)stream, p, seeds, t0, c0);
+        if (boom) hipLaunchKernelGGL((bps_init_kernel<NS, true>), grid, block, lds, s, p, seeds, t0, c0);
+        else hipLaunchKernelGGL((bps_init_kernel<NS, false>), grid, block, lds, s, p, seeds, t0, c0);
     } else if (boom) {
-        hipLaunchKernelGGL((bps_run_kernel<NS, false, true, false, false, true>), grid, block, lds, (hipStream_t)stream, p);
+        launch_run<NS, false, true, false, false, true>(p, m, grid, block, lds, s);
     } else {
-        hipLaunchKernelGGL((bps_run_kernel<NS, false, false, false, false, true>), grid, block, lds, (hipStream_t)stream, p);
+        launch_run<NS, false, false, false, false, true>(p, m, grid, block, lds, s);
     }
     return (int)hipGetLastError();
 }
 
-static int dispatch(const BpsRunParams& p, int64_t nchains, bool diag, bool init, const uint64_t* seeds, double t0,
+static int dispatch(const BpsRunParams& p, const BpsMomParams& m, int64_t nchains, bool diag, bool init, const uint64_t* seeds, double t0,
                     double c0, void* stream) {
     const int64_t ns = (p.d + 63) / 64;
-    if (ns <= 1) return launch_ns<1>(p, nchains, diag, init, seeds, t0, c0, stream);
-    if (ns <= 2) return launch_ns<2>(p, nchains, diag, init, seeds, t0, c0, stream);
-    if (ns <= 4) return launch_ns<4>(p, nchains, diag, init, seeds, t0, c0, stream);
-    if (ns <= 8) return launch_ns<8>(p, nchains, diag, init, seeds, t0, c0, stream);
-    if (ns <= 16) return launch_ns<16>(p, nchains, diag, init, seeds, t0, c0, stream);
+    if (ns <= 1) return launch_ns<1>(p, m, nchains, diag, init, seeds, t0, c0, stream);
+    if (ns <= 2) return launch_ns<2>(p, m, nchains, diag, init, seeds, t0, c0, stream);
+    if (ns <= 4) return launch_ns<4>(p, m, nchains, diag, init, seeds, t0, c0, stream);
+    if (ns <= 8) return launch_ns<8>(p, m, nchains, diag, init, seeds, t0, c0, stream);
+    if (ns <= 16) return launch_ns<16>(p, m, nchains, diag, init, seeds, t0, c0, stream);
     // beyond 1024 coordinates the vectors no longer fit the register file as they are used here: the general instantiation (every option) is
     // compiled for 32 and 64 slots per lane, the compiler keeping what does not fit in AGPRs and scratch -- a capability, not a fast path
-    if (ns <= 32) return launch_big<32>(p, nchains, init, seeds, t0, c0, stream);
-    if (ns <= 64) return launch_big<64>(p, nchains, init, seeds, t0, c0, stream);
+    if (ns <= 32) return launch_big<32>(p, m, nchains, init, seeds, t0, c0, stream);
+    if (ns <= 64) return launch_big<64>(p, m, nchains, init, seeds, t0, c0, stream);
     return -1;
 }
 
@@ -905,11 +964,125 @@ int launch_sector_probe(double* rec, int64_t d, int64_t nchains, int rounds, int
     return (int)hipGetLastError();
 }
 
-int launch_bps_init(const BpsRunParams& p, int64_t nchains, const uint64_t* seeds, double t0, double c0, void* stream) {
-    return dispatch(p, nchains, false, true, seeds, t0, c0, stream);
+// ------------------------------------------------------------------------------------------ path moments (pdmp_ensemble_bps_moments)
+//
+// J(T) = J + ∫_t^T of chains [chain_first, chain_first + n) from their state (t = scal[0], x, θ) -- the closed forms of the event loop's
+// move(); the caller has checked t <= T <= the chain's next event.  One thread per element; o1 / o2 are [n x d] (o2 nullptr: J1 only).
+template <bool BOOM>
+__global__ __launch_bounds__(256) void bps_moments_tail_kernel(BpsRunParams P, BpsMomParams M, int64_t chain_first, int64_t n, double T,
+                                                               double* o1, double* o2) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t d = P.d;
+    if (k >= n * d) return;
+    const int64_t r = k / d, i = k - r * d;
+    const int64_t o = (chain_first + r) * d + i;
+    const double tau = T - P.scal[(chain_first + r) * 8];
+    double sn = 0.0, cs = 1.0, m = 0.0;
+    if constexpr (BOOM) {
+        pdmp_sincos(tau, &sn, &cs);
+        m = P.mu_flow[i];
+    }
+    double j1 = M.J1[o], j2 = (o2 && M.J2) ? M.J2[o] : 0.0;
+    if (o2) bps_seg_moments<BOOM, 2>(P.x[o], P.th[o], m, tau, sn, cs, j1, j2);
+    else bps_seg_moments<BOOM, 1>(P.x[o], P.th[o], m, tau, sn, cs, j1, j2);
+    o1[k] = j1;
+    if (o2) o2[k] = j2;
 }
-int launch_bps_run(const BpsRunParams& p, int64_t nchains, bool diag, void* stream) {
-    return dispatch(p, nchains, diag, false, nullptr, 0.0, 0.0, stream);
+int launch_bps_moments_tail(const BpsRunParams& p, const BpsMomParams& mp, int64_t chain_first, int64_t n, double T, double* o1, double* o2,
+                            void* stream) {
+    const int64_t m = n * p.d;
+    if (m <= 0) return 0;
+    const dim3 grid((unsigned)((m + 255) / 256));
+    if (p.flow_kind == 1) hipLaunchKernelGGL((bps_moments_tail_kernel<true>), grid, dim3(256), 0, (hipStream_t)stream, p, mp, chain_first, n, T, o1, o2);
+    else hipLaunchKernelGGL((bps_moments_tail_kernel<false>), grid, dim3(256), 0, (hipStream_t)stream, p, mp, chain_first, n, T, o1, o2);
+    return (int)hipGetLastError();
+}
+
+// Batch means and ESS sums over chains of a dense J(T) [nchains x d]: the arithmetic of zz_batch_means_kernel / zz_ess_kernel
+// (pdmp_kernels.hip), which read J off the ZigZag's records.  Threads own a coordinate and walk a group of chains.
+__global__ __launch_bounds__(256) void dense_batch_means_kernel(const double* J, double* jprev, int64_t d, int64_t nchains,
+                                                                int64_t chains_per_group, double T_prev, double T, double* sum_y,
+                                                                double* sum_y2) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= d) return;
+    const int64_t c0 = (int64_t)blockIdx.y * chains_per_group;
+    const int64_t c1 = (c0 + chains_per_group < nchains) ? (c0 + chains_per_group) : nchains;
+    const double inv = 1.0 / (T - T_prev);
+    double s1 = 0.0, s2 = 0.0;
+    for (int64_t ch = c0; ch < c1; ++ch) {
+        const double Jc = J[ch * d + i];
+        const double y = (Jc - jprev[ch * d + i]) * inv;
+        jprev[ch * d + i] = Jc;
+        s1 += y;
+        s2 += y * y;
+    }
+    atomicAdd(sum_y + i, s1);
+    atomicAdd(sum_y2 + i, s2);
+}
+// mode 0 snapshots J into jprev and jstart; mode 1: Y = (J − jprev)/ΔT, jprev = J, acc[0..1] += Y, Y²; mode 2: M = (J − jstart)/(T − T0),
+// acc[2..3] += M, M² (jprev / jstart untouched) -- as zz_ess_kernel
+__global__ __launch_bounds__(256) void dense_ess_kernel(const double* J, double* jprev, double* jstart, int64_t d, int64_t nchains,
+                                                        int64_t chains_per_group, int mode, double T_prev, double T, double* acc) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= d) return;
+    const int64_t c0 = (int64_t)blockIdx.y * chains_per_group;
+    const int64_t c1 = (c0 + chains_per_group < nchains) ? (c0 + chains_per_group) : nchains;
+    const double inv = (mode == 0) ? 0.0 : 1.0 / (T - T_prev);
+    double s1 = 0.0, s2 = 0.0;
+    for (int64_t ch = c0; ch < c1; ++ch) {
+        const double Jc = J[ch * d + i];
+        if (mode == 0) {
+            jprev[ch * d + i] = Jc;
+            jstart[ch * d + i] = Jc;
+        } else {
+            const double y = (Jc - ((mode == 1) ? jprev : jstart)[ch * d + i]) * inv;
+            if (mode == 1) jprev[ch * d + i] = Jc;
+            s1 += y;
+            s2 += y * y;
+        }
+    }
+    if (mode == 1) {
+        atomicAdd(acc + i, s1);
+        atomicAdd(acc + d + i, s2);
+    } else if (mode == 2) {
+        atomicAdd(acc + 2 * d + i, s1);
+        atomicAdd(acc + 3 * d + i, s2);
+    }
+}
+__global__ __launch_bounds__(256) void dense_gather_kernel(const double* J, int64_t d, int64_t nchains, const int64_t* __restrict__ probes,
+                                                           int64_t nprobe, double* __restrict__ out) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= nchains * nprobe) return;
+    const int64_t ch = k / nprobe, p = k - ch * nprobe;
+    out[k] = J[ch * d + probes[p]];
+}
+int launch_dense_batch_means(const double* J, double* jprev, int64_t d, int64_t nchains, double T_prev, double T, double* sum_y,
+                             double* sum_y2, void* stream) {
+    const int64_t groups = (nchains < 64) ? 1 : 64;
+    const int64_t per = (nchains + groups - 1) / groups;
+    dim3 grid((unsigned)((d + 255) / 256), (unsigned)groups);
+    hipLaunchKernelGGL(dense_batch_means_kernel, grid, dim3(256), 0, (hipStream_t)stream, J, jprev, d, nchains, per, T_prev, T, sum_y, sum_y2);
+    return (int)hipGetLastError();
+}
+int launch_dense_ess(const double* J, double* jprev, double* jstart, int64_t d, int64_t nchains, int mode, double T_prev, double T,
+                     double* acc, void* stream) {
+    const int64_t groups = (nchains < 64) ? 1 : 64;
+    const int64_t per = (nchains + groups - 1) / groups;
+    dim3 grid((unsigned)((d + 255) / 256), (unsigned)groups);
+    hipLaunchKernelGGL(dense_ess_kernel, grid, dim3(256), 0, (hipStream_t)stream, J, jprev, jstart, d, nchains, per, mode, T_prev, T, acc);
+    return (int)hipGetLastError();
+}
+int launch_dense_gather(const double* J, int64_t d, int64_t nchains, const int64_t* probes, int64_t nprobe, double* out, void* stream) {
+    const int64_t n = nchains * nprobe;
+    hipLaunchKernelGGL(dense_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, J, d, nchains, probes, nprobe, out);
+    return (int)hipGetLastError();
+}
+
+int launch_bps_init(const BpsRunParams& p, int64_t nchains, const uint64_t* seeds, double t0, double c0, void* stream) {
+    return dispatch(p, BpsMomParams{}, nchains, false, true, seeds, t0, c0, stream);
+}
+int launch_bps_run(const BpsRunParams& p, int64_t nchains, bool diag, void* stream, const BpsMomParams& m) {
+    return dispatch(p, m, nchains, diag, false, nullptr, 0.0, 0.0, stream);
 }
 
 }  // namespace pdmp

@@ -238,6 +238,9 @@ struct pdmp_ensemble {
     bool bps_mass_tables = false;
     int bps_local_bound = 0, bps_subsample = 0;
     bool bps_own_target = false;  // set_target_gaussian_csc on a BouncyParticle ensemble: ∇ϕ! differs from B.Γ(x − B.μ)
+    int bps_mom = 0;                // pdmp_ensemble_set_bps_moments: 0 off, 1 ∫x dt, 2 ∫x dt and ∫x² dt
+    DevBuf<double> b_j1, b_j2;      // [nchains x d] the moments up to each chain's clock (kept by the event loop)
+    DevBuf<double> b_jT, b_jT2;     // [nchains x d] the moments at the T of a read (pdmp_ensemble_bps_moments, the batch means / ESS sums)
     DevBuf<int64_t> bt_colptr, bt_rowval;
     DevBuf<double> bt_nzval, bt_mu;
     DevBuf<int32_t> m_Lcp, m_Lrv, m_Ucp, m_Urv;
@@ -1617,6 +1620,7 @@ pdmp_status pdmp_ensemble_set_state_synthetic(pdmp_ensemble* e, double t0, const
 }
 
 static void fill_bps_ext(const pdmp_ensemble* e, pdmp::BpsRunParams& B);
+static pdmp::BpsMomParams bps_moments_params(const pdmp_ensemble* e);
 
 pdmp_status pdmp_ensemble_run(pdmp_ensemble* e, double T, int flags, void* stream) {
     pdmp_status st = ensemble_run_impl(e, T, flags, stream);
@@ -1657,7 +1661,7 @@ static pdmp_status ensemble_run_impl(pdmp_ensemble* e, double T, int flags, void
         fill_bps_ext(e, B);
         HIP_TRY(hipEventRecord(e->ev0, s));
         e->last_kernel = "bps_run_kernel";
-        int rcb = pdmp::launch_bps_run(B, e->cfg.nchains, e->bps_diag, s);
+        int rcb = pdmp::launch_bps_run(B, e->cfg.nchains, e->bps_diag, s, bps_moments_params(e));
         if (rcb != 0) return fail(PDMP_ERR_HIP, "bps_run launch failed (%d)", rcb);
         HIP_TRY(hipEventRecord(e->ev1, s));
         e->timed = true;
@@ -2045,6 +2049,7 @@ pdmp_status pdmp_ensemble_final_state(pdmp_ensemble* e, int64_t chain_first, int
 }
 
 static pdmp_status ess_ready(pdmp_ensemble* e);
+static pdmp_status bps_moments_at(pdmp_ensemble* e, double T, int64_t chain_first, int64_t n, bool two);
 
 pdmp_status pdmp_ensemble_batch_means(pdmp_ensemble* e, double T_prev, double T, double* sum_y, double* sum_y2) {
     pdmp_status st0 = ess_ready(e);
@@ -2053,16 +2058,19 @@ pdmp_status pdmp_ensemble_batch_means(pdmp_ensemble* e, double T_prev, double T,
     HIP_TRY(hipSetDevice(e->cfg.device));
     HIP_TRY(device_sync(e));
     const int64_t d = e->cfg.d, n = e->cfg.nchains;
+    const bool bps = e->cfg.sampler == PDMP_SAMPLER_BPS;
     pdmp_status st;
+    if (bps && (st = bps_moments_at(e, T, 0, n, false)) != PDMP_OK) return st;  // J1(T) of every chain into b_jT (the validity rule first)
     if (e->d_jprev.n != (size_t)(n * d)) {
         if ((st = e->d_jprev.alloc((size_t)(n * d))) != PDMP_OK) return st;
         HIP_TRY(hipMemsetAsync(e->d_jprev.p, 0, (size_t)(n * d) * sizeof(double), e->stream));  // (same stream as the kernel: the ensemble's stream is non-blocking, the null stream does not order against it)
     }
     if (e->d_sum.n != (size_t)(2 * d) && (st = e->d_sum.alloc((size_t)(2 * d))) != PDMP_OK) return st;
-    if ((st = ensure_canon(e)) != PDMP_OK) return st;
+    if (!bps && (st = ensure_canon(e)) != PDMP_OK) return st;
     HIP_TRY(hipMemsetAsync(e->d_sum.p, 0, (size_t)(2 * d) * sizeof(double), e->stream));
-    int rc = pdmp::launch_zz_batch_means(e->d_rec.p, e->track ? 128 : 64, e->d_jprev.p, d, n, T_prev, T, e->d_sum.p, e->d_sum.p + d,
-                                         e->stream);
+    int rc = bps ? pdmp::launch_dense_batch_means(e->b_jT.p, e->d_jprev.p, d, n, T_prev, T, e->d_sum.p, e->d_sum.p + d, e->stream)
+                 : pdmp::launch_zz_batch_means(e->d_rec.p, e->track ? 128 : 64, e->d_jprev.p, d, n, T_prev, T, e->d_sum.p, e->d_sum.p + d,
+                                               e->stream);
     if (rc != 0) return fail(PDMP_ERR_HIP, "batch_means launch failed: %s", hipGetErrorString((hipError_t)rc));
     HIP_TRY(hipStreamSynchronize(e->stream));
     if (sum_y) HIP_TRY(hipMemcpy(sum_y, e->d_sum.p, (size_t)d * sizeof(double), hipMemcpyDeviceToHost));
@@ -2072,8 +2080,10 @@ pdmp_status pdmp_ensemble_batch_means(pdmp_ensemble* e, double T_prev, double T,
 
 static pdmp_status ess_ready(pdmp_ensemble* e) {
     if (!e) return fail(PDMP_ERR_INVALID, "null argument");
-    if (e->cfg.sampler == PDMP_SAMPLER_BPS) return fail(PDMP_ERR_INVALID, "path integrals are kept by the factorised samplers only");
+    if (e->cfg.sampler == PDMP_SAMPLER_BPS && e->bps_mom < 1)
+        return fail(PDMP_ERR_INVALID, "path integrals are kept by the factorised samplers only");  // (and by a BPS ensemble with moments on)
     if (!e->has_state) return fail(PDMP_ERR_INVALID, "no state");
+    if (e->cfg.sampler == PDMP_SAMPLER_BPS) return PDMP_OK;
     if (!e->keep_integrals) return fail(PDMP_ERR_INVALID, "the path integrals were switched off (pdmp_ensemble_set_path_integrals)");
     if (e->flow_kind != 0)
         return fail(PDMP_ERR_UNSUPPORTED, "path integrals assume the linear flow of the ZigZag (FactBoomerang rotates between events)");
@@ -2086,12 +2096,15 @@ pdmp_status pdmp_ensemble_ess_begin(pdmp_ensemble* e, double T0) {
     HIP_TRY(hipSetDevice(e->cfg.device));
     HIP_TRY(device_sync(e));
     const int64_t d = e->cfg.d, n = e->cfg.nchains;
+    const bool bps = e->cfg.sampler == PDMP_SAMPLER_BPS;
+    if (bps && (st = bps_moments_at(e, T0, 0, n, false)) != PDMP_OK) return st;
     if (e->d_jprev.n != (size_t)(n * d) && (st = e->d_jprev.alloc((size_t)(n * d))) != PDMP_OK) return st;
     if (e->d_jstart.n != (size_t)(n * d) && (st = e->d_jstart.alloc((size_t)(n * d))) != PDMP_OK) return st;
     if (e->d_essacc.n != (size_t)(4 * d) && (st = e->d_essacc.alloc((size_t)(4 * d))) != PDMP_OK) return st;
-    if ((st = ensure_canon(e)) != PDMP_OK) return st;
+    if (!bps && (st = ensure_canon(e)) != PDMP_OK) return st;
     HIP_TRY(hipMemsetAsync(e->d_essacc.p, 0, (size_t)(4 * d) * sizeof(double), e->stream));
-    int rc = pdmp::launch_zz_ess(e->d_rec.p, e->track ? 128 : 64, e->d_jprev.p, e->d_jstart.p, d, n, 0, T0, T0, e->d_essacc.p, e->stream);
+    int rc = bps ? pdmp::launch_dense_ess(e->b_jT.p, e->d_jprev.p, e->d_jstart.p, d, n, 0, T0, T0, e->d_essacc.p, e->stream)
+                 : pdmp::launch_zz_ess(e->d_rec.p, e->track ? 128 : 64, e->d_jprev.p, e->d_jstart.p, d, n, 0, T0, T0, e->d_essacc.p, e->stream);
     if (rc != 0) return fail(PDMP_ERR_HIP, "ess launch failed: %s", hipGetErrorString((hipError_t)rc));
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->ess_T0 = e->ess_Tlast = T0;
@@ -2106,9 +2119,15 @@ pdmp_status pdmp_ensemble_ess_batch(pdmp_ensemble* e, double T) {
     if (!(T > e->ess_Tlast)) return fail(PDMP_ERR_INVALID, "batch end %g does not exceed the previous one %g", T, e->ess_Tlast);
     HIP_TRY(hipSetDevice(e->cfg.device));
     HIP_TRY(device_sync(e));
-    if ((st = ensure_canon(e)) != PDMP_OK) return st;
-    int rc = pdmp::launch_zz_ess(e->d_rec.p, e->track ? 128 : 64, e->d_jprev.p, e->d_jstart.p, e->cfg.d, e->cfg.nchains, 1, e->ess_Tlast, T,
+    int rc;
+    if (e->cfg.sampler == PDMP_SAMPLER_BPS) {
+        if ((st = bps_moments_at(e, T, 0, e->cfg.nchains, false)) != PDMP_OK) return st;
+        rc = pdmp::launch_dense_ess(e->b_jT.p, e->d_jprev.p, e->d_jstart.p, e->cfg.d, e->cfg.nchains, 1, e->ess_Tlast, T, e->d_essacc.p, e->stream);
+    } else {
+        if ((st = ensure_canon(e)) != PDMP_OK) return st;
+        rc = pdmp::launch_zz_ess(e->d_rec.p, e->track ? 128 : 64, e->d_jprev.p, e->d_jstart.p, e->cfg.d, e->cfg.nchains, 1, e->ess_Tlast, T,
                                  e->d_essacc.p, e->stream);
+    }
     if (rc != 0) return fail(PDMP_ERR_HIP, "ess launch failed: %s", hipGetErrorString((hipError_t)rc));
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->ess_Tlast = T;
@@ -2123,10 +2142,14 @@ pdmp_status pdmp_ensemble_ess_end(pdmp_ensemble* e, double* sum_y, double* sum_y
     if (e->ess_batches < 1) return fail(PDMP_ERR_INVALID, "no batch accumulated (ess_begin, then ess_batch)");
     HIP_TRY(hipSetDevice(e->cfg.device));
     const int64_t d = e->cfg.d;
-    if ((st = ensure_canon(e)) != PDMP_OK) return st;
+    const bool bps = e->cfg.sampler == PDMP_SAMPLER_BPS;
+    if (!bps && (st = ensure_canon(e)) != PDMP_OK) return st;
     HIP_TRY(hipMemsetAsync(e->d_essacc.p + 2 * d, 0, (size_t)(2 * d) * sizeof(double), e->stream));
-    int rc = pdmp::launch_zz_ess(e->d_rec.p, e->track ? 128 : 64, e->d_jprev.p, e->d_jstart.p, d, e->cfg.nchains, 2, e->ess_T0, e->ess_Tlast,
-                                 e->d_essacc.p, e->stream);
+    // (BPS: J at the last batch end is the jprev that batch left -- the state may since have run past it)
+    int rc = bps ? pdmp::launch_dense_ess(e->d_jprev.p, e->d_jprev.p, e->d_jstart.p, d, e->cfg.nchains, 2, e->ess_T0, e->ess_Tlast, e->d_essacc.p,
+                                          e->stream)
+                 : pdmp::launch_zz_ess(e->d_rec.p, e->track ? 128 : 64, e->d_jprev.p, e->d_jstart.p, d, e->cfg.nchains, 2, e->ess_T0, e->ess_Tlast,
+                                       e->d_essacc.p, e->stream);
     if (rc != 0) return fail(PDMP_ERR_HIP, "ess launch failed: %s", hipGetErrorString((hipError_t)rc));
     HIP_TRY(hipStreamSynchronize(e->stream));
     double* outs[4] = {sum_y, sum_y2, sum_m, sum_m2};
@@ -2430,8 +2453,14 @@ pdmp_status pdmp_ensemble_path_integrals(pdmp_ensemble* e, double T, int64_t npr
     DevBuf<double> dout;
     if ((st = dp.upload(std::vector<int64_t>(probes, probes + nprobe))) != PDMP_OK) return st;
     if ((st = dout.alloc((size_t)(n * nprobe))) != PDMP_OK) return st;
-    if ((st = ensure_canon(e)) != PDMP_OK) return st;
-    int rc = pdmp::launch_zz_path_integrals(e->d_rec.p, e->track ? 128 : 64, d, n, dp.p, nprobe, T, dout.p, e->stream);
+    int rc;
+    if (e->cfg.sampler == PDMP_SAMPLER_BPS) {
+        if ((st = bps_moments_at(e, T, 0, n, false)) != PDMP_OK) return st;
+        rc = pdmp::launch_dense_gather(e->b_jT.p, d, n, dp.p, nprobe, dout.p, e->stream);
+    } else {
+        if ((st = ensure_canon(e)) != PDMP_OK) return st;
+        rc = pdmp::launch_zz_path_integrals(e->d_rec.p, e->track ? 128 : 64, d, n, dp.p, nprobe, T, dout.p, e->stream);
+    }
     if (rc != 0) return fail(PDMP_ERR_HIP, "path_integrals launch failed: %s", hipGetErrorString((hipError_t)rc));
     HIP_TRY(hipStreamSynchronize(e->stream));
     HIP_TRY(hipMemcpy(out, dout.p, (size_t)(n * nprobe) * sizeof(double), hipMemcpyDeviceToHost));
@@ -2633,6 +2662,7 @@ static pdmp_status set_flow_nf(pdmp_ensemble* e, const int64_t* colptr, const in
     e->bps_has_mass = e->bps_mass_tables = false;
     e->bps_own_target = false;
     e->bps_local_bound = e->bps_subsample = 0;
+    e->bps_mom = 0;
     e->bps_lambda = lambda_ref;
     e->bps_rho = rho;
     pdmp_status st;
@@ -2742,6 +2772,93 @@ pdmp_status pdmp_ensemble_set_bps_options(pdmp_ensemble* e, int local_bound, int
     return PDMP_OK;
 }
 
+pdmp_status pdmp_ensemble_set_bps_moments(pdmp_ensemble* e, int order) {
+    if (!e) return fail(PDMP_ERR_INVALID, "null argument");
+    if (e->cfg.sampler != PDMP_SAMPLER_BPS || !e->has_flow)
+        return fail(PDMP_ERR_INVALID, "set_flow_bps / set_flow_boomerang first (PDMP_SAMPLER_BPS)");
+    if (order < 0 || order > 2) return fail(PDMP_ERR_INVALID, "moments order %d: 0 (off), 1 (∫x dt) or 2 (∫x dt and ∫x² dt)", order);
+    if (e->has_state) return fail(PDMP_ERR_INVALID, "set_bps_moments goes before set_state_bps");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    const size_t nd = (size_t)(e->cfg.nchains * e->cfg.d);
+    pdmp_status st;
+    if (order >= 1) {
+        if (e->b_j1.n != nd && (st = e->b_j1.alloc(nd)) != PDMP_OK) return st;
+    } else {
+        e->b_j1.release();
+    }
+    if (order >= 2) {
+        if (e->b_j2.n != nd && (st = e->b_j2.alloc(nd)) != PDMP_OK) return st;
+    } else {
+        e->b_j2.release();
+    }
+    e->bps_mom = order;
+    return PDMP_OK;
+}
+
+static pdmp::BpsMomParams bps_moments_params(const pdmp_ensemble* e) {
+    pdmp::BpsMomParams m{};
+    m.mom = e->bps_mom;
+    m.J1 = e->bps_mom >= 1 ? e->b_j1.p : nullptr;
+    m.J2 = e->bps_mom >= 2 ? e->b_j2.p : nullptr;
+    return m;
+}
+
+// The moments of chains [chain_first, chain_first + n) at T into b_jT (and b_jT2 with `two`), rows 0..n-1 -- after checking that T lies
+// on the stretch of every chain's path its state describes: t <= T <= min(tp, tau_ref) (no event between the chain's clock and T), the
+// chain neither BOUND_VIOLATED nor STALLED.
+static pdmp_status bps_moments_at(pdmp_ensemble* e, double T, int64_t chain_first, int64_t n, bool two) {
+    const int64_t d = e->cfg.d, nch = e->cfg.nchains;
+    std::vector<double> sc((size_t)(n * 8));
+    std::vector<pdmp::DevChain> h((size_t)n);
+    if (n > 0) {
+        HIP_TRY(hipMemcpy(sc.data(), e->b_scal.p + chain_first * 8, sc.size() * sizeof(double), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(h.data(), e->d_hdr.p + chain_first, h.size() * sizeof(pdmp::DevChain), hipMemcpyDeviceToHost));
+    }
+    for (int64_t k = 0; k < n; ++k) {
+        const long long ch = (long long)(chain_first + k);
+        const uint32_t cs = h[(size_t)k].c.status;
+        if (cs != PDMP_CHAIN_OK && cs != PDMP_CHAIN_TRACE_FULL)
+            return fail(PDMP_ERR_INVALID, "chain %lld: status %u (bound violated / stalled): its path moments are not defined", ch, cs);
+        const double t = sc[(size_t)(k * 8)], next = std::min(sc[(size_t)(k * 8 + 3)], sc[(size_t)(k * 8 + 4)]);
+        if (!(t <= T))
+            return fail(PDMP_ERR_INVALID, "chain %lld: T = %.17g lies before the chain's clock %.17g (a reference-tail run passes T)", ch, T, t);
+        if (!(T <= next))
+            return fail(PDMP_ERR_INVALID, "chain %lld: T = %.17g lies past the chain's next event at %.17g (run to T with PDMP_RUN_STOP_BEFORE)",
+                        ch, T, next);
+    }
+    pdmp_status st;
+    if (e->b_jT.n != (size_t)(nch * d) && (st = e->b_jT.alloc((size_t)(nch * d))) != PDMP_OK) return st;
+    if (two && e->b_jT2.n != (size_t)(nch * d) && (st = e->b_jT2.alloc((size_t)(nch * d))) != PDMP_OK) return st;
+    pdmp::BpsRunParams B{};
+    B.x = e->b_x.p;
+    B.th = e->b_th.p;
+    B.scal = e->b_scal.p;
+    B.mu_flow = e->b_mu_flow.p;
+    B.flow_kind = e->bps_flow_kind;
+    B.d = d;
+    int rc = pdmp::launch_bps_moments_tail(B, bps_moments_params(e), chain_first, n, T, e->b_jT.p, two ? e->b_jT2.p : nullptr, e->stream);
+    if (rc != 0) return fail(PDMP_ERR_HIP, "bps_moments_tail launch failed: %s", hipGetErrorString((hipError_t)rc));
+    return PDMP_OK;
+}
+
+pdmp_status pdmp_ensemble_bps_moments(pdmp_ensemble* e, double T, int64_t chain_first, int64_t n, double* j1, double* j2) {
+    if (!e || !j1) return fail(PDMP_ERR_INVALID, "null argument");
+    if (e->cfg.sampler != PDMP_SAMPLER_BPS || e->bps_mom < 1)
+        return fail(PDMP_ERR_INVALID, "no path moments: a BPS ensemble with pdmp_ensemble_set_bps_moments(order >= 1)");
+    if (j2 && e->bps_mom < 2) return fail(PDMP_ERR_INVALID, "∫x² dt needs moments of order 2 (this ensemble keeps order %d)", e->bps_mom);
+    if (!e->has_state) return fail(PDMP_ERR_INVALID, "no state");
+    if (chain_first < 0 || n < 0 || chain_first + n > e->cfg.nchains) return fail(PDMP_ERR_INVALID, "chain range");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(device_sync(e));
+    pdmp_status st = bps_moments_at(e, T, chain_first, n, j2 != nullptr);
+    if (st != PDMP_OK || n == 0) return st;
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    const size_t cnt = (size_t)(n * e->cfg.d);
+    HIP_TRY(hipMemcpy(j1, e->b_jT.p, cnt * sizeof(double), hipMemcpyDeviceToHost));
+    if (j2) HIP_TRY(hipMemcpy(j2, e->b_jT2.p, cnt * sizeof(double), hipMemcpyDeviceToHost));
+    return PDMP_OK;
+}
+
 static pdmp_status init_state_bps(pdmp_ensemble* e, double t0, const double* x0, const double* theta0, double c, const uint64_t* seeds) {
     if (!e || !x0 || !theta0 || !seeds) return fail(PDMP_ERR_INVALID, "null argument");
     if (e->cfg.sampler != PDMP_SAMPLER_BPS || !e->has_flow) return fail(PDMP_ERR_INVALID, "set_flow_bps first");
@@ -2787,6 +2904,9 @@ static pdmp_status init_state_bps(pdmp_ensemble* e, double t0, const double* x0,
     B.lambda_ref = e->bps_lambda;
     B.rho = e->bps_rho;
     fill_bps_ext(e, B);
+    // the moments start at t0 (also after set_state_bps's placement probes, which run launches in between)
+    if (e->bps_mom >= 1) HIP_TRY(hipMemsetAsync(e->b_j1.p, 0, (size_t)(n * d) * sizeof(double), e->stream));
+    if (e->bps_mom >= 2) HIP_TRY(hipMemsetAsync(e->b_j2.p, 0, (size_t)(n * d) * sizeof(double), e->stream));
     int rc = pdmp::launch_bps_init(B, n, sseed.p, t0, c, e->stream);
     if (rc != 0) return fail(PDMP_ERR_HIP, "bps_init launch failed (%d)", rc);
     HIP_TRY(hipStreamSynchronize(e->stream));

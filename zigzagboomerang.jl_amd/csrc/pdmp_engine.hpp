@@ -357,10 +357,25 @@ struct BpsRunParams {
     const int32_t* __restrict__ Urv;
     const double* __restrict__ Unz;
 };
+// path moments (pdmp_ensemble_set_bps_moments): mom = 0 off, 1 J1 = ∫x dt, 2 J1 and J2 = ∫x² dt, each [nchains x d] from the chain's t0.
+// A second kernel argument of the event loop where mom > 0 only: the kernels of mom = 0 keep their argument block, and their code, as is.
+struct BpsMomParams {
+    double* J1;
+    double* J2;
+    int32_t mom, pad_;
+};
 int launch_bps_write_probe(double* ev_x, double* ev_th, int64_t d, int64_t cap, int64_t nrec, int64_t nchains, void* stream);
 int launch_sector_probe(double* rec, int64_t d, int64_t nchains, int rounds, int write, double* sink, void* stream);
 int launch_bps_init(const BpsRunParams& p, int64_t nchains, const uint64_t* seeds, double t0, double c0, void* stream);
-int launch_bps_run(const BpsRunParams& p, int64_t nchains, bool diag, void* stream);
+int launch_bps_run(const BpsRunParams& p, int64_t nchains, bool diag, void* stream, const BpsMomParams& m = BpsMomParams{});
+// path moments of a BPS ensemble (pdmp_bps.hip): J(T) = J + ∫_t^T of chains [chain_first, chain_first + n) into o1 / o2 (o2 may be nullptr);
+// dense batch means / ESS sums (the arithmetic of zz_batch_means_kernel / zz_ess_kernel on an [nchains x d] array J(T)); probe gather
+int launch_bps_moments_tail(const BpsRunParams& p, const BpsMomParams& m, int64_t chain_first, int64_t n, double T, double* o1, double* o2, void* stream);
+int launch_dense_batch_means(const double* J, double* jprev, int64_t d, int64_t nchains, double T_prev, double T, double* sum_y,
+                             double* sum_y2, void* stream);
+int launch_dense_ess(const double* J, double* jprev, double* jstart, int64_t d, int64_t nchains, int mode, double T_prev, double T,
+                     double* acc, void* stream);
+int launch_dense_gather(const double* J, int64_t d, int64_t nchains, const int64_t* probes, int64_t nprobe, double* out, void* stream);
 
 // launch wrappers implemented in pdmp_kernels.hip (hipStream_t passed as void*)
 int launch_zz_init(const ZzInitParams& p, void* stream);

@@ -33,6 +33,7 @@ class Ensemble:
         self.trace_capacity = int(trace_capacity)
         self.adapt = bool(adapt)
         self.device = int(device)
+        self._bps_mom = 0  # set_bps_moments
         cfg = _lib.PdmpConfig(C.sizeof(_lib.PdmpConfig), int(device), int(sampler), int(bool(adapt)), float(factor),
                               self.nchains, self.d, self.trace_capacity)
         h = C.c_void_p()
@@ -187,6 +188,7 @@ class Ensemble:
         cp, rv, nz, mu = _i64(G.indptr), _i64(G.indices), _f64(G.data), _f64(B.μ)
         _lib.check(self._L.pdmp_ensemble_set_flow_bps(self._h, _ptr(cp), _ptr(rv), _ptr(nz), _ptr(mu), float(B.λref),
                                                      float(B.ρ)))
+        self._bps_mom = 0
         self._set_mass(B)
 
     def _set_mass(self, B, explicit_identity=False):
@@ -207,6 +209,22 @@ class Ensemble:
         """c::LocalBound (src/not_fact_samplers.jl:29-31,65-71) and the `subsample` keyword (:53,90) of the non-factorised sampler."""
         _lib.check(self._L.pdmp_ensemble_set_bps_options(self._h, int(bool(local_bound)), int(bool(subsample))))
 
+    def set_bps_moments(self, order):
+        """Keep the path moments ∫x dt (order 1) and ∫x² dt (order 2) beside the state (pdmp_ensemble_set_bps_moments); 0 = off.
+        After set_flow_bps / set_flow_boomerang, before set_state_bps."""
+        _lib.check(self._L.pdmp_ensemble_set_bps_moments(self._h, int(order)))
+        self._bps_mom = int(order)
+
+    def bps_moments(self, T, chain_first=0, n=None):
+        """(J1, J2) = (∫_{t0}^{T} x dt, ∫_{t0}^{T} x² dt) of chains [chain_first, chain_first + n), each [n x d]; J2 is None when the
+        ensemble keeps order 1.  Every chain must have t <= T <= its next event (pdmp_ensemble_bps_moments)."""
+        if n is None:
+            n = self.nchains - chain_first
+        J1 = np.empty((n, self.d))
+        J2 = np.empty((n, self.d)) if self._bps_mom >= 2 else None
+        _lib.check(self._L.pdmp_ensemble_bps_moments(self._h, float(T), int(chain_first), int(n), _ptr(J1), _ptr(J2)))
+        return J1, J2
+
     def set_flow_boomerang(self, target, B):
         """Flow = Boomerang(Γ, μ, λ; ρ) on the Gaussian target ∇ϕ!(y, x) = Γt(x − μt)."""
         G = B.Γ
@@ -218,6 +236,7 @@ class Ensemble:
         mf = _f64(B.μ)
         _lib.check(self._L.pdmp_ensemble_set_flow_boomerang(self._h, _ptr(cp), _ptr(rv), _ptr(nz), _ptr(mt), _ptr(mf),
                                                            float(B.λref), float(B.ρ)))
+        self._bps_mom = 0
         self._set_mass(B, explicit_identity=True)
 
     def set_state_bps(self, t0, x0, theta0, c, seeds):

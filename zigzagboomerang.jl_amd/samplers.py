@@ -64,18 +64,19 @@ def spdmp(target, t0, x0, θ0, T, c, *GF, factor=1.8, adapt=False, adaptscale=Fa
                    adaptscale=adaptscale, tracked=tracked, G=G)
 
 
-def pdmp(target, *args, factor=1.8, adapt=False, subsample=False, seed=DEFAULT_SEED, device=0, trace_capacity=None, trace=True):
+def pdmp(target, *args, factor=1.8, adapt=False, subsample=False, seed=DEFAULT_SEED, device=0, trace_capacity=None, trace=True,
+         moments=False):
     """pdmp(∇ϕ, t0, x0, θ0, T, c, F, ...) -- the d-dimensional drivers, see _pdmp_nd -- or, with a 1-d flow as the sixth argument,
     pdmp(∇ϕ, x, θ, T, c, Flow::Union{ZigZag1d, Boomerang1d}; adapt=false, factor=2.0) -> Ξ, acc/num  (src/zigzagboom1d.jl:34-67)."""
     if len(args) == 5 and isinstance(args[4], (ZigZag1d, Boomerang1d)):
-        if subsample:
-            raise TypeError("subsample is a keyword of the non-factorised pdmp (BouncyParticle / Boomerang)")
+        if subsample or moments:
+            raise TypeError("subsample and moments are keywords of the non-factorised pdmp (BouncyParticle / Boomerang)")
         x0, θ0, T, c, Flow = args
         return _pdmp_1d(target, x0, θ0, T, c, Flow, 2.0 if factor == 1.8 else factor, adapt, seed, device, trace_capacity)
     if len(args) != 6:
         raise TypeError("expected pdmp(target, t0, x0, θ0, T, c, F, ...) or pdmp(target, x, θ, T, c, Flow1d, ...)")
     return _pdmp_nd(target, *args, factor=factor, adapt=adapt, subsample=subsample, seed=seed, device=device, trace_capacity=trace_capacity,
-                    trace=trace)
+                    trace=trace, moments=moments)
 
 
 def _pdmp_1d(target, x0, θ0, T, c, Flow, factor, adapt, seed, device, trace_capacity):
@@ -116,7 +117,7 @@ def _pdmp_1d(target, x0, θ0, T, c, Flow, factor, adapt, seed, device, trace_cap
 
 
 def _pdmp_nd(target, t0, x0, θ0, T, c, F, *, factor=1.8, adapt=False, subsample=False, seed=DEFAULT_SEED, device=0,
-             trace_capacity=None, trace=True):
+             trace_capacity=None, trace=True, moments=False):
     """pdmp(∇ϕ, t0, x0, θ0, T, c, F::ZigZag, args...) = spdmp(..., All(), ...) (src/sfact.jl:236): every proposal moves
     ALL coordinates (no sparsity assumption on ∇ϕ); same return value as spdmp.
 
@@ -124,19 +125,23 @@ def _pdmp_nd(target, t0, x0, θ0, T, c, F, *, factor=1.8, adapt=False, subsample
     BouncyParticle: the target is ∇ϕ!(y, x) = B.Γ(x − B.μ) (pass target=None) or a GaussianTarget of its own -- ab(…GlobalBound…) then
     keeps the flow's B.Γ, B.μ while gradient, rate and reflection use the target's (src/not_fact_samplers.jl:26-28,122) --, c is the scalar of GlobalBound(c) or a
     LocalBound(c) (src/not_fact_samplers.jl:29-31; the second derivative v = θ'Γθ is the Gaussian target's own);
-    `subsample` as in the reference (:53,90); returns Ξ::PDMPTrace, (t, x, θ), (acc, num), c."""
+    `subsample` as in the reference (:53,90); returns Ξ::PDMPTrace, (t, x, θ), (acc, num), c.
+
+    moments=True (BouncyParticle / Boomerang, engine-only keyword): a fifth element dict(mean, var, T) -- the exact time averages
+    ∫x dt/(T − t0) and ∫x² dt/(T − t0) − mean² over [t0, T] kept by the event loop (pdmp_ensemble_set_bps_moments), [n x d] or [d]; the
+    first four elements are bit for bit those of moments=False.  With trace=False no event is written at all."""
     if isinstance(F, BouncyParticle):
         if target is not None and not isinstance(target, GaussianTarget):
             raise TypeError("BouncyParticle: target is None (∇ϕ!(y, x) = B.Γ(x − B.μ)) or a GaussianTarget of its own")
         return _bps(t0, x0, θ0, T, c, F, 2.0 if factor == 1.8 else factor, adapt, seed, device, trace_capacity, trace,
-                    target=target, subsample=subsample)
+                    target=target, subsample=subsample, moments=moments)
     if isinstance(F, Boomerang):  # pdmp(∇ϕ!, t0, x0, θ0, T, c, B::Boomerang) (test/maintest.jl:139-154); target = GaussianTarget
         if not isinstance(target, GaussianTarget):
             raise TypeError("Boomerang: target must be a GaussianTarget (∇ϕ!(y, x) = Γ(x − μ))")
         return _bps(t0, x0, θ0, T, c, F, 2.0 if factor == 1.8 else factor, adapt, seed, device, trace_capacity, trace,
-                    target=target, subsample=subsample)
-    if subsample:
-        raise TypeError("subsample is a keyword of the non-factorised pdmp (BouncyParticle / Boomerang)")
+                    target=target, subsample=subsample, moments=moments)
+    if subsample or moments:
+        raise TypeError("subsample and moments are keywords of the non-factorised pdmp (BouncyParticle / Boomerang)")
     return _zigzag(_lib.SAMPLER_ZIGZAG_ALL, target, t0, x0, θ0, T, c, F, factor, adapt, seed, device, trace_capacity, trace)
 
 
@@ -332,7 +337,7 @@ def _zigzag(sampler, target, t0, x0, θ0, T, c, F, factor, adapt, seed, device, 
     return traces, (fs["t"], fs["x"], fs["theta"]), (acc, num), c_out
 
 
-def _bps(t0, x0, θ0, T, c, B, factor, adapt, seed, device, trace_capacity, trace, target=None, subsample=False):
+def _bps(t0, x0, θ0, T, c, B, factor, adapt, seed, device, trace_capacity, trace, target=None, subsample=False, moments=False):
     local_bound = isinstance(c, LocalBound)
     if local_bound:
         c = float(np.asarray(c.c, dtype=np.float64).reshape(-1)[0])
@@ -355,25 +360,33 @@ def _bps(t0, x0, θ0, T, c, B, factor, adapt, seed, device, trace_capacity, trac
                 ens.set_target(target)
         if local_bound or subsample:
             ens.set_bps_options(local_bound, subsample)
+        if moments:
+            ens.set_bps_moments(2)
         ens.set_state_bps(t0, X0, TH0, float(c), seeds)
         ts = [[] for _ in range(nch)]
         xs = [[] for _ in range(nch)]
         ths = [[] for _ in range(nch)]
-        while True:
-            ens.run(T, _lib.RUN_REFERENCE_TAIL)
-            cnt = ens.counters()
-            if np.any(cnt["status"] == _lib.CHAIN_BOUND_VIOLATED):
-                raise RuntimeError("Tuning parameter `c` too small.")  # src/not_fact_samplers.jl:82
-            if trace:
-                for k in range(nch):
-                    if cnt["ntrace"][k]:
-                        a, b_, c_ = ens.bps_trace(k, counters=cnt)
-                        ts[k].append(a)
-                        xs[k].append(b_)
-                        ths[k].append(c_)
-                ens.trace_reset()
-            if not _lib.needs_rerun(cnt["status"]):  # (both resume with the next run)
-                break
+        J = None
+        # moments: every chain paused before its first event at or past T (the moments are read there), then the reference's tail --
+        # the same events in the same order as one reference-tail run
+        for flags in ((_lib.RUN_STOP_BEFORE, _lib.RUN_REFERENCE_TAIL) if moments else (_lib.RUN_REFERENCE_TAIL,)):
+            while True:
+                ens.run(T, flags)
+                cnt = ens.counters()
+                if np.any(cnt["status"] == _lib.CHAIN_BOUND_VIOLATED):
+                    raise RuntimeError("Tuning parameter `c` too small.")  # src/not_fact_samplers.jl:82
+                if trace:
+                    for k in range(nch):
+                        if cnt["ntrace"][k]:
+                            a, b_, c_ = ens.bps_trace(k, counters=cnt)
+                            ts[k].append(a)
+                            xs[k].append(b_)
+                            ths[k].append(c_)
+                    ens.trace_reset()
+                if not _lib.needs_rerun(cnt["status"]):  # (both resume with the next run)
+                    break
+            if flags == _lib.RUN_STOP_BEFORE:
+                J = ens.bps_moments(T)
         fs = ens.bps_final_state()
         cnt = ens.counters()
     finally:
@@ -387,5 +400,13 @@ def _bps(t0, x0, θ0, T, c, B, factor, adapt, seed, device, trace_capacity, trac
             traces.append(PDMPTrace(B, t0, X0[k].copy(), TH0[k].copy(), np.empty(0), np.empty((0, d)), np.empty((0, d))))
     acc, num = cnt["nacc"].astype(np.int64), cnt["num"].astype(np.int64)
     if single:
-        return traces[0], (fs["t"][0], fs["x"][0], fs["theta"][0]), (int(acc[0]), int(num[0])), fs["c"][0]
-    return traces, (fs["t"], fs["x"], fs["theta"]), (acc, num), fs["c"]
+        out = traces[0], (fs["t"][0], fs["x"][0], fs["theta"][0]), (int(acc[0]), int(num[0])), fs["c"][0]
+    else:
+        out = traces, (fs["t"], fs["x"], fs["theta"]), (acc, num), fs["c"]
+    if not moments:
+        return out
+    mean = J[0] / (T - t0)
+    var = J[1] / (T - t0) - mean * mean
+    if single:
+        mean, var = mean[0], var[0]
+    return out + (dict(mean=mean, var=var, T=T),)

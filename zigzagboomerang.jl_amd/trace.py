@@ -263,6 +263,30 @@ def moments(tr: FactTrace, T_end=None):
     return m, s2 / L - m * m
 
 
+def path_moments(tr: PDMPTrace, T):
+    """(∫_{t0}^{T} x dt, ∫_{t0}^{T} x² dt) of the path a PDMPTrace describes, [d] each, in closed form per segment: between two events
+    the state flows freely from the earlier one's (x, θ) -- linearly for a BouncyParticle (src/dynamics.jl:11-15), by the rotation about
+    F.μ for a Boomerang (:29-36).  Past the last event the path goes on from that event's (x, θ) (the caller guarantees that T lies
+    before the next one); events after T are cut off.  The host statement of pdmp_ensemble_bps_moments (mean = ∫x/(T − t0))."""
+    d = len(tr.x0)
+    X = np.vstack([np.asarray(tr.x0, dtype=np.float64)[None], np.asarray(tr.x, dtype=np.float64).reshape(-1, d)])
+    TH = np.vstack([np.asarray(tr.θ0, dtype=np.float64)[None], np.asarray(tr.θ, dtype=np.float64).reshape(-1, d)])
+    te = np.concatenate([[tr.t0], np.asarray(tr.t, dtype=np.float64)])
+    end = np.minimum(np.append(te[1:], np.inf), T)
+    tau = np.maximum(end - te, 0.0)[:, None]
+    if isinstance(tr.F, Boomerang):
+        m = np.asarray(tr.F.μ, dtype=np.float64)[None]
+        A = X - m
+        s, c = np.sin(tau), np.cos(tau)
+        rot = A * s + TH * (1.0 - c)
+        j1 = m * tau + rot
+        j2 = m * m * tau + 2.0 * m * rot + A * A * (tau / 2 + s * c / 2) + TH * TH * (tau / 2 - s * c / 2) + A * TH * s * s
+    else:
+        j1 = tau * (X + TH * tau / 2)
+        j2 = tau * (X * X + X * TH * tau + TH * TH * tau * tau / 3)
+    return j1.sum(0), j2.sum(0)
+
+
 def subtrace(tr: FactTrace, J):
     """subtrace(Ξ, J): trace of the subvector x[J] -- src/trace.jl:275-290."""
     J = np.asarray(J)
