@@ -11,6 +11,7 @@
  *   pdmp_u01             draw #n of a chain's stream as a double in the OPEN interval (0,1)
  *   pdmp_log             natural log for positive normal doubles, < 1 ulp, only + - * / on doubles
  *   pdmp_exp             exp, < 1 ulp, only + - * / on doubles (logistic targets)
+ *   pdmp_sincos          sin and cos for |x| <= 2^30 (Boomerang rotations); pdmp_sincos2pi: of 2*pi*v for v in [0,1)
  *   pdmp_randexp         -log(u)                       (replaces Random.randexp, src/poissontime.jl:77)
  *   pdmp_randn           Box-Muller normal             (replaces Random.randn,   src/dynamics.jl:115)
  *   pdmp_randn2          both Box-Muller branches of one block (the d-vector refresh of the non-factorised samplers)
@@ -243,20 +244,36 @@ PDMP_HD void pdmp_sincos2pi(double v, double* s_out, double* c_out) {
     }
 }
 
-/* sin and cos of an arbitrary angle |x| < 2^20: three-term Cody-Waite reduction by pi/2 (every product n*pio2_k is exact),
- * then the kernels above.  Replaces Base.sincos in the Boomerang rotation (src/sfact.jl:29-36, src/dynamics.jl:29-36). */
+/* sin and cos of an angle |x| <= 2^30 (PDMP_SINCOS_MAX): Cody-Waite reduction r = x - n pi/2 by pi/2 in three 33-bit pieces and a
+ * tail, then the kernels above.  Replaces Base.sincos in the Boomerang rotation (src/sfact.jl:29-36, src/dynamics.jl:29-36).
+ * n = nh + nl with |nl| < 2^20 and nh a multiple of 2^20 (10 significant bits), so every product nh*pio2_k and nl*pio2_k is exact; for
+ * |n| < 2^20 the nh terms are +0 and the operations are those of the plain three-term reduction, bit for bit.  Absolute error <= 2.5e-16
+ * in both outputs over the whole domain (tests/test_detmath_accuracy.py).  Beyond it, and for NaN and +-Inf, both outputs are NaN:
+ * that is decided before any conversion to an integer, so host and device agree there too. */
+#define PDMP_SINCOS_MAX 0x1.0p+30
 PDMP_HD void pdmp_sincos(double x, double* s_out, double* c_out) {
     const double invpio2 = 0x1.45f306dc9c883p-1; /* 2/pi */
     const double pio2_1 = 0x1.921fb54400000p+0;  /* first 33 bits of pi/2 */
     const double pio2_2 = 0x1.0b4611a600000p-34; /* next 33 bits */
     const double pio2_3 = 0x1.3198a2e000000p-69; /* next 33 bits */
     const double pio2_3t = 0x1.b839a252049c1p-104;
+    if (!(__builtin_fabs(x) <= PDMP_SINCOS_MAX)) {
+        *s_out = __builtin_nan("");
+        *c_out = __builtin_nan("");
+        return;
+    }
     const double fnr = x * invpio2 + ((x < 0) ? -0.5 : 0.5);
     const int32_t n = (int32_t)fnr;
+    const int32_t nl = n % 0x100000; /* (C's % takes the sign of n) */
     const double fn = (double)n;
-    double r = x - fn * pio2_1;
-    r = r - fn * pio2_2;
-    r = r - fn * pio2_3;
+    const double fnh = (double)(n - nl);
+    const double fnl = (double)nl;
+    double r = x - fnh * pio2_1;
+    r = r - fnl * pio2_1;
+    r = r - fnh * pio2_2;
+    r = r - fnl * pio2_2;
+    r = r - fnh * pio2_3;
+    r = r - fnl * pio2_3;
     r = r - fn * pio2_3t;
     const double sr = pdmp_sin_poly(r);
     const double cr = pdmp_cos_poly(r);
@@ -292,17 +309,22 @@ PDMP_HD double pdmp_randn(uint64_t seed, uint32_t stream, uint64_t n) {
     return pdmp_randn_from_u(u1, u2);
 }
 
-/* Both Box-Muller branches of block #n: z0 = r cos 2πu2, z1 = r sin 2πu2 (two independent standard normals per Philox block). */
-PDMP_HD void pdmp_randn2(uint64_t seed, uint32_t stream, uint64_t n, double* z0, double* z1) {
-    pdmp_u32x4 r = pdmp_philox4x32_10((uint32_t)n, (uint32_t)(n >> 32), stream, 0u, (uint32_t)seed,
-                                      (uint32_t)(seed >> 32));
-    double u1 = pdmp_bits_to_u01(((uint64_t)r.v[0] << 32) | (uint64_t)r.v[1]);
-    double u2 = pdmp_bits_to_u01(((uint64_t)r.v[2] << 32) | (uint64_t)r.v[3]);
+/* Both Box-Muller branches of one pair of uniforms: z0 = r cos 2πu2, z1 = r sin 2πu2. */
+PDMP_HD void pdmp_randn2_from_u(double u1, double u2, double* z0, double* z1) {
     double rad = PDMP_SQRT(-2.0 * pdmp_log(u1));
     double s, c;
     pdmp_sincos2pi(u2, &s, &c);
     *z0 = rad * c;
     *z1 = rad * s;
+}
+
+/* Both Box-Muller branches of block #n (two independent standard normals per Philox block). */
+PDMP_HD void pdmp_randn2(uint64_t seed, uint32_t stream, uint64_t n, double* z0, double* z1) {
+    pdmp_u32x4 r = pdmp_philox4x32_10((uint32_t)n, (uint32_t)(n >> 32), stream, 0u, (uint32_t)seed,
+                                      (uint32_t)(seed >> 32));
+    double u1 = pdmp_bits_to_u01(((uint64_t)r.v[0] << 32) | (uint64_t)r.v[1]);
+    double u2 = pdmp_bits_to_u01(((uint64_t)r.v[2] << 32) | (uint64_t)r.v[3]);
+    pdmp_randn2_from_u(u1, u2, z0, z1);
 }
 
 #endif /* PDMP_DETMATH_H */

@@ -2147,6 +2147,16 @@ void orc_math_probe(uint64_t seed, int64_t n, double* out) {
     }
 }
 double orc_log(double x) { return pdmp_log(x); }
+double orc_exp(double x) { return pdmp_exp(x); }
+void orc_sincos(double x, double* s, double* c) { pdmp_sincos(x, s, c); }
+void orc_sincos2pi(double v, double* s, double* c) { pdmp_sincos2pi(v, s, c); }
+double orc_bits_to_u01(uint64_t bits) { return pdmp_bits_to_u01(bits); }
+double orc_randn_from_u(double u1, double u2) { return pdmp_randn_from_u(u1, u2); }
+void orc_randn2_from_u(double u1, double u2, double* z0, double* z1) { pdmp_randn2_from_u(u1, u2, z0, z1); }
+void orc_randn2(uint64_t seed, uint32_t stream, uint64_t n, double* z0, double* z1) { pdmp_randn2(seed, stream, n, z0, z1); }
+uint32_t orc_randint(uint64_t seed, uint32_t stream, uint64_t n_draw, uint32_t n) { return pdmp_randint(seed, stream, n_draw, n); }
+double orc_sigmoid(double x) { return lg_sigmoid(x); }
+double orc_pos(double x) { return pos(x); }
 double orc_u01(uint64_t seed, uint32_t stream, uint64_t n) { return pdmp_u01(seed, stream, n); }
 double orc_randn(uint64_t seed, uint32_t stream, uint64_t n) { return pdmp_randn(seed, stream, n); }
 void orc_philox(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {

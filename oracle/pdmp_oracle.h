@@ -262,6 +262,17 @@ int orc_parallel_spdmp(int64_t d, const orc_zz_params* p, int K, double delta, d
 /* helpers for the tests: the shared numerical contract evaluated on the host */
 void orc_math_probe(uint64_t seed, int64_t n, double* out);
 double orc_log(double x);
+/* the rest of the shared contract and the oracle's own scalar helpers, one value at a time (tests/test_detmath*.py) */
+double orc_exp(double x);
+void orc_sincos(double x, double* s, double* c);
+void orc_sincos2pi(double v, double* s, double* c);
+double orc_bits_to_u01(uint64_t bits);
+double orc_randn_from_u(double u1, double u2);
+void orc_randn2_from_u(double u1, double u2, double* z0, double* z1);
+void orc_randn2(uint64_t seed, uint32_t stream, uint64_t n, double* z0, double* z1);
+uint32_t orc_randint(uint64_t seed, uint32_t stream, uint64_t n_draw, uint32_t n);
+double orc_sigmoid(double x); /* lg_sigmoid: sigmoid of the logistic targets */
+double orc_pos(double x);     /* pos(x) = max(0, x), NaN kept */
 double orc_u01(uint64_t seed, uint32_t stream, uint64_t n);
 double orc_randn(uint64_t seed, uint32_t stream, uint64_t n);
 void orc_philox(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);

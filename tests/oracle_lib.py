@@ -129,6 +129,19 @@ def lib():
         L.orc_math_probe.argtypes = [C.c_uint64, C.c_int64, C.c_void_p]
         L.orc_log.restype = C.c_double
         L.orc_log.argtypes = [C.c_double]
+        for name in ("orc_exp", "orc_sigmoid", "orc_pos"):
+            getattr(L, name).restype = C.c_double
+            getattr(L, name).argtypes = [C.c_double]
+        L.orc_sincos.argtypes = [C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.orc_sincos2pi.argtypes = [C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.orc_bits_to_u01.restype = C.c_double
+        L.orc_bits_to_u01.argtypes = [C.c_uint64]
+        L.orc_randn_from_u.restype = C.c_double
+        L.orc_randn_from_u.argtypes = [C.c_double, C.c_double]
+        L.orc_randn2_from_u.argtypes = [C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.orc_randn2.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.orc_randint.restype = C.c_uint32
+        L.orc_randint.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32]
         L.orc_u01.restype = C.c_double
         L.orc_u01.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64]
         L.orc_randn.restype = C.c_double
@@ -143,6 +156,37 @@ def math_probe(seed, n):
     out = np.empty((8, n))
     lib().orc_math_probe(int(seed), int(n), out.ctypes.data)
     return out
+
+
+def _pair(fn, *args):
+    s, c = C.c_double(), C.c_double()
+    fn(*args, C.byref(s), C.byref(c))
+    return s.value, c.value
+
+
+def sincos(x):
+    """(sin x, cos x) of pdmp_sincos"""
+    return _pair(lib().orc_sincos, float(x))
+
+
+def sincos2pi(v):
+    """(sin 2 pi v, cos 2 pi v) of pdmp_sincos2pi"""
+    return _pair(lib().orc_sincos2pi, float(v))
+
+
+def randn2_from_u(u1, u2):
+    """(z0, z1) = both Box-Muller branches of pdmp_randn2_from_u"""
+    return _pair(lib().orc_randn2_from_u, float(u1), float(u2))
+
+
+def randn2(seed, stream, n):
+    return _pair(lib().orc_randn2, int(seed), int(stream), int(n))
+
+
+def vec(fn, *cols):
+    """fn applied row by row to equally long columns -> float64 array (a scalar result) or [2 x n] (a pair)"""
+    out = [fn(*row) for row in zip(*[np.asarray(c).tolist() for c in cols])]
+    return np.array(out, dtype=np.float64).T
 
 
 def philox(ctr, key):

@@ -73,3 +73,32 @@ def test_headers_are_plain_c99(tmp_path):
     exe = tmp_path / "t"
     subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-ffp-contract=off", "-I", inc, str(src), "-o", str(exe)])
     assert subprocess.call([str(exe)]) == 0
+
+
+def test_scalar_probe_covers_every_device_copy():
+    """Every __device__ copy of poisson_time, sigmoid and pos in csrc/ has its own pdmp_debug_math_eval id (include/pdmp_debug.h names the
+    file and function of each), and the probe of that id calls it: a new copy without a probe fails here (tests/test_gpu_detmath.py
+    holds every probed copy to the oracle bit for bit)."""
+    csrc = os.path.join(ROOT, "zigzagboomerang.jl_amd", "csrc")
+    found = set()
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith((".hip", ".inc")):
+            for name in re.findall(r"__device__[^;{(]*?\b(\w+)\s*\(\s*double\b", open(os.path.join(csrc, f)).read()):
+                if "poisson_time" in name or "sigmoid" in name or name.endswith("_pos") or name == "pos_part":
+                    found.add((f, name))
+    src = open(os.path.join(ROOT, "include", "pdmp_debug.h")).read()
+    ids = re.findall(r"#define (PDMP_MATH_\w+) \d+\s*/\* (pdmp_\w+\.hip) (\w+) \*/", src)
+    assert found == {(f, name) for _, f, name in ids}
+    assert len(found) == 26  # 13 poisson_time, 3 sigmoid, 10 pos
+    for macro, f, name in ids:  # the probe of the unit that owns the copy calls it under that id
+        text = open(os.path.join(csrc, f)).read()
+        assert re.search(r"(case %s: return %s\(|default: return %s\([^;]*;\s*//\s*%s\b)" % (macro, name, name, macro), text), (macro, f, name)
+
+
+def test_scalar_probe_is_parity_library_only(pkg):
+    """the default library exports pdmp_debug_math_eval (every pdmp_debug.h symbol) but has no probe kernels: it answers UNSUPPORTED"""
+    pkg.build.build()
+    a = (ctypes.c_double * 1)(0.5)
+    out = (ctypes.c_double * 2)()
+    st = pkg._lib.load().pdmp_debug_math_eval(0, 2, 1, a, a, a, out)
+    assert st == pkg._lib.PDMP_ERR_UNSUPPORTED

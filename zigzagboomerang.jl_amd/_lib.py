@@ -53,7 +53,7 @@ EXPORTED_SYMBOLS = [
 ]
 # include/pdmp_debug.h: diagnostics, not part of the drop-in boundary
 DEBUG_SYMBOLS = ["pdmp_debug_set_kernel", "pdmp_debug_set_spec_g2", "pdmp_debug_set_phase_profile", "pdmp_debug_phase_profile",
-                 "pdmp_debug_set_proposal_dump", "pdmp_debug_set_track_groups", "pdmp_debug_set_helper_wave", "pdmp_debug_set_track_lines", "pdmp_debug_buffer_addresses", "pdmp_debug_placement", "pdmp_debug_set_placement", "pdmp_debug_move_buffer", "pdmp_debug_set_helper_steering", "pdmp_debug_set_launch_count_limit", "pdmp_debug_host_drain_probe", "pdmp_debug_set_consumer_overlap", "pdmp_debug_last_kernel", "pdmp_debug_set_logistic_rows", "pdmp_debug_math_probe", "pdmp_debug_write_probe", "pdmp_debug_sector_probe"]
+                 "pdmp_debug_set_proposal_dump", "pdmp_debug_set_track_groups", "pdmp_debug_set_helper_wave", "pdmp_debug_set_track_lines", "pdmp_debug_buffer_addresses", "pdmp_debug_placement", "pdmp_debug_set_placement", "pdmp_debug_move_buffer", "pdmp_debug_set_helper_steering", "pdmp_debug_set_launch_count_limit", "pdmp_debug_host_drain_probe", "pdmp_debug_set_consumer_overlap", "pdmp_debug_last_kernel", "pdmp_debug_set_logistic_rows", "pdmp_debug_math_probe", "pdmp_debug_math_eval", "pdmp_debug_write_probe", "pdmp_debug_sector_probe"]
 DEBUG_KERNELS = {"auto": 0, "seq": 1, "spec4": 2, "spec8": 3, "exactp": 4}
 
 
@@ -152,6 +152,7 @@ def load():
     L.pdmp_ensemble_trace_dev.argtypes = [vp, C.POINTER(vp), C.POINTER(i64)]
     L.pdmp_ensemble_counters_dev.argtypes = [vp, C.POINTER(vp)]
     L.pdmp_debug_math_probe.argtypes = [C.c_int, C.c_uint64, i64, vp]
+    L.pdmp_debug_math_eval.argtypes = [C.c_int, C.c_int, i64, vp, vp, vp, vp]
     L.pdmp_debug_write_probe.argtypes = [C.c_int, i64, i64, i64, C.c_int, C.POINTER(C.c_double)]
     L.pdmp_debug_sector_probe.argtypes = [C.c_int, i64, i64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]
     L.pdmp_ensemble_set_target_logistic.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, f64, i64]
@@ -230,6 +231,16 @@ def sector_probe(nchains, d, rounds, write, iters=3, device=0):
 def math_probe(seed, n, device=0):
     out = np.empty((8, n))
     check(load().pdmp_debug_math_probe(int(device), int(seed), int(n), out.ctypes.data))
+    return out
+
+
+def math_eval(fn, a, b=None, c=None, device=0):
+    """[2 x n] outputs of the device's scalar function `fn` (PDMP_MATH_* of include/pdmp_debug.h) at (a[k], b[k], c[k]); parity library only."""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    b = np.zeros_like(a) if b is None else np.ascontiguousarray(np.broadcast_to(b, a.shape), dtype=np.float64)
+    c = np.zeros_like(a) if c is None else np.ascontiguousarray(np.broadcast_to(c, a.shape), dtype=np.float64)
+    out = np.empty((2, a.size))
+    check(load().pdmp_debug_math_eval(int(device), int(fn), int(a.size), a.ctypes.data, b.ctypes.data, c.ctypes.data, out.ctypes.data))
     return out
 
 

@@ -213,3 +213,23 @@ extern "C" pdmp_status pdmp_1d_run(const pdmp_1d_config* cfg, pdmp_1d_state* sta
 #undef D1_TRY
     return PDMP_OK;
 }
+
+#ifdef PDMP_EXTRA_KERNELS
+#include "pdmp_engine.hpp"
+// pdmp_debug_math_eval: this unit's own copies, called as they are
+namespace {
+struct D1MathEval {
+    __device__ double operator()(int fn, double a, double b, double c, double*) const {
+        switch (fn) {
+        case PDMP_MATH_PT_D1: return d1_poisson_time(a, b, c);
+        default: return d1_pos(a);  // PDMP_MATH_POS_D1
+        }
+    }
+};
+}  // namespace
+namespace pdmp {
+int launch_math_eval_1d(int fn, int64_t n, const double* a, const double* b, const double* c, double* out, void* stream) {
+    return launch_math_eval<D1MathEval>(fn, n, a, b, c, out, stream);
+}
+}  // namespace pdmp
+#endif

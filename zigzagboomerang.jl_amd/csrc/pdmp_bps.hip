@@ -1085,4 +1085,22 @@ int launch_bps_run(const BpsRunParams& p, int64_t nchains, bool diag, void* stre
     return dispatch(p, m, nchains, diag, false, nullptr, 0.0, 0.0, stream);
 }
 
+#ifdef PDMP_EXTRA_KERNELS
+// pdmp_debug_math_eval: this unit's own copies, called as they are
+namespace {
+struct BpsMathEval {
+    __device__ double operator()(int fn, double a, double b, double c, double*) const {
+        switch (fn) {
+        case PDMP_MATH_PT_BPS: return bps_poisson_time(a, b, c);
+        case PDMP_MATH_PT_BPS_L: return bps_poisson_time_L(a, b, pdmp_log(c));
+        default: return bps_pos(a);  // PDMP_MATH_POS_BPS
+        }
+    }
+};
+}  // namespace
+int launch_math_eval_bps(int fn, int64_t n, const double* a, const double* b, const double* c, double* out, void* stream) {
+    return launch_math_eval<BpsMathEval>(fn, n, a, b, c, out, stream);
+}
+#endif
+
 }  // namespace pdmp

@@ -424,6 +424,46 @@ pdmp_status pdmp_debug_math_probe(int device, uint64_t seed, int64_t n, double* 
     return PDMP_OK;
 }
 
+pdmp_status pdmp_debug_math_eval(int device, int fn, int64_t n, const double* a, const double* b, const double* c, double* out) {
+#ifndef PDMP_EXTRA_KERNELS
+    (void)device, (void)fn, (void)n, (void)a, (void)b, (void)c, (void)out;
+    return fail(PDMP_ERR_UNSUPPORTED, "pdmp_debug_math_eval: the probe kernels live in the parity build (build.py --variant parity, -DPDMP_EXTRA_KERNELS)");
+#else
+    if (!a || !b || !c || !out || n <= 0 || n > ((int64_t)1 << 30)) return fail(PDMP_ERR_INVALID, "bad argument");
+    decltype(&pdmp::launch_math_eval_kernels) launch = nullptr;
+    switch (fn) {
+    case PDMP_MATH_U01: case PDMP_MATH_LOG: case PDMP_MATH_EXP: case PDMP_MATH_SINCOS: case PDMP_MATH_SINCOS2PI: case PDMP_MATH_RANDN:
+    case PDMP_MATH_RANDN2: case PDMP_MATH_RANDINT: case PDMP_MATH_DIV: case PDMP_MATH_SQRT:
+    case PDMP_MATH_PT_DEV: case PDMP_MATH_PT_DEV_L: case PDMP_MATH_POS_DEV: launch = pdmp::launch_math_eval_kernels; break;
+    case PDMP_MATH_PT_BPS: case PDMP_MATH_PT_BPS_L: case PDMP_MATH_POS_BPS: launch = pdmp::launch_math_eval_bps; break;
+    case PDMP_MATH_PT_D1: case PDMP_MATH_POS_D1: launch = pdmp::launch_math_eval_1d; break;
+    case PDMP_MATH_PT_G: case PDMP_MATH_PT_G_L: case PDMP_MATH_SIGMOID_G: case PDMP_MATH_POS_G: launch = pdmp::launch_math_eval_general; break;
+    case PDMP_MATH_PT_Q: case PDMP_MATH_POS_Q: launch = pdmp::launch_math_eval_partition; break;
+    case PDMP_MATH_PT_W_L: case PDMP_MATH_POS_W: launch = pdmp::launch_math_eval_trackp; break;
+    case PDMP_MATH_PT_LOGISTIC_L: case PDMP_MATH_SIGMOID_LOGISTIC: case PDMP_MATH_POS_LOGISTIC: launch = pdmp::launch_math_eval_logistic; break;
+    case PDMP_MATH_PT_TRACKL_L: case PDMP_MATH_POS_TRACKL: launch = pdmp::launch_math_eval_trackl; break;
+    case PDMP_MATH_PT_X_L: case PDMP_MATH_POS_X: launch = pdmp::launch_math_eval_exactp; break;
+    case PDMP_MATH_PT_R_L: case PDMP_MATH_SIGMOID_R: case PDMP_MATH_POS_R: launch = pdmp::launch_math_eval_logrows; break;
+    default: return fail(PDMP_ERR_INVALID, "pdmp_debug_math_eval: unknown function id %d", fn);
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(PDMP_ERR_NO_DEVICE, "no HIP device visible");
+    HIP_TRY(hipSetDevice(device));
+    DevBuf<double> in, res;
+    pdmp_status st = in.alloc((size_t)(3 * n));
+    if (st == PDMP_OK) st = res.alloc((size_t)(2 * n));
+    if (st != PDMP_OK) return st;
+    HIP_TRY(hipMemcpy(in.p, a, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(in.p + n, b, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(in.p + 2 * n, c, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    int rc = launch(fn, n, in.p, in.p + n, in.p + 2 * n, res.p, nullptr);
+    if (rc != 0) return fail(PDMP_ERR_HIP, "math eval launch failed: %s", hipGetErrorString((hipError_t)rc));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, res.p, (size_t)(2 * n) * sizeof(double), hipMemcpyDeviceToHost));
+    return PDMP_OK;
+#endif
+}
+
 // The factorised samplers (ZigZag / FactBoomerang / sticky) and the non-factorised ones (BouncyParticle / Boomerang) keep different
 // device state: an entry point of the wrong family is a call-order error, reported as a status (never a crash).
 #define NEED_FACTORISED(e)                                                                                               \

@@ -25,6 +25,9 @@
 #include <vector>
 
 #include "../../include/pdmp_mi355.h"
+#ifdef PDMP_EXTRA_KERNELS
+#include "../../include/pdmp_debug.h"  // (the PDMP_MATH_* ids of the probe kernels)
+#endif
 
 namespace pdmp {
 
@@ -443,5 +446,36 @@ int launch_consume_inclusion(int64_t d, int64_t nchains, bool with_z, double t0,
 int launch_zz_path_integrals(const ZzRec* rec, int64_t rec_stride, int64_t d, int64_t nchains, const int64_t* probes, int64_t nprobe,
                              double T, double* out, void* stream);
 int launch_math_probe(uint64_t seed, int64_t n, double* out, void* stream);
+
+#ifdef PDMP_EXTRA_KERNELS
+// pdmp_debug_math_eval (include/pdmp_debug.h, parity library only): a translation unit that owns copies of small scalar functions probes
+// them with math_eval_kernel<F>, where F{}(fn, a, b, c, &y1) calls the unit's copy for id fn as it is and returns its (first) output.
+template <class F>
+__global__ __launch_bounds__(256) void math_eval_kernel(int fn, int64_t n, const double* a, const double* b, const double* c, double* out) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= n) return;
+    double y1 = 0.0;
+    const double y0 = F{}(fn, a[k], b[k], c[k], &y1);
+    out[k] = y0;
+    out[n + k] = y1;
+}
+template <class F>
+int launch_math_eval(int fn, int64_t n, const double* a, const double* b, const double* c, double* out, void* stream) {
+    hipLaunchKernelGGL(math_eval_kernel<F>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, fn, n, a, b, c, out);
+    return (int)hipGetLastError();
+}
+// one launcher per owning unit (the ids of each are listed in pdmp_debug.h); pdmp_kernels.hip also evaluates the shared contract
+#define PDMP_MATH_EVAL_DECL(unit) int launch_math_eval_##unit(int fn, int64_t n, const double* a, const double* b, const double* c, double* out, void* stream)
+PDMP_MATH_EVAL_DECL(kernels);
+PDMP_MATH_EVAL_DECL(bps);
+PDMP_MATH_EVAL_DECL(1d);
+PDMP_MATH_EVAL_DECL(general);
+PDMP_MATH_EVAL_DECL(partition);
+PDMP_MATH_EVAL_DECL(trackp);
+PDMP_MATH_EVAL_DECL(logistic);
+PDMP_MATH_EVAL_DECL(trackl);
+PDMP_MATH_EVAL_DECL(exactp);
+PDMP_MATH_EVAL_DECL(logrows);
+#endif
 
 }  // namespace pdmp

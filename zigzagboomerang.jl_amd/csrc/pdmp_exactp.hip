@@ -962,4 +962,21 @@ int launch_zz_local_exactp(const ZzRunParams& p, int64_t nchains, void* stream) 
     return (int)hipGetLastError();
 }
 
+#ifdef PDMP_EXTRA_KERNELS
+// pdmp_debug_math_eval: this unit's own copies, called as they are
+namespace {
+struct ExactpMathEval {
+    __device__ double operator()(int fn, double a, double b, double c, double*) const {
+        switch (fn) {
+        case PDMP_MATH_PT_X_L: return x_poisson_time_L(a, b, pdmp_log(c));
+        default: return x_pos(a);  // PDMP_MATH_POS_X
+        }
+    }
+};
+}  // namespace
+int launch_math_eval_exactp(int fn, int64_t n, const double* a, const double* b, const double* c, double* out, void* stream) {
+    return launch_math_eval<ExactpMathEval>(fn, n, a, b, c, out, stream);
+}
+#endif
+
 }  // namespace pdmp

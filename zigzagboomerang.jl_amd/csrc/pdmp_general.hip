@@ -1020,4 +1020,23 @@ int launch_zz_general_run(const ZzRunParams& p, const ZzGeneralParams& q_in, int
     return (int)hipGetLastError();
 }
 
+#ifdef PDMP_EXTRA_KERNELS
+// pdmp_debug_math_eval: this unit's own copies, called as they are
+namespace {
+struct GeneralMathEval {
+    __device__ double operator()(int fn, double a, double b, double c, double*) const {
+        switch (fn) {
+        case PDMP_MATH_PT_G: return g_poisson_time(a, b, c);
+        case PDMP_MATH_PT_G_L: return g_poisson_time_L(a, b, pdmp_log(c));
+        case PDMP_MATH_SIGMOID_G: return g_sigmoid(a);
+        default: return g_pos(a);  // PDMP_MATH_POS_G
+        }
+    }
+};
+}  // namespace
+int launch_math_eval_general(int fn, int64_t n, const double* a, const double* b, const double* c, double* out, void* stream) {
+    return launch_math_eval<GeneralMathEval>(fn, n, a, b, c, out, stream);
+}
+#endif
+
 }  // namespace pdmp

@@ -4319,6 +4319,35 @@ int launch_math_probe(uint64_t seed, int64_t n, double* out, void* stream) {
     return (int)hipGetLastError();
 }
 
+#ifdef PDMP_EXTRA_KERNELS
+// pdmp_debug_math_eval: the shared contract at chosen points, and this unit's own copies
+namespace {
+struct KernelsMathEval {
+    __device__ double operator()(int fn, double a, double b, double c, double* y1) const {
+        double s, co;
+        switch (fn) {
+        case PDMP_MATH_U01: return pdmp_bits_to_u01(pdmp_f2u(a));
+        case PDMP_MATH_LOG: return pdmp_log(a);
+        case PDMP_MATH_EXP: return pdmp_exp(a);
+        case PDMP_MATH_SINCOS: pdmp_sincos(a, &s, &co); *y1 = co; return s;
+        case PDMP_MATH_SINCOS2PI: pdmp_sincos2pi(a, &s, &co); *y1 = co; return s;
+        case PDMP_MATH_RANDN: return pdmp_randn_from_u(a, b);
+        case PDMP_MATH_RANDN2: pdmp_randn2_from_u(a, b, &s, &co); *y1 = co; return s;
+        case PDMP_MATH_RANDINT: return (double)pdmp_randint(pdmp_f2u(a), PDMP_STREAM_GLOBAL, (uint64_t)b, (uint32_t)c);
+        case PDMP_MATH_DIV: return a / b;
+        case PDMP_MATH_SQRT: return sqrt(a);
+        case PDMP_MATH_PT_DEV: return dev_poisson_time(a, b, c);
+        case PDMP_MATH_PT_DEV_L: return dev_poisson_time_L(a, b, pdmp_log(c));
+        default: return pos_part(a);  // PDMP_MATH_POS_DEV
+        }
+    }
+};
+}  // namespace
+int launch_math_eval_kernels(int fn, int64_t n, const double* a, const double* b, const double* c, double* out, void* stream) {
+    return launch_math_eval<KernelsMathEval>(fn, n, a, b, c, out, stream);
+}
+#endif
+
 // ------------------------------------------------------------------------------------------ launchers
 
 int launch_zz_init(const ZzInitParams& p, void* stream) {

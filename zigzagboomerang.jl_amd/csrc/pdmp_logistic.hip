@@ -779,4 +779,22 @@ int launch_zz_logistic_lds(const ZzRunParams& p, const ZzGeneralParams& q, const
     return (int)hipGetLastError();
 }
 
+#ifdef PDMP_EXTRA_KERNELS
+// pdmp_debug_math_eval: this unit's own copies, called as they are
+namespace {
+struct LogisticMathEval {
+    __device__ double operator()(int fn, double a, double b, double c, double*) const {
+        switch (fn) {
+        case PDMP_MATH_PT_LOGISTIC_L: return l_poisson_time_L(a, b, pdmp_log(c));
+        case PDMP_MATH_SIGMOID_LOGISTIC: return l_sigmoid(a);
+        default: return l_pos(a);  // PDMP_MATH_POS_LOGISTIC
+        }
+    }
+};
+}  // namespace
+int launch_math_eval_logistic(int fn, int64_t n, const double* a, const double* b, const double* c, double* out, void* stream) {
+    return launch_math_eval<LogisticMathEval>(fn, n, a, b, c, out, stream);
+}
+#endif
+
 }  // namespace pdmp

@@ -432,4 +432,22 @@ int launch_zz_logistic_rows(const ZzRunParams& p, const ZzGeneralParams& q, cons
     return (int)hipGetLastError();
 }
 
+#ifdef PDMP_EXTRA_KERNELS
+// pdmp_debug_math_eval: this unit's own copies, called as they are
+namespace {
+struct LogrowsMathEval {
+    __device__ double operator()(int fn, double a, double b, double c, double*) const {
+        switch (fn) {
+        case PDMP_MATH_PT_R_L: return r_poisson_time_L(a, b, pdmp_log(c));
+        case PDMP_MATH_SIGMOID_R: return r_sigmoid(a);
+        default: return r_pos(a);  // PDMP_MATH_POS_R
+        }
+    }
+};
+}  // namespace
+int launch_math_eval_logrows(int fn, int64_t n, const double* a, const double* b, const double* c, double* out, void* stream) {
+    return launch_math_eval<LogrowsMathEval>(fn, n, a, b, c, out, stream);
+}
+#endif
+
 }  // namespace pdmp

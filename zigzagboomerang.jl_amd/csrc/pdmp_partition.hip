@@ -412,4 +412,21 @@ int launch_zz_partitioned(const ZzPartParams& p, int64_t nchains, void* stream) 
     return (int)hipGetLastError();
 }
 
+#ifdef PDMP_EXTRA_KERNELS
+// pdmp_debug_math_eval: this unit's own copies, called as they are
+namespace {
+struct PartitionMathEval {
+    __device__ double operator()(int fn, double a, double b, double c, double*) const {
+        switch (fn) {
+        case PDMP_MATH_PT_Q: return q_poisson_time(a, b, c);
+        default: return q_pos(a);  // PDMP_MATH_POS_Q
+        }
+    }
+};
+}  // namespace
+int launch_math_eval_partition(int fn, int64_t n, const double* a, const double* b, const double* c, double* out, void* stream) {
+    return launch_math_eval<PartitionMathEval>(fn, n, a, b, c, out, stream);
+}
+#endif
+
 }  // namespace pdmp

@@ -1180,4 +1180,21 @@ int launch_zz_trackl_unpack(const void* lines, const void* cold, void* rec, void
     return (int)hipGetLastError();
 }
 
+#ifdef PDMP_EXTRA_KERNELS
+// pdmp_debug_math_eval: this unit's own copies, called as they are
+namespace {
+struct TracklMathEval {
+    __device__ double operator()(int fn, double a, double b, double c, double*) const {
+        switch (fn) {
+        case PDMP_MATH_PT_TRACKL_L: return l_poisson_time_L(a, b, pdmp_log(c));
+        default: return l_pos(a);  // PDMP_MATH_POS_TRACKL
+        }
+    }
+};
+}  // namespace
+int launch_math_eval_trackl(int fn, int64_t n, const double* a, const double* b, const double* c, double* out, void* stream) {
+    return launch_math_eval<TracklMathEval>(fn, n, a, b, c, out, stream);
+}
+#endif
+
 }  // namespace pdmp

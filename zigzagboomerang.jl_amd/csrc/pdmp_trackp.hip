@@ -1468,4 +1468,21 @@ int launch_zz_keys_to_pairs(const double* keys, void* kp, int64_t n, double t0, 
     return (int)hipGetLastError();
 }
 
+#ifdef PDMP_EXTRA_KERNELS
+// pdmp_debug_math_eval: this unit's own copies, called as they are
+namespace {
+struct TrackpMathEval {
+    __device__ double operator()(int fn, double a, double b, double c, double*) const {
+        switch (fn) {
+        case PDMP_MATH_PT_W_L: return w_poisson_time_L(a, b, pdmp_log(c));
+        default: return w_pos(a);  // PDMP_MATH_POS_W
+        }
+    }
+};
+}  // namespace
+int launch_math_eval_trackp(int fn, int64_t n, const double* a, const double* b, const double* c, double* out, void* stream) {
+    return launch_math_eval<TrackpMathEval>(fn, n, a, b, c, out, stream);
+}
+#endif
+
 }  // namespace pdmp
