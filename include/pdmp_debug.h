@@ -90,11 +90,12 @@ pdmp_status pdmp_debug_math_probe(int device, uint64_t seed, int64_t n, double* 
 
 /*
  * Test hook: evaluate ONE small scalar function of the device at the points (a[k], b[k], c[k]), k = 0..n-1; out is [2 x n] row-major,
- * row 1 holds the second output of the two-output functions and 0 otherwise.  There is one id per function of the shared contract and
- * one per device copy of poisson_time, sigmoid and pos; a copy is probed by a kernel of the translation unit that owns it, calling it
- * as it is (the _L forms receive L = pdmp_log(c)).  The host evaluates the same ids with the oracle: the results must agree bit for bit
- * (tests/test_gpu_detmath.py).  The probe kernels exist only in the parity library (-DPDMP_EXTRA_KERNELS); the default library answers
- * PDMP_ERR_UNSUPPORTED.  The comment of each copy's id names its file and function (the test checks that against the sources).
+ * row 1 holds the second output of the two-output functions and 0 otherwise.  There is one id per function of the shared contract and,
+ * for poisson_time, sigmoid and pos (defined once, csrc/pdmp_device.hpp), one per unit that uses it: the function is probed by a kernel of
+ * that translation unit, i.e. as compiled there under the library's flags (the _L forms receive L = pdmp_log(c)).  The host evaluates the
+ * same ids with the oracle: the results must agree bit for bit (tests/test_gpu_detmath.py).  The probe kernels exist only in the parity
+ * library (-DPDMP_EXTRA_KERNELS); the default library answers PDMP_ERR_UNSUPPORTED.  The comment of each such id names the unit and the
+ * shared function it calls (tests/test_abi.py checks that against the sources).
  */
 /* include/pdmp_detmath.h */
 #define PDMP_MATH_U01 0        /* pdmp_bits_to_u01 of the 64 bits of a */
@@ -107,35 +108,35 @@ pdmp_status pdmp_debug_math_probe(int device, uint64_t seed, int64_t n, double* 
 #define PDMP_MATH_RANDINT 7    /* pdmp_randint(seed = 64 bits of a, PDMP_STREAM_GLOBAL, draw (uint64_t)b, n (uint32_t)c) */
 #define PDMP_MATH_DIV 8        /* a / b */
 #define PDMP_MATH_SQRT 9       /* sqrt(a) */
-/* poisson_time(a, b, u = c), one id per device copy */
-#define PDMP_MATH_PT_DEV 16      /* pdmp_kernels.hip dev_poisson_time */
-#define PDMP_MATH_PT_DEV_L 17    /* pdmp_kernels.hip dev_poisson_time_L */
-#define PDMP_MATH_PT_BPS 18      /* pdmp_bps.hip bps_poisson_time */
-#define PDMP_MATH_PT_BPS_L 19    /* pdmp_bps.hip bps_poisson_time_L */
-#define PDMP_MATH_PT_D1 20       /* pdmp_1d.hip d1_poisson_time */
-#define PDMP_MATH_PT_G 21        /* pdmp_general.hip g_poisson_time */
-#define PDMP_MATH_PT_G_L 22      /* pdmp_general.hip g_poisson_time_L */
-#define PDMP_MATH_PT_Q 23        /* pdmp_partition.hip q_poisson_time */
-#define PDMP_MATH_PT_W_L 24      /* pdmp_trackp.hip w_poisson_time_L */
-#define PDMP_MATH_PT_LOGISTIC_L 25 /* pdmp_logistic.hip l_poisson_time_L */
-#define PDMP_MATH_PT_TRACKL_L 26 /* pdmp_trackl.hip l_poisson_time_L */
-#define PDMP_MATH_PT_X_L 27      /* pdmp_exactp.hip x_poisson_time_L */
-#define PDMP_MATH_PT_R_L 28      /* pdmp_logrows.hip r_poisson_time_L */
+/* poisson_time(a, b, u = c), one id per unit that uses it */
+#define PDMP_MATH_PT_DEV 16      /* pdmp_kernels.hip poisson_time */
+#define PDMP_MATH_PT_DEV_L 17    /* pdmp_kernels.hip poisson_time_L */
+#define PDMP_MATH_PT_BPS 18      /* pdmp_bps.hip poisson_time */
+#define PDMP_MATH_PT_BPS_L 19    /* pdmp_bps.hip poisson_time_L_ref */
+#define PDMP_MATH_PT_D1 20       /* pdmp_1d.hip poisson_time */
+#define PDMP_MATH_PT_G 21        /* pdmp_general.hip poisson_time */
+#define PDMP_MATH_PT_G_L 22      /* pdmp_general.hip poisson_time_L */
+#define PDMP_MATH_PT_Q 23        /* pdmp_partition.hip poisson_time */
+#define PDMP_MATH_PT_W_L 24      /* pdmp_trackp.hip poisson_time_L */
+#define PDMP_MATH_PT_LOGISTIC_L 25 /* pdmp_logistic.hip poisson_time_L */
+#define PDMP_MATH_PT_TRACKL_L 26 /* pdmp_trackl.hip poisson_time_L */
+#define PDMP_MATH_PT_X_L 27      /* pdmp_exactp.hip poisson_time_L */
+#define PDMP_MATH_PT_R_L 28      /* pdmp_logrows.hip poisson_time_L */
 /* sigmoid(a) */
-#define PDMP_MATH_SIGMOID_G 32        /* pdmp_general.hip g_sigmoid */
-#define PDMP_MATH_SIGMOID_LOGISTIC 33 /* pdmp_logistic.hip l_sigmoid */
-#define PDMP_MATH_SIGMOID_R 34        /* pdmp_logrows.hip r_sigmoid */
+#define PDMP_MATH_SIGMOID_G 32        /* pdmp_general.hip sigmoid */
+#define PDMP_MATH_SIGMOID_LOGISTIC 33 /* pdmp_logistic.hip sigmoid */
+#define PDMP_MATH_SIGMOID_R 34        /* pdmp_logrows.hip sigmoid */
 /* pos(a) */
 #define PDMP_MATH_POS_DEV 40      /* pdmp_kernels.hip pos_part */
-#define PDMP_MATH_POS_BPS 41      /* pdmp_bps.hip bps_pos */
-#define PDMP_MATH_POS_D1 42       /* pdmp_1d.hip d1_pos */
-#define PDMP_MATH_POS_G 43        /* pdmp_general.hip g_pos */
-#define PDMP_MATH_POS_Q 44        /* pdmp_partition.hip q_pos */
-#define PDMP_MATH_POS_W 45        /* pdmp_trackp.hip w_pos */
-#define PDMP_MATH_POS_LOGISTIC 46 /* pdmp_logistic.hip l_pos */
-#define PDMP_MATH_POS_TRACKL 47   /* pdmp_trackl.hip l_pos */
-#define PDMP_MATH_POS_X 48        /* pdmp_exactp.hip x_pos */
-#define PDMP_MATH_POS_R 49        /* pdmp_logrows.hip r_pos */
+#define PDMP_MATH_POS_BPS 41      /* pdmp_bps.hip pos_part */
+#define PDMP_MATH_POS_D1 42       /* pdmp_1d.hip pos_part */
+#define PDMP_MATH_POS_G 43        /* pdmp_general.hip pos_part */
+#define PDMP_MATH_POS_Q 44        /* pdmp_partition.hip pos_part */
+#define PDMP_MATH_POS_W 45        /* pdmp_trackp.hip pos_part */
+#define PDMP_MATH_POS_LOGISTIC 46 /* pdmp_logistic.hip pos_part */
+#define PDMP_MATH_POS_TRACKL 47   /* pdmp_trackl.hip pos_part */
+#define PDMP_MATH_POS_X 48        /* pdmp_exactp.hip pos_part */
+#define PDMP_MATH_POS_R 49        /* pdmp_logrows.hip pos_part */
 pdmp_status pdmp_debug_math_eval(int device, int fn, int64_t n, const double* a, const double* b, const double* c, double* out);
 
 /*

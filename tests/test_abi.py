@@ -75,24 +75,39 @@ def test_headers_are_plain_c99(tmp_path):
     assert subprocess.call([str(exe)]) == 0
 
 
-def test_scalar_probe_covers_every_device_copy():
-    """Every __device__ copy of poisson_time, sigmoid and pos in csrc/ has its own pdmp_debug_math_eval id (include/pdmp_debug.h names the
-    file and function of each), and the probe of that id calls it: a new copy without a probe fails here (tests/test_gpu_detmath.py
-    holds every probed copy to the oracle bit for bit)."""
+SHARED_SCALARS = ("pos_part", "sigmoid", "poisson_time", "poisson_time_L", "poisson_time_L_ref")
+
+
+def test_shared_scalars_are_defined_once_and_probed_in_every_unit_that_calls_them():
+    """poisson_time, sigmoid and pos exist ONCE on the device, in csrc/pdmp_device.hpp: no translation unit defines a copy of its own.  Every
+    unit that calls one of them (outside its probe) has a pdmp_debug_math_eval id for that call (include/pdmp_debug.h names the unit and the
+    function of each), and the unit's probe returns that call under that id: a new user without a probe, or a private copy, fails here
+    (tests/test_gpu_detmath.py holds every probed call, as compiled inside its unit, to the oracle bit for bit)."""
     csrc = os.path.join(ROOT, "zigzagboomerang.jl_amd", "csrc")
-    found = set()
-    for f in sorted(os.listdir(csrc)):
-        if f.endswith((".hip", ".inc")):
-            for name in re.findall(r"__device__[^;{(]*?\b(\w+)\s*\(\s*double\b", open(os.path.join(csrc, f)).read()):
-                if "poisson_time" in name or "sigmoid" in name or name.endswith("_pos") or name == "pos_part":
-                    found.add((f, name))
+
+    def scalar_definitions(f):
+        names = re.findall(r"__device__[^;{(]*?\b(\w+)\s*\(\s*double\b", open(os.path.join(csrc, f)).read())
+        return sorted(n for n in names if "poisson_time" in n or "sigmoid" in n or n.endswith("_pos") or n == "pos_part")
+
+    units = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".inc")))
+    assert [(f, scalar_definitions(f)) for f in sorted(os.listdir(csrc)) if f != "pdmp_device.hpp" and scalar_definitions(f)] == []
+    assert scalar_definitions("pdmp_device.hpp") == sorted(SHARED_SCALARS)
+
+    called = set()  # (unit, scalar): calls in the unit's code before its probe functor (an .inc file belongs to the unit that includes it)
+    for f in units:
+        text = re.sub(r"//[^\n]*|/\*.*?\*/", "", open(os.path.join(csrc, f)).read(), flags=re.S)
+        text = re.split(r"struct \w+MathEval\b", text)[0]
+        owner = f if f.endswith(".hip") else next(u for u in units if '#include "%s"' % f in open(os.path.join(csrc, u)).read())
+        called |= {(owner, name) for name in re.findall(r"(?<![\w.])(%s)\s*\(" % "|".join(SHARED_SCALARS), text)}
     src = open(os.path.join(ROOT, "include", "pdmp_debug.h")).read()
     ids = re.findall(r"#define (PDMP_MATH_\w+) \d+\s*/\* (pdmp_\w+\.hip) (\w+) \*/", src)
-    assert found == {(f, name) for _, f, name in ids}
-    assert len(found) == 26  # 13 poisson_time, 3 sigmoid, 10 pos
-    for macro, f, name in ids:  # the probe of the unit that owns the copy calls it under that id
-        text = open(os.path.join(csrc, f)).read()
-        assert re.search(r"(case %s: return %s\(|default: return %s\([^;]*;\s*//\s*%s\b)" % (macro, name, name, macro), text), (macro, f, name)
+    probed = {(f, name) for _, f, name in ids}
+    assert called <= probed, called - probed
+    assert probed - called == {("pdmp_general.hip", "poisson_time")}  # (an id kept for a unit whose event loop takes the _L form only)
+    assert len(ids) == len(probed) == 26  # 13 poisson_time (5 plain, 7 _L, 1 _L_ref), 3 sigmoid, 10 pos
+    for macro, f, name in ids:  # the probe of the unit returns that call under that id
+        probe = re.split(r"struct \w+MathEval\b", open(os.path.join(csrc, f)).read())[1]
+        assert re.search(r"(case %s: return %s\(|default: return %s\([^;]*;\s*//\s*%s\b)" % (macro, name, name, macro), probe), (macro, f, name)
 
 
 def test_scalar_probe_is_parity_library_only(pkg):

@@ -12,34 +12,14 @@
 
 #include "../../include/pdmp_detmath.h"
 #include "../../include/pdmp_mi355.h"
+#include "pdmp_device.hpp"
 
 extern "C" void pdmp_set_last_error_(const char* msg);  // pdmp_capi.hip
 
 namespace {
 
-#define D1_INF __builtin_inf()
-
-__device__ __forceinline__ double d1_pos(double x) {  // pos(x), src/common.jl:8
-    return (x > 0.0) ? x : ((x != x) ? x : 0.0);
-}
-// poisson_time(a, b, u), src/poissontime.jl:8-30
-__device__ __forceinline__ double d1_poisson_time(double a, double b, double u) {
-    const double L = pdmp_log(u);
-    if (b > 0) {
-        const double r = a / b;
-        if (a < 0) return sqrt(-L * 2.0 / b) - r;
-        return sqrt(r * r - L * 2.0 / b) - r;
-    } else if (b == 0) {
-        return (a > 0) ? -L / a : D1_INF;
-    } else {
-        if (a <= 0) return D1_INF;
-        if (-L <= -(a * a) / b + (a * a) / (2 * b)) {
-            const double r = a / b;
-            return -sqrt(r * r - L * 2.0 / b) - r;
-        }
-        return D1_INF;
-    }
-}
+using pdmp::poisson_time;
+using pdmp::pos_part;
 
 struct D1Params {
     pdmp_1d_config cfg;
@@ -81,9 +61,9 @@ __global__ __launch_bounds__(64) void pdmp1d_run_kernel(D1Params P) {
     if (!S.started) {
         t = 0.0;  // :35
         if (cap > 0) push(t, x, th);  // :36
-        t_ref = boom ? t + pdmp_randexp_from_u(pdmp_u01(seed, PDMP_STREAM_MAIN, nm++)) / blam : D1_INF;  // :19-20,37
+        t_ref = boom ? t + pdmp_randexp_from_u(pdmp_u01(seed, PDMP_STREAM_MAIN, nm++)) / blam : PDMP_INF;  // :19-20,37
         bound();
-        tp = t + d1_poisson_time(a, b, pdmp_u01(seed, PDMP_STREAM_MAIN, nm++));  // :40
+        tp = t + poisson_time(a, b, pdmp_u01(seed, PDMP_STREAM_MAIN, nm++));  // :40
         S.started = 1;
     }
     while (t < P.T) {  // :41
@@ -116,8 +96,8 @@ __global__ __launch_bounds__(64) void pdmp1d_run_kernel(D1Params P) {
             }
             double gx = (x - P.cfg.mu) / P.cfg.sigma2;                                                        // test/test1d.jl:9
             if (P.cfg.noise != 0.0) gx = gx + P.cfg.noise * (pdmp_u01(seed, PDMP_STREAM_MAIN, nm++) - 0.5);  // :10
-            const double l = boom ? d1_pos(th * (gx - (x - bmu) / bsig)) : d1_pos(th * gx);  // λ, :5-6
-            const double lb = d1_pos(a + b * tau);                                           // λ_bar, :9,50
+            const double l = boom ? pos_part(th * (gx - (x - bmu) / bsig)) : pos_part(th * gx);  // λ, :5-6
+            const double lb = pos_part(a + b * tau);                                             // λ_bar, :9,50
             num += 1;
             if (pdmp_u01(seed, PDMP_STREAM_MAIN, nm++) * lb < l) {  // :52
                 acc += 1;
@@ -131,8 +111,8 @@ __global__ __launch_bounds__(64) void pdmp1d_run_kernel(D1Params P) {
                 push(t, x, th);                       // :60
             }
         }
-        bound();                                                                  // :63
-        tp = t + d1_poisson_time(a, b, pdmp_u01(seed, PDMP_STREAM_MAIN, nm++));  // :64
+        bound();                                                               // :63
+        tp = t + poisson_time(a, b, pdmp_u01(seed, PDMP_STREAM_MAIN, nm++));  // :64
     }
     S.t = t;
     S.x = x;
@@ -216,13 +196,13 @@ extern "C" pdmp_status pdmp_1d_run(const pdmp_1d_config* cfg, pdmp_1d_state* sta
 
 #ifdef PDMP_EXTRA_KERNELS
 #include "pdmp_engine.hpp"
-// pdmp_debug_math_eval: this unit's own copies, called as they are
+// pdmp_debug_math_eval: the shared scalars (pdmp_device.hpp) this unit calls, as compiled here
 namespace {
 struct D1MathEval {
     __device__ double operator()(int fn, double a, double b, double c, double*) const {
         switch (fn) {
-        case PDMP_MATH_PT_D1: return d1_poisson_time(a, b, c);
-        default: return d1_pos(a);  // PDMP_MATH_POS_D1
+        case PDMP_MATH_PT_D1: return poisson_time(a, b, c);
+        default: return pos_part(a);  // PDMP_MATH_POS_D1
         }
     }
 };

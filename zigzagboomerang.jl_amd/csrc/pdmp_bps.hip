@@ -15,83 +15,26 @@
 #include <cstdint>
 
 #include "../../include/pdmp_detmath.h"
+#include "pdmp_device.hpp"
 #include "pdmp_engine.hpp"
 
 namespace pdmp {
 
-#define BPS_INF __builtin_inf()
-
-__device__ __forceinline__ double b_readlane(double v, int srclane) {
-    int lo = __builtin_amdgcn_readlane(__double2loint(v), srclane);
-    int hi = __builtin_amdgcn_readlane(__double2hiint(v), srclane);
-    return __hiloint2double(hi, lo);
-}
-template <int CTRL>
-__device__ __forceinline__ double b_dpp(double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, true);  // every lane has a valid source: no tied `old` operand, no copies
-    hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
 // all-lanes sum in the oracle's order: xor 1, 2 (quads), 4, 8 (row of 16), then (r0+r1)+(r2+r3)
 __device__ __forceinline__ double wave_sum_f64(double v) {
-    v = v + b_dpp<0xB1>(v);   // lane ^ 1
-    v = v + b_dpp<0x4E>(v);   // lane ^ 2
-    v = v + b_dpp<0x141>(v);  // other quad of the half row (same value in every lane of a quad: == lane ^ 4)
-    v = v + b_dpp<0x140>(v);  // other half row (== lane ^ 8)
-    const double r0 = b_readlane(v, 0), r1 = b_readlane(v, 16), r2 = b_readlane(v, 32), r3 = b_readlane(v, 48);
+    v = v + dpp_f64<0xB1>(v);   // lane ^ 1
+    v = v + dpp_f64<0x4E>(v);   // lane ^ 2
+    v = v + dpp_f64<0x141>(v);  // other quad of the half row (same value in every lane of a quad: == lane ^ 4)
+    v = v + dpp_f64<0x140>(v);  // other half row (== lane ^ 8)
+    const double r0 = readlane_f64(v, 0), r1 = readlane_f64(v, 16), r2 = readlane_f64(v, 32), r3 = readlane_f64(v, 48);
     return (r0 + r1) + (r2 + r3);  // lane ^ 16, then lane ^ 32
-}
-
-__device__ __forceinline__ double bps_pos(double x) {
-    return (x > 0.0) ? x : ((x != x) ? x : 0.0);
-}
-
-// poisson_time(a, b, u), src/poissontime.jl:8-30
-__device__ __forceinline__ double bps_poisson_time(double a, double b, double u) {
-    const double L = pdmp_log(u);
-    if (b > 0) {
-        const double r = a / b;
-        if (a < 0) return sqrt(-L * 2.0 / b) - r;
-        return sqrt(r * r - L * 2.0 / b) - r;
-    } else if (b == 0) {
-        return (a > 0) ? (-L / a) : BPS_INF;
-    } else {
-        if (a <= 0) return BPS_INF;
-        if (-L <= -(a * a) / b + (a * a) / (2 * b)) {
-            const double r = a / b;
-            return -sqrt(r * r - L * 2.0 / b) - r;
-        }
-        return BPS_INF;
-    }
-}
-
-// IDENT: Γ = I and μ = 0 exactly (config C2, the isotropic target): ∇ϕ!(y, x) = 0 + 1·(x − 0) is x itself, so the gradient array,
-// μ and the diagonal leave the register file (256 -> about 100 VGPRs at NS = 16: 1 -> 4 waves per SIMD) and Γθ = θ.
-// poisson_time(a, b, u) with L = log(u) already taken (the draw's index is known before the rates are: the logarithm is
-// evaluated off the critical path)
-__device__ __forceinline__ double bps_poisson_time_L(double a, double b, double L) {
-    if (b > 0) {
-        const double r = a / b;
-        if (a < 0) return sqrt(-L * 2.0 / b) - r;
-        return sqrt(r * r - L * 2.0 / b) - r;
-    } else if (b == 0) {
-        return (a > 0) ? (-L / a) : BPS_INF;
-    } else {
-        if (a <= 0) return BPS_INF;
-        if (-L <= -(a * a) / b + (a * a) / (2 * b)) {
-            const double r = a / b;
-            return -sqrt(r * r - L * 2.0 / b) - r;
-        }
-        return BPS_INF;
-    }
 }
 
 // IDENT: Γ = I and μ = 0 exactly (config C2, the isotropic target): ∇ϕ!(y, x) = 0 + 1·(x − 0) is x itself, so the gradient array,
 // μ and the diagonal leave the register file (256 -> about 100 VGPRs at NS = 16: 1 -> 4 waves per SIMD) and Γθ = θ.
 // t′ − t = poisson_time(a, b, rand(rng)) behind a call as well (log polynomial, two divisions, sqrt: constants and temporaries)
 __device__ __attribute__((noinline)) double bps_next_dt(uint64_t seed, uint64_t n, double a, double b) {
-    return bps_poisson_time(a, b, pdmp_u01(seed, PDMP_STREAM_MAIN, n));
+    return poisson_time(a, b, pdmp_u01(seed, PDMP_STREAM_MAIN, n));
 }
 
 // ∫_0^τ x(s) ds (MOM >= 1) and ∫_0^τ x(s)² ds (MOM >= 2) along the free flow from (x, θ), one element: linear, x(s) = x + θs
@@ -144,7 +87,7 @@ __global__ __launch_bounds__(64) void bps_run_kernel(BpsRunParams P, Mom... M) {
              nevents = hdr->c.nevents;
     double t = sc[0], a = sc[1], b = sc[2], tp = sc[3], tau_ref = sc[4], c = sc[5];
     bool renew = EXT && sc[6] != 0.0;  // next_time's flag (src/not_fact_samplers.jl:43-50): t′ is the bound's expiry, not a proposal
-    double hz = EXT ? sc[7] : BPS_INF; // abc[3]
+    double hz = EXT ? sc[7] : PDMP_INF; // abc[3]
     const bool has_mass = EXT && P.Lcp != nullptr;
 
     constexpr int NG = IDENT ? 1 : NS;
@@ -326,12 +269,12 @@ __global__ __launch_bounds__(64) void bps_run_kernel(BpsRunParams P, Mom... M) {
         }
         if constexpr (EXT) {
             // ab(x, θ, C::LocalBound, ∇ϕx, v, B) = (c + dot(θ, ∇ϕx), v, 2√d/c/‖θ‖₂), :29-31; next_time, :43-50
-            hz = (P.local_bound && !BOOM) ? 2 * sqrt((double)d) / c / sqrt(dot(th, th)) : BPS_INF;
-            const double dt = bps_poisson_time_L(a, b, Lnext);
+            hz = (P.local_bound && !BOOM) ? 2 * sqrt((double)d) / c / sqrt(dot(th, th)) : PDMP_INF;
+            const double dt = poisson_time_L_ref(a, b, Lnext);
             renew = dt > hz;
             tp = renew ? t + hz : t + dt;
         } else {
-            tp = t + bps_poisson_time_L(a, b, Lnext);
+            tp = t + poisson_time_L_ref(a, b, Lnext);
         }
         nm += 1;
     };
@@ -408,7 +351,7 @@ __global__ __launch_bounds__(64) void bps_run_kernel(BpsRunParams P, Mom... M) {
         }
         const bool is_ref = tau_ref < tp;  // :55
         const double tnext = is_ref ? tau_ref : tp;
-        if (!(tnext < BPS_INF)) {
+        if (!(tnext < PDMP_INF)) {
             status = PDMP_CHAIN_STALLED;
             break;
         }
@@ -460,8 +403,8 @@ __global__ __launch_bounds__(64) void bps_run_kernel(BpsRunParams P, Mom... M) {
             double gt;
             if constexpr (IDENT) gt = dot(x, th);
             else gt = dot(g, th);
-            const double l = bps_pos(gt);            // λ, :14
-            const double lb = bps_pos(a + b * tau);  // :77
+            const double l = pos_part(gt);            // λ, :14
+            const double lb = pos_part(a + b * tau);  // :77
             num += 1;
             nm += 1;
             if (coin * lb <= l) {  // :79
@@ -513,7 +456,7 @@ __global__ __launch_bounds__(64) void bps_run_kernel(BpsRunParams P, Mom... M) {
                 } else {
                     a = c + gt;  // :92 (θ'g == g'θ bit for bit; b = θ'Γθ is unchanged because θ is)
                 }
-                const double dt = bps_poisson_time_L(a, b, Lnext);  // :93 (the horizon is unchanged: θ and c are)
+                const double dt = poisson_time_L_ref(a, b, Lnext);  // :93 (the horizon is unchanged: θ and c are)
                 if constexpr (EXT) {
                     renew = dt > hz;
                     tp = renew ? t + hz : t + dt;
@@ -667,12 +610,12 @@ __global__ __launch_bounds__(64) void bps_init_kernel(BpsRunParams P, const uint
         else apply_gamma(th, false, gt);
         b = dot(th, gt);
     }
-    double tp = t0 + bps_poisson_time(a, b, pdmp_u01(seed, PDMP_STREAM_MAIN, 1));          // :135
-    double hz = BPS_INF;
+    double tp = t0 + poisson_time(a, b, pdmp_u01(seed, PDMP_STREAM_MAIN, 1));  // :135
+    double hz = PDMP_INF;
     bool renew = false;
     if (!BOOM && P.local_bound) {  // next_time with the LocalBound horizon, :29-31,43-50
         hz = 2 * sqrt((double)d) / c0 / sqrt(dot(th, th));
-        const double dt = bps_poisson_time(a, b, pdmp_u01(seed, PDMP_STREAM_MAIN, 1));
+        const double dt = poisson_time(a, b, pdmp_u01(seed, PDMP_STREAM_MAIN, 1));
         renew = dt > hz;
         tp = renew ? t0 + hz : t0 + dt;
     }
@@ -1086,14 +1029,14 @@ int launch_bps_run(const BpsRunParams& p, int64_t nchains, bool diag, void* stre
 }
 
 #ifdef PDMP_EXTRA_KERNELS
-// pdmp_debug_math_eval: this unit's own copies, called as they are
+// pdmp_debug_math_eval: the shared scalars (pdmp_device.hpp) this unit calls, as compiled here
 namespace {
 struct BpsMathEval {
     __device__ double operator()(int fn, double a, double b, double c, double*) const {
         switch (fn) {
-        case PDMP_MATH_PT_BPS: return bps_poisson_time(a, b, c);
-        case PDMP_MATH_PT_BPS_L: return bps_poisson_time_L(a, b, pdmp_log(c));
-        default: return bps_pos(a);  // PDMP_MATH_POS_BPS
+        case PDMP_MATH_PT_BPS: return poisson_time(a, b, c);
+        case PDMP_MATH_PT_BPS_L: return poisson_time_L_ref(a, b, pdmp_log(c));
+        default: return pos_part(a);  // PDMP_MATH_POS_BPS
         }
     }
 };

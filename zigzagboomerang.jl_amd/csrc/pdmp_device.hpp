@@ -1,0 +1,201 @@
+// pdmp_device.hpp -- the device helpers every event-loop translation unit shares: the contract scalars of the reference (pos, sigmoid,
+// poisson_time) and the lane / wave primitives of a 64-lane wavefront.  Device code only, each function defined ONCE; a unit keeps what
+// is truly its own.  pdmp_debug_math_eval probes the scalars inside every unit that calls them (include/pdmp_debug.h).
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <type_traits>
+
+#include "../../include/pdmp_detmath.h"
+
+#define PDMP_INF __builtin_inf()
+
+// Cross-lane hand-off through LDS inside ONE wavefront: DS operations execute in issue order, so no s_barrier
+// and no s_waitcnt vmcnt(0) is needed -- but the COMPILER must be told that memory changed behind the thread's
+// back (otherwise it may forward a lane's own earlier store to its later load of the same slot).
+#define PDMP_LDS_ORDER()                 \
+    do {                                 \
+        __builtin_amdgcn_wave_barrier(); \
+        asm volatile("" ::: "memory");   \
+    } while (0)
+
+namespace pdmp {
+
+// ------------------------------------------------------------------------------------------ lane helpers
+
+__device__ __forceinline__ double readlane_f64(double v, int srclane) {
+    int lo = __builtin_amdgcn_readlane(__double2loint(v), srclane);
+    int hi = __builtin_amdgcn_readlane(__double2hiint(v), srclane);
+    return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ uint32_t uniform_u32(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+}
+__device__ __forceinline__ double uniform_f64(double v) {
+    int lo = __builtin_amdgcn_readfirstlane(__double2loint(v));
+    int hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
+    return __hiloint2double(hi, lo);
+}
+// value of lane `src` (any lane, per-lane choice): two ds_bpermute_b32
+__device__ __forceinline__ double bperm_f64(double v, uint32_t src) {
+    const int lo = __builtin_amdgcn_ds_bpermute((int)(src << 2), __double2loint(v));
+    const int hi = __builtin_amdgcn_ds_bpermute((int)(src << 2), __double2hiint(v));
+    return __hiloint2double(hi, lo);
+}
+
+// DPP move of both halves.  The control codes used here and in the units:
+//   0xB1 quad_perm [1,0,3,2] (lane ^ 1)    0x4E quad_perm [2,3,0,1] (lane ^ 2)    0x141 row_half_mirror    0x140 row_mirror
+//   0x111 .. 0x11F row_shr 1 .. 15         0x142 row_bcast:15 (row r takes lane 15 of row r-1)      0x143 row_bcast:31 (rows 2, 3 take lane 31)
+template <int CTRL>
+__device__ __forceinline__ double dpp_f64(double v) {
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, true);  // every lane has a valid source: no tied `old` operand, no copies
+    hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, true);
+    return __hiloint2double(hi, lo);
+}
+
+// One v_min_f64.  Written as the instruction itself: fmin() of a value that came out of a load or a DPP move is preceded by a
+// canonicalising v_max_f64 x, x per operand (IEEE-mode minnum lowering), i.e. three DP instructions per minimum in the queue
+// reductions.  Keys are never NaN unless a chain has diverged; v_min_f64 then returns the other operand (NaN loses, as +Inf).
+__device__ __forceinline__ double min_f64(double a, double b) {
+    double r;
+    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ double max_f64(double a, double b) {
+    double r;
+    asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+
+// ------------------------------------------------------------------------------------------ wave reductions and scans
+
+// Minimum over the 64 lanes, returned wave-uniform.  4 DPP steps inside each row of 16 lanes (quad xor-1, quad xor-2, half-row
+// mirror, row mirror), then row_bcast:15 (row r takes lane 15 of row r-1) and row_bcast:31 (rows 2, 3 take lane 31): lane 63 ends
+// with the minimum of the four rows.  Lanes that have no source read 0 and hold garbage afterwards; only lane 63 is read.
+__device__ __forceinline__ double wave_min_f64(double v) {
+    v = min_f64(v, dpp_f64<0xB1>(v));   // quad_perm [1,0,3,2]
+    v = min_f64(v, dpp_f64<0x4E>(v));   // quad_perm [2,3,0,1]
+    v = min_f64(v, dpp_f64<0x141>(v));  // row_half_mirror
+    v = min_f64(v, dpp_f64<0x140>(v));  // row_mirror
+    v = min_f64(v, dpp_f64<0x142>(v));  // row_bcast:15
+    v = min_f64(v, dpp_f64<0x143>(v));  // row_bcast:31
+    return readlane_f64(v, 63);
+}
+// minimum over the 8 lanes of a group, returned in every lane of the group
+__device__ __forceinline__ double grp8_min_f64(double v) {
+    v = min_f64(v, dpp_f64<0xB1>(v));
+    v = min_f64(v, dpp_f64<0x4E>(v));
+    v = min_f64(v, dpp_f64<0x141>(v));  // row_half_mirror: reverses each half row
+    return v;
+}
+// The same six steps for u32, wave-uniform (DPP: six steps on the vector unit instead of six ds_bpermute round trips; pdmp_kernels.hip
+// keeps a __shfl_xor form, wave_min_u32, of its own)
+__device__ __forceinline__ uint32_t wave_min_u32_dpp(uint32_t v) {
+    auto step = [](uint32_t x, auto ctrl) -> uint32_t {
+        const uint32_t o = (uint32_t)__builtin_amdgcn_mov_dpp((int)x, decltype(ctrl)::value, 0xf, 0xf, true);
+        return (o < x) ? o : x;
+    };
+    v = step(v, std::integral_constant<int, 0xB1>{});
+    v = step(v, std::integral_constant<int, 0x4E>{});
+    v = step(v, std::integral_constant<int, 0x141>{});
+    v = step(v, std::integral_constant<int, 0x140>{});
+    // (row_bcast: lanes that receive nothing read 0 and are not used: the result is lane 63's)
+    v = step(v, std::integral_constant<int, 0x142>{});
+    v = step(v, std::integral_constant<int, 0x143>{});
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
+// DPP prefix operations over the 64 lanes (row_shr 1, 2, 3 of the input, then row_shr 4 / 8 of the partial result inside the enabled banks,
+// then row_bcast 15 / 31 across the rows): lanes without a source keep the identity.
+template <int CTRL, int ROWM, int BANKM>
+__device__ __forceinline__ uint32_t dpp_id_u32(uint32_t identity, uint32_t src) {
+    return (uint32_t)__builtin_amdgcn_update_dpp((int)identity, (int)src, CTRL, ROWM, BANKM, false);
+}
+__device__ __forceinline__ uint32_t scan_add_u32(uint32_t v) {  // inclusive
+    uint32_t x = v;
+    x += dpp_id_u32<0x111, 0xf, 0xf>(0u, v);
+    x += dpp_id_u32<0x112, 0xf, 0xf>(0u, v);
+    x += dpp_id_u32<0x113, 0xf, 0xf>(0u, v);
+    x += dpp_id_u32<0x114, 0xf, 0xe>(0u, x);
+    x += dpp_id_u32<0x118, 0xf, 0xc>(0u, x);
+    x += dpp_id_u32<0x142, 0xa, 0xf>(0u, x);
+    x += dpp_id_u32<0x143, 0xc, 0xf>(0u, x);
+    return x;
+}
+template <int CTRL, int ROWM, int BANKM>
+__device__ __forceinline__ double dpp_inf(double src) {  // (identity +Inf)
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(src), CTRL, ROWM, BANKM, false);
+    const int hi = __builtin_amdgcn_update_dpp(0x7FF00000, __double2hiint(src), CTRL, ROWM, BANKM, false);
+    return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ double scan_min_f64(double v) {  // inclusive
+    double x = v;
+    x = min_f64(x, dpp_inf<0x111, 0xf, 0xf>(v));
+    x = min_f64(x, dpp_inf<0x112, 0xf, 0xf>(v));
+    x = min_f64(x, dpp_inf<0x113, 0xf, 0xf>(v));
+    x = min_f64(x, dpp_inf<0x114, 0xf, 0xe>(x));
+    x = min_f64(x, dpp_inf<0x118, 0xf, 0xc>(x));
+    x = min_f64(x, dpp_inf<0x142, 0xa, 0xf>(x));
+    x = min_f64(x, dpp_inf<0x143, 0xc, 0xf>(x));
+    return x;
+}
+
+// ------------------------------------------------------------------------------------------ contract scalars
+
+// pos(x) = max(zero(x), x), src/common.jl:8
+__device__ __forceinline__ double pos_part(double x) {
+    return (x > 0.0) ? x : ((x != x) ? x : 0.0);
+}
+// sigmoid(x) = inv(one(x) + exp(-x)), scripts/logistic.jl:33
+__device__ __forceinline__ double sigmoid(double x) {
+    return 1.0 / (1.0 + pdmp_exp(-x));
+}
+// the largest double below a finite x (x > 0, or x < 0, or x == 0 all handled by the integer image)
+__device__ __forceinline__ double pdmp_below(double x) {
+    long long b = __double_as_longlong(x);
+    if (x > 0) b -= 1;
+    else if (x < 0) b += 1;
+    else b = (long long)0x8000000000000001ull;  // -denorm_min
+    return __longlong_as_double(b);
+}
+
+// poisson_time(a, b, u) with L = log(u) supplied, src/poissontime.jl:8-30, in the reference's form: a branch per sign of b and of a,
+// each with its own divisions and square root (the Bouncy Particle kernels; poisson_time_L below is what the other event loops use)
+__device__ __forceinline__ double poisson_time_L_ref(double a, double b, double L) {
+    if (b > 0) {
+        const double r = a / b;
+        if (a < 0) return sqrt(-L * 2.0 / b) - r;
+        return sqrt(r * r - L * 2.0 / b) - r;
+    } else if (b == 0) {
+        return (a > 0) ? (-L / a) : PDMP_INF;
+    } else {
+        if (a <= 0) return PDMP_INF;
+        if (-L <= -(a * a) / b + (a * a) / (2 * b)) {
+            const double r = a / b;
+            return -sqrt(r * r - L * 2.0 / b) - r;
+        }
+        return PDMP_INF;
+    }
+}
+// poisson_time(a, b, u), src/poissontime.jl:8-30
+__device__ __forceinline__ double poisson_time(double a, double b, double u) {
+    return poisson_time_L_ref(a, b, pdmp_log(u));
+}
+// poisson_time(a, b, u) with L = log(u) supplied (src/poissontime.jl:8-30), merged: the same value as poisson_time_L_ref bit for bit
+__device__ __forceinline__ double poisson_time_L(double a, double b, double L) {
+    // The three b != 0 formulas share a / b, L * 2 / b and the square root (sqrt(-L * 2.0 / b) is sqrt(-(L * 2.0 / b)) bit for
+    // bit), so a wavefront whose lanes disagree on the signs of a and b runs ONE division pair and ONE square root instead of
+    // one set per branch; only the admissibility test of the b < 0 branch keeps its own two divisions.
+    if (b == 0) return (a > 0) ? -L / a : PDMP_INF;
+    const double r = a / b;
+    const double q = L * 2.0 / b;
+    const double sq = sqrt((b > 0 && a < 0) ? -q : r * r - q);
+    if (b > 0) return sq - r;
+    if (a <= 0) return PDMP_INF;
+    if (-L <= -(a * a) / b + (a * a) / (2 * b)) return -sq - r;
+    return PDMP_INF;
+}
+
+}  // namespace pdmp

@@ -448,8 +448,8 @@ int launch_zz_path_integrals(const ZzRec* rec, int64_t rec_stride, int64_t d, in
 int launch_math_probe(uint64_t seed, int64_t n, double* out, void* stream);
 
 #ifdef PDMP_EXTRA_KERNELS
-// pdmp_debug_math_eval (include/pdmp_debug.h, parity library only): a translation unit that owns copies of small scalar functions probes
-// them with math_eval_kernel<F>, where F{}(fn, a, b, c, &y1) calls the unit's copy for id fn as it is and returns its (first) output.
+// pdmp_debug_math_eval (include/pdmp_debug.h, parity library only): a translation unit that calls the shared scalar functions of pdmp_device.hpp
+// probes them, as compiled inside it, with math_eval_kernel<F>, where F{}(fn, a, b, c, &y1) makes the call of id fn and returns its (first) output.
 template <class F>
 __global__ __launch_bounds__(256) void math_eval_kernel(int fn, int64_t n, const double* a, const double* b, const double* c, double* out) {
     const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -464,7 +464,7 @@ int launch_math_eval(int fn, int64_t n, const double* a, const double* b, const 
     hipLaunchKernelGGL(math_eval_kernel<F>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, fn, n, a, b, c, out);
     return (int)hipGetLastError();
 }
-// one launcher per owning unit (the ids of each are listed in pdmp_debug.h); pdmp_kernels.hip also evaluates the shared contract
+// one launcher per unit (the ids of each are listed in pdmp_debug.h); pdmp_kernels.hip also evaluates the shared contract
 #define PDMP_MATH_EVAL_DECL(unit) int launch_math_eval_##unit(int fn, int64_t n, const double* a, const double* b, const double* c, double* out, void* stream)
 PDMP_MATH_EVAL_DECL(kernels);
 PDMP_MATH_EVAL_DECL(bps);

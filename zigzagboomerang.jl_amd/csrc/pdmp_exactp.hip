@@ -28,113 +28,13 @@
 #include <cstdint>
 
 #include "../../include/pdmp_detmath.h"
+#include "pdmp_device.hpp"
 #include "pdmp_engine.hpp"
 
 namespace pdmp {
 
-#define X_INF __builtin_inf()
-#define X_ORDER()                        \
-    do {                                 \
-        __builtin_amdgcn_wave_barrier(); \
-        asm volatile("" ::: "memory");   \
-    } while (0)
-
 namespace {
 
-__device__ __forceinline__ double x_readlane(double v, int srclane) {
-    int lo = __builtin_amdgcn_readlane(__double2loint(v), srclane);
-    int hi = __builtin_amdgcn_readlane(__double2hiint(v), srclane);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double x_uniform(double v) {
-    int lo = __builtin_amdgcn_readfirstlane(__double2loint(v));
-    int hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
-    return __hiloint2double(hi, lo);
-}
-template <int CTRL>
-__device__ __forceinline__ double x_dpp(double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, true);
-    hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double x_min(double a, double b) {
-    double r;
-    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ double x_wave_min(double v) {
-    v = x_min(v, x_dpp<0xB1>(v));
-    v = x_min(v, x_dpp<0x4E>(v));
-    v = x_min(v, x_dpp<0x141>(v));
-    v = x_min(v, x_dpp<0x140>(v));
-    v = x_min(v, x_dpp<0x142>(v));
-    v = x_min(v, x_dpp<0x143>(v));
-    return x_readlane(v, 63);
-}
-__device__ __forceinline__ double x_grp8_min(double v) {  // minimum over the 8 lanes of a group, in every lane of the group
-    v = x_min(v, x_dpp<0xB1>(v));
-    v = x_min(v, x_dpp<0x4E>(v));
-    v = x_min(v, x_dpp<0x141>(v));
-    return v;
-}
-__device__ __forceinline__ double x_pos(double x) {
-    return (x > 0.0) ? x : ((x != x) ? x : 0.0);
-}
-__device__ __forceinline__ double x_poisson_time_L(double a, double b, double L) {  // src/poissontime.jl:8-30 with L = log(u)
-    if (b == 0) return (a > 0) ? -L / a : X_INF;
-    const double r = a / b;
-    const double q = L * 2.0 / b;
-    const double sq = sqrt((b > 0 && a < 0) ? -q : r * r - q);
-    if (b > 0) return sq - r;
-    if (a <= 0) return X_INF;
-    if (-L <= -(a * a) / b + (a * a) / (2 * b)) return -sq - r;
-    return X_INF;
-}
-__device__ __forceinline__ double x_below(double x) {  // the largest double below a finite x
-    long long b = __double_as_longlong(x);
-    if (x > 0) b -= 1;
-    else if (x < 0) b += 1;
-    else b = (long long)0x8000000000000001ull;
-    return __longlong_as_double(b);
-}
-template <int CTRL, int ROWM, int BANKM>
-__device__ __forceinline__ uint32_t x_dpp_id_u32(uint32_t identity, uint32_t src) {
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)identity, (int)src, CTRL, ROWM, BANKM, false);
-}
-__device__ __forceinline__ uint32_t x_scan_add_u32(uint32_t v) {  // inclusive
-    uint32_t x = v;
-    x += x_dpp_id_u32<0x111, 0xf, 0xf>(0u, v);
-    x += x_dpp_id_u32<0x112, 0xf, 0xf>(0u, v);
-    x += x_dpp_id_u32<0x113, 0xf, 0xf>(0u, v);
-    x += x_dpp_id_u32<0x114, 0xf, 0xe>(0u, x);
-    x += x_dpp_id_u32<0x118, 0xf, 0xc>(0u, x);
-    x += x_dpp_id_u32<0x142, 0xa, 0xf>(0u, x);
-    x += x_dpp_id_u32<0x143, 0xc, 0xf>(0u, x);
-    return x;
-}
-template <int CTRL, int ROWM, int BANKM>
-__device__ __forceinline__ double x_dpp_inf(double src) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(src), CTRL, ROWM, BANKM, false);
-    const int hi = __builtin_amdgcn_update_dpp(0x7FF00000, __double2hiint(src), CTRL, ROWM, BANKM, false);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double x_scan_min_f64(double v) {  // inclusive
-    double x = v;
-    x = x_min(x, x_dpp_inf<0x111, 0xf, 0xf>(v));
-    x = x_min(x, x_dpp_inf<0x112, 0xf, 0xf>(v));
-    x = x_min(x, x_dpp_inf<0x113, 0xf, 0xf>(v));
-    x = x_min(x, x_dpp_inf<0x114, 0xf, 0xe>(x));
-    x = x_min(x, x_dpp_inf<0x118, 0xf, 0xc>(x));
-    x = x_min(x, x_dpp_inf<0x142, 0xa, 0xf>(x));
-    x = x_min(x, x_dpp_inf<0x143, 0xc, 0xf>(x));
-    return x;
-}
-__device__ __forceinline__ double x_shfl(double v, uint32_t src) {
-    const int lo = __builtin_amdgcn_ds_bpermute((int)(src << 2), __double2loint(v));
-    const int hi = __builtin_amdgcn_ds_bpermute((int)(src << 2), __double2hiint(v));
-    return __hiloint2double(hi, lo);
-}
 __device__ __forceinline__ uint32_t x_shfl_u32(uint32_t v, uint32_t src) {
     return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(src << 2), (int)v);
 }
@@ -153,7 +53,7 @@ __device__ __forceinline__ uint32_t q_thr(double tau, double tb) {  // the large
     return __float_as_uint((float)dlt) + 1u;
 }
 __device__ __forceinline__ double q_dec(uint32_t bits, double tb) {
-    return x_below(tb + (double)__uint_as_float(bits & ~15u));
+    return pdmp_below(tb + (double)__uint_as_float(bits & ~15u));
 }
 constexpr uint32_t Q_INFBITS = 0x7f7ffff0u;  // patterns from here on: the block is empty (+Inf)
 
@@ -230,9 +130,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         for (uint32_t b = lane; b < nblk; b += 64) {
             const double* p = keys + (size_t)b * 16;
 #pragma unroll
-            for (int q = 0; q < 16; ++q) mloc = x_min(mloc, p[q]);
+            for (int q = 0; q < 16; ++q) mloc = min_f64(mloc, p[q]);
         }
-        tb = x_wave_min(mloc);
+        tb = wave_min_f64(mloc);
     }
     for (uint32_t b = lane; b < X_NBLK; b += 64) {
         uint32_t e = Q_INFBITS;
@@ -248,11 +148,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                     mi = q;
                 }
             }
-            e = (mk < X_INF) ? q_enc(mk, tb, mi) : Q_INFBITS;
+            e = (mk < PDMP_INF) ? q_enc(mk, tb, mi) : Q_INFBITS;
         }
         lbf[b] = e;
     }
-    X_ORDER();
+    PDMP_LDS_ORDER();
 
 #ifdef X_PHASES
     uint64_t ph[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -312,7 +212,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             }
         }
         auto draw = [&](uint32_t n) -> double {  // draw nm0 + n for dnm <= n < dnm + 128 (every lane calls it)
-            const double v0 = x_shfl(ureg[0], n & 63u), v1 = x_shfl(ureg[1], n & 63u);
+            const double v0 = bperm_f64(ureg[0], n & 63u), v1 = bperm_f64(ureg[1], n & 63u);
             return ((n >> 6) & 1u) ? v1 : v0;
         };
         X_PH(0);
@@ -359,20 +259,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                 }
                 mqb = mloc;
                 mql = q_dec(mqb, tb);
-                X_ORDER();
+                PDMP_LDS_ORDER();
             }
             if (mqb >= Q_INFBITS) {
                 stalled = true;
             } else if (stop_before && !(mql < T)) {
                 finished = true;
             } else {
-                double dt_sel = x_uniform(SELDT[0]);
+                double dt_sel = uniform_f64(SELDT[0]);
                 uint32_t cm = 0, ncl = 0, incl = 0;
                 for (int tries = 0;; ++tries) {
                     tau = mql + dt_sel;
                     tau_clipped = false;
                     if (stop_before && !(tau < T)) {
-                        tau = x_below(T);
+                        tau = pdmp_below(T);
                         tau_clipped = true;
                     }
                     if (tries >= 64) tau = mql;
@@ -381,7 +281,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 #pragma unroll
                     for (int j = 15; j >= 0; --j) cm = cm + cm + ((kk[j] <= thr) ? 1u : 0u);
                     ncl = (uint32_t)__builtin_popcount(cm);
-                    incl = x_scan_add_u32(ncl);
+                    incl = scan_add_u32(ncl);
                     Cc = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
                     if (Cc <= (uint32_t)X_CMAX || tries >= 64) break;
                     dt_sel *= 0.5;
@@ -405,7 +305,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             break;
         }
         if (finished) break;
-        X_ORDER();
+        PDMP_LDS_ORDER();
         const bool crowded = Cc > (uint32_t)X_CMAX;
         if (crowded) Cc = (uint32_t)X_CMAX;
         X_PH(1);
@@ -449,7 +349,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const int e = 8 * (p0 + q) + g;
-                    k2[q] = make_double2(X_INF, X_INF);
+                    k2[q] = make_double2(PDMP_INF, PDMP_INF);
                     if (e < (int)Cc) k2[q] = *reinterpret_cast<const double2*>(keys + (size_t)TB[e] * 16 + 2 * gl);
                 }
 #pragma unroll
@@ -459,7 +359,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                     const double ka = k2[q].x, kb = k2[q].y;  // positions 2 gl and 2 gl + 1
                     const bool bfirst = kb < ka;              // (ties: the lower position)
                     const double lm = bfirst ? kb : ka;
-                    const double gm = x_grp8_min(lm);
+                    const double gm = grp8_min_f64(lm);
                     const uint64_t winball = __ballot(lm == gm);
                     const int wl = __ffs((unsigned)((winball >> (8 * g)) & 0xffu)) - 1;  // (>= 0)
                     const uint32_t wpos = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(((uint32_t)(lane & ~7) + (uint32_t)wl) << 2),
@@ -467,7 +367,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                     // the rest: the winner's lane offers its other key
                     const double lr = (gl == wl) ? (bfirst ? ka : kb) : lm;
                     const uint32_t lrpos = (gl == wl) ? (2u * (uint32_t)gl + (bfirst ? 0u : 1u)) : (2u * (uint32_t)gl + (bfirst ? 1u : 0u));
-                    const double gr = x_grp8_min(lr);
+                    const double gr = grp8_min_f64(lr);
                     const uint64_t rball = __ballot(lr == gr);
                     const int rl = __ffs((unsigned)((rball >> (8 * g)) & 0xffu)) - 1;
                     const uint32_t rpos = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(((uint32_t)(lane & ~7) + (uint32_t)(rl < 0 ? 0 : rl)) << 2), (int)lrpos);
@@ -479,43 +379,43 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                 }
             }
         }
-        X_ORDER();
+        PDMP_LDS_ORDER();
         X_PH(2);
         // ---------------- events = candidates whose exact minimum is within the threshold; everybody refreshes its bound
-        const double c_km = isc ? KM[lane] : X_INF;
+        const double c_km = isc ? KM[lane] : PDMP_INF;
         const uint32_t c_pb = isc ? (uint32_t)PB[lane] : 0u;
-        if (isc) lbf[cblk] = (c_km < X_INF) ? q_enc(c_km, tb, c_pb & 15u) : Q_INFBITS;
+        if (isc) lbf[cblk] = (c_km < PDMP_INF) ? q_enc(c_km, tb, c_pb & 15u) : Q_INFBITS;
         bool isev = isc && c_km <= tau;
         if (crowded) {
             isev = false;
             need_rebase = true;
         }
-        const double own = isev ? c_km : X_INF;
+        const double own = isev ? c_km : PDMP_INF;
         uint32_t rank = 0;
         for (uint32_t m0 = 0; m0 < Cc; m0 += 4) {
 #pragma unroll
             for (uint32_t q = 0; q < 4; ++q) {
-                const double km = x_readlane(own, (int)(m0 + q));
+                const double km = readlane_f64(own, (int)(m0 + q));
                 rank += (km < own) ? 1u : 0u;
             }
         }
         const uint64_t evb = __ballot(isev);
         int nev = __popcll(evb);
         if (isev) RO[rank] = (uint8_t)lane;
-        X_ORDER();
+        PDMP_LDS_ORDER();
         const bool dup = isev && RO[rank] != (uint8_t)lane;
         if (__ballot(dup) != 0) {
             // exactly equal keys among the events: one event this iteration, the tied minimum of the lowest block (= lowest coordinate)
-            const double mn = x_wave_min(own);
+            const double mn = wave_min_f64(own);
             uint32_t bsel = (isev && own == mn) ? cblk : 0xffffffffu;
             for (int off = 32; off >= 1; off >>= 1) {
                 const uint32_t o = (uint32_t)__shfl_xor((int)bsel, off, 64);
                 bsel = (o < bsel) ? o : bsel;
             }
-            X_ORDER();
+            PDMP_LDS_ORDER();
             if (isev && cblk == bsel) RO[0] = (uint8_t)lane;
             nev = 1;
-            X_ORDER();
+            PDMP_LDS_ORDER();
         }
         {
             const bool wrongpos = isev && (c_pb & 15u) != cpos;  // the records were requested at another position: the list ends there
@@ -538,7 +438,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                 break;
             }
             if (lane == 0) SELDT[0] = dt_used * 2.0;
-            X_ORDER();
+            PDMP_LDS_ORDER();
             continue;
         }
         X_PH(3);
@@ -549,7 +449,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         const bool evc0 = isev && rank < (uint32_t)C;  // (rank < C: the records were requested at the right position)
         const uint32_t i = ci;
         const double tp = c_km;
-        const double rest = isc ? RS[lane] : X_INF;
+        const double rest = isc ? RS[lane] : PDMP_INF;
         const uint32_t rarg = cblk * 16u + (c_pb >> 4);
         const double th = cS0.y;
         const double told_i = cS2.x, a_i = cS2.y, b_i = b_own;
@@ -585,8 +485,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             X_TERM(hasD, cD0, cD1);
             X_TERM(hasR, cR0, cR1);
 #undef X_TERM
-            l_c = x_pos(gsum * th);
-            lb_c = x_pos(a_i + b_i * (tp - told_i));
+            l_c = pos_part(gsum * th);
+            lb_c = pos_part(a_i + b_i * (tp - told_i));
             a2 = kA.x + gsum * th;  // ab of a rejected proposal (src/fact_samplers.jl:50-54)
             b2 = kA.y + th * s2;
         }
@@ -594,18 +494,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         // ---------------- rank space
         const bool evq0 = lane < C;
         const uint32_t srcq = evq0 ? (uint32_t)RO[lane] : 0u;
-        const double l = x_shfl(l_c, srcq), lbound = x_shfl(lb_c, srcq);
+        const double l = bperm_f64(l_c, srcq), lbound = bperm_f64(lb_c, srcq);
         const uint32_t k_i = x_shfl_u32(k_c, srcq);
         const uint32_t rc_b = x_shfl_u32(rc_c, srcq);
         const uint32_t rc_i = evq0 ? rc_b : 0xffffu;
-        const double tpq = evq0 ? KM[srcq] : X_INF;
+        const double tpq = evq0 ? KM[srcq] : PDMP_INF;
         bool ev = evq0;
         // accept chain: offsets and outcomes as a fix-point
         uint32_t cost = ev ? 2u : 0u;
         uint32_t off = 0;
         bool acc = false;
         for (int round = 0; round < 66; ++round) {
-            const uint32_t incl = x_scan_add_u32(cost);
+            const uint32_t incl = scan_add_u32(cost);
             off = incl - cost;
             const bool inwin = ev && (off + 1u + k_i <= X_WIN);
             const double u = draw(dnm + ((off < 127u) ? off : 127u));
@@ -664,16 +564,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         const uint64_t accball = __ballot(acc);  // (bit q: the event of RANK q is accepted)
         const int nacc_it = __popcll(accball);
         if (acc) ACL[__popcll(accball & ((1ull << lane) - 1ull))] = (uint16_t)lane;
-        X_ORDER();
+        PDMP_LDS_ORDER();
         // ---------------- back in the candidates' lanes: the outcome of the own event, its draw offset
         const uint32_t off_c = x_shfl_u32(off, (rank < 64u) ? rank : 0u);
         const bool evc = isev && rank < (uint32_t)C;
         const bool acc_c = evc && ((accball >> rank) & 1ull) != 0;
         // a rejected proposal's new bound (:137-140): ab from the moved neighbourhood (src/fact_samplers.jl:50-54)
-        double key2 = X_INF;
+        double key2 = PDMP_INF;
         {
             const double ur = draw(dnm + ((off_c + 1u < 127u) ? off_c + 1u : 127u));  // (every lane takes part in the ring's ds_bpermute)
-            if (evc && !acc_c) key2 = tp + x_poisson_time_L(a2, b2, pdmp_log(ur));
+            if (evc && !acc_c) key2 = tp + poisson_time_L(a2, b2, pdmp_log(ur));
         }
         X_PH(5);
         // ---------------- accepted events, one 8-lane group each (the LAST nacc_it groups of the wave, in event order)
@@ -686,14 +586,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         const uint32_t offa = x_shfl_u32(off, ea);
         const uint32_t blka_b = x_shfl_u32(cblk, la);
         const uint32_t blka = gact ? blka_b : 0u;
-        const double tpa = x_shfl(tp, la);
-        const double resta_b = x_shfl(rest, la);
+        const double tpa = bperm_f64(tp, la);
+        const double resta_b = bperm_f64(rest, la);
         const uint32_t rarga_b = x_shfl_u32(rarg, la);
         const uint32_t cola = __umulhi(ia, nmagic), rowa = ia - cola * nlat;
         // the 13 members of S[ia], two per lane: window offsets (dc, dr) with |dc| + |dr| <= 2, inside the grid.  Everything is COMPUTED here
         // (records read, moved values in registers, (x, θ) of the window staged in LDS, the members' new bounds and keys); nothing is stored
         // before the commit prefix is known.
-        double keyj = X_INF, aj = 0.0, bj = 0.0;
+        double keyj = PDMP_INF, aj = 0.0, bj = 0.0;
         uint32_t jmem = 0;
         bool memb = false;
         double zx[2] = {0.0, 0.0}, zI[2] = {0.0, 0.0}, zth = 0.0;
@@ -740,7 +640,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                     ZS[(dc + 2) * 5 + (dr + 2)] = make_double2(xn, self ? -v0.y : v0.y);
                 }
             }
-            X_ORDER();
+            PDMP_LDS_ORDER();
             // Γ[:,j]·x, Γ[:,j]·θ over G1[j] in ascending order, from the staged window
             // rank of this member among the present ones = its draw (:131-135: one uniform per member, ascending)
             const uint32_t rk = (uint32_t)((gl > 0 && cola > 0u) ? 1 : 0) + (uint32_t)((gl > 1 && rowa > 0u) ? 1 : 0) + (uint32_t)((gl > 2) ? 1 : 0) +
@@ -767,11 +667,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                 const double thj = ZS[(dcm + 2) * 5 + (drm + 2)].y;
                 aj = jA.x + s1j * thj;  // src/fact_samplers.jl:51
                 bj = jA.y + thj * s2j;  // :52
-                keyj = tpa + x_poisson_time_L(aj, bj, pdmp_log(uj));
+                keyj = tpa + poisson_time_L(aj, bj, pdmp_log(uj));
             }
         }
         // new minimum of the popped block of a rejected event, and what the event exposes
-        double rowmin = X_INF;
+        double rowmin = PDMP_INF;
         uint32_t cand = i;
         if (evc && !acc_c) {
             const bool mine = key2 < rest || (key2 == rest && i < rarg);
@@ -780,29 +680,29 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         }
         // the accepted event's block: a LOWER BOUND of its new minimum is enough (level 1 holds bounds): the smaller of the block without the
         // event -- which may still count a member's OLD key: then the bound is stale low and costs a look later -- and the members' new keys in it
-        double rowmin_a = X_INF;
+        double rowmin_a = PDMP_INF;
         uint32_t cand_a = 0;
         {
-            const double kin = (memb && (jmem >> 4) == blka) ? keyj : X_INF;
-            const double kinmin = x_grp8_min(kin);
+            const double kin = (memb && (jmem >> 4) == blka) ? keyj : PDMP_INF;
+            const double kinmin = grp8_min_f64(kin);
             const uint64_t winball = __ballot(gact && kin == kinmin);
             const int wl = __ffs((unsigned)((winball >> (8 * g)) & 0xffu)) - 1;
             const uint32_t jwin = x_shfl_u32(jmem, (uint32_t)(lane & ~7) + (uint32_t)(wl < 0 ? 0 : wl));
             const bool restwins = resta_b <= kinmin;
             rowmin_a = restwins ? resta_b : kinmin;
             cand_a = restwins ? (rarga_b & 15u) : (jwin & 15u);
-            const double keymin = x_grp8_min(memb ? keyj : X_INF);
-            if (gact && gl == 0) EX[ea] = x_min(rowmin_a, keymin);
+            const double keymin = grp8_min_f64(memb ? keyj : PDMP_INF);
+            if (gact && gl == 0) EX[ea] = min_f64(rowmin_a, keymin);
         }
         if (evc && !acc_c) EX[rank] = rowmin;  // (by rank; rowmin <= key2: the new key is one of its candidates)
-        X_ORDER();
+        PDMP_LDS_ORDER();
         X_PH(6);
         // ---------------- validate: nothing produced or exposed by the earlier events comes before t′ (zone conflicts ended the list already)
         uint32_t Rc;
         {
-            const double expo = ev ? EX[lane] : X_INF;
-            const double prev = x_shfl(expo, (uint32_t)((lane > 0) ? lane - 1 : 0));
-            const double pref = x_scan_min_f64((lane > 0) ? prev : X_INF);  // exclusive prefix minimum
+            const double expo = ev ? EX[lane] : PDMP_INF;
+            const double prev = bperm_f64(expo, (uint32_t)((lane > 0) ? lane - 1 : 0));
+            const double pref = scan_min_f64((lane > 0) ? prev : PDMP_INF);  // exclusive prefix minimum
             const bool okr = ev && (lane == 0 || pref > tpq);
             const uint64_t bad = ~__ballot(okr);
             const uint32_t r_ok = bad ? (uint32_t)(__ffsll((unsigned long long)bad) - 1) : 64u;
@@ -821,7 +721,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                     status = PDMP_CHAIN_TRACE_FULL;
                     stopped = true;
                 }
-                if (!stop_before && !(x_readlane(tpq, r) < T)) {
+                if (!stop_before && !(readlane_f64(tpq, r) < T)) {
                     running = false;
                     stopped = true;
                 }
@@ -851,7 +751,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             *reinterpret_cast<double2*>(&wS->t_old) = make_double2(tp, a2);
             wS->b = b2;
             keys[i] = key2;
-            lbf[cblk] = (rowmin < X_INF) ? q_enc(rowmin, tb, cand & 15u) : Q_INFBITS;
+            lbf[cblk] = (rowmin < PDMP_INF) ? q_enc(rowmin, tb, cand & 15u) : Q_INFBITS;
         }
         const bool gcommit = gact && ea < Rc;
         const uint64_t acc_cm = accball & ((Rc < 64u) ? ((1ull << Rc) - 1ull) : ~0ull);
@@ -884,16 +784,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                 w->b = bj;
                 keys[jmem] = keyj;
             }
-            if (gl == 0) lbf[blka] = (rowmin_a < X_INF) ? q_enc(rowmin_a, tb, cand_a) : Q_INFBITS;
+            if (gl == 0) lbf[blka] = (rowmin_a < PDMP_INF) ? q_enc(rowmin_a, tb, cand_a) : Q_INFBITS;
         }
-        X_ORDER();
+        PDMP_LDS_ORDER();
         // ---------------- bounds of the blocks of re-bounded neighbours: lowered where the new key is below them (an LDS atomic minimum); a key
         // that ROSE leaves its block's bound stale low, which costs a look at the block later and nothing else
         {
             const bool upd = gcommit && memb && (jmem >> 4) != blka;
-            if (upd && keyj < X_INF) atomicMin(&lbf[jmem >> 4], q_enc(keyj, tb, jmem & 15u));
+            if (upd && keyj < PDMP_INF) atomicMin(&lbf[jmem >> 4], q_enc(keyj, tb, jmem & 15u));
         }
-        X_ORDER();
+        PDMP_LDS_ORDER();
         X_PH(7);
         // ---------------- counters; the violating proposal itself (counted, acc bumped, then error(...), :120-124)
         st_commit += Rc;
@@ -904,8 +804,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             idle = 0;
             dnacc += (uint32_t)__popcll(acc_cm);
             dnm += offL + costL;
-            t_last = x_readlane(tpq, (int)(Rc - 1u));
-            if (acc_cm) t_event = x_readlane(tpq, 63 - __builtin_clzll(acc_cm));
+            t_last = readlane_f64(tpq, (int)(Rc - 1u));
+            if (acc_cm) t_event = readlane_f64(tpq, 63 - __builtin_clzll(acc_cm));
         }
         if (vsel >= 0) {  // (vsel == Rc: every earlier event is committed)
             // the reference moved G[i] (:82) and counted the proposal before it threw (:120-124); acc[i] -- bumped there too, and gone with
@@ -920,11 +820,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             dnum += 1;
             vnacc = 1;
             dnm += 1;  // its coin
-            t_last = x_readlane(tpq, vsel);
+            t_last = readlane_f64(tpq, vsel);
             status = PDMP_CHAIN_BOUND_VIOLATED;
         }
         if (status != PDMP_CHAIN_OK) break;
-        X_ORDER();
+        PDMP_LDS_ORDER();
     }
 
     if (P.dbg && chain == 0 && lane == 0) {
@@ -963,13 +863,13 @@ int launch_zz_local_exactp(const ZzRunParams& p, int64_t nchains, void* stream) 
 }
 
 #ifdef PDMP_EXTRA_KERNELS
-// pdmp_debug_math_eval: this unit's own copies, called as they are
+// pdmp_debug_math_eval: the shared scalars (pdmp_device.hpp) this unit calls, as compiled here
 namespace {
 struct ExactpMathEval {
     __device__ double operator()(int fn, double a, double b, double c, double*) const {
         switch (fn) {
-        case PDMP_MATH_PT_X_L: return x_poisson_time_L(a, b, pdmp_log(c));
-        default: return x_pos(a);  // PDMP_MATH_POS_X
+        case PDMP_MATH_PT_X_L: return poisson_time_L(a, b, pdmp_log(c));
+        default: return pos_part(a);  // PDMP_MATH_POS_X
         }
     }
 };

@@ -13,87 +13,10 @@
 #include <cstdint>
 
 #include "../../include/pdmp_detmath.h"
+#include "pdmp_device.hpp"
 #include "pdmp_engine.hpp"
 
 namespace pdmp {
-
-#define G_INF __builtin_inf()
-#define G_ORDER()                        \
-    do {                                 \
-        __builtin_amdgcn_wave_barrier(); \
-        asm volatile("" ::: "memory");   \
-    } while (0)
-
-__device__ __forceinline__ double g_readlane(double v, int srclane) {
-    int lo = __builtin_amdgcn_readlane(__double2loint(v), srclane);
-    int hi = __builtin_amdgcn_readlane(__double2hiint(v), srclane);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ uint32_t g_uniform(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
-}
-template <int CTRL>
-__device__ __forceinline__ double g_dpp(double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, true);  // every lane has a valid source: no tied `old` operand, no copies
-    hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-// one v_min_f64 (fmin() would canonicalise each loaded / DPP-moved operand with a v_max_f64 x, x first); NaN loses
-__device__ __forceinline__ double g_min(double a, double b) {
-    double r;
-    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-// row steps, then row_bcast:15 / row_bcast:31: lane 63 holds the minimum of the wave (the other lanes garbage)
-__device__ __forceinline__ double g_wave_min(double v) {
-    v = g_min(v, g_dpp<0xB1>(v));
-    v = g_min(v, g_dpp<0x4E>(v));
-    v = g_min(v, g_dpp<0x141>(v));
-    v = g_min(v, g_dpp<0x140>(v));
-    v = g_min(v, g_dpp<0x142>(v));
-    v = g_min(v, g_dpp<0x143>(v));
-    return g_readlane(v, 63);
-}
-__device__ __forceinline__ double g_pos(double x) {
-    return (x > 0.0) ? x : ((x != x) ? x : 0.0);
-}
-// poisson_time(a, b, u), src/poissontime.jl:8-30
-__device__ __forceinline__ double g_poisson_time(double a, double b, double u) {
-    const double L = pdmp_log(u);
-    if (b > 0) {
-        const double r = a / b;
-        if (a < 0) return sqrt(-L * 2.0 / b) - r;
-        return sqrt(r * r - L * 2.0 / b) - r;
-    } else if (b == 0) {
-        return (a > 0) ? (-L / a) : G_INF;
-    } else {
-        if (a <= 0) return G_INF;
-        if (-L <= -(a * a) / b + (a * a) / (2 * b)) {
-            const double r = a / b;
-            return -sqrt(r * r - L * 2.0 / b) - r;
-        }
-        return G_INF;
-    }
-}
-// the same with L = log(u) already taken (the draw's index is known before the bound is: Philox and the logarithm run while
-// the dot products' operands are still on their way)
-__device__ __forceinline__ double g_poisson_time_L(double a, double b, double L) {
-    // the b != 0 formulas share a / b, L * 2 / b and the square root (sqrt(-L * 2.0 / b) == sqrt(-(L * 2.0 / b)) bit for bit):
-    // lanes that disagree on the signs of a and b run one division pair and one square root, not one set per branch
-    if (b == 0) return (a > 0) ? (-L / a) : G_INF;
-    const double r = a / b;
-    const double q = L * 2.0 / b;
-    const double sq = sqrt((b > 0 && a < 0) ? -q : r * r - q);
-    if (b > 0) return sq - r;
-    if (a <= 0) return G_INF;
-    if (-L <= -(a * a) / b + (a * a) / (2 * b)) return -sq - r;
-    return G_INF;
-}
-// sigmoid(x) = inv(one(x) + exp(-x)), scripts/logistic.jl:33
-__device__ __forceinline__ double g_sigmoid(double x) {
-    return 1.0 / (1.0 + pdmp_exp(-x));
-}
 
 #define G_PCH 128u  // (member, entry) products staged per chunk by the re-bound step
 #define G_PROW 65u  // doubles between the product lines of two sampled rows (ranged sweep)
@@ -206,12 +129,12 @@ __global__ __launch_bounds__(64) void zz_general_run_kernel(ZzRunParams P_in, Zz
         bk[b] = mk;
         bi[b] = b * 64 + mi;
     }
-    G_ORDER();
+    PDMP_LDS_ORDER();
 
     // level 1 of the queue after keys[] of G1[i][jj0 .. jj1) (and optionally of one extra coordinate) changed: every 64-key
     // block that holds a changed key is rescanned once (min, lowest index on ties -- the same pair the per-key update keeps)
     auto requeue = [&](uint32_t cp0, uint32_t jj0, uint32_t jj1, bool has_extra, uint32_t extra_j) {
-        G_ORDER();
+        PDMP_LDS_ORDER();
         const uint32_t cnt = jj1 - jj0 + (has_extra ? 1u : 0u);
         for (uint32_t base = 0; base < cnt; base += 64) {
             const uint32_t q = base + (uint32_t)lane;
@@ -224,7 +147,7 @@ __global__ __launch_bounds__(64) void zz_general_run_kernel(ZzRunParams P_in, Zz
                 const uint32_t bsel = (uint32_t)__builtin_amdgcn_readlane((int)bj, lead);
                 todo &= ~__ballot(bj == bsel);
                 const double kv = __hip_atomic_load(keys + (size_t)bsel * 64 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const double mn = g_wave_min(kv);
+                const double mn = wave_min_f64(kv);
                 const uint64_t bl = __ballot(kv == mn);
                 const int arg = bl ? (__ffsll((unsigned long long)bl) - 1) : 0;
                 if (lane == 0) {
@@ -233,7 +156,7 @@ __global__ __launch_bounds__(64) void zz_general_run_kernel(ZzRunParams P_in, Zz
                 }
             }
         }
-        G_ORDER();
+        PDMP_LDS_ORDER();
     };
     // move the members S[i][p0 .. p1) to time tp, write them back, stage (x, θ) by position
     auto move_members = [&](uint32_t sp0, uint32_t p0, uint32_t p1, double tp) {
@@ -271,7 +194,7 @@ __global__ __launch_bounds__(64) void zz_general_run_kernel(ZzRunParams P_in, Zz
                 }
             }
         }
-        G_ORDER();
+        PDMP_LDS_ORDER();
     };
     // G = All() (pdmp, src/sfact.jl:236): smove_forward!(t, x, θ, t′, F) over all d coordinates (:23-28, :37-48)
     auto move_everything = [&](double tp) {
@@ -297,7 +220,7 @@ __global__ __launch_bounds__(64) void zz_general_run_kernel(ZzRunParams P_in, Zz
                 }
             }
         }
-        G_ORDER();
+        PDMP_LDS_ORDER();
     };
     // stage members WITHOUT moving them (refresh branch: G1[i] is re-bounded at the coordinates' own clocks)
     auto stage_members = [&](uint32_t sp0, uint32_t p0, uint32_t p1) {
@@ -310,7 +233,7 @@ __global__ __launch_bounds__(64) void zz_general_run_kernel(ZzRunParams P_in, Zz
                 if (boom) smu[pp] = Q.mu[j];
             }
         }
-        G_ORDER();
+        PDMP_LDS_ORDER();
     };
     // ab + new event time for the members jj0 .. jj1 of G1[i]; own_clock: Q[j] = t[j] + ... at j's own (stale) clock.
     // The dot products Γ[:,j]·x, Γ[:,j]·θ keep idot's order (ascending row, src/common.jl:16-24) but their PRODUCTS are formed
@@ -345,7 +268,7 @@ __global__ __launch_bounds__(64) void zz_general_run_kernel(ZzRunParams P_in, Zz
             double s1 = 0.0, s2 = 0.0;  // ZigZag: Γ[:,j]·x, Γ[:,j]·θ; FactBoomerang: Σ (x−μ)² + θ²
             for (uint32_t cb = qs; cb < qe; cb += G_PCH) {
                 const uint32_t ce = (cb + G_PCH < qe) ? (cb + G_PCH) : qe;
-                G_ORDER();
+                PDMP_LDS_ORDER();
                 for (uint32_t f = cb + (uint32_t)lane; f < ce; f += 64) {
                     const uint32_t ps = Q.pos16[f];
                     if (!boom) {
@@ -357,7 +280,7 @@ __global__ __launch_bounds__(64) void zz_general_run_kernel(ZzRunParams P_in, Zz
                         px[f - cb] = dx * dx + sth[ps] * sth[ps];
                     }
                 }
-                G_ORDER();
+                PDMP_LDS_ORDER();
                 const uint32_t z0 = (q0 > cb) ? q0 : cb, z1 = (q0 + kj < ce) ? (q0 + kj) : ce;
                 // sequential sums; the LDS reads of 8 terms are issued together, the adds stay in order
                 uint32_t z = z0;
@@ -390,12 +313,12 @@ __global__ __launch_bounds__(64) void zz_general_run_kernel(ZzRunParams P_in, Zz
                     for (; z < z1; ++z) s1 += px[z - cb];
                 }
             }
-            G_ORDER();
+            PDMP_LDS_ORDER();
             if (live) {
                 const double cj = cvec[j];
                 const double xj = sx[jj], thj = sth[jj];
                 double a, b;
-                double hz = G_INF;
+                double hz = PDMP_INF;
                 if (local) {  // ab(G, j, x, θ, C::LocalBound, ∇ϕj, vj, Z), src/local.jl:2-6
                     const double gj = P.tb.gmu_t ? (s1 - P.tb.gmu_t[j]) : s1;
                     a = cj + gj * thj;
@@ -412,14 +335,14 @@ __global__ __launch_bounds__(64) void zz_general_run_kernel(ZzRunParams P_in, Zz
                 }
                 ZzRec* r = rec + j;
                 const double tj = own_clock ? H(j)->t : tp;
-                double dtn = g_poisson_time_L(a, b, Ldraw);
+                double dtn = poisson_time_L(a, b, Ldraw);
                 if (local) {  // next_time, src/not_fact_samplers.jl:43-50: the bound expires after its horizon
                     const bool rn = dtn > hz;
                     dtn = rn ? hz : dtn;
                     rnw[j] = rn ? 1.0 : 0.0;
                 }
                 if (sticky) {  // queue_time!, src/ss_fact.jl:54-66: the earlier of the reflection proposal and the hitting time of 0
-                    const double tfreeze = (thj * xj >= 0) ? G_INF : (-xj / thj);  // freezing_time, :10-16
+                    const double tfreeze = (thj * xj >= 0) ? PDMP_INF : (-xj / thj);  // freezing_time, :10-16
                     const bool fz = tfreeze <= dtn;
                     dtn = fz ? tfreeze : dtn;
                     r->acc = fz ? 1u : 0u;  // f[j]
@@ -442,7 +365,7 @@ __global__ __launch_bounds__(64) void zz_general_run_kernel(ZzRunParams P_in, Zz
             break;
         }
         // ---------------- peek(Q), src/sfact.jl:77
-        double mk = G_INF;
+        double mk = PDMP_INF;
         uint32_t mb = 0xffffffffu;
         for (uint32_t b = lane; b < nblk; b += 64) {
             const double v = bk[b];
@@ -451,8 +374,8 @@ __global__ __launch_bounds__(64) void zz_general_run_kernel(ZzRunParams P_in, Zz
                 mb = b;
             }
         }
-        const double tp = g_wave_min(mk);
-        if (!(tp < G_INF)) {
+        const double tp = wave_min_f64(mk);
+        if (!(tp < PDMP_INF)) {
             status = PDMP_CHAIN_STALLED;
             break;
         }
@@ -466,9 +389,9 @@ __global__ __launch_bounds__(64) void zz_general_run_kernel(ZzRunParams P_in, Zz
                 cand = (o < cand) ? o : cand;
             }
             (void)ball;
-            blk = g_uniform(cand);
+            blk = uniform_u32(cand);
         }
-        const uint32_t i = g_uniform(bi[blk]);
+        const uint32_t i = uniform_u32(bi[blk]);
         t_last = tp;
         GPHASE(0);
 
@@ -529,12 +452,12 @@ __global__ __launch_bounds__(64) void zz_general_run_kernel(ZzRunParams P_in, Zz
                 nm += 1;
             }
             if (sigc && lane == 0) sigc[i2] = sg2;
-            G_ORDER();
+            PDMP_LDS_ORDER();
             if (lane == 0) {
                 sth[self2] = thn;
                 H(i2)->th = thn;
             }
-            G_ORDER();
+            PDMP_LDS_ORDER();
             const double newref = tp + (-pdmp_log(pdmp_u01(seed, PDMP_STREAM_GLOBAL, ng))) / P.lambda_ref;  // :108
             ng += 1;
             reb_count = 0;
@@ -555,7 +478,7 @@ __global__ __launch_bounds__(64) void zz_general_run_kernel(ZzRunParams P_in, Zz
             nevents += 1;
             t_event = tp;
             if (!stop_before && !(tp < T)) running = false;
-            G_ORDER();
+            PDMP_LDS_ORDER();
             continue;
         }
         // ∇ϕmoving of the subsampled logistic target (SelfMoving: it moves what it reads); needs sx[self] = x[i] at t′
@@ -688,13 +611,13 @@ __global__ __launch_bounds__(64) void zz_general_run_kernel(ZzRunParams P_in, Zz
                                     }
                                 }
                             }
-                            G_ORDER();
+                            PDMP_LDS_ORDER();
                             for (int k2 = 0; k2 < 64; ++k2) {
                                 const bool more = k2 < mycnt;
                                 if (__ballot(more) == 0) break;
                                 if (more) urow += prodm[lane * G_PROW + k2];
                             }
-                            G_ORDER();
+                            PDMP_LDS_ORDER();
                         }
                     }
                 }
@@ -725,7 +648,7 @@ __global__ __launch_bounds__(64) void zz_general_run_kernel(ZzRunParams P_in, Zz
                         }
                         sprod[lane] = we * xe;
                     }
-                    G_ORDER();
+                    PDMP_LDS_ORDER();
                     // every lane continues the running sum of its row over the entries of this chunk, in entry order
                     {
                         const int z0 = (excl > fb) ? excl : fb, z1 = (incl < fb + 64) ? incl : (fb + 64);
@@ -735,19 +658,19 @@ __global__ __launch_bounds__(64) void zz_general_run_kernel(ZzRunParams P_in, Zz
                             urow = u;
                         }
                     }
-                    G_ORDER();
+                    PDMP_LDS_ORDER();
                 }
                 const double u = (ne > 0) ? urow : 0.0;
                 const double w = (double)l / (double)Q.ksub * v;
-                const double t1 = w * yr * g_sigmoid(-u);     // sigmoidn(u) = sigmoid(-u)
-                const double t2 = w * nyr * (-g_sigmoid(u));  // nsigmoid(u) = -sigmoid(u)
+                const double t1 = w * yr * sigmoid(-u);     // sigmoidn(u) = sigmoid(-u)
+                const double t2 = w * nyr * (-sigmoid(u));  // nsigmoid(u) = -sigmoid(u)
                 const double t3 = w * yr * sn0;               // sigmoidn(u0), u0 = idot(At, row, μ): tabulated per observation
                 const double t4 = w * nyr * ns0;              // nsigmoid(u0)
                 for (int z = 0; z < nq; ++z) {
-                    s += g_readlane(t1, z);
-                    s += g_readlane(t2, z);
-                    s -= g_readlane(t3, z);
-                    s -= g_readlane(t4, z);
+                    s += readlane_f64(t1, z);
+                    s += readlane_f64(t2, z);
+                    s -= readlane_f64(t3, z);
+                    s -= readlane_f64(t4, z);
                 }
             }
             ng += (uint64_t)Q.ksub;
@@ -756,8 +679,8 @@ __global__ __launch_bounds__(64) void zz_general_run_kernel(ZzRunParams P_in, Zz
         if (sticky) {
             // ---------------- sspdmp_inner!, src/ss_fact.jl:78-157, for neighbourhoods of any size
             const double x_i0 = H(i)->x, th_i0 = H(i)->th;
-            const bool is_freeze = g_uniform(acc_i != 0 ? 1u : 0u) != 0;  // f[i]: rec.acc holds the flag for sticky chains
-            const bool is_thaw = !is_freeze && g_uniform((x_i0 == 0 && th_i0 == 0) ? 1u : 0u) != 0;
+            const bool is_freeze = uniform_u32(acc_i != 0 ? 1u : 0u) != 0;  // f[i]: rec.acc holds the flag for sticky chains
+            const bool is_thaw = !is_freeze && uniform_u32((x_i0 == 0 && th_i0 == 0) ? 1u : 0u) != 0;
             bool emit = true;
             if (is_freeze) {  // case 1, :87-107
                 const double dt = tp - H(i)->t;
@@ -780,7 +703,7 @@ __global__ __launch_bounds__(64) void zz_general_run_kernel(ZzRunParams P_in, Zz
                     thf[i] = th_i0;
                     keys[i] = knew;
                 }
-                G_ORDER();
+                PDMP_LDS_ORDER();
                 if (!P.strong_upperbounds) {  // :97-107
                     move_members(sp0, 0, m, tp);  // G and G2, non-frozen only (i is frozen now)
                     reb_count = 0;
@@ -804,7 +727,7 @@ __global__ __launch_bounds__(64) void zz_general_run_kernel(ZzRunParams P_in, Zz
                     w->t_old = tp;  // :114
                     thf[i] = 0.0;
                 }
-                G_ORDER();
+                PDMP_LDS_ORDER();
                 move_members(sp0, 0, m, tp);  // :115-116 (i itself: dt = 0)
                 reb_count = 0;
                 rebound(cp0, 0, k, tp, nm + head, true, false);  // :117-123, non-frozen members including i
@@ -820,8 +743,8 @@ __global__ __launch_bounds__(64) void zz_general_run_kernel(ZzRunParams P_in, Zz
                     if (P.tb.gmu_t) g = g - P.tb.gmu_t[i];
                 }
                 const double th_i = sth[self];
-                const double l_rate = g_pos(g * th_i);
-                const double lbound = g_pos(a_i + b_i * (tp - told_i));  // :128
+                const double l_rate = pos_part(g * th_i);
+                const double lbound = pos_part(a_i + b_i * (tp - told_i));  // :128
                 num += 1;
                 const double coin = pdmp_u01(seed, PDMP_STREAM_MAIN, nm);
                 nm += 1;
@@ -841,7 +764,7 @@ __global__ __launch_bounds__(64) void zz_general_run_kernel(ZzRunParams P_in, Zz
                         sth[self] = -th_i;  // :139
                         H(i)->th = -th_i;
                     }
-                    G_ORDER();
+                    PDMP_LDS_ORDER();
                     reb_count = 0;
                     rebound(cp0, 0, k, tp, nm, true, false);  // :140-146
                     nm += reb_count;
@@ -855,7 +778,7 @@ __global__ __launch_bounds__(64) void zz_general_run_kernel(ZzRunParams P_in, Zz
                 }
             }
             if (emit) {  // push!(Ξ, event(i, t, x, θ, F)), :154
-                G_ORDER();
+                PDMP_LDS_ORDER();
                 if (ev && lane == 0) {
                     const ZzHot* w = H(i);
                     pdmp_event e;
@@ -870,7 +793,7 @@ __global__ __launch_bounds__(64) void zz_general_run_kernel(ZzRunParams P_in, Zz
                 t_event = tp;
                 if (!stop_before && !(tp < T)) running = false;
             }
-            G_ORDER();
+            PDMP_LDS_ORDER();
             continue;
         }
         if (P.move_all) {
@@ -880,12 +803,12 @@ __global__ __launch_bounds__(64) void zz_general_run_kernel(ZzRunParams P_in, Zz
             move_members(sp0, 0, k, tp);  // smove_forward!(G, i, ...), :82
         }
         const double ucoin = pdmp_u01(seed, PDMP_STREAM_MAIN, nm);  // thinning coin: its index is known before the gradient is
-        if (local && g_uniform((__hip_atomic_load(rnw + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0.0) ? 1u : 0u)) {
+        if (local && uniform_u32((__hip_atomic_load(rnw + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0.0) ? 1u : 0u)) {
             // src/local.jl:36-43: the bound of i expired -- renew it from the moved state (one draw), no proposal
             rebound(cp0, self, self + 1u, tp, nm, false, false);
             nm += 1;
             requeue(cp0, self, self + 1u, false, 0u);
-            G_ORDER();
+            PDMP_LDS_ORDER();
             continue;
         }
         GPHASE(1);
@@ -900,9 +823,9 @@ __global__ __launch_bounds__(64) void zz_general_run_kernel(ZzRunParams P_in, Zz
         }
         GPHASE(2);
         const double th_i = sth[self];
-        const double l_rate = boom ? g_pos((g - (sx[self] - Q.mu[i]) * Q.diag[i]) * th_i)  // src/fact_samplers.jl:37-39
-                                   : g_pos(g * th_i);                                        // :119
-        const double lbound = g_pos(a_i + b_i * (tp - told_i));     // :119
+        const double l_rate = boom ? pos_part((g - (sx[self] - Q.mu[i]) * Q.diag[i]) * th_i)  // src/fact_samplers.jl:37-39
+                                   : pos_part(g * th_i);                                      // :119
+        const double lbound = pos_part(a_i + b_i * (tp - told_i));                            // :119
         num += 1;
         nm += 1;  // the coin is draw nm (taken above, before the gradient), :121
         const bool accept = (ucoin * lbound < l_rate);
@@ -922,7 +845,7 @@ __global__ __launch_bounds__(64) void zz_general_run_kernel(ZzRunParams P_in, Zz
                 H(i)->th = -th_i;
                 rec[i].acc = acc_i + 1;
             }
-            G_ORDER();
+            PDMP_LDS_ORDER();
         }
         GPHASE(3);
         // ---------------- re-bound: all of G1[i] on accept (:131-135), i alone on reject (:137-139)
@@ -949,7 +872,7 @@ __global__ __launch_bounds__(64) void zz_general_run_kernel(ZzRunParams P_in, Zz
             t_event = tp;
             if (!stop_before && !(tp < T)) running = false;
         }
-        G_ORDER();
+        PDMP_LDS_ORDER();
         GPHASE(6);
     }
     if (PROF && chain == 0 && lane == 0 && P.dbg) {
@@ -1021,15 +944,15 @@ int launch_zz_general_run(const ZzRunParams& p, const ZzGeneralParams& q_in, int
 }
 
 #ifdef PDMP_EXTRA_KERNELS
-// pdmp_debug_math_eval: this unit's own copies, called as they are
+// pdmp_debug_math_eval: the shared scalars (pdmp_device.hpp) this unit calls, as compiled here
 namespace {
 struct GeneralMathEval {
     __device__ double operator()(int fn, double a, double b, double c, double*) const {
         switch (fn) {
-        case PDMP_MATH_PT_G: return g_poisson_time(a, b, c);
-        case PDMP_MATH_PT_G_L: return g_poisson_time_L(a, b, pdmp_log(c));
-        case PDMP_MATH_SIGMOID_G: return g_sigmoid(a);
-        default: return g_pos(a);  // PDMP_MATH_POS_G
+        case PDMP_MATH_PT_G: return poisson_time(a, b, c);
+        case PDMP_MATH_PT_G_L: return poisson_time_L(a, b, pdmp_log(c));
+        case PDMP_MATH_SIGMOID_G: return sigmoid(a);
+        default: return pos_part(a);  // PDMP_MATH_POS_G
         }
     }
 };

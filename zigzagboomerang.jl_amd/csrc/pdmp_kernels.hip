@@ -21,105 +21,24 @@
 #include <cstring>
 
 #include "../../include/pdmp_detmath.h"
+#include "pdmp_device.hpp"
 #include "pdmp_engine.hpp"
 
 namespace pdmp {
 
-#define PDMP_INF __builtin_inf()
-
 // ------------------------------------------------------------------------------------------ lane helpers
 
-__device__ __forceinline__ double readlane_f64(double v, int srclane) {
-    int lo = __builtin_amdgcn_readlane(__double2loint(v), srclane);
-    int hi = __builtin_amdgcn_readlane(__double2hiint(v), srclane);
-    return __hiloint2double(hi, lo);
-}
 __device__ __forceinline__ uint32_t readlane_u32(uint32_t v, int srclane) {
     return (uint32_t)__builtin_amdgcn_readlane((int)v, srclane);
 }
-__device__ __forceinline__ uint32_t uniform_u32(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
-}
-__device__ __forceinline__ double uniform_f64(double v) {
-    int lo = __builtin_amdgcn_readfirstlane(__double2loint(v));
-    int hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
-    return __hiloint2double(hi, lo);
-}
 
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, true);
-    hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-
-// One v_min_f64.  Written as the instruction itself: fmin() of a value that came out of a load or a DPP move is preceded by a
-// canonicalising v_max_f64 x, x per operand (IEEE-mode minnum lowering), i.e. three DP instructions per minimum in the queue
-// reductions.  Keys are never NaN unless a chain has diverged; v_min_f64 then returns the other operand (NaN loses, as +Inf).
-__device__ __forceinline__ double min_f64(double a, double b) {
-    double r;
-    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ double max_f64(double a, double b) {
-    double r;
-    asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-
-// Minimum over the 64 lanes, returned wave-uniform.  4 DPP steps inside each row of 16 lanes (quad xor-1, quad xor-2, half-row
-// mirror, row mirror), then row_bcast:15 (row r takes lane 15 of row r-1) and row_bcast:31 (rows 2, 3 take lane 31): lane 63 ends
-// with the minimum of the four rows.  Lanes that have no source read 0 and hold garbage afterwards; only lane 63 is read.
-__device__ __forceinline__ double wave_min_f64(double v) {
-    v = min_f64(v, dpp_f64<0xB1>(v));   // quad_perm [1,0,3,2]
-    v = min_f64(v, dpp_f64<0x4E>(v));   // quad_perm [2,3,0,1]
-    v = min_f64(v, dpp_f64<0x141>(v));  // row_half_mirror
-    v = min_f64(v, dpp_f64<0x140>(v));  // row_mirror
-    v = min_f64(v, dpp_f64<0x142>(v));  // row_bcast:15
-    v = min_f64(v, dpp_f64<0x143>(v));  // row_bcast:31
-    return readlane_f64(v, 63);
-}
-
+// (the __shfl_xor form; wave_min_u32_dpp of pdmp_device.hpp is the DPP one of the tracked kernels)
 __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
     for (int off = 32; off >= 1; off >>= 1) {
         uint32_t o = (uint32_t)__shfl_xor((int)v, off, 64);
         v = (o < v) ? o : v;
     }
     return uniform_u32(v);
-}
-
-// pos(x) = max(zero(x), x), src/common.jl:8
-__device__ __forceinline__ double pos_part(double x) {
-    return (x > 0.0) ? x : ((x != x) ? x : 0.0);
-}
-
-// poisson_time(a, b, u), src/poissontime.jl:8-30 (device restatement; the oracle has its own)
-__device__ __forceinline__ double dev_poisson_time(double a, double b, double u) {
-    const double L = pdmp_log(u);
-    if (b > 0) {
-        const double r = a / b;
-        if (a < 0) {
-            return sqrt(-L * 2.0 / b) - r;
-        } else {
-            return sqrt(r * r - L * 2.0 / b) - r;
-        }
-    } else if (b == 0) {
-        if (a > 0) {
-            return -L / a;
-        } else {
-            return PDMP_INF;
-        }
-    } else {
-        if (a <= 0) {
-            return PDMP_INF;
-        } else if (-L <= -(a * a) / b + (a * a) / (2 * b)) {
-            const double r = a / b;
-            return -sqrt(r * r - L * 2.0 / b) - r;
-        } else {
-            return PDMP_INF;
-        }
-    }
 }
 
 // ------------------------------------------------------------------------------------------ init kernel
@@ -183,12 +102,12 @@ __global__ __launch_bounds__(256) void zz_init_kernel(ZzInitParams P) {
             a = ci + gi * thi;
             b = ci / 100 + thi * ht;
             const double hz = 2.0 / ci / fabs(thi);
-            const double dt = dev_poisson_time(a, b, pdmp_u01(seed, PDMP_STREAM_MAIN, (uint64_t)i));
+            const double dt = poisson_time(a, b, pdmp_u01(seed, PDMP_STREAM_MAIN, (uint64_t)i));
             const bool rn = dt > hz;
             key = P.t0 + (rn ? hz : dt);
             P.thf[chain * d + i] = rn ? 1.0 : 0.0;
         } else {
-            key = dev_poisson_time(a, b, pdmp_u01(seed, PDMP_STREAM_MAIN, (uint64_t)i));  // :186
+            key = poisson_time(a, b, pdmp_u01(seed, PDMP_STREAM_MAIN, (uint64_t)i));  // :186
         }
         uint64_t fflag = 0;
         if (P.sticky) {
@@ -286,35 +205,11 @@ size_t zz_local_lds_bytes(uint32_t nblk_pad, uint32_t blob_w_pad) {
     return (size_t)nblk_pad * 8 + 3 * 64 * 8 + (size_t)blob_w_pad * 8 + (size_t)nblk_pad * 4;
 }
 
-// poisson_time(a, b, u) with L = log(u) supplied (src/poissontime.jl:8-30)
-__device__ __forceinline__ double dev_poisson_time_L(double a, double b, double L) {
-    // The three b != 0 formulas share a / b, L * 2 / b and the square root (sqrt(-L * 2.0 / b) is sqrt(-(L * 2.0 / b)) bit for
-    // bit), so a wavefront whose lanes disagree on the signs of a and b runs ONE division pair and ONE square root instead of
-    // one set per branch; only the admissibility test of the b < 0 branch keeps its own two divisions.
-    if (b == 0) return (a > 0) ? -L / a : PDMP_INF;
-    const double r = a / b;
-    const double q = L * 2.0 / b;
-    const double sq = sqrt((b > 0 && a < 0) ? -q : r * r - q);
-    if (b > 0) return sq - r;
-    if (a <= 0) return PDMP_INF;
-    if (-L <= -(a * a) / b + (a * a) / (2 * b)) return -sq - r;
-    return PDMP_INF;
-}
-
-// Cross-lane hand-off through LDS inside ONE wavefront: DS operations execute in issue order, so no s_barrier
-// and no s_waitcnt vmcnt(0) is needed -- but the COMPILER must be told that memory changed behind the thread's
-// back (otherwise it may forward a lane's own earlier store to its later load of the same slot).
-#define LDS_ORDER()                      \
-    do {                                 \
-        __builtin_amdgcn_wave_barrier(); \
-        asm volatile("" ::: "memory");   \
-    } while (0)
-
 // Level-1 entry (block minimum, argmin) of the block of coordinate j after keys[j] became kj: smaller than the entry -> replace;
 // j WAS the entry and grew -> rescan the 64 keys of the block (lowest index on ties); otherwise nothing to do.
 __device__ __forceinline__ void level1_update(double* bk, uint32_t* bi, const double* keys, int lane, uint32_t j, double kj) {
     const uint32_t bj = j >> 6;
-    LDS_ORDER();
+    PDMP_LDS_ORDER();
     const double cur = bk[bj];
     const uint32_t ci = bi[bj];
     if (kj < cur || (kj == cur && j < ci)) {
@@ -388,7 +283,7 @@ __global__ __launch_bounds__(64) void zz_local_run_kernel(ZzRunParams P) {
     // generic level-1 update for one changed key (j, kj) whose new value is already stored in keys[]
     auto queue_update = [&](uint32_t j, double kj) {
         level1_update(bk, bi, keys, lane, j, kj);
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
     };
 
     // ---- rebuild level 1 of the queue from the keys in HBM (each lane scans whole blocks)
@@ -407,7 +302,7 @@ __global__ __launch_bounds__(64) void zz_local_run_kernel(ZzRunParams P) {
         bk[b] = mk;
         bi[b] = b * 64 + mi;
     }
-    LDS_ORDER();
+    PDMP_LDS_ORDER();
 
     bool running = stop_before || (t_event < T);  // `while t′ < T`, src/sfact.jl:199
     PrioTurn prio;
@@ -454,7 +349,7 @@ __global__ __launch_bounds__(64) void zz_local_run_kernel(ZzRunParams P) {
             } else {
                 const uint64_t* bsrc = P.blob + (size_t)P.tix[i1] * P.blob_w_pad;
                 for (uint32_t w = lane; w < W; w += 64) lb[w] = bsrc[w];
-                LDS_ORDER();
+                PDMP_LDS_ORDER();
                 const int k1 = (int)uniform_u32((uint32_t)(lb[0] & 0xff));
                 if (lane < k1) {
                     const uint64_t sw = lb[1 + (lane >> 1)];
@@ -467,7 +362,7 @@ __global__ __launch_bounds__(64) void zz_local_run_kernel(ZzRunParams P) {
                     r1->t = tp;
                     r1->I = I0 + dt * ((x0 + xn) * 0.5);
                 }
-                LDS_ORDER();
+                PDMP_LDS_ORDER();
             }
             const uint32_t i2 = pdmp_randint(seed, PDMP_STREAM_GLOBAL, ng, (uint32_t)d);
             ng += 1;
@@ -475,7 +370,7 @@ __global__ __launch_bounds__(64) void zz_local_run_kernel(ZzRunParams P) {
                 const uint64_t* bsrc = P.blob + (size_t)P.tix[i2] * P.blob_w_pad;
                 for (uint32_t w = lane; w < W; w += 64) lb[w] = bsrc[w];
             }
-            LDS_ORDER();
+            PDMP_LDS_ORDER();
             const uint64_t hw = lb[0];
             const int k = (int)uniform_u32((uint32_t)(hw & 0xff));
             const int m = (int)uniform_u32((uint32_t)((hw >> 8) & 0xff));
@@ -511,7 +406,7 @@ __global__ __launch_bounds__(64) void zz_local_run_kernel(ZzRunParams P) {
                 sx[lane] = x;
                 sth[lane] = th;
             }
-            LDS_ORDER();
+            PDMP_LDS_ORDER();
             const uint32_t sub = 1 + SW + (uint32_t)lane * R;
             double key = PDMP_INF;
             if (lane < k) {  // :110-114
@@ -535,7 +430,7 @@ __global__ __launch_bounds__(64) void zz_local_run_kernel(ZzRunParams P) {
                 const double a = cj + (gx - gmu) * th;
                 const double b = cj / 100 + th * gt;
                 const double L = pdmp_log(pdmp_u01(seed, PDMP_STREAM_MAIN, nm + (uint64_t)lane));
-                key = t + dev_poisson_time_L(a, b, L);  // Q[j] = t[j] + poisson_time(...): t[j] is j's OWN clock here
+                key = t + poisson_time_L(a, b, L);  // Q[j] = t[j] + poisson_time(...): t[j] is j's OWN clock here
                 rs->t_old = t;
                 rs->a = a;
                 rs->b = b;
@@ -600,7 +495,7 @@ __global__ __launch_bounds__(64) void zz_local_run_kernel(ZzRunParams P) {
         const double L_reject = readlane_f64(Llane, 0);
 
         // ---------------- neighbourhood header and member list from the blob (now in LDS)
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         const uint64_t hw = lb[0];
         const int k = (int)uniform_u32((uint32_t)(hw & 0xff));
         const int m = (int)uniform_u32((uint32_t)((hw >> 8) & 0xff));
@@ -677,7 +572,7 @@ __global__ __launch_bounds__(64) void zz_local_run_kernel(ZzRunParams P) {
             sth[lane] = th;
         }
         pk[lane] = kb0;
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
 
         // ---------------- ab + new event time for j in G1[i] (accept, :131-135) or for i alone (reject, :137-139)
         const bool active = accept ? (lane < k) : (lane == self);
@@ -706,7 +601,7 @@ __global__ __launch_bounds__(64) void zz_local_run_kernel(ZzRunParams P) {
             const double a = cj + (gx - gmu) * th;  // src/fact_samplers.jl:51
             const double b = cj / 100 + th * gt;   // :52
             const double L = accept ? Llane : L_reject;
-            key = t + dev_poisson_time_L(a, b, L);  // Q[j] = t[j] + poisson_time(b[j], rand(rng))
+            key = t + poisson_time_L(a, b, L);  // Q[j] = t[j] + poisson_time(b[j], rand(rng))
             rs->t_old = t;                          // t_old[j] = t[j]
             rs->a = a;
             rs->b = b;
@@ -735,7 +630,7 @@ __global__ __launch_bounds__(64) void zz_local_run_kernel(ZzRunParams P) {
         if (accept && lane == self) rs->acc = acc_i + 1;
 
         // ---------------- queue: re-reduce the popped block from the patched copy
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         {
             const double kb = pk[lane];
             const double mn = wave_min_f64(kb);
@@ -753,7 +648,7 @@ __global__ __launch_bounds__(64) void zz_local_run_kernel(ZzRunParams P) {
                 const uint32_t bj = j >> 6;
                 if (bj == blk) continue;
                 const double kj = readlane_f64(key, jj);
-                LDS_ORDER();
+                PDMP_LDS_ORDER();
                 const double cur = bk[bj];
                 const uint32_t ci = bi[bj];
                 if (kj < cur || (kj == cur && j < ci)) {
@@ -791,7 +686,7 @@ __global__ __launch_bounds__(64) void zz_local_run_kernel(ZzRunParams P) {
             t_event = tp;
             if (!stop_before && !(tp < T)) running = false;  // `while t′ < T`
         }
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
     }
 
     if (lane == 0) {
@@ -872,11 +767,11 @@ __global__ __launch_bounds__(64) void zz_sticky_run_kernel(ZzRunParams P) {
         bk[b] = mk;
         bi[b] = b * 64 + mi;
     }
-    LDS_ORDER();
+    PDMP_LDS_ORDER();
 
     auto queue_update = [&](uint32_t j, double kj) {
         level1_update(bk, bi, keys, lane, j, kj);
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
     };
 
     bool running = stop_before || (t_event < T);
@@ -926,7 +821,7 @@ __global__ __launch_bounds__(64) void zz_sticky_run_kernel(ZzRunParams P) {
             UU[lane] = u;
             LU[lane] = pdmp_log(u);
         }
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         const uint64_t hw = lb[0];
         const int k = (int)uniform_u32((uint32_t)(hw & 0xff));
         const int m = (int)uniform_u32((uint32_t)((hw >> 8) & 0xff));
@@ -1043,7 +938,7 @@ __global__ __launch_bounds__(64) void zz_sticky_run_kernel(ZzRunParams P) {
             sx[lane] = x;
             sth[lane] = th;
         }
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         // ---------------- ab + queue_time! for the re-bound set, :54-65
         const uint64_t rball = __ballot(rebound_set);
         const uint32_t rank = (uint32_t)__popcll(rball & ((1ull << lane) - 1ull));
@@ -1072,7 +967,7 @@ __global__ __launch_bounds__(64) void zz_sticky_run_kernel(ZzRunParams P) {
             const double a = cj + (gx - gmu) * th;
             const double b = cj / 100 + th * gt;
             const double L = LU[ndraw0 + rank];
-            const double trefl = dev_poisson_time_L(a, b, L);
+            const double trefl = poisson_time_L(a, b, L);
             const double tfreeze = (th * x >= 0) ? PDMP_INF : (-x / th);  // freezing_time, :10-16
             const bool fz = tfreeze <= trefl;                              // :57
             key = t + (fz ? tfreeze : trefl);
@@ -1116,7 +1011,7 @@ __global__ __launch_bounds__(64) void zz_sticky_run_kernel(ZzRunParams P) {
             t_event = tp;
             if (!stop_before && !(tp < T)) running = false;
         }
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
     }
 
     if (lane == 0) {
@@ -1450,7 +1345,7 @@ __device__ __forceinline__ void zz_local_spec_body(const ZzRunParams& P_in) {
         bk[b] = mk;
         bi[b] = b * 64 + mi;
     }
-    LDS_ORDER();
+    PDMP_LDS_ORDER();
 
     uint32_t rng_base = 0xffffffffu;  // first draw (as a delta to nm0) held in U/LU; none yet
     uint64_t ph[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -1484,7 +1379,7 @@ __device__ __forceinline__ void zz_local_spec_body(const ZzRunParams& P_in) {
             if (first_inf) status = PDMP_CHAIN_STALLED;
             break;
         }
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         if (P.has_refresh) {
             // ---------------- the refresh clock (key d, src/sfact.jl:78-114) among the candidates: the events before it go through the speculative
             // iteration as usual; once it is the chain's NEXT event it is processed by itself, the whole wave on one event, exactly as
@@ -1507,7 +1402,7 @@ __device__ __forceinline__ void zz_local_spec_body(const ZzRunParams& P_in) {
                     {
                         const uint64_t* bsrc = P.blob + (size_t)P.tix[i1] * P.blob_w_pad;
                         for (uint32_t w = lane; w < P.blob_w; w += 64) lb0[w] = bsrc[w];
-                        LDS_ORDER();
+                        PDMP_LDS_ORDER();
                         const int k1 = (int)uniform_u32((uint32_t)(lb0[0] & 0xff));
                         if (lane < k1) {  // smove_forward!(G, i1, ...), :82
                             const uint64_t sw = lb0[1 + (lane >> 1)];
@@ -1520,7 +1415,7 @@ __device__ __forceinline__ void zz_local_spec_body(const ZzRunParams& P_in) {
                             r1->t = tp;
                             r1->I = I0 + dt * ((x0 + xn) * 0.5);
                         }
-                        LDS_ORDER();
+                        PDMP_LDS_ORDER();
                     }
                     const uint32_t i2 = pdmp_randint(seed, PDMP_STREAM_GLOBAL, ng, (uint32_t)d);  // :84
                     ng += 1;
@@ -1528,7 +1423,7 @@ __device__ __forceinline__ void zz_local_spec_body(const ZzRunParams& P_in) {
                         const uint64_t* bsrc = P.blob + (size_t)P.tix[i2] * P.blob_w_pad;
                         for (uint32_t w = lane; w < P.blob_w; w += 64) lb0[w] = bsrc[w];
                     }
-                    LDS_ORDER();
+                    PDMP_LDS_ORDER();
                     const uint64_t hw = lb0[0];
                     const int k = (int)uniform_u32((uint32_t)(hw & 0xff));
                     const int m = (int)uniform_u32((uint32_t)((hw >> 8) & 0xff));
@@ -1563,7 +1458,7 @@ __device__ __forceinline__ void zz_local_spec_body(const ZzRunParams& P_in) {
                         sx0[lane] = x;
                         sth0[lane] = th;
                     }
-                    LDS_ORDER();
+                    PDMP_LDS_ORDER();
                     const uint32_t sub0 = 1 + SW + (uint32_t)lane * R_;
                     double key = PDMP_INF;
                     if (lane < k) {  // :110-114 (at the coordinates' OWN, possibly stale, clocks: the reference's behaviour)
@@ -1587,7 +1482,7 @@ __device__ __forceinline__ void zz_local_spec_body(const ZzRunParams& P_in) {
                         const double a = cj + (gx - gmu) * th;
                         const double b = cj / 100 + th * gt;
                         const double L = pdmp_log(pdmp_u01(seed, PDMP_STREAM_MAIN, nm + 1 + (uint64_t)lane));
-                        key = t + dev_poisson_time_L(a, b, L);
+                        key = t + poisson_time_L(a, b, L);
                         rs->t_old = t;
                         rs->a = a;
                         rs->b = b;
@@ -1605,7 +1500,7 @@ __device__ __forceinline__ void zz_local_spec_body(const ZzRunParams& P_in) {
                         const uint32_t j = (jj < k) ? readlane_u32(s, jj) : (uint32_t)d;
                         const double kjv = (jj < k) ? readlane_f64(key, jj < k ? jj : 0) : newref;
                         level1_update(bk, bi, keys, lane, j, kjv);
-                        LDS_ORDER();
+                        PDMP_LDS_ORDER();
                     }
                     const double t_i = readlane_f64(t, self), x_i = readlane_f64(x, self), th_i2 = readlane_f64(th, self);
                     if (ev && lane == 0) {  // event(i, t, x, θ, F) = (t[i], i, x[i], θ[i]), :143
@@ -1619,7 +1514,7 @@ __device__ __forceinline__ void zz_local_spec_body(const ZzRunParams& P_in) {
                     dnref += 1;
                     t_event = tp;
                     if (!stop_before && !(tp < T)) running = false;
-                    LDS_ORDER();
+                    PDMP_LDS_ORDER();
                     continue;
                 }
             }
@@ -1651,7 +1546,7 @@ __device__ __forceinline__ void zz_local_spec_body(const ZzRunParams& P_in) {
             LU[lane] = pdmp_log(u);
         }
         const uint32_t rng_off = dnm - rng_base;
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         PHASE(1);
         // ---------------- neighbourhood header and member list
         int k = 0, m = 0, self = 0, kjmax = 0;
@@ -1722,7 +1617,7 @@ __device__ __forceinline__ void zz_local_spec_body(const ZzRunParams& P_in) {
         if (gvalid && gl < k) cj = cmut ? cmut[s] : __longlong_as_double((long long)lb[sub + 2]);
 
         // ---------------- zone conflicts with earlier groups (exact: compare member ids)
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         const uint64_t confball = WIDE ? __ballot(spec_zone_conflict_wide<E>(Z, s, s2, g, member, member2))
                                        : __ballot(spec_zone_conflict<E>(Z, s, g, member));
         PHASE(3);
@@ -1739,7 +1634,7 @@ __device__ __forceinline__ void zz_local_spec_body(const ZzRunParams& P_in) {
             sx[gl] = x;
             sth[gl] = th;
         }
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         {
             double gr = 0.0;
             for (uint32_t p = 0; p < KMAX; ++p) {
@@ -1757,7 +1652,7 @@ __device__ __forceinline__ void zz_local_spec_body(const ZzRunParams& P_in) {
                 }
             }
         }
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         // ---------------- accept chain in time order: every lane walks it (per-lane arithmetic on LDS broadcasts, no
         // scalar registers), keeping only its own group's outcome
         uint32_t accept_u = 0, violated_u = 0, myoff = 0;
@@ -1827,7 +1722,7 @@ __device__ __forceinline__ void zz_local_spec_body(const ZzRunParams& P_in) {
             pk2[0] = make_double2(kq[0], kq[1]);
             pk2[1] = make_double2(kq[2], kq[3]);
         }
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         // ---------------- re-bound (ab + poisson_time) -- results stay in registers until the commit
         const bool active = gvalid && (accept ? (gl < k) : (gl == self));
         double key = PDMP_INF, a = 0.0, b = 0.0;
@@ -1852,17 +1747,17 @@ __device__ __forceinline__ void zz_local_spec_body(const ZzRunParams& P_in) {
             a = cj + (gx - gmu) * th;
             b = cj / 100 + th * gt;
             const double L = LU[rng_off + myoff + 1 + (accept ? (uint32_t)gl : 0u)];
-            key = t + dev_poisson_time_L(a, b, L);
+            key = t + poisson_time_L(a, b, L);
             if (!WIDE && (s >> 6) == blk) pk[s & 63] = key;
         }
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         if (WIDE) {  // the patched key blocks go where sx / sth were: all their readers are done
             double2* pk2 = reinterpret_cast<double2*>(pk + gl * 4);
             pk2[0] = make_double2(kq[0], kq[1]);
             pk2[1] = make_double2(kq[2], kq[3]);
-            LDS_ORDER();
+            PDMP_LDS_ORDER();
             if (active && (s >> 6) == blk) pk[s & 63] = key;
-            LDS_ORDER();
+            PDMP_LDS_ORDER();
         }
         PHASE(5);
         // ---------------- patched minimum of the popped block, and everything this event could expose
@@ -1874,7 +1769,7 @@ __device__ __forceinline__ void zz_local_spec_body(const ZzRunParams& P_in) {
         const double keymin = row_min_f64(key);
         const double expose = min_f64(min_f64(rowmin, keymin), hidg);
         if (gl == 0) Mr[g] = expose;
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         // ---------------- validate: event g commits iff all earlier ones do, its zone is disjoint from theirs, and nothing
         // they produce or expose comes before it.  Per-lane evaluation + ballots; the prefix is resolved on the scalar unit.
         uint32_t Rc;
@@ -1967,7 +1862,7 @@ __device__ __forceinline__ void zz_local_spec_body(const ZzRunParams& P_in) {
                 ev[ntrace0 + dnacc + dnref + rank] = e;
             }
         }
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         PHASE(7);
         // ---------------- level-1 updates for re-bounded neighbours living in other blocks.  A block's final entry is the
         // smallest (key, coordinate) among its old entry and the new keys, whatever the order: when no two of these lanes aim at
@@ -1975,14 +1870,14 @@ __device__ __forceinline__ void zz_local_spec_body(const ZzRunParams& P_in) {
         // one LDS round trip; otherwise one by one in event order.
         const bool upd = commit && accept && gl < k && (s >> 6) != blk;
         if (__ballot(upd) != 0) {
-            LDS_ORDER();
+            PDMP_LDS_ORDER();
             const uint32_t bjv = upd ? (s >> 6) : 0u;
             const double curv = bk[bjv];
             const uint32_t civ = bi[bjv];
             const bool lower = upd && (key < curv || (key == curv && s < civ));
             const bool resc = upd && !lower && civ == s;
             if (lower) Z[bjv & 63u] = (uint32_t)lane;
-            LDS_ORDER();
+            PDMP_LDS_ORDER();
             const bool lost = lower && Z[bjv & 63u] != (uint32_t)lane;
             if (__ballot(lost || resc) == 0) {
                 if (lower) {
@@ -2027,7 +1922,7 @@ __device__ __forceinline__ void zz_local_spec_body(const ZzRunParams& P_in) {
         }
         if (vsel >= 0) t_last = uniform_f64(SLT[vsel]);  // the violating event's time is the chain's current time
         if (status != PDMP_CHAIN_OK) break;
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
     }
 
     if (PROF && P.dbg && chain == 0 && lane == 0) {
@@ -2111,27 +2006,6 @@ static_assert(S8_SLB + 8 * 4 <= S8_LB && (S8_LB % 16) == 0 && (S8_BK % 16) == 0 
               "LDS sub-arrays must stay 16-byte aligned");
 size_t zz_spec8_lds_bytes() { return S8_BYTES; }
 
-// the largest double below a finite x (x > 0, or x < 0, or x == 0 all handled by the integer image)
-__device__ __forceinline__ double pdmp_below(double x) {
-    long long b = __double_as_longlong(x);
-    if (x > 0) b -= 1;
-    else if (x < 0) b += 1;
-    else b = (long long)0x8000000000000001ull;  // -denorm_min
-    return __longlong_as_double(b);
-}
-// value of lane `src` (any lane, per-lane choice): two ds_bpermute_b32
-__device__ __forceinline__ double bperm_f64(double v, uint32_t src) {
-    const int lo = __builtin_amdgcn_ds_bpermute((int)(src << 2), __double2loint(v));
-    const int hi = __builtin_amdgcn_ds_bpermute((int)(src << 2), __double2hiint(v));
-    return __hiloint2double(hi, lo);
-}
-// minimum over the 8 lanes of a group, returned in every lane of the group
-__device__ __forceinline__ double grp8_min_f64(double v) {
-    v = min_f64(v, dpp_f64<0xB1>(v));
-    v = min_f64(v, dpp_f64<0x4E>(v));
-    v = min_f64(v, dpp_f64<0x141>(v));  // row_half_mirror: reverses each half row
-    return v;
-}
 __device__ __forceinline__ uint32_t umin3(uint32_t a, uint32_t b, uint32_t c) {
     const uint32_t ab = (a < b) ? a : b;
     return (ab < c) ? ab : c;  // v_min3_u32
@@ -2231,7 +2105,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         bk[b] = PDMP_INF;
         bi[b] = 0;
     }
-    LDS_ORDER();
+    PDMP_LDS_ORDER();
     if (has_refresh && lane == 0) __hip_atomic_store(keys + d, PDMP_INF, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 
     uint32_t rng_base = 0xffffffffu;
@@ -2316,10 +2190,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                     C = base;
                     if (C <= SEL_CAP) break;
                     dt_sel *= 0.5;
-                    LDS_ORDER();
+                    PDMP_LDS_ORDER();
                     if (lane < (int)SEL_CAP) TK[lane] = PDMP_INF;  // (entries past the new count must read +Inf in the ranking)
                 }
-                LDS_ORDER();
+                PDMP_LDS_ORDER();
                 // rank of candidate n among all (ties by index), on a 16 x 4 grid: lane = 16 * part + n counts the candidates
                 // 4 * part .. 4 * part + 3 that precede n; the four partial counts meet in LDS.  Unused entries hold +Inf.
                 {
@@ -2334,7 +2208,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                     pr += (o23.x < own || (o23.x == own && q + 2 < n)) ? 1u : 0u;
                     pr += (o23.y < own || (o23.y == own && q + 3 < n)) ? 1u : 0u;
                     PR[n * 4 + part] = pr;
-                    LDS_ORDER();
+                    PDMP_LDS_ORDER();
                     if ((uint32_t)lane < C) {
                         const uint4 p4 = reinterpret_cast<const uint4*>(PR)[lane];
                         const uint32_t rank = p4.x + p4.y + p4.z + p4.w;
@@ -2365,7 +2239,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             {
                 const uint64_t* bsrc = P.blob + (size_t)P.tix[i1] * WPAD;
                 if (lane < (int)WPAD) lb0[lane] = bsrc[lane];
-                LDS_ORDER();
+                PDMP_LDS_ORDER();
                 const int k1 = (int)uniform_u32((uint32_t)(lb0[0] & 0xff));
                 if (lane < k1) {  // smove_forward!(G, i1, ...), :82
                     const uint64_t sw = lb0[1 + (lane >> 1)];
@@ -2378,7 +2252,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                     r1->t = tp;
                     r1->I = I0 + dt * ((x0 + xn) * 0.5);
                 }
-                LDS_ORDER();
+                PDMP_LDS_ORDER();
             }
             const uint32_t i2 = pdmp_randint(seed, PDMP_STREAM_GLOBAL, ng, (uint32_t)d);
             ng += 1;
@@ -2386,7 +2260,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                 const uint64_t* bsrc = P.blob + (size_t)P.tix[i2] * WPAD;
                 if (lane < (int)WPAD) lb0[lane] = bsrc[lane];
             }
-            LDS_ORDER();
+            PDMP_LDS_ORDER();
             const uint64_t hw = lb0[0];
             const int k = (int)uniform_u32((uint32_t)(hw & 0xff));
             const int m = (int)uniform_u32((uint32_t)((hw >> 8) & 0xff));
@@ -2419,7 +2293,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                 sx0[lane] = x;
                 sth0[lane] = th;
             }
-            LDS_ORDER();
+            PDMP_LDS_ORDER();
             const uint32_t sub0 = 1 + SW + (uint32_t)lane * R_;
             double key = PDMP_INF;
             if (lane < k) {  // :110-114
@@ -2440,7 +2314,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                 const double a = cj + (gx - gmu) * th;
                 const double b = cj / 100 + th * gt;
                 const double L = pdmp_log(pdmp_u01(seed, PDMP_STREAM_MAIN, nm + 1 + (uint64_t)lane));
-                key = t + dev_poisson_time_L(a, b, L);
+                key = t + poisson_time_L(a, b, L);
                 rs->t_old = t;
                 rs->a = a;
                 rs->b = b;
@@ -2458,7 +2332,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                 const uint32_t j = readlane_u32(s, jj);
                 const double kjv = readlane_f64(key, jj);
                 const uint32_t bj = j >> 5;
-                LDS_ORDER();
+                PDMP_LDS_ORDER();
                 const double cur = bk[bj];
                 const uint32_t ci = bi[bj];
                 if (kjv < cur || (kjv == cur && j < ci)) {
@@ -2476,7 +2350,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                         bi[bj] = (uint16_t)(bj * 32 + (uint32_t)arg);
                     }
                 }
-                LDS_ORDER();
+                PDMP_LDS_ORDER();
             }
             const double t_i = readlane_f64(t, self), x_i = readlane_f64(x, self), th_i2 = readlane_f64(th, self);
             if (ev && lane == 0) {  // event(i, t, x, θ, F) = (t[i], i, x[i], θ[i]), :143
@@ -2490,7 +2364,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             dnref += 1;
             t_event = tp;
             if (!stop_before && !(tp < T)) running = false;
-            LDS_ORDER();
+            PDMP_LDS_ORDER();
             continue;
         }
         if (Esel == 0) {
@@ -2500,7 +2374,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             }
             break;
         }
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         PHASE(0);
         if (PROF) ph_iters += 1;
         bool gvalid = g < Esel;
@@ -2540,7 +2414,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             }
         }
         const uint64_t* lb = LB + slot * WPAD;
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         PHASE(1);
         // ---------------- neighbourhood header and member list: positions gl and gl + 8 of S[i]
         // (straight-line: every lane reads its slot's words, the selects below sort out who is a member)
@@ -2578,7 +2452,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 
         // ---------------- zone conflicts with earlier groups: id spans first, the exact id comparison only for pairs of groups
         // whose spans overlap
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         uint64_t confball;
         {
             uint32_t lo = memberA ? sA : 0xffffffffu, hi = memberA ? sA : 0u;
@@ -2626,7 +2500,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             sx[gl] = x;
             sth[gl] = th;
         }
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         double l, lbound;
         {
             // Γ[:, i] . x in ascending row order; the template's entries past k are 0.0 and sx[0..7] are all finite numbers of
@@ -2643,7 +2517,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                 LBr[g] = lbound;
             }
         }
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         // ---------------- accept chain in time order.  Lane o evaluates every event's test for the draw at offset o; the ballots
         // are then walked on the scalar unit: event r reads its bit at the offset the earlier outcomes imply.
         // The offsets (each <= 48) travel packed six bits apiece in one 64-bit scalar: offset after r events = bits 6r .. 6r+5.
@@ -2701,7 +2575,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                 sth[gl] = th;
             }
         }
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         // ---------------- re-bound (ab + poisson_time) -- results stay in registers until the commit
         const bool active = gvalid && (accept ? (gl < k) : (gl == self));
         double key = PDMP_INF, a = 0.0, b = 0.0;
@@ -2723,9 +2597,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             a = cj + (gx - gmu) * th;
             b = cj / 100 + th * gt;
             const double L = LU[(rng_off + myoff + 1u + (accept ? (uint32_t)gl : 0u)) & 63u];
-            key = t + dev_poisson_time_L(a, b, L);
+            key = t + poisson_time_L(a, b, L);
         }
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         // the patched copy of the popped key block goes where sx / sth / the zone ids were: all their readers are done
         // (the four 16-byte pieces of a lane's 64-byte chunk are stored in the order piece ^ pk_t, pk_t = 0..3 over the four lanes
         // of a quarter wave that would otherwise share their banks: b128 accesses without bank conflicts)
@@ -2734,12 +2608,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             pk2[0 ^ pk_t] = make_double2(kq[0], kq[1]);
             pk2[1 ^ pk_t] = make_double2(kq[2], kq[3]);
         }
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         if (active && (sA >> 5) == blk) {
             const uint32_t e_ = sA & 31u;
             pk[(e_ & ~3u) + ((((e_ & 3u) >> 1) ^ pk_t) << 1) + (e_ & 1u)] = key;
         }
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         PHASE(5);
         // ---------------- patched minimum of the popped block, and everything this event could expose
         double rowmin;
@@ -2769,7 +2643,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         const double keymin = grp8_min_f64(key);
         const double expose = min_f64(rowmin, keymin);
         if (gl == 0) Mr[g] = expose;
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         // ---------------- validate: event g commits iff all earlier ones do, its zone is disjoint from theirs, and nothing they
         // produce or expose comes before it
         uint32_t Rc;
@@ -2860,7 +2734,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                 ev[ntrace0 + dnacc + dnref + rank] = e;
             }
         }
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         PHASE(7);
         // ---------------- level-1 updates for re-bounded neighbours living in other blocks.  The final entry of a block is the
         // smallest (key, coordinate) among its old entry and the new keys, whatever the order -- so when no two of these lanes aim
@@ -2869,14 +2743,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         const bool upd = commit && accept && gl < k && (sA >> 5) != blk;
         if (__ballot(upd) != 0) {
             uint8_t* const CL = reinterpret_cast<uint8_t*>(smem + S8_CL);
-            LDS_ORDER();
+            PDMP_LDS_ORDER();
             const uint32_t bjv = upd ? (sA >> 5) : 0u;
             const double curv = bk[bjv];
             const uint32_t civ = bi[bjv];
             const bool lower = upd && (key < curv || (key == curv && sA < civ));
             const bool resc = upd && !lower && civ == sA;
             if (lower) CL[bjv & 63u] = (uint8_t)lane;
-            LDS_ORDER();
+            PDMP_LDS_ORDER();
             const bool lost = lower && CL[bjv & 63u] != (uint8_t)lane;
             if (__ballot(lost || resc) == 0) {
                 if (lower) {
@@ -2894,7 +2768,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                     // first-level entry of j's 32-key block: a lower key replaces it; if j WAS the entry and grew, the block is rescanned
                     const double kj = readlane_f64(key, 8 * (int)r + jj);
                     const uint32_t bj = j >> 5;
-                    LDS_ORDER();
+                    PDMP_LDS_ORDER();
                     const double cur = bk[bj];
                     const uint32_t ci = bi[bj];
                     if (kj < cur || (kj == cur && j < ci)) {
@@ -2939,7 +2813,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         }
         if (vsel >= 0) t_last = uniform_f64(SLT[vsel]);  // the violating event's time is the chain's current time
         if (status != PDMP_CHAIN_OK) break;
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
     }
 
     if (PROF && P.dbg && chain == 0 && lane == 0) {
@@ -3061,7 +2935,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         bk[b] = PDMP_INF;
         bi[b] = 0;
     }
-    LDS_ORDER();
+    PDMP_LDS_ORDER();
 
     uint32_t rng_base = 0xffffffffu;
     double ureg = 0.0;  // draw rng_base + lane of the chain's stream
@@ -3142,10 +3016,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                     C = base;
                     if (C <= SEL_CAP) break;
                     dt_sel *= 0.5;
-                    LDS_ORDER();
+                    PDMP_LDS_ORDER();
                     if (lane < (int)SEL_CAP) TK[lane] = PDMP_INF;  // (entries past the new count must read +Inf in the ranking)
                 }
-                LDS_ORDER();
+                PDMP_LDS_ORDER();
                 // rank of candidate n among all (ties by index), on a 16 x 4 grid: lane = 16 * part + n counts the candidates
                 // 4 * part .. 4 * part + 3 that precede n; the four partial counts meet in LDS.  Unused entries hold +Inf.
                 {
@@ -3160,7 +3034,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                     pr += (o23.x < own || (o23.x == own && q + 2 < n)) ? 1u : 0u;
                     pr += (o23.y < own || (o23.y == own && q + 3 < n)) ? 1u : 0u;
                     PR[n * 4 + part] = pr;
-                    LDS_ORDER();
+                    PDMP_LDS_ORDER();
                     if ((uint32_t)lane < C) {
                         const uint4 p4 = reinterpret_cast<const uint4*>(PR)[lane];
                         const uint32_t rank = p4.x + p4.y + p4.z + p4.w;
@@ -3180,7 +3054,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             if (first_inf) status = PDMP_CHAIN_STALLED;
             break;
         }
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         PHASE(0);
         if (PROF) ph_iters += 1;
         bool gvalid = g < Esel;
@@ -3220,7 +3094,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             }
         }
         const uint64_t* lb = LB + slot * WPAD;
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         PHASE(1);
         // ---------------- neighbourhood header and member list: positions gl and gl + 8 of S[i]
         // (straight-line: every lane reads its slot's words, the selects below sort out who is a member)
@@ -3265,7 +3139,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 
         // ---------------- zone conflicts with earlier groups: id spans first, the exact id comparison only for pairs of groups
         // whose spans overlap
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         uint64_t confball;
         {
             uint32_t lo = memberA ? sA : 0xffffffffu, hi = memberA ? sA : 0u;
@@ -3316,7 +3190,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                 LBr[g] = lbound;
             }
         }
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         // ---------------- accept chain in time order.  Lane o evaluates every event's test for the draw at offset o; the ballots
         // are then walked on the scalar unit: event r reads its bit at the offset the earlier outcomes imply.
         // The offsets (each <= 48) travel packed six bits apiece in one 64-bit scalar: offset after r events = bits 6r .. 6r+5.
@@ -3397,9 +3271,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             a = cj + (gbj - gmu) * thj;
             b = cj / 100 + thj * gdbj;
             const double L = LU[(rng_off + myoff + 1u + (accept ? (uint32_t)gl : 0u)) & 63u];
-            key = tp + dev_poisson_time_L(a, b, L);
+            key = tp + poisson_time_L(a, b, L);
         }
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         // the patched copy of the popped key block goes where the zone ids were: all their readers are done
         // (the four 16-byte pieces of a lane's 64-byte chunk are stored in the order piece ^ pk_t, pk_t = 0..3 over the four lanes
         // of a quarter wave that would otherwise share their banks: b128 accesses without bank conflicts)
@@ -3408,12 +3282,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             pk2[0 ^ pk_t] = make_double2(kq[0], kq[1]);
             pk2[1 ^ pk_t] = make_double2(kq[2], kq[3]);
         }
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         if (active && (sA >> 5) == blk) {
             const uint32_t e_ = sA & 31u;
             pk[(e_ & ~3u) + ((((e_ & 3u) >> 1) ^ pk_t) << 1) + (e_ & 1u)] = key;
         }
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         PHASE(5);
         // ---------------- patched minimum of the popped block, and everything this event could expose
         double rowmin;
@@ -3443,7 +3317,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         const double keymin = grp8_min_f64(key);
         const double expose = min_f64(rowmin, keymin);
         if (gl == 0) Mr[g] = expose;
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         // ---------------- validate: event g commits iff all earlier ones do, its zone is disjoint from theirs, and nothing they
         // produce or expose comes before it
         uint32_t Rc;
@@ -3541,7 +3415,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                 ev[ntrace0 + dnacc + rank] = e;
             }
         }
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         PHASE(7);
         // ---------------- level-1 updates for re-bounded neighbours living in other blocks.  The final entry of a block is the
         // smallest (key, coordinate) among its old entry and the new keys, whatever the order -- so when no two of these lanes aim
@@ -3550,14 +3424,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         const bool upd = commit && accept && gl < k && (sA >> 5) != blk;
         if (__ballot(upd) != 0) {
             uint8_t* const CL = reinterpret_cast<uint8_t*>(smem + S8_CL);
-            LDS_ORDER();
+            PDMP_LDS_ORDER();
             const uint32_t bjv = upd ? (sA >> 5) : 0u;
             const double curv = bk[bjv];
             const uint32_t civ = bi[bjv];
             const bool lower = upd && (key < curv || (key == curv && sA < civ));
             const bool resc = upd && !lower && civ == sA;
             if (lower) CL[bjv & 63u] = (uint8_t)lane;
-            LDS_ORDER();
+            PDMP_LDS_ORDER();
             const bool lost = lower && CL[bjv & 63u] != (uint8_t)lane;
             if (__ballot(lost || resc) == 0) {
                 if (lower) {
@@ -3575,7 +3449,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                     // first-level entry of j's 32-key block: a lower key replaces it; if j WAS the entry and grew, the block is rescanned
                     const double kj = readlane_f64(key, 8 * (int)r + jj);
                     const uint32_t bj = j >> 5;
-                    LDS_ORDER();
+                    PDMP_LDS_ORDER();
                     const double cur = bk[bj];
                     const uint32_t ci = bi[bj];
                     if (kj < cur || (kj == cur && j < ci)) {
@@ -3616,7 +3490,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         }
         if (vsel >= 0) t_last = uniform_f64(SLT[vsel]);  // the violating event's time is the chain's current time
         if (status != PDMP_CHAIN_OK) break;
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
     }
 
     if (PROF && P.dbg && chain == 0 && lane == 0) {
@@ -3747,7 +3621,7 @@ __global__ __launch_bounds__(64) void zz_sticky_spec_kernel(ZzRunParams P_in) {
         bk[b] = mk;
         bi[b] = b * 64 + mi;
     }
-    LDS_ORDER();
+    PDMP_LDS_ORDER();
 
     uint32_t rng_base = 0xffffffffu;
     bool running = stop_before || (t_event < T);
@@ -3769,7 +3643,7 @@ __global__ __launch_bounds__(64) void zz_sticky_spec_kernel(ZzRunParams P_in) {
             if (first_inf) status = PDMP_CHAIN_STALLED;
             break;
         }
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         const bool gvalid = g < Esel;
         const double tp = gvalid ? SLT[g] : PDMP_INF;
         const uint32_t blk = gvalid ? SLB[g] : 0u;
@@ -3791,7 +3665,7 @@ __global__ __launch_bounds__(64) void zz_sticky_spec_kernel(ZzRunParams P_in) {
             LU[lane] = pdmp_log(u);
         }
         const uint32_t rng_off = dnm - rng_base;
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         int k = 0, m = 0, self = 0, kjmax = 0;
         uint32_t s = 0xffffff00u + (uint32_t)lane;
         if (gvalid) {
@@ -3843,7 +3717,7 @@ __global__ __launch_bounds__(64) void zz_sticky_spec_kernel(ZzRunParams P_in) {
         }
 
         // ---------------- zone conflicts with earlier groups
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         const uint64_t confball = __ballot(spec_zone_conflict<E>(Z, s, g, member));
 
         // ---------------- event type, moves that do not depend on a draw, gradient
@@ -3879,12 +3753,12 @@ __global__ __launch_bounds__(64) void zz_sticky_spec_kernel(ZzRunParams P_in) {
             if (gl < k && th != 0.0) move_lane();  // :125
         }
         const uint64_t xerrball = __ballot(xerr);
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         if (member) {
             sx[gl] = x;
             sth[gl] = th;
         }
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         // re-bounded lanes if the event happens: non-frozen members of G1[i] (freeze: i itself now has θ = 0; nothing if strong)
         const bool reb_if = gvalid && gl < k && th != 0.0 && !(is_freeze && strong);
         const uint64_t rebball = __ballot(reb_if);
@@ -3908,7 +3782,7 @@ __global__ __launch_bounds__(64) void zz_sticky_spec_kernel(ZzRunParams P_in) {
                 }
             }
         }
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         // ---------------- chain walk in time order: draw offsets, accept outcomes
         uint32_t accept_u = 0, violated_u = 0, myoff = 0;
         {
@@ -3949,7 +3823,7 @@ __global__ __launch_bounds__(64) void zz_sticky_spec_kernel(ZzRunParams P_in) {
             pk2[0] = make_double2(kq[0], kq[1]);
             pk2[1] = make_double2(kq[2], kq[3]);
         }
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         // ---------------- ab + queue_time! (:54-66) for the re-bound set
         const bool active = gvalid && (happens ? reb_if : (gl == self));
         double key = PDMP_INF, a = 0.0, b = 0.0;
@@ -3977,7 +3851,7 @@ __global__ __launch_bounds__(64) void zz_sticky_spec_kernel(ZzRunParams P_in) {
             const uint32_t rank = happens ? (uint32_t)__popc(rowmask & ((1u << gl) - 1u)) : 0u;
             const uint32_t head = happens ? ((is_prop || is_freeze) ? 1u : (reversible ? 1u : 0u)) : 1u;
             const double L = LU[rng_off + myoff + head + rank];
-            const double trefl = dev_poisson_time_L(a, b, L);
+            const double trefl = poisson_time_L(a, b, L);
             const double tfreeze = (th * x >= 0) ? PDMP_INF : (-x / th);  // freezing_time, :10-16
             const bool fz = tfreeze <= trefl;                              // :57
             fzflag = fz ? 1u : 0u;
@@ -3986,7 +3860,7 @@ __global__ __launch_bounds__(64) void zz_sticky_spec_kernel(ZzRunParams P_in) {
         if (is_freeze && gl == self) key = tp - LU[rng_off + myoff] / kappa_i;  // Q[i] = t[i] - log(rand())/κ[i], :96
         const bool newkey = active || (is_freeze && gl == self);
         if (newkey && (s >> 6) == blk) pk[s & 63] = key;
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         // ---------------- patched minimum of the popped block, exposure
         double rowmin, candmin;
         uint32_t cand;
@@ -3996,7 +3870,7 @@ __global__ __launch_bounds__(64) void zz_sticky_spec_kernel(ZzRunParams P_in) {
         const double keymin = row_min_f64(newkey ? key : PDMP_INF);
         const double expose = min_f64(min_f64(rowmin, keymin), hidg);
         if (gl == 0) Mr[g] = expose;
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         // ---------------- validate
         uint32_t Rc;
         uint32_t happb_c;  // bit r: committed event r is a trace event
@@ -4095,21 +3969,21 @@ __global__ __launch_bounds__(64) void zz_sticky_spec_kernel(ZzRunParams P_in) {
                 ev[ntrace0 + dnev + rank] = e;
             }
         }
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         // ---------------- level-1 updates for new keys living in other blocks.  A block's final entry is the smallest
         // (key, coordinate) among its old entry and the new keys, whatever the order: when no two of these lanes aim at one block
         // (claims through the now idle zone-id array) and none has to rescan, every lane updates its block by itself in one LDS
         // round trip; otherwise one by one in event order.
         const bool upd = commit && newkey && (s >> 6) != blk;
         if (__ballot(upd) != 0) {
-            LDS_ORDER();
+            PDMP_LDS_ORDER();
             const uint32_t bjv = upd ? (s >> 6) : 0u;
             const double curv = bk[bjv];
             const uint32_t civ = bi[bjv];
             const bool lower = upd && (key < curv || (key == curv && s < civ));
             const bool resc = upd && !lower && civ == s;
             if (lower) Z[bjv & 63u] = (uint32_t)lane;
-            LDS_ORDER();
+            PDMP_LDS_ORDER();
             const bool lost = lower && Z[bjv & 63u] != (uint32_t)lane;
             if (__ballot(lost || resc) == 0) {
                 if (lower) {
@@ -4163,7 +4037,7 @@ __global__ __launch_bounds__(64) void zz_sticky_spec_kernel(ZzRunParams P_in) {
             t_last = uniform_f64(SLT[vsel]);
         }
         if (status != PDMP_CHAIN_OK) break;
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
     }
 
     if (lane == 0) {
@@ -4303,7 +4177,7 @@ __global__ __launch_bounds__(256) void math_probe_kernel(uint64_t seed, int64_t 
     out[1 * n + k] = pdmp_log(u);
     out[2 * n + k] = a / ((v - 0.5) * 4.0);
     out[3 * n + k] = sqrt(u * 1000.0 + v);
-    out[4 * n + k] = dev_poisson_time(a, b, w);
+    out[4 * n + k] = poisson_time(a, b, w);
     out[5 * n + k] = pdmp_randn(seed, 3u, (uint64_t)k);
     out[6 * n + k] = pdmp_exp((u - 0.5) * 60.0 + v);
     {
@@ -4320,7 +4194,7 @@ int launch_math_probe(uint64_t seed, int64_t n, double* out, void* stream) {
 }
 
 #ifdef PDMP_EXTRA_KERNELS
-// pdmp_debug_math_eval: the shared contract at chosen points, and this unit's own copies
+// pdmp_debug_math_eval: the shared contract at chosen points, and the shared scalars (pdmp_device.hpp) this unit calls, as compiled here
 namespace {
 struct KernelsMathEval {
     __device__ double operator()(int fn, double a, double b, double c, double* y1) const {
@@ -4336,8 +4210,8 @@ struct KernelsMathEval {
         case PDMP_MATH_RANDINT: return (double)pdmp_randint(pdmp_f2u(a), PDMP_STREAM_GLOBAL, (uint64_t)b, (uint32_t)c);
         case PDMP_MATH_DIV: return a / b;
         case PDMP_MATH_SQRT: return sqrt(a);
-        case PDMP_MATH_PT_DEV: return dev_poisson_time(a, b, c);
-        case PDMP_MATH_PT_DEV_L: return dev_poisson_time_L(a, b, pdmp_log(c));
+        case PDMP_MATH_PT_DEV: return poisson_time(a, b, c);
+        case PDMP_MATH_PT_DEV_L: return poisson_time_L(a, b, pdmp_log(c));
         default: return pos_part(a);  // PDMP_MATH_POS_DEV
         }
     }

@@ -30,61 +30,12 @@
 #include <cstdint>
 
 #include "../../include/pdmp_detmath.h"
+#include "pdmp_device.hpp"
 #include "pdmp_engine.hpp"
 
 namespace pdmp {
 
-#define L_INF __builtin_inf()
-#define L_ORDER()                        \
-    do {                                 \
-        __builtin_amdgcn_wave_barrier(); \
-        asm volatile("" ::: "memory");   \
-    } while (0)
-
 namespace {
-
-__device__ __forceinline__ double l_readlane(double v, int srclane) {
-    int lo = __builtin_amdgcn_readlane(__double2loint(v), srclane);
-    int hi = __builtin_amdgcn_readlane(__double2hiint(v), srclane);
-    return __hiloint2double(hi, lo);
-}
-template <int CTRL>
-__device__ __forceinline__ double l_dpp(double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, true);
-    hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double l_min(double a, double b) {
-    double r;
-    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ double l_wave_min(double v) {
-    v = l_min(v, l_dpp<0xB1>(v));
-    v = l_min(v, l_dpp<0x4E>(v));
-    v = l_min(v, l_dpp<0x141>(v));
-    v = l_min(v, l_dpp<0x140>(v));
-    v = l_min(v, l_dpp<0x142>(v));
-    v = l_min(v, l_dpp<0x143>(v));
-    return l_readlane(v, 63);
-}
-__device__ __forceinline__ double l_pos(double x) {
-    return (x > 0.0) ? x : ((x != x) ? x : 0.0);
-}
-__device__ __forceinline__ double l_poisson_time_L(double a, double b, double L) {  // src/poissontime.jl:8-30 with L = log(u)
-    if (b == 0) return (a > 0) ? (-L / a) : L_INF;
-    const double r = a / b;
-    const double q = L * 2.0 / b;
-    const double sq = sqrt((b > 0 && a < 0) ? -q : r * r - q);
-    if (b > 0) return sq - r;
-    if (a <= 0) return L_INF;
-    if (-L <= -(a * a) / b + (a * a) / (2 * b)) return -sq - r;
-    return L_INF;
-}
-__device__ __forceinline__ double l_sigmoid(double x) {  // sigmoid(x) = inv(one(x) + exp(-x)), scripts/logistic.jl:33
-    return 1.0 / (1.0 + pdmp_exp(-x));
-}
 
 constexpr uint32_t LG_PCH = 64;  // (member, entry) products staged per chunk by the re-bound of an accepted event
 constexpr int LG_KREG = 8;       // event times per lane: coordinate j lives in lane j % 64, slot j / 64 (d < 512)
@@ -93,7 +44,7 @@ constexpr int LG_KREG = 8;       // event times per lane: coordinate j lives in 
 __device__ __forceinline__ void l_wave_argmin(double& key, uint32_t& idx) {
 #define L_STEP(CTRL)                                                                                   \
     do {                                                                                               \
-        const double k2 = l_dpp<CTRL>(key);                                                            \
+        const double k2 = dpp_f64<CTRL>(key);                                                            \
         const uint32_t i2 = (uint32_t)__builtin_amdgcn_mov_dpp((int)idx, CTRL, 0xf, 0xf, true);        \
         const bool take = (k2 < key) || (k2 == key && i2 < idx);                                       \
         key = take ? k2 : key;                                                                         \
@@ -107,13 +58,8 @@ __device__ __forceinline__ void l_wave_argmin(double& key, uint32_t& idx) {
     L_STEP(0x142);
     L_STEP(0x143);
 #undef L_STEP
-    key = l_readlane(key, 63);
+    key = readlane_f64(key, 63);
     idx = (uint32_t)__builtin_amdgcn_readlane((int)idx, 63);
-}
-__device__ __forceinline__ double l_shfl(double v, uint32_t src) {
-    const int lo = __builtin_amdgcn_ds_bpermute((int)(src << 2), __double2loint(v));
-    const int hi = __builtin_amdgcn_ds_bpermute((int)(src << 2), __double2hiint(v));
-    return __hiloint2double(hi, lo);
 }
 
 }  // namespace
@@ -196,7 +142,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 #pragma unroll
     for (int q = 0; q < LG_KREG; ++q) {
         const uint32_t j = (uint32_t)lane + 64u * (uint32_t)q;
-        kreg[q] = (j < dk) ? keys[j] : L_INF;
+        kreg[q] = (j < dk) ? keys[j] : PDMP_INF;
     }
     auto set_key = [&](uint32_t j, double key) {  // (j wave-uniform or not: the owner lane takes it)
         const bool mine = (j & 63u) == (uint32_t)lane;
@@ -204,7 +150,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 #pragma unroll
         for (int q = 0; q < LG_KREG; ++q) kreg[q] = (mine && slot == (uint32_t)q) ? key : kreg[q];
     };
-    L_ORDER();
+    PDMP_LDS_ORDER();
 
     // smove_forward!(i::Int, ...) (src/sfact.jl:13-16) of one coordinate in LDS; returns (x at t′, θ).  A second move to the same t′ is
     // the identity (dt = 0), so lanes that meet on a coordinate store the same values.
@@ -223,7 +169,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             const uint32_t pp = base + (uint32_t)lane;
             if (pp < p1) (void)move1(P.tb.sidx[sp0 + pp], tp);
         }
-        L_ORDER();
+        PDMP_LDS_ORDER();
     };
 
     // s1 += px[z0 .. z1), s2 += pt[z0 .. z1) in order: the LDS reads of 8 terms are issued together, the adds stay sequential
@@ -337,7 +283,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         {
             // the minimum first (a DPP reduction of the keys alone), then who holds it: one lane in all but exactly tied cases, where the
             // (key, coordinate) reduction decides as before -- a third fewer vector instructions than reducing pairs every time
-            const double gmin = l_wave_min(tp);
+            const double gmin = wave_min_f64(tp);
             const uint64_t holders = __ballot(tp == gmin);
             if (__popcll(holders) == 1) {
                 i = (uint32_t)__builtin_amdgcn_readlane((int)i, __ffsll((unsigned long long)holders) - 1);
@@ -346,7 +292,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                 l_wave_argmin(tp, i);
             }
         }
-        if (!(tp < L_INF)) {
+        if (!(tp < PDMP_INF)) {
             status = PDMP_CHAIN_STALLED;
             break;
         }
@@ -375,7 +321,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         const uint32_t goff = dng - gbase, moff = dnm - mbase;
         const bool qa = (uint32_t)lane - goff < (uint32_t)nq;
         const uint64_t bits = gbits;
-        const double ucoin = l_readlane(mu, (int)moff);
+        const double ucoin = readlane_f64(mu, (int)moff);
         const uint32_t cp0 = H.cp0, k = H.k, sp0 = H.sp0, m = H.m;
         // [2]: the sampled entries of column i of the design FIRST (the observation records hang on them: the longest chain of look-ups), then
         // G1[i] and its Γ values -- every lane loads (lanes past k re-read the last entry): a load under a lane mask makes the number of loads
@@ -413,20 +359,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         // ---------------- smove_forward!(G, i, ...), :82, and with it the sums of i's own re-bound: Γ[:,i]·x, Γ[:,i]·θ in idot's order
         double s1r = 0.0, s2r = 0.0;
         if constexpr (TRK) {
-            L_ORDER();
+            PDMP_LDS_ORDER();
             if (lane == 0) (void)move1(i, tp);  // x_i at t′: the prior term and the event record read it
-            L_ORDER();
+            PDMP_LDS_ORDER();
         } else {
-            L_ORDER();
+            PDMP_LDS_ORDER();
             if (gm) {
                 const double2 nx = move1(jm, tp);
                 px[lane] = wm * nx.x;
                 pt[lane] = wm * nx.y;
             }
-            L_ORDER();
+            PDMP_LDS_ORDER();
             run_sums_uniform((k < 64u) ? k : 64u, s1r, s2r);  // (every lane the same sums: LDS broadcasts)
             for (uint32_t base = 64u; base < k; base += 64u) {  // (columns beyond 64 entries: the intercept's)
-                L_ORDER();
+                PDMP_LDS_ORDER();
                 const uint32_t pp = base + (uint32_t)lane;
                 if (pp < k) {
                     const double2 nx = move1(P.tb.sidx[sp0 + pp], tp);
@@ -434,10 +380,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                     px[lane] = w * nx.x;
                     pt[lane] = w * nx.y;
                 }
-                L_ORDER();
+                PDMP_LDS_ORDER();
                 run_sums_uniform((k - base < 64u) ? (k - base) : 64u, s1r, s2r);
             }
-            L_ORDER();
+            PDMP_LDS_ORDER();
         }
         LPHASE(1);
         // ---------------- ∇ϕmoving = γ0 x[i] − fdot_moving(A, At, i, t, x, θ, t′, F, μ, y, ny, k), scripts/logistic.jl:78-95,107
@@ -452,15 +398,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 #pragma unroll
             for (int e = 0; e < 6; ++e) {
                 if (e < ne) u += wv[e] * move1(id[e], tp).x;
-                L_ORDER();
+                PDMP_LDS_ORDER();
             }
             const double w = H.lk * v;  // l / k * vals[i]
             // the two sigmoids of an observation are evaluated SIDE BY SIDE: its own lane takes sigmoid(-u), the lane 32 further on (idle: at most
             // 32 observations are sampled) takes sigmoid(u) -- one exponential and one division per lane instead of two
             const bool qb = (((uint32_t)lane - 32u - goff) & 63u) < (uint32_t)nq;  // partner of an observation lane
-            const double u_p = l_shfl(u, (uint32_t)(lane ^ 32));
-            const double sg = l_sigmoid(qb ? u_p : -u);
-            const double sg_p = l_shfl(sg, (uint32_t)(lane ^ 32));
+            const double u_p = bperm_f64(u, (uint32_t)(lane ^ 32));
+            const double sg = sigmoid(qb ? u_p : -u);
+            const double sg_p = bperm_f64(sg, (uint32_t)(lane ^ 32));
             const double t1 = w * c0.x * sg;        // sigmoidn(u) = sigmoid(-u)
             const double t2 = w * c0.y * (-sg_p);   // nsigmoid(u) = -sigmoid(u)
             const double t3 = w * c0.x * c0.z;              // sigmoidn(u0), u0 = idot(At, row, μ): tabulated per observation
@@ -470,13 +416,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             double s = 0.0;
             {
                 double2* const q2 = reinterpret_cast<double2*>(px);  // [k_sub][2] (k_sub <= 32: px and pt together)
-                L_ORDER();
+                PDMP_LDS_ORDER();
                 if (qa) {
                     const uint32_t qrel = (uint32_t)lane - goff;
                     q2[2 * qrel] = make_double2(t1, t2);
                     q2[2 * qrel + 1] = make_double2(t3, t4);
                 }
-                L_ORDER();
+                PDMP_LDS_ORDER();
                 for (int z = 0; z < nq; z += 2) {
                     const double2 a0 = q2[2 * z], b0 = q2[2 * z + 1];
                     const bool two = z + 1 < nq;
@@ -492,7 +438,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                         s -= b1.y;
                     }
                 }
-                L_ORDER();
+                PDMP_LDS_ORDER();
             }
             dng += (uint32_t)Q.ksub;
             g = prior - s;
@@ -503,8 +449,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         // STORES: round 5, read off the ISA of the tracked lattice kernel first)
         asm volatile("" ::"v"(c_i), "v"(gmu_i), "v"(told_i), "v"(a_i), "v"(b_i), "v"(acc_i), "v"(jm), "v"(wm), "v"(trk_i.x), "v"(trk_i.y), "v"(trk_i.z));
         const double th_i = xt[i].y;
-        const double l_rate = l_pos(g * th_i);                   // :119
-        const double lbound = l_pos(a_i + b_i * (tp - told_i));  // :119
+        const double l_rate = pos_part(g * th_i);                   // :119
+        const double lbound = pos_part(a_i + b_i * (tp - told_i));  // :119
         dnum += 1;
         dnm += 1;  // the coin is draw nm, :121
         const bool accept = (ucoin * lbound < l_rate);
@@ -524,10 +470,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                 r->b = b;
             }
             asm volatile("" ::: "memory");
-            const double key = tp + l_poisson_time_L(a, b, l_readlane(mL, (int)moff + 1));
+            const double key = tp + poisson_time_L(a, b, readlane_f64(mL, (int)moff + 1));
             set_key(i, key);
             dnm += 1;
-            L_ORDER();
+            PDMP_LDS_ORDER();
             LPHASE(4);
             continue;
         }
@@ -558,7 +504,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             xt[i].y = -th_i;  // reflect!, :130
             rec[i].acc = acc_i + 1;
         }
-        L_ORDER();
+        PDMP_LDS_ORDER();
         LPHASE(3);
         if constexpr (TRK) {
             // ---------------- the members of G1[i], one per lane: sums advanced to t′, gd_j += Γ[j,i]·(−2θ_i), bound and event time (:131-135)
@@ -573,7 +519,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                 const double cj = (j == i) ? ci_new : cj_tab;
                 const double gmu = P.tb.gmu_b[j];
                 const uint32_t src = moff + 1u + jj;  // draw nm + jj (nm already counts the coin)
-                double Ldraw = l_shfl(mL, (src < 64u) ? src : 63u);
+                double Ldraw = bperm_f64(mL, (src < 64u) ? src : 63u);
                 if (__ballot(valid && src >= 64u) != 0) {
                     const double Lx = pdmp_log(pdmp_u01(seed, PDMP_STREAM_MAIN, nm0 + (uint64_t)dnm + (uint64_t)jj));
                     Ldraw = (src >= 64u) ? Lx : Ldraw;
@@ -584,7 +530,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                     const double thj = xt[j].y;
                     const double a = cj + (gj - gmu) * thj;  // src/fact_samplers.jl:51
                     const double b = cj / 100 + thj * gdj;   // :52
-                    const double keyj = tp + l_poisson_time_L(a, b, Ldraw);
+                    const double keyj = tp + poisson_time_L(a, b, Ldraw);
                     trkc[j] = make_double4(gj, gdj, tp, 0.0);
                     ZzRec* r = rec + j;
                     r->t_old = tp;
@@ -593,7 +539,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                     px[lane] = keyj;
                     pj[lane] = j;
                 }
-                L_ORDER();
+                PDMP_LDS_ORDER();
                 const uint32_t last = (base + 64u < k) ? (base + 64u) : k;
                 for (uint32_t z = 0; z < last - base; z += 4) {
                     uint32_t jn[4];
@@ -607,7 +553,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                     for (int q = 0; q < 4; ++q)
                         if (z + q < last - base) set_key(jn[q], kn[q]);
                 }
-                L_ORDER();
+                PDMP_LDS_ORDER();
             }
         } else
         // ---------------- ab + new event time of every member of G1[i] (:131-135; src/fact_samplers.jl:50-54).  The dot products keep idot's
@@ -626,7 +572,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             const double gmu = (base == 0) ? gmu0 : P.tb.gmu_b[valid ? j : i];
             // draw nm + jj (nm already counts the coin): from the block where it reaches, else formed now
             const uint32_t src = moff + 1u + jj;
-            double Ldraw = l_shfl(mL, (src < 64u) ? src : 63u);
+            double Ldraw = bperm_f64(mL, (src < 64u) ? src : 63u);
             if (__ballot(valid && src >= 64u) != 0) {
                 const double Lx = pdmp_log(pdmp_u01(seed, PDMP_STREAM_MAIN, nm0 + (uint64_t)dnm + (uint64_t)jj));
                 Ldraw = (src >= 64u) ? Lx : Ldraw;
@@ -647,23 +593,23 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                     rn = LT.qrow16[cb + LG_PCH + (uint32_t)lane];
                     wn = Q.qbval[cb + LG_PCH + (uint32_t)lane];
                 }
-                L_ORDER();
+                PDMP_LDS_ORDER();
                 if (cb + (uint32_t)lane < ce) {
                     const double2 a = xt[rc];
                     px[lane] = wc * a.x;
                     pt[lane] = wc * a.y;
                 }
-                L_ORDER();
+                PDMP_LDS_ORDER();
                 const uint32_t z0 = (q0 > cb) ? q0 : cb, z1 = (q0 + kj < ce) ? (q0 + kj) : ce;
                 if (z0 < z1) run_sums(z0 - cb, z1 - cb, s1, s2);
             }
-            L_ORDER();
-            double keyj = L_INF;
+            PDMP_LDS_ORDER();
+            double keyj = PDMP_INF;
             if (valid) {
                 const double thj = xt[j].y;
                 const double a = cj + (s1 - gmu) * thj;  // src/fact_samplers.jl:51
                 const double b = cj / 100 + thj * s2;    // :52
-                keyj = tp + l_poisson_time_L(a, b, Ldraw);
+                keyj = tp + poisson_time_L(a, b, Ldraw);
                 ZzRec* r = rec + j;
                 r->t_old = tp;
                 r->a = a;
@@ -671,7 +617,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                 px[lane] = keyj;
                 pj[lane] = j;
             }
-            L_ORDER();
+            PDMP_LDS_ORDER();
             // the new keys go to their owner lanes
             for (uint32_t z = 0; z < last - base; z += 4) {
                 uint32_t jn[4];
@@ -685,10 +631,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                 for (int q = 0; q < 4; ++q)
                     if (z + q < last - base) set_key(jn[q], kn[q]);
             }
-            L_ORDER();
+            PDMP_LDS_ORDER();
         }
         dnm += k;
-        L_ORDER();
+        PDMP_LDS_ORDER();
         LPHASE(4);
         if (ev && lane == 0) {
             pdmp_event e;
@@ -701,11 +647,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         dnev += 1;
         t_event = tp;
         if (!stop_before && !(tp < T)) running = false;
-        L_ORDER();
+        PDMP_LDS_ORDER();
         LPHASE(5);
     }
     // ---------------- the state goes back (every other entry point reads the records)
-    L_ORDER();
+    PDMP_LDS_ORDER();
     for (uint32_t j = lane; j < d; j += 64) {
         const double2 a = xt[j];
         ZzRec* r = rec + j;
@@ -780,14 +726,14 @@ int launch_zz_logistic_lds(const ZzRunParams& p, const ZzGeneralParams& q, const
 }
 
 #ifdef PDMP_EXTRA_KERNELS
-// pdmp_debug_math_eval: this unit's own copies, called as they are
+// pdmp_debug_math_eval: the shared scalars (pdmp_device.hpp) this unit calls, as compiled here
 namespace {
 struct LogisticMathEval {
     __device__ double operator()(int fn, double a, double b, double c, double*) const {
         switch (fn) {
-        case PDMP_MATH_PT_LOGISTIC_L: return l_poisson_time_L(a, b, pdmp_log(c));
-        case PDMP_MATH_SIGMOID_LOGISTIC: return l_sigmoid(a);
-        default: return l_pos(a);  // PDMP_MATH_POS_LOGISTIC
+        case PDMP_MATH_PT_LOGISTIC_L: return poisson_time_L(a, b, pdmp_log(c));
+        case PDMP_MATH_SIGMOID_LOGISTIC: return sigmoid(a);
+        default: return pos_part(a);  // PDMP_MATH_POS_LOGISTIC
         }
     }
 };

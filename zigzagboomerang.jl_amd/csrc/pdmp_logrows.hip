@@ -15,26 +15,13 @@
 #include <cstdint>
 
 #include "../../include/pdmp_detmath.h"
+#include "pdmp_device.hpp"
 #include "pdmp_engine.hpp"
 
 namespace pdmp {
 
-#define R_INF __builtin_inf()
-#define R_ORDER()                        \
-    do {                                 \
-        __builtin_amdgcn_wave_barrier(); \
-        asm volatile("" ::: "memory");   \
-    } while (0)
-
 namespace {
 
-template <int CTRL>
-__device__ __forceinline__ double r_dpp(double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, true);
-    hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
 __device__ __forceinline__ double r_perm(double v, uint32_t srclane) {  // value of lane srclane (which must be active)
     const int lo = __builtin_amdgcn_ds_bpermute((int)(srclane << 2), __double2loint(v));
     const int hi = __builtin_amdgcn_ds_bpermute((int)(srclane << 2), __double2hiint(v));
@@ -43,29 +30,12 @@ __device__ __forceinline__ double r_perm(double v, uint32_t srclane) {  // value
 __device__ __forceinline__ uint32_t r_perm_u32(uint32_t v, uint32_t srclane) {
     return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(srclane << 2), (int)v);
 }
-__device__ __forceinline__ double r_pos(double x) {
-    return (x > 0.0) ? x : ((x != x) ? x : 0.0);
-}
-__device__ __forceinline__ double r_poisson_time_L(double a, double b, double L) {  // src/poissontime.jl:8-30 with L = log(u)
-    if (b == 0) return (a > 0) ? (-L / a) : R_INF;
-    const double r = a / b;
-    const double q = L * 2.0 / b;
-    const double sq = sqrt((b > 0 && a < 0) ? -q : r * r - q);
-    if (b > 0) return sq - r;
-    if (a <= 0) return R_INF;
-    if (-L <= -(a * a) / b + (a * a) / (2 * b)) return -sq - r;
-    return R_INF;
-}
-__device__ __forceinline__ double r_sigmoid(double x) {  // sigmoid(x) = inv(one(x) + exp(-x)), scripts/logistic.jl:33
-    return 1.0 / (1.0 + pdmp_exp(-x));
-}
-
 // minimum of (key, index) pairs over a row of W lanes, lowest index on exactly equal keys; result in every lane of the row
 template <int W>
 __device__ __forceinline__ void r_row_argmin(double& key, uint32_t& idx, int lane) {
 #define R_STEP(CTRL)                                                                            \
     do {                                                                                        \
-        const double k2 = r_dpp<CTRL>(key);                                                     \
+        const double k2 = dpp_f64<CTRL>(key);                                                     \
         const uint32_t i2 = (uint32_t)__builtin_amdgcn_mov_dpp((int)idx, CTRL, 0xf, 0xf, true); \
         const bool take = (k2 < key) || (k2 == key && i2 < idx);                                \
         key = take ? k2 : key;                                                                  \
@@ -152,7 +122,7 @@ __global__ __launch_bounds__(64) void zz_logistic_rows_kernel(ZzRunParams P, ZzG
 #pragma unroll
     for (int q = 0; q < KREG; ++q) {
         const uint32_t j = rl + (uint32_t)W * (uint32_t)q;
-        kreg[q] = (j < dk) ? keys[j] : R_INF;
+        kreg[q] = (j < dk) ? keys[j] : PDMP_INF;
     }
     auto set_key = [&](uint32_t j, double key) {  // (j the same in the whole row or not: the owner lane takes it)
         const bool mine = (j & (uint32_t)(W - 1)) == rl;
@@ -160,7 +130,7 @@ __global__ __launch_bounds__(64) void zz_logistic_rows_kernel(ZzRunParams P, ZzG
 #pragma unroll
         for (int q = 0; q < KREG; ++q) kreg[q] = (mine && slot == (uint32_t)q) ? key : kreg[q];
     };
-    R_ORDER();
+    PDMP_LDS_ORDER();
 
     // smove_forward!(i::Int, ...) (src/sfact.jl:13-16) of one coordinate in LDS; returns (x at t′, θ).  A second move to the same t′ is
     // the identity (dt = 0), so lanes that meet on a coordinate store the same values.
@@ -198,7 +168,7 @@ __global__ __launch_bounds__(64) void zz_logistic_rows_kernel(ZzRunParams P, ZzG
             i = lt ? (rl + (uint32_t)W * (uint32_t)q) : i;
         }
         r_row_argmin<W>(tp, i, lane);
-        if (!(tp < R_INF)) {
+        if (!(tp < PDMP_INF)) {
             status = PDMP_CHAIN_STALLED;
             break;
         }
@@ -232,7 +202,7 @@ __global__ __launch_bounds__(64) void zz_logistic_rows_kernel(ZzRunParams P, ZzG
         // ---------------- smove_forward!(G, i, ...), :82, and with it the sums of i's own re-bound: Γ[:,i]·x, Γ[:,i]·θ in idot's order
         double s1r = 0.0, s2r = 0.0;
         for (uint32_t mb = 0; mb < k; mb += W) {
-            R_ORDER();
+            PDMP_LDS_ORDER();
             const uint32_t pp = mb + rl;
             if (pp < k) {
                 const double2 nx = move1(P.tb.sidx[sp0 + pp], tp);
@@ -240,10 +210,10 @@ __global__ __launch_bounds__(64) void zz_logistic_rows_kernel(ZzRunParams P, ZzG
                 px[rl] = w * nx.x;
                 pt[rl] = w * nx.y;
             }
-            R_ORDER();
+            PDMP_LDS_ORDER();
             run_sums(0u, (k - mb < (uint32_t)W) ? (k - mb) : (uint32_t)W, s1r, s2r);  // (every lane of the row the same sums: LDS broadcasts)
         }
-        R_ORDER();
+        PDMP_LDS_ORDER();
         // ---------------- ∇ϕmoving = γ0 x[i] − fdot_moving(A, At, i, t, x, θ, t′, F, μ, y, ny, k), scripts/logistic.jl:78-95,107
         double g;
         {
@@ -256,11 +226,11 @@ __global__ __launch_bounds__(64) void zz_logistic_rows_kernel(ZzRunParams P, ZzG
 #pragma unroll
             for (int e = 0; e < 6; ++e) {
                 if (e < ne) u += wv[e] * move1(id[e], tp).x;
-                R_ORDER();
+                PDMP_LDS_ORDER();
             }
             const double w = H.lk * v;  // l / k * vals[i]
-            const double t1 = w * c0.x * r_sigmoid(-u);    // sigmoidn(u) = sigmoid(-u)
-            const double t2 = w * c0.y * (-r_sigmoid(u));  // nsigmoid(u) = -sigmoid(u)
+            const double t1 = w * c0.x * sigmoid(-u);    // sigmoidn(u) = sigmoid(-u)
+            const double t2 = w * c0.y * (-sigmoid(u));  // nsigmoid(u) = -sigmoid(u)
             const double t3 = w * c0.x * c0.z;             // sigmoidn(u0), u0 = idot(At, row, μ): tabulated per observation
             const double t4 = w * c0.y * c0.w;             // nsigmoid(u0)
             double s = 0.0;
@@ -274,8 +244,8 @@ __global__ __launch_bounds__(64) void zz_logistic_rows_kernel(ZzRunParams P, ZzG
             g = prior - s;
         }
         const double th_i = xt[i].y;
-        const double l_rate = r_pos(g * th_i);                   // :119
-        const double lbound = r_pos(a_i + b_i * (tp - told_i));  // :119
+        const double l_rate = pos_part(g * th_i);                   // :119
+        const double lbound = pos_part(a_i + b_i * (tp - told_i));  // :119
         num += 1;
         nm += 1;  // the coin is draw nm, :121
         const bool accept = (ucoin * lbound < l_rate);
@@ -283,7 +253,7 @@ __global__ __launch_bounds__(64) void zz_logistic_rows_kernel(ZzRunParams P, ZzG
             // ---------------- rejected (:137-139): the bound from the sums taken above
             const double a = c_i + (s1r - gmu_i) * th_i;  // src/fact_samplers.jl:51
             const double b = c_i / 100 + th_i * s2r;      // :52
-            const double key = tp + r_poisson_time_L(a, b, Lrej);
+            const double key = tp + poisson_time_L(a, b, Lrej);
             if (rl == 0) {
                 ZzRec* r = rec + i;
                 r->t_old = tp;
@@ -292,7 +262,7 @@ __global__ __launch_bounds__(64) void zz_logistic_rows_kernel(ZzRunParams P, ZzG
             }
             set_key(i, key);
             nm += 1;
-            R_ORDER();
+            PDMP_LDS_ORDER();
             continue;
         }
         // ---------------- accepted
@@ -312,12 +282,12 @@ __global__ __launch_bounds__(64) void zz_logistic_rows_kernel(ZzRunParams P, ZzG
             const uint32_t pp = mb + rl;
             if (pp < m) (void)move1(P.tb.sidx[sp0 + pp], tp);
         }
-        R_ORDER();
+        PDMP_LDS_ORDER();
         if (rl == 0) {
             xt[i].y = -th_i;  // reflect!, :130
             rec[i].acc = acc_i + 1;
         }
-        R_ORDER();
+        PDMP_LDS_ORDER();
         // ---------------- ab + new event time of every member of G1[i] (:131-135; src/fact_samplers.jl:50-54).  The dot products keep idot's
         // order (ascending row); their products are formed W at a time by the row's lanes, then every lane adds up the run of its member.
         for (uint32_t mb = 0; mb < k; mb += W) {
@@ -339,7 +309,7 @@ __global__ __launch_bounds__(64) void zz_logistic_rows_kernel(ZzRunParams P, ZzG
             double s1 = 0.0, s2 = 0.0;
             for (uint32_t cb = qs; cb < qe; cb += W) {
                 const uint32_t ce = (cb + (uint32_t)W < qe) ? (cb + (uint32_t)W) : qe;
-                R_ORDER();
+                PDMP_LDS_ORDER();
                 if (cb + rl < ce) {
                     const uint32_t rc = LT.qrow16[cb + rl];
                     const double wc = Q.qbval[cb + rl];
@@ -347,16 +317,16 @@ __global__ __launch_bounds__(64) void zz_logistic_rows_kernel(ZzRunParams P, ZzG
                     px[rl] = wc * a.x;
                     pt[rl] = wc * a.y;
                 }
-                R_ORDER();
+                PDMP_LDS_ORDER();
                 const uint32_t z0 = (q0 > cb) ? q0 : cb, z1 = (q0 + kj < ce) ? (q0 + kj) : ce;
                 if (z0 < z1) run_sums(z0 - cb, z1 - cb, s1, s2);
             }
-            R_ORDER();
+            PDMP_LDS_ORDER();
             if (valid) {
                 const double thj = xt[j].y;
                 const double a = cj + (s1 - gmu) * thj;  // src/fact_samplers.jl:51
                 const double b = cj / 100 + thj * s2;    // :52
-                const double keyj = tp + r_poisson_time_L(a, b, Ldraw);
+                const double keyj = tp + poisson_time_L(a, b, Ldraw);
                 ZzRec* r = rec + j;
                 r->t_old = tp;
                 r->a = a;
@@ -364,10 +334,10 @@ __global__ __launch_bounds__(64) void zz_logistic_rows_kernel(ZzRunParams P, ZzG
                 px[rl] = keyj;
                 pj[rl] = j;
             }
-            R_ORDER();
+            PDMP_LDS_ORDER();
             // the new keys go to their owner lanes
             for (uint32_t z = 0; z < last - mb; ++z) set_key(pj[z], px[z]);
-            R_ORDER();
+            PDMP_LDS_ORDER();
         }
         nm += (uint64_t)k;
         if (ev && rl == 0) {
@@ -382,10 +352,10 @@ __global__ __launch_bounds__(64) void zz_logistic_rows_kernel(ZzRunParams P, ZzG
         nevents += 1;
         t_event = tp;
         if (!stop_before && !(tp < T)) running = false;
-        R_ORDER();
+        PDMP_LDS_ORDER();
     }
     // ---------------- the state goes back (every other entry point reads the records)
-    R_ORDER();
+    PDMP_LDS_ORDER();
     for (uint32_t j = rl; j < d; j += W) {
         const double2 a = xt[j];
         ZzRec* r = rec + j;
@@ -433,14 +403,14 @@ int launch_zz_logistic_rows(const ZzRunParams& p, const ZzGeneralParams& q, cons
 }
 
 #ifdef PDMP_EXTRA_KERNELS
-// pdmp_debug_math_eval: this unit's own copies, called as they are
+// pdmp_debug_math_eval: the shared scalars (pdmp_device.hpp) this unit calls, as compiled here
 namespace {
 struct LogrowsMathEval {
     __device__ double operator()(int fn, double a, double b, double c, double*) const {
         switch (fn) {
-        case PDMP_MATH_PT_R_L: return r_poisson_time_L(a, b, pdmp_log(c));
-        case PDMP_MATH_SIGMOID_R: return r_sigmoid(a);
-        default: return r_pos(a);  // PDMP_MATH_POS_R
+        case PDMP_MATH_PT_R_L: return poisson_time_L(a, b, pdmp_log(c));
+        case PDMP_MATH_SIGMOID_R: return sigmoid(a);
+        default: return pos_part(a);  // PDMP_MATH_POS_R
         }
     }
 };

@@ -20,50 +20,20 @@
 #include <cstdint>
 
 #include "../../include/pdmp_detmath.h"
+#include "pdmp_device.hpp"
 #include "pdmp_engine.hpp"
 
 namespace pdmp {
 
-#define Q_INF __builtin_inf()
-#define Q_ORDER()                        \
-    do {                                 \
-        __builtin_amdgcn_wave_barrier(); \
-        asm volatile("" ::: "memory");   \
-    } while (0)
-
 namespace {
 
-__device__ __forceinline__ double q_readlane(double v, int srclane) {
-    int lo = __builtin_amdgcn_readlane(__double2loint(v), srclane);
-    int hi = __builtin_amdgcn_readlane(__double2hiint(v), srclane);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double q_wave_min(double v) {
+// minimum over the 64 lanes in EVERY lane, by __shfl_xor (wave_min_f64 of pdmp_device.hpp: DPP, the result in lane 63 only, then made uniform)
+__device__ __forceinline__ double wave_min_shfl_f64(double v) {
     for (int off = 32; off >= 1; off >>= 1) {
         const double o = __shfl_xor(v, off, 64);
         v = (o < v) ? o : v;
     }
     return v;
-}
-__device__ __forceinline__ double q_pos(double x) {  // src/common.jl:8
-    return (x > 0.0) ? x : ((x != x) ? x : 0.0);
-}
-__device__ __forceinline__ double q_poisson_time(double a, double b, double u) {  // src/poissontime.jl:8-30
-    const double L = pdmp_log(u);
-    if (b > 0) {
-        const double r = a / b;
-        if (a < 0) return sqrt(-L * 2.0 / b) - r;
-        return sqrt(r * r - L * 2.0 / b) - r;
-    } else if (b == 0) {
-        return (a > 0) ? -L / a : Q_INF;
-    } else {
-        if (a <= 0) return Q_INF;
-        if (-L <= -(a * a) / b + (a * a) / (2 * b)) {
-            const double r = a / b;
-            return -sqrt(r * r - L * 2.0 / b) - r;
-        }
-        return Q_INF;
-    }
 }
 // loads / stores of data that another lane or wave of the WORKGROUP wrote (all of a workgroup's waves share one vector L1: workgroup scope
 // keeps them cached; nothing outside the workgroup touches a chain during a launch)
@@ -112,18 +82,18 @@ __global__ __launch_bounds__(1024) void zz_partitioned_run_kernel(ZzPartParams P
     // ---- the queue of chunk ti
     auto rescan = [&](int ti, uint32_t b) {
         const uint32_t idx = b * 64u + (uint32_t)lane;
-        const double kv = (idx < (uint32_t)k) ? q_ld(keys + (size_t)ti * k + idx) : Q_INF;
-        const double m = q_wave_min(kv);
+        const double kv = (idx < (uint32_t)k) ? q_ld(keys + (size_t)ti * k + idx) : PDMP_INF;
+        const double m = wave_min_shfl_f64(kv);
         const uint64_t bl = __ballot(kv == m);
         const int arg = bl ? (__ffsll((unsigned long long)bl) - 1) : 0;
         if (lane == 0) {
             bk[(size_t)ti * nbc + b] = m;
             bi[(size_t)ti * nbc + b] = (uint16_t)arg;
         }
-        Q_ORDER();
+        PDMP_LDS_ORDER();
     };
     auto peek = [&](int ti, uint32_t& ii, double& tp) {
-        double m = Q_INF;
+        double m = PDMP_INF;
         uint32_t mb = 0xffffffffu;
         for (uint32_t b = (uint32_t)lane; b < nbc; b += 64u) {
             const double v = bk[(size_t)ti * nbc + b];
@@ -132,7 +102,7 @@ __global__ __launch_bounds__(1024) void zz_partitioned_run_kernel(ZzPartParams P
                 mb = b;
             }
         }
-        const double mm = q_wave_min(m);
+        const double mm = wave_min_shfl_f64(m);
         uint32_t cand = (m == mm && mb != 0xffffffffu) ? mb : 0xffffffffu;
         for (int off = 32; off >= 1; off >>= 1) {
             const uint32_t o = (uint32_t)__shfl_xor((int)cand, off, 64);
@@ -177,17 +147,17 @@ __global__ __launch_bounds__(1024) void zz_partitioned_run_kernel(ZzPartParams P
         // ∇ϕ(x, i) = idot(Γt, i, x) (− (Γt μt)_i): products side by side, summed in ascending row order
         const double pr = mG ? P.tb.tval[cp + lane] * xn : 0.0;
         double s = 0.0;
-        for (uint32_t q = 0; q < kG; ++q) s += q_readlane(pr, (int)q);
+        for (uint32_t q = 0; q < kG; ++q) s += readlane_f64(pr, (int)q);
         double gi = s;
         if (P.tb.gmu_t) gi = gi - P.tb.gmu_t[i];
         const uint64_t selfb = __ballot(mG && j == (uint32_t)i);
         const int sp = selfb ? (__ffsll((unsigned long long)selfb) - 1) : 0;
-        double th_i = q_readlane(thj, sp);
-        const double x_i = q_readlane(xn, sp);
+        double th_i = readlane_f64(thj, sp);
+        const double x_i = readlane_f64(xn, sp);
         const ZzRec* const ri = rec + i;
         const double a_i = q_ld(&ri->a), b_i = q_ld(&ri->b), told_i = q_ld(&ri->t_old);
-        const double l = q_pos(gi * th_i);
-        const double lb = q_pos(a_i + b_i * (tp - told_i));
+        const double l = pos_part(gi * th_i);
+        const double lb = pos_part(a_i + b_i * (tp - told_i));
         const double u = pdmp_u01(seed, stream, nd);
         nd += 1;
         const bool accept = u * lb < l;
@@ -221,7 +191,7 @@ __global__ __launch_bounds__(1024) void zz_partitioned_run_kernel(ZzPartParams P
             m1 = mG && j == (uint32_t)i;
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-        Q_ORDER();
+        PDMP_LDS_ORDER();
         const uint64_t m1b = __ballot(m1);
         const uint32_t rk = (uint32_t)__popcll(m1b & ((1ull << lane) - 1ull));
         if (m1) {  // ab(G1, j, x, θ, c, F), src/fact_samplers.jl:50-54: two idots over column j of the bounding Γ, each lane its own serial sum
@@ -241,11 +211,11 @@ __global__ __launch_bounds__(1024) void zz_partitioned_run_kernel(ZzPartParams P
             q_st(&rj->a, aj);
             q_st(&rj->b, bj);
             q_st(&rj->t_old, tp);
-            q_st(keys + j, tp + q_poisson_time(aj, bj, uj));
+            q_st(keys + j, tp + poisson_time(aj, bj, uj));
         }
         nd += (uint64_t)__popcll(m1b);
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-        Q_ORDER();
+        PDMP_LDS_ORDER();
         uint32_t lastb = 0xffffffffu;
         for (uint64_t todo = m1b; todo; todo &= todo - 1) {
             const int q = __ffsll((unsigned long long)todo) - 1;
@@ -311,7 +281,7 @@ __global__ __launch_bounds__(1024) void zz_partitioned_run_kernel(ZzPartParams P
                     if (lane == 0) {
                         sh[1] = 1u;
                         ret_i[wave] = (int32_t)i;
-                        ret_t[wave] = Q_INF;
+                        ret_t[wave] = PDMP_INF;
                         ret_acc[wave] = acc;
                         ret_num[wave] = num;
                     }
@@ -327,7 +297,7 @@ __global__ __launch_bounds__(1024) void zz_partitioned_run_kernel(ZzPartParams P
         if (wave == 0) {
             for (int ti = 0; ti < K; ++ti)
                 if (waitfor[ti] == 0 && lane == 0) evtime[ti] = ret_t[ti];  // (the workers' events are in the trace already)
-            Q_ORDER();
+            PDMP_LDS_ORDER();
             if (lane == 0) {  // sortperm!(perm, evtime, alg=InsertionSort), :204
                 for (int a = 1; a < K; ++a) {
                     const int v = perm[a];
@@ -339,7 +309,7 @@ __global__ __launch_bounds__(1024) void zz_partitioned_run_kernel(ZzPartParams P
                     perm[b + 1] = v;
                 }
             }
-            Q_ORDER();
+            PDMP_LDS_ORDER();
             for (int a = 0; a < K; ++a) {  // :206-233
                 const int ti = perm[a];
                 const int64_t i = ret_i[ti];
@@ -347,10 +317,10 @@ __global__ __launch_bounds__(1024) void zz_partitioned_run_kernel(ZzPartParams P
                 if (waitfor[ti] == 0) {
                     num_tot += ret_num[ti];
                     acc_tot += ret_acc[ti];
-                    Q_ORDER();
+                    PDMP_LDS_ORDER();
                     if (lane == 0) tpr[ti] = tpi;
                 }
-                Q_ORDER();
+                PDMP_LDS_ORDER();
                 const uint32_t cp = P.tb.colptr[i], kG = P.tb.colptr[i + 1] - cp;
                 bool behind = false;
                 if ((uint32_t)lane < kG) {
@@ -358,26 +328,26 @@ __global__ __launch_bounds__(1024) void zz_partitioned_run_kernel(ZzPartParams P
                     behind = j != i && tpr[j / k] < tpi;
                 }
                 const bool wf = __ballot(behind) != 0;
-                Q_ORDER();
+                PDMP_LDS_ORDER();
                 if (lane == 0) waitfor[ti] = wf ? (int32_t)(i + 1) : 0;
-                Q_ORDER();
+                PDMP_LDS_ORDER();
                 if (wf) continue;
-                if (!(tpi < Q_INF)) continue;  // a chunk parked for good
+                if (!(tpi < PDMP_INF)) continue;  // a chunk parked for good
                 const int ok = innermost(i, tpi, 15u, nd_outer);
                 if (ok < 0) {
                     if (lane == 0) sh[1] = 1u;
                 } else if (ok) {
                     acc_tot += 1;
                 }
-                Q_ORDER();
+                PDMP_LDS_ORDER();
             }
-            Q_ORDER();
+            PDMP_LDS_ORDER();
             tmin = tpr[0];
             for (int ti = 1; ti < K; ++ti) tmin = (tpr[ti] < tmin) ? tpr[ti] : tmin;  // :235
             if (sh[1]) tmin = T;
             rounds += 1;
             const bool done = tmin >= T;
-            Q_ORDER();
+            PDMP_LDS_ORDER();
             if (lane == 0) {
                 for (int ti = 0; ti < K; ++ti) wake[ti] = (waitfor[ti] == 0 || done) ? 1 : 0;  // :241-249
                 sh[0] = done ? 1u : 0u;
@@ -413,13 +383,13 @@ int launch_zz_partitioned(const ZzPartParams& p, int64_t nchains, void* stream) 
 }
 
 #ifdef PDMP_EXTRA_KERNELS
-// pdmp_debug_math_eval: this unit's own copies, called as they are
+// pdmp_debug_math_eval: the shared scalars (pdmp_device.hpp) this unit calls, as compiled here
 namespace {
 struct PartitionMathEval {
     __device__ double operator()(int fn, double a, double b, double c, double*) const {
         switch (fn) {
-        case PDMP_MATH_PT_Q: return q_poisson_time(a, b, c);
-        default: return q_pos(a);  // PDMP_MATH_POS_Q
+        case PDMP_MATH_PT_Q: return poisson_time(a, b, c);
+        default: return pos_part(a);  // PDMP_MATH_POS_Q
         }
     }
 };

@@ -127,7 +127,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         bk[b] = PDMP_INF;
         bi[b] = 0;
     }
-    LDS_ORDER();
+    PDMP_LDS_ORDER();
     if (has_refresh && lane0 == 0) __hip_atomic_store(keys + d, PDMP_INF, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 
     uint32_t rng_base = 0xffffffffu;
@@ -212,10 +212,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                     C = base;
                     if (C <= SEL_CAP) break;
                     dt_sel *= 0.5;
-                    LDS_ORDER();
+                    PDMP_LDS_ORDER();
                     if (lane < (int)SEL_CAP) TK[lane] = PDMP_INF;
                 }
-                LDS_ORDER();
+                PDMP_LDS_ORDER();
                 {
                     const uint32_t n = (uint32_t)lane & 15u, part = (uint32_t)lane >> 4;
                     const double own = TK[n];
@@ -228,12 +228,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                     pr += (o23.x < own || (o23.x == own && q + 2 < n)) ? 1u : 0u;
                     pr += (o23.y < own || (o23.y == own && q + 3 < n)) ? 1u : 0u;
                     PR[n * 4 + part] = pr;
-                    LDS_ORDER();
+                    PDMP_LDS_ORDER();
                     if ((uint32_t)lane < C) {
                         const uint4 p4 = reinterpret_cast<const uint4*>(PR)[lane];
                         const uint32_t rank = p4.x + p4.y + p4.z + p4.w;
                         const uint32_t tbl = TB[lane];
-                        LDS_ORDER();
+                        PDMP_LDS_ORDER();
                         if (rank < (uint32_t)E) {
                             SLT[rank] = own;
                             SLB[rank] = tbl;
@@ -262,7 +262,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             {
                 const uint64_t* bsrc = P.blob + (size_t)P.tix[i1] * P.blob_w_pad;
                 for (uint32_t w = lane; w < W; w += 64) lb0[w] = bsrc[w];
-                LDS_ORDER();
+                PDMP_LDS_ORDER();
                 const int k1 = (int)uniform_u32((uint32_t)(lb0[0] & 0xff));
                 if (lane < k1) {  // smove_forward!(G, i1, ...), :82
                     const uint64_t sw = lb0[1 + (lane >> 1)];
@@ -275,7 +275,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                     r1->t = tp;
                     r1->I = I0 + dt * ((x0 + xn) * 0.5);
                 }
-                LDS_ORDER();
+                PDMP_LDS_ORDER();
             }
             const uint32_t i2 = pdmp_randint(seed, PDMP_STREAM_GLOBAL, ng, (uint32_t)d);
             ng += 1;
@@ -283,7 +283,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                 const uint64_t* bsrc = P.blob + (size_t)P.tix[i2] * P.blob_w_pad;
                 for (uint32_t w = lane; w < W; w += 64) lb0[w] = bsrc[w];
             }
-            LDS_ORDER();
+            PDMP_LDS_ORDER();
             const uint64_t hw = lb0[0];
             const int k = (int)uniform_u32((uint32_t)(hw & 0xff));
             const int m = (int)uniform_u32((uint32_t)((hw >> 8) & 0xff));
@@ -317,7 +317,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                 sx0[lane] = x;
                 sth0[lane] = th;
             }
-            LDS_ORDER();
+            PDMP_LDS_ORDER();
             const uint32_t sub0 = 1 + SW + (uint32_t)lane * R_;
             double key = PDMP_INF;
             if (lane < k) {  // :110-114
@@ -341,7 +341,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                 const double a = cj + (gx - gmu) * th;
                 const double b = cj / 100 + th * gt;
                 const double L = pdmp_log(pdmp_u01(seed, PDMP_STREAM_MAIN, nm + 1 + (uint64_t)lane));
-                key = t + dev_poisson_time_L(a, b, L);
+                key = t + poisson_time_L(a, b, L);
                 rs->t_old = t;
                 rs->a = a;
                 rs->b = b;
@@ -359,7 +359,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                 const uint32_t j = readlane_u32(s, jj);
                 const double kjv = readlane_f64(key, jj);
                 const uint32_t bj = j >> 5;
-                LDS_ORDER();
+                PDMP_LDS_ORDER();
                 const double cur = bk[bj];
                 const uint32_t ci = bi[bj];
                 if (kjv < cur || (kjv == cur && j < ci)) {
@@ -377,7 +377,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                         bi[bj] = (uint16_t)(bj * 32 + (uint32_t)arg);
                     }
                 }
-                LDS_ORDER();
+                PDMP_LDS_ORDER();
             }
             const double t_i = readlane_f64(t, self), x_i = readlane_f64(x, self), th_i2 = readlane_f64(th, self);
             if (ev && lane == 0) {  // event(i, t, x, θ, F) = (t[i], i, x[i], θ[i]), :143
@@ -391,7 +391,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             dnref += 1;
             t_event = tp;
             if (!stop_before && !(tp < T)) running = false;
-            LDS_ORDER();
+            PDMP_LDS_ORDER();
             continue;
         }
         if (Esel == 0) {
@@ -401,7 +401,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 #ifdef PDMP_G8_DEBUG
         if (chain == 0 && lane == 0 && (prio.it % 64u) == 0u) printf("g8 iter %u Esel %d t_ref %.17g t_last %.17g dnum %u\n", (unsigned)prio.it, Esel, t_ref, t_last, dnum);
 #endif
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         PHASE(0);
         if (PROF) ph_iters += 1;
         bool gvalid = g < Esel;
@@ -471,14 +471,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 
         // ---------------- zone conflicts with earlier groups: a bitmap of the coordinates, set by the groups in event order and tested by the
         // next one.  The DS operations of a wave execute in order, so the E set / test pairs are issued back to back and waited for once.
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         uint64_t confball;
         {
-            // (the selection scratch is dead: its readers finished before the LDS_ORDER above)
+            // (the selection scratch is dead: its readers finished before the PDMP_LDS_ORDER above)
 #pragma unroll
             for (int q = 0; q < 2; ++q) reinterpret_cast<uint4*>(BM)[lane + 64 * q] = make_uint4(0u, 0u, 0u, 0u);
             if (lane == 0) BM[512] = 0u;
-            LDS_ORDER();
+            PDMP_LDS_ORDER();
             const uint32_t wA = memberA ? (sA >> 5) : 512u, wB = memberB ? (sB >> 5) : 512u, wC = memberC ? (sC >> 5) : 512u,
                            wD = memberD ? (sD >> 5) : 512u;
             const uint32_t bA = memberA ? (1u << (sA & 31u)) : 0u, bB = memberB ? (1u << (sB & 31u)) : 0u, bC = memberC ? (1u << (sC & 31u)) : 0u,
@@ -498,9 +498,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                     atomicOr(&BM[wC], bC);
                     atomicOr(&BM[wD], bD);
                 }
-                LDS_ORDER();  // (keeps the groups' blocks in event order: to a single lane they are mutually exclusive branches)
+                PDMP_LDS_ORDER();  // (keeps the groups' blocks in event order: to a single lane they are mutually exclusive branches)
             }
-            LDS_ORDER();
+            PDMP_LDS_ORDER();
             const bool hit = ((rA & bA) | (rB & bB) | (rC & bC) | (rD & bD)) != 0u;
             const uint64_t hb = __ballot(hit);
             uint32_t confmask = 0;
@@ -508,7 +508,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             for (int s_ = 1; s_ < E; ++s_) confmask |= (((hb >> (GW * s_)) & GM) != 0ull) ? (1u << s_) : 0u;
             confball = confmask;
         }
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         PHASE(3);
 
         // ---------------- smove_forward!(G, i, ...), gradient, rates
@@ -521,7 +521,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             sx[gl] = x;
             sth[gl] = th;
         }
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         double l, lbound;
         {
             // Γt[:, i] . x in ascending row order (idot): lane p forms its own term, the sum runs over the group's lanes in order; the terms past k
@@ -539,7 +539,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                 LBr[g] = lbound;
             }
         }
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         // ---------------- accept chain in time order (lane o evaluates every event's test for the draw at offset o; scalar walk)
         uint32_t accbits = 0;
         uint64_t offpack = 0;
@@ -633,7 +633,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                 sth[gl] = th;
             }
         }
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         // ---------------- re-bound (ab + poisson_time) -- results stay in registers until the commit
         const bool active = gvalid && (accept ? isG1 : (gl == self));
         double key = PDMP_INF, a = 0.0, b = 0.0;
@@ -661,9 +661,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             a = cj + (gx - gmu) * th;
             b = cj / 100 + th * gt;
             const double L = LU[(myoff + 1u + (accept ? (uint32_t)gl : 0u)) & 63u];
-            key = t + dev_poisson_time_L(a, b, L);
+            key = t + poisson_time_L(a, b, L);
         }
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         // the patched copy of the popped key block goes where sx / sth were: all their readers are done
         if (KPL == 4) {
             double2* pk2 = reinterpret_cast<double2*>(pk + gl * 4);
@@ -672,13 +672,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         } else {
             reinterpret_cast<double2*>(pk + gl * 2)[0] = make_double2(kq[0], kq[1]);
         }
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         if (active && (sA >> 5) == blk) {
             const uint32_t e_ = sA & 31u;
             if (KPL == 4) pk[(e_ & ~3u) + ((((e_ & 3u) >> 1) ^ pk_t) << 1) + (e_ & 1u)] = key;
             else pk[e_] = key;
         }
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         PHASE(5);
         // ---------------- patched minimum of the popped block, and everything this event could expose
         double rowmin;
@@ -719,7 +719,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         const double keymin = (GW == 8) ? grp8_min_f64(key) : row_min_f64(key);
         const double expose = min_f64(rowmin, keymin);
         if (gl == 0) Mr[g] = expose;
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         // ---------------- validate: event g commits iff all earlier ones do, its zone is disjoint from theirs, and nothing they produce or
         // expose comes before it
         uint32_t Rc;
@@ -817,20 +817,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                 ev[ntrace0 + dnacc + dnref + rank] = e;
             }
         }
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
         PHASE(7);
         // ---------------- level-1 updates for re-bounded neighbours living in other blocks (zz_local_spec8_kernel's, unchanged)
         const bool upd = commit && accept && isG1 && (sA >> 5) != blk;
         if (__ballot(upd) != 0) {
             uint8_t* const CL = reinterpret_cast<uint8_t*>(smem + G8_CL);
-            LDS_ORDER();
+            PDMP_LDS_ORDER();
             const uint32_t bjv = upd ? (sA >> 5) : 0u;
             const double curv = bk[bjv];
             const uint32_t civ = bi[bjv];
             const bool lower = upd && (key < curv || (key == curv && sA < civ));
             const bool resc = upd && !lower && civ == sA;
             if (lower) CL[bjv & 63u] = (uint8_t)lane;
-            LDS_ORDER();
+            PDMP_LDS_ORDER();
             const bool lost = lower && CL[bjv & 63u] != (uint8_t)lane;
             if (__ballot(lost || resc) == 0) {
                 if (lower) {
@@ -847,7 +847,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                         if ((j >> 5) == own) continue;
                         const double kj = readlane_f64(key, GW * (int)r + jj);
                         const uint32_t bj = j >> 5;
-                        LDS_ORDER();
+                        PDMP_LDS_ORDER();
                         const double cur = bk[bj];
                         const uint32_t ci = bi[bj];
                         if (kj < cur || (kj == cur && j < ci)) {
@@ -891,7 +891,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         }
         if (vsel >= 0) t_last = uniform_f64(SLT[vsel]);
         if (status != PDMP_CHAIN_OK) break;
-        LDS_ORDER();
+        PDMP_LDS_ORDER();
     }
 
     if (PROF && P.dbg && chain == 0 && lane0 == 0) {

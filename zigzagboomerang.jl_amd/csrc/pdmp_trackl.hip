@@ -21,122 +21,14 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <type_traits>
 
 #include "../../include/pdmp_detmath.h"
+#include "pdmp_device.hpp"
 #include "pdmp_engine.hpp"
 
 namespace pdmp {
 
-#define L_INF __builtin_inf()
-#define L_ORDER()                        \
-    do {                                 \
-        __builtin_amdgcn_wave_barrier(); \
-        asm volatile("" ::: "memory");   \
-    } while (0)
-
 namespace {
-
-__device__ __forceinline__ double l_readlane(double v, int srclane) {
-    int lo = __builtin_amdgcn_readlane(__double2loint(v), srclane);
-    int hi = __builtin_amdgcn_readlane(__double2hiint(v), srclane);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double l_uniform(double v) {
-    int lo = __builtin_amdgcn_readfirstlane(__double2loint(v));
-    int hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
-    return __hiloint2double(hi, lo);
-}
-template <int CTRL>
-__device__ __forceinline__ double l_dpp(double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, true);
-    hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double l_min(double a, double b) {
-    double r;
-    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ double l_wave_min(double v) {
-    v = l_min(v, l_dpp<0xB1>(v));
-    v = l_min(v, l_dpp<0x4E>(v));
-    v = l_min(v, l_dpp<0x141>(v));
-    v = l_min(v, l_dpp<0x140>(v));
-    v = l_min(v, l_dpp<0x142>(v));
-    v = l_min(v, l_dpp<0x143>(v));
-    return l_readlane(v, 63);
-}
-__device__ __forceinline__ double l_grp8_min(double v) {  // minimum over the 8 lanes of a group, in every lane of the group
-    v = l_min(v, l_dpp<0xB1>(v));
-    v = l_min(v, l_dpp<0x4E>(v));
-    v = l_min(v, l_dpp<0x141>(v));
-    return v;
-}
-__device__ __forceinline__ double l_pos(double x) {
-    return (x > 0.0) ? x : ((x != x) ? x : 0.0);
-}
-__device__ __forceinline__ double l_poisson_time_L(double a, double b, double L) {  // src/poissontime.jl:8-30 with L = log(u)
-    if (b == 0) return (a > 0) ? -L / a : L_INF;
-    const double r = a / b;
-    const double q = L * 2.0 / b;
-    const double sq = sqrt((b > 0 && a < 0) ? -q : r * r - q);
-    if (b > 0) return sq - r;
-    if (a <= 0) return L_INF;
-    if (-L <= -(a * a) / b + (a * a) / (2 * b)) return -sq - r;
-    return L_INF;
-}
-__device__ __forceinline__ uint32_t l_wave_min_u32(uint32_t v) {
-    auto step = [](uint32_t x, auto ctrl) -> uint32_t {
-        const uint32_t o = (uint32_t)__builtin_amdgcn_mov_dpp((int)x, decltype(ctrl)::value, 0xf, 0xf, true);
-        return (o < x) ? o : x;
-    };
-    v = step(v, std::integral_constant<int, 0xB1>{});
-    v = step(v, std::integral_constant<int, 0x4E>{});
-    v = step(v, std::integral_constant<int, 0x141>{});
-    v = step(v, std::integral_constant<int, 0x140>{});
-    v = step(v, std::integral_constant<int, 0x142>{});
-    v = step(v, std::integral_constant<int, 0x143>{});
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
-}
-template <int CTRL, int ROWM, int BANKM>
-__device__ __forceinline__ uint32_t l_dpp_id_u32(uint32_t identity, uint32_t src) {
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)identity, (int)src, CTRL, ROWM, BANKM, false);
-}
-__device__ __forceinline__ uint32_t l_scan_add_u32(uint32_t v) {  // inclusive
-    uint32_t x = v;
-    x += l_dpp_id_u32<0x111, 0xf, 0xf>(0u, v);
-    x += l_dpp_id_u32<0x112, 0xf, 0xf>(0u, v);
-    x += l_dpp_id_u32<0x113, 0xf, 0xf>(0u, v);
-    x += l_dpp_id_u32<0x114, 0xf, 0xe>(0u, x);
-    x += l_dpp_id_u32<0x118, 0xf, 0xc>(0u, x);
-    x += l_dpp_id_u32<0x142, 0xa, 0xf>(0u, x);
-    x += l_dpp_id_u32<0x143, 0xc, 0xf>(0u, x);
-    return x;
-}
-template <int CTRL, int ROWM, int BANKM>
-__device__ __forceinline__ double l_dpp_inf(double src) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(src), CTRL, ROWM, BANKM, false);
-    const int hi = __builtin_amdgcn_update_dpp(0x7FF00000, __double2hiint(src), CTRL, ROWM, BANKM, false);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double l_scan_min_f64(double v) {  // inclusive
-    double x = v;
-    x = l_min(x, l_dpp_inf<0x111, 0xf, 0xf>(v));
-    x = l_min(x, l_dpp_inf<0x112, 0xf, 0xf>(v));
-    x = l_min(x, l_dpp_inf<0x113, 0xf, 0xf>(v));
-    x = l_min(x, l_dpp_inf<0x114, 0xf, 0xe>(x));
-    x = l_min(x, l_dpp_inf<0x118, 0xf, 0xc>(x));
-    x = l_min(x, l_dpp_inf<0x142, 0xa, 0xf>(x));
-    x = l_min(x, l_dpp_inf<0x143, 0xc, 0xf>(x));
-    return x;
-}
-__device__ __forceinline__ double l_shfl(double v, uint32_t src) {
-    const int lo = __builtin_amdgcn_ds_bpermute((int)(src << 2), __double2loint(v));
-    const int hi = __builtin_amdgcn_ds_bpermute((int)(src << 2), __double2hiint(v));
-    return __hiloint2double(hi, lo);
-}
 
 // LDS layout (bytes)
 struct LL {
@@ -240,7 +132,7 @@ __device__ __forceinline__ void trackl_body(const ZzRunParams& P) {
     int32_t F = 0;               // front: every key's quantum is >= F
     // one pass over the chain's lines: images (s > 0) and the exact minimum key; with counting = true the blocks below tmin0 + 2^-e, e = 2 .. 17
     auto pass = [&](const bool write, const bool counting, const double tmin0, uint32_t* cnt) -> double {
-        double mloc = L_INF;
+        double mloc = PDMP_INF;
         for (int j = 0; j < 8; ++j) {
             const uint32_t u = (uint32_t)lane + 64u * (uint32_t)j;
             if (16u * u >= nb2p) break;
@@ -250,8 +142,8 @@ __device__ __forceinline__ void trackl_body(const ZzRunParams& P) {
             for (uint32_t r = 0; r < 16u; ++r) {
                 const uint32_t b = 16u * u + r;
                 const double4 s0 = *reinterpret_cast<const double4*>(lines + (size_t)b * 128);
-                const double mk = l_min(s0.x, s0.z);
-                mloc = l_min(mloc, mk);
+                const double mk = min_f64(s0.x, s0.z);
+                mloc = min_f64(mloc, mk);
                 if (write) {
                     const uint32_t w9 = (uint32_t)tl_q(mk, tref, s) & 511u;
                     wv[r >> 2] |= (w9 & 255u) << ((r & 3u) << 3);
@@ -273,21 +165,21 @@ __device__ __forceinline__ void trackl_body(const ZzRunParams& P) {
                 *hw = (*hw & keep) | hp;  // (the lane's own words: nobody else writes them here)
             }
         }
-        return l_wave_min(mloc);
+        return wave_min_f64(mloc);
     };
     bool stalled0 = false;
     auto rebuild = [&]() {
         uint32_t dummy[16];
         const double tmin = pass(true, false, 0.0, dummy);
-        L_ORDER();
-        if (!(tmin < L_INF)) stalled0 = true;
+        PDMP_LDS_ORDER();
+        if (!(tmin < PDMP_INF)) stalled0 = true;
         F = tl_q(tmin, tref, s);
     };
     {
         // (plane words start from zero: a lane's pass writes its own)
         reinterpret_cast<uint4*>(smem + LL::HB)[lane] = make_uint4(0u, 0u, 0u, 0u);
         for (uint32_t u = lane; u < LL::NB2 / 16u; u += 64u) reinterpret_cast<uint4*>(smem + LL::IMG)[u] = make_uint4(0u, 0u, 0u, 0u);
-        L_ORDER();
+        PDMP_LDS_ORDER();
         if (!(s > 0.0)) {
             // first launch of the chain: the density of block minima at the front -- the smallest Δ = 2^-e below which at least 96 blocks lie
             uint32_t cnt[16];
@@ -295,15 +187,15 @@ __device__ __forceinline__ void trackl_body(const ZzRunParams& P) {
             for (int e = 0; e < 16; ++e) cnt[e] = 0u;
             uint32_t dummy[16];
             const double tmin = pass(false, false, 0.0, dummy);
-            if (tmin < L_INF) {
+            if (tmin < PDMP_INF) {
                 (void)pass(false, true, tmin, cnt);
                 double rho = 4.0;
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
-                    const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane((int)l_scan_add_u32(cnt[e]), 63);
+                    const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane((int)scan_add_u32(cnt[e]), 63);
                     if (tot >= 96u || e == 0) rho = (double)(tot > 0u ? tot : 1u) * __builtin_ldexp(1.0, e + 2);
                 }
-                s = l_uniform(rho / targetq);
+                s = uniform_f64(rho / targetq);
             } else {
                 s = 1.0;
             }
@@ -384,7 +276,7 @@ __device__ __forceinline__ void trackl_body(const ZzRunParams& P) {
         }
         LPHASE(7);
         auto draw = [&](uint32_t n) -> double {  // draw nm0 + n for dnm <= n < dnm + L_WIN (every lane calls it: ds_bpermute)
-            const double v0 = l_shfl(ureg[0], n & 63u), v1 = l_shfl(ureg[1], n & 63u);
+            const double v0 = bperm_f64(ureg[0], n & 63u), v1 = bperm_f64(ureg[1], n & 63u);
             return ((n >> 6) & 1u) ? v1 : v0;
         };
         auto drawlog = [&](uint32_t n) -> double { return pdmp_log(draw(n)); };
@@ -393,7 +285,7 @@ __device__ __forceinline__ void trackl_body(const ZzRunParams& P) {
             const uint32_t fwc = (uint32_t)F & 511u;
             for (uint32_t b = lane; b < nb2p; b += 64) {
                 const double4 s0 = *reinterpret_cast<const double4*>(lines + (size_t)b * 128);
-                const double mk = l_min(s0.x, s0.z);
+                const double mk = min_f64(s0.x, s0.z);
                 const int64_t R = (int64_t)tl_q(mk, tref, s) - (int64_t)F;
                 const uint32_t r = (img_get(smem, b) - fwc) & 511u;
                 if (R < (int64_t)r && tlc_bad < 3) { tlc_bad += 1; printf("TLCHECK chain %d iter %u block %u r %u R %lld F %d key %.17g tlast %.17g dnum %u\n", (int)chain, (unsigned)prio.it, b, r, (long long)R, F, mk, t_last, dnum); }
@@ -453,7 +345,7 @@ __device__ __forceinline__ void trackl_body(const ZzRunParams& P) {
                     PK[q] = ~accn[q] & VM[q] & (hbw[q] ^ FHX);
                     ncl += (uint32_t)__builtin_popcount(PK[q]);
                 }
-                const uint32_t incl = l_scan_add_u32(ncl);
+                const uint32_t incl = scan_add_u32(ncl);
                 Cc = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
                 if (Cc <= (uint32_t)L_CMAX) {
                     uint32_t ix = incl - ncl;
@@ -484,7 +376,7 @@ __device__ __forceinline__ void trackl_body(const ZzRunParams& P) {
                 status = PDMP_CHAIN_STALLED;  // (more than 64 block minima that no scale separates: keys tied by construction)
                 break;
             }
-            s = l_uniform(s * 2.0);
+            s = uniform_f64(s * 2.0);
             inv_s = 1.0 / s;
             evq = evq * 0.5;
             rqf = rqf * 0.5;
@@ -499,12 +391,12 @@ __device__ __forceinline__ void trackl_body(const ZzRunParams& P) {
             }
             continue;
         }
-        L_ORDER();
+        PDMP_LDS_ORDER();
         LPHASE(8);
         // ---------------- candidate lane c: ITS line -- both coordinates' pairs, sums and constants: eight 16-byte loads, the lines are distinct
         const bool isc = (uint32_t)lane < Cc;
         const uint32_t cblk = isc ? (uint32_t)TB[lane] : 0u;
-        double c_km = L_INF, c_rs = L_INF, c_tp = 0.0, c_th = 0.0, c_g = 0.0, c_gd = 0.0, c_tg = 0.0, c_c = 0.0, c_c100 = 0.0;
+        double c_km = PDMP_INF, c_rs = PDMP_INF, c_tp = 0.0, c_th = 0.0, c_g = 0.0, c_gd = 0.0, c_tg = 0.0, c_c = 0.0, c_c100 = 0.0;
         uint32_t c_pb = 0u;
         {
             const char* const ln = lines + (size_t)cblk * 128;
@@ -533,7 +425,7 @@ __device__ __forceinline__ void trackl_body(const ZzRunParams& P) {
 #endif
         if (isc) img_set(smem, cblk, (uint32_t)c_q & 511u);
         const bool isev = isc && ((int64_t)c_q - (int64_t)F < (int64_t)meff) && (!stop_before || c_km < T);
-        const double own = isev ? c_km : L_INF;
+        const double own = isev ? c_km : PDMP_INF;
         // rank = the number of events with a smaller key: on 15-bit images of the keys first (pdmp_trackp.hip), exactly where two images meet
         const uint64_t evb = __ballot(isev);
         int nev = __popcll(evb);
@@ -544,11 +436,11 @@ __device__ __forceinline__ void trackl_body(const ZzRunParams& P) {
             const double tlo = tref + (double)F * inv_s;
             const double scale = 32766.0 * s * __builtin_amdgcn_rcp((double)meff);
             const double img = (own - tlo) * scale;
-            const uint32_t qi = isev ? (uint32_t)l_pos(img) : 32767u;
+            const uint32_t qi = isev ? (uint32_t)pos_part(img) : 32767u;
             const uint32_t qk = isev ? ((qi < 32766u) ? qi : 32766u) : 32767u;
-            L_ORDER();
+            PDMP_LDS_ORDER();
             QK[lane] = (uint16_t)qk;
-            L_ORDER();
+            PDMP_LDS_ORDER();
             typedef short pk16 __attribute__((ext_vector_type(2)));
             typedef unsigned short upk16 __attribute__((ext_vector_type(2)));
             const pk16 own2 = {(short)qk, (short)qk};
@@ -568,12 +460,12 @@ __device__ __forceinline__ void trackl_body(const ZzRunParams& P) {
                 }
             }
             rank = (uint32_t)cnt.x + (uint32_t)cnt.y;
-            L_ORDER();
-            rsum = (uint32_t)__builtin_amdgcn_readlane((int)l_scan_add_u32(isev ? rank : 0u), 63);
+            PDMP_LDS_ORDER();
+            rsum = (uint32_t)__builtin_amdgcn_readlane((int)scan_add_u32(isev ? rank : 0u), 63);
         }
         if (rsum != (uint32_t)(nev * (nev - 1) / 2)) {
             KM[lane] = own;
-            L_ORDER();
+            PDMP_LDS_ORDER();
             rank = 0;
             for (uint32_t m0 = 0; m0 < Cc; m0 += 8) {
                 double km[8];
@@ -582,14 +474,14 @@ __device__ __forceinline__ void trackl_body(const ZzRunParams& P) {
 #pragma unroll
                 for (uint32_t q = 0; q < 8; ++q) rank += (km[q] < own) ? 1u : 0u;
             }
-            L_ORDER();
-            rsum = (uint32_t)__builtin_amdgcn_readlane((int)l_scan_add_u32(isev ? rank : 0u), 63);
+            PDMP_LDS_ORDER();
+            rsum = (uint32_t)__builtin_amdgcn_readlane((int)scan_add_u32(isev ? rank : 0u), 63);
         }
         // exactly equal keys among the events: one event this iteration, the tied minimum of the lowest block
         bool slot = isev;
         if (rsum != (uint32_t)(nev * (nev - 1) / 2)) {
-            const double mn = l_wave_min(own);
-            const uint32_t bsel = l_wave_min_u32((isev && own == mn) ? cblk : 0xffffffffu);
+            const double mn = wave_min_f64(own);
+            const uint32_t bsel = wave_min_u32_dpp((isev && own == mn) ? cblk : 0xffffffffu);
             slot = isev && cblk == bsel;
             rank = 0;
             nev = 1;
@@ -605,7 +497,7 @@ __device__ __forceinline__ void trackl_body(const ZzRunParams& P) {
         const double e_km = push64(c_km), e_rs = push64(c_rs), e_tp = push64(c_tp);
         const double e_th = push64(c_th), e_g = push64(c_g), e_gd = push64(c_gd), e_tg = push64(c_tg), e_c = push64(c_c), e_c100 = push64(c_c100);
         const uint32_t e_bu = push32(cblk | (c_pb << 16));
-        L_ORDER();
+        PDMP_LDS_ORDER();
         LPHASE(9);
         int C = nev;
         if (PROF) ph_iters += 1;
@@ -640,16 +532,16 @@ __device__ __forceinline__ void trackl_body(const ZzRunParams& P) {
             continue;
         }
         bool ev = lane < C;
-        const double tp = ev ? e_km : L_INF;  // the event time: the exact block minimum
-        const double rest = ev ? e_rs : L_INF;
+        const double tp = ev ? e_km : PDMP_INF;  // the event time: the exact block minimum
+        const double rest = ev ? e_rs : PDMP_INF;
         const double tprop_i = ev ? e_tp : 0.0;
         const uint32_t blk = e_bu & 0xffffu, pbe = e_bu >> 16;
         const double th = e_th, g_i = e_g, gd_i = e_gd, tg_i = e_tg;
         const double c_i = e_c, c100_i = e_c100;
         const uint32_t i = ev ? (blk * 2u + (pbe & 1u)) : 0u;
-        L_ORDER();
+        PDMP_LDS_ORDER();
         if (ev) SLB[lane] = (uint16_t)blk;
-        L_ORDER();
+        PDMP_LDS_ORDER();
         LPHASE(0);
         uint32_t rc_i = 0xffffu, k_i;
         {
@@ -659,15 +551,15 @@ __device__ __forceinline__ void trackl_body(const ZzRunParams& P) {
             rc_i = ev ? (row_i | (col_i << 8)) : 0xffffu;
             k_i = 1u + (col_i > 0u ? 1u : 0u) + (row_i > 0u ? 1u : 0u) + (row_i + 1u < nlat ? 1u : 0u) + (col_i + 1u < nlat ? 1u : 0u);
         }
-        L_ORDER();
+        PDMP_LDS_ORDER();
         // ---------------- rates from the tracked sums (src/sfact.jl:116-119 with g_i(t′) = g_i + gd_i (t′ − tg_i))
         const double g_now = g_i + gd_i * (tp - tg_i);
-        const double l = l_pos(g_now * th);
+        const double l = pos_part(g_now * th);
         // the bound in force (src/fact_samplers.jl:50-54), re-derived from the stored operands (pdmp_trackp.hip)
         const double told_i = tprop_i;
         const double a_i = c_i + (g_i + gd_i * (told_i - tg_i)) * th;
         const double b_i = c100_i + th * gd_i;
-        const double lbound = l_pos(a_i + b_i * (tp - told_i));
+        const double lbound = pos_part(a_i + b_i * (tp - told_i));
         // ---------------- accept chain: offsets and outcomes as a fix-point
         const uint32_t ex_i = k_i - 1u;
         uint32_t off = 2u * (uint32_t)lane;
@@ -780,11 +672,11 @@ __device__ __forceinline__ void trackl_body(const ZzRunParams& P) {
         const uint64_t accball = __ballot(acc);
         const int nacc_it = __popcll(accball);
         if (acc) ACL[__popcll(accball & ((1ull << lane) - 1ull))] = (uint16_t)lane;
-        L_ORDER();
+        PDMP_LDS_ORDER();
         LPHASE(2);
         // ---------------- accepted events, one 8-lane group each: members of G1[i] (ascending, :131-135); the groups of the accepted events are the
         // LAST groups of the wave, in event order: the low lanes -- lane r = event r -- re-bound their rejected proposals in the same evaluation
-        double key2 = L_INF;  // the new key of this lane's rejected proposal (event lanes)
+        double key2 = PDMP_INF;  // the new key of this lane's rejected proposal (event lanes)
         const int g0 = 8 - nacc_it;
         const bool gact = g >= g0;
         const uint32_t ea = gact ? (uint32_t)ACL[g - g0] : 0u;  // the event of this lane's group
@@ -792,7 +684,7 @@ __device__ __forceinline__ void trackl_body(const ZzRunParams& P) {
         const uint32_t off_b = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(ea << 2), (int)off);
         const uint32_t ia = gact ? ia_b : 0u;
         const uint32_t blka = gact ? (uint32_t)SLB[ea] : 0u;
-        const double tpa_b = l_shfl(tp, ea);
+        const double tpa_b = bperm_f64(tp, ea);
         const double tpa = gact ? tpa_b : 0.0;
         const uint32_t offa = gact ? off_b : 0u;
         uint32_t jm = ia;
@@ -831,7 +723,7 @@ __device__ __forceinline__ void trackl_body(const ZzRunParams& P) {
         double kmate = *reinterpret_cast<const double*>(lj + 16 * (pj ^ 1u));      // the member's pair mate's key (same line: the line's new image, exactly)
         asm volatile("" : "+v"(cjm2.x), "+v"(cjm2.y), "+v"(sj1.x), "+v"(sj1.y), "+v"(kmate));
         const double thj0 = sj0.x, gj0 = sj0.y, gdj0 = sj1.x, tgj = sj1.y;
-        const double resta_b = l_shfl(rest, ea);  // the accepted event's pair mate's key
+        const double resta_b = bperm_f64(rest, ea);  // the accepted event's pair mate's key
         // ---------------- ONE evaluation of the new bound and key per lane: the re-bound of a rejected proposal (:137-140) in its event lane, the
         // re-bound of a member of G1 (:131-135) in its group lane.  A lane that is both evaluates its rejected proposal again below.
         const bool selfl = mem && jm == ia;
@@ -847,14 +739,14 @@ __device__ __forceinline__ void trackl_body(const ZzRunParams& P) {
             const double gg = mine ? gj : g_now, tt = mine ? thj : th, gdd = mine ? gdj : gd_i;
             const double a2l = cc + gg * tt;
             const double b2l = cc100 + tt * gdd;
-            key2l = (mine ? tpa : tp) + l_poisson_time_L(a2l, b2l, Lg);
+            key2l = (mine ? tpa : tp) + poisson_time_L(a2l, b2l, Lg);
         }
-        const double keyj = mem ? key2l : L_INF;
+        const double keyj = mem ? key2l : PDMP_INF;
         if (__ballot(ev && !acc && gact) != 0) {
             const double Le = drawlog(dnm + ((off + 1u < L_WIN - 1u) ? off + 1u : L_WIN - 1u));
             const double a2e = c_i + g_now * th;
             const double b2e = c100_i + th * gd_i;
-            const double k2e = tp + l_poisson_time_L(a2e, b2e, Le);
+            const double k2e = tp + poisson_time_L(a2e, b2e, Le);
             if (gact) key2l = k2e;
         }
         key2 = key2l;
@@ -866,24 +758,24 @@ __device__ __forceinline__ void trackl_body(const ZzRunParams& P) {
             txa = tpa;
         }
         // the accepted event's line: its mate's key, or -- where the mate is a member of G1[ia] -- the mate's new key
-        const double kin = (mem && (jm >> 1) == blka) ? keyj : L_INF;  // (ia itself and, on the lattice, its mate)
-        const double kinmin = l_grp8_min(kin);
-        const bool mate_in = l_grp8_min((mem && jm == (ia ^ 1u)) ? 0.0 : 1.0) == 0.0;  // the mate is re-bounded by this event: its old key is void
-        const double rowmin_a = mate_in ? kinmin : l_min(resta_b, kinmin);
-        const double keymin = l_grp8_min(keyj);
-        if (gact && gl == 0) EX[ea] = l_min(rowmin_a, keymin);
+        const double kin = (mem && (jm >> 1) == blka) ? keyj : PDMP_INF;  // (ia itself and, on the lattice, its mate)
+        const double kinmin = grp8_min_f64(kin);
+        const bool mate_in = grp8_min_f64((mem && jm == (ia ^ 1u)) ? 0.0 : 1.0) == 0.0;  // the mate is re-bounded by this event: its old key is void
+        const double rowmin_a = mate_in ? kinmin : min_f64(resta_b, kinmin);
+        const double keymin = grp8_min_f64(keyj);
+        if (gact && gl == 0) EX[ea] = min_f64(rowmin_a, keymin);
         asm volatile("" ::"v"(xa), "v"(txa), "v"(Ia), "v"(acc_ia));
         // new minimum of the line of a rejected event, and what the event exposes
-        double rowmin = L_INF;
-        if (ev && !acc) rowmin = l_min(key2, rest);
+        double rowmin = PDMP_INF;
+        if (ev && !acc) rowmin = min_f64(key2, rest);
         if (ev && !acc) EX[lane] = rowmin;
-        L_ORDER();
+        PDMP_LDS_ORDER();
         LPHASE(3);
         // ---------------- validate: all earlier events commit, zones disjoint, nothing produced or exposed earlier than t′
         uint32_t Rc;
         {
-            const double prev = (lane > 0 && lane <= C) ? EX[lane - 1] : L_INF;  // what event lane − 1 exposes
-            const double pref = l_scan_min_f64(prev);                            // exclusive prefix minimum
+            const double prev = (lane > 0 && lane <= C) ? EX[lane - 1] : PDMP_INF;  // what event lane − 1 exposes
+            const double pref = scan_min_f64(prev);                                 // exclusive prefix minimum
             const bool okr = ev && (lane == 0 || pref > tp);
             const uint64_t bad = ~__ballot(okr);
             const uint32_t r_ok = bad ? (uint32_t)(__ffsll((unsigned long long)bad) - 1) : 64u;
@@ -908,7 +800,7 @@ __device__ __forceinline__ void trackl_body(const ZzRunParams& P) {
         // from here on must not lie behind it -- the front passes the window's positions without looking at them again
         int32_t Fn = F;
         if (Rc > 0u) {
-            const int32_t fq = tl_q(l_readlane(tp, (int)(Rc - 1u)), tref, s);
+            const int32_t fq = tl_q(readlane_f64(tp, (int)(Rc - 1u)), tref, s);
             Fn = (fq > F) ? fq : F;
         }
         auto img_pos = [&](double key) -> uint32_t {
@@ -951,7 +843,7 @@ __device__ __forceinline__ void trackl_body(const ZzRunParams& P) {
 #endif
             if (gl == 0) img_set(smem, blka, img_pos(rowmin_a));
         }
-        L_ORDER();
+        PDMP_LDS_ORDER();
         LPHASE(5);
         // ---------------- images of the lines of re-bounded neighbours: LOWERED where the new key's quantum is below them (a key that rose leaves
         // its line's image stale low: a look in vain later, nothing else).  An image INSIDE this iteration's window cannot be compared -- it is
@@ -972,7 +864,7 @@ __device__ __forceinline__ void trackl_body(const ZzRunParams& P) {
                 // the pair mate's key as the line held it: beyond this window it is no event of this iteration, hence still the mate's key --
                 // the line's minimum is known exactly and its image is SET (a key that rose leaves nothing stale behind)
                 const bool trust = want0 && ((int64_t)tl_q(kmate, tref, s) - (int64_t)F >= (int64_t)meff);
-                const uint32_t wx = img_pos(l_min(keyj, kmate));
+                const uint32_t wx = img_pos(min_f64(keyj, kmate));
 #ifdef PDMP_TL_CHECK
                 if (want0 && chain == (int64_t)P.dbg_cap && bj == (uint32_t)P.hw_ahead) printf("W lower it %u F %d rn %u cur %u rcur %u keyj %.17g jm %u kmate %.17g trust %d\n", (unsigned)prio.it, F, rn, cur, rcur, keyj, jm, kmate, (int)trust);
 #endif
@@ -982,7 +874,7 @@ __device__ __forceinline__ void trackl_body(const ZzRunParams& P) {
                 const bool act = want0 && (trust || inw || rn < rcur);
                 unsigned char* const CL = smem + LL::EX;
                 if (act) CL[bj & 63u] = (unsigned char)lane;
-                L_ORDER();
+                PDMP_LDS_ORDER();
                 const bool lost = act && CL[bj & 63u] != (unsigned char)lane;
                 if (__ballot(lost) == 0) {
                     if (act) img_set(smem, bj, trust ? wx : (((inw ? dn : rn) + fw) & 511u));
@@ -996,12 +888,12 @@ __device__ __forceinline__ void trackl_body(const ZzRunParams& P) {
                             const bool inw2 = rc2 < (uint32_t)meff;
                             if (inw2 || rn < rc2) img_set(smem, bj, ((inw2 ? dn : rn) + fw) & 511u);
                         }
-                        L_ORDER();
+                        PDMP_LDS_ORDER();
                     }
                 }
             }
         }
-        L_ORDER();
+        PDMP_LDS_ORDER();
         LPHASE(6);
         // ---------------- counters; the violating proposal itself (counted, acc bumped, then error(...), :120-124)
         if (Rc > 0u) {
@@ -1011,11 +903,11 @@ __device__ __forceinline__ void trackl_body(const ZzRunParams& P) {
             idle = 0;
             dnacc += (uint32_t)__popcll(acc_c);
             dnm += offL + costL;
-            t_last = l_readlane(tp, (int)(Rc - 1u));
-            if (acc_c) t_event = l_readlane(tp, 63 - __builtin_clzll(acc_c));
+            t_last = readlane_f64(tp, (int)(Rc - 1u));
+            if (acc_c) t_event = readlane_f64(tp, 63 - __builtin_clzll(acc_c));
         }
         if (vsel >= 0) {  // (vsel == Rc: every earlier event is committed)
-            const double tpv = l_readlane(tp, vsel);
+            const double tpv = readlane_f64(tp, vsel);
             const uint32_t iv = (uint32_t)__builtin_amdgcn_readlane((int)i, vsel);
             if (lane == 0) *reinterpret_cast<double*>(lines + (size_t)(iv >> 1) * 128 + 16 * (iv & 1u) + 8) = tpv;
             dnum += 1;
@@ -1033,8 +925,8 @@ __device__ __forceinline__ void trackl_body(const ZzRunParams& P) {
             if (newq >= 1) {
                 const double inv = __builtin_amdgcn_rcp((double)newq);
                 const double rawn = (double)Cc - 1.3 * prev_left, evn = (double)nev0 - prev_left;
-                rqf = l_uniform(rqf + (((rawn > 0.0) ? rawn : 0.0) * inv - rqf) * (1.0 / 16.0));
-                evq = l_uniform(evq + (((evn > 0.0) ? evn : 0.0) * inv - evq) * (1.0 / 16.0));
+                rqf = uniform_f64(rqf + (((rawn > 0.0) ? rawn : 0.0) * inv - rqf) * (1.0 / 16.0));
+                evq = uniform_f64(evq + (((evn > 0.0) ? evn : 0.0) * inv - evq) * (1.0 / 16.0));
             }
             F = Fn;
             const double left = (double)(nev0 - (int)Rc);
@@ -1043,14 +935,14 @@ __device__ __forceinline__ void trackl_body(const ZzRunParams& P) {
             if (extra < 1.0 && left < 12.0) extra = 1.0;
             extra = (extra < 32.0) ? extra : 32.0;
             prev_base = Bend - F;
-            prev_left = l_uniform(left);
+            prev_left = uniform_f64(left);
             const int32_t mn = prev_base + (int32_t)extra;
             m = (mn < 1) ? 1 : ((mn > L_MMAX) ? L_MMAX : mn);
             // the scale follows the density of events: a quantum should hold about targetq of them
             since_rescale += 1;
             if (since_rescale >= 512u && (evq > 1.5 * targetq || evq < 0.6 * targetq)) {
-                s = l_uniform(s * evq / targetq);
-                inv_s = l_uniform(1.0 / s);
+                s = uniform_f64(s * evq / targetq);
+                inv_s = uniform_f64(1.0 / s);
                 evq = targetq;
                 rqf = 1.5 * targetq;
                 since_rescale = 0;
@@ -1060,7 +952,7 @@ __device__ __forceinline__ void trackl_body(const ZzRunParams& P) {
                 prev_left = 0.0;
             }
         }
-        L_ORDER();
+        PDMP_LDS_ORDER();
     }
 
     if (PROF && P.dbg && chain == 0 && lane == 0) {
@@ -1114,7 +1006,7 @@ __global__ __launch_bounds__(256) void zz_trackl_pack_kernel(const TrRecP* __res
         double* const Lw = reinterpret_cast<double*>(&L);
         for (int p = 0; p < 2; ++p) {
             const int64_t i = 2 * b + p;
-            double key = L_INF, told = 0.0, th = 0.0, gq = 0.0, gd = 0.0, tg = 0.0, c = 0.0, c100 = 0.0;
+            double key = PDMP_INF, told = 0.0, th = 0.0, gq = 0.0, gd = 0.0, tg = 0.0, c = 0.0, c100 = 0.0;
             if (i < d) {
                 const TrRecP* r = rec + ch * d + i;
                 const double2 k2 = kp[ch * dk + i];
@@ -1181,13 +1073,13 @@ int launch_zz_trackl_unpack(const void* lines, const void* cold, void* rec, void
 }
 
 #ifdef PDMP_EXTRA_KERNELS
-// pdmp_debug_math_eval: this unit's own copies, called as they are
+// pdmp_debug_math_eval: the shared scalars (pdmp_device.hpp) this unit calls, as compiled here
 namespace {
 struct TracklMathEval {
     __device__ double operator()(int fn, double a, double b, double c, double*) const {
         switch (fn) {
-        case PDMP_MATH_PT_TRACKL_L: return l_poisson_time_L(a, b, pdmp_log(c));
-        default: return l_pos(a);  // PDMP_MATH_POS_TRACKL
+        case PDMP_MATH_PT_TRACKL_L: return poisson_time_L(a, b, pdmp_log(c));
+        default: return pos_part(a);  // PDMP_MATH_POS_TRACKL
         }
     }
 };

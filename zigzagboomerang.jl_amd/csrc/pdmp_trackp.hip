@@ -28,60 +28,16 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <type_traits>
 
 #include "../../include/pdmp_detmath.h"
+#include "pdmp_device.hpp"
 #include "pdmp_engine.hpp"
 
 namespace pdmp {
 
-#define W_INF __builtin_inf()
-#define W_ORDER()                        \
-    do {                                 \
-        __builtin_amdgcn_wave_barrier(); \
-        asm volatile("" ::: "memory");   \
-    } while (0)
-
 namespace {
 
-__device__ __forceinline__ double w_readlane(double v, int srclane) {
-    int lo = __builtin_amdgcn_readlane(__double2loint(v), srclane);
-    int hi = __builtin_amdgcn_readlane(__double2hiint(v), srclane);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double w_uniform(double v) {
-    int lo = __builtin_amdgcn_readfirstlane(__double2loint(v));
-    int hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
-    return __hiloint2double(hi, lo);
-}
-template <int CTRL>
-__device__ __forceinline__ double w_dpp(double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, true);
-    hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double w_min(double a, double b) {
-    double r;
-    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ double w_wave_min(double v) {
-    v = w_min(v, w_dpp<0xB1>(v));
-    v = w_min(v, w_dpp<0x4E>(v));
-    v = w_min(v, w_dpp<0x141>(v));
-    v = w_min(v, w_dpp<0x140>(v));
-    v = w_min(v, w_dpp<0x142>(v));
-    v = w_min(v, w_dpp<0x143>(v));
-    return w_readlane(v, 63);
-}
-// minimum over the 8 lanes of a group, in every lane of the group
-__device__ __forceinline__ double w_grp8_min(double v) {
-    v = w_min(v, w_dpp<0xB1>(v));
-    v = w_min(v, w_dpp<0x4E>(v));
-    v = w_min(v, w_dpp<0x141>(v));
-    return v;
-}
+// grp8_min_f64 (pdmp_device.hpp) for u32: minimum over the 8 lanes of a group, in every lane of the group
 __device__ __forceinline__ uint32_t w_grp8_min_u32(uint32_t v) {
     uint32_t o = (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xf, 0xf, true);
     v = (o < v) ? o : v;
@@ -90,81 +46,6 @@ __device__ __forceinline__ uint32_t w_grp8_min_u32(uint32_t v) {
     o = (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x141, 0xf, 0xf, true);
     return (o < v) ? o : v;
 }
-__device__ __forceinline__ double w_pos(double x) {
-    return (x > 0.0) ? x : ((x != x) ? x : 0.0);
-}
-__device__ __forceinline__ double w_poisson_time_L(double a, double b, double L) {  // src/poissontime.jl:8-30 with L = log(u)
-    if (b == 0) return (a > 0) ? -L / a : W_INF;
-    const double r = a / b;
-    const double q = L * 2.0 / b;
-    const double sq = sqrt((b > 0 && a < 0) ? -q : r * r - q);
-    if (b > 0) return sq - r;
-    if (a <= 0) return W_INF;
-    if (-L <= -(a * a) / b + (a * a) / (2 * b)) return -sq - r;
-    return W_INF;
-}
-__device__ __forceinline__ double w_below(double x) {  // the largest double below a finite x
-    long long b = __double_as_longlong(x);
-    if (x > 0) b -= 1;
-    else if (x < 0) b += 1;
-    else b = (long long)0x8000000000000001ull;
-    return __longlong_as_double(b);
-}
-
-__device__ __forceinline__ uint32_t w_wave_min_u32(uint32_t v) {  // (DPP: six steps on the vector unit instead of six ds_bpermute round trips)
-    auto step = [](uint32_t x, auto ctrl) -> uint32_t {
-        const uint32_t o = (uint32_t)__builtin_amdgcn_mov_dpp((int)x, decltype(ctrl)::value, 0xf, 0xf, true);
-        return (o < x) ? o : x;
-    };
-    v = step(v, std::integral_constant<int, 0xB1>{});
-    v = step(v, std::integral_constant<int, 0x4E>{});
-    v = step(v, std::integral_constant<int, 0x141>{});
-    v = step(v, std::integral_constant<int, 0x140>{});
-    // (row_bcast: lanes that receive nothing read 0 and are not used: the result is lane 63's)
-    v = step(v, std::integral_constant<int, 0x142>{});
-    v = step(v, std::integral_constant<int, 0x143>{});
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
-}
-// DPP prefix operations over the 64 lanes (row_shr 1, 2, 3 of the input, then row_shr 4 / 8 of the partial result inside the enabled banks,
-// then row_bcast 15 / 31 across the rows): lanes without a source keep the identity.
-template <int CTRL, int ROWM, int BANKM>
-__device__ __forceinline__ uint32_t w_dpp_id_u32(uint32_t identity, uint32_t src) {
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)identity, (int)src, CTRL, ROWM, BANKM, false);
-}
-__device__ __forceinline__ uint32_t w_scan_add_u32(uint32_t v) {  // inclusive
-    uint32_t x = v;
-    x += w_dpp_id_u32<0x111, 0xf, 0xf>(0u, v);
-    x += w_dpp_id_u32<0x112, 0xf, 0xf>(0u, v);
-    x += w_dpp_id_u32<0x113, 0xf, 0xf>(0u, v);
-    x += w_dpp_id_u32<0x114, 0xf, 0xe>(0u, x);
-    x += w_dpp_id_u32<0x118, 0xf, 0xc>(0u, x);
-    x += w_dpp_id_u32<0x142, 0xa, 0xf>(0u, x);
-    x += w_dpp_id_u32<0x143, 0xc, 0xf>(0u, x);
-    return x;
-}
-template <int CTRL, int ROWM, int BANKM>
-__device__ __forceinline__ double w_dpp_inf(double src) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(src), CTRL, ROWM, BANKM, false);
-    const int hi = __builtin_amdgcn_update_dpp(0x7FF00000, __double2hiint(src), CTRL, ROWM, BANKM, false);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double w_scan_min_f64(double v) {  // inclusive
-    double x = v;
-    x = w_min(x, w_dpp_inf<0x111, 0xf, 0xf>(v));
-    x = w_min(x, w_dpp_inf<0x112, 0xf, 0xf>(v));
-    x = w_min(x, w_dpp_inf<0x113, 0xf, 0xf>(v));
-    x = w_min(x, w_dpp_inf<0x114, 0xf, 0xe>(x));
-    x = w_min(x, w_dpp_inf<0x118, 0xf, 0xc>(x));
-    x = w_min(x, w_dpp_inf<0x142, 0xa, 0xf>(x));
-    x = w_min(x, w_dpp_inf<0x143, 0xc, 0xf>(x));
-    return x;
-}
-__device__ __forceinline__ double w_shfl(double v, uint32_t src) {
-    const int lo = __builtin_amdgcn_ds_bpermute((int)(src << 2), __double2loint(v));
-    const int hi = __builtin_amdgcn_ds_bpermute((int)(src << 2), __double2hiint(v));
-    return __hiloint2double(hi, lo);
-}
-
 // level-1 entry: a lower bound of (key - tb) as the bit pattern of a non-negative float, 8 ulp below the (nearest-rounded: off by at most half
 // an ulp) difference, with the argument's position in the 3 low bits (bit patterns of non-negative floats order like the floats)
 __device__ __forceinline__ uint32_t p_enc(double key, double tb, uint32_t pos) {
@@ -180,7 +61,7 @@ __device__ __forceinline__ uint32_t p_thr(double tau, double tb) {
     return __float_as_uint((float)dlt) + 1u;  // (one ulp above the nearest float; +Inf stays above every finite pattern)
 }
 __device__ __forceinline__ double p_dec(uint32_t bits, double tb) {
-    return w_below(tb + (double)__uint_as_float(bits & ~7u));  // (one ulp below the rounded sum: never above the exact one)
+    return pdmp_below(tb + (double)__uint_as_float(bits & ~7u));  // (one ulp below the rounded sum: never above the exact one)
 }
 constexpr uint32_t P_INFBITS = 0x7f7ffff8u;  // patterns from here on: the block is empty (+Inf)
 __device__ __forceinline__ uint32_t lbf_pos(const unsigned char* smem, uint32_t b) {  // position bits of block b's level-1 entry
@@ -282,7 +163,7 @@ __device__ __forceinline__ void trackp_helper(const ZzRunParams& P, unsigned cha
     const char* const kpb = reinterpret_cast<const char*>(reinterpret_cast<const double2*>(P.keys) + chain * P.dk);
     uint16_t* const HPF = reinterpret_cast<uint16_t*>(smem + L::HPF);
     uint32_t filled = 0, sink = 0;
-    double pf_done = -W_INF;  // blocks with bounds up to here have been requested
+    double pf_done = -PDMP_INF;  // blocks with bounds up to here have been requested
     for (;;) {
         if (ctl->exitf != 0u) break;
         bool did = false;
@@ -291,7 +172,7 @@ __device__ __forceinline__ void trackp_helper(const ZzRunParams& P, unsigned cha
             const uint32_t n = filled + (uint32_t)lane;
             const double u = pdmp_u01(seed, PDMP_STREAM_MAIN, nm0 + (uint64_t)n);
             ring[n & (W_NR - 1u)] = make_double2(u, pdmp_log(u));
-            W_ORDER();
+            PDMP_LDS_ORDER();
             filled += 64u;
             if (lane == 0) ctl->filled = filled;
             did = true;
@@ -312,7 +193,7 @@ __device__ __forceinline__ void trackp_helper(const ZzRunParams& P, unsigned cha
                      ((v.w > lo && v.w <= hi) ? 8u : 0u);
             }
             const uint32_t ncl = (uint32_t)__builtin_popcount(cm);
-            const uint32_t incl = w_scan_add_u32(ncl);
+            const uint32_t incl = scan_add_u32(ncl);
             const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
             uint32_t ix = incl - ncl, m_ = cm;
             while (m_ != 0u) {
@@ -322,7 +203,7 @@ __device__ __forceinline__ void trackp_helper(const ZzRunParams& P, unsigned cha
                 ix += 1;
                 m_ &= m_ - 1u;
             }
-            W_ORDER();
+            PDMP_LDS_ORDER();
             if ((uint32_t)lane < tot && (uint32_t)HPF[lane] < (uint32_t)d) {
                 const uint32_t i = (uint32_t)HPF[lane];
                 const char* const kl = kpb + (size_t)(i >> 3) * 128;
@@ -384,7 +265,7 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
             ctl->filled = 0u;
             ctl->consumed = 0u;
             ctl->exitf = 0u;
-            ctl->pf_tau = -W_INF;
+            ctl->pf_tau = -PDMP_INF;
             ctl->pf_dt = 0.0;
             ctl->pf_tb = 0.0;
         }
@@ -415,9 +296,9 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
         for (uint32_t b = lane; b < nblk; b += 64) {
             const double2* p = kp + (size_t)b * 8;
 #pragma unroll
-            for (int q = 0; q < 8; ++q) mloc = w_min(mloc, p[q].x);
+            for (int q = 0; q < 8; ++q) mloc = min_f64(mloc, p[q].x);
         }
-        tb = w_wave_min(mloc);
+        tb = wave_min_f64(mloc);
     }
     for (uint32_t b = lane; b < W_NBLK; b += 64) {
         uint32_t e = P_INFBITS;
@@ -433,11 +314,11 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
                     mi = q;
                 }
             }
-            e = (mk < W_INF) ? p_enc(mk, tb, mi) : P_INFBITS;
+            e = (mk < PDMP_INF) ? p_enc(mk, tb, mi) : P_INFBITS;
         }
         lbf[b] = e;
     }
-    W_ORDER();
+    PDMP_LDS_ORDER();
 
     uint64_t ph[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t ph_t0 = PROF ? (uint64_t)__builtin_readcyclecounter() : 0;
@@ -476,7 +357,7 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
         if (HW) {
             if (lane == 0) ctl->consumed = dnm;
             while (ctl->filled < dnm + W_WIN) __builtin_amdgcn_s_sleep(1);
-            W_ORDER();
+            PDMP_LDS_ORDER();
         } else {
             const uint32_t n0 = dnm + (((uint32_t)lane - dnm) & 63u);  // the smallest n >= dnm with n % 64 == lane
 #pragma unroll
@@ -500,7 +381,7 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
         WPHASE(7);
         auto draw = [&](uint32_t n) -> double {  // draw nm0 + n for dnm <= n < dnm + W_WIN (every lane calls it: ds_bpermute)
             if (HW) return ring[n & (W_NR - 1u)].x;
-            const double v0 = w_shfl(ureg[0], n & 63u), v1 = w_shfl(ureg[1], n & 63u);
+            const double v0 = bperm_f64(ureg[0], n & 63u), v1 = bperm_f64(ureg[1], n & 63u);
             return ((n >> 6) & 1u) ? v1 : v0;
         };
         auto drawlog = [&](uint32_t n) -> double {  // its logarithm (HW: computed once, by the helper wave, with the same pdmp_log)
@@ -541,7 +422,7 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
                 const uint32_t m_ = lanemin();
                 mloc = (m_ < mloc) ? m_ : mloc;
             }
-            uint32_t mqb = w_wave_min_u32(mloc);
+            uint32_t mqb = wave_min_u32_dpp(mloc);
             double mql = p_dec(mqb, tb);  // a lower bound of the next event time
             if (mqb < P_INFBITS && (need_rebase || mql - tb > 0.25)) {
                 // move the base of the bounds up to the front (a float resolves 2^-24 of its distance from the base)
@@ -560,9 +441,9 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
                 }
                 tb = mql;
                 need_rebase = false;
-                mqb = w_wave_min_u32(mloc);
+                mqb = wave_min_u32_dpp(mloc);
                 mql = p_dec(mqb, tb);
-                W_ORDER();
+                PDMP_LDS_ORDER();
             }
             if (mqb >= P_INFBITS) {
                 stalled = true;
@@ -575,7 +456,7 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
                     tau = mql + dt_sel;
                     tau_clipped = false;
                     if (stop_before && !(tau < T)) {
-                        tau = w_below(T);
+                        tau = pdmp_below(T);
                         tau_clipped = true;
                     }
                     if (tries >= 64) tau = mql;
@@ -592,7 +473,7 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
                         cm[c] = m_;
                         ncl += (uint32_t)__builtin_popcount(m_);
                     }
-                    incl = w_scan_add_u32(ncl);
+                    incl = scan_add_u32(ncl);
                     Cc = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
                     if (Cc <= (uint32_t)W_CMAX || tries >= 64) break;
                     // (HW: shrink to what the count asks for, not by half -- the 64 candidate lanes are the resource the threshold is steered by)
@@ -628,7 +509,7 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
             ctl->pf_dt = dt_used;
             ctl->pf_tb = tb;
         }
-        W_ORDER();
+        PDMP_LDS_ORDER();
         WPHASE(8);
         const bool crowded = Cc > (uint32_t)W_CMAX;  // exact ties beyond W_CMAX blocks (keys tied by construction): handled one event at a time
         if (crowded) Cc = (uint32_t)W_CMAX;
@@ -640,7 +521,7 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
         {
             const double2* const bl = kp + (size_t)cblk * 8;
 #pragma unroll
-            for (int q = 0; q < 8; ++q) q8[q] = isc ? bl[q] : make_double2(W_INF, 0.0);
+            for (int q = 0; q < 8; ++q) q8[q] = isc ? bl[q] : make_double2(PDMP_INF, 0.0);
         }
         const uint32_t cpos = isc ? (lbf[cblk] & 7u) : 0u;
         const uint32_t ci = cblk * 8u + cpos;
@@ -657,7 +538,7 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
         if (!LAT) c_nb = *reinterpret_cast<const uint4*>(&rci->gam0);  // G1[ci]: eight 16-bit ids
         // the exact minimum of the block, its position (the lowest on ties) and time, the minimum of the rest and its position: in the lane's own
         // registers, one pass for all candidates instead of one per 8 of them
-        double c_km = W_INF, c_rs = W_INF, c_tp = 0.0;
+        double c_km = PDMP_INF, c_rs = PDMP_INF, c_tp = 0.0;
         uint32_t c_pb = 0u;
         {
             double m1 = q8[0].x, t1 = q8[0].y;
@@ -669,12 +550,12 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
                 t1 = lt ? q8[q].y : t1;
                 p1 = lt ? (uint32_t)q : p1;
             }
-            double m2 = W_INF;
+            double m2 = PDMP_INF;
 #pragma unroll
-            for (int q = 0; q < 8; ++q) m2 = w_min(m2, ((uint32_t)q == p1) ? W_INF : q8[q].x);
+            for (int q = 0; q < 8; ++q) m2 = min_f64(m2, ((uint32_t)q == p1) ? PDMP_INF : q8[q].x);
             uint32_t p2 = 0u;
 #pragma unroll
-            for (int q = 7; q >= 0; --q) p2 = ((((uint32_t)q == p1) ? W_INF : q8[q].x) == m2) ? (uint32_t)q : p2;  // (the lowest position that holds it)
+            for (int q = 7; q >= 0; --q) p2 = ((((uint32_t)q == p1) ? PDMP_INF : q8[q].x) == m2) ? (uint32_t)q : p2;  // (the lowest position that holds it)
             if (isc) {
                 c_km = m1;
                 c_rs = m2;
@@ -683,7 +564,7 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
             }
         }
         // ---------------- events = candidates whose exact minimum is within the threshold; everybody refreshes its bound
-        if (isc) lbf[cblk] = (c_km < W_INF) ? p_enc(c_km, tb, c_pb & 7u) : P_INFBITS;
+        if (isc) lbf[cblk] = (c_km < PDMP_INF) ? p_enc(c_km, tb, c_pb & 7u) : P_INFBITS;
         bool isev = isc && c_km <= tau;
         if (crowded) {
             // the narrowest threshold still holds more than W_CMAX blocks (their bounds fall into one float bucket): no event this iteration --
@@ -691,7 +572,7 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
             isev = false;
             need_rebase = true;
         }
-        const double own = isev ? c_km : W_INF;
+        const double own = isev ? c_km : PDMP_INF;
         // rank = the number of events with a smaller key.  First on 15-bit images of the keys -- (key − front) scaled so that the window maps onto
         // 0 .. 32766, a monotone map: distinct images order like their keys -- two candidates per packed instruction (a 16-bit difference, its sign
         // bit, a 16-bit add) from one 128-byte table that every lane reads whole; candidates that are no events hold 32767.  Two events with one
@@ -704,10 +585,10 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
             uint16_t* const QK = TB;  // (the candidates' blocks are in registers by now)
             const double scale = 32766.0 * __builtin_amdgcn_rcp(tau - mql_sel);
             const double img = (own - mql_sel) * scale;
-            const uint32_t qi = isev ? (uint32_t)w_pos(img) : 32767u;
+            const uint32_t qi = isev ? (uint32_t)pos_part(img) : 32767u;
             const uint32_t qk = isev ? ((qi < 32766u) ? qi : 32766u) : 32767u;
             QK[lane] = (uint16_t)qk;
-            W_ORDER();
+            PDMP_LDS_ORDER();
             typedef short pk16 __attribute__((ext_vector_type(2)));
             typedef unsigned short upk16 __attribute__((ext_vector_type(2)));
             const pk16 own2 = {(short)qk, (short)qk};
@@ -727,13 +608,13 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
                 }
             }
             rank = (uint32_t)cnt.x + (uint32_t)cnt.y;
-            W_ORDER();
-            rsum = (uint32_t)__builtin_amdgcn_readlane((int)w_scan_add_u32(isev ? rank : 0u), 63);
+            PDMP_LDS_ORDER();
+            rsum = (uint32_t)__builtin_amdgcn_readlane((int)scan_add_u32(isev ? rank : 0u), 63);
         }
         if (rsum != (uint32_t)(nev * (nev - 1) / 2)) {
             // every lane compares its key with all of them, read from LDS one after the other (one address for the wave: a broadcast)
             KM[lane] = own;  // (KM is free here: the event slots are written into it only after the ranks are known)
-            W_ORDER();
+            PDMP_LDS_ORDER();
             rank = 0;
             for (uint32_t m0 = 0; m0 < Cc; m0 += 8) {  // (lanes past the candidates hold +Inf: reading them changes nothing)
                 double km[8];
@@ -742,22 +623,22 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
 #pragma unroll
                 for (uint32_t q = 0; q < 8; ++q) rank += (km[q] < own) ? 1u : 0u;
             }
-            W_ORDER();
-            rsum = (uint32_t)__builtin_amdgcn_readlane((int)w_scan_add_u32(isev ? rank : 0u), 63);
+            PDMP_LDS_ORDER();
+            rsum = (uint32_t)__builtin_amdgcn_readlane((int)scan_add_u32(isev ? rank : 0u), 63);
         }
         // exactly equal keys among the events (probability zero unless keys are tied by construction) give equal ranks -- ranks count the strictly
         // smaller keys, so their sum then falls short of 0 + 1 + .. + (nev − 1): one event this iteration, the tied minimum of the lowest block
         bool slot = isev;  // this lane's candidate takes event slot `rank`
         if (rsum != (uint32_t)(nev * (nev - 1) / 2)) {
-            const double mn = w_wave_min(own);
-            const uint32_t bsel = w_wave_min_u32((isev && own == mn) ? cblk : 0xffffffffu);
+            const double mn = wave_min_f64(own);
+            const uint32_t bsel = wave_min_u32_dpp((isev && own == mn) ? cblk : 0xffffffffu);
             slot = isev && cblk == bsel;  // (rank 0: nothing is smaller than the minimum)
             nev = 1;
         }
         // a candidate whose record was requested at the wrong position ends the list at its rank
         {
             const bool wrongpos = isev && (c_pb & 7u) != cpos;
-            const uint32_t wr = w_wave_min_u32(wrongpos ? rank : 0xffffffffu);
+            const uint32_t wr = wave_min_u32_dpp(wrongpos ? rank : 0xffffffffu);
             if (wr < (uint32_t)nev) nev = (int)wr;
         }
         // ---------------- lane r = event r: everything moves over from its candidate's lane, PUSHED to lane `rank` (ds_permute: one trip through the
@@ -777,7 +658,7 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
         const uint32_t e_bu = push32(cblk | (c_pb << 16));
         uint4 e_nb = make_uint4(~0u, ~0u, ~0u, ~0u);
         if (!LAT) e_nb = make_uint4(push32(c_nb.x), push32(c_nb.y), push32(c_nb.z), push32(c_nb.w));
-        W_ORDER();
+        PDMP_LDS_ORDER();
         WPHASE(9);
         C = nev;
         if (PROF) ph_iters += 1;
@@ -794,12 +675,12 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
                 status = PDMP_CHAIN_STALLED;  // (more than W_CMAX exactly tied block minima: keys tied by construction)
                 break;
             }
-            seldt = w_uniform(dt_used * 2.0);
+            seldt = uniform_f64(dt_used * 2.0);
             continue;
         }
         bool ev = lane < C;
-        const double tp = ev ? e_km : W_INF;  // the event time: the exact block minimum
-        const double rest = ev ? e_rs : W_INF;
+        const double tp = ev ? e_km : PDMP_INF;  // the event time: the exact block minimum
+        const double rest = ev ? e_rs : PDMP_INF;
         const double tprop_i = ev ? e_tp : 0.0;
         const uint32_t blk = e_bu & 0xffffu, pbe = e_bu >> 16;
         const double th = e_th, g_i = e_g, gd_i = e_gd, tg_i = e_tg;
@@ -808,9 +689,9 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
         const uint32_t i = ev ? (blk * 8u + (pbe & 7u)) : 0u;
         const uint32_t rarg = blk * 8u + (pbe >> 4);
         const double c_i = c_i2.x;
-        W_ORDER();
+        PDMP_LDS_ORDER();
         if (ev) SLB[lane] = (uint16_t)blk;
-        W_ORDER();
+        PDMP_LDS_ORDER();
         WPHASE(0);
         uint32_t rc_i = 0xffffu, k_i;
         if (LAT) {
@@ -824,18 +705,18 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
             // G1[i] came with the candidate's line
             k_i = nb_count(nb_i);
         }
-        W_ORDER();
+        PDMP_LDS_ORDER();
         // ---------------- rates from the tracked sums (src/sfact.jl:116-119 with g_i(t′) = g_i + gd_i (t′ − tg_i))
         const double g_now = g_i + gd_i * (tp - tg_i);
         const double gmu_i = e_gmu;
-        const double l = w_pos(((tmean == 2) ? g_now - gmu_i : g_now) * th);
+        const double l = pos_part(((tmean == 2) ? g_now - gmu_i : g_now) * th);
         // the bound in force (src/fact_samplers.jl:50-54), re-derived: it was computed at t_old (the coordinate's last proposal or the last
         // re-basing of its sums, whichever came later: stored with the key) from exactly these operands
         const double told_i = tprop_i;
         const double g_told = g_i + gd_i * (told_i - tg_i);
         const double a_i = c_i + (tmean ? g_told - gmu_i : g_told) * th;
         const double b_i = c_i2.y + th * gd_i;
-        const double lbound = w_pos(a_i + b_i * (tp - told_i));
+        const double lbound = pos_part(a_i + b_i * (tp - told_i));
         // ---------------- accept chain: offsets and outcomes as a fix-point (every round settles the events up to the next change).  Event r's coin is
         // draw 2 r + the draws the accepted events before it took beyond two (k − 1 each, k <= 8): three ballots of the accept mask by the bits of
         // k − 1, counted below the lane (v_mbcnt) -- no prefix scan
@@ -926,10 +807,10 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
             uint32_t* const ZA = reinterpret_cast<uint32_t*>(smem + L::NB);  // (the ids' room of the LAT = false instantiation)
             const uint64_t ab = __ballot(acc) & ((C < 64) ? ((1ull << C) - 1ull) : ~0ull);
             if (lane < W_AMAX) ZA[lane] = 0x00fffefeu;  // (an empty slot: event 255 -- behind every lane, so it disturbs none, and a key it claims is stored by its lane all the same)
-            W_ORDER();
+            PDMP_LDS_ORDER();
             if (acc && lane < C)
                 ZA[__builtin_amdgcn_mbcnt_hi((uint32_t)(ab >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ab, 0u))] = rc_i | ((uint32_t)lane << 16);
-            W_ORDER();
+            PDMP_LDS_ORDER();
             const uint4 z0 = reinterpret_cast<const uint4*>(ZA)[0], z1 = reinterpret_cast<const uint4*>(ZA)[1];
             const uint32_t zz[8] = {z0.x, z0.y, z0.z, z0.w, z1.x, z1.y, z1.z, z1.w};
             bool conf = false;
@@ -975,7 +856,7 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
                 NB4[sl] = nb_i;
                 ACL[sl] = (uint16_t)lane;
             }
-            W_ORDER();
+            PDMP_LDS_ORDER();
             const uint32_t jt = (g < nacc0) ? (uint32_t)NB16[lane] : 0xffffu;  // (slot g, member gl: NB16[8 g + gl])
             const uint32_t jt2 = jt | (jt << 16), i2 = i | (i << 16);
             uint64_t confb = 0, ghit = 0;
@@ -1023,7 +904,7 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
         const uint64_t accball = __ballot(acc);
         const int nacc_it = __popcll(accball);
         if (LAT && !HW && acc) ACL[__popcll(accball & ((1ull << lane) - 1ull))] = (uint16_t)lane;  // (LAT = false: written with the zones, same slots; HW on the lattice: not read)
-        W_ORDER();
+        PDMP_LDS_ORDER();
         WPHASE(2);
         // ---------------- accepted events, one 8-lane group each: members of G1[i] (ascending, :131-135)
         // (the groups of the accepted events are the LAST groups of the wave, in event order: the low lanes -- lane r = event r -- are then free
@@ -1035,7 +916,7 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
             double tpa, gj, gdj, keyj, xa, txa, Ia, th_ia, rowmin_a;
             uint64_t acc_ia;
         };
-        double key2 = W_INF;  // the new key of this lane's rejected proposal (event lanes)
+        double key2 = PDMP_INF;  // the new key of this lane's rejected proposal (event lanes)
         auto group_stage = [&](const int base, const int ng, const bool first) -> GOut {
             GOut o;
             const int g0 = 8 - ng;
@@ -1058,7 +939,7 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
             const uint32_t off_b = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(ea << 2), (int)off);
             const uint32_t ia = gact ? ia_b : 0u;
             const uint32_t blka = gact ? (uint32_t)SLB[ea] : 0u;
-            const double tpa_b = w_shfl(tp, ea);
+            const double tpa_b = bperm_f64(tp, ea);
             const double tpa = gact ? tpa_b : 0.0;
             const uint32_t offa = gact ? off_b : 0u;
             uint32_t ka = 0, jm = ia;
@@ -1105,7 +986,7 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
             if (tmean) gmu_j = rj->tacc;
             double2 cjm2 = *reinterpret_cast<const double2*>(&rj->c);
             asm volatile("" : "+v"(cjm2.x), "+v"(cjm2.y));  // (one 16-byte load with the others: hipcc sank the second half under the select below, a dependent round trip)
-            const double resta_b = w_shfl(rest, ea);  // the accepted event's block without it, and where that minimum sits
+            const double resta_b = bperm_f64(rest, ea);  // the accepted event's block without it, and where that minimum sits
             const uint32_t rarga_b = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(ea << 2), (int)rarg);
             // ---------------- ONE evaluation of the new bound and key per lane (logarithm, two divisions, square root): the re-bound of a
             // rejected proposal (:137-140) in its event lane (first pass), the re-bound of a member of G1 (:131-135) in its group lane.  A lane
@@ -1130,15 +1011,15 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
                 const double gg = tmean ? gg0 - (mine ? gmu_j : gmu_i) : gg0;
                 a2l = cc + gg * tt;
                 b2l = cc100 + tt * gdd;
-                key2l = (mine ? tpa : tp) + w_poisson_time_L(a2l, b2l, Lg);
+                key2l = (mine ? tpa : tp) + poisson_time_L(a2l, b2l, Lg);
             }
-            const double keyj = mem ? key2l : W_INF;
+            const double keyj = mem ? key2l : PDMP_INF;
             if (first) {
                 if (__ballot(ev && !acc && gact) != 0) {
                     const double Le = drawlog(dnm + ((off + 1u < W_WIN - 1u) ? off + 1u : W_WIN - 1u));
                     const double a2e = c_i + (tmean ? g_now - gmu_i : g_now) * th;
                     const double b2e = c_i2.y + th * gd_i;
-                    const double k2e = tp + w_poisson_time_L(a2e, b2e, Le);
+                    const double k2e = tp + poisson_time_L(a2e, b2e, Le);
                     if (gact) key2l = k2e;
                 }
                 key2 = key2l;
@@ -1152,16 +1033,16 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
             }
             // the accepted event's block: a LOWER BOUND of its new minimum is enough (level 1 holds bounds): the smaller of the block without the
             // event -- which may still count a member's OLD key: then the bound is stale low and costs a look later -- and the members' new keys in it
-            const double kin = (mem && (jm >> 3) == blka) ? keyj : W_INF;
-            const double kinmin = w_grp8_min(kin);
+            const double kin = (mem && (jm >> 3) == blka) ? keyj : PDMP_INF;
+            const double kinmin = grp8_min_f64(kin);
             // position bits of the member that holds it (the lowest lane of the group on ties): a DPP minimum of (lane in group, position)
             const uint32_t wkey = (gact && kin == kinmin) ? (((uint32_t)gl << 3) | (jm & 7u)) : 0xffu;
             const uint32_t jwin = w_grp8_min_u32(wkey);  // (no lane of an inactive group is read below)
             const bool restwins = resta_b <= kinmin;
             const double rowmin_a = restwins ? resta_b : kinmin;
             const uint32_t cand_a = restwins ? (rarga_b & 7u) : (jwin & 7u);
-            const double keymin = w_grp8_min(keyj);
-            if (gact && gl == 0) EX[ea] = w_min(rowmin_a, keymin);
+            const double keymin = grp8_min_f64(keyj);
+            if (gact && gl == 0) EX[ea] = min_f64(rowmin_a, keymin);
             // (the reflecting coordinate's fields are used under lane masks only: named here, or the path around the commit carries their loads to
             // the loop's head, where the wait for them is a wait for the commit's stores)
             asm volatile("" ::"v"(xa), "v"(txa), "v"(Ia), "v"(acc_ia));
@@ -1190,7 +1071,7 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
         };
         const GOut G0 = group_stage(0, nacc_it, true);
         // new minimum of the popped block of a rejected event, and what the event exposes
-        double rowmin = W_INF;
+        double rowmin = PDMP_INF;
         uint32_t cand = i;
         if (ev && !acc) {
             const bool mine = key2 < rest || (key2 == rest && i < rarg);
@@ -1198,13 +1079,13 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
             cand = mine ? i : rarg;
         }
         if (ev && !acc) EX[lane] = rowmin;  // (rowmin <= key2: the new key is one of its candidates)
-        W_ORDER();
+        PDMP_LDS_ORDER();
         WPHASE(3);
         // ---------------- validate: all earlier events commit, zones disjoint, nothing produced or exposed earlier than t′
         uint32_t Rc;
         {
-            const double prev = (lane > 0 && lane <= C) ? EX[lane - 1] : W_INF;  // what event lane − 1 exposes
-            const double pref = w_scan_min_f64(prev);  // exclusive prefix minimum
+            const double prev = (lane > 0 && lane <= C) ? EX[lane - 1] : PDMP_INF;  // what event lane − 1 exposes
+            const double pref = scan_min_f64(prev);  // exclusive prefix minimum
             const bool okr = ev && (lane == 0 || pref > tp);  // (zone conflicts ended the candidate list already)
             const uint64_t bad = ~__ballot(okr);
             const uint32_t r_ok = bad ? (uint32_t)(__ffsll((unsigned long long)bad) - 1) : 64u;
@@ -1232,16 +1113,16 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
             // the two-wave form (and the one-wave forms of an under-occupied launch: hw_target set by the launcher) aims the raw candidate count at a target -- a candidate read in vain costs an under-occupied device nothing, idle
             // candidate lanes do -- moving a fraction of the way per iteration
             const double want = (double)P.hw_target / (double)(Craw > 0 ? Craw : 1);
-            seldt = w_uniform(dt_used * (1.0 + P.hw_gain * (((want < 2.0) ? want : 2.0) - 1.0)));
+            seldt = uniform_f64(dt_used * (1.0 + P.hw_gain * (((want < 2.0) ? want : 2.0) - 1.0)));
         } else {
-            seldt = w_uniform(dt_used * (((int)Rc >= Craw) ? W_GROW : (((int)Rc + (int)W_SLACK < Craw) ? W_SHRINK : 1.0)));
+            seldt = uniform_f64(dt_used * (((int)Rc >= Craw) ? W_GROW : (((int)Rc + (int)W_SLACK < Craw) ? W_SHRINK : 1.0)));
         }
         WPHASE(4);
         // ---------------- commit the valid prefix
         const bool commit = ev && (uint32_t)lane < Rc;
         if (commit && !acc) {  // a rejected proposal: ONE 16-byte store (the record stays clean), and the block's new bound
             if (!(rekey_by < Rc)) kp[i] = make_double2(key2, tp);  // (else a later accepted neighbour of this iteration re-bounds i: its pair)
-            lbf[blk] = (rowmin < W_INF) ? p_enc(rowmin, tb, cand & 7u) : P_INFBITS;
+            lbf[blk] = (rowmin < PDMP_INF) ? p_enc(rowmin, tb, cand & 7u) : P_INFBITS;
         }
         const uint64_t acc_c = accball & ((Rc < 64u) ? ((1ull << Rc) - 1ull) : ~0ull);
         auto commit_groups = [&](const GOut& o) {
@@ -1274,19 +1155,19 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
                         evout[ntrace0 + dnacc + rnk] = e;
                     }
                 }
-                if (gl == 0) lbf[o.blka] = (o.rowmin_a < W_INF) ? p_enc(o.rowmin_a, tb, o.cand_a) : P_INFBITS;  // (lane 0 of the group stores the bound)
+                if (gl == 0) lbf[o.blka] = (o.rowmin_a < PDMP_INF) ? p_enc(o.rowmin_a, tb, o.cand_a) : P_INFBITS;  // (lane 0 of the group stores the bound)
             }
             return gcommit;
         };
         const bool gc0 = commit_groups(G0);
-        W_ORDER();
+        PDMP_LDS_ORDER();
         WPHASE(5);
         // ---------------- bounds of the blocks of re-bounded neighbours: lowered where the new key is below them (an LDS atomic minimum); a key
         // that ROSE leaves its block's bound stale low, which costs a look at the block later and nothing else
         {
-            if (gc0 && G0.mem && (G0.jm >> 3) != G0.blka && G0.keyj < W_INF) atomicMin(&lbf[G0.jm >> 3], p_enc(G0.keyj, tb, G0.jm & 7u));
+            if (gc0 && G0.mem && (G0.jm >> 3) != G0.blka && G0.keyj < PDMP_INF) atomicMin(&lbf[G0.jm >> 3], p_enc(G0.keyj, tb, G0.jm & 7u));
         }
-        W_ORDER();
+        PDMP_LDS_ORDER();
         WPHASE(6);
         // ---------------- counters; the violating proposal itself (counted, acc bumped, then error(...), :120-124)
         if (Rc > 0u) {
@@ -1296,11 +1177,11 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
             idle = 0;
             dnacc += (uint32_t)__popcll(acc_c);
             dnm += offL + costL;
-            t_last = w_readlane(tp, (int)(Rc - 1u));
-            if (acc_c) t_event = w_readlane(tp, 63 - __builtin_clzll(acc_c));
+            t_last = readlane_f64(tp, (int)(Rc - 1u));
+            if (acc_c) t_event = readlane_f64(tp, 63 - __builtin_clzll(acc_c));
         }
         if (vsel >= 0) {  // (vsel == Rc: every earlier event is committed)
-            const double tpv = w_readlane(tp, vsel);
+            const double tpv = readlane_f64(tp, vsel);
             const uint32_t iv = (uint32_t)__builtin_amdgcn_readlane((int)i, vsel);
             if (lane == 0) kp[iv].y = tpv;
             dnum += 1;
@@ -1310,7 +1191,7 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
             status = PDMP_CHAIN_BOUND_VIOLATED;
         }
         if (status != PDMP_CHAIN_OK) break;
-        W_ORDER();
+        PDMP_LDS_ORDER();
     }
 
     if (PROF && P.dbg && chain == 0 && lane == 0) {
@@ -1469,13 +1350,13 @@ int launch_zz_keys_to_pairs(const double* keys, void* kp, int64_t n, double t0, 
 }
 
 #ifdef PDMP_EXTRA_KERNELS
-// pdmp_debug_math_eval: this unit's own copies, called as they are
+// pdmp_debug_math_eval: the shared scalars (pdmp_device.hpp) this unit calls, as compiled here
 namespace {
 struct TrackpMathEval {
     __device__ double operator()(int fn, double a, double b, double c, double*) const {
         switch (fn) {
-        case PDMP_MATH_PT_W_L: return w_poisson_time_L(a, b, pdmp_log(c));
-        default: return w_pos(a);  // PDMP_MATH_POS_W
+        case PDMP_MATH_PT_W_L: return poisson_time_L(a, b, pdmp_log(c));
+        default: return pos_part(a);  // PDMP_MATH_POS_W
         }
     }
 };
