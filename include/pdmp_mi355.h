@@ -232,6 +232,15 @@ pdmp_status pdmp_ensemble_final_state(pdmp_ensemble* ens, int64_t chain_first, i
  * mean(trace), src/trace.jl:182-200).  Requires all chains paused with PDMP_RUN_STOP_BEFORE at time T.
  * Adds, for this batch [T_prev, T], Y = (1/ΔT) ∫ x_i dt per chain and accumulates over chains:
  *   sum_y[i] += Y, sum_y2[i] += Y*Y   (device reduction; outputs are host [d] arrays, may be NULL)
+ *
+ * Which T may be read (this call, pdmp_ensemble_ess_begin / _batch and pdmp_ensemble_path_integrals; checked on the host from one copy
+ * of the chain headers per read, else PDMP_ERR_INVALID with the chain and the times in pdmp_last_error(), and neither the previous
+ * batch's J nor any accumulator is touched): J_i(T) continues every coordinate linearly from its own clock to T, which is the path's
+ * integral only while no event of the chain lies in between.  So every chain must be PDMP_CHAIN_OK (not TRACE_FULL, PAUSED,
+ * BOUND_VIOLATED or STALLED short of the horizon: drain / run again first) and  t_last <= T <= horizon of the last run  (t0 before the
+ * first run; t_last of pdmp_chain_counters).  A PDMP_RUN_REFERENCE_TAIL run processes one proposal at or past its horizon and is
+ * refused at it.  With a refresh clock (λref > 0) proposals are not processed in time order and t_last is not the latest of them: T must
+ * then EQUAL the horizon of the last run (a PDMP_RUN_STOP_BEFORE run, by the rule above).
  */
 pdmp_status pdmp_ensemble_batch_means(pdmp_ensemble* ens, double T_prev, double T, double* sum_y, double* sum_y2);
 

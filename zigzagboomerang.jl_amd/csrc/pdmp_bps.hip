@@ -950,14 +950,15 @@ __global__ __launch_bounds__(256) void dense_batch_means_kernel(const double* J,
     if (i >= d) return;
     const int64_t c0 = (int64_t)blockIdx.y * chains_per_group;
     const int64_t c1 = (c0 + chains_per_group < nchains) ? (c0 + chains_per_group) : nchains;
-    const double inv = 1.0 / (T - T_prev);
+    double wh, wl;
+    two_diff(T, T_prev, wh, wl);
     double s1 = 0.0, s2 = 0.0;
     for (int64_t ch = c0; ch < c1; ++ch) {
         const double Jc = J[ch * d + i];
-        const double y = (Jc - jprev[ch * d + i]) * inv;
+        const BatchMean b = batch_mean_exactly_rounded(Jc, jprev[ch * d + i], wh, wl);
         jprev[ch * d + i] = Jc;
-        s1 += y;
-        s2 += y * y;
+        s1 += b.y;
+        s2 += b.y2;
     }
     atomicAdd(sum_y + i, s1);
     atomicAdd(sum_y2 + i, s2);
@@ -970,7 +971,8 @@ __global__ __launch_bounds__(256) void dense_ess_kernel(const double* J, double*
     if (i >= d) return;
     const int64_t c0 = (int64_t)blockIdx.y * chains_per_group;
     const int64_t c1 = (c0 + chains_per_group < nchains) ? (c0 + chains_per_group) : nchains;
-    const double inv = (mode == 0) ? 0.0 : 1.0 / (T - T_prev);
+    double wh = 1.0, wl = 0.0;
+    if (mode != 0) two_diff(T, T_prev, wh, wl);
     double s1 = 0.0, s2 = 0.0;
     for (int64_t ch = c0; ch < c1; ++ch) {
         const double Jc = J[ch * d + i];
@@ -978,10 +980,10 @@ __global__ __launch_bounds__(256) void dense_ess_kernel(const double* J, double*
             jprev[ch * d + i] = Jc;
             jstart[ch * d + i] = Jc;
         } else {
-            const double y = (Jc - ((mode == 1) ? jprev : jstart)[ch * d + i]) * inv;
+            const BatchMean b = batch_mean_exactly_rounded(Jc, ((mode == 1) ? jprev : jstart)[ch * d + i], wh, wl);
             if (mode == 1) jprev[ch * d + i] = Jc;
-            s1 += y;
-            s2 += y * y;
+            s1 += b.y;
+            s2 += b.y2;
         }
     }
     if (mode == 1) {

@@ -169,6 +169,7 @@ struct pdmp_ensemble {
     const char* last_kernel = "";  // event-loop kernel of the last pdmp_ensemble_run (pdmp_debug_last_kernel)
     int32_t lattice_n = 0;  // the flow's graph is the n x n 5-point lattice in column-major numbering (0: it is not)
     double t0_state = 0.0;
+    double run_T = 0.0;  // horizon of the last run (t0 before the first): no read of the path integrals beyond it (fact_integrals_at)
     DevBuf<double> d_jstart, d_essacc;  // pdmp_ensemble_ess_*
     double ess_T0 = 0.0, ess_Tlast = 0.0;
     int64_t ess_batches = -1;  // -1: no ess_begin yet
@@ -1485,6 +1486,7 @@ static pdmp_status init_state(pdmp_ensemble* e, double t0, const double* x0, con
     }
     P.track = e->track ? 1 : 0;
     e->t0_state = t0;
+    e->run_T = t0;
     if (sticky || e->local_bound) {
         if (e->d_thf.n != (size_t)(n * d) && (st = e->d_thf.alloc((size_t)(n * d))) != PDMP_OK) return st;
         P.thf = e->d_thf.p;
@@ -1664,6 +1666,7 @@ static pdmp::BpsMomParams bps_moments_params(const pdmp_ensemble* e);
 
 pdmp_status pdmp_ensemble_run(pdmp_ensemble* e, double T, int flags, void* stream) {
     pdmp_status st = ensemble_run_impl(e, T, flags, stream);
+    if (st == PDMP_OK && e->cfg.sampler != PDMP_SAMPLER_BPS) e->run_T = T;  // (only a launch that went out moves the horizon: fact_integrals_at)
     if (st == PDMP_OK && e->deferred_k >= 0) st = launch_deferred_consumer(e);  // (behind the event loop's launch: see pdmp_ensemble_consume_async)
     return st;
 }
@@ -2089,6 +2092,7 @@ pdmp_status pdmp_ensemble_final_state(pdmp_ensemble* e, int64_t chain_first, int
 }
 
 static pdmp_status ess_ready(pdmp_ensemble* e);
+static pdmp_status fact_integrals_at(pdmp_ensemble* e, double T);
 static pdmp_status bps_moments_at(pdmp_ensemble* e, double T, int64_t chain_first, int64_t n, bool two);
 
 pdmp_status pdmp_ensemble_batch_means(pdmp_ensemble* e, double T_prev, double T, double* sum_y, double* sum_y2) {
@@ -2101,6 +2105,7 @@ pdmp_status pdmp_ensemble_batch_means(pdmp_ensemble* e, double T_prev, double T,
     const bool bps = e->cfg.sampler == PDMP_SAMPLER_BPS;
     pdmp_status st;
     if (bps && (st = bps_moments_at(e, T, 0, n, false)) != PDMP_OK) return st;  // J1(T) of every chain into b_jT (the validity rule first)
+    if (!bps && (st = fact_integrals_at(e, T)) != PDMP_OK) return st;  // (before jprev is allocated or touched)
     if (e->d_jprev.n != (size_t)(n * d)) {
         if ((st = e->d_jprev.alloc((size_t)(n * d))) != PDMP_OK) return st;
         HIP_TRY(hipMemsetAsync(e->d_jprev.p, 0, (size_t)(n * d) * sizeof(double), e->stream));  // (same stream as the kernel: the ensemble's stream is non-blocking, the null stream does not order against it)
@@ -2130,6 +2135,38 @@ static pdmp_status ess_ready(pdmp_ensemble* e) {
     return PDMP_OK;
 }
 
+// The factorised counterpart of bps_moments_at's rule.  J_i(T) = I_i + dt (x_i + θ_i dt / 2), dt = T - t_i, is the integral of the sampled path
+// only where no event of the chain lies between a coordinate's clock and T: every chain PDMP_CHAIN_OK (a chain that stopped short of the
+// horizon -- TRACE_FULL, PAUSED, BOUND_VIOLATED, STALLED -- would be extrapolated through events it has not sampled yet), T not before the
+// latest proposal the chain has processed (a reference-tail run passes its horizon: the coordinate that reflected there would be extrapolated
+// backwards with its new velocity) and T not beyond the horizon of the last run (t0 before the first).  Without a refresh clock the
+// proposals come off the queue in time order and the header's t_last, the time of the last one, is the latest; with one they do not
+// (src/sfact.jl:84-85 re-bounds at stale clocks), t_last may lie below an earlier proposal, and the only T known to be at or past all of
+// them is the horizon of a run that stopped before it.  With t0 != 0 the first proposals lie before t0 (the reference draws the first
+// queue times without adding t0): t_last <= T holds for them as it must.  One copy of the chain headers per read; nothing on the hot path.
+static pdmp_status fact_integrals_at(pdmp_ensemble* e, double T) {
+    const int64_t n = e->cfg.nchains;
+    if (!(T <= e->run_T))
+        return fail(PDMP_ERR_INVALID, "T = %.17g lies past the horizon %.17g of the last run (t0 before the first): the path is not sampled there "
+                                      "(run to T with PDMP_RUN_STOP_BEFORE)", T, e->run_T);
+    if (e->lambda_ref > 0 && T != e->run_T)
+        return fail(PDMP_ERR_INVALID, "T = %.17g is not the horizon %.17g of the last run: with a refresh clock the proposals are not processed in "
+                                      "time order and the path integrals are read at the end of a PDMP_RUN_STOP_BEFORE run only", T, e->run_T);
+    std::vector<pdmp::DevChain> h((size_t)n);
+    HIP_TRY(hipMemcpy(h.data(), e->d_hdr.p, h.size() * sizeof(pdmp::DevChain), hipMemcpyDeviceToHost));
+    for (int64_t k = 0; k < n; ++k) {
+        const uint32_t cs = h[(size_t)k].c.status;
+        const double tl = h[(size_t)k].c.t_last;
+        if (cs != PDMP_CHAIN_OK)
+            return fail(PDMP_ERR_INVALID, "chain %lld: status %u at t = %.17g (trace full / paused / bound violated / stalled): it has not reached "
+                                          "T = %.17g, its path integrals are not defined there (drain and run again)", (long long)k, cs, tl, T);
+        if (!(tl <= T))
+            return fail(PDMP_ERR_INVALID, "chain %lld: T = %.17g lies before the chain's last proposal at %.17g (a reference-tail run passes T; "
+                                          "run to T with PDMP_RUN_STOP_BEFORE)", (long long)k, T, tl);
+    }
+    return PDMP_OK;
+}
+
 pdmp_status pdmp_ensemble_ess_begin(pdmp_ensemble* e, double T0) {
     pdmp_status st = ess_ready(e);
     if (st != PDMP_OK) return st;
@@ -2138,6 +2175,7 @@ pdmp_status pdmp_ensemble_ess_begin(pdmp_ensemble* e, double T0) {
     const int64_t d = e->cfg.d, n = e->cfg.nchains;
     const bool bps = e->cfg.sampler == PDMP_SAMPLER_BPS;
     if (bps && (st = bps_moments_at(e, T0, 0, n, false)) != PDMP_OK) return st;
+    if (!bps && (st = fact_integrals_at(e, T0)) != PDMP_OK) return st;
     if (e->d_jprev.n != (size_t)(n * d) && (st = e->d_jprev.alloc((size_t)(n * d))) != PDMP_OK) return st;
     if (e->d_jstart.n != (size_t)(n * d) && (st = e->d_jstart.alloc((size_t)(n * d))) != PDMP_OK) return st;
     if (e->d_essacc.n != (size_t)(4 * d) && (st = e->d_essacc.alloc((size_t)(4 * d))) != PDMP_OK) return st;
@@ -2164,6 +2202,7 @@ pdmp_status pdmp_ensemble_ess_batch(pdmp_ensemble* e, double T) {
         if ((st = bps_moments_at(e, T, 0, e->cfg.nchains, false)) != PDMP_OK) return st;
         rc = pdmp::launch_dense_ess(e->b_jT.p, e->d_jprev.p, e->d_jstart.p, e->cfg.d, e->cfg.nchains, 1, e->ess_Tlast, T, e->d_essacc.p, e->stream);
     } else {
+        if ((st = fact_integrals_at(e, T)) != PDMP_OK) return st;
         if ((st = ensure_canon(e)) != PDMP_OK) return st;
         rc = pdmp::launch_zz_ess(e->d_rec.p, e->track ? 128 : 64, e->d_jprev.p, e->d_jstart.p, e->cfg.d, e->cfg.nchains, 1, e->ess_Tlast, T,
                                  e->d_essacc.p, e->stream);
@@ -2498,6 +2537,7 @@ pdmp_status pdmp_ensemble_path_integrals(pdmp_ensemble* e, double T, int64_t npr
         if ((st = bps_moments_at(e, T, 0, n, false)) != PDMP_OK) return st;
         rc = pdmp::launch_dense_gather(e->b_jT.p, d, n, dp.p, nprobe, dout.p, e->stream);
     } else {
+        if ((st = fact_integrals_at(e, T)) != PDMP_OK) return st;
         if ((st = ensure_canon(e)) != PDMP_OK) return st;
         rc = pdmp::launch_zz_path_integrals(e->d_rec.p, e->track ? 128 : 64, d, n, dp.p, nprobe, T, dout.p, e->stream);
     }
@@ -2623,6 +2663,7 @@ pdmp_status pdmp_ensemble_run_partitioned(pdmp_ensemble* e, double T, int K, dou
     HIP_TRY(hipEventRecord(e->ev0, s));
     const int rc = pdmp::launch_zz_partitioned(P, e->cfg.nchains, s);
     if (rc != 0) return fail(PDMP_ERR_HIP, "zz_partitioned_run launch failed (%d)", rc);
+    e->run_T = T;
     HIP_TRY(hipEventRecord(e->ev1, s));
     e->timed = true;
     HIP_TRY(hipStreamSynchronize(s));  // (the tables of this call live until here)

@@ -198,4 +198,36 @@ __device__ __forceinline__ double poisson_time_L(double a, double b, double L) {
     return PDMP_INF;
 }
 
+// One batch mean and its square to ONE rounding each.  y = (J − Jprev)/(T − T_prev) formed as written costs three roundings (the
+// difference, the reciprocal, the product) and y·y doubles them and adds one: 7u on a term of ΣY², more than the (n + 3)u a sum of n
+// terms is held to when n is small (tests/test_gpu_path_integrals.py).  Here the two differences are kept exactly
+// as unevaluated pairs (TwoSum), the quotient is carried as a pair (error ~u²) and y and y² are each rounded once from it.  Explicit
+// fma() is meant: the units are compiled with -ffp-contract=off, which leaves explicit calls alone.  Used by the reductions of both families
+// (zz_batch_means_kernel / zz_ess_kernel, dense_batch_means_kernel / dense_ess_kernel): not on any hot path.
+struct BatchMean {
+    double y, y2;
+};
+__device__ __forceinline__ void two_diff(double a, double b, double& h, double& l) {  // a − b = h + l exactly
+    h = a - b;
+    const double bb = a - h;
+    l = (a - (h + bb)) + (bb - b);
+}
+__device__ __forceinline__ BatchMean batch_mean_exactly_rounded(double J, double Jprev, double wh, double wl) {
+    double dh, dl;
+    two_diff(J, Jprev, dh, dl);
+    const double q1 = dh / wh;
+    const double p = q1 * wh;
+    const double pe = fma(q1, wh, -p);                      // q1·wh = p + pe exactly
+    const double r = (((dh - p) - pe) + dl) - q1 * wl;      // (dh + dl) − q1·(wh + wl), to ~u² of the quotient's scale
+    const double q2 = r / wh;
+    const double yh = q1 + q2;                              // y rounded once
+    const double yl = q2 - (yh - q1);                       // (q1, q2) renormalised: y = yh + yl to ~u²
+    const double sh = yh * yh;
+    const double se = fma(yh, yh, -sh);
+    BatchMean out;
+    out.y = yh;
+    out.y2 = sh + (se + 2.0 * (yh * yl));                   // (yh + yl)² rounded once
+    return out;
+}
+
 }  // namespace pdmp

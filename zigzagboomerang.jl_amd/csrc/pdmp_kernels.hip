@@ -4111,16 +4111,17 @@ __global__ __launch_bounds__(256) void zz_batch_means_kernel(const ZzRec* rec0, 
     if (i >= d) return;
     const int64_t c0 = (int64_t)blockIdx.y * chains_per_group;
     const int64_t c1 = (c0 + chains_per_group < nchains) ? (c0 + chains_per_group) : nchains;
-    const double inv = 1.0 / (T - T_prev);
+    double wh, wl;
+    two_diff(T, T_prev, wh, wl);
     double s1 = 0.0, s2 = 0.0;
     for (int64_t ch = c0; ch < c1; ++ch) {
         const ZzRec* r = reinterpret_cast<const ZzRec*>(reinterpret_cast<const char*>(rec0) + (ch * d + i) * rec_stride);
         const double dt = T - r->t;
         const double J = r->I + dt * (r->x + r->th * (dt * 0.5));
-        const double y = (J - jprev[ch * d + i]) * inv;
+        const BatchMean b = batch_mean_exactly_rounded(J, jprev[ch * d + i], wh, wl);
         jprev[ch * d + i] = J;
-        s1 += y;
-        s2 += y * y;
+        s1 += b.y;
+        s2 += b.y2;
     }
     atomicAdd(sum_y + i, s1);
     atomicAdd(sum_y2 + i, s2);
@@ -4136,7 +4137,8 @@ __global__ __launch_bounds__(256) void zz_ess_kernel(const ZzRec* rec0, int64_t 
     if (i >= d) return;
     const int64_t c0 = (int64_t)blockIdx.y * chains_per_group;
     const int64_t c1 = (c0 + chains_per_group < nchains) ? (c0 + chains_per_group) : nchains;
-    const double inv = (mode == 0) ? 0.0 : 1.0 / (T - T_prev);
+    double wh = 1.0, wl = 0.0;
+    if (mode != 0) two_diff(T, T_prev, wh, wl);
     double s1 = 0.0, s2 = 0.0;
     for (int64_t ch = c0; ch < c1; ++ch) {
         const ZzRec* r = reinterpret_cast<const ZzRec*>(reinterpret_cast<const char*>(rec0) + (ch * d + i) * rec_stride);
@@ -4146,10 +4148,10 @@ __global__ __launch_bounds__(256) void zz_ess_kernel(const ZzRec* rec0, int64_t 
             jprev[ch * d + i] = J;
             jstart[ch * d + i] = J;
         } else {
-            const double y = (J - ((mode == 1) ? jprev : jstart)[ch * d + i]) * inv;
+            const BatchMean b = batch_mean_exactly_rounded(J, ((mode == 1) ? jprev : jstart)[ch * d + i], wh, wl);
             if (mode == 1) jprev[ch * d + i] = J;
-            s1 += y;
-            s2 += y * y;
+            s1 += b.y;
+            s2 += b.y2;
         }
     }
     if (mode == 1) {

@@ -354,6 +354,9 @@ class Ensemble:
         return dict(t=t, x=x, theta=th, acc=acc, c=c)
 
     def batch_means(self, T_prev, T):
+        """(ΣY, ΣY²) over chains of the batch means Y = (J(T) − J(T_prev)) / (T − T_prev) (pdmp_ensemble_batch_means).  T must be a time
+        every chain's state describes: all chains CHAIN_OK and t_last <= T <= the horizon of the last run (with a refresh clock: T equal to
+        it), i.e. the end of a finished RUN_STOP_BEFORE slice; anything else raises PdmpError(PDMP_ERR_INVALID) and changes nothing."""
         s1 = np.empty(self.d)
         s2 = np.empty(self.d)
         _lib.check(self._L.pdmp_ensemble_batch_means(self._h, float(T_prev), float(T), _ptr(s1), _ptr(s2)))
@@ -441,13 +444,15 @@ class Ensemble:
         _lib.check(self._L.pdmp_ensemble_set_path_integrals(self._h, int(bool(enable))))
 
     def path_integrals(self, T, probes):
-        """J_i(T) = ∫ x_i dt of every chain at the probe coordinates: [nchains x len(probes)] (pdmp_ensemble_path_integrals)."""
+        """J_i(T) = ∫ x_i dt of every chain at the probe coordinates: [nchains x len(probes)] (pdmp_ensemble_path_integrals).
+        T as for batch_means: the end of a finished RUN_STOP_BEFORE slice (all chains CHAIN_OK, t_last <= T <= the last run's horizon)."""
         probes = _i64(probes)
         out = np.empty((self.nchains, probes.size))
         _lib.check(self._L.pdmp_ensemble_path_integrals(self._h, float(T), int(probes.size), _ptr(probes), _ptr(out)))
         return out
 
     def ess_begin(self, T0):
+        """Snapshot J(T0) of every chain; T0 and every later ess_batch(T) obey batch_means' rule for T (else PDMP_ERR_INVALID, sums untouched)."""
         _lib.check(self._L.pdmp_ensemble_ess_begin(self._h, float(T0)))
 
     def ess_batch(self, T):
