@@ -168,6 +168,7 @@ struct pdmp_ensemble {
     DevBuf<uint16_t> d_nb16;
     const char* last_kernel = "";  // event-loop kernel of the last pdmp_ensemble_run (pdmp_debug_last_kernel)
     int32_t lattice_n = 0;  // the flow's graph is the n x n 5-point lattice in column-major numbering (0: it is not)
+    uint32_t typ_extra = 0;  // the most frequent |G1[i]| - 1 of the flow's graph (set_flow): what the one-proposal-per-lane tracked kernels unroll for
     double t0_state = 0.0;
     double run_T = 0.0;  // horizon of the last run (t0 before the first): no read of the path integrals beyond it (fact_integrals_at)
     DevBuf<double> d_jstart, d_essacc;  // pdmp_ensemble_ess_*
@@ -272,6 +273,33 @@ struct pdmp_ensemble {
 
 #define PDMP_LG_ROWS_DEFAULT 0  // chains per wavefront of the LDS-resident logistic kernel by default: 0 = one (pdmp_logistic.hip), 16 / 32 = rows (pdmp_logrows.hip)
 #define PDMP_LG_FILL 0.95       // lanes of a 64-entry chunk a range fills on average (ranged sweep of long logistic rows; 0.6 .. 1.1 measured on C5)
+
+// The event-loop kernel families of pdmp_ensemble_run.  select_family alone decides which one serves an ensemble; what a family does with the phase
+// profile (pdmp_debug_set_phase_profile) and how its launcher's failure reads is stated here, once.
+enum KernelFamily { FAM_BPS, FAM_GENERAL, FAM_LOGISTIC_LDS, FAM_LOGISTIC_ROWS, FAM_TRACKL, FAM_TRACKP, FAM_TRACK_GROUPS, FAM_EXACTP,
+                    FAM_STICKY_SPEC, FAM_STICKY_RUN, FAM_SPEC, FAM_ONE_EVENT };
+struct FamilyInfo {
+    int phase_kind;        // the `kind` of pdmp_debug_phase_profile its kernels record (pdmp_debug.h), 0: they have no profiling form -- no buffer, no read-back
+    const char* launcher;  // "<launcher> launch failed ..."
+    bool hip_rc;           // ... with the return code spelled out as a hipError_t, or as a number
+};
+static const FamilyInfo FAMILY[] = {
+    /* FAM_BPS           */ {0, "bps_run", false},
+    /* FAM_GENERAL       */ {2, "zz_general_run", true},   // [0..6] = select, move G1, gradient, coin + G2, re-bound, re-queue, tail; [10] = proposals
+    /* FAM_LOGISTIC_LDS  */ {2, "zz_general_run", true},
+    /* FAM_LOGISTIC_ROWS */ {0, "zz_general_run", true},   // (zz_logistic_rows_supported: never chosen for a profiled run)
+    /* FAM_TRACKL        */ {1, "zz_local_trackl", false},
+    /* FAM_TRACKP        */ {1, "zz_local_trackp", false},
+    /* FAM_TRACK_GROUPS  */ {1, "zz_local_track", false},
+    /* FAM_EXACTP        */ {1, "zz_local_exactp", false},  // [10] iterations, [11] candidates, [12] left by the zone test, [13] committed, [14] events among the candidates
+    /* FAM_STICKY_SPEC   */ {0, "zz_local_run", true},
+    /* FAM_STICKY_RUN    */ {0, "zz_local_run", true},
+    /* FAM_SPEC          */ {1, "zz_local_run", true},     // speculative kernels: [0..8] = cycles per phase, [10] = iterations
+    /* FAM_ONE_EVENT     */ {0, "zz_local_run", true},
+};
+
+// neighbourhoods beyond 64 members, G ⊋ G1, FactBoomerang, the logistic target, adaptscale, LocalBound: pdmp_general.hip / pdmp_logistic.hip
+static bool general_path(const pdmp_ensemble* e) { return e->needs_general || e->target_kind == 1 || e->adaptscale || e->local_bound; }
 
 static pdmp_status launch_deferred_consumer(pdmp_ensemble* e) {
     if (e->deferred_k < 0) return PDMP_OK;
@@ -815,6 +843,13 @@ static pdmp_status set_flow_common(pdmp_ensemble* e, const int64_t* colptr, cons
         member[(size_t)p * 4 + 2] = qptr[p];
         member[(size_t)p * 4 + 3] = (!g1mask || g1mask[p]) ? 1u : 0u;
     }
+    {
+        uint32_t hist[16] = {0}, best = 0;
+        for (int64_t k = 0; k < d; ++k) hist[std::min<uint32_t>(e->colptr[(size_t)k + 1] - e->colptr[(size_t)k], 15u)] += 1;
+        for (uint32_t k = 1; k < 16; ++k)
+            if (hist[k] > hist[best]) best = k;
+        e->typ_extra = best > 0 ? best - 1u : 0u;
+    }
     e->flow_kind = kind;
     e->has_g1mask = g1mask != nullptr;
     e->needs_general = general || kind == 1 || e->has_g1mask;  // FactBoomerang and G ⊋ G1 run on the general kernel
@@ -1268,6 +1303,39 @@ static pdmp_status alloc_state(pdmp_ensemble* e) {
     return PDMP_OK;
 }
 
+// Γ[i,j] is read where the reference reads Γ[j,i] (the stored column of the reflecting coordinate): is the bounding matrix symmetric, in pattern and
+// values?  With two_sums also the target's, and *two_sums tells whether the two matrices differ anywhere.
+static bool symmetric_matrices(const pdmp_ensemble* e, bool* two_sums) {
+    bool two = false;
+    for (int64_t col = 0; col < e->cfg.d; ++col)
+        for (uint32_t pp = e->colptr[col]; pp < e->colptr[col + 1]; ++pp) {
+            const uint32_t row = e->rowval[pp];
+            const uint32_t* lo = e->rowval.data() + e->colptr[row];
+            const uint32_t* hi = e->rowval.data() + e->colptr[row + 1];
+            const uint32_t* it = std::lower_bound(lo, hi, (uint32_t)col);
+            if (it == hi || *it != (uint32_t)col) return false;
+            const size_t q = (size_t)(it - e->rowval.data());
+            if (e->bval[q] != e->bval[pp] || (two_sums && e->h_tval[q] != e->h_tval[pp])) return false;
+            if (two_sums && e->bval[pp] != e->h_tval[pp]) two = true;
+        }
+    if (two_sums) *two_sums = two;
+    return true;
+}
+
+// what zz_trackp_supported / zz_trackl_supported ask about an ensemble whose state is being set (track_mean decided)
+static pdmp::ZzRunParams track_query_params(const pdmp_ensemble* e) {
+    pdmp::ZzRunParams G{};
+    G.tb = e->tables();
+    if (e->track_mean == 2) G.tb.gmu_t = nullptr;  // (the target's mean is served: the support tests need not refuse it)
+    G.lattice_n = e->lattice_n;
+    G.adapt = e->cfg.adapt;
+    G.c_chain = e->cfg.adapt ? e->d_c_chain.p : nullptr;
+    G.track_two_sums = e->track_two_sums ? 1 : 0;
+    G.has_refresh = e->lambda_ref > 0;
+    G.d = e->cfg.d;
+    return G;
+}
+
 static pdmp_status init_state(pdmp_ensemble* e, double t0, const double* x0, const double* th0, const double* c,
                               const uint64_t* seeds, uint64_t seed0) {
     if (!e->has_flow || !e->has_target) return fail(PDMP_ERR_INVALID, "flow and target must be set before the state");
@@ -1283,16 +1351,7 @@ static pdmp_status init_state(pdmp_ensemble* e, double t0, const double* x0, con
         if (e->cfg.sampler != PDMP_SAMPLER_ZIGZAG_LOCAL || e->flow_kind != 0 || e->adaptscale || e->local_bound || e->lambda_ref > 0 ||
             e->dbg_kernel != PDMP_DEBUG_KERNEL_AUTO || e->dbg_dump > 0 || e->has_g1mask)
             return fail(PDMP_ERR_UNSUPPORTED, "gradient tracking with the logistic target: spdmp, ZigZag flow without refresh, G = Matched()");
-        bool sym = true;
-        for (int64_t col = 0; col < d && sym; ++col)
-            for (uint32_t pp = e->colptr[col]; pp < e->colptr[col + 1] && sym; ++pp) {
-                const uint32_t row = e->rowval[pp];
-                const uint32_t* lo = e->rowval.data() + e->colptr[row];
-                const uint32_t* hi = e->rowval.data() + e->colptr[row + 1];
-                const uint32_t* it = std::lower_bound(lo, hi, (uint32_t)col);
-                if (it == hi || *it != (uint32_t)col || e->bval[(size_t)(it - e->rowval.data())] != e->bval[pp]) sym = false;
-            }
-        if (!sym) return fail(PDMP_ERR_UNSUPPORTED, "gradient tracking needs a symmetric bounding matrix");
+        if (!symmetric_matrices(e, nullptr)) return fail(PDMP_ERR_UNSUPPORTED, "gradient tracking needs a symmetric bounding matrix");
         e->track_lg = true;
     } else
     if (e->track_requested) {
@@ -1300,23 +1359,8 @@ static pdmp_status init_state(pdmp_ensemble* e, double t0, const double* x0, con
         if (e->cfg.sampler != PDMP_SAMPLER_ZIGZAG_LOCAL || e->needs_general || e->target_kind != 0 || e->flow_kind != 0 || e->adaptscale ||
             e->local_bound || e->lambda_ref > 0 || e->dbg_kernel != PDMP_DEBUG_KERNEL_AUTO || e->dbg_dump > 0)
             return fail(PDMP_ERR_UNSUPPORTED, "gradient tracking: spdmp with a ZigZag flow without refresh and the Gaussian target only");
-        // Γ[i,j] is read where the reference reads Γ[j,i] (the stored column of the reflecting coordinate): both matrices must be symmetric
-        bool sym = true, two = false;
-        for (int64_t col = 0; col < d && sym; ++col)
-            for (uint32_t pp = e->colptr[col]; pp < e->colptr[col + 1] && sym; ++pp) {
-                const uint32_t row = e->rowval[pp];
-                const uint32_t* lo = e->rowval.data() + e->colptr[row];
-                const uint32_t* hi = e->rowval.data() + e->colptr[row + 1];
-                const uint32_t* it = std::lower_bound(lo, hi, (uint32_t)col);
-                if (it == hi || *it != (uint32_t)col) {
-                    sym = false;
-                    break;
-                }
-                const size_t q = (size_t)(it - e->rowval.data());
-                if (e->bval[q] != e->bval[pp] || e->h_tval[q] != e->h_tval[pp]) sym = false;
-                if (e->bval[pp] != e->h_tval[pp]) two = true;
-            }
-        if (!sym) return fail(PDMP_ERR_UNSUPPORTED, "gradient tracking needs symmetric precision matrices (flow and target)");
+        bool two = false;
+        if (!symmetric_matrices(e, &two)) return fail(PDMP_ERR_UNSUPPORTED, "gradient tracking needs symmetric precision matrices (flow and target)");
         e->track_two_sums = two;
         e->track = true;
         detect_lattice(e);
@@ -1357,7 +1401,7 @@ static pdmp_status init_state(pdmp_ensemble* e, double t0, const double* x0, con
         }
         if ((st = e->d_cc.upload(ccv)) != PDMP_OK) return st;
     }
-    if (e->needs_general || e->target_kind == 1 || e->adaptscale || e->local_bound) {
+    if (general_path(e)) {
         if (e->cfg.sampler != PDMP_SAMPLER_ZIGZAG_LOCAL && e->cfg.sampler != PDMP_SAMPLER_ZIGZAG_ALL &&
             e->cfg.sampler != PDMP_SAMPLER_STICKY_ZIGZAG)
             return fail(PDMP_ERR_UNSUPPORTED,
@@ -1447,14 +1491,6 @@ static pdmp_status init_state(pdmp_ensemble* e, double t0, const double* x0, con
             if ((st = e->d_gam8.upload(g8)) != PDMP_OK) return st;
             e->track_generic = true;
         }
-        pdmp::ZzRunParams G{};
-        G.tb = e->tables();
-        G.lattice_n = e->lattice_n;
-        G.adapt = e->cfg.adapt;
-        G.c_chain = e->cfg.adapt ? e->d_c_chain.p : nullptr;
-        G.track_two_sums = e->track_two_sums ? 1 : 0;
-        G.has_refresh = e->lambda_ref > 0;
-        G.d = d;
         // the means (round 6): the one-proposal-per-lane kernel keeps ONE constant Γ[:,i]·μ per coordinate -- the flow's, which enters every bound
         // (src/fact_samplers.jl:51); a target mean is served where its Γμ is the same numbers (the usual Z = ZigZag(Γ, μ) on ∇ϕ = Γ(x − μ))
         {
@@ -1463,12 +1499,10 @@ static pdmp_status init_state(pdmp_ensemble* e, double t0, const double* x0, con
             e->track_mean = flow_mean ? 1 : 0;
             if (e->has_tmu) {
                 const bool same = e->h_gmu_t.size() == e->h_gmu_b.size() && std::equal(e->h_gmu_t.begin(), e->h_gmu_t.end(), e->h_gmu_b.begin());
-                if (same && !e->track_two_sums) {
-                    e->track_mean = 2;
-                    G.tb.gmu_t = nullptr;  // (served: the support test below need not refuse it)
-                }
+                if (same && !e->track_two_sums) e->track_mean = 2;
             }
         }
+        pdmp::ZzRunParams G = track_query_params(e);
         trackp_ok = pdmp::zz_trackp_supported(G) && e->dbg_track_groups == 0;
         if (!trackp_ok) e->track_generic = false;
         G.blob_sw = e->blob_sw;
@@ -1511,16 +1545,9 @@ static pdmp_status init_state(pdmp_ensemble* e, double t0, const double* x0, con
             if (rc != 0) return fail(PDMP_ERR_HIP, "trackp_consts launch failed: %s", hipGetErrorString((hipError_t)rc));
             e->track_pairs = true;
             // the line layout where the ensemble fills the device (decided here: the layout belongs to the kernel)
-            pdmp::ZzRunParams G{};
-            G.tb = e->tables();
-            G.lattice_n = e->lattice_n;
-            G.adapt = e->cfg.adapt;
-            G.track_two_sums = e->track_two_sums ? 1 : 0;
-            G.has_refresh = e->lambda_ref > 0;
-            G.d = d;
             // (measured, round 6: 2.7 instead of 3.2 lines read per proposal, but 72 instead of 54 vector instructions -- 47.9 ms against 45.4 / 38.8 ms
             // for pdmp_trackp.hip's form on boxes in the slow / fast timing mode: the layout is kept as an opt-in form, never chosen by width)
-            if (pdmp::zz_trackl_supported(G) && !e->track_generic && e->track_mean == 0 && e->dbg_track_lines == 1) {
+            if (pdmp::zz_trackl_supported(track_query_params(e)) && !e->track_generic && e->track_mean == 0 && e->dbg_track_lines == 1) {
                 if (e->d_tl_lines.n != (size_t)(n * e->dk / 2) && (st = e->d_tl_lines.alloc((size_t)(n * e->dk / 2))) != PDMP_OK) return st;
                 if (e->d_tl_cold.n != (size_t)(n * e->dk) && (st = e->d_tl_cold.alloc((size_t)(n * e->dk))) != PDMP_OK) return st;
                 rc = pdmp::launch_zz_trackl_pack(e->d_rec.p, e->d_kp.p, e->d_tl_lines.p, e->d_tl_cold.p, d, e->dk, n, e->stream);
@@ -1534,6 +1561,182 @@ static pdmp_status init_state(pdmp_ensemble* e, double t0, const double* x0, con
     e->ran = false;
     e->timed = false;
     e->consuming = false;
+    return PDMP_OK;
+}
+
+// Everything the ZigZag event-loop kernels read of a run to T, but the dump / profile buffer (dbg, dbg_cap: ensemble_run_impl allocates them)
+static pdmp::ZzRunParams run_params(const pdmp_ensemble* e, double T, int flags) {
+    pdmp::ZzRunParams P{};
+    P.count_limit = e->dbg_count_limit ? e->dbg_count_limit : pdmp::PDMP_LAUNCH_COUNT_LIMIT;
+    P.tb = e->tables();
+    P.rec = e->d_rec.p;
+    P.keys = e->d_keys.p;
+    P.hdr = e->d_hdr.p;
+    P.ev = e->cfg.trace_capacity > 0 ? e->d_ev.p : nullptr;
+    P.c_chain = e->cfg.adapt ? e->d_c_chain.p : nullptr;
+    P.blob = e->d_blob.p;
+    P.tix = e->d_tix.p;
+    P.common_tix = e->common_tix;
+    if (e->has_g8) {
+        P.g8_line = e->d_g8_line.p;
+        P.g8_member = e->d_g8_member.p;
+        P.g8_gamt = e->g8_same ? nullptr : e->d_g8_gamt.p;
+        P.g8_gw = e->g8_gw;
+    }
+    P.blob_w = e->blob_w;
+    P.blob_w_pad = e->blob_w_pad;
+    P.blob_sw = e->blob_sw;
+    P.blob_pw = e->blob_pw;
+    P.blob_kmax = e->blob_kmax;
+    P.d = e->cfg.d;
+    P.dk = e->dk;
+    P.trace_cap = e->cfg.trace_capacity;
+    P.nblk = e->nblk;
+    P.nblk_pad = e->nblk_pad;
+    P.T = T;
+    P.factor = e->cfg.factor;
+    P.lambda_ref = e->lambda_ref;
+    // G2[i] is fetched only once an event is accepted (18 % of proposals): same throughput at 4 waves/SIMD, 37 % less HBM
+    // traffic; pdmp_debug_set_spec_g2 restores the speculative fetch (3 % faster when the SIMDs are under-occupied)
+    P.flags = flags | (e->dbg_spec_g2 ? 0 : 0x100);
+    P.force_spec4 = e->dbg_kernel == PDMP_DEBUG_KERNEL_SPEC4 ? 1 : 0;
+    P.adapt = e->cfg.adapt;
+    P.has_refresh = e->lambda_ref > 0;
+    P.move_all = e->cfg.sampler == PDMP_SAMPLER_ZIGZAG_ALL;
+    P.kappa = e->d_kappa.p;
+    P.thf = e->d_thf.p;
+    P.reversible = e->reversible;
+    P.strong_upperbounds = e->strong_upperbounds;
+    if (general_path(e)) return P;
+    if (e->track || e->exactp) {  // the kernels that take a coordinate's neighbours from its index on the plain lattice
+        P.lattice_n = e->lattice_n;
+        P.lattice_magic = e->lattice_n ? (uint32_t)(((uint64_t)1 << 32) / (uint64_t)e->lattice_n + 1) : 0u;
+    }
+    if (!e->track) return P;
+    P.track_two_sums = e->track_two_sums ? 1 : 0;
+    if (!e->track_pairs) return P;  // (the 8-lane-group kernel)
+    // one proposal per lane (pdmp_trackp.hip, and pdmp_trackl.hip on its line layout)
+    P.typ_extra = e->typ_extra;
+    P.hw_gain = e->dbg_hw_steer[0];  // (pdmp_debug_set_helper_steering: block minima per quantum, events per window -- A/B; 0: the kernel's)
+    P.hw_target = (uint32_t)e->dbg_hw_steer[1];
+    P.hw_ahead = e->dbg_hw_steer[2];  // (a block to watch: the -DPDMP_TL_CHECK build of pdmp_trackl.hip)
+    if (e->track_lines) {
+        P.tl_lines = e->d_tl_lines.p;
+        P.tl_cold = e->d_tl_cold.p;
+        return P;
+    }
+    P.keys = e->d_kp.p;
+    P.track_mean = e->track_mean;
+    if (e->track_mean == 2) P.tb.gmu_t = nullptr;  // (the rate's mean rides in the record lines)
+    P.n_cu = e->n_cu;
+    // the two-wave form (a helper wave per chain) where the ensemble leaves SIMDs idle: at most two resident waves per SIMD with it
+    // (1024 SIMDs, two waves per chain) -- a rank's share of a strong-scaled job; wider ensembles hide a wave's latency with other chains
+    P.helper_wave = (e->dbg_helper_wave == 1 || (e->dbg_helper_wave == -1 && e->cfg.nchains <= (int64_t)HELPER_WAVE_MAX_CHAINS_PER_CU * (e->n_cu > 0 ? e->n_cu : 256))) ? 1 : 0;
+    if (pdmp::zz_trackp_big(e->cfg.d)) P.helper_wave = 0;
+    return P;
+}
+
+// (hot: the run allocates d_hot before it asks, where rows are long)
+static pdmp::ZzGeneralParams general_params(const pdmp_ensemble* e) {
+    pdmp::ZzGeneralParams Q{};
+    Q.local_bound = e->local_bound ? 1 : 0;
+    Q.masked = e->has_g1mask ? 1 : 0;
+    Q.sticky = e->cfg.sampler == PDMP_SAMPLER_STICKY_ZIGZAG ? 1 : 0;
+    Q.qtval = e->d_qtval.p;
+    Q.renew_chain = e->local_bound ? e->d_thf.p : nullptr;
+    Q.sig_chain = e->adaptscale ? e->d_sig_chain.p : nullptr;
+    Q.adaptscale = e->adaptscale ? 1 : 0;
+    Q.pos16 = e->d_pos16.p;
+    Q.qbval = e->d_qbval.p;
+    Q.member = reinterpret_cast<const uint4*>(e->d_member.p);
+    Q.selfpos16 = e->d_selfpos16.p;
+    Q.mmax_pad = (e->mmax_all + 63u) & ~63u;
+    Q.target_kind = e->target_kind;
+    Q.A_colptr = e->lg_Acp.p;
+    Q.A_rowval = e->lg_Arv.p;
+    Q.A_nzval = e->lg_Anz.p;
+    Q.At_colptr = e->lg_Atcp.p;
+    Q.At_rowval = e->lg_Atrv.p;
+    Q.At_row32 = e->lg_Atrv32.p;
+    Q.At_nzval = e->lg_Atnz.p;
+    Q.y = e->lg_y.p;
+    Q.ny = e->lg_ny.p;
+    Q.sn0 = e->lg_u0.p;
+    Q.ns0 = e->lg_ns0.p;
+    Q.gamma0 = e->lg_gamma0;
+    Q.ksub = e->lg_k;
+    Q.lg_ne_max = (int32_t)std::min<int64_t>(e->lg_nemax, 1 << 30);
+    // rows of thousands of coefficients: ranges that hold about 50 of a row's entries (64 lanes per chunk)
+    const bool long_rows = e->lg_nemax >= 1024;
+    Q.hot = long_rows ? e->d_hot.p : nullptr;
+    Q.lg_range = long_rows ? (int32_t)std::max<int64_t>(16, (int64_t)(PDMP_LG_FILL * 64.0 * (double)e->cfg.d / (double)e->lg_nemax)) : 0;
+    Q.flow_kind = e->flow_kind;
+    Q.mu = e->d_mu.p;
+    Q.diag = e->d_diag.p;
+    Q.rho = e->rho;
+    return Q;
+}
+
+static int logistic_rows_width(const pdmp_ensemble* e) { return e->dbg_lg_rows >= 0 ? e->dbg_lg_rows : PDMP_LG_ROWS_DEFAULT; }  // lanes per chain of FAM_LOGISTIC_ROWS
+static pdmp::ZzLogisticTables logistic_tables(const pdmp_ensemble* e) {
+    pdmp::ZzLogisticTables LT{};
+    LT.coord = e->lg_coord.p;
+    LT.obs = e->lg_obs.p;
+    LT.a_row = e->lg_arow.p;
+    LT.a_val = e->lg_Anz.p;
+    LT.qrow16 = e->d_qrow16.p;
+    LT.trk = e->track_lg ? e->d_trk.p : nullptr;
+    return LT;
+}
+
+// The family that serves the next run of this ensemble (P, Q, LT: its filled parameters), or the refusal the run raises -- *fam is then the family
+// that was asked for.  Reads, launches nothing.
+static pdmp_status select_family(const pdmp_ensemble* e, const pdmp::ZzRunParams& P, const pdmp::ZzGeneralParams& Q, const pdmp::ZzLogisticTables& LT,
+                                 KernelFamily* fam) {
+    *fam = FAM_BPS;
+    if (e->cfg.sampler == PDMP_SAMPLER_BPS) return PDMP_OK;
+    const bool sticky = e->cfg.sampler == PDMP_SAMPLER_STICKY_ZIGZAG, dump = e->dbg_dump > 0, profile = e->dbg_phase != 0;
+    if (general_path(e)) {
+        // small d: the chain's state lives in LDS for the whole slice (PDMP_DEBUG_KERNEL_SEQ keeps the records in HBM: A/B runs, parity tests)
+        const bool lds_resident = e->dbg_kernel != PDMP_DEBUG_KERNEL_SEQ && pdmp::zz_logistic_lds_supported(P, Q, LT);
+        *fam = (lds_resident || e->track_lg) ? FAM_LOGISTIC_LDS : FAM_GENERAL;
+        if (e->track_lg && !lds_resident)
+            return fail(PDMP_ERR_UNSUPPORTED, "gradient tracking with the logistic target runs on the LDS-resident kernel: d <= 512, k_sub <= 32, rows of <= 6 regressors");
+#ifdef PDMP_EXTRA_KERNELS
+        // ... several chains per wavefront where the draws of a proposal fit a row (pdmp_logrows.hip); pdmp_debug_set_logistic_rows picks the width.
+        // The rows kernel takes neither a dump nor a profile buffer: the run hands one to every general kernel that is asked for either
+        pdmp::ZzRunParams Pb = P;
+        if (dump || profile) Pb.dbg = const_cast<double*>(e->dbg_phase_out);  // (read as "not null" only)
+        const int rows_w = (!lds_resident || e->track_lg) ? 0 : logistic_rows_width(e);
+        const bool rows = rows_w > 0 && pdmp::zz_logistic_rows_supported(Pb, Q, LT, rows_w);
+        if (rows || (lds_resident && e->dbg_lg_rows > 0)) *fam = FAM_LOGISTIC_ROWS;
+        if (lds_resident && e->dbg_lg_rows > 0 && !rows) return fail(PDMP_ERR_UNSUPPORTED, "pdmp_debug_set_logistic_rows: this ensemble does not fit rows of %d lanes", rows_w);
+#endif
+        return PDMP_OK;
+    }
+    if (e->track) {
+        // one proposal per lane where the graph is the plain lattice or tabulated (pdmp_trackp.hip; its line layout on request); elsewhere, and on
+        // request, the 8-lane-group kernel -- decided with the layout, by set_state
+        *fam = e->track_lines ? FAM_TRACKL : e->track_pairs ? FAM_TRACKP : FAM_TRACK_GROUPS;
+        if (dump) return fail(PDMP_ERR_UNSUPPORTED, "the proposal dump belongs to the one-event kernel");
+        return PDMP_OK;
+    }
+    // (33 <= |S| <= 64: no blob kernel takes it, but zz_local_spec8g_kernel<.., GW = 16> does where its own conditions hold)
+    const bool g16_ok = e->has_g8 && e->g8_gw == 16 && e->dbg_kernel == PDMP_DEBUG_KERNEL_AUTO && (P.flags & 0x100) && !profile;
+    // (a refresh clock, src/sfact.jl:78-114: the speculative kernels process the clock's events by themselves between their iterations -- round 6)
+    const bool spec_ok = (e->use_spec || g16_ok) && !dump && !P.move_all && !sticky;
+    *fam = FAM_EXACTP;
+#ifdef PDMP_EXTRA_KERNELS
+    if (e->exactp && spec_ok && !P.has_refresh && pdmp::zz_exactp_supported(P)) return PDMP_OK;
+#endif
+    if (e->dbg_kernel == PDMP_DEBUG_KERNEL_EXACTP)  // asked for by name: never another kernel in its place
+#ifndef PDMP_EXTRA_KERNELS
+        return fail(PDMP_ERR_UNSUPPORTED, "PDMP_DEBUG_KERNEL_EXACTP: zz_local_exactp_kernel is not part of this library: it lives in the parity build (build.py --variant parity, -DPDMP_EXTRA_KERNELS)");
+#else
+        return fail(PDMP_ERR_UNSUPPORTED, "PDMP_DEBUG_KERNEL_EXACTP: spdmp on a plain lattice (16 <= n <= 128, d >= 2048) with the bounding matrix equal to the target's, no adaptation, and a trace or no trace");
+#endif
+    const bool sticky_spec = sticky && e->use_spec && e->blob_mmax <= 16 && !dump;  // the ZigZag speculative kernel's requirements, one zone member per lane
+    *fam = sticky ? (sticky_spec ? FAM_STICKY_SPEC : FAM_STICKY_RUN) : spec_ok ? FAM_SPEC : FAM_ONE_EVENT;
     return PDMP_OK;
 }
 
@@ -1554,13 +1757,16 @@ static pdmp_status init_state_tuned(pdmp_ensemble* e, double t0, const double* x
     pdmp_status st = init_state(e, t0, x0, th0, c, seeds, seed0);
     if (st != PDMP_OK) return st;
     // the two arrays the event loop scatters over: the records, and level 0 of the queue -- (key, time) pairs under tracking, plain keys otherwise.
-    // Kernels of pdmp_kernels.hip / pdmp_trackp.hip only (they pause on the draw count; the general-degree, logistic and sticky paths are not probed)
+    // The families of pdmp_kernels.hip / pdmp_trackp.hip / pdmp_exactp.hip only, under spdmp (they pause on the draw count; the general-degree, logistic
+    // and sticky ones are not probed).  A family the run would refuse is reported too: the probe's run then raises the refusal and set_state returns it.
     DevBuf<double>& keybuf = e->track_pairs ? e->d_kp : e->d_keys;
     const size_t rec_bytes = e->d_rec.n * sizeof(*e->d_rec.p), kp_bytes = keybuf.n * sizeof(double);
-    const bool probed_kernel = e->cfg.sampler == PDMP_SAMPLER_ZIGZAG_LOCAL && (e->track_pairs || !e->track) && !e->track_lines && !e->needs_general &&
-                               e->target_kind == 0 && !e->adaptscale && !e->local_bound && e->dbg_dump == 0;
-    if (e->place_tune == 0 || !probed_kernel || e->cfg.nchains < PLACE_TUNE_MIN_CHAINS || rec_bytes < ((size_t)2 << 30) || e->d_rec.placed.va ||
-        keybuf.placed.va || e->dbg_count_limit != 0)
+    KernelFamily fam;
+    (void)select_family(e, run_params(e, t0, PDMP_RUN_STOP_BEFORE), general_params(e), logistic_tables(e), &fam);
+    const bool probed_kernel = e->cfg.sampler == PDMP_SAMPLER_ZIGZAG_LOCAL &&
+                               (fam == FAM_SPEC || fam == FAM_TRACKP || fam == FAM_EXACTP || fam == FAM_ONE_EVENT);  // (FAM_ONE_EVENT never pauses)
+    if (e->place_tune == 0 || !probed_kernel || e->dbg_dump != 0 || e->cfg.nchains < PLACE_TUNE_MIN_CHAINS || rec_bytes < ((size_t)2 << 30) ||
+        e->d_rec.placed.va || keybuf.placed.va || e->dbg_count_limit != 0)
         return PDMP_OK;
     size_t freeb = 0, totb = 0;
     if (hipMemGetInfo(&freeb, &totb) != hipSuccess || freeb < 3 * (rec_bytes + kp_bytes) + ((size_t)8 << 30)) {
@@ -1661,7 +1867,7 @@ pdmp_status pdmp_ensemble_set_state_synthetic(pdmp_ensemble* e, double t0, const
     return init_state_tuned(e, t0, nullptr, nullptr, c, nullptr, seed0);
 }
 
-static void fill_bps_ext(const pdmp_ensemble* e, pdmp::BpsRunParams& B);
+static pdmp::BpsRunParams bps_run_params(const pdmp_ensemble* e, double T, int flags);
 static pdmp::BpsMomParams bps_moments_params(const pdmp_ensemble* e);
 
 pdmp_status pdmp_ensemble_run(pdmp_ensemble* e, double T, int flags, void* stream) {
@@ -1670,6 +1876,8 @@ pdmp_status pdmp_ensemble_run(pdmp_ensemble* e, double T, int flags, void* strea
     if (st == PDMP_OK && e->deferred_k >= 0) st = launch_deferred_consumer(e);  // (behind the event loop's launch: see pdmp_ensemble_consume_async)
     return st;
 }
+
+// validate, fill, select, launch, finish
 static pdmp_status ensemble_run_impl(pdmp_ensemble* e, double T, int flags, void* stream) {
     if (!e) return fail(PDMP_ERR_INVALID, "null argument");
     if (!e->has_state) return fail(PDMP_ERR_INVALID, "set_state must be called before run");
@@ -1677,296 +1885,65 @@ static pdmp_status ensemble_run_impl(pdmp_ensemble* e, double T, int flags, void
     HIP_TRY(hipSetDevice(e->cfg.device));
     e->ran = true;
     hipStream_t s = stream ? (hipStream_t)stream : e->stream;
-    if (e->cfg.sampler == PDMP_SAMPLER_BPS) {
-        pdmp::BpsRunParams B{};
-        B.colptr = e->b_colptr.p;
-        B.rowval = e->b_rowval.p;
-        B.nzval = e->b_nzval.p;
-        B.mu = e->b_mu.p;
-        B.mu_flow = e->b_mu_flow.p;
-        B.flow_kind = e->bps_flow_kind;
-        B.ident = e->bps_ident ? 1 : 0;
-        B.x = e->b_x.p;
-        B.th = e->b_th.p;
-        B.scal = e->b_scal.p;
-        B.hdr = e->d_hdr.p;
-        B.ev_t = e->b_ev_t.p;
-        B.ev_x = e->b_ev_x.p;
-        B.ev_th = e->b_ev_th.p;
-        B.d = e->cfg.d;
-        B.trace_cap = e->cfg.trace_capacity;
-        B.T = T;
-        B.factor = e->cfg.factor;
-        B.lambda_ref = e->bps_lambda;
-        B.rho = e->bps_rho;
-        B.flags = flags;
-        B.adapt = e->cfg.adapt;
-        fill_bps_ext(e, B);
-        HIP_TRY(hipEventRecord(e->ev0, s));
-        e->last_kernel = "bps_run_kernel";
-        int rcb = pdmp::launch_bps_run(B, e->cfg.nchains, e->bps_diag, s, bps_moments_params(e));
-        if (rcb != 0) return fail(PDMP_ERR_HIP, "bps_run launch failed (%d)", rcb);
-        HIP_TRY(hipEventRecord(e->ev1, s));
-        e->timed = true;
-        return PDMP_OK;
-    }
-    pdmp::ZzRunParams P{};
-    P.count_limit = e->dbg_count_limit ? e->dbg_count_limit : pdmp::PDMP_LAUNCH_COUNT_LIMIT;
-    P.tb = e->tables();
-    P.rec = e->d_rec.p;
-    P.keys = e->d_keys.p;
-    P.hdr = e->d_hdr.p;
-    P.ev = e->cfg.trace_capacity > 0 ? e->d_ev.p : nullptr;
-    P.c_chain = e->cfg.adapt ? e->d_c_chain.p : nullptr;
-    P.blob = e->d_blob.p;
-    P.tix = e->d_tix.p;
-    P.common_tix = e->common_tix;
-    if (e->has_g8) {
-        P.g8_line = e->d_g8_line.p;
-        P.g8_member = e->d_g8_member.p;
-        P.g8_gamt = e->g8_same ? nullptr : e->d_g8_gamt.p;
-        P.g8_gw = e->g8_gw;
-    }
-    DevBuf<double> dbgbuf;
-    const int64_t dbg_cap = e->dbg_dump;
+    const int64_t n = e->cfg.nchains;
+    const bool bps = e->cfg.sampler == PDMP_SAMPLER_BPS;
+    pdmp_status st;
+    if (!bps) e->dbg_phase_valid = 0;
+    if (!bps && general_path(e) && e->lg_nemax >= 1024 && !e->d_hot.p && (st = e->d_hot.alloc((size_t)n * (size_t)e->cfg.d * 4)) != PDMP_OK) return st;
+    // (plain fills of pointers and numbers: the other sampler's block goes unread)
+    const pdmp::BpsRunParams B = bps_run_params(e, T, flags);
+    pdmp::ZzRunParams P = run_params(e, T, flags);
+    const pdmp::ZzGeneralParams Q = general_params(e);
+    const pdmp::ZzLogisticTables LT = logistic_tables(e);
+    KernelFamily fam;
+    if ((st = select_family(e, P, Q, LT, &fam)) != PDMP_OK) return st;
+    const FamilyInfo& F = FAMILY[fam];
+    // on the stream: the dump buffer's memset, ev0, the profile buffer's memset, the kernel, ev1
+    DevBuf<double> dbgbuf, phbuf;
+    const int64_t dbg_cap = bps ? 0 : e->dbg_dump;
     if (dbg_cap > 0) {
-        pdmp_status st2 = dbgbuf.alloc((size_t)dbg_cap * 16);
-        if (st2 != PDMP_OK) return st2;
+        if ((st = dbgbuf.alloc((size_t)dbg_cap * 16)) != PDMP_OK) return st;
         HIP_TRY(hipMemsetAsync(dbgbuf.p, 0, (size_t)dbg_cap * 16 * sizeof(double), s));
         P.dbg = dbgbuf.p;
         P.dbg_cap = dbg_cap;
     }
-    P.blob_w = e->blob_w;
-    P.blob_w_pad = e->blob_w_pad;
-    P.blob_sw = e->blob_sw;
-    P.blob_pw = e->blob_pw;
-    P.blob_kmax = e->blob_kmax;
-    P.d = e->cfg.d;
-    P.dk = e->dk;
-    P.trace_cap = e->cfg.trace_capacity;
-    P.nblk = e->nblk;
-    P.nblk_pad = e->nblk_pad;
-    P.T = T;
-    P.factor = e->cfg.factor;
-    P.lambda_ref = e->lambda_ref;
-    // G2[i] is fetched only once an event is accepted (18 % of proposals): same throughput at 4 waves/SIMD, 37 % less HBM
-    // traffic; pdmp_debug_set_spec_g2 restores the speculative fetch (3 % faster when the SIMDs are under-occupied)
-    P.flags = flags | (e->dbg_spec_g2 ? 0 : 0x100);
-    P.force_spec4 = e->dbg_kernel == PDMP_DEBUG_KERNEL_SPEC4 ? 1 : 0;
-    P.adapt = e->cfg.adapt;
-    P.has_refresh = e->lambda_ref > 0;
-    P.move_all = e->cfg.sampler == PDMP_SAMPLER_ZIGZAG_ALL;
     HIP_TRY(hipEventRecord(e->ev0, s));
-    const bool sticky = e->cfg.sampler == PDMP_SAMPLER_STICKY_ZIGZAG;
-    P.kappa = e->d_kappa.p;
-    P.thf = e->d_thf.p;
-    P.reversible = e->reversible;
-    P.strong_upperbounds = e->strong_upperbounds;
-    const bool phenv = e->dbg_phase != 0;
-    e->dbg_phase_valid = 0;
-    DevBuf<double> phbuf;
-    // (33 <= |S| <= 64: no blob kernel takes it, but zz_local_spec8g_kernel<.., GW = 16> does where its own conditions hold)
-    const bool g16_ok = e->has_g8 && e->g8_gw == 16 && e->dbg_kernel == PDMP_DEBUG_KERNEL_AUTO && (P.flags & 0x100) && !phenv;
-    // (a refresh clock, src/sfact.jl:78-114: the speculative kernels process the clock's events by themselves between their iterations -- round 6)
-    const bool spec_ok = (e->use_spec || g16_ok) && dbg_cap == 0 && !P.move_all && !sticky;
-    const bool general_path = e->needs_general || e->target_kind == 1 || e->adaptscale || e->local_bound;
-    if (phenv && (spec_ok || general_path || e->track)) {  // (the tracked kernels take every d their layout serves: d = 65536 has no speculative kernel beside it)
-        pdmp_status st3 = phbuf.alloc(16);
-        if (st3 != PDMP_OK) return st3;
+    const bool profiled = e->dbg_phase != 0 && F.phase_kind != 0;
+    if (profiled) {
+        if ((st = phbuf.alloc(16)) != PDMP_OK) return st;
         HIP_TRY(hipMemsetAsync(phbuf.p, 0, 16 * sizeof(double), s));
         P.dbg = phbuf.p;
         P.dbg_cap = 0;
     }
-    if (general_path) {
-        pdmp::ZzGeneralParams Q{};
-        Q.local_bound = e->local_bound ? 1 : 0;
-        Q.masked = e->has_g1mask ? 1 : 0;
-        Q.sticky = sticky ? 1 : 0;
-        Q.qtval = e->d_qtval.p;
-        Q.renew_chain = e->local_bound ? e->d_thf.p : nullptr;
-        Q.sig_chain = e->adaptscale ? e->d_sig_chain.p : nullptr;
-        Q.adaptscale = e->adaptscale ? 1 : 0;
-        Q.pos16 = e->d_pos16.p;
-        Q.qbval = e->d_qbval.p;
-        Q.member = reinterpret_cast<const uint4*>(e->d_member.p);
-        Q.selfpos16 = e->d_selfpos16.p;
-        Q.mmax_pad = (e->mmax_all + 63u) & ~63u;
-        Q.target_kind = e->target_kind;
-        Q.A_colptr = e->lg_Acp.p;
-        Q.A_rowval = e->lg_Arv.p;
-        Q.A_nzval = e->lg_Anz.p;
-        Q.At_colptr = e->lg_Atcp.p;
-        Q.At_rowval = e->lg_Atrv.p;
-        Q.At_row32 = e->lg_Atrv32.p;
-        Q.At_nzval = e->lg_Atnz.p;
-        Q.y = e->lg_y.p;
-        Q.ny = e->lg_ny.p;
-        Q.sn0 = e->lg_u0.p;
-        Q.ns0 = e->lg_ns0.p;
-        Q.gamma0 = e->lg_gamma0;
-        Q.ksub = e->lg_k;
-        Q.lg_ne_max = (int32_t)std::min<int64_t>(e->lg_nemax, 1 << 30);
-        // rows of thousands of coefficients: ranges that hold about 50 of a row's entries (64 lanes per chunk)
-        Q.hot = nullptr;
-        if (e->lg_nemax >= 1024) {
-            if (!e->d_hot.p) {
-                pdmp_status sth_ = e->d_hot.alloc((size_t)e->cfg.nchains * (size_t)e->cfg.d * 4);
-                if (sth_ != PDMP_OK) return sth_;
-            }
-            Q.hot = e->d_hot.p;
-        }
-        Q.lg_range = (e->lg_nemax >= 1024) ? (int32_t)std::max<int64_t>(16, (int64_t)(PDMP_LG_FILL * 64.0 * (double)e->cfg.d / (double)e->lg_nemax)) : 0;
-        Q.flow_kind = e->flow_kind;
-        Q.mu = e->d_mu.p;
-        Q.diag = e->d_diag.p;
-        Q.rho = e->rho;
-        pdmp::ZzLogisticTables LT{};
-        LT.coord = e->lg_coord.p;
-        LT.obs = e->lg_obs.p;
-        LT.a_row = e->lg_arow.p;
-        LT.a_val = e->lg_Anz.p;
-        LT.qrow16 = e->d_qrow16.p;
-        LT.trk = e->track_lg ? e->d_trk.p : nullptr;
-        // small d: the chain's state lives in LDS for the whole slice (PDMP_DEBUG_KERNEL_SEQ keeps the records in HBM: A/B runs, parity tests)
-        const bool lds_resident = e->dbg_kernel != PDMP_DEBUG_KERNEL_SEQ && pdmp::zz_logistic_lds_supported(P, Q, LT);
-        // ... several chains per wavefront where the draws of a proposal fit a row (pdmp_logrows.hip); pdmp_debug_set_logistic_rows picks the width
-        if (e->track_lg && !lds_resident)
-            return fail(PDMP_ERR_UNSUPPORTED, "gradient tracking with the logistic target runs on the LDS-resident kernel: d <= 512, k_sub <= 32, rows of <= 6 regressors");
+    int rc = 0;
+    switch (fam) {
+    case FAM_BPS: e->last_kernel = "bps_run_kernel"; rc = pdmp::launch_bps_run(B, n, e->bps_diag, s, bps_moments_params(e)); break;
+    case FAM_GENERAL: e->last_kernel = "zz_general_run_kernel"; rc = pdmp::launch_zz_general_run(P, Q, n, s); break;
+    case FAM_LOGISTIC_LDS: e->last_kernel = "zz_logistic_lds_kernel"; rc = pdmp::launch_zz_logistic_lds(P, Q, LT, e->keep_integrals, n, s); break;
+    case FAM_TRACKL: e->last_kernel = "zz_local_trackl_kernel"; e->canon_stale = true; rc = pdmp::launch_zz_local_trackl(P, n, s); break;
+    case FAM_TRACKP: rc = pdmp::launch_zz_local_trackp(P, n, s, &e->last_kernel); break;
+    case FAM_TRACK_GROUPS: e->last_kernel = "zz_local_track_kernel"; rc = pdmp::launch_zz_local_track(P, n, s); break;
+    case FAM_STICKY_SPEC: e->last_kernel = "zz_sticky_spec_kernel"; rc = pdmp::launch_zz_sticky_spec(P, n, s); break;
+    case FAM_STICKY_RUN: e->last_kernel = "zz_sticky_run_kernel"; rc = pdmp::launch_zz_sticky_run(P, n, s); break;
+    case FAM_SPEC: rc = pdmp::launch_zz_local_spec(P, n, s, &e->last_kernel); break;
+    case FAM_ONE_EVENT: e->last_kernel = "zz_local_run_kernel"; rc = pdmp::launch_zz_local_run(P, n, s); break;
 #ifdef PDMP_EXTRA_KERNELS
-        const int rows_w = (!lds_resident || e->track_lg) ? 0 : (e->dbg_lg_rows >= 0 ? e->dbg_lg_rows : PDMP_LG_ROWS_DEFAULT);
-        const bool rows = rows_w > 0 && pdmp::zz_logistic_rows_supported(P, Q, LT, rows_w);
-        if (lds_resident && e->dbg_lg_rows > 0 && !rows) return fail(PDMP_ERR_UNSUPPORTED, "pdmp_debug_set_logistic_rows: this ensemble does not fit rows of %d lanes", rows_w);
-        e->last_kernel = rows ? "zz_logistic_rows_kernel" : lds_resident ? "zz_logistic_lds_kernel" : "zz_general_run_kernel";
-        int rcg = rows ? pdmp::launch_zz_logistic_rows(P, Q, LT, e->keep_integrals, rows_w, e->cfg.nchains, s)
-                       : lds_resident ? pdmp::launch_zz_logistic_lds(P, Q, LT, e->keep_integrals, e->cfg.nchains, s) : pdmp::launch_zz_general_run(P, Q, e->cfg.nchains, s);
+    case FAM_LOGISTIC_ROWS: e->last_kernel = "zz_logistic_rows_kernel"; rc = pdmp::launch_zz_logistic_rows(P, Q, LT, e->keep_integrals, logistic_rows_width(e), n, s); break;
+    case FAM_EXACTP: e->last_kernel = "zz_local_exactp_kernel"; rc = pdmp::launch_zz_local_exactp(P, n, s); break;
 #else
-        e->last_kernel = lds_resident ? "zz_logistic_lds_kernel" : "zz_general_run_kernel";
-        int rcg = lds_resident ? pdmp::launch_zz_logistic_lds(P, Q, LT, e->keep_integrals, e->cfg.nchains, s) : pdmp::launch_zz_general_run(P, Q, e->cfg.nchains, s);
+    case FAM_LOGISTIC_ROWS: case FAM_EXACTP: return fail(PDMP_ERR_UNSUPPORTED, "kernel family %d is not part of this library", (int)fam);  // (select_family never returns them here)
 #endif
-        if (rcg != 0) return fail(PDMP_ERR_HIP, "zz_general_run launch failed: %s", hipGetErrorString((hipError_t)rcg));
-        HIP_TRY(hipEventRecord(e->ev1, s));
-        e->timed = true;
-        if (phenv) {
-            HIP_TRY(device_sync(e));
-            HIP_TRY(hipMemcpy(e->dbg_phase_out, phbuf.p, sizeof e->dbg_phase_out, hipMemcpyDeviceToHost));
-            e->dbg_phase_valid = 2;  // general kernel: [0..6] = select, move G1, gradient, coin + G2, re-bound, re-queue, tail; [10] = proposals
-        }
-        return PDMP_OK;
     }
-    if (e->track) {
-        if (dbg_cap > 0) return fail(PDMP_ERR_UNSUPPORTED, "the proposal dump belongs to the one-event kernel");
-        P.track_two_sums = e->track_two_sums ? 1 : 0;
-        P.lattice_n = e->lattice_n;
-        P.lattice_magic = e->lattice_n ? (uint32_t)(((uint64_t)1 << 32) / (uint64_t)e->lattice_n + 1) : 0u;
-        // one proposal per lane where the graph is the plain lattice (pdmp_trackp.hip); elsewhere, and on request, the 8-lane-group kernel
-        if (e->track_lines) {
-            {
-                uint32_t hist[16] = {0}, best = 0;
-                for (int64_t k = 0; k < e->cfg.d; ++k) hist[std::min<uint32_t>(e->colptr[(size_t)k + 1] - e->colptr[(size_t)k], 15u)] += 1;
-                for (uint32_t k = 1; k < 16; ++k)
-                    if (hist[k] > hist[best]) best = k;
-                P.typ_extra = best > 0 ? best - 1u : 0u;
-            }
-            P.tl_lines = e->d_tl_lines.p;
-            P.tl_cold = e->d_tl_cold.p;
-            P.hw_gain = e->dbg_hw_steer[0];  // (pdmp_debug_set_helper_steering: block minima per quantum, events per window -- A/B; 0: the kernel's)
-            P.hw_target = (uint32_t)e->dbg_hw_steer[1];
-            P.hw_ahead = e->dbg_hw_steer[2];  // (a block to watch: the -DPDMP_TL_CHECK build of pdmp_trackl.hip)
-            e->last_kernel = "zz_local_trackl_kernel";
-            e->canon_stale = true;
-            int rcl = pdmp::launch_zz_local_trackl(P, e->cfg.nchains, s);
-            if (rcl != 0) return fail(PDMP_ERR_HIP, "zz_local_trackl launch failed (%d)", rcl);
-            HIP_TRY(hipEventRecord(e->ev1, s));
-            e->timed = true;
-            if (phenv) {
-                HIP_TRY(device_sync(e));
-                HIP_TRY(hipMemcpy(e->dbg_phase_out, phbuf.p, sizeof e->dbg_phase_out, hipMemcpyDeviceToHost));
-                e->dbg_phase_valid = 1;
-            }
-            return PDMP_OK;
-        }
-        if (e->track_pairs) {
-            P.keys = e->d_kp.p;
-            P.track_mean = e->track_mean;
-            if (e->track_mean == 2) P.tb.gmu_t = nullptr;  // (the rate's mean rides in the record lines)
-            // the two-wave form (a helper wave per chain) where the ensemble leaves SIMDs idle: at most two resident waves per SIMD with it
-            // (1024 SIMDs, two waves per chain) -- a rank's share of a strong-scaled job; wider ensembles hide a wave's latency with other chains
-            {
-                uint32_t hist[16] = {0}, best = 0;
-                for (int64_t k = 0; k < e->cfg.d; ++k) hist[std::min<uint32_t>(e->colptr[(size_t)k + 1] - e->colptr[(size_t)k], 15u)] += 1;
-                for (uint32_t k = 1; k < 16; ++k)
-                    if (hist[k] > hist[best]) best = k;
-                P.typ_extra = best > 0 ? best - 1u : 0u;
-            }
-            P.n_cu = e->n_cu;
-            P.hw_gain = e->dbg_hw_steer[0];
-            P.hw_target = (uint32_t)e->dbg_hw_steer[1];
-            P.hw_ahead = e->dbg_hw_steer[2];
-            P.helper_wave = (e->dbg_helper_wave == 1 || (e->dbg_helper_wave == -1 && e->cfg.nchains <= (int64_t)HELPER_WAVE_MAX_CHAINS_PER_CU * (e->n_cu > 0 ? e->n_cu : 256))) ? 1 : 0;
-            if (e->cfg.d > 16384) P.helper_wave = 0;  // (8192 block bounds leave no LDS for the ring: zz_local_trackp_big_kernel, one wave per chain)
-            e->last_kernel = e->cfg.d > 16384 ? "zz_local_trackp_big_kernel" : P.helper_wave ? (e->lattice_n ? "zz_local_trackp2_kernel" : "zz_local_trackp2_kernel<LAT=false>")
-                                           : (e->lattice_n ? "zz_local_trackp_kernel" : "zz_local_trackp_kernel<LAT=false>");
-            int rcp = pdmp::launch_zz_local_trackp(P, e->cfg.nchains, s);
-            if (rcp != 0) return fail(PDMP_ERR_HIP, "zz_local_trackp launch failed (%d)", rcp);
-            HIP_TRY(hipEventRecord(e->ev1, s));
-            e->timed = true;
-            if (phenv) {
-                HIP_TRY(device_sync(e));
-                HIP_TRY(hipMemcpy(e->dbg_phase_out, phbuf.p, sizeof e->dbg_phase_out, hipMemcpyDeviceToHost));
-                e->dbg_phase_valid = 1;
-            }
-            return PDMP_OK;
-        }
-        e->last_kernel = "zz_local_track_kernel";
-        int rct = pdmp::launch_zz_local_track(P, e->cfg.nchains, s);
-        if (rct != 0) return fail(PDMP_ERR_HIP, "zz_local_track launch failed (%d)", rct);
-        HIP_TRY(hipEventRecord(e->ev1, s));
-        e->timed = true;
-        if (phenv) {
-            HIP_TRY(device_sync(e));
-            HIP_TRY(hipMemcpy(e->dbg_phase_out, phbuf.p, sizeof e->dbg_phase_out, hipMemcpyDeviceToHost));
-            e->dbg_phase_valid = 1;
-        }
-        return PDMP_OK;
-    }
-#ifdef PDMP_EXTRA_KERNELS
-    if (e->exactp && spec_ok && !P.has_refresh) {
-        P.lattice_n = e->lattice_n;
-        P.lattice_magic = (uint32_t)(((uint64_t)1 << 32) / (uint64_t)e->lattice_n + 1);
-        if (pdmp::zz_exactp_supported(P)) {
-            e->last_kernel = "zz_local_exactp_kernel";
-            int rcx = pdmp::launch_zz_local_exactp(P, e->cfg.nchains, s);
-            if (rcx != 0) return fail(PDMP_ERR_HIP, "zz_local_exactp launch failed (%d)", rcx);
-            HIP_TRY(hipEventRecord(e->ev1, s));
-            e->timed = true;
-            if (phenv) {  // [10] iterations, [11] candidates, [12] left by the zone test, [13] committed, [14] events among the candidates
-                HIP_TRY(device_sync(e));
-                HIP_TRY(hipMemcpy(e->dbg_phase_out, phbuf.p, sizeof e->dbg_phase_out, hipMemcpyDeviceToHost));
-                e->dbg_phase_valid = 1;
-            }
-            return PDMP_OK;
-        }
-    }
-#endif
-    if (e->dbg_kernel == PDMP_DEBUG_KERNEL_EXACTP)  // asked for by name: never another kernel in its place
-#ifndef PDMP_EXTRA_KERNELS
-        return fail(PDMP_ERR_UNSUPPORTED, "PDMP_DEBUG_KERNEL_EXACTP: zz_local_exactp_kernel is not part of this library: it lives in the parity build (build.py --variant parity, -DPDMP_EXTRA_KERNELS)");
-#else
-        return fail(PDMP_ERR_UNSUPPORTED, "PDMP_DEBUG_KERNEL_EXACTP: spdmp on a plain lattice (16 <= n <= 128, d >= 2048) with the bounding matrix equal to the target's, no adaptation, and a trace or no trace");
-#endif
-    const bool sticky_spec = sticky && e->use_spec && e->blob_mmax <= 16 && dbg_cap == 0;  // the ZigZag speculative kernel's requirements, one zone member per lane
-    e->last_kernel = sticky ? (sticky_spec ? "zz_sticky_spec_kernel" : "zz_sticky_run_kernel") : "zz_local_run_kernel";
-    int rc = sticky ? (sticky_spec ? pdmp::launch_zz_sticky_spec(P, e->cfg.nchains, s) : pdmp::launch_zz_sticky_run(P, e->cfg.nchains, s))
-                    : spec_ok ? pdmp::launch_zz_local_spec(P, e->cfg.nchains, s, &e->last_kernel) : pdmp::launch_zz_local_run(P, e->cfg.nchains, s);
-    if (rc != 0) return fail(PDMP_ERR_HIP, "zz_local_run launch failed: %s", hipGetErrorString((hipError_t)rc));
+    if (rc != 0 && F.hip_rc) return fail(PDMP_ERR_HIP, "%s launch failed: %s", F.launcher, hipGetErrorString((hipError_t)rc));
+    if (rc != 0) return fail(PDMP_ERR_HIP, "%s launch failed (%d)", F.launcher, rc);
     HIP_TRY(hipEventRecord(e->ev1, s));
     e->timed = true;
-    if (phenv && spec_ok) {
+    if (profiled) {
         HIP_TRY(device_sync(e));
         HIP_TRY(hipMemcpy(e->dbg_phase_out, phbuf.p, sizeof e->dbg_phase_out, hipMemcpyDeviceToHost));
-        e->dbg_phase_valid = 1;  // speculative kernels: [0..8] = cycles per phase, [10] = iterations
+        e->dbg_phase_valid = F.phase_kind;
     }
-    if (dbg_cap > 0) {
+    if (dbg_cap > 0 && (fam == FAM_ONE_EVENT || fam == FAM_STICKY_RUN)) {  // (the general kernels take the buffer for a profile of theirs: nothing to print)
         HIP_TRY(device_sync(e));
         std::vector<double> hd((size_t)dbg_cap * 16);
         HIP_TRY(hipMemcpy(hd.data(), dbgbuf.p, hd.size() * sizeof(double), hipMemcpyDeviceToHost));
@@ -2795,6 +2772,34 @@ static void fill_bps_ext(const pdmp_ensemble* e, pdmp::BpsRunParams& B) {
     }
 }
 
+static pdmp::BpsRunParams bps_run_params(const pdmp_ensemble* e, double T, int flags) {
+    pdmp::BpsRunParams B{};
+    B.colptr = e->b_colptr.p;
+    B.rowval = e->b_rowval.p;
+    B.nzval = e->b_nzval.p;
+    B.mu = e->b_mu.p;
+    B.mu_flow = e->b_mu_flow.p;
+    B.flow_kind = e->bps_flow_kind;
+    B.ident = e->bps_ident ? 1 : 0;
+    B.x = e->b_x.p;
+    B.th = e->b_th.p;
+    B.scal = e->b_scal.p;
+    B.hdr = e->d_hdr.p;
+    B.ev_t = e->b_ev_t.p;
+    B.ev_x = e->b_ev_x.p;
+    B.ev_th = e->b_ev_th.p;
+    B.d = e->cfg.d;
+    B.trace_cap = e->cfg.trace_capacity;
+    B.T = T;
+    B.factor = e->cfg.factor;
+    B.lambda_ref = e->bps_lambda;
+    B.rho = e->bps_rho;
+    B.flags = flags;
+    B.adapt = e->cfg.adapt;
+    fill_bps_ext(e, B);
+    return B;
+}
+
 pdmp_status pdmp_ensemble_set_mass_cholesky(pdmp_ensemble* e, const int64_t* colptr, const int64_t* rowval,
                                             const double* nzval) {
     if (!e || !colptr || !rowval || !nzval) return fail(PDMP_ERR_INVALID, "null argument");
@@ -2969,22 +2974,7 @@ static pdmp_status init_state_bps(pdmp_ensemble* e, double t0, const double* x0,
     DevBuf<uint64_t> sseed;
     if ((st = sseed.alloc((size_t)n)) != PDMP_OK) return st;
     HIP_TRY(hipMemcpy(sseed.p, seeds, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice));
-    pdmp::BpsRunParams B{};
-    B.colptr = e->b_colptr.p;
-    B.rowval = e->b_rowval.p;
-    B.nzval = e->b_nzval.p;
-    B.mu = e->b_mu.p;
-    B.mu_flow = e->b_mu_flow.p;
-    B.flow_kind = e->bps_flow_kind;
-    B.ident = e->bps_ident ? 1 : 0;
-    B.x = e->b_x.p;
-    B.th = e->b_th.p;
-    B.scal = e->b_scal.p;
-    B.hdr = e->d_hdr.p;
-    B.d = d;
-    B.lambda_ref = e->bps_lambda;
-    B.rho = e->bps_rho;
-    fill_bps_ext(e, B);
+    const pdmp::BpsRunParams B = bps_run_params(e, t0, 0);  // (the init kernel reads the tables and the state arrays of the event loop's block)
     // the moments start at t0 (also after set_state_bps's placement probes, which run launches in between)
     if (e->bps_mom >= 1) HIP_TRY(hipMemsetAsync(e->b_j1.p, 0, (size_t)(n * d) * sizeof(double), e->stream));
     if (e->bps_mom >= 2) HIP_TRY(hipMemsetAsync(e->b_j2.p, 0, (size_t)(n * d) * sizeof(double), e->stream));

@@ -397,7 +397,8 @@ int launch_zz_local_track(const ZzRunParams& p, int64_t nchains, void* stream);
 bool zz_exactp_supported(const ZzRunParams& p);  // pdmp_exactp.hip: the moving evaluation, one proposal per lane
 int launch_zz_local_exactp(const ZzRunParams& p, int64_t nchains, void* stream);
 bool zz_trackp_supported(const ZzRunParams& p);
-int launch_zz_local_trackp(const ZzRunParams& p, int64_t nchains, void* stream);
+bool zz_trackp_big(int64_t d);  // beyond the two-wave form's lattice: one wave per chain whatever helper_wave says
+int launch_zz_local_trackp(const ZzRunParams& p, int64_t nchains, void* stream, const char** kname = nullptr);
 int launch_zz_keys_to_pairs(const double* keys, void* kp, int64_t n, double t0, void* stream);
 int launch_zz_trackp_c_out(const void* rec, double* c_chain, int64_t n, void* stream);
 int launch_zz_trackp_consts(void* rec, const CoordConst* cc, const uint16_t* nb16, const double* gmu, int64_t d, int64_t nchains, void* stream);

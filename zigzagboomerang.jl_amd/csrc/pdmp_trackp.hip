@@ -1249,24 +1249,28 @@ bool zz_trackp_supported(const ZzRunParams& p) {
     return (lattice || graph) && p.tb.gmu_t == nullptr && !p.track_two_sums && !p.has_refresh && p.d >= 2048;
 }
 
-int launch_zz_local_trackp(const ZzRunParams& p, int64_t nchains, void* stream) {
+bool zz_trackp_big(int64_t d) { return d > (int64_t)WL<false>::NBLK * 8; }  // 8192 block bounds in LDS (the lattice only), no room for the helper's ring: one wave per chain
+
+int launch_zz_local_trackp(const ZzRunParams& p, int64_t nchains, void* stream, const char** kname) {
     dim3 grid((unsigned)nchains), block(64);
     ZzRunParams q = p;
     q.nblk = (uint32_t)((p.d + 7) / 8);  // (dk is a multiple of 64, the padding keys are +Inf)
     const bool lat = p.lattice_n != 0;
+    if (kname) *kname = zz_trackp_big(p.d) ? "zz_local_trackp_big_kernel" : p.helper_wave ? (lat ? "zz_local_trackp2_kernel" : "zz_local_trackp2_kernel<LAT=false>")
+                                                                                        : (lat ? "zz_local_trackp_kernel" : "zz_local_trackp_kernel<LAT=false>");
     if (!p.helper_wave && !(q.hw_gain > 0.0)) {
         // one-wave forms: the step rule (W_GROW / W_SHRINK / W_SLACK: few candidates read in vain) where the launch fills the device and the memory
         // system is the other limit; a target count, as in the two-wave form, where it does not (at most three chains per SIMD, and always at
         // d > 16384, where LDS admits one chain per SIMD): a chain's rate is then set by how much one iteration commits.  A/B in one session,
         // round 5: 2048 chains 25.8 -> 22.0 ms, d = 65536 at 1024 chains 90.4 -> 80.4 ms; 4096 chains 46.6 -> 48.1 ms (so not there)
-        if (nchains <= (int64_t)W_TARGET_1W_MAX_PER_CU * (p.n_cu > 0 ? p.n_cu : 256) || p.d > (int64_t)WL<false>::NBLK * 8) {
+        if (nchains <= (int64_t)W_TARGET_1W_MAX_PER_CU * (p.n_cu > 0 ? p.n_cu : 256) || zz_trackp_big(p.d)) {
             q.hw_gain = W_GAIN_HW;
             q.hw_target = W_TARGET_1W;
         } else {
             q.hw_target = 0u;
         }
     }
-    if (p.d > (int64_t)WL<false>::NBLK * 8) {  // 8192 block bounds in LDS (the lattice only), one wave per chain
+    if (zz_trackp_big(p.d)) {
         if (p.dbg) hipLaunchKernelGGL((zz_local_trackp_big_kernel<true>), grid, block, W_BYTES_BIG, (hipStream_t)stream, q);
         else hipLaunchKernelGGL((zz_local_trackp_big_kernel<false>), grid, block, W_BYTES_BIG, (hipStream_t)stream, q);
         return (int)hipGetLastError();

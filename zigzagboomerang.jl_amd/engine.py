@@ -74,7 +74,7 @@ class Ensemble:
         _lib.check(self._L.pdmp_debug_set_helper_wave(self._h, int(mode)))
 
     def debug_set_track_lines(self, mode):
-        """zz_local_trackl (the line layout): -1 by ensemble width (default), 0 never, 1 wherever it serves; before set_state (include/pdmp_debug.h)."""
+        """zz_local_trackl (the line layout): -1 (default) and 0 never, 1 wherever it serves; before set_state (include/pdmp_debug.h)."""
         _lib.check(self._L.pdmp_debug_set_track_lines(self._h, int(mode)))
 
     def debug_buffer_addresses(self):
