@@ -138,6 +138,14 @@ pdmp_status pdmp_debug_math_probe(int device, uint64_t seed, int64_t n, double* 
 #define PDMP_MATH_POS_X 48        /* pdmp_exactp.hip pos_part */
 #define PDMP_MATH_POS_R 49        /* pdmp_logrows.hip pos_part */
 pdmp_status pdmp_debug_math_eval(int device, int fn, int64_t n, const double* a, const double* b, const double* c, double* out);
+/*
+ * Test hook: the scalars of the sticky Bouncy Particle / Boomerang loop as compiled inside pdmp_bps.hip, at (a[k], b[k], c[k]); out is [n].
+ * fn 0: pdmp_atan(a); 1: the linear freezing_time(x = a, θ = b) (src/ss_fact.jl:10-16); 2: the Boomerang's freezing_time(x = a, θ = b, μ = c)
+ * (src/ss_not_fact.jl:5-20).  The host restatement (tests/ref/sticky_notfact_ref.c) must agree bit for bit wherever the value is a number or
+ * an infinity.  Where it is a NaN -- a NaN argument, or x = 0 with θ = 0 (0/0) -- both sides return a NaN; its sign and payload are outside the
+ * contract (the default NaN of a 0/0 differs between x86-64 and gfx950), and the loop never lets a NaN clock win.  In every build of the library.
+ */
+pdmp_status pdmp_debug_sticky_eval(int device, int fn, int64_t n, const double* a, const double* b, const double* c, double* out);
 
 /*
  * Measurement hook: time (ms per launch, HIP events) of a write-only kernel with the event-record store pattern of the bouncy

@@ -12,6 +12,7 @@
  *   pdmp_log             natural log for positive normal doubles, < 1 ulp, only + - * / on doubles
  *   pdmp_exp             exp, < 1 ulp, only + - * / on doubles (logistic targets)
  *   pdmp_sincos          sin and cos for |x| <= 2^30 (Boomerang rotations); pdmp_sincos2pi: of 2*pi*v for v in [0,1)
+ *   pdmp_atan            atan for every double, < 1 ulp, only + - * / on doubles (the sticky Boomerang's freezing time)
  *   pdmp_randexp         -log(u)                       (replaces Random.randexp, src/poissontime.jl:77)
  *   pdmp_randn           Box-Muller normal             (replaces Random.randn,   src/dynamics.jl:115)
  *   pdmp_randn2          both Box-Muller branches of one block (the d-vector refresh of the non-factorised samplers)
@@ -283,6 +284,60 @@ PDMP_HD void pdmp_sincos(double x, double* s_out, double* c_out) {
     case 2: *s_out = -sr; *c_out = -cr; break;
     default: *s_out = -cr; *c_out = sr; break;
     }
+}
+
+/* ---------------------------------------------------------------- atan */
+/*
+ * atan for every double (Sun fdlibm s_atan.c): |x| is reduced at 7/16, 11/16, 19/16, 39/16 to t = (2|x|-1)/(2+|x|), (|x|-1)/(|x|+1),
+ * (|x|-1.5)/(1+1.5|x|) or -1/|x|, atan(x) = atan(k/2) + atan(t) with a two-part constant, and atan(t) = t - t*(odd polynomial in t^2).
+ * < 1 ulp; only + - * / on doubles, so the result is bit-identical on x86-64 and gfx950.  |x| < 2^-27 (subnormals, +-0) -> x itself;
+ * |x| >= 2^66 and +-Inf -> +-pi/2; NaN -> NaN.  Odd: atan(-x) = -atan(x) bit for bit.
+ * Replaces Base.atan in the Boomerang's freezing_time (src/ss_not_fact.jl:5-20).
+ */
+PDMP_HD double pdmp_atan(double x) {
+    const double hi0 = 4.63647609000806093515e-01, lo0 = 2.26987774529616870924e-17; /* atan(0.5) */
+    const double hi1 = 7.85398163397448278999e-01, lo1 = 3.06161699786838301793e-17; /* atan(1.0) */
+    const double hi2 = 9.82793723247329054082e-01, lo2 = 1.39033110312309984516e-17; /* atan(1.5) */
+    const double hi3 = 1.57079632679489655800e+00, lo3 = 6.12323399573676603587e-17; /* atan(inf) */
+    const double aT0 = 3.33333333333329318027e-01, aT1 = -1.99999999998764832476e-01, aT2 = 1.42857142725034663711e-01;
+    const double aT3 = -1.11111104054623557880e-01, aT4 = 9.09088713343650656196e-02, aT5 = -7.69187620504482999495e-02;
+    const double aT6 = 6.66107313738753120669e-02, aT7 = -5.83357013379057348645e-02, aT8 = 4.97687799461593236017e-02;
+    const double aT9 = -3.65315727442169155270e-02, aT10 = 1.62858201153657823623e-02;
+    if (x != x) return x;
+    const int neg = (pdmp_f2u(x) >> 63) != 0;
+    const double ax = neg ? -x : x;
+    double t, hi, lo;
+    if (ax >= 0x1.0p+66) return neg ? -hi3 : hi3;
+    if (ax < 0.4375) {
+        if (ax < 0x1.0p-27) return x;
+        t = ax;
+        hi = 0.0;
+        lo = 0.0;
+    } else if (ax < 0.6875) {
+        t = (2.0 * ax - 1.0) / (2.0 + ax);
+        hi = hi0;
+        lo = lo0;
+    } else if (ax < 1.1875) {
+        t = (ax - 1.0) / (ax + 1.0);
+        hi = hi1;
+        lo = lo1;
+    } else if (ax < 2.4375) {
+        t = (ax - 1.5) / (1.0 + 1.5 * ax);
+        hi = hi2;
+        lo = lo2;
+    } else {
+        t = -1.0 / ax;
+        hi = hi3;
+        lo = lo3;
+    }
+    const double z = t * t;
+    const double w = z * z;
+    const double s1 = z * (aT0 + w * (aT2 + w * (aT4 + w * (aT6 + w * (aT8 + w * aT10)))));
+    const double s2 = w * (aT1 + w * (aT3 + w * (aT5 + w * (aT7 + w * aT9))));
+    double r;
+    if (ax < 0.4375) r = t - t * (s1 + s2);
+    else r = hi - ((t * (s1 + s2) - lo) - t);
+    return neg ? -r : r;
 }
 
 #if defined(__HIPCC__)

@@ -39,7 +39,9 @@ extern "C" {
  * 3: pdmp_ensemble_consume_discretized no longer clamps *npoints (it reports the grid points the trace reaches; row 0 is always x0),
  *    pdmp_ensemble_gather_bps_traces / pdmp_comm_gathered_bps_copy / pdmp_ensemble_bps_trace_dev exist, and ensembles of at most seven chains per compute unit (1792 on an MI355X)
  *    run the tracked local ZigZag with a helper wavefront per chain (same results; include/pdmp_debug.h: pdmp_debug_set_helper_wave).
- *    A host binding must check pdmp_abi_version() at load time. */
+ *    A host binding must check pdmp_abi_version() at load time.
+ *    (still 3: pdmp_ensemble_set_bps_sticky, pdmp_ensemble_bps_trace_free_copy and pdmp_ensemble_bps_final_sticky were ADDED later -- the sticky
+ *    Bouncy Particle / Boomerang; nothing that existed changed, so a binding that wants them looks the symbols up.) */
 #define PDMP_ABI_VERSION 3
 
 typedef enum {
@@ -407,6 +409,24 @@ pdmp_status pdmp_ensemble_set_bps_moments(pdmp_ensemble* ens, int order);
  * for any BPS ensemble).
  */
 pdmp_status pdmp_ensemble_bps_moments(pdmp_ensemble* ens, double T, int64_t chain_first, int64_t n, double* j1, double* j2);
+
+/*
+ * sspdmp(∇ϕ!, t0, x0, θ0, T, c, Flow::Union{BouncyParticle,Boomerang}, κ, ...; strong_upperbounds) (src/ss_not_fact.jl:104-201): the sticky
+ * Bouncy Particle / Boomerang.  Every coordinate freezes when it hits 0 and thaws after an Exp(κ_i |θf_i|) time; reflections and refreshments
+ * act on the free coordinates; every event carries the free mask f.  The trace begins with the event (t0, x0, θ0, all free) (:189).
+ * kappa: [d] thaw-rate factors (> 0).  PDMP_SAMPLER_BPS; after set_flow_bps / set_flow_boomerang, before set_state_bps.  d <= 1024.
+ * The loop never reads the mass factor of a BouncyParticle (set_state_bps does not ask for one and ignores one that was given); a Boomerang
+ * needs the identity factor handed over explicitly (grad_correct!), a general one is refused.  Not combined with c::LocalBound, subsample or
+ * pdmp_ensemble_set_bps_moments(order >= 1): set_state_bps returns PDMP_ERR_UNSUPPORTED naming the option.  A freeze that finds
+ * |x_i| > 1e-8 (the reference's error(...), :129-132) and a violated bound without adapt end the chain as PDMP_CHAIN_BOUND_VIOLATED.
+ * PDMP_ERR_INVALID: a kappa entry <= 0 or not finite, NULL, a state exists, another sampler.  set_flow_* clears the setting.
+ * pdmp_ensemble_bps_trace_copy / _bps_final_state, the counters and trace_reset work as on a plain ensemble.
+ */
+pdmp_status pdmp_ensemble_set_bps_sticky(pdmp_ensemble* ens, const double* kappa, int strong_upperbounds);
+/* f of events [first, first+count) of one chain: [count x d] bytes, 1 = free (sevent, :100-102) */
+pdmp_status pdmp_ensemble_bps_trace_free_copy(pdmp_ensemble* ens, int64_t chain, int64_t first, int64_t count, uint8_t* f);
+/* final free mask and saved speeds θf of chains [chain_first, chain_first+n): [n x d] each, either may be NULL */
+pdmp_status pdmp_ensemble_bps_final_sticky(pdmp_ensemble* ens, int64_t chain_first, int64_t n, uint8_t* f, double* theta_f);
 
 /* ------------------------------------------------------------------ trace consumers on the device (what callers do next with Ξ)
  *

@@ -152,6 +152,13 @@ class Ensemble {
     int64_t nchains() const { return nchains_; }
     int64_t d() const { return d_; }
 
+    // sspdmp(…, Flow::Union{BouncyParticle, Boomerang}, κ; strong_upperbounds) (src/ss_not_fact.jl:182-201): after set_flow_bps /
+    // set_flow_boomerang, before set_state_bps; events then carry the free mask (pdmp_ensemble_bps_trace_free_copy)
+    void set_bps_sticky(const std::vector<double>& kappa, bool strong_upperbounds = false) {
+        if ((int64_t)kappa.size() != d_) throw std::invalid_argument("set_bps_sticky: kappa needs d entries");
+        check(pdmp_ensemble_set_bps_sticky(h_, kappa.data(), strong_upperbounds ? 1 : 0));
+    }
+
     std::vector<pdmp_chain_counters> counters() const {
         std::vector<pdmp_chain_counters> c((size_t)nchains_);
         check(pdmp_ensemble_counters(h_, c.data()));

@@ -25,6 +25,7 @@ PARITY_DEFINES = ("PDMP_EXTRA_KERNELS",)
 HEADERS = [os.path.join(CSRC, "pdmp_engine.hpp"),
            os.path.join(CSRC, "pdmp_device.hpp"),  # (the scalar and wave-level helpers every event-loop unit shares)
            os.path.join(CSRC, "pdmp_spec8g.inc"),  # (included by pdmp_kernels.hip)
+           os.path.join(CSRC, "pdmp_bps_sticky.inc"),  # (included by pdmp_bps.hip)
            os.path.join(PKG_DIR, "..", "include", "pdmp_mi355.h"),
            os.path.join(PKG_DIR, "..", "include", "pdmp_debug.h"),
            os.path.join(PKG_DIR, "..", "include", "pdmp_detmath.h")]

@@ -1030,6 +1030,8 @@ int launch_bps_run(const BpsRunParams& p, int64_t nchains, bool diag, void* stre
     return dispatch(p, m, nchains, diag, false, nullptr, 0.0, 0.0, stream);
 }
 
+#include "pdmp_bps_sticky.inc"  // the sticky Bouncy Particle / Boomerang (src/ss_not_fact.jl): kernels of their own, nothing above changes
+
 #ifdef PDMP_EXTRA_KERNELS
 // pdmp_debug_math_eval: the shared scalars (pdmp_device.hpp) this unit calls, as compiled here
 namespace {

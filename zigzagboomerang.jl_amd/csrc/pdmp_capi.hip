@@ -243,6 +243,11 @@ struct pdmp_ensemble {
     int bps_mom = 0;                // pdmp_ensemble_set_bps_moments: 0 off, 1 ∫x dt, 2 ∫x dt and ∫x² dt
     DevBuf<double> b_j1, b_j2;      // [nchains x d] the moments up to each chain's clock (kept by the event loop)
     DevBuf<double> b_jT, b_jT2;     // [nchains x d] the moments at the T of a read (pdmp_ensemble_bps_moments, the batch means / ESS sums)
+    // sticky Bouncy Particle / Boomerang (pdmp_ensemble_set_bps_sticky, src/ss_not_fact.jl)
+    bool bps_sticky = false;
+    int bps_strong = 0;
+    DevBuf<double> b_kappa, b_thf, b_tfrez;  // [d]; [nchains x d] saved speeds; [nchains x d] freezing / thaw times
+    DevBuf<uint64_t> b_fmask, b_ev_f;        // [nchains x 16], [nchains x cap x 16] free masks (bit e & 63 of word e >> 6)
     DevBuf<int64_t> bt_colptr, bt_rowval;
     DevBuf<double> bt_nzval, bt_mu;
     DevBuf<int32_t> m_Lcp, m_Lrv, m_Ucp, m_Urv;
@@ -1869,6 +1874,7 @@ pdmp_status pdmp_ensemble_set_state_synthetic(pdmp_ensemble* e, double t0, const
 
 static pdmp::BpsRunParams bps_run_params(const pdmp_ensemble* e, double T, int flags);
 static pdmp::BpsMomParams bps_moments_params(const pdmp_ensemble* e);
+static pdmp::BpsStickyParams bps_sticky_params(const pdmp_ensemble* e);
 
 pdmp_status pdmp_ensemble_run(pdmp_ensemble* e, double T, int flags, void* stream) {
     pdmp_status st = ensemble_run_impl(e, T, flags, stream);
@@ -1917,7 +1923,15 @@ static pdmp_status ensemble_run_impl(pdmp_ensemble* e, double T, int flags, void
     }
     int rc = 0;
     switch (fam) {
-    case FAM_BPS: e->last_kernel = "bps_run_kernel"; rc = pdmp::launch_bps_run(B, n, e->bps_diag, s, bps_moments_params(e)); break;
+    case FAM_BPS:
+        if (e->bps_sticky) {
+            e->last_kernel = "bps_sticky_run_kernel";
+            rc = pdmp::launch_bps_sticky_run(B, bps_sticky_params(e), n, s);
+        } else {
+            e->last_kernel = "bps_run_kernel";
+            rc = pdmp::launch_bps_run(B, n, e->bps_diag, s, bps_moments_params(e));
+        }
+        break;
     case FAM_GENERAL: e->last_kernel = "zz_general_run_kernel"; rc = pdmp::launch_zz_general_run(P, Q, n, s); break;
     case FAM_LOGISTIC_LDS: e->last_kernel = "zz_logistic_lds_kernel"; rc = pdmp::launch_zz_logistic_lds(P, Q, LT, e->keep_integrals, n, s); break;
     case FAM_TRACKL: e->last_kernel = "zz_local_trackl_kernel"; e->canon_stale = true; rc = pdmp::launch_zz_local_trackl(P, n, s); break;
@@ -2721,6 +2735,8 @@ static pdmp_status set_flow_nf(pdmp_ensemble* e, const int64_t* colptr, const in
     e->bps_own_target = false;
     e->bps_local_bound = e->bps_subsample = 0;
     e->bps_mom = 0;
+    e->bps_sticky = false;
+    e->bps_strong = 0;
     e->bps_lambda = lambda_ref;
     e->bps_rho = rho;
     pdmp_status st;
@@ -2881,6 +2897,33 @@ pdmp_status pdmp_ensemble_set_bps_moments(pdmp_ensemble* e, int order) {
     return PDMP_OK;
 }
 
+pdmp_status pdmp_ensemble_set_bps_sticky(pdmp_ensemble* e, const double* kappa, int strong_upperbounds) {
+    if (!e || !kappa) return fail(PDMP_ERR_INVALID, "null argument");
+    if (e->cfg.sampler != PDMP_SAMPLER_BPS || !e->has_flow)
+        return fail(PDMP_ERR_INVALID, "set_flow_bps / set_flow_boomerang first (PDMP_SAMPLER_BPS)");
+    if (e->has_state) return fail(PDMP_ERR_INVALID, "set_bps_sticky goes before set_state_bps");
+    const int64_t d = e->cfg.d;
+    for (int64_t i = 0; i < d; ++i)
+        if (!(kappa[i] > 0) || !std::isfinite(kappa[i])) return fail(PDMP_ERR_INVALID, "kappa[%lld] must be positive and finite", (long long)i);
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    pdmp_status st;
+    if ((st = e->b_kappa.upload(std::vector<double>(kappa, kappa + d))) != PDMP_OK) return st;
+    e->bps_sticky = true;
+    e->bps_strong = strong_upperbounds ? 1 : 0;
+    return PDMP_OK;
+}
+
+static pdmp::BpsStickyParams bps_sticky_params(const pdmp_ensemble* e) {
+    pdmp::BpsStickyParams q{};
+    q.kappa = e->b_kappa.p;
+    q.thf = e->b_thf.p;
+    q.tfrez = e->b_tfrez.p;
+    q.fmask = e->b_fmask.p;
+    q.ev_f = e->b_ev_f.p;
+    q.strong_upperbounds = e->bps_strong;
+    return q;
+}
+
 static pdmp::BpsMomParams bps_moments_params(const pdmp_ensemble* e) {
     pdmp::BpsMomParams m{};
     m.mom = e->bps_mom;
@@ -2948,7 +2991,17 @@ pdmp_status pdmp_ensemble_bps_moments(pdmp_ensemble* e, double T, int64_t chain_
 static pdmp_status init_state_bps(pdmp_ensemble* e, double t0, const double* x0, const double* theta0, double c, const uint64_t* seeds) {
     if (!e || !x0 || !theta0 || !seeds) return fail(PDMP_ERR_INVALID, "null argument");
     if (e->cfg.sampler != PDMP_SAMPLER_BPS || !e->has_flow) return fail(PDMP_ERR_INVALID, "set_flow_bps first");
-    if (e->bps_flow_kind == 0 && !e->bps_gamma_is_I && !e->bps_has_mass)
+    if (e->bps_sticky) {
+        // sticky_pdmp_inner! (src/ss_not_fact.jl:104-179) has no LocalBound, subsample or path-moment form here, and never reads a BouncyParticle's L
+        if (e->cfg.d > 64 * pdmp::BPS_STICKY_WORDS)
+            return fail(PDMP_ERR_UNSUPPORTED, "sticky BouncyParticle / Boomerang keeps d <= 1024 coordinates in registers: got %lld", (long long)e->cfg.d);
+        if (e->bps_local_bound) return fail(PDMP_ERR_UNSUPPORTED, "set_bps_sticky: not together with local_bound (set_bps_options)");
+        if (e->bps_subsample) return fail(PDMP_ERR_UNSUPPORTED, "set_bps_sticky: not together with subsample (set_bps_options)");
+        if (e->bps_mom >= 1) return fail(PDMP_ERR_UNSUPPORTED, "set_bps_sticky: not together with set_bps_moments(order >= 1)");
+        if (e->bps_flow_kind == 1 && e->bps_mass_tables)
+            return fail(PDMP_ERR_UNSUPPORTED, "set_bps_sticky: a Boomerang with a general mass factor L (set_mass_cholesky) is not implemented: identity only");
+    }
+    if (!e->bps_sticky && e->bps_flow_kind == 0 && !e->bps_gamma_is_I && !e->bps_has_mass)
         return fail(PDMP_ERR_UNSUPPORTED,
                     "BouncyParticle(Γ ≠ I) carries the mass factor L = cholesky(Symmetric(Γ)).L (src/types.jl:43): pass it with "
                     "pdmp_ensemble_set_mass_cholesky (an identity factor selects the identity mass explicitly)");
@@ -2978,6 +3031,23 @@ static pdmp_status init_state_bps(pdmp_ensemble* e, double t0, const double* x0,
     // the moments start at t0 (also after set_state_bps's placement probes, which run launches in between)
     if (e->bps_mom >= 1) HIP_TRY(hipMemsetAsync(e->b_j1.p, 0, (size_t)(n * d) * sizeof(double), e->stream));
     if (e->bps_mom >= 2) HIP_TRY(hipMemsetAsync(e->b_j2.p, 0, (size_t)(n * d) * sizeof(double), e->stream));
+    if (e->bps_sticky) {
+        const size_t W = (size_t)pdmp::BPS_STICKY_WORDS;
+        if (e->b_thf.n != (size_t)(n * d) && (st = e->b_thf.alloc((size_t)(n * d))) != PDMP_OK) return st;
+        if (e->b_tfrez.n != (size_t)(n * d) && (st = e->b_tfrez.alloc((size_t)(n * d))) != PDMP_OK) return st;
+        if (e->b_fmask.n != (size_t)n * W && (st = e->b_fmask.alloc((size_t)n * W)) != PDMP_OK) return st;
+        if (cap > 0) {
+            if (e->b_ev_f.n != (size_t)(n * cap) * W && (st = e->b_ev_f.alloc((size_t)(n * cap) * W)) != PDMP_OK) return st;
+            HIP_TRY(hipMemsetAsync(e->b_ev_f.p, 0, e->b_ev_f.n * sizeof(uint64_t), e->stream));  // (words past the last slot stay 0)
+        }
+        int rcs = pdmp::launch_bps_sticky_init(B, bps_sticky_params(e), n, sseed.p, t0, c, e->stream);
+        if (rcs != 0) return fail(PDMP_ERR_HIP, "bps_sticky_init launch failed (%d)", rcs);
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        e->has_state = true;
+        e->ran = false;
+        e->timed = false;
+        return PDMP_OK;
+    }
     int rc = pdmp::launch_bps_init(B, n, sseed.p, t0, c, e->stream);
     if (rc != 0) return fail(PDMP_ERR_HIP, "bps_init launch failed (%d)", rc);
     HIP_TRY(hipStreamSynchronize(e->stream));
@@ -3097,6 +3167,64 @@ pdmp_status pdmp_ensemble_bps_final_state(pdmp_ensemble* e, int64_t chain_first,
             if (c) c[k] = sc[k * 8 + 5];
         }
     }
+    return PDMP_OK;
+}
+
+// bit e & 63 of word e >> 6 -> one byte per coordinate
+static void unpack_free_mask(const uint64_t* w, int64_t d, uint8_t* f) {
+    for (int64_t i = 0; i < d; ++i) f[i] = (uint8_t)((w[i >> 6] >> (i & 63)) & 1ull);
+}
+
+pdmp_status pdmp_ensemble_bps_trace_free_copy(pdmp_ensemble* e, int64_t chain, int64_t first, int64_t count, uint8_t* f) {
+    if (!e || !f) return fail(PDMP_ERR_INVALID, "null argument");
+    const int64_t cap = e->cfg.trace_capacity, d = e->cfg.d, W = pdmp::BPS_STICKY_WORDS;
+    if (e->cfg.sampler != PDMP_SAMPLER_BPS || !e->bps_sticky || !e->has_state || cap <= 0)
+        return fail(PDMP_ERR_INVALID, "no sticky BPS trace buffer (pdmp_ensemble_set_bps_sticky, trace_capacity > 0, set_state_bps)");
+    if (chain < 0 || chain >= e->cfg.nchains || first < 0 || count < 0 || first + count > cap)
+        return fail(PDMP_ERR_INVALID, "trace range out of bounds");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(device_sync(e));
+    if (count == 0) return PDMP_OK;
+    std::vector<uint64_t> w((size_t)(count * W));
+    HIP_TRY(hipMemcpy(w.data(), e->b_ev_f.p + (chain * cap + first) * W, w.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    for (int64_t k = 0; k < count; ++k) unpack_free_mask(w.data() + k * W, d, f + k * d);
+    return PDMP_OK;
+}
+
+pdmp_status pdmp_ensemble_bps_final_sticky(pdmp_ensemble* e, int64_t chain_first, int64_t n, uint8_t* f, double* theta_f) {
+    if (!e) return fail(PDMP_ERR_INVALID, "null argument");
+    if (e->cfg.sampler != PDMP_SAMPLER_BPS || !e->bps_sticky || !e->has_state) return fail(PDMP_ERR_INVALID, "no sticky BPS state");
+    if (chain_first < 0 || n < 0 || chain_first + n > e->cfg.nchains) return fail(PDMP_ERR_INVALID, "chain range");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(device_sync(e));
+    const int64_t d = e->cfg.d, W = pdmp::BPS_STICKY_WORDS;
+    if (n == 0) return PDMP_OK;
+    if (f) {
+        std::vector<uint64_t> w((size_t)(n * W));
+        HIP_TRY(hipMemcpy(w.data(), e->b_fmask.p + chain_first * W, w.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        for (int64_t k = 0; k < n; ++k) unpack_free_mask(w.data() + k * W, d, f + k * d);
+    }
+    if (theta_f) HIP_TRY(hipMemcpy(theta_f, e->b_thf.p + chain_first * d, (size_t)(n * d) * sizeof(double), hipMemcpyDeviceToHost));
+    return PDMP_OK;
+}
+
+pdmp_status pdmp_debug_sticky_eval(int device, int fn, int64_t n, const double* a, const double* b, const double* c, double* out) {
+    if (!a || !b || !c || !out || n <= 0 || n > ((int64_t)1 << 30)) return fail(PDMP_ERR_INVALID, "bad argument");
+    if (fn < 0 || fn > 2) return fail(PDMP_ERR_INVALID, "pdmp_debug_sticky_eval: fn 0 (atan), 1 (linear freezing time) or 2 (Boomerang freezing time)");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(PDMP_ERR_NO_DEVICE, "no HIP device visible");
+    HIP_TRY(hipSetDevice(device));
+    DevBuf<double> in, res;
+    pdmp_status st = in.alloc((size_t)(3 * n));
+    if (st == PDMP_OK) st = res.alloc((size_t)n);
+    if (st != PDMP_OK) return st;
+    HIP_TRY(hipMemcpy(in.p, a, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(in.p + n, b, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(in.p + 2 * n, c, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    int rc = pdmp::launch_bps_sticky_eval(fn, n, in.p, in.p + n, in.p + 2 * n, res.p, nullptr);
+    if (rc != 0) return fail(PDMP_ERR_HIP, "sticky eval launch failed: %s", hipGetErrorString((hipError_t)rc));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, res.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
     return PDMP_OK;
 }
 

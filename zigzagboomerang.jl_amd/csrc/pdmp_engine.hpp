@@ -367,6 +367,20 @@ struct BpsMomParams {
     double* J2;
     int32_t mom, pad_;
 };
+// sticky Bouncy Particle / Boomerang (pdmp_bps_sticky.inc, src/ss_not_fact.jl): what the sticky loop keeps beside BpsRunParams' state.
+// scal[6] holds told there.  Free masks are bit e & 63 of word e >> 6.
+struct BpsStickyParams {
+    const double* __restrict__ kappa;  // [d]
+    double* thf;                       // [nchains x d] saved speeds θf (0 where free)
+    double* tfrez;                     // [nchains x d] freezing time where free, thaw time where frozen
+    uint64_t* fmask;                   // [nchains x 16] free mask of the state
+    uint64_t* ev_f;                    // [nchains x cap x 16] free mask of every event
+    int32_t strong_upperbounds, pad_;
+};
+constexpr int BPS_STICKY_WORDS = 16;   // d <= 1024
+int launch_bps_sticky_init(const BpsRunParams& p, const BpsStickyParams& q, int64_t nchains, const uint64_t* seeds, double t0, double c0, void* stream);
+int launch_bps_sticky_run(const BpsRunParams& p, const BpsStickyParams& q, int64_t nchains, void* stream);
+int launch_bps_sticky_eval(int fn, int64_t n, const double* a, const double* b, const double* c, double* out, void* stream);
 int launch_bps_write_probe(double* ev_x, double* ev_th, int64_t d, int64_t cap, int64_t nrec, int64_t nchains, void* stream);
 int launch_sector_probe(double* rec, int64_t d, int64_t nchains, int rounds, int write, double* sink, void* stream);
 int launch_bps_init(const BpsRunParams& p, int64_t nchains, const uint64_t* seeds, double t0, double c0, void* stream);

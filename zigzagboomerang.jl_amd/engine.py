@@ -215,6 +215,31 @@ class Ensemble:
         _lib.check(self._L.pdmp_ensemble_set_bps_moments(self._h, int(order)))
         self._bps_mom = int(order)
 
+    def set_bps_sticky(self, kappa, strong_upperbounds=False):
+        """sspdmp(..., Flow::Union{BouncyParticle, Boomerang}, κ; strong_upperbounds) (src/ss_not_fact.jl:182-201): κ is [d] or a scalar.
+        After set_flow_bps / set_flow_boomerang, before set_state_bps (pdmp_ensemble_set_bps_sticky)."""
+        k = np.ascontiguousarray(np.broadcast_to(np.asarray(kappa, dtype=np.float64), (self.d,)))
+        _lib.check(self._L.pdmp_ensemble_set_bps_sticky(self._h, _ptr(k), int(bool(strong_upperbounds))))
+
+    def bps_trace_free(self, chain, first=0, count=None, counters=None):
+        """f of events [first, first + count) of one chain of a sticky ensemble: [count x d] bool (pdmp_ensemble_bps_trace_free_copy)."""
+        if counters is None:
+            counters = self.counters()
+        if count is None:
+            count = int(counters["ntrace"][chain]) - first
+        f = np.empty((count, self.d), dtype=np.uint8)
+        _lib.check(self._L.pdmp_ensemble_bps_trace_free_copy(self._h, int(chain), int(first), int(count), _ptr(f)))
+        return f.astype(bool)
+
+    def bps_final_sticky(self, chain_first=0, n=None):
+        """Final free mask f ([n x d] bool) and saved speeds θf ([n x d]) of a sticky ensemble (pdmp_ensemble_bps_final_sticky)."""
+        if n is None:
+            n = self.nchains - chain_first
+        f = np.empty((n, self.d), dtype=np.uint8)
+        thf = np.empty((n, self.d))
+        _lib.check(self._L.pdmp_ensemble_bps_final_sticky(self._h, int(chain_first), int(n), _ptr(f), _ptr(thf)))
+        return dict(f=f.astype(bool), theta_f=thf)
+
     def bps_moments(self, T, chain_first=0, n=None):
         """(J1, J2) = (∫_{t0}^{T} x dt, ∫_{t0}^{T} x² dt) of chains [chain_first, chain_first + n), each [n x d]; J2 is None when the
         ensemble keeps order 1.  Every chain must have t <= T <= its next event (pdmp_ensemble_bps_moments)."""

@@ -210,6 +210,9 @@ class PDMPTrace:
     t: np.ndarray = field(default_factory=lambda: np.empty(0))
     x: np.ndarray = field(default_factory=lambda: np.empty((0, 0)))
     θ: np.ndarray = field(default_factory=lambda: np.empty((0, 0)))
+    # sticky samplers (src/ss_not_fact.jl:100-102, Trace(t0, x0, θ0, f, Flow)): the free mask at t0 and after every event, [events x d] bool
+    f0: Optional[np.ndarray] = None
+    f: Optional[np.ndarray] = None
 
     def __len__(self):
         return 1 + len(self.t)

@@ -145,16 +145,33 @@ def _pdmp_nd(target, t0, x0, θ0, T, c, F, *, factor=1.8, adapt=False, subsample
     return _zigzag(_lib.SAMPLER_ZIGZAG_ALL, target, t0, x0, θ0, T, c, F, factor, adapt, seed, device, trace_capacity, trace)
 
 
-def sspdmp(target, t0, x0, θ0, T, c, *GFκ, reversible=False, strong_upperbounds=False, factor=1.5, adapt=False,
+def sspdmp(target, t0, x0, θ0, T, c, *GFκ, reversible=False, strong_upperbounds=False, factor=None, adapt=False,
            seed=DEFAULT_SEED, device=0, trace_capacity=None, trace=True, G=None):
     """Sticky ZigZag: sspdmp(∇ϕ, t0, x0, θ0, T, c, [G,] F::ZigZag, κ, args...; reversible, strong_upperbounds, factor=1.5,
-    adapt) (src/ss_fact.jl:159-160,217) -> Ξ, (t, x, θ), (acc, num), c with scalar acc, num (:175,214).  G as in spdmp (:167-172)."""
+    adapt) (src/ss_fact.jl:159-160,217) -> Ξ, (t, x, θ), (acc, num), c with scalar acc, num (:175,214).  G as in spdmp (:167-172).
+
+    Sticky Bouncy Particle / Boomerang: sspdmp(∇ϕ!, t0, x0, θ0, T, c, Flow::Union{BouncyParticle, Boomerang}, κ, args...;
+    strong_upperbounds, adapt, factor=2.0) (src/ss_not_fact.jl:182-201) -> Ξ, (t, x, θ), (acc, num), c.  Ξ is a PDMPTrace carrying f0 and f
+    ([events x d] bool, True = free); its first event is (t0, x0, θ0, all free) (:189).  target as in pdmp: None (∇ϕ!(y, x) = B.Γ(x − B.μ))
+    or a GaussianTarget for a BouncyParticle, a GaussianTarget for a Boomerang.  κ: [d] or a scalar.  No G, no `reversible`.
+
+    factor=None is each signature's own default: 1.5 for a ZigZag, 2.0 for a BouncyParticle / Boomerang; a value given is used as given."""
+    if len(GFκ) == 2 and isinstance(GFκ[0], (BouncyParticle, Boomerang)):
+        if G is not None or reversible:
+            raise TypeError("sspdmp(..., Flow::Union{BouncyParticle, Boomerang}, κ): no G and no `reversible` (src/ss_not_fact.jl:182-183)")
+        F = GFκ[0]
+        if isinstance(F, Boomerang) and not isinstance(target, GaussianTarget):
+            raise TypeError("Boomerang: target must be a GaussianTarget (∇ϕ!(y, x) = Γ(x − μ))")
+        if isinstance(F, BouncyParticle) and target is not None and not isinstance(target, GaussianTarget):
+            raise TypeError("BouncyParticle: target is None (∇ϕ!(y, x) = B.Γ(x − B.μ)) or a GaussianTarget of its own")
+        return _bps(t0, x0, θ0, T, c, F, 2.0 if factor is None else factor, adapt, seed, device, trace_capacity, trace, target=target,
+                    sticky=(GFκ[1], strong_upperbounds))
     if len(GFκ) not in (2, 3):
         raise TypeError("expected sspdmp(target, t0, x0, θ0, T, c, [G,] F, κ, ...)")
     G, F = _split_G(GFκ[:-1], G)
     κ = GFκ[-1]
-    return _zigzag(_lib.SAMPLER_STICKY_ZIGZAG, target, t0, x0, θ0, T, c, F, factor, adapt, seed, device, trace_capacity, trace,
-                   sticky=(np.asarray(κ, dtype=np.float64), reversible, strong_upperbounds), G=G)
+    return _zigzag(_lib.SAMPLER_STICKY_ZIGZAG, target, t0, x0, θ0, T, c, F, 1.5 if factor is None else factor, adapt, seed, device,
+                   trace_capacity, trace, sticky=(np.asarray(κ, dtype=np.float64), reversible, strong_upperbounds), G=G)
 
 
 class Partition:
@@ -337,7 +354,7 @@ def _zigzag(sampler, target, t0, x0, θ0, T, c, F, factor, adapt, seed, device, 
     return traces, (fs["t"], fs["x"], fs["theta"]), (acc, num), c_out
 
 
-def _bps(t0, x0, θ0, T, c, B, factor, adapt, seed, device, trace_capacity, trace, target=None, subsample=False, moments=False):
+def _bps(t0, x0, θ0, T, c, B, factor, adapt, seed, device, trace_capacity, trace, target=None, subsample=False, moments=False, sticky=None):
     local_bound = isinstance(c, LocalBound)
     if local_bound:
         c = float(np.asarray(c.c, dtype=np.float64).reshape(-1)[0])
@@ -362,7 +379,10 @@ def _bps(t0, x0, θ0, T, c, B, factor, adapt, seed, device, trace_capacity, trac
             ens.set_bps_options(local_bound, subsample)
         if moments:
             ens.set_bps_moments(2)
+        if sticky is not None:
+            ens.set_bps_sticky(*sticky)
         ens.set_state_bps(t0, X0, TH0, float(c), seeds)
+        fs_ = [[] for _ in range(nch)]
         ts = [[] for _ in range(nch)]
         xs = [[] for _ in range(nch)]
         ths = [[] for _ in range(nch)]
@@ -374,6 +394,8 @@ def _bps(t0, x0, θ0, T, c, B, factor, adapt, seed, device, trace_capacity, trac
                 ens.run(T, flags)
                 cnt = ens.counters()
                 if np.any(cnt["status"] == _lib.CHAIN_BOUND_VIOLATED):
+                    if sticky is not None:  # (either error(...) of src/ss_not_fact.jl:129-132,160)
+                        raise RuntimeError("Tuning parameter `c` too small, or a coordinate froze away from 0 (|x[i]| > 1e-8).")
                     raise RuntimeError("Tuning parameter `c` too small.")  # src/not_fact_samplers.jl:82
                 if trace:
                     for k in range(nch):
@@ -382,6 +404,8 @@ def _bps(t0, x0, θ0, T, c, B, factor, adapt, seed, device, trace_capacity, trac
                             ts[k].append(a)
                             xs[k].append(b_)
                             ths[k].append(c_)
+                            if sticky is not None:
+                                fs_[k].append(ens.bps_trace_free(k, counters=cnt))
                     ens.trace_reset()
                 if not _lib.needs_rerun(cnt["status"]):  # (both resume with the next run)
                     break
@@ -398,6 +422,9 @@ def _bps(t0, x0, θ0, T, c, B, factor, adapt, seed, device, trace_capacity, trac
                                     np.concatenate(ths[k])))
         else:
             traces.append(PDMPTrace(B, t0, X0[k].copy(), TH0[k].copy(), np.empty(0), np.empty((0, d)), np.empty((0, d))))
+        if sticky is not None:
+            traces[-1].f0 = np.ones(d, dtype=bool)
+            traces[-1].f = np.concatenate(fs_[k]) if fs_[k] else np.empty((0, d), dtype=bool)
     acc, num = cnt["nacc"].astype(np.int64), cnt["num"].astype(np.int64)
     if single:
         out = traces[0], (fs["t"][0], fs["x"][0], fs["theta"][0]), (int(acc[0]), int(num[0])), fs["c"][0]

@@ -113,6 +113,9 @@ def _discretize_pdmp(tr: PDMPTrace, dt):
         xs = (X[idx] - mu) * np.cos(tau) + TH[idx] * np.sin(tau) + mu
     else:
         xs = X[idx] + TH[idx] * tau
+    if tr.f is not None:  # a sticky trace: smove_forward!(…, f, …) moves the free coordinates only (src/ss_not_fact.jl:78-97)
+        Fm = np.vstack([np.asarray(tr.f0, dtype=bool)[None], np.asarray(tr.f, dtype=bool).reshape(-1, d)])
+        xs = np.where(Fm[idx], xs, X[idx])
     return grid, xs
 
 
@@ -301,7 +304,17 @@ def subtrace(tr: FactTrace, J):
 
 
 def inclusion_prob(tr: FactTrace):
-    """inclusion_prob(Ξ): fraction of time each coordinate is non-zero -- src/trace.jl:161-178."""
+    """inclusion_prob(Ξ): fraction of time each coordinate is non-zero -- src/trace.jl:161-178.  A sticky PDMPTrace (one carrying f):
+    the fraction of [t0, T_last] each coordinate is free, from the recorded masks."""
+    if isinstance(tr, PDMPTrace):
+        if tr.f is None:
+            raise TypeError("inclusion_prob of a PDMPTrace needs the free masks of a sticky sampler (sspdmp)")
+        d = len(tr.x0)
+        te = np.concatenate([[tr.t0], np.asarray(tr.t, dtype=np.float64)])
+        Fm = np.vstack([np.asarray(tr.f0, dtype=bool)[None], np.asarray(tr.f, dtype=bool).reshape(-1, d)])
+        if len(te) < 2 or not te[-1] > tr.t0:
+            return Fm[0].astype(np.float64)
+        return (Fm[:-1] * np.diff(te)[:, None]).sum(0) / (te[-1] - tr.t0)
     ev = tr.events
     i, dt, _, xp = _segment_integrals(tr)
     T = ev["t"][-1]
