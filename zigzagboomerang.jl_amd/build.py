@@ -24,6 +24,7 @@ EXTRA_SOURCES = ["pdmp_exactp.hip", "pdmp_logrows.hip"]
 PARITY_DEFINES = ("PDMP_EXTRA_KERNELS",)
 HEADERS = [os.path.join(CSRC, "pdmp_engine.hpp"),
            os.path.join(CSRC, "pdmp_device.hpp"),  # (the scalar and wave-level helpers every event-loop unit shares)
+           os.path.join(CSRC, "pdmp_spec8_common.hpp"),  # (the 8-event loop's machinery, shared by pdmp_kernels.hip's three kernels of it)
            os.path.join(CSRC, "pdmp_spec8g.inc"),  # (included by pdmp_kernels.hip)
            os.path.join(CSRC, "pdmp_bps_sticky.inc"),  # (included by pdmp_bps.hip)
            os.path.join(PKG_DIR, "..", "include", "pdmp_mi355.h"),

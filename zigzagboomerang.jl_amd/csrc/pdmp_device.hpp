@@ -30,6 +30,9 @@ __device__ __forceinline__ double readlane_f64(double v, int srclane) {
     int hi = __builtin_amdgcn_readlane(__double2hiint(v), srclane);
     return __hiloint2double(hi, lo);
 }
+__device__ __forceinline__ uint32_t readlane_u32(uint32_t v, int srclane) {
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, srclane);
+}
 __device__ __forceinline__ uint32_t uniform_u32(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
 }
@@ -54,6 +57,14 @@ __device__ __forceinline__ double dpp_f64(double v) {
     lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, true);  // every lane has a valid source: no tied `old` operand, no copies
     hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, true);
     return __hiloint2double(hi, lo);
+}
+template <int CTRL>
+__device__ __forceinline__ uint32_t dpp_u32(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, CTRL, 0xf, 0xf, true);
+}
+__device__ __forceinline__ uint32_t umin3(uint32_t a, uint32_t b, uint32_t c) {
+    const uint32_t ab = (a < b) ? a : b;
+    return (ab < c) ? ab : c;  // v_min3_u32
 }
 
 // One v_min_f64.  Written as the instruction itself: fmin() of a value that came out of a load or a DPP move is preceded by a
@@ -91,8 +102,23 @@ __device__ __forceinline__ double grp8_min_f64(double v) {
     v = min_f64(v, dpp_f64<0x141>(v));  // row_half_mirror: reverses each half row
     return v;
 }
-// The same six steps for u32, wave-uniform (DPP: six steps on the vector unit instead of six ds_bpermute round trips; pdmp_kernels.hip
-// keeps a __shfl_xor form, wave_min_u32, of its own)
+// minimum over the 16 lanes of a DPP row, returned in every lane of the row
+__device__ __forceinline__ double row_min_f64(double v) {
+    v = min_f64(v, dpp_f64<0xB1>(v));
+    v = min_f64(v, dpp_f64<0x4E>(v));
+    v = min_f64(v, dpp_f64<0x141>(v));
+    v = min_f64(v, dpp_f64<0x140>(v));
+    return v;
+}
+// Minimum of a u32 over the 64 lanes, wave-uniform: the __shfl_xor form of pdmp_kernels.hip's older kernels ...
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
+    for (int off = 32; off >= 1; off >>= 1) {
+        uint32_t o = (uint32_t)__shfl_xor((int)v, off, 64);
+        v = (o < v) ? o : v;
+    }
+    return uniform_u32(v);
+}
+// ... and the same six steps as wave_min_f64 (DPP: on the vector unit instead of six ds_bpermute round trips) of the tracked kernels
 __device__ __forceinline__ uint32_t wave_min_u32_dpp(uint32_t v) {
     auto step = [](uint32_t x, auto ctrl) -> uint32_t {
         const uint32_t o = (uint32_t)__builtin_amdgcn_mov_dpp((int)x, decltype(ctrl)::value, 0xf, 0xf, true);

@@ -23,23 +23,9 @@
 #include "../../include/pdmp_detmath.h"
 #include "pdmp_device.hpp"
 #include "pdmp_engine.hpp"
+#include "pdmp_spec8_common.hpp"
 
 namespace pdmp {
-
-// ------------------------------------------------------------------------------------------ lane helpers
-
-__device__ __forceinline__ uint32_t readlane_u32(uint32_t v, int srclane) {
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, srclane);
-}
-
-// (the __shfl_xor form; wave_min_u32_dpp of pdmp_device.hpp is the DPP one of the tracked kernels)
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
-    for (int off = 32; off >= 1; off >>= 1) {
-        uint32_t o = (uint32_t)__shfl_xor((int)v, off, 64);
-        v = (o < v) ? o : v;
-    }
-    return uniform_u32(v);
-}
 
 // ------------------------------------------------------------------------------------------ init kernel
 //
@@ -1083,15 +1069,6 @@ size_t zz_spec_wide_lds_bytes(uint32_t nblk_pad, uint32_t blob_w_pad) {
     return (size_t)SPW_LB + (size_t)4 * blob_w_pad * 8 + (size_t)nblk_pad * 8 + (size_t)nblk_pad * 4;
 }
 
-// minimum over the 16 lanes of a DPP row, returned in every lane of the row
-__device__ __forceinline__ double row_min_f64(double v) {
-    v = min_f64(v, dpp_f64<0xB1>(v));
-    v = min_f64(v, dpp_f64<0x4E>(v));
-    v = min_f64(v, dpp_f64<0x141>(v));
-    v = min_f64(v, dpp_f64<0x140>(v));
-    return v;
-}
-
 
 // ---- pieces shared by the two speculative kernels (always inlined: same code as written in place) ----
 
@@ -1151,23 +1128,19 @@ __device__ __forceinline__ int spec_select(const double* bk, uint32_t nblk, int 
 // a group q < g?  A cheap necessary condition runs first -- the id must lie inside the [min, max] id span of an earlier group's
 // zone (two u32 row reductions, six scalar reads) -- and only if some lane of the wave passes it (about one iteration in three
 // on the 128 x 128 lattice) are the 48 id comparisons made.
-template <int CTRL>
-__device__ __forceinline__ uint32_t zone_dpp_u32(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, CTRL, 0xf, 0xf, true);
-}
 template <int E>
 __device__ __forceinline__ bool spec_zone_conflict(const uint32_t* Z, uint32_t s, int g, bool member) {
     uint32_t lo = member ? s : 0xffffffffu, hi = member ? s : 0u;
     {
         uint32_t o;
-        o = zone_dpp_u32<0xB1>(lo);   lo = (o < lo) ? o : lo;
-        o = zone_dpp_u32<0x4E>(lo);   lo = (o < lo) ? o : lo;
-        o = zone_dpp_u32<0x141>(lo);  lo = (o < lo) ? o : lo;
-        o = zone_dpp_u32<0x140>(lo);  lo = (o < lo) ? o : lo;
-        o = zone_dpp_u32<0xB1>(hi);   hi = (o > hi) ? o : hi;
-        o = zone_dpp_u32<0x4E>(hi);   hi = (o > hi) ? o : hi;
-        o = zone_dpp_u32<0x141>(hi);  hi = (o > hi) ? o : hi;
-        o = zone_dpp_u32<0x140>(hi);  hi = (o > hi) ? o : hi;
+        o = dpp_u32<0xB1>(lo);   lo = (o < lo) ? o : lo;
+        o = dpp_u32<0x4E>(lo);   lo = (o < lo) ? o : lo;
+        o = dpp_u32<0x141>(lo);  lo = (o < lo) ? o : lo;
+        o = dpp_u32<0x140>(lo);  lo = (o < lo) ? o : lo;
+        o = dpp_u32<0xB1>(hi);   hi = (o > hi) ? o : hi;
+        o = dpp_u32<0x4E>(hi);   hi = (o > hi) ? o : hi;
+        o = dpp_u32<0x141>(hi);  hi = (o > hi) ? o : hi;
+        o = dpp_u32<0x140>(hi);  hi = (o > hi) ? o : hi;
     }
     bool maybe = false;
 #pragma unroll
@@ -1200,14 +1173,14 @@ __device__ __forceinline__ bool spec_zone_conflict_wide(const uint32_t* Z, uint3
     hi = (member2 && s2 > hi) ? s2 : hi;
     {
         uint32_t o;
-        o = zone_dpp_u32<0xB1>(lo);   lo = (o < lo) ? o : lo;
-        o = zone_dpp_u32<0x4E>(lo);   lo = (o < lo) ? o : lo;
-        o = zone_dpp_u32<0x141>(lo);  lo = (o < lo) ? o : lo;
-        o = zone_dpp_u32<0x140>(lo);  lo = (o < lo) ? o : lo;
-        o = zone_dpp_u32<0xB1>(hi);   hi = (o > hi) ? o : hi;
-        o = zone_dpp_u32<0x4E>(hi);   hi = (o > hi) ? o : hi;
-        o = zone_dpp_u32<0x141>(hi);  hi = (o > hi) ? o : hi;
-        o = zone_dpp_u32<0x140>(hi);  hi = (o > hi) ? o : hi;
+        o = dpp_u32<0xB1>(lo);   lo = (o < lo) ? o : lo;
+        o = dpp_u32<0x4E>(lo);   lo = (o < lo) ? o : lo;
+        o = dpp_u32<0x141>(lo);  lo = (o < lo) ? o : lo;
+        o = dpp_u32<0x140>(lo);  lo = (o < lo) ? o : lo;
+        o = dpp_u32<0xB1>(hi);   hi = (o > hi) ? o : hi;
+        o = dpp_u32<0x4E>(hi);   hi = (o > hi) ? o : hi;
+        o = dpp_u32<0x141>(hi);  hi = (o > hi) ? o : hi;
+        o = dpp_u32<0x140>(hi);  hi = (o > hi) ? o : hi;
     }
     bool maybe = false;
 #pragma unroll
@@ -1348,17 +1321,7 @@ __device__ __forceinline__ void zz_local_spec_body(const ZzRunParams& P_in) {
     PDMP_LDS_ORDER();
 
     uint32_t rng_base = 0xffffffffu;  // first draw (as a delta to nm0) held in U/LU; none yet
-    uint64_t ph[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    uint64_t ph_t0 = PROF ? (uint64_t)__builtin_readcyclecounter() : 0;
-    uint64_t ph_iters = 0;
-#define PHASE(k)                                                          \
-    do {                                                                  \
-        if (PROF) {                                                       \
-            const uint64_t now_ = (uint64_t)__builtin_readcyclecounter(); \
-            ph[k] += now_ - ph_t0;                                        \
-            ph_t0 = now_;                                                 \
-        }                                                                 \
-    } while (0)
+    PhaseClock<PROF> phc;
 
     bool running = stop_before || (t_event < T);
     PrioTurn prio;
@@ -1519,8 +1482,8 @@ __device__ __forceinline__ void zz_local_spec_body(const ZzRunParams& P_in) {
                 }
             }
         }
-        PHASE(0);
-        if (PROF) ph_iters += 1;
+        phc.mark(0);
+        if (PROF) phc.iters += 1;
         const bool gvalid = g < Esel;
         const double tp = gvalid ? SLT[g] : PDMP_INF;
         const uint32_t blk = gvalid ? SLB[g] : 0u;
@@ -1547,7 +1510,7 @@ __device__ __forceinline__ void zz_local_spec_body(const ZzRunParams& P_in) {
         }
         const uint32_t rng_off = dnm - rng_base;
         PDMP_LDS_ORDER();
-        PHASE(1);
+        phc.mark(1);
         // ---------------- neighbourhood header and member list
         int k = 0, m = 0, self = 0, kjmax = 0;
         uint32_t s = 0xffffff00u + (uint32_t)lane;
@@ -1569,7 +1532,7 @@ __device__ __forceinline__ void zz_local_spec_body(const ZzRunParams& P_in) {
         }
         const bool member = gvalid && gl < m;
         const bool member2 = WIDE && gvalid && gl + 16 < m;
-        PHASE(2);
+        phc.mark(2);
         ZzRec* rs = rec + (member ? s : i);
         ZzRec* rs2 = rec + (member2 ? s2 : i);
         double x = 0.0, th = 0.0, t = 0.0, I = 0.0;
@@ -1620,7 +1583,7 @@ __device__ __forceinline__ void zz_local_spec_body(const ZzRunParams& P_in) {
         PDMP_LDS_ORDER();
         const uint64_t confball = WIDE ? __ballot(spec_zone_conflict_wide<E>(Z, s, s2, g, member, member2))
                                        : __ballot(spec_zone_conflict<E>(Z, s, g, member));
-        PHASE(3);
+        phc.mark(3);
 
         // ---------------- smove_forward!(G, i, ...), gradient, rates
         if (gvalid && gl < k) {
@@ -1678,7 +1641,7 @@ __device__ __forceinline__ void zz_local_spec_body(const ZzRunParams& P_in) {
         }
         const bool accept = accept_u != 0;
         const bool violated = violated_u != 0;
-        PHASE(4);
+        phc.mark(4);
 
         int nmoved = k;
         if (gvalid && accept) {
@@ -1759,7 +1722,7 @@ __device__ __forceinline__ void zz_local_spec_body(const ZzRunParams& P_in) {
             if (active && (s >> 6) == blk) pk[s & 63] = key;
             PDMP_LDS_ORDER();
         }
-        PHASE(5);
+        phc.mark(5);
         // ---------------- patched minimum of the popped block, and everything this event could expose
         double rowmin, candmin;
         uint32_t cand;
@@ -1822,7 +1785,7 @@ __device__ __forceinline__ void zz_local_spec_body(const ZzRunParams& P_in) {
                 vsel = (int)r_ok;
             }
         }
-        PHASE(6);
+        phc.mark(6);
 
         // ---------------- commit the valid prefix
         const bool commit = gvalid && (uint32_t)g < Rc;
@@ -1863,7 +1826,7 @@ __device__ __forceinline__ void zz_local_spec_body(const ZzRunParams& P_in) {
             }
         }
         PDMP_LDS_ORDER();
-        PHASE(7);
+        phc.mark(7);
         // ---------------- level-1 updates for re-bounded neighbours living in other blocks.  A block's final entry is the
         // smallest (key, coordinate) among its old entry and the new keys, whatever the order: when no two of these lanes aim at
         // one block (claims through the now idle zone-id array) and none has to rescan, every lane updates its block by itself in
@@ -1897,7 +1860,7 @@ __device__ __forceinline__ void zz_local_spec_body(const ZzRunParams& P_in) {
             }
             }
         }
-        PHASE(8);
+        phc.mark(8);
         // ---------------- the violating proposal itself (reference: counted, G[i] moved, acc bumped -- then error(...), :120-124):
         // what zz_local_run_kernel and the oracle leave behind
         if (vsel >= 0) {
@@ -1925,11 +1888,7 @@ __device__ __forceinline__ void zz_local_spec_body(const ZzRunParams& P_in) {
         PDMP_LDS_ORDER();
     }
 
-    if (PROF && P.dbg && chain == 0 && lane == 0) {
-        for (int q = 0; q < 10; ++q) P.dbg[q] = (double)ph[q];
-        P.dbg[10] = (double)ph_iters;
-    }
-#undef PHASE
+    if (PROF && P.dbg && chain == 0 && lane == 0) phc.store(P.dbg);
     if (lane == 0) {
         hdr->c.t_last = t_last;
         hdr->t_event = t_event;
@@ -1956,25 +1915,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 
 // ------------------------------------------------------------------------------------------ 8 events per iteration
 //
-// zz_local_spec_kernel's scheme with EIGHT event slots per iteration, one per 8-lane group, for the north-star workload (the
-// PLAIN configuration on the 128 x 128 lattice: |G1| <= 5 <= 8 lanes, |S| <= 13 <= 16 = two zone members per lane).  The
-// instruction stream of an iteration -- selection, loads, accept chain, validation, commit -- is issued once for eight events
-// instead of four.  The kernel sits at the memory system's random-sector rate and at the instruction issue rate of 4 waves per
-// SIMD at the same time, so both the sectors and the instructions per event count.  What changes:
-//   queue     the first level has 512 entries over key blocks of 32: a popped block is four 64-byte sectors, not eight
-//   select    one wave minimum m, then every first-level entry <= m + sel_dt is a candidate (compares + population counts);
-//             the candidates (<= 16, else sel_dt is halved) are compacted into LDS by ballot prefix counts and rank
-//             themselves against each other; ranks 0..7 become the slots.  The slots hold exactly the smallest entries in
-//             time order whatever sel_dt is, so there is no hidden second-best to carry into the validation bound
+// zz_local_spec8_kernel: the 8-event scheme (pdmp_spec8_common.hpp) for the north-star workload, the PLAIN configuration on the 128 x 128
+// lattice: |G1| <= 5 <= 8 lanes, |S| <= 13 <= 16 = two zone members per lane.  What is this kernel's own:
 //   templates slot 0 of the LDS blob area holds the lattice's common template for the whole launch; the (border) events of an
 //             iteration that need another one share two spare slots, a third such event ends the iteration's candidate list
 //   members   lane gl of a group owns zone positions gl and gl + 8; positions >= 8 are always G2-only (k <= 5), so their
 //             records are touched on accept only; all HBM loads of an iteration are one straight-line batch
-//   accept    every lane evaluates the thinning test of every event for the draw offset equal to its lane number; the ballots
-//             are walked on the scalar unit (offset of event r+1 = offset of r + 2 or 1 + k_r), no dependent LDS round trips
-//   LDS       10 136 bytes per chain = 16 chains per CU: the selection scratch, then zone ids + sx/sth, then the patched key
+//   LDS       10 200 bytes per chain = 16 chains per CU: the selection scratch, then zone ids + sx/sth, then the patched key
 //             blocks take turns in one 2816-byte area; pitches and piece order are chosen against bank conflicts
-// Validation and commit rules are unchanged, so the committed sequence is bit-identical to the other kernels and the oracle.
 constexpr uint32_t S8_LU = 0;       // [64] f64 logs of the draw window (the draws themselves stay in a register per lane)
 constexpr uint32_t S8_R = 512;      // 2816 bytes used in turn by: TK/TB (selection), zone ids + sx/sth, the patched key blocks
 constexpr uint32_t S8_SXP = 18;     // doubles per group in sx / sth (16 + 2: eight groups on eight different banks)
@@ -1982,7 +1930,6 @@ constexpr uint32_t S8_SX = S8_R;            // [8][18] f64
 constexpr uint32_t S8_STH = S8_R + 1152;    // [8][18] f64
 constexpr uint32_t S8_Z = S8_R + 2304;      // [8][16] u32 zone ids
 constexpr uint32_t S8_PK = S8_R;            // [8][32] f64 patched key blocks (sx / sth / zone ids are dead by then)
-constexpr uint32_t SEL_CAP = 16;            // candidates ranked per iteration (power of two)
 constexpr uint32_t S8_TK = S8_R;            // [64] f64 candidate keys (selection only; the first SEL_CAP are ranked)
 constexpr uint32_t S8_TB = S8_R + 64 * 8;       // [64] u32 their blocks (the first SEL_CAP are ranked)
 constexpr uint32_t S8_SLT = 3328;   // [8] f64 candidate keys
@@ -1991,7 +1938,6 @@ constexpr uint32_t S8_LBR = 3456;   // [8] f64 bounds
 constexpr uint32_t S8_MR = 3520;    // [8] f64 what each event exposes
 constexpr uint32_t S8_SLB = 3584;   // [8] u32 candidate blocks
 constexpr uint32_t S8_LB = 3616;    // [3][58] u64 blob slots
-constexpr uint32_t S8_NBLK = 512;   // first-level entries: key blocks of 32 (four 64-byte sectors per popped block)
 constexpr uint32_t S8_BK = S8_LB + 3 * 58 * 8;      // [512] f64 block minima
 constexpr uint32_t S8_BI = S8_BK + S8_NBLK * 8;     // [512] u16 their coordinates (d = 16384)
 constexpr uint32_t S8_SELDT = S8_BI + S8_NBLK * 2;  // f64 selection threshold above the minimum
@@ -2005,15 +1951,6 @@ static_assert(S8_TB + 64 * 4 <= S8_Z, "selection scratch must not reach the zone
 static_assert(S8_SLB + 8 * 4 <= S8_LB && (S8_LB % 16) == 0 && (S8_BK % 16) == 0 && (S8_STH % 16) == 0 && (S8_Z % 16) == 0,
               "LDS sub-arrays must stay 16-byte aligned");
 size_t zz_spec8_lds_bytes() { return S8_BYTES; }
-
-__device__ __forceinline__ uint32_t umin3(uint32_t a, uint32_t b, uint32_t c) {
-    const uint32_t ab = (a < b) ? a : b;
-    return (ab < c) ? ab : c;  // v_min3_u32
-}
-template <int CTRL>
-__device__ __forceinline__ uint32_t dpp_u32(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, CTRL, 0xf, 0xf, true);
-}
 
 // FULL: also `adapt` (per-chain bounds c, multiplied by `factor` when a proposal violates its bound, src/fact_samplers.jl:67-70)
 // and a target with a mean (Γμ subtracted from the gradient); the north-star instantiation has neither.
@@ -2084,43 +2021,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     if (lane < (int)W2) {
         reinterpret_cast<ulonglong2*>(LB)[lane] = reinterpret_cast<const ulonglong2*>(P.blob + (size_t)common * WPAD)[lane];
     }
-    for (uint32_t b = lane; b < nblk; b += 64) {
-        const double* kp = keys + (size_t)b * 32;
-        // (the refresh clock's slot, key d, sits inside the last block when d is no multiple of 32: it is no coordinate -- its time lives in t_ref,
-        // and the slot holds +Inf in memory for as long as this launch runs, so that the rescans of its block do not see it either)
-        double mk = (has_refresh && b * 32 == (uint32_t)d) ? PDMP_INF : kp[0];
-        uint32_t mi = 0;
-#pragma unroll 8
-        for (int q = 1; q < 32; ++q) {
-            const double v = (has_refresh && b * 32 + (uint32_t)q == (uint32_t)d) ? PDMP_INF : kp[q];
-            if (v < mk) {
-                mk = v;
-                mi = q;
-            }
-        }
-        bk[b] = mk;
-        bi[b] = (uint16_t)(b * 32 + mi);
-    }
-    for (uint32_t b = nblk + lane; b < S8_NBLK; b += 64) {
-        bk[b] = PDMP_INF;
-        bi[b] = 0;
-    }
+    s8_build_level1<true>(keys, bk, bi, nblk, d, has_refresh, lane);
     PDMP_LDS_ORDER();
     if (has_refresh && lane == 0) __hip_atomic_store(keys + d, PDMP_INF, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 
     uint32_t rng_base = 0xffffffffu;
     double ureg = 0.0;  // draw rng_base + lane of the chain's stream
-    uint64_t ph[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    uint64_t ph_t0 = PROF ? (uint64_t)__builtin_readcyclecounter() : 0;
-    uint64_t ph_iters = 0;
-#define PHASE(k)                                                          \
-    do {                                                                  \
-        if (PROF) {                                                       \
-            const uint64_t now_ = (uint64_t)__builtin_readcyclecounter(); \
-            ph[k] += now_ - ph_t0;                                        \
-            ph_t0 = now_;                                                 \
-        }                                                                 \
-    } while (0)
+    PhaseClock<PROF> phc;
 
     bool running = stop_before || (t_event < T);
     PrioTurn prio;
@@ -2134,96 +2041,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             status = PDMP_CHAIN_PAUSED;
             break;
         }
-        // ---------------- select the (up to) E smallest block minima, in time order, WITHOUT a tournament per candidate: one
-        // wave minimum m, then every first-level entry below the threshold m + sel_dt is a candidate -- four compares and four
-        // population counts tell how many there are.  The candidates (at most SEL_CAP, else the threshold is halved) are compacted
-        // into LDS by ballot prefix counts, each ranks itself against the others with broadcast reads, and ranks 0..E-1 become
-        // the event slots.  Whatever sel_dt is, the slots hold exactly the smallest entries of the queue, so the committed
-        // sequence does not depend on it; it is steered towards ~12 candidates per iteration.
-        int Esel = 0;
-        bool first_inf = false, do_ref = false;
-        {
-            double kk[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) kk[j] = bk[lane + 64 * j];
-            const double mloc = min_f64(min_f64(min_f64(kk[0], kk[1]), min_f64(kk[2], kk[3])),
-                                        min_f64(min_f64(kk[4], kk[5]), min_f64(kk[6], kk[7])));
-            const double mq = wave_min_f64(mloc);
-            do_ref = has_refresh && t_ref < mq && !(stop_before && !(t_ref < T));  // (a coordinate's event at the clock's very time goes first)
-            if (do_ref) {
-            } else if (!(mq < PDMP_INF)) {
-                first_inf = true;
-            } else if (!(stop_before && !(mq < T))) {
-                if (lane < (int)SEL_CAP) TK[lane] = PDMP_INF;
-                double dt_sel = uniform_f64(SELDT[0]);
-                // (the candidate masks are recomputed where they are needed instead of being kept: eight 64-bit masks would
-                // crowd the scalar registers)
-                // Compaction: entry (lane, j) gets index (candidates of slots < j) + (candidates of slot j in lower lanes).  There is
-                // no separate counting pass: the scratch arrays take up to 64 candidates, and a pass that ends with more than
-                // SEL_CAP is repeated with half the threshold.
-                auto below = [](uint64_t m_) -> uint32_t {
-                    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m_ >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m_, 0u));
-                };
-                double tau;
-                uint32_t C;
-                for (int tries = 0;; ++tries) {
-                    tau = mq + dt_sel;  // (>= mq: the minimum itself always qualifies)
-                    if (stop_before && !(tau < T)) tau = pdmp_below(T);
-                    if (!(tau < t_ref)) tau = (t_ref > mq) ? pdmp_below(t_ref) : mq;  // nothing at or beyond the refresh clock's time (but the minimum itself)
-                    const bool pile = tries > 64;  // more than SEL_CAP entries EQUAL to the minimum: one (lowest block) per iteration
-                    if (tries >= 64) tau = mq;     // a pile of exactly equal keys: the entries equal to the minimum only
-                    uint32_t base = 0;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const bool cj_ = kk[j] <= tau;
-                        uint64_t Mj = __ballot(cj_);
-                        if (pile) Mj = (base == 0 && Mj) ? (Mj & (~Mj + 1)) : 0ull;
-                        if (cj_ && ((Mj >> lane) & 1ull)) {
-                            const uint32_t ix = base + below(Mj);
-                            if (ix < 64u) {
-                                TK[ix] = kk[j];
-                                TB[ix] = (uint32_t)lane + 64u * j;
-                            }
-                        }
-                        base += (uint32_t)__popcll(Mj);
-                    }
-                    C = base;
-                    if (C <= SEL_CAP) break;
-                    dt_sel *= 0.5;
-                    PDMP_LDS_ORDER();
-                    if (lane < (int)SEL_CAP) TK[lane] = PDMP_INF;  // (entries past the new count must read +Inf in the ranking)
-                }
-                PDMP_LDS_ORDER();
-                // rank of candidate n among all (ties by index), on a 16 x 4 grid: lane = 16 * part + n counts the candidates
-                // 4 * part .. 4 * part + 3 that precede n; the four partial counts meet in LDS.  Unused entries hold +Inf.
-                {
-                    const uint32_t n = (uint32_t)lane & 15u, part = (uint32_t)lane >> 4;
-                    const double own = TK[n];
-                    const double2* T2 = reinterpret_cast<const double2*>(TK + 4 * part);
-                    const double2 o01 = T2[0], o23 = T2[1];
-                    const uint32_t q = 4 * part;
-                    uint32_t pr = 0;
-                    pr += (o01.x < own || (o01.x == own && q + 0 < n)) ? 1u : 0u;
-                    pr += (o01.y < own || (o01.y == own && q + 1 < n)) ? 1u : 0u;
-                    pr += (o23.x < own || (o23.x == own && q + 2 < n)) ? 1u : 0u;
-                    pr += (o23.y < own || (o23.y == own && q + 3 < n)) ? 1u : 0u;
-                    PR[n * 4 + part] = pr;
-                    PDMP_LDS_ORDER();
-                    if ((uint32_t)lane < C) {
-                        const uint4 p4 = reinterpret_cast<const uint4*>(PR)[lane];
-                        const uint32_t rank = p4.x + p4.y + p4.z + p4.w;
-                        if (rank < (uint32_t)E) {
-                            SLT[rank] = own;
-                            SLB[rank] = TB[lane];
-                        }
-                    }
-                }
-                Esel = (C < (uint32_t)E) ? (int)C : E;
-                // steer the threshold: ~10 candidates next time
-                const double f = (C > 14u) ? 0.8 : (C < 11u) ? ((C < 6u) ? 2.0 : 1.2) : 1.0;
-                if (lane == 0) SELDT[0] = dt_sel * f;
-            }
-        }
+        // ---------------- select the (up to) E smallest block minima in time order
+        int Esel;
+        bool first_inf, do_ref;
+        s8_select<E, true, false>(bk, TK, TB, PR, SLT, SLB, SELDT, lane, stop_before, T, has_refresh, t_ref, Esel, first_inf, do_ref);
         if (do_ref) {
             // ---------------- the refresh clock is the chain's next event: src/sfact.jl:78-114, restated with its quirks exactly as
             // zz_local_run_kernel does (two independent coordinate draws from the global stream -- the neighbourhood that is moved, :80, and the
@@ -2329,27 +2150,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             }
             t_ref = newref;  // (stored into keys[d] when the launch ends)
             for (int jj = 0; jj < k; ++jj) {  // first level: blocks of 32 keys
-                const uint32_t j = readlane_u32(s, jj);
-                const double kjv = readlane_f64(key, jj);
-                const uint32_t bj = j >> 5;
-                PDMP_LDS_ORDER();
-                const double cur = bk[bj];
-                const uint32_t ci = bi[bj];
-                if (kjv < cur || (kjv == cur && j < ci)) {
-                    if (lane == 0) {
-                        bk[bj] = kjv;
-                        bi[bj] = (uint16_t)j;
-                    }
-                } else if (ci == j) {
-                    const double kv = (lane < 32) ? __hip_atomic_load(keys + (size_t)bj * 32 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : PDMP_INF;
-                    const double mn = wave_min_f64(kv);
-                    const uint64_t bl = __ballot(kv == mn);
-                    const int arg = bl ? (__ffsll((unsigned long long)bl) - 1) : 0;
-                    if (lane == 0) {
-                        bk[bj] = mn;
-                        bi[bj] = (uint16_t)(bj * 32 + (uint32_t)arg);
-                    }
-                }
+                s8_level1_update(bk, bi, keys, lane, readlane_u32(s, jj), readlane_f64(key, jj));
                 PDMP_LDS_ORDER();
             }
             const double t_i = readlane_f64(t, self), x_i = readlane_f64(x, self), th_i2 = readlane_f64(th, self);
@@ -2375,8 +2176,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             break;
         }
         PDMP_LDS_ORDER();
-        PHASE(0);
-        if (PROF) ph_iters += 1;
+        phc.mark(0);
+        if (PROF) phc.iters += 1;
         bool gvalid = g < Esel;
         const double tp = gvalid ? SLT[g] : PDMP_INF;
         const uint32_t blk = gvalid ? SLB[g] : 0u;
@@ -2384,38 +2185,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         const uint32_t tixi = gvalid ? P.tix[i] : common;
 
         // ---------------- candidate draws (window of 64 draws and their logs in LDS, as in zz_local_spec_kernel)
-        if (dnm < rng_base || dnm + E * (1u + KMAX) > rng_base + 64u) {
-            rng_base = dnm;
-            ureg = pdmp_u01(seed, PDMP_STREAM_MAIN, nm0 + (uint64_t)dnm + (uint64_t)lane);
-            LU[lane] = pdmp_log(ureg);
-        }
-        const uint32_t rng_off = dnm - rng_base;
+        const uint32_t rng_off = s8_draw_window(E * (1u + KMAX), dnm, seed, nm0, lane, LU, rng_base, ureg);
         // ---------------- blob slots: 0 for the common template, 1 and 2 for the first two events that need another one
-        uint32_t slot = 0;
-        {
-            const bool nc = gvalid && tixi != common;
-            const uint64_t ncball = __ballot(nc && gl == 0);
-            if (ncball != 0) {
-                const uint32_t rank = (uint32_t)__popcll(ncball & ((1ull << (8 * g)) - 1ull));
-                if (__popcll(ncball) > 2) {  // the third such event and everything after it wait for the next iteration
-                    uint64_t m_ = ncball;
-                    m_ &= m_ - 1;
-                    m_ &= m_ - 1;
-                    const int cut = (__ffsll((unsigned long long)m_) - 1) >> 3;
-                    Esel = cut;
-                    gvalid = g < Esel;
-                }
-                if (nc && gvalid) {
-                    slot = 1 + rank;
-                    const ulonglong2* bsrc = reinterpret_cast<const ulonglong2*>(P.blob + (size_t)tixi * WPAD);
-                    ulonglong2* bdst = reinterpret_cast<ulonglong2*>(LB + slot * WPAD);
-                    for (uint32_t w = gl; w < W2; w += 8) bdst[w] = bsrc[w];
-                }
-            }
-        }
-        const uint64_t* lb = LB + slot * WPAD;
+        const uint64_t* lb = LB + s8_blob_slot<WPAD>(P.blob, LB, tixi, common, g, gl, Esel, gvalid) * WPAD;
         PDMP_LDS_ORDER();
-        PHASE(1);
+        phc.mark(1);
         // ---------------- neighbourhood header and member list: positions gl and gl + 8 of S[i]
         // (straight-line: every lane reads its slot's words, the selects below sort out who is a member)
         const uint32_t hw = gvalid ? (uint32_t)lb[0] : 0u;
@@ -2424,7 +2198,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         const uint64_t swa = lb[1 + (gl >> 1)], swb = lb[5 + (gl >> 1)];
         const uint32_t sA = memberA ? i + ((gl & 1) ? (uint32_t)(swa >> 32) : (uint32_t)swa) : 0xffffff00u + (uint32_t)lane;
         const uint32_t sB = memberB ? i + ((gl & 1) ? (uint32_t)(swb >> 32) : (uint32_t)swb) : 0xffffff40u + (uint32_t)lane;
-        PHASE(2);
+        phc.mark(2);
         // All HBM loads of the iteration in ONE straight-line batch (no exec-masked regions: lanes without a record of their own
         // read i's, which coalesces with the group's other readers of it; empty slots read coordinate 0): the wait counters
         // stay exact and nothing here is serialised behind an earlier round trip.
@@ -2453,41 +2227,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         // ---------------- zone conflicts with earlier groups: id spans first, the exact id comparison only for pairs of groups
         // whose spans overlap
         PDMP_LDS_ORDER();
-        uint64_t confball;
-        {
-            uint32_t lo = memberA ? sA : 0xffffffffu, hi = memberA ? sA : 0u;
-            lo = (memberB && sB < lo) ? sB : lo;
-            hi = (memberB && sB > hi) ? sB : hi;
-            uint32_t o;
-            o = dpp_u32<0xB1>(lo);   lo = (o < lo) ? o : lo;
-            o = dpp_u32<0x4E>(lo);   lo = (o < lo) ? o : lo;
-            o = dpp_u32<0x141>(lo);  lo = (o < lo) ? o : lo;
-            o = dpp_u32<0xB1>(hi);   hi = (o > hi) ? o : hi;
-            o = dpp_u32<0x4E>(hi);   hi = (o > hi) ? o : hi;
-            o = dpp_u32<0x141>(hi);  hi = (o > hi) ? o : hi;
-            // A pair of groups (q < g) whose spans overlap is compared exactly by the WHOLE wave: lane L holds id L & 15 of g
-            // against ids 4 (L >> 4) .. + 3 of q -- the 256 id pairs in four xor / two min instructions per lane.  Empty
-            // positions hold sentinels that equal nothing.
-            uint32_t confmask = 0;
-            const uint4* Z4 = reinterpret_cast<const uint4*>(Z);
-            // lane gl of group g looks at the pair (g, q = gl): one ballot finds all pairs of groups whose spans overlap
-            {
-                const uint32_t lq = (uint32_t)__builtin_amdgcn_ds_bpermute(32 * gl, (int)lo);  // span of group gl (its lane 0)
-                const uint32_t hq = (uint32_t)__builtin_amdgcn_ds_bpermute(32 * gl, (int)hi);
-                uint64_t ovb = __ballot(gvalid && gl < g && lo <= hq && lq <= hi);
-                while (ovb != 0) {
-                    const int bit = __ffsll((unsigned long long)ovb) - 1;
-                    const int gsel = bit >> 3, q = bit & 7;
-                    ovb &= ovb - 1;
-                    const uint32_t idg = Z[gsel * 16 + (lane & 15)];
-                    const uint4 zq = Z4[q * 4 + (lane >> 4)];
-                    const uint32_t mn = umin3(idg ^ zq.x, idg ^ zq.y, umin3(idg ^ zq.z, idg ^ zq.w, 0xffffffffu));
-                    if (__ballot(mn == 0u) != 0) confmask |= 1u << gsel;
-                }
-            }
-            confball = confmask;
-        }
-        PHASE(3);
+        const uint64_t confball = s8_zone_conflicts(Z, memberA, sA, memberB, sB, gvalid, lane, g, gl);
+        phc.mark(3);
 
         // ---------------- smove_forward!(G, i, ...), gradient, rates
         // (every lane runs the move: lanes that hold no G1 member carry i's record and are re-loaded before they matter)
@@ -2518,30 +2259,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             }
         }
         PDMP_LDS_ORDER();
-        // ---------------- accept chain in time order.  Lane o evaluates every event's test for the draw at offset o; the ballots
-        // are then walked on the scalar unit: event r reads its bit at the offset the earlier outcomes imply.
-        // The offsets (each <= 48) travel packed six bits apiece in one 64-bit scalar: offset after r events = bits 6r .. 6r+5.
-        uint32_t accbits = 0;
-        uint64_t offpack = 0;
-        {
-            const double coin = bperm_f64(ureg, (rng_off + (uint32_t)lane) & 63u);
-            uint32_t off = 0;
-#pragma unroll
-            for (int r = 0; r < E; ++r) {  // slots >= Esel hold stale rates: their bits are masked off below, their offsets unused
-                const uint64_t am_r = __ballot(coin * LBr[r] < Lr[r]);  // :121
-                const uint32_t a_r = (uint32_t)(am_r >> off) & 1u;
-                const uint32_t k_r = readlane_u32((uint32_t)k, 8 * r);
-                off += a_r ? (1u + k_r) : 2u;
-                off = (off < 63u) ? off : 63u;  // (only stale slots can run past the window; keeps the shifts defined)
-                accbits |= a_r << r;
-                offpack |= (uint64_t)off << (6 * (r + 1));
-            }
-            accbits &= (1u << Esel) - 1u;
-        }
+        // ---------------- accept chain in time order: the draw at offset o of the iteration is lane o's coin
+        uint32_t accbits;
+        uint64_t offpack;
+        s8_accept_walk<E, 8, false>(bperm_f64(ureg, (rng_off + (uint32_t)lane) & 63u), LBr, Lr, k, Esel, accbits, offpack);
         const uint32_t myoff = (uint32_t)(offpack >> (6 * g)) & 63u;
         const bool accept = gvalid && ((accbits >> g) & 1u) != 0;
         const bool violated = accept && (l >= lbound);  // :123
-        PHASE(4);
+        phc.mark(4);
 
         double x2 = 0.0, th2 = 0.0, t2 = 0.0, I2 = 0.0;
         if (accept) {
@@ -2600,101 +2325,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             key = t + poisson_time_L(a, b, L);
         }
         PDMP_LDS_ORDER();
-        // the patched copy of the popped key block goes where sx / sth / the zone ids were: all their readers are done
-        // (the four 16-byte pieces of a lane's 64-byte chunk are stored in the order piece ^ pk_t, pk_t = 0..3 over the four lanes
-        // of a quarter wave that would otherwise share their banks: b128 accesses without bank conflicts)
-        {
-            double2* pk2 = reinterpret_cast<double2*>(pk + gl * 4);
-            pk2[0 ^ pk_t] = make_double2(kq[0], kq[1]);
-            pk2[1 ^ pk_t] = make_double2(kq[2], kq[3]);
-        }
-        PDMP_LDS_ORDER();
-        if (active && (sA >> 5) == blk) {
-            const uint32_t e_ = sA & 31u;
-            pk[(e_ & ~3u) + ((((e_ & 3u) >> 1) ^ pk_t) << 1) + (e_ & 1u)] = key;
-        }
-        PDMP_LDS_ORDER();
-        PHASE(5);
+        // the patched copy of the popped key block goes where the zone ids (and sx / sth) were: all their readers are done
+        s8_patch_block<4>(pk, pk_t, gl, kq, active && (sA >> 5) == blk, sA, key);
+        phc.mark(5);
         // ---------------- patched minimum of the popped block, and everything this event could expose
         double rowmin;
         uint32_t cand;
         int wl2;
-        {
-            const double2* pk2 = reinterpret_cast<const double2*>(pk + gl * 4);
-            const double2 p01 = pk2[0 ^ pk_t], p23 = pk2[1 ^ pk_t];
-            double lm = p01.x;
-            uint32_t li = 0;
-#define PMIN(v, idx)    \
-    do {                \
-        if ((v) < lm) { \
-            lm = (v);   \
-            li = (idx); \
-        }               \
-    } while (0)
-            PMIN(p01.y, 1);
-            PMIN(p23.x, 2);
-            PMIN(p23.y, 3);
-#undef PMIN
-            cand = blk * 32u + (uint32_t)gl * 4u + li;
-            rowmin = grp8_min_f64(lm);
-            const uint64_t winball = __ballot(gvalid && lm == rowmin);
-            wl2 = __ffs((unsigned)((winball >> (8 * g)) & 0xffu)) - 1;
-        }
-        const double keymin = grp8_min_f64(key);
-        const double expose = min_f64(rowmin, keymin);
-        if (gl == 0) Mr[g] = expose;
-        PDMP_LDS_ORDER();
-        // ---------------- validate: event g commits iff all earlier ones do, its zone is disjoint from theirs, and nothing they
-        // produce or expose comes before it
-        uint32_t Rc;
-        uint32_t nacc_c;
-        int vsel = -1;  // the event that violates its bound, if it is the chain's next one
-        {
-            double pref = PDMP_INF;
-#pragma unroll
-            for (int q = 0; q < E - 1; ++q) {
-                const double mq = Mr[q];
-                pref = (q < g) ? min_f64(pref, mq) : pref;
-            }
-            const bool confg = ((confball >> g) & 1ull) != 0;
-            const bool okg = gvalid && ((g == 0) || (!confg && pref > tp));
-            const bool vstop = violated && !adapt;  // reference: error(...), :124 -> the event is not committed
-            const uint64_t okball = __ballot(okg && !vstop && gl == 0);
-            const uint64_t vball = __ballot(okg && vstop && gl == 0);
-            const uint64_t accball = __ballot(accept && gl == 0);
-            // length of the run of committable slots from slot 0 (one bit per slot at bit 8 r): first zero among those bits
-            const uint64_t gap = ~okball & 0x0101010101010101ull;
-            const uint32_t r_ok = gap ? (uint32_t)((__ffsll((unsigned long long)gap) - 1) >> 3) : (uint32_t)E;
-            Rc = 0;
-            nacc_c = 0;
-            bool stopped = false;
-            // the usual case needs no walk: the slice mode stops on time alone, and the trace has room for every accepted slot
-            const uint32_t nacc_all = (uint32_t)__popcll(accball & ((r_ok < 8u) ? ((1ull << (8 * r_ok)) - 1ull) : ~0ull));
-            const bool plainrun = stop_before && !(P.trace_cap > 0 && dnacc + dnref + nacc_all >= trace_room);
-            if (plainrun) {
-                Rc = r_ok;
-                nacc_c = nacc_all;
-            }
-            for (uint32_t r = 0; !plainrun && r < r_ok && !stopped; ++r) {
-                Rc = r + 1;
-                if ((accball >> (8 * r)) & 1ull) {
-                    nacc_c += 1;
-                    if (dnacc + dnref + nacc_c >= trace_room && P.trace_cap > 0) {
-                        status = PDMP_CHAIN_TRACE_FULL;
-                        stopped = true;
-                    }
-                    if (!stop_before && !(uniform_f64(SLT[r]) < T)) {
-                        running = false;
-                        stopped = true;
-                    }
-                }
-            }
-            if (!stopped && r_ok < (uint32_t)E && ((vball >> (8 * r_ok)) & 1ull)) {
-                status = PDMP_CHAIN_BOUND_VIOLATED;
-                vsel = (int)r_ok;
-            }
-        }
-        PHASE(6);
+        s8_patched_min<8>(pk, pk_t, blk, gvalid, key, g, gl, Mr, rowmin, cand, wl2);
+        // ---------------- validate: the committable prefix Rc, its accepted events, the event that violates its bound if it is the next one
+        uint32_t Rc, nacc_c;
+        int vsel;
+        s8_validate<E, 8>(Mr, SLT, confball, gvalid, accept, violated, adapt, tp, g, gl, stop_before, T, P.trace_cap > 0, dnacc + dnref, trace_room, Rc,
+                          nacc_c, vsel, status, running);
+        phc.mark(6);
 
         // ---------------- commit the valid prefix
         const bool commit = gvalid && (uint32_t)g < Rc;
@@ -2735,105 +2379,24 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             }
         }
         PDMP_LDS_ORDER();
-        PHASE(7);
-        // ---------------- level-1 updates for re-bounded neighbours living in other blocks.  The final entry of a block is the
-        // smallest (key, coordinate) among its old entry and the new keys, whatever the order -- so when no two of these lanes aim
-        // at one block (checked through a small claim table) and none has to rescan, every lane updates its block by itself, in
-        // one LDS round trip for all of them; otherwise the updates are made one by one in event order.
-        const bool upd = commit && accept && gl < k && (sA >> 5) != blk;
-        if (__ballot(upd) != 0) {
-            uint8_t* const CL = reinterpret_cast<uint8_t*>(smem + S8_CL);
-            PDMP_LDS_ORDER();
-            const uint32_t bjv = upd ? (sA >> 5) : 0u;
-            const double curv = bk[bjv];
-            const uint32_t civ = bi[bjv];
-            const bool lower = upd && (key < curv || (key == curv && sA < civ));
-            const bool resc = upd && !lower && civ == sA;
-            if (lower) CL[bjv & 63u] = (uint8_t)lane;
-            PDMP_LDS_ORDER();
-            const bool lost = lower && CL[bjv & 63u] != (uint8_t)lane;
-            if (__ballot(lost || resc) == 0) {
-                if (lower) {
-                    bk[bjv] = key;
-                    bi[bjv] = (uint16_t)sA;
-                }
-            } else {
-            for (uint32_t r = 0; r < Rc; ++r) {
-                if (!((accball2 >> (8 * r)) & 1ull)) continue;
-                const uint32_t own = uniform_u32(SLB[r]);
-                const int kr = (int)readlane_u32((uint32_t)k, 8 * (int)r);
-                for (int jj = 0; jj < kr; ++jj) {
-                    const uint32_t j = readlane_u32(sA, 8 * (int)r + jj);
-                    if ((j >> 5) == own) continue;
-                    // first-level entry of j's 32-key block: a lower key replaces it; if j WAS the entry and grew, the block is rescanned
-                    const double kj = readlane_f64(key, 8 * (int)r + jj);
-                    const uint32_t bj = j >> 5;
-                    PDMP_LDS_ORDER();
-                    const double cur = bk[bj];
-                    const uint32_t ci = bi[bj];
-                    if (kj < cur || (kj == cur && j < ci)) {
-                        if (lane == 0) {
-                            bk[bj] = kj;
-                            bi[bj] = (uint16_t)j;
-                        }
-                    } else if (ci == j) {
-                        const double kv = __hip_atomic_load(keys + (size_t)bj * 32 + (lane & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        const double mn = wave_min_f64(kv);
-                        const uint64_t bl = __ballot(kv == mn);
-                        const int arg = bl ? (__ffsll((unsigned long long)bl) - 1) : 0;
-                        if (lane == 0) {
-                            bk[bj] = mn;
-                            bi[bj] = (uint16_t)(bj * 32 + (uint32_t)arg);
-                        }
-                    }
-                }
-            }
-            }
+        phc.mark(7);
+        // ---------------- level-1 updates for re-bounded neighbours living in other blocks
+        s8_level1_commit<8>(bk, bi, reinterpret_cast<uint8_t*>(smem + S8_CL), keys, SLB, commit && accept && gl < k && (sA >> 5) != blk, sA, key, k, Rc,
+                            accball2, lane);
+        phc.mark(8);
+        // ---------------- the violating proposal itself (reference: counted, G[i] moved, acc bumped -- then error(...), :120-124), counters
+        if (vsel >= 0 && g == vsel && gl < k) {
+            rsA->x = x;
+            rsA->t = t;
+            rsA->I = I;
         }
-        PHASE(8);
-        // ---------------- the violating proposal itself (reference: counted, G[i] moved, acc bumped -- then error(...), :120-124):
-        // what zz_local_run_kernel and the oracle leave behind
-        if (vsel >= 0) {
-            if (g == vsel && gl < k) {
-                rsA->x = x;
-                rsA->t = t;
-                rsA->I = I;
-            }
-            dnum += 1;
-            vnacc = 1;
-            dnm += ((uint32_t)(offpack >> (6 * vsel)) & 63u) + 1u - ((uint32_t)(offpack >> (6 * Rc)) & 63u);
-        }
-        // ---------------- counters
-        if (Rc > 0) {
-            dnum += Rc;
-            dnacc += nacc_c;
-            dnm += (uint32_t)(offpack >> (6 * Rc)) & 63u;
-            t_last = uniform_f64(SLT[Rc - 1]);
-            if (accball2) t_event = uniform_f64(SLT[(63 - __builtin_clzll(accball2)) >> 3]);
-        }
-        if (vsel >= 0) t_last = uniform_f64(SLT[vsel]);  // the violating event's time is the chain's current time
+        s8_count<8>(vsel, Rc, nacc_c, offpack, accball2, SLT, dnum, dnacc, dnm, vnacc, t_last, t_event);
         if (status != PDMP_CHAIN_OK) break;
         PDMP_LDS_ORDER();
     }
 
-    if (PROF && P.dbg && chain == 0 && lane == 0) {
-        for (int q = 0; q < 10; ++q) P.dbg[q] = (double)ph[q];
-        P.dbg[10] = (double)ph_iters;
-    }
-#undef PHASE
-    if (lane == 0) {
-        hdr->c.t_last = t_last;
-        hdr->t_event = t_event;
-        hdr->c.num += dnum;
-        hdr->c.nacc += dnacc + vnacc;
-        hdr->c.ntrace = ntrace0 + dnacc + dnref;
-        hdr->c.nevents += dnacc + dnref;
-        hdr->c.nrefresh += dnref;
-        hdr->c.ndraw_global = ng;
-        if (has_refresh) keys[d] = t_ref;
-        hdr->c.ndraw_main = nm0 + dnm;
-        hdr->c.status = status;
-    }
+    if (PROF && P.dbg && chain == 0 && lane == 0) phc.store(P.dbg);
+    if (lane == 0) s8_store_header<true>(hdr, keys, d, t_last, t_event, dnum, dnacc, vnacc, ntrace0, nm0, dnm, status, has_refresh, t_ref, dnref, ng);
 }
 
 #include "pdmp_spec8g.inc"
@@ -2916,40 +2479,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     if (lane < (int)W2) {
         reinterpret_cast<ulonglong2*>(LB)[lane] = reinterpret_cast<const ulonglong2*>(P.blob + (size_t)common * WPAD)[lane];
     }
-    for (uint32_t b = lane; b < nblk; b += 64) {
-        const double* kp = keys + (size_t)b * 32;
-        double mk = kp[0];
-        uint32_t mi = 0;
-#pragma unroll 8
-        for (int q = 1; q < 32; ++q) {
-            const double v = kp[q];
-            if (v < mk) {
-                mk = v;
-                mi = q;
-            }
-        }
-        bk[b] = mk;
-        bi[b] = (uint16_t)(b * 32 + mi);
-    }
-    for (uint32_t b = nblk + lane; b < S8_NBLK; b += 64) {
-        bk[b] = PDMP_INF;
-        bi[b] = 0;
-    }
+    s8_build_level1<false>(keys, bk, bi, nblk, d, false, lane);
     PDMP_LDS_ORDER();
 
     uint32_t rng_base = 0xffffffffu;
     double ureg = 0.0;  // draw rng_base + lane of the chain's stream
-    uint64_t ph[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    uint64_t ph_t0 = PROF ? (uint64_t)__builtin_readcyclecounter() : 0;
-    uint64_t ph_iters = 0;
-#define PHASE(k)                                                          \
-    do {                                                                  \
-        if (PROF) {                                                       \
-            const uint64_t now_ = (uint64_t)__builtin_readcyclecounter(); \
-            ph[k] += now_ - ph_t0;                                        \
-            ph_t0 = now_;                                                 \
-        }                                                                 \
-    } while (0)
+    PhaseClock<PROF> phc;
 
     bool running = stop_before || (t_event < T);
     PrioTurn prio;
@@ -2963,100 +2498,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             status = PDMP_CHAIN_PAUSED;
             break;
         }
-        // ---------------- select the (up to) E smallest block minima, in time order, WITHOUT a tournament per candidate: one
-        // wave minimum m, then every first-level entry below the threshold m + sel_dt is a candidate -- four compares and four
-        // population counts tell how many there are.  The candidates (at most SEL_CAP, else the threshold is halved) are compacted
-        // into LDS by ballot prefix counts, each ranks itself against the others with broadcast reads, and ranks 0..E-1 become
-        // the event slots.  Whatever sel_dt is, the slots hold exactly the smallest entries of the queue, so the committed
-        // sequence does not depend on it; it is steered towards ~12 candidates per iteration.
-        int Esel = 0;
-        bool first_inf = false;
-        {
-            double kk[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) kk[j] = bk[lane + 64 * j];
-            const double mloc = min_f64(min_f64(min_f64(kk[0], kk[1]), min_f64(kk[2], kk[3])),
-                                        min_f64(min_f64(kk[4], kk[5]), min_f64(kk[6], kk[7])));
-            const double mq = wave_min_f64(mloc);
-            if (!(mq < PDMP_INF)) {
-                first_inf = true;
-            } else if (!(stop_before && !(mq < T))) {
-                if (lane < (int)SEL_CAP) TK[lane] = PDMP_INF;
-                double dt_sel = uniform_f64(SELDT[0]);
-                // (the candidate masks are recomputed where they are needed instead of being kept: eight 64-bit masks would
-                // crowd the scalar registers)
-                // Compaction: entry (lane, j) gets index (candidates of slots < j) + (candidates of slot j in lower lanes).  There is
-                // no separate counting pass: the scratch arrays take up to 64 candidates, and a pass that ends with more than
-                // SEL_CAP is repeated with half the threshold.
-                auto below = [](uint64_t m_) -> uint32_t {
-                    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m_ >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m_, 0u));
-                };
-                double tau;
-                uint32_t C;
-                for (int tries = 0;; ++tries) {
-                    tau = mq + dt_sel;  // (>= mq: the minimum itself always qualifies)
-                    if (stop_before && !(tau < T)) tau = pdmp_below(T);
-                    const bool pile = tries > 64;  // more than SEL_CAP entries EQUAL to the minimum: one (lowest block) per iteration
-                    if (tries >= 64) tau = mq;     // a pile of exactly equal keys: the entries equal to the minimum only
-                    uint32_t base = 0;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const bool cj_ = kk[j] <= tau;
-                        uint64_t Mj = __ballot(cj_);
-                        if (pile) Mj = (base == 0 && Mj) ? (Mj & (~Mj + 1)) : 0ull;
-                        if (cj_ && ((Mj >> lane) & 1ull)) {
-                            const uint32_t ix = base + below(Mj);
-                            if (ix < 64u) {
-                                TK[ix] = kk[j];
-                                TB[ix] = (uint32_t)lane + 64u * j;
-                            }
-                        }
-                        base += (uint32_t)__popcll(Mj);
-                    }
-                    C = base;
-                    if (C <= SEL_CAP) break;
-                    dt_sel *= 0.5;
-                    PDMP_LDS_ORDER();
-                    if (lane < (int)SEL_CAP) TK[lane] = PDMP_INF;  // (entries past the new count must read +Inf in the ranking)
-                }
-                PDMP_LDS_ORDER();
-                // rank of candidate n among all (ties by index), on a 16 x 4 grid: lane = 16 * part + n counts the candidates
-                // 4 * part .. 4 * part + 3 that precede n; the four partial counts meet in LDS.  Unused entries hold +Inf.
-                {
-                    const uint32_t n = (uint32_t)lane & 15u, part = (uint32_t)lane >> 4;
-                    const double own = TK[n];
-                    const double2* T2 = reinterpret_cast<const double2*>(TK + 4 * part);
-                    const double2 o01 = T2[0], o23 = T2[1];
-                    const uint32_t q = 4 * part;
-                    uint32_t pr = 0;
-                    pr += (o01.x < own || (o01.x == own && q + 0 < n)) ? 1u : 0u;
-                    pr += (o01.y < own || (o01.y == own && q + 1 < n)) ? 1u : 0u;
-                    pr += (o23.x < own || (o23.x == own && q + 2 < n)) ? 1u : 0u;
-                    pr += (o23.y < own || (o23.y == own && q + 3 < n)) ? 1u : 0u;
-                    PR[n * 4 + part] = pr;
-                    PDMP_LDS_ORDER();
-                    if ((uint32_t)lane < C) {
-                        const uint4 p4 = reinterpret_cast<const uint4*>(PR)[lane];
-                        const uint32_t rank = p4.x + p4.y + p4.z + p4.w;
-                        if (rank < (uint32_t)E) {
-                            SLT[rank] = own;
-                            SLB[rank] = TB[lane];
-                        }
-                    }
-                }
-                Esel = (C < (uint32_t)E) ? (int)C : E;
-                // steer the threshold: ~10 candidates next time
-                const double f = (C > 14u) ? 0.8 : (C < 11u) ? ((C < 6u) ? 2.0 : 1.2) : 1.0;
-                if (lane == 0) SELDT[0] = dt_sel * f;
-            }
-        }
+        // ---------------- select the (up to) E smallest block minima in time order
+        int Esel;
+        bool first_inf, do_ref;
+        s8_select<E, false, false>(bk, TK, TB, PR, SLT, SLB, SELDT, lane, stop_before, T, false, PDMP_INF, Esel, first_inf, do_ref);
+        (void)do_ref;
         if (Esel == 0) {
             if (first_inf) status = PDMP_CHAIN_STALLED;
             break;
         }
         PDMP_LDS_ORDER();
-        PHASE(0);
-        if (PROF) ph_iters += 1;
+        phc.mark(0);
+        if (PROF) phc.iters += 1;
         bool gvalid = g < Esel;
         const double tp = gvalid ? SLT[g] : PDMP_INF;
         const uint32_t blk = gvalid ? SLB[g] : 0u;
@@ -3064,38 +2517,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         const uint32_t tixi = gvalid ? P.tix[i] : common;
 
         // ---------------- candidate draws (window of 64 draws and their logs in LDS, as in zz_local_spec_kernel)
-        if (dnm < rng_base || dnm + E * (1u + KMAX) > rng_base + 64u) {
-            rng_base = dnm;
-            ureg = pdmp_u01(seed, PDMP_STREAM_MAIN, nm0 + (uint64_t)dnm + (uint64_t)lane);
-            LU[lane] = pdmp_log(ureg);
-        }
-        const uint32_t rng_off = dnm - rng_base;
+        const uint32_t rng_off = s8_draw_window(E * (1u + KMAX), dnm, seed, nm0, lane, LU, rng_base, ureg);
         // ---------------- blob slots: 0 for the common template, 1 and 2 for the first two events that need another one
-        uint32_t slot = 0;
-        {
-            const bool nc = gvalid && tixi != common;
-            const uint64_t ncball = __ballot(nc && gl == 0);
-            if (ncball != 0) {
-                const uint32_t rank = (uint32_t)__popcll(ncball & ((1ull << (8 * g)) - 1ull));
-                if (__popcll(ncball) > 2) {  // the third such event and everything after it wait for the next iteration
-                    uint64_t m_ = ncball;
-                    m_ &= m_ - 1;
-                    m_ &= m_ - 1;
-                    const int cut = (__ffsll((unsigned long long)m_) - 1) >> 3;
-                    Esel = cut;
-                    gvalid = g < Esel;
-                }
-                if (nc && gvalid) {
-                    slot = 1 + rank;
-                    const ulonglong2* bsrc = reinterpret_cast<const ulonglong2*>(P.blob + (size_t)tixi * WPAD);
-                    ulonglong2* bdst = reinterpret_cast<ulonglong2*>(LB + slot * WPAD);
-                    for (uint32_t w = gl; w < W2; w += 8) bdst[w] = bsrc[w];
-                }
-            }
-        }
-        const uint64_t* lb = LB + slot * WPAD;
+        const uint64_t* lb = LB + s8_blob_slot<WPAD>(P.blob, LB, tixi, common, g, gl, Esel, gvalid) * WPAD;
         PDMP_LDS_ORDER();
-        PHASE(1);
+        phc.mark(1);
         // ---------------- neighbourhood header and member list: positions gl and gl + 8 of S[i]
         // (straight-line: every lane reads its slot's words, the selects below sort out who is a member)
         const uint32_t hw = gvalid ? (uint32_t)lb[0] : 0u;
@@ -3106,7 +2532,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         const uint32_t sA = memberA ? i + ((gl & 1) ? (uint32_t)(swa >> 32) : (uint32_t)swa) : 0xffffff00u + (uint32_t)lane;
         const uint32_t sB = 0xffffff40u + (uint32_t)lane;
         constexpr bool memberB = false;
-        PHASE(2);
+        phc.mark(2);
         // All HBM loads of the iteration in ONE straight-line batch (no exec-masked regions: lanes without a record of their own
         // read i's, which coalesces with the group's other readers of it; empty slots read coordinate 0): the wait counters
         // stay exact and nothing here is serialised behind an earlier round trip.
@@ -3140,41 +2566,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         // ---------------- zone conflicts with earlier groups: id spans first, the exact id comparison only for pairs of groups
         // whose spans overlap
         PDMP_LDS_ORDER();
-        uint64_t confball;
-        {
-            uint32_t lo = memberA ? sA : 0xffffffffu, hi = memberA ? sA : 0u;
-            lo = (memberB && sB < lo) ? sB : lo;
-            hi = (memberB && sB > hi) ? sB : hi;
-            uint32_t o;
-            o = dpp_u32<0xB1>(lo);   lo = (o < lo) ? o : lo;
-            o = dpp_u32<0x4E>(lo);   lo = (o < lo) ? o : lo;
-            o = dpp_u32<0x141>(lo);  lo = (o < lo) ? o : lo;
-            o = dpp_u32<0xB1>(hi);   hi = (o > hi) ? o : hi;
-            o = dpp_u32<0x4E>(hi);   hi = (o > hi) ? o : hi;
-            o = dpp_u32<0x141>(hi);  hi = (o > hi) ? o : hi;
-            // A pair of groups (q < g) whose spans overlap is compared exactly by the WHOLE wave: lane L holds id L & 15 of g
-            // against ids 4 (L >> 4) .. + 3 of q -- the 256 id pairs in four xor / two min instructions per lane.  Empty
-            // positions hold sentinels that equal nothing.
-            uint32_t confmask = 0;
-            const uint4* Z4 = reinterpret_cast<const uint4*>(Z);
-            // lane gl of group g looks at the pair (g, q = gl): one ballot finds all pairs of groups whose spans overlap
-            {
-                const uint32_t lq = (uint32_t)__builtin_amdgcn_ds_bpermute(32 * gl, (int)lo);  // span of group gl (its lane 0)
-                const uint32_t hq = (uint32_t)__builtin_amdgcn_ds_bpermute(32 * gl, (int)hi);
-                uint64_t ovb = __ballot(gvalid && gl < g && lo <= hq && lq <= hi);
-                while (ovb != 0) {
-                    const int bit = __ffsll((unsigned long long)ovb) - 1;
-                    const int gsel = bit >> 3, q = bit & 7;
-                    ovb &= ovb - 1;
-                    const uint32_t idg = Z[gsel * 16 + (lane & 15)];
-                    const uint4 zq = Z4[q * 4 + (lane >> 4)];
-                    const uint32_t mn = umin3(idg ^ zq.x, idg ^ zq.y, umin3(idg ^ zq.z, idg ^ zq.w, 0xffffffffu));
-                    if (__ballot(mn == 0u) != 0) confmask |= 1u << gsel;
-                }
-            }
-            confball = confmask;
-        }
-        PHASE(3);
+        const uint64_t confball = s8_zone_conflicts(Z, memberA, sA, memberB, sB, gvalid, lane, g, gl);
+        phc.mark(3);
 
         // ---------------- rates: the tracked sums stand in for smove_forward!(G, i, ...) + idot (src/sfact.jl:82,116-119): g_i(t′) = g_i + gd_i (t′ − tg_i)
         double l, lbound;
@@ -3191,30 +2584,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             }
         }
         PDMP_LDS_ORDER();
-        // ---------------- accept chain in time order.  Lane o evaluates every event's test for the draw at offset o; the ballots
-        // are then walked on the scalar unit: event r reads its bit at the offset the earlier outcomes imply.
-        // The offsets (each <= 48) travel packed six bits apiece in one 64-bit scalar: offset after r events = bits 6r .. 6r+5.
-        uint32_t accbits = 0;
-        uint64_t offpack = 0;
-        {
-            const double coin = bperm_f64(ureg, (rng_off + (uint32_t)lane) & 63u);
-            uint32_t off = 0;
-#pragma unroll
-            for (int r = 0; r < E; ++r) {  // slots >= Esel hold stale rates: their bits are masked off below, their offsets unused
-                const uint64_t am_r = __ballot(coin * LBr[r] < Lr[r]);  // :121
-                const uint32_t a_r = (uint32_t)(am_r >> off) & 1u;
-                const uint32_t k_r = readlane_u32((uint32_t)k, 8 * r);
-                off += a_r ? (1u + k_r) : 2u;
-                off = (off < 63u) ? off : 63u;  // (only stale slots can run past the window; keeps the shifts defined)
-                accbits |= a_r << r;
-                offpack |= (uint64_t)off << (6 * (r + 1));
-            }
-            accbits &= (1u << Esel) - 1u;
-        }
+        // ---------------- accept chain in time order: the draw at offset o of the iteration is lane o's coin
+        uint32_t accbits;
+        uint64_t offpack;
+        s8_accept_walk<E, 8, false>(bperm_f64(ureg, (rng_off + (uint32_t)lane) & 63u), LBr, Lr, k, Esel, accbits, offpack);
         const uint32_t myoff = (uint32_t)(offpack >> (6 * g)) & 63u;
         const bool accept = gvalid && ((accbits >> g) & 1u) != 0;
         const bool violated = accept && (l >= lbound);  // :123
-        PHASE(4);
+        phc.mark(4);
 
         // ---------------- accept: reflect!(i) (:130) changes θ_i by δ; every j in G1[i] brings its sums to t′, takes Γ[i,j] δ into its
         // velocity sum and is re-bounded (:131-135); reject: i is re-bounded from its own sums (:137-140)
@@ -3274,101 +2651,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             key = tp + poisson_time_L(a, b, L);
         }
         PDMP_LDS_ORDER();
-        // the patched copy of the popped key block goes where the zone ids were: all their readers are done
-        // (the four 16-byte pieces of a lane's 64-byte chunk are stored in the order piece ^ pk_t, pk_t = 0..3 over the four lanes
-        // of a quarter wave that would otherwise share their banks: b128 accesses without bank conflicts)
-        {
-            double2* pk2 = reinterpret_cast<double2*>(pk + gl * 4);
-            pk2[0 ^ pk_t] = make_double2(kq[0], kq[1]);
-            pk2[1 ^ pk_t] = make_double2(kq[2], kq[3]);
-        }
-        PDMP_LDS_ORDER();
-        if (active && (sA >> 5) == blk) {
-            const uint32_t e_ = sA & 31u;
-            pk[(e_ & ~3u) + ((((e_ & 3u) >> 1) ^ pk_t) << 1) + (e_ & 1u)] = key;
-        }
-        PDMP_LDS_ORDER();
-        PHASE(5);
+        // the patched copy of the popped key block goes where the zone ids (and sx / sth) were: all their readers are done
+        s8_patch_block<4>(pk, pk_t, gl, kq, active && (sA >> 5) == blk, sA, key);
+        phc.mark(5);
         // ---------------- patched minimum of the popped block, and everything this event could expose
         double rowmin;
         uint32_t cand;
         int wl2;
-        {
-            const double2* pk2 = reinterpret_cast<const double2*>(pk + gl * 4);
-            const double2 p01 = pk2[0 ^ pk_t], p23 = pk2[1 ^ pk_t];
-            double lm = p01.x;
-            uint32_t li = 0;
-#define PMIN(v, idx)    \
-    do {                \
-        if ((v) < lm) { \
-            lm = (v);   \
-            li = (idx); \
-        }               \
-    } while (0)
-            PMIN(p01.y, 1);
-            PMIN(p23.x, 2);
-            PMIN(p23.y, 3);
-#undef PMIN
-            cand = blk * 32u + (uint32_t)gl * 4u + li;
-            rowmin = grp8_min_f64(lm);
-            const uint64_t winball = __ballot(gvalid && lm == rowmin);
-            wl2 = __ffs((unsigned)((winball >> (8 * g)) & 0xffu)) - 1;
-        }
-        const double keymin = grp8_min_f64(key);
-        const double expose = min_f64(rowmin, keymin);
-        if (gl == 0) Mr[g] = expose;
-        PDMP_LDS_ORDER();
-        // ---------------- validate: event g commits iff all earlier ones do, its zone is disjoint from theirs, and nothing they
-        // produce or expose comes before it
-        uint32_t Rc;
-        uint32_t nacc_c;
-        int vsel = -1;  // the event that violates its bound, if it is the chain's next one
-        {
-            double pref = PDMP_INF;
-#pragma unroll
-            for (int q = 0; q < E - 1; ++q) {
-                const double mq = Mr[q];
-                pref = (q < g) ? min_f64(pref, mq) : pref;
-            }
-            const bool confg = ((confball >> g) & 1ull) != 0;
-            const bool okg = gvalid && ((g == 0) || (!confg && pref > tp));
-            const bool vstop = violated && !adapt;  // reference: error(...), :124 -> the event is not committed
-            const uint64_t okball = __ballot(okg && !vstop && gl == 0);
-            const uint64_t vball = __ballot(okg && vstop && gl == 0);
-            const uint64_t accball = __ballot(accept && gl == 0);
-            // length of the run of committable slots from slot 0 (one bit per slot at bit 8 r): first zero among those bits
-            const uint64_t gap = ~okball & 0x0101010101010101ull;
-            const uint32_t r_ok = gap ? (uint32_t)((__ffsll((unsigned long long)gap) - 1) >> 3) : (uint32_t)E;
-            Rc = 0;
-            nacc_c = 0;
-            bool stopped = false;
-            // the usual case needs no walk: the slice mode stops on time alone, and the trace has room for every accepted slot
-            const uint32_t nacc_all = (uint32_t)__popcll(accball & ((r_ok < 8u) ? ((1ull << (8 * r_ok)) - 1ull) : ~0ull));
-            const bool plainrun = stop_before && !(P.trace_cap > 0 && dnacc + nacc_all >= trace_room);
-            if (plainrun) {
-                Rc = r_ok;
-                nacc_c = nacc_all;
-            }
-            for (uint32_t r = 0; !plainrun && r < r_ok && !stopped; ++r) {
-                Rc = r + 1;
-                if ((accball >> (8 * r)) & 1ull) {
-                    nacc_c += 1;
-                    if (dnacc + nacc_c >= trace_room && P.trace_cap > 0) {
-                        status = PDMP_CHAIN_TRACE_FULL;
-                        stopped = true;
-                    }
-                    if (!stop_before && !(uniform_f64(SLT[r]) < T)) {
-                        running = false;
-                        stopped = true;
-                    }
-                }
-            }
-            if (!stopped && r_ok < (uint32_t)E && ((vball >> (8 * r_ok)) & 1ull)) {
-                status = PDMP_CHAIN_BOUND_VIOLATED;
-                vsel = (int)r_ok;
-            }
-        }
-        PHASE(6);
+        s8_patched_min<8>(pk, pk_t, blk, gvalid, key, g, gl, Mr, rowmin, cand, wl2);
+        // ---------------- validate: the committable prefix Rc, its accepted events, the event that violates its bound if it is the next one
+        uint32_t Rc, nacc_c;
+        int vsel;
+        s8_validate<E, 8>(Mr, SLT, confball, gvalid, accept, violated, adapt, tp, g, gl, stop_before, T, P.trace_cap > 0, dnacc, trace_room, Rc,
+                          nacc_c, vsel, status, running);
+        phc.mark(6);
 
         // ---------------- commit the valid prefix
         const bool commit = gvalid && (uint32_t)g < Rc;
@@ -3416,98 +2712,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             }
         }
         PDMP_LDS_ORDER();
-        PHASE(7);
-        // ---------------- level-1 updates for re-bounded neighbours living in other blocks.  The final entry of a block is the
-        // smallest (key, coordinate) among its old entry and the new keys, whatever the order -- so when no two of these lanes aim
-        // at one block (checked through a small claim table) and none has to rescan, every lane updates its block by itself, in
-        // one LDS round trip for all of them; otherwise the updates are made one by one in event order.
-        const bool upd = commit && accept && gl < k && (sA >> 5) != blk;
-        if (__ballot(upd) != 0) {
-            uint8_t* const CL = reinterpret_cast<uint8_t*>(smem + S8_CL);
-            PDMP_LDS_ORDER();
-            const uint32_t bjv = upd ? (sA >> 5) : 0u;
-            const double curv = bk[bjv];
-            const uint32_t civ = bi[bjv];
-            const bool lower = upd && (key < curv || (key == curv && sA < civ));
-            const bool resc = upd && !lower && civ == sA;
-            if (lower) CL[bjv & 63u] = (uint8_t)lane;
-            PDMP_LDS_ORDER();
-            const bool lost = lower && CL[bjv & 63u] != (uint8_t)lane;
-            if (__ballot(lost || resc) == 0) {
-                if (lower) {
-                    bk[bjv] = key;
-                    bi[bjv] = (uint16_t)sA;
-                }
-            } else {
-            for (uint32_t r = 0; r < Rc; ++r) {
-                if (!((accball2 >> (8 * r)) & 1ull)) continue;
-                const uint32_t own = uniform_u32(SLB[r]);
-                const int kr = (int)readlane_u32((uint32_t)k, 8 * (int)r);
-                for (int jj = 0; jj < kr; ++jj) {
-                    const uint32_t j = readlane_u32(sA, 8 * (int)r + jj);
-                    if ((j >> 5) == own) continue;
-                    // first-level entry of j's 32-key block: a lower key replaces it; if j WAS the entry and grew, the block is rescanned
-                    const double kj = readlane_f64(key, 8 * (int)r + jj);
-                    const uint32_t bj = j >> 5;
-                    PDMP_LDS_ORDER();
-                    const double cur = bk[bj];
-                    const uint32_t ci = bi[bj];
-                    if (kj < cur || (kj == cur && j < ci)) {
-                        if (lane == 0) {
-                            bk[bj] = kj;
-                            bi[bj] = (uint16_t)j;
-                        }
-                    } else if (ci == j) {
-                        const double kv = __hip_atomic_load(keys + (size_t)bj * 32 + (lane & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        const double mn = wave_min_f64(kv);
-                        const uint64_t bl = __ballot(kv == mn);
-                        const int arg = bl ? (__ffsll((unsigned long long)bl) - 1) : 0;
-                        if (lane == 0) {
-                            bk[bj] = mn;
-                            bi[bj] = (uint16_t)(bj * 32 + (uint32_t)arg);
-                        }
-                    }
-                }
-            }
-            }
-        }
-        PHASE(8);
-        // ---------------- the violating proposal itself (reference: counted, G[i] moved, acc bumped -- then error(...), :120-124):
-        // what zz_local_run_kernel and the oracle leave behind
-        if (vsel >= 0) {
-            if (g == vsel && gl == self) ri->tprop = uniform_f64(SLT[vsel]);
-            dnum += 1;
-            vnacc = 1;
-            dnm += ((uint32_t)(offpack >> (6 * vsel)) & 63u) + 1u - ((uint32_t)(offpack >> (6 * Rc)) & 63u);
-        }
-        // ---------------- counters
-        if (Rc > 0) {
-            dnum += Rc;
-            dnacc += nacc_c;
-            dnm += (uint32_t)(offpack >> (6 * Rc)) & 63u;
-            t_last = uniform_f64(SLT[Rc - 1]);
-            if (accball2) t_event = uniform_f64(SLT[(63 - __builtin_clzll(accball2)) >> 3]);
-        }
-        if (vsel >= 0) t_last = uniform_f64(SLT[vsel]);  // the violating event's time is the chain's current time
+        phc.mark(7);
+        // ---------------- level-1 updates for re-bounded neighbours living in other blocks
+        s8_level1_commit<8>(bk, bi, reinterpret_cast<uint8_t*>(smem + S8_CL), keys, SLB, commit && accept && gl < k && (sA >> 5) != blk, sA, key, k, Rc,
+                            accball2, lane);
+        phc.mark(8);
+        // ---------------- the violating proposal itself (reference: counted, G[i] moved, acc bumped -- then error(...), :120-124), counters
+        if (vsel >= 0 && g == vsel && gl == self) ri->tprop = uniform_f64(SLT[vsel]);
+        s8_count<8>(vsel, Rc, nacc_c, offpack, accball2, SLT, dnum, dnacc, dnm, vnacc, t_last, t_event);
         if (status != PDMP_CHAIN_OK) break;
         PDMP_LDS_ORDER();
     }
 
-    if (PROF && P.dbg && chain == 0 && lane == 0) {
-        for (int q = 0; q < 10; ++q) P.dbg[q] = (double)ph[q];
-        P.dbg[10] = (double)ph_iters;
-    }
-#undef PHASE
-    if (lane == 0) {
-        hdr->c.t_last = t_last;
-        hdr->t_event = t_event;
-        hdr->c.num += dnum;
-        hdr->c.nacc += dnacc + vnacc;
-        hdr->c.ntrace = ntrace0 + dnacc;
-        hdr->c.nevents += dnacc;
-        hdr->c.ndraw_main = nm0 + dnm;
-        hdr->c.status = status;
-    }
+    if (PROF && P.dbg && chain == 0 && lane == 0) phc.store(P.dbg);
+    if (lane == 0) s8_store_header<false>(hdr, keys, d, t_last, t_event, dnum, dnacc, vnacc, ntrace0, nm0, dnm, status, false, PDMP_INF, 0u, 0ull);
 }
 
 

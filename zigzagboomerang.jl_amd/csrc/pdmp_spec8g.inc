@@ -1,5 +1,4 @@
-// pdmp_spec8g.inc -- zz_local_spec8g_kernel: zz_local_spec8_kernel's scheme (eight event slots per iteration in 8-lane groups, threshold selection,
-// scalar accept walk, exact validation, commit of the valid prefix; included by pdmp_kernels.hip after it, whose helpers it uses) for ANY sparse Γ
+// pdmp_spec8g.inc -- zz_local_spec8g_kernel: the 8-event scheme (pdmp_spec8_common.hpp; included by pdmp_kernels.hip after zz_local_spec8_kernel) for ANY sparse Γ
 // with |G1[i]| <= 8 and |S[i]| <= 32 (GW = 8: eight events per iteration) or <= 64 (GW = 16: four) -- `spdmp` builds G1 / G2 from whatever CSC pattern it is given (src/sfact.jl:170-179).  What the lattice
 // kernel takes from a blob template in LDS (one template serves 94 % of a lattice's coordinates; on a graph without that regularity every
 // coordinate has its own, and eight of them do not fit beside the queue) each lane here reads straight from two per-coordinate tables of ONE 128-byte
@@ -49,7 +48,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     constexpr int E = 64 / GW;
     constexpr int LG = (GW == 8) ? 3 : 4;
     constexpr uint64_t GM = (GW == 8) ? 0xffull : 0xffffull;                                // the lanes of one group in a ballot
-    constexpr uint64_t G0 = (GW == 8) ? 0x0101010101010101ull : 0x0001000100010001ull;     // lane 0 of every group
     constexpr uint32_t G8_SXP = 4 * GW + 1;
     constexpr uint32_t LSTR = (GW == 8) ? 16u : 24u;  // u64 words per coordinate in the line table: GW id words + 8 position words
     constexpr int KPL = 32 / GW;                      // keys of the popped block per lane
@@ -106,43 +104,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                                     : 0xffffffffu;
 
     if (lane0 == 0) SELDT[0] = 1e-3;
-    for (uint32_t b = lane0; b < nblk; b += 64) {
-        const double* kp = keys + (size_t)b * 32;
-        // (the refresh clock's slot, key d, sits inside the last block when d is no multiple of 32: it is no coordinate -- its time lives in t_ref,
-        // and the slot holds +Inf in memory for as long as this launch runs, so that the rescans of its block do not see it either)
-        double mk = (has_refresh && b * 32 == (uint32_t)d) ? PDMP_INF : kp[0];
-        uint32_t mi = 0;
-#pragma unroll 8
-        for (int q = 1; q < 32; ++q) {
-            const double v = (has_refresh && b * 32 + (uint32_t)q == (uint32_t)d) ? PDMP_INF : kp[q];
-            if (v < mk) {
-                mk = v;
-                mi = q;
-            }
-        }
-        bk[b] = mk;
-        bi[b] = (uint16_t)(b * 32 + mi);
-    }
-    for (uint32_t b = nblk + lane0; b < S8_NBLK; b += 64) {
-        bk[b] = PDMP_INF;
-        bi[b] = 0;
-    }
+    s8_build_level1<true>(keys, bk, bi, nblk, d, has_refresh, lane0);
     PDMP_LDS_ORDER();
     if (has_refresh && lane0 == 0) __hip_atomic_store(keys + d, PDMP_INF, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 
     uint32_t rng_base = 0xffffffffu;
     double ureg = 0.0;  // draw rng_base + lane of the chain's stream
-    uint64_t ph[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    uint64_t ph_t0 = PROF ? (uint64_t)__builtin_readcyclecounter() : 0;
-    uint64_t ph_iters = 0;
-#define PHASE(k)                                                          \
-    do {                                                                  \
-        if (PROF) {                                                       \
-            const uint64_t now_ = (uint64_t)__builtin_readcyclecounter(); \
-            ph[k] += now_ - ph_t0;                                        \
-            ph_t0 = now_;                                                 \
-        }                                                                 \
-    } while (0)
+    PhaseClock<PROF> phc;
 
     bool running = stop_before || (t_event < T);
     PrioTurn prio;
@@ -166,85 +134,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             status = PDMP_CHAIN_PAUSED;
             break;
         }
-        // ---------------- select the (up to) E smallest block minima in time order (zz_local_spec8_kernel's threshold selection, unchanged)
-        int Esel = 0;
-        bool first_inf = false, do_ref = false;
-        {
-            double kk[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) kk[j] = bk[lane + 64 * j];
-            const double mloc = min_f64(min_f64(min_f64(kk[0], kk[1]), min_f64(kk[2], kk[3])),
-                                        min_f64(min_f64(kk[4], kk[5]), min_f64(kk[6], kk[7])));
-            const double mq = wave_min_f64(mloc);
-            do_ref = has_refresh && t_ref < mq && !(stop_before && !(t_ref < T));  // (a coordinate's event at the clock's very time goes first)
-            if (do_ref) {
-            } else if (!(mq < PDMP_INF)) {
-                first_inf = true;
-            } else if (!(stop_before && !(mq < T))) {
-                if (lane < (int)SEL_CAP) TK[lane] = PDMP_INF;
-                double dt_sel = uniform_f64(SELDT[0]);
-                auto below = [](uint64_t m_) -> uint32_t {
-                    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m_ >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m_, 0u));
-                };
-                double tau;
-                uint32_t C;
-                for (int tries = 0;; ++tries) {
-                    tau = mq + dt_sel;
-                    if (stop_before && !(tau < T)) tau = pdmp_below(T);
-                    if (!(tau < t_ref)) tau = (t_ref > mq) ? pdmp_below(t_ref) : mq;  // nothing at or beyond the refresh clock's time (but the minimum itself)
-                    const bool pile = tries > 64;
-                    if (tries >= 64) tau = mq;
-                    uint32_t base = 0;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const bool cj_ = kk[j] <= tau;
-                        uint64_t Mj = __ballot(cj_);
-                        if (pile) Mj = (base == 0 && Mj) ? (Mj & (~Mj + 1)) : 0ull;
-                        if (cj_ && ((Mj >> lane) & 1ull)) {
-                            const uint32_t ix = base + below(Mj);
-                            if (ix < 64u) {
-                                TK[ix] = kk[j];
-                                TB[ix] = (uint32_t)lane + 64u * j;
-                            }
-                        }
-                        base += (uint32_t)__popcll(Mj);
-                    }
-                    C = base;
-                    if (C <= SEL_CAP) break;
-                    dt_sel *= 0.5;
-                    PDMP_LDS_ORDER();
-                    if (lane < (int)SEL_CAP) TK[lane] = PDMP_INF;
-                }
-                PDMP_LDS_ORDER();
-                {
-                    const uint32_t n = (uint32_t)lane & 15u, part = (uint32_t)lane >> 4;
-                    const double own = TK[n];
-                    const double2* T2 = reinterpret_cast<const double2*>(TK + 4 * part);
-                    const double2 o01 = T2[0], o23 = T2[1];
-                    const uint32_t q = 4 * part;
-                    uint32_t pr = 0;
-                    pr += (o01.x < own || (o01.x == own && q + 0 < n)) ? 1u : 0u;
-                    pr += (o01.y < own || (o01.y == own && q + 1 < n)) ? 1u : 0u;
-                    pr += (o23.x < own || (o23.x == own && q + 2 < n)) ? 1u : 0u;
-                    pr += (o23.y < own || (o23.y == own && q + 3 < n)) ? 1u : 0u;
-                    PR[n * 4 + part] = pr;
-                    PDMP_LDS_ORDER();
-                    if ((uint32_t)lane < C) {
-                        const uint4 p4 = reinterpret_cast<const uint4*>(PR)[lane];
-                        const uint32_t rank = p4.x + p4.y + p4.z + p4.w;
-                        const uint32_t tbl = TB[lane];
-                        PDMP_LDS_ORDER();
-                        if (rank < (uint32_t)E) {
-                            SLT[rank] = own;
-                            SLB[rank] = tbl;
-                        }
-                    }
-                }
-                Esel = (C < (uint32_t)E) ? (int)C : E;
-                const double f = (C > 14u) ? 0.8 : (C < 11u) ? ((C < 6u) ? 2.0 : 1.2) : 1.0;
-                if (lane == 0) SELDT[0] = dt_sel * f;
-            }
-        }
+        // ---------------- select the (up to) E smallest block minima in time order
+        int Esel;
+        bool first_inf, do_ref;
+        s8_select<E, true, true>(bk, TK, TB, PR, SLT, SLB, SELDT, lane, stop_before, T, has_refresh, t_ref, Esel, first_inf, do_ref);
         if (do_ref) {
             // ---------------- the refresh clock is the chain's next event (src/sfact.jl:78-114, with its quirks: zz_local_run_kernel's restatement)
             const double tp = t_ref;
@@ -356,27 +249,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             }
             t_ref = newref;  // (stored into keys[d] when the launch ends)
             for (int jj = 0; jj < k; ++jj) {  // first level: blocks of 32 keys
-                const uint32_t j = readlane_u32(s, jj);
-                const double kjv = readlane_f64(key, jj);
-                const uint32_t bj = j >> 5;
-                PDMP_LDS_ORDER();
-                const double cur = bk[bj];
-                const uint32_t ci = bi[bj];
-                if (kjv < cur || (kjv == cur && j < ci)) {
-                    if (lane == 0) {
-                        bk[bj] = kjv;
-                        bi[bj] = (uint16_t)j;
-                    }
-                } else if (ci == j) {
-                    const double kv = (lane < 32) ? __hip_atomic_load(keys + (size_t)bj * 32 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : PDMP_INF;
-                    const double mn = wave_min_f64(kv);
-                    const uint64_t bl = __ballot(kv == mn);
-                    const int arg = bl ? (__ffsll((unsigned long long)bl) - 1) : 0;
-                    if (lane == 0) {
-                        bk[bj] = mn;
-                        bi[bj] = (uint16_t)(bj * 32 + (uint32_t)arg);
-                    }
-                }
+                s8_level1_update(bk, bi, keys, lane, readlane_u32(s, jj), readlane_f64(key, jj));
                 PDMP_LDS_ORDER();
             }
             const double t_i = readlane_f64(t, self), x_i = readlane_f64(x, self), th_i2 = readlane_f64(th, self);
@@ -402,8 +275,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         if (chain == 0 && lane == 0 && (prio.it % 64u) == 0u) printf("g8 iter %u Esel %d t_ref %.17g t_last %.17g dnum %u\n", (unsigned)prio.it, Esel, t_ref, t_last, dnum);
 #endif
         PDMP_LDS_ORDER();
-        PHASE(0);
-        if (PROF) ph_iters += 1;
+        phc.mark(0);
+        if (PROF) phc.iters += 1;
         bool gvalid = g < Esel;
         const double tp = gvalid ? SLT[g] : PDMP_INF;
         const uint32_t blk = gvalid ? SLB[g] : 0u;
@@ -436,7 +309,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             ureg = pdmp_u01(seed, PDMP_STREAM_MAIN, nm0 + (uint64_t)dnm + (uint64_t)lane);
             LU[lane] = pdmp_log(ureg);
         }
-        PHASE(1);
+        phc.mark(1);
         const uint32_t idlo = (uint32_t)idw64, idhi = (uint32_t)(idw64 >> 32);
         const bool memberA = gvalid && (idlo & 0x7fffu) != 0x7fffu, memberB = gvalid && ((idlo >> 16) & 0x7fffu) != 0x7fffu,
                    memberC = gvalid && (idhi & 0x7fffu) != 0x7fffu, memberD = gvalid && ((idhi >> 16) & 0x7fffu) != 0x7fffu;
@@ -447,7 +320,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         const uint32_t sD = memberD ? ((idhi >> 16) & 0x7fffu) : 0xffffffffu;
         const int k = __popc((unsigned)((__ballot(isG1) >> (GW * g)) & GM));                              // |G1[i]|
         const int self = __ffs((unsigned)((__ballot(memberA && sA == i) >> (GW * g)) & GM)) - 1;          // position of i in G1[i]
-        PHASE(2);
+        phc.mark(2);
         // ---------------- level-2 loads (functions of the member ids), one straight-line batch: the record of G1 member gl (lanes without one
         // read i's) and the tables of member j = G1[i][gl] (lanes without one read i's: L2 hits)
         const uint32_t jA = isG1 ? sA : i;
@@ -509,7 +382,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             confball = confmask;
         }
         PDMP_LDS_ORDER();
-        PHASE(3);
+        phc.mark(3);
 
         // ---------------- smove_forward!(G, i, ...), gradient, rates
         {
@@ -540,35 +413,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             }
         }
         PDMP_LDS_ORDER();
-        // ---------------- accept chain in time order (lane o evaluates every event's test for the draw at offset o; scalar walk)
-        uint32_t accbits = 0;
-        uint64_t offpack = 0;
-        {
-            const double coin = ureg;  // (the window starts at the front: the draw at offset o is lane o's)
-            uint32_t off = 0;
-            int fit = Esel;
-#pragma unroll
-            for (int r = 0; r < E; ++r) {
-                const uint64_t am_r = __ballot(coin * LBr[r] < Lr[r]);  // :121
-                const uint32_t k_r = readlane_u32((uint32_t)k, GW * r);
-                // its draws would leave the window -- or its end offset the six bits it travels in (offsets are kept <= 63): the list ends here
-                if (r < fit && off + 1u + k_r > 63u) fit = r;
-                const uint32_t a_r = (uint32_t)(am_r >> (off & 63u)) & 1u;
-                off += a_r ? (1u + k_r) : 2u;
-                off = (off < 63u) ? off : 63u;
-                accbits |= a_r << r;
-                offpack |= (uint64_t)off << (6 * (r + 1));
-            }
-            if (fit < Esel) {
-                Esel = fit;
-                gvalid = g < Esel;
-            }
-            accbits &= (1u << Esel) - 1u;
-        }
+        // ---------------- accept chain in time order (the window starts at the front: the draw at offset o is lane o's); an event whose draws
+        // would leave the window ends the candidate list
+        uint32_t accbits;
+        uint64_t offpack;
+        s8_accept_walk<E, GW, true>(ureg, LBr, Lr, k, Esel, accbits, offpack);
+        gvalid = g < Esel;
         const uint32_t myoff = (uint32_t)(offpack >> (6 * g)) & 63u;
         const bool accept = gvalid && ((accbits >> g) & 1u) != 0;
         const bool violated = accept && (l >= lbound);  // :123
-        PHASE(4);
+        phc.mark(4);
 
         // (a G2 member's velocity does not change: it is not kept, and not stored again)
         double x2 = 0.0, I2 = 0.0, x3 = 0.0, I3 = 0.0, x4 = 0.0, I4 = 0.0;
@@ -665,110 +519,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         }
         PDMP_LDS_ORDER();
         // the patched copy of the popped key block goes where sx / sth were: all their readers are done
-        if (KPL == 4) {
-            double2* pk2 = reinterpret_cast<double2*>(pk + gl * 4);
-            pk2[0 ^ pk_t] = make_double2(kq[0], kq[1]);
-            pk2[1 ^ pk_t] = make_double2(kq[2], kq[3]);
-        } else {
-            reinterpret_cast<double2*>(pk + gl * 2)[0] = make_double2(kq[0], kq[1]);
-        }
-        PDMP_LDS_ORDER();
-        if (active && (sA >> 5) == blk) {
-            const uint32_t e_ = sA & 31u;
-            if (KPL == 4) pk[(e_ & ~3u) + ((((e_ & 3u) >> 1) ^ pk_t) << 1) + (e_ & 1u)] = key;
-            else pk[e_] = key;
-        }
-        PDMP_LDS_ORDER();
-        PHASE(5);
+        s8_patch_block<KPL>(pk, pk_t, gl, kq, active && (sA >> 5) == blk, sA, key);
+        phc.mark(5);
         // ---------------- patched minimum of the popped block, and everything this event could expose
         double rowmin;
         uint32_t cand;
         int wl2;
-        {
-            double lm;
-            uint32_t li = 0;
-            if (KPL == 4) {
-                const double2* pk2 = reinterpret_cast<const double2*>(pk + gl * 4);
-                const double2 p01 = pk2[0 ^ pk_t], p23 = pk2[1 ^ pk_t];
-                lm = p01.x;
-                if (p01.y < lm) {
-                    lm = p01.y;
-                    li = 1;
-                }
-                if (p23.x < lm) {
-                    lm = p23.x;
-                    li = 2;
-                }
-                if (p23.y < lm) {
-                    lm = p23.y;
-                    li = 3;
-                }
-            } else {
-                const double2 p01 = reinterpret_cast<const double2*>(pk + gl * 2)[0];
-                lm = p01.x;
-                if (p01.y < lm) {
-                    lm = p01.y;
-                    li = 1;
-                }
-            }
-            cand = blk * 32u + (uint32_t)gl * (uint32_t)KPL + li;
-            rowmin = (GW == 8) ? grp8_min_f64(lm) : row_min_f64(lm);
-            const uint64_t winball = __ballot(gvalid && lm == rowmin);
-            wl2 = __ffs((unsigned)((winball >> (GW * g)) & GM)) - 1;
-        }
-        const double keymin = (GW == 8) ? grp8_min_f64(key) : row_min_f64(key);
-        const double expose = min_f64(rowmin, keymin);
-        if (gl == 0) Mr[g] = expose;
-        PDMP_LDS_ORDER();
-        // ---------------- validate: event g commits iff all earlier ones do, its zone is disjoint from theirs, and nothing they produce or
-        // expose comes before it
-        uint32_t Rc;
-        uint32_t nacc_c;
-        int vsel = -1;
-        {
-            double pref = PDMP_INF;
-#pragma unroll
-            for (int q = 0; q < E - 1; ++q) {
-                const double mq = Mr[q];
-                pref = (q < g) ? min_f64(pref, mq) : pref;
-            }
-            const bool confg = ((confball >> g) & 1ull) != 0;
-            const bool okg = gvalid && ((g == 0) || (!confg && pref > tp));
-            const bool vstop = violated && !adapt;  // reference: error(...), :124 -> the event is not committed
-            const uint64_t okball = __ballot(okg && !vstop && gl == 0);
-            const uint64_t vball = __ballot(okg && vstop && gl == 0);
-            const uint64_t accball = __ballot(accept && gl == 0);
-            const uint64_t gap = ~okball & G0;
-            const uint32_t r_ok = gap ? (uint32_t)((__ffsll((unsigned long long)gap) - 1) >> LG) : (uint32_t)E;
-            Rc = 0;
-            nacc_c = 0;
-            bool stopped = false;
-            const uint32_t nacc_all = (uint32_t)__popcll(accball & ((r_ok < (uint32_t)E) ? ((1ull << (GW * r_ok)) - 1ull) : ~0ull));
-            const bool plainrun = stop_before && !(P.trace_cap > 0 && dnacc + dnref + nacc_all >= trace_room);
-            if (plainrun) {
-                Rc = r_ok;
-                nacc_c = nacc_all;
-            }
-            for (uint32_t r = 0; !plainrun && r < r_ok && !stopped; ++r) {
-                Rc = r + 1;
-                if ((accball >> (GW * r)) & 1ull) {
-                    nacc_c += 1;
-                    if (dnacc + dnref + nacc_c >= trace_room && P.trace_cap > 0) {
-                        status = PDMP_CHAIN_TRACE_FULL;
-                        stopped = true;
-                    }
-                    if (!stop_before && !(uniform_f64(SLT[r]) < T)) {
-                        running = false;
-                        stopped = true;
-                    }
-                }
-            }
-            if (!stopped && r_ok < (uint32_t)E && ((vball >> (GW * r_ok)) & 1ull)) {
-                status = PDMP_CHAIN_BOUND_VIOLATED;
-                vsel = (int)r_ok;
-            }
-        }
-        PHASE(6);
+        s8_patched_min<GW>(pk, pk_t, blk, gvalid, key, g, gl, Mr, rowmin, cand, wl2);
+        // ---------------- validate: the committable prefix Rc, its accepted events, the event that violates its bound if it is the next one
+        uint32_t Rc, nacc_c;
+        int vsel;
+        s8_validate<E, GW>(Mr, SLT, confball, gvalid, accept, violated, adapt, tp, g, gl, stop_before, T, P.trace_cap > 0, dnacc + dnref, trace_room, Rc,
+                           nacc_c, vsel, status, running);
+        phc.mark(6);
 
         // ---------------- commit the valid prefix
         const bool commit = gvalid && (uint32_t)g < Rc;
@@ -818,98 +581,22 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             }
         }
         PDMP_LDS_ORDER();
-        PHASE(7);
-        // ---------------- level-1 updates for re-bounded neighbours living in other blocks (zz_local_spec8_kernel's, unchanged)
-        const bool upd = commit && accept && isG1 && (sA >> 5) != blk;
-        if (__ballot(upd) != 0) {
-            uint8_t* const CL = reinterpret_cast<uint8_t*>(smem + G8_CL);
-            PDMP_LDS_ORDER();
-            const uint32_t bjv = upd ? (sA >> 5) : 0u;
-            const double curv = bk[bjv];
-            const uint32_t civ = bi[bjv];
-            const bool lower = upd && (key < curv || (key == curv && sA < civ));
-            const bool resc = upd && !lower && civ == sA;
-            if (lower) CL[bjv & 63u] = (uint8_t)lane;
-            PDMP_LDS_ORDER();
-            const bool lost = lower && CL[bjv & 63u] != (uint8_t)lane;
-            if (__ballot(lost || resc) == 0) {
-                if (lower) {
-                    bk[bjv] = key;
-                    bi[bjv] = (uint16_t)sA;
-                }
-            } else {
-                for (uint32_t r = 0; r < Rc; ++r) {
-                    if (!((accball2 >> (GW * r)) & 1ull)) continue;
-                    const uint32_t own = uniform_u32(SLB[r]);
-                    const int kr = (int)readlane_u32((uint32_t)k, GW * (int)r);
-                    for (int jj = 0; jj < kr; ++jj) {
-                        const uint32_t j = readlane_u32(sA, GW * (int)r + jj);
-                        if ((j >> 5) == own) continue;
-                        const double kj = readlane_f64(key, GW * (int)r + jj);
-                        const uint32_t bj = j >> 5;
-                        PDMP_LDS_ORDER();
-                        const double cur = bk[bj];
-                        const uint32_t ci = bi[bj];
-                        if (kj < cur || (kj == cur && j < ci)) {
-                            if (lane == 0) {
-                                bk[bj] = kj;
-                                bi[bj] = (uint16_t)j;
-                            }
-                        } else if (ci == j) {
-                            const double kv = __hip_atomic_load(keys + (size_t)bj * 32 + (lane & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            const double mn = wave_min_f64(kv);
-                            const uint64_t bl = __ballot(kv == mn);
-                            const int arg = bl ? (__ffsll((unsigned long long)bl) - 1) : 0;
-                            if (lane == 0) {
-                                bk[bj] = mn;
-                                bi[bj] = (uint16_t)(bj * 32 + (uint32_t)arg);
-                            }
-                        }
-                    }
-                }
-            }
+        phc.mark(7);
+        // ---------------- level-1 updates for re-bounded neighbours living in other blocks
+        s8_level1_commit<GW>(bk, bi, reinterpret_cast<uint8_t*>(smem + G8_CL), keys, SLB, commit && accept && isG1 && (sA >> 5) != blk, sA, key, k, Rc,
+                             accball2, lane);
+        phc.mark(8);
+        // ---------------- the violating proposal itself (counted, G[i] moved, acc bumped -- then error(...), :120-124), counters
+        if (vsel >= 0 && g == vsel && isG1) {
+            rsA->x = x;
+            rsA->t = t;
+            rsA->I = I;
         }
-        PHASE(8);
-        // ---------------- the violating proposal itself (counted, G[i] moved, acc bumped -- then error(...), :120-124)
-        if (vsel >= 0) {
-            if (g == vsel && isG1) {
-                rsA->x = x;
-                rsA->t = t;
-                rsA->I = I;
-            }
-            dnum += 1;
-            vnacc = 1;
-            dnm += ((uint32_t)(offpack >> (6 * vsel)) & 63u) + 1u - ((uint32_t)(offpack >> (6 * Rc)) & 63u);
-        }
-        // ---------------- counters
-        if (Rc > 0) {
-            dnum += Rc;
-            dnacc += nacc_c;
-            dnm += (uint32_t)(offpack >> (6 * Rc)) & 63u;
-            t_last = uniform_f64(SLT[Rc - 1]);
-            if (accball2) t_event = uniform_f64(SLT[(63 - __builtin_clzll(accball2)) >> LG]);
-        }
-        if (vsel >= 0) t_last = uniform_f64(SLT[vsel]);
+        s8_count<GW>(vsel, Rc, nacc_c, offpack, accball2, SLT, dnum, dnacc, dnm, vnacc, t_last, t_event);
         if (status != PDMP_CHAIN_OK) break;
         PDMP_LDS_ORDER();
     }
 
-    if (PROF && P.dbg && chain == 0 && lane0 == 0) {
-        for (int q = 0; q < 10; ++q) P.dbg[q] = (double)ph[q];
-        P.dbg[10] = (double)ph_iters;
-    }
-#undef PHASE
-    if (lane0 == 0) {
-        hdr->c.t_last = t_last;
-        hdr->t_event = t_event;
-        hdr->c.num += dnum;
-        hdr->c.nacc += dnacc + vnacc;
-        hdr->c.ntrace = ntrace0 + dnacc + dnref;
-        hdr->c.nevents += dnacc + dnref;
-        hdr->c.nrefresh += dnref;
-        hdr->c.ndraw_global = ng;
-        if (has_refresh) keys[d] = t_ref;
-        hdr->c.ndraw_main = nm0 + dnm;
-        hdr->c.status = status;
-    }
+    if (PROF && P.dbg && chain == 0 && lane0 == 0) phc.store(P.dbg);
+    if (lane0 == 0) s8_store_header<true>(hdr, keys, d, t_last, t_event, dnum, dnacc, vnacc, ntrace0, nm0, dnm, status, has_refresh, t_ref, dnref, ng);
 }
