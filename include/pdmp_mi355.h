@@ -41,7 +41,8 @@ extern "C" {
  *    run the tracked local ZigZag with a helper wavefront per chain (same results; include/pdmp_debug.h: pdmp_debug_set_helper_wave).
  *    A host binding must check pdmp_abi_version() at load time.
  *    (still 3: pdmp_ensemble_set_bps_sticky, pdmp_ensemble_bps_trace_free_copy and pdmp_ensemble_bps_final_sticky were ADDED later -- the sticky
- *    Bouncy Particle / Boomerang; nothing that existed changed, so a binding that wants them looks the symbols up.) */
+ *    Bouncy Particle / Boomerang; nothing that existed changed, so a binding that wants them looks the symbols up.  The same holds for
+ *    pdmp_ensemble_set_flow_bps_modern and pdmp_ensemble_set_bps_record_limit, the speed-recorded Bouncy Particle.) */
 #define PDMP_ABI_VERSION 3
 
 typedef enum {
@@ -427,6 +428,35 @@ pdmp_status pdmp_ensemble_set_bps_sticky(pdmp_ensemble* ens, const double* kappa
 pdmp_status pdmp_ensemble_bps_trace_free_copy(pdmp_ensemble* ens, int64_t chain, int64_t first, int64_t count, uint8_t* f);
 /* final free mask and saved speeds θf of chains [chain_first, chain_first+n): [n x d] each, either may be NULL */
 pdmp_status pdmp_ensemble_bps_final_sticky(pdmp_ensemble* ens, int64_t chain_first, int64_t n, uint8_t* f, double* theta_f);
+
+/*
+ * pdmp(dϕ, ∇ϕ!, t0, x0, θ0, T, c::LocalBound, flow::BouncyParticle; oscn, adapt, factor) (src/not_fact_samplers.jl:151-384, "ModernBPS"): the
+ * speed-recorded Bouncy Particle.  It bounds with both directional derivatives dϕ = (θ'Γt(x−μt), θ'Γtθ) and an expiry horizon, redraws the
+ * refreshment time with every bound, refreshes and RECORDS in proportion to the speed V = record_rate(θ): a record (t, x, θ) every 1/λref of
+ * speed-time ∫V dt, and nothing else -- the trace is the sample, no discretize pass is needed.  The trace does not begin with (t0, x0, θ0).
+ *   u_diag  NULL: the L form, V ≡ 1, the mass factor L is the identity or what pdmp_ensemble_set_mass_cholesky hands over (reflect!
+ *           :161-164, refresh! :173-180);  [d] > 0: the diagonal-U form, U = PDiagMat(u): reflect! with z = u .* ∇ϕx, refresh! with
+ *           unwhiten = √u .* z, V = ‖θ ./ √u‖ (:156-172, :197).
+ *   oscn    the orthogonal-subspace Crank-Nicolson bounce of src/oscn.jl (normalize = false) instead of reflect!; L = I only.
+ * Call order, on a PDMP_SAMPLER_BPS ensemble: set_flow_bps_modern; pdmp_ensemble_set_target_gaussian_csc (REQUIRED: this flow has no Γ of
+ * its own); optionally pdmp_ensemble_set_mass_cholesky (L form only); pdmp_ensemble_set_state_bps(t0, x0, θ0, c, seeds) with c = LocalBound(c).c.
+ * adapt / factor are the ensemble configuration's.  d <= 1024.
+ * set_state_bps returns PDMP_ERR_UNSUPPORTED naming the option for: d > 1024; set_bps_moments(order >= 1); set_bps_sticky; set_bps_options
+ * (subsample or local_bound: they belong to the other driver, this one always bounds locally and always subsamples); oscn with u_diag or with
+ * a mass factor that is not the identity; u_diag together with a mass factor.  PDMP_ERR_INVALID: lambda_ref <= 0, |rho| > 1, a u_diag entry
+ * <= 0 or not finite, a missing target or a c that is not finite and > 0 (at set_state_bps), another sampler, a state exists.  Any set_flow_* clears the setting.
+ * Records go to the BPS trace buffer: pdmp_ensemble_bps_trace_copy / _bps_final_state, trace_reset, the counters and the gather of BPS traces
+ * serve them unchanged.  nevents counts records, num / nacc are the reference's, nrefresh counts refreshments.  l > lb without adapt (at a
+ * record or at an accepted proposal) ends the chain as PDMP_CHAIN_BOUND_VIOLATED; the reference's `@assert Δrec > 0` failing ends it as
+ * PDMP_CHAIN_STALLED.  PDMP_RUN_REFERENCE_TAIL stops at the first record with t >= T; PDMP_RUN_STOP_BEFORE pauses before any event, record
+ * or expiry at a time >= T; sliced, drained (PDMP_CHAIN_TRACE_FULL) and paused (PDMP_CHAIN_PAUSED) runs continue bit for bit.
+ */
+pdmp_status pdmp_ensemble_set_flow_bps_modern(pdmp_ensemble* ens, double lambda_ref, double rho, const double* u_diag, int oscn);
+/*
+ * `T::Int` of the reference: a chain stops once nevents == n (0: no limit).  May be raised between runs to continue; a run takes whichever of
+ * T and n comes first (pass T = +Inf for the count alone).  After set_flow_bps_modern (which resets it to 0); PDMP_ERR_INVALID otherwise or for n < 0.
+ */
+pdmp_status pdmp_ensemble_set_bps_record_limit(pdmp_ensemble* ens, int64_t n);
 
 /* ------------------------------------------------------------------ trace consumers on the device (what callers do next with Ξ)
  *

@@ -18,6 +18,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <limits>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -57,11 +58,18 @@ struct FactBoomerang {
 // BouncyParticle(Γ, μ, λ, ρ, U, L)  src/types.jl:35-45.  L is the mass factor the reference's short constructor computes as
 // cholesky(Symmetric(Γ)).L (:43): LOWER triangular CSC with a stored diagonal; leave it empty (n == 0) only for Γ = I -- the engine refuses a
 // general Γ without its factor (PDMP_ERR_UNSUPPORTED) instead of running with a silent L = I.
+// BouncyParticle(missing, missing, λ, ρ, U, L) of the speed-recorded driver (src/not_fact_samplers.jl:336-384): Gamma empty (n == 0), L empty
+// (identity) or the factor, U empty or the diagonal of a PDiagMat metric ([d] > 0; not together with L).
 struct BouncyParticle {
     SparseCSC Gamma;
     std::vector<double> mu;
     double lambda_ref = 1.0, rho = 0.0;
     SparseCSC L;
+    std::vector<double> U;
+};
+// LocalBound(c), src/types.jl:122-124: selects the speed-recorded pdmp below
+struct LocalBound {
+    double c = 1.0;
 };
 // Boomerang(Γ, μ, λ; ρ=0)  src/types.jl:59-66: Γ enters through its factor L only (empty: identity)
 struct Boomerang {
@@ -90,6 +98,7 @@ struct Options {  // the reference's keyword arguments
     bool local_bound = false;  // c is LocalBound(c): spdmp(∇ϕ, t0, x0, θ0, T, C::LocalBound, F, args...), src/local.jl:95-149; for the
                                // non-factorised pdmp: src/not_fact_samplers.jl:29-31,65-71
     bool subsample = false;    // pdmp(∇ϕ!, ...; subsample) of the non-factorised samplers, src/not_fact_samplers.jl:53,90
+    bool oscn = false;         // pdmp(dϕ, ∇ϕ!, ..., c::LocalBound, flow::BouncyParticle; oscn): the orthogonal-subspace Crank-Nicolson bounce, src/oscn.jl
     bool tracked = false;      // engine-only: tracked-gradient evaluation of spdmp (pdmp_ensemble_set_gradient_tracking), the engine's fast
                                // path (2.5 x the default's rate on C3).  NOT the reference's arithmetic: floats to ~1e-13 instead of bit for
                                // bit; indices / counters / bounds identical until such a difference flips a test -- measured 3 of 4096
@@ -393,6 +402,39 @@ inline Result<PDMPTrace> pdmp(const GaussianTarget& target, double t0, const std
     }
     if (o.subsample) check(pdmp_ensemble_set_bps_options(e.get(), 0, 1));
     return detail::not_factorised(e, t0, x0, theta0, T, c, o);
+}
+
+// pdmp(dϕ, ∇ϕ!, t0, x0, θ0, T, c::LocalBound, flow::BouncyParticle; oscn, adapt, factor=2.0)  -- src/not_fact_samplers.jl:336-384, the
+// speed-recorded Bouncy Particle: dϕ = (θ'Γt(x−μt), θ'Γtθ) and ∇ϕ! = Γt(x−μt) of the Gaussian target; B.Gamma is empty.  The trace holds one
+// record per 1/λref of speed-time and does not begin with (t0, x0, θ0).  T is an end time (the last record has t >= T); the overload taking
+// an int64_t is the reference's `T::Int`, a number of samples.
+namespace detail {
+inline Result<PDMPTrace> modern(const GaussianTarget& target, double t0, const std::vector<double>& x0, const std::vector<double>& theta0,
+                                double T, int64_t nsamples, LocalBound c, const BouncyParticle& B, Options o) {
+    if (o.factor == 1.8) o.factor = 2.0;
+    if (B.Gamma.n != 0) throw std::invalid_argument("pdmp(..., c::LocalBound, B): the speed-recorded driver takes BouncyParticle(missing, missing, ...): B.Gamma must be empty");
+    const int64_t d = (int64_t)x0.size();
+    if (!B.U.empty() && (int64_t)B.U.size() != d) throw std::invalid_argument("BouncyParticle::U needs d entries");
+    const int64_t want = nsamples > 0 ? nsamples : (int64_t)(4 * B.lambda_ref * std::max(T - t0, 1.0));
+    const int64_t cap = o.trace_capacity > 0 ? o.trace_capacity : std::max<int64_t>(64, want);
+    Ensemble e(1, d, PDMP_SAMPLER_BPS, o, cap);
+    check(pdmp_ensemble_set_flow_bps_modern(e.get(), B.lambda_ref, B.rho, opt(B.U), o.oscn ? 1 : 0));
+    set_target(e, target);
+    if (B.L.n > 0) check(pdmp_ensemble_set_mass_cholesky(e.get(), B.L.colptr.data(), B.L.rowval.data(), B.L.nzval.data()));
+    if (nsamples > 0) {  // (set_state_bps comes first inside not_factorised: the limit is set on the flow, which keeps it)
+        check(pdmp_ensemble_set_bps_record_limit(e.get(), nsamples));
+    }
+    return not_factorised(e, t0, x0, theta0, T, c.c, o);
+}
+}  // namespace detail
+inline Result<PDMPTrace> pdmp(const GaussianTarget& target, double t0, const std::vector<double>& x0, const std::vector<double>& theta0,
+                              double T, LocalBound c, const BouncyParticle& B, Options o = {}) {
+    return detail::modern(target, t0, x0, theta0, T, 0, c, B, o);
+}
+inline Result<PDMPTrace> pdmp(const GaussianTarget& target, double t0, const std::vector<double>& x0, const std::vector<double>& theta0,
+                              int64_t nsamples, LocalBound c, const BouncyParticle& B, Options o = {}) {
+    if (nsamples <= 0) throw std::invalid_argument("pdmp(..., T::Int, ...): a positive number of samples");
+    return detail::modern(target, t0, x0, theta0, std::numeric_limits<double>::infinity(), nsamples, c, B, o);
 }
 
 // ---- the one-dimensional samplers: pdmp(∇ϕ, x, θ, T, c, Flow::Union{ZigZag1d, Boomerang1d}; adapt, factor = 2.0) -> Ξ, acc/num

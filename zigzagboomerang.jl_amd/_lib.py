@@ -45,6 +45,7 @@ EXPORTED_SYMBOLS = [
     "pdmp_ensemble_bps_final_state", "pdmp_ensemble_set_sticky", "pdmp_ensemble_set_adaptscale", "pdmp_ensemble_final_sigma", "pdmp_ensemble_set_flow_boomerang", "pdmp_ensemble_set_local_bound", "pdmp_ensemble_set_target_logistic", "pdmp_ensemble_set_flow_factboomerang",
     "pdmp_ensemble_set_mass_cholesky", "pdmp_ensemble_set_bps_options", "pdmp_ensemble_set_bps_moments", "pdmp_ensemble_bps_moments",
     "pdmp_ensemble_set_bps_sticky", "pdmp_ensemble_bps_trace_free_copy", "pdmp_ensemble_bps_final_sticky",
+    "pdmp_ensemble_set_flow_bps_modern", "pdmp_ensemble_set_bps_record_limit",
     "pdmp_ensemble_ess_begin", "pdmp_ensemble_ess_batch", "pdmp_ensemble_ess_end", "pdmp_ensemble_set_gradient_tracking",
     "pdmp_ensemble_path_integrals", "pdmp_ensemble_set_path_integrals", "pdmp_ensemble_set_neighbourhood", "pdmp_ensemble_info",
     "pdmp_ensemble_consume_begin", "pdmp_ensemble_consume", "pdmp_ensemble_consume_async", "pdmp_ensemble_last_consume_ms", "pdmp_ensemble_consume_mean", "pdmp_ensemble_consume_inclusion", "pdmp_ensemble_consume_discretized", "pdmp_ensemble_consume_cummean", "pdmp_ensemble_consume_cummean_copy", "pdmp_ensemble_subtrace_copy", "pdmp_1d_run",
@@ -176,6 +177,8 @@ def load():
     L.pdmp_ensemble_set_bps_sticky.argtypes = [vp, vp, C.c_int]
     L.pdmp_ensemble_bps_trace_free_copy.argtypes = [vp, i64, i64, i64, vp]
     L.pdmp_ensemble_bps_final_sticky.argtypes = [vp, i64, i64, vp, vp]
+    L.pdmp_ensemble_set_flow_bps_modern.argtypes = [vp, C.c_double, C.c_double, vp, C.c_int]
+    L.pdmp_ensemble_set_bps_record_limit.argtypes = [vp, i64]
     L.pdmp_debug_sticky_eval.argtypes = [C.c_int, C.c_int, i64, vp, vp, vp, vp]
     L.pdmp_ensemble_bps_trace_copy.argtypes = [vp, i64, i64, i64, vp, vp, vp]
     L.pdmp_ensemble_bps_final_state.argtypes = [vp, i64, i64, vp, vp, vp, vp]

@@ -248,6 +248,12 @@ struct pdmp_ensemble {
     int bps_strong = 0;
     DevBuf<double> b_kappa, b_thf, b_tfrez;  // [d]; [nchains x d] saved speeds; [nchains x d] freezing / thaw times
     DevBuf<uint64_t> b_fmask, b_ev_f;        // [nchains x 16], [nchains x cap x 16] free masks (bit e & 63 of word e >> 6)
+    // speed-recorded Bouncy Particle (pdmp_ensemble_set_flow_bps_modern, src/not_fact_samplers.jl:151-384)
+    bool bps_modern = false;
+    bool bps_udiag = false;
+    int bps_oscn = 0;
+    int64_t bps_record_limit = 0;
+    DevBuf<double> b_udiag, b_sudiag, b_mstate;  // [d] u, [d] sqrt(u), [nchains x 4] {Δ, action, V, Δrec}
     DevBuf<int64_t> bt_colptr, bt_rowval;
     DevBuf<double> bt_nzval, bt_mu;
     DevBuf<int32_t> m_Lcp, m_Lrv, m_Ucp, m_Urv;
@@ -1875,6 +1881,7 @@ pdmp_status pdmp_ensemble_set_state_synthetic(pdmp_ensemble* e, double t0, const
 static pdmp::BpsRunParams bps_run_params(const pdmp_ensemble* e, double T, int flags);
 static pdmp::BpsMomParams bps_moments_params(const pdmp_ensemble* e);
 static pdmp::BpsStickyParams bps_sticky_params(const pdmp_ensemble* e);
+static pdmp::BpsModernParams bps_modern_params(const pdmp_ensemble* e);
 
 pdmp_status pdmp_ensemble_run(pdmp_ensemble* e, double T, int flags, void* stream) {
     pdmp_status st = ensemble_run_impl(e, T, flags, stream);
@@ -1924,7 +1931,10 @@ static pdmp_status ensemble_run_impl(pdmp_ensemble* e, double T, int flags, void
     int rc = 0;
     switch (fam) {
     case FAM_BPS:
-        if (e->bps_sticky) {
+        if (e->bps_modern) {
+            e->last_kernel = "bps_modern_run_kernel";
+            rc = pdmp::launch_bps_modern_run(B, bps_modern_params(e), n, s);
+        } else if (e->bps_sticky) {
             e->last_kernel = "bps_sticky_run_kernel";
             rc = pdmp::launch_bps_sticky_run(B, bps_sticky_params(e), n, s);
         } else {
@@ -2737,6 +2747,9 @@ static pdmp_status set_flow_nf(pdmp_ensemble* e, const int64_t* colptr, const in
     e->bps_mom = 0;
     e->bps_sticky = false;
     e->bps_strong = 0;
+    e->bps_modern = e->bps_udiag = false;
+    e->bps_oscn = 0;
+    e->bps_record_limit = 0;
     e->bps_lambda = lambda_ref;
     e->bps_rho = rho;
     pdmp_status st;
@@ -2765,6 +2778,71 @@ pdmp_status pdmp_ensemble_set_flow_boomerang(pdmp_ensemble* e, const int64_t* co
                                              const double* nzval, const double* mu_target, const double* mu_flow,
                                              double lambda_ref, double rho) {
     return set_flow_nf(e, colptr, rowval, nzval, mu_target, lambda_ref, rho, 1, mu_flow);
+}
+
+// pdmp(dϕ, ∇ϕ!, t0, x0, θ0, T, c::LocalBound, flow::BouncyParticle; oscn, adapt, factor), src/not_fact_samplers.jl:336-384: the flow carries
+// no Γ of its own (BouncyParticle(missing, missing, λref, ρ, U, L)); the target follows with pdmp_ensemble_set_target_gaussian_csc.
+pdmp_status pdmp_ensemble_set_flow_bps_modern(pdmp_ensemble* e, double lambda_ref, double rho, const double* u_diag, int oscn) {
+    if (!e) return fail(PDMP_ERR_INVALID, "null argument");
+    if (e->cfg.sampler != PDMP_SAMPLER_BPS) return fail(PDMP_ERR_INVALID, "ensemble was not created with PDMP_SAMPLER_BPS");
+    if (e->has_state) return fail(PDMP_ERR_INVALID, "set_flow_bps_modern goes before set_state_bps");
+    if (!(lambda_ref > 0) || !std::isfinite(lambda_ref)) return fail(PDMP_ERR_INVALID, "BouncyParticle needs a strictly positive refreshment rate");
+    if (!(std::fabs(rho) <= 1.0)) return fail(PDMP_ERR_INVALID, "rho = %g: the refreshment's autocorrelation lies in [-1, 1]", rho);
+    const int64_t d = e->cfg.d;
+    if (u_diag)
+        for (int64_t i = 0; i < d; ++i)
+            if (!(u_diag[i] > 0) || !std::isfinite(u_diag[i])) return fail(PDMP_ERR_INVALID, "u_diag[%lld] must be positive and finite", (long long)i);
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    e->bps_diag = e->bps_ident = e->bps_gamma_is_I = false;
+    e->bps_has_mass = e->bps_mass_tables = false;
+    e->bps_own_target = false;
+    e->bps_local_bound = e->bps_subsample = 0;
+    e->bps_mom = 0;
+    e->bps_sticky = false;
+    e->bps_strong = 0;
+    e->bps_lambda = lambda_ref;
+    e->bps_rho = rho;
+    e->bps_flow_kind = 0;
+    e->b_colptr.release();
+    e->b_rowval.release();
+    e->b_nzval.release();
+    e->b_mu.release();
+    e->b_mu_flow.release();
+    pdmp_status st;
+    if (u_diag) {
+        std::vector<double> u(u_diag, u_diag + d), su((size_t)d);
+        for (int64_t i = 0; i < d; ++i) su[(size_t)i] = std::sqrt(u[(size_t)i]);
+        if ((st = e->b_udiag.upload(u)) != PDMP_OK) return st;
+        if ((st = e->b_sudiag.upload(su)) != PDMP_OK) return st;
+    }
+    e->bps_modern = true;
+    e->bps_udiag = u_diag != nullptr;
+    e->bps_oscn = oscn ? 1 : 0;
+    e->bps_record_limit = 0;
+    e->has_flow = true;
+    e->has_target = false;
+    e->has_state = false;
+    return PDMP_OK;
+}
+
+pdmp_status pdmp_ensemble_set_bps_record_limit(pdmp_ensemble* e, int64_t n) {
+    if (!e) return fail(PDMP_ERR_INVALID, "null argument");
+    if (e->cfg.sampler != PDMP_SAMPLER_BPS || !e->bps_modern)
+        return fail(PDMP_ERR_INVALID, "set_bps_record_limit: pdmp_ensemble_set_flow_bps_modern first (PDMP_SAMPLER_BPS)");
+    if (n < 0) return fail(PDMP_ERR_INVALID, "record limit %lld: 0 (no limit) or a positive number of records", (long long)n);
+    e->bps_record_limit = n;
+    return PDMP_OK;
+}
+
+static pdmp::BpsModernParams bps_modern_params(const pdmp_ensemble* e) {
+    pdmp::BpsModernParams q{};
+    q.u_diag = e->bps_udiag ? e->b_udiag.p : nullptr;
+    q.su_diag = e->bps_udiag ? e->b_sudiag.p : nullptr;
+    q.mstate = e->b_mstate.p;
+    q.record_limit = e->bps_record_limit;
+    q.count_limit = e->dbg_count_limit ? e->dbg_count_limit : pdmp::PDMP_LAUNCH_COUNT_LIMIT;
+    q.oscn = e->bps_oscn;
+    return q;
 }
 
 static void fill_bps_ext(const pdmp_ensemble* e, pdmp::BpsRunParams& B) {
@@ -3001,7 +3079,23 @@ static pdmp_status init_state_bps(pdmp_ensemble* e, double t0, const double* x0,
         if (e->bps_flow_kind == 1 && e->bps_mass_tables)
             return fail(PDMP_ERR_UNSUPPORTED, "set_bps_sticky: a Boomerang with a general mass factor L (set_mass_cholesky) is not implemented: identity only");
     }
-    if (!e->bps_sticky && e->bps_flow_kind == 0 && !e->bps_gamma_is_I && !e->bps_has_mass)
+    if (e->bps_modern) {
+        // the speed-recorded driver always bounds locally and always subsamples; its options are its own
+        if (!e->bps_own_target)
+            return fail(PDMP_ERR_INVALID, "set_flow_bps_modern: the flow has no Γ of its own, pdmp_ensemble_set_target_gaussian_csc must follow it");
+        if (e->cfg.d > 1024)
+            return fail(PDMP_ERR_UNSUPPORTED, "set_flow_bps_modern keeps d <= 1024 coordinates in registers: got d = %lld", (long long)e->cfg.d);
+        if (e->bps_mom >= 1) return fail(PDMP_ERR_UNSUPPORTED, "set_flow_bps_modern: not together with set_bps_moments(order >= 1)");
+        if (e->bps_sticky) return fail(PDMP_ERR_UNSUPPORTED, "set_flow_bps_modern: not together with set_bps_sticky");
+        if (e->bps_subsample) return fail(PDMP_ERR_UNSUPPORTED, "set_flow_bps_modern: not together with subsample (set_bps_options): this driver always subsamples");
+        if (e->bps_local_bound) return fail(PDMP_ERR_UNSUPPORTED, "set_flow_bps_modern: not together with local_bound (set_bps_options): this driver always bounds locally");
+        if (e->bps_oscn && e->bps_udiag) return fail(PDMP_ERR_UNSUPPORTED, "set_flow_bps_modern: oscn with u_diag is not defined (src/not_fact_samplers.jl:267 asserts L == I)");
+        if (e->bps_oscn && e->bps_mass_tables)
+            return fail(PDMP_ERR_UNSUPPORTED, "set_flow_bps_modern: oscn with a mass factor (set_mass_cholesky) that is not the identity (src/not_fact_samplers.jl:267)");
+        if (e->bps_udiag && e->bps_has_mass) return fail(PDMP_ERR_UNSUPPORTED, "set_flow_bps_modern: u_diag together with a mass factor (set_mass_cholesky): one metric only");
+        if (!(c > 0) || !std::isfinite(c)) return fail(PDMP_ERR_INVALID, "LocalBound(c) needs a finite c > 0 (the bound expires after 2√d/c/V): got %g", c);
+    }
+    if (!e->bps_modern && !e->bps_sticky && e->bps_flow_kind == 0 && !e->bps_gamma_is_I && !e->bps_has_mass)
         return fail(PDMP_ERR_UNSUPPORTED,
                     "BouncyParticle(Γ ≠ I) carries the mass factor L = cholesky(Symmetric(Γ)).L (src/types.jl:43): pass it with "
                     "pdmp_ensemble_set_mass_cholesky (an identity factor selects the identity mass explicitly)");
@@ -3031,6 +3125,16 @@ static pdmp_status init_state_bps(pdmp_ensemble* e, double t0, const double* x0,
     // the moments start at t0 (also after set_state_bps's placement probes, which run launches in between)
     if (e->bps_mom >= 1) HIP_TRY(hipMemsetAsync(e->b_j1.p, 0, (size_t)(n * d) * sizeof(double), e->stream));
     if (e->bps_mom >= 2) HIP_TRY(hipMemsetAsync(e->b_j2.p, 0, (size_t)(n * d) * sizeof(double), e->stream));
+    if (e->bps_modern) {
+        if (e->b_mstate.n != (size_t)(n * 4) && (st = e->b_mstate.alloc((size_t)(n * 4))) != PDMP_OK) return st;
+        int rcm = pdmp::launch_bps_modern_init(B, bps_modern_params(e), n, sseed.p, t0, c, e->stream);
+        if (rcm != 0) return fail(PDMP_ERR_HIP, "bps_modern_init launch failed (%d)", rcm);
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        e->has_state = true;
+        e->ran = false;
+        e->timed = false;
+        return PDMP_OK;
+    }
     if (e->bps_sticky) {
         const size_t W = (size_t)pdmp::BPS_STICKY_WORDS;
         if (e->b_thf.n != (size_t)(n * d) && (st = e->b_thf.alloc((size_t)(n * d))) != PDMP_OK) return st;
@@ -3068,6 +3172,7 @@ pdmp_status pdmp_ensemble_set_state_bps(pdmp_ensemble* e, double t0, const doubl
     if (st != PDMP_OK) return st;
     const size_t ev_bytes = e->b_ev_th.n * sizeof(double);
     size_t freeb = 0, totb = 0;
+    if (e->bps_modern) return PDMP_OK;  // (a record per 1/λref of speed-time: the trace writes do not bound this loop, nothing to place)
     if (e->place_tune == 0 || e->cfg.trace_capacity <= 0 || ev_bytes < ((size_t)2 << 30) || e->b_ev_th.placed.va) return PDMP_OK;
     if (hipMemGetInfo(&freeb, &totb) != hipSuccess || freeb < 6 * ev_bytes + ((size_t)8 << 30)) {
         (void)hipGetLastError();

@@ -381,6 +381,18 @@ constexpr int BPS_STICKY_WORDS = 16;   // d <= 1024
 int launch_bps_sticky_init(const BpsRunParams& p, const BpsStickyParams& q, int64_t nchains, const uint64_t* seeds, double t0, double c0, void* stream);
 int launch_bps_sticky_run(const BpsRunParams& p, const BpsStickyParams& q, int64_t nchains, void* stream);
 int launch_bps_sticky_eval(int fn, int64_t n, const double* a, const double* b, const double* c, double* out, void* stream);
+// speed-recorded Bouncy Particle (pdmp_bps_modern.inc, src/not_fact_samplers.jl:151-384): what its loop keeps beside BpsRunParams' state.
+// The target is BpsRunParams' t_colptr / t_rowval / t_nzval / t_mu, the mass factor its Lcp .. Unz; scal keeps {t, a, b, t′, -, c, -, -}.
+struct BpsModernParams {
+    const double* __restrict__ u_diag;   // [d] diagonal of U, or nullptr: the L form
+    const double* __restrict__ su_diag;  // [d] sqrt(u_diag)
+    double* mstate;                      // [nchains x 4] {Δ (the bound's expiry, absolute), action (0 bounce, 1 expire, 2 refresh), V, Δrec}
+    int64_t record_limit;                // a chain stops once nevents == record_limit (0: no limit)
+    uint32_t count_limit;                // a chain whose launch has used this many draws pauses (PDMP_LAUNCH_COUNT_LIMIT, or a test's)
+    int32_t oscn;
+};
+int launch_bps_modern_init(const BpsRunParams& p, const BpsModernParams& q, int64_t nchains, const uint64_t* seeds, double t0, double c0, void* stream);
+int launch_bps_modern_run(const BpsRunParams& p, const BpsModernParams& q, int64_t nchains, void* stream);
 int launch_bps_write_probe(double* ev_x, double* ev_th, int64_t d, int64_t cap, int64_t nrec, int64_t nchains, void* stream);
 int launch_sector_probe(double* rec, int64_t d, int64_t nchains, int rounds, int write, double* sink, void* stream);
 int launch_bps_init(const BpsRunParams& p, int64_t nchains, const uint64_t* seeds, double t0, double c0, void* stream);

@@ -221,6 +221,29 @@ class Ensemble:
         k = np.ascontiguousarray(np.broadcast_to(np.asarray(kappa, dtype=np.float64), (self.d,)))
         _lib.check(self._L.pdmp_ensemble_set_bps_sticky(self._h, _ptr(k), int(bool(strong_upperbounds))))
 
+    def set_flow_bps_modern(self, lambda_ref, rho=0.0, u_diag=None, oscn=False):
+        """The speed-recorded Bouncy Particle, pdmp(dϕ, ∇ϕ!, ..., c::LocalBound, flow::BouncyParticle; oscn) (src/not_fact_samplers.jl:151-384):
+        u_diag None = the L form (V ≡ 1; set_mass_cholesky may follow), [d] > 0 = the diagonal-U form.  set_target (a Gaussian) must follow
+        (pdmp_ensemble_set_flow_bps_modern)."""
+        u = None if u_diag is None else _f64(u_diag).reshape(self.d)
+        _lib.check(self._L.pdmp_ensemble_set_flow_bps_modern(self._h, float(lambda_ref), float(rho), _ptr(u), int(bool(oscn))))
+        self._bps_mom = 0
+
+    def set_mass_cholesky(self, L):
+        """The lower-triangular mass factor L of a BouncyParticle / Boomerang as a sparse matrix (pdmp_ensemble_set_mass_cholesky)."""
+        import scipy.sparse as sp
+        L = sp.csc_matrix(L)
+        L.sort_indices()
+        if L.shape != (self.d, self.d):
+            raise ValueError("mass factor L has the wrong shape")
+        cp, rv, nz = _i64(L.indptr), _i64(L.indices), _f64(L.data)
+        _lib.check(self._L.pdmp_ensemble_set_mass_cholesky(self._h, _ptr(cp), _ptr(rv), _ptr(nz)))
+
+    def set_bps_record_limit(self, n):
+        """`T::Int` of the speed-recorded driver: a chain stops once it holds n records (0: no limit); may be raised between runs
+        (pdmp_ensemble_set_bps_record_limit)."""
+        _lib.check(self._L.pdmp_ensemble_set_bps_record_limit(self._h, int(n)))
+
     def bps_trace_free(self, chain, first=0, count=None, counters=None):
         """f of events [first, first + count) of one chain of a sticky ensemble: [count x d] bool (pdmp_ensemble_bps_trace_free_copy)."""
         if counters is None:

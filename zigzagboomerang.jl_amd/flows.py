@@ -81,14 +81,25 @@ def cholesky_lower(Γ):
 class BouncyParticle:
     """BouncyParticle(Γ, μ, λ; ρ=0.0) -- src/types.jl:35-45.  L is the mass factor the reference stores in the struct
     (`cholesky(Symmetric(Γ)).L`, :43): computed here when not given (None and Γ = I: identity); the 6-field constructor
-    BouncyParticle(Γ, μ, λ, ρ, U, L) of the reference corresponds to passing `L=` explicitly."""
-    Γ: sp.csc_matrix
-    μ: np.ndarray
+    BouncyParticle(Γ, μ, λ, ρ, U, L) of the reference corresponds to passing `L=` (or `U=`) explicitly.
+    Γ = None, μ = None is the reference's BouncyParticle(missing, missing, λ, ρ, U, L) of the speed-recorded driver
+    (src/not_fact_samplers.jl:336-384): L stays as given (None: identity), U is the diagonal of a PDiagMat metric ([d] > 0) or None."""
+    Γ: Optional[sp.csc_matrix]
+    μ: Optional[np.ndarray]
     λref: float
     ρ: float = 0.0
     L: Optional[sp.csc_matrix] = None
+    U: Optional[np.ndarray] = None
 
     def __post_init__(self):
+        if self.U is not None:
+            self.U = np.ascontiguousarray(self.U, dtype=np.float64)
+        if self.Γ is None:
+            if self.μ is not None:
+                raise ValueError("BouncyParticle(missing, missing, ...): μ is given without Γ")
+            if self.L is not None:
+                self.L = _csc(self.L)
+            return
         self.Γ = _csc(self.Γ)
         self.μ = np.ascontiguousarray(self.μ, dtype=np.float64)
         if self.L is None:

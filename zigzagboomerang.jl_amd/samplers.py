@@ -64,19 +64,19 @@ def spdmp(target, t0, x0, θ0, T, c, *GF, factor=1.8, adapt=False, adaptscale=Fa
                    adaptscale=adaptscale, tracked=tracked, G=G)
 
 
-def pdmp(target, *args, factor=1.8, adapt=False, subsample=False, seed=DEFAULT_SEED, device=0, trace_capacity=None, trace=True,
-         moments=False):
+def pdmp(target, *args, factor=1.8, adapt=False, subsample=None, seed=DEFAULT_SEED, device=0, trace_capacity=None, trace=True,
+         moments=False, oscn=False):
     """pdmp(∇ϕ, t0, x0, θ0, T, c, F, ...) -- the d-dimensional drivers, see _pdmp_nd -- or, with a 1-d flow as the sixth argument,
     pdmp(∇ϕ, x, θ, T, c, Flow::Union{ZigZag1d, Boomerang1d}; adapt=false, factor=2.0) -> Ξ, acc/num  (src/zigzagboom1d.jl:34-67)."""
     if len(args) == 5 and isinstance(args[4], (ZigZag1d, Boomerang1d)):
-        if subsample or moments:
+        if subsample or moments or oscn:
             raise TypeError("subsample and moments are keywords of the non-factorised pdmp (BouncyParticle / Boomerang)")
         x0, θ0, T, c, Flow = args
         return _pdmp_1d(target, x0, θ0, T, c, Flow, 2.0 if factor == 1.8 else factor, adapt, seed, device, trace_capacity)
     if len(args) != 6:
         raise TypeError("expected pdmp(target, t0, x0, θ0, T, c, F, ...) or pdmp(target, x, θ, T, c, Flow1d, ...)")
     return _pdmp_nd(target, *args, factor=factor, adapt=adapt, subsample=subsample, seed=seed, device=device, trace_capacity=trace_capacity,
-                    trace=trace, moments=moments)
+                    trace=trace, moments=moments, oscn=oscn)
 
 
 def _pdmp_1d(target, x0, θ0, T, c, Flow, factor, adapt, seed, device, trace_capacity):
@@ -116,8 +116,8 @@ def _pdmp_1d(target, x0, θ0, T, c, Flow, factor, adapt, seed, device, trace_cap
     return (Ξ[0], float(ratio[0])) if scalar else (Ξ, ratio)
 
 
-def _pdmp_nd(target, t0, x0, θ0, T, c, F, *, factor=1.8, adapt=False, subsample=False, seed=DEFAULT_SEED, device=0,
-             trace_capacity=None, trace=True, moments=False):
+def _pdmp_nd(target, t0, x0, θ0, T, c, F, *, factor=1.8, adapt=False, subsample=None, seed=DEFAULT_SEED, device=0,
+             trace_capacity=None, trace=True, moments=False, oscn=False):
     """pdmp(∇ϕ, t0, x0, θ0, T, c, F::ZigZag, args...) = spdmp(..., All(), ...) (src/sfact.jl:236): every proposal moves
     ALL coordinates (no sparsity assumption on ∇ϕ); same return value as spdmp.
 
@@ -129,7 +129,26 @@ def _pdmp_nd(target, t0, x0, θ0, T, c, F, *, factor=1.8, adapt=False, subsample
 
     moments=True (BouncyParticle / Boomerang, engine-only keyword): a fifth element dict(mean, var, T) -- the exact time averages
     ∫x dt/(T − t0) and ∫x² dt/(T − t0) − mean² over [t0, T] kept by the event loop (pdmp_ensemble_set_bps_moments), [n x d] or [d]; the
-    first four elements are bit for bit those of moments=False.  With trace=False no event is written at all."""
+    first four elements are bit for bit those of moments=False.  With trace=False no event is written at all.
+
+    pdmp(dϕ, ∇ϕ!, t0, x0, θ0, T, c::LocalBound, B::BouncyParticle; oscn=false, adapt=false, factor=2.0) (src/not_fact_samplers.jl:336-384),
+    the speed-recorded driver: B.Γ is None (BouncyParticle(None, None, λref, ρ, L=..., U=...)), target is a GaussianTarget (dϕ and ∇ϕ! are
+    its two directional derivatives and its gradient), c a LocalBound.  An integer T is a number of samples, a float an end time.  The
+    trace holds one record per 1/λref of speed-time and does not begin with (t0, x0, θ0); subsample defaults to True here and
+    subsample=False raises the reference's ArgumentError (:338)."""
+    if isinstance(F, BouncyParticle) and F.Γ is None:
+        if not isinstance(target, GaussianTarget):
+            raise TypeError("BouncyParticle(missing, missing, ...): target must be a GaussianTarget (dϕ, ∇ϕ! of Γt(x − μt))")
+        if not isinstance(c, LocalBound):
+            raise TypeError("pdmp(dϕ, ∇ϕ!, ..., c::LocalBound, flow::BouncyParticle): pass c as LocalBound(c)")
+        if subsample is not None and not subsample:
+            raise ValueError("`subsample=true` required.")  # ArgumentError, :338
+        if moments:
+            raise TypeError("moments is a keyword of the event-recorded pdmp (a BouncyParticle with a Γ, or a Boomerang)")
+        return _bps_modern(target, t0, x0, θ0, T, c, F, 2.0 if factor == 1.8 else factor, adapt, seed, device, trace_capacity, trace, oscn)
+    if oscn:
+        raise TypeError("oscn is a keyword of the speed-recorded pdmp (BouncyParticle(None, None, ...), c::LocalBound)")
+    subsample = bool(subsample)
     if isinstance(F, BouncyParticle):
         if target is not None and not isinstance(target, GaussianTarget):
             raise TypeError("BouncyParticle: target is None (∇ϕ!(y, x) = B.Γ(x − B.μ)) or a GaussianTarget of its own")
@@ -352,6 +371,66 @@ def _zigzag(sampler, target, t0, x0, θ0, T, c, F, factor, adapt, seed, device, 
     if single:
         return traces[0], (fs["t"][0], fs["x"][0], fs["theta"][0]), (acc[0], int(num[0])), c_out[0]
     return traces, (fs["t"], fs["x"], fs["theta"]), (acc, num), c_out
+
+
+def _bps_modern(target, t0, x0, θ0, T, c, B, factor, adapt, seed, device, trace_capacity, trace, oscn):
+    """The speed-recorded Bouncy Particle on the device (pdmp_ensemble_set_flow_bps_modern): one chain per row of x0."""
+    c = float(np.asarray(c.c, dtype=np.float64).reshape(-1)[0])
+    x0 = np.asarray(x0, dtype=np.float64)
+    θ0 = np.asarray(θ0, dtype=np.float64)
+    single = x0.ndim == 1
+    X0, TH0 = np.atleast_2d(x0), np.atleast_2d(θ0)
+    nch, d = X0.shape
+    seeds = (np.uint64(seed) + np.arange(nch, dtype=np.uint64)) if np.isscalar(seed) else np.asarray(seed, np.uint64)
+    count = isinstance(T, (int, np.integer)) and not isinstance(T, bool)  # `T isa Int`: a number of samples
+    if count and T < 0:
+        raise ValueError("a sample count T must not be negative")
+    if trace_capacity is None:
+        want = int(T) if count else int(4 * B.λref * max(float(T) - t0, 1.0))
+        trace_capacity = int(min(max(64, want), (1 << 28) // max(2 * d, 1)))
+    cap = trace_capacity if trace else 0
+    ens = Ensemble(nch, d, sampler=_lib.SAMPLER_BPS, adapt=adapt, factor=factor, device=device, trace_capacity=cap)
+    ts, xs, ths = [[] for _ in range(nch)], [[] for _ in range(nch)], [[] for _ in range(nch)]
+    try:
+        ens.set_flow_bps_modern(B.λref, B.ρ, B.U, oscn)
+        ens.set_target(target)
+        if B.L is not None:
+            ens.set_mass_cholesky(B.L)
+        ens.set_state_bps(t0, X0, TH0, c, seeds)
+        if count:
+            ens.set_bps_record_limit(int(T))
+        T_end = float("inf") if count else float(T)
+        while not (count and int(T) == 0):
+            ens.run(T_end, _lib.RUN_REFERENCE_TAIL)
+            cnt = ens.counters()
+            if np.any(cnt["status"] == _lib.CHAIN_BOUND_VIOLATED):
+                raise RuntimeError("Tuning parameter `c` too small.")  # :230, :262
+            if np.any(cnt["status"] == _lib.CHAIN_STALLED):
+                raise AssertionError("Δrec > 0.0")  # :239
+            if trace:
+                for k in range(nch):
+                    if cnt["ntrace"][k]:
+                        a, b_, c_ = ens.bps_trace(k, counters=cnt)
+                        ts[k].append(a)
+                        xs[k].append(b_)
+                        ths[k].append(c_)
+                ens.trace_reset()
+            if not _lib.needs_rerun(cnt["status"]):
+                break
+        fs = ens.bps_final_state()
+        cnt = ens.counters()
+    finally:
+        ens.close()
+    traces = []
+    for k in range(nch):
+        if ts[k]:
+            traces.append(PDMPTrace(B, t0, X0[k].copy(), TH0[k].copy(), np.concatenate(ts[k]), np.concatenate(xs[k]), np.concatenate(ths[k])))
+        else:
+            traces.append(PDMPTrace(B, t0, X0[k].copy(), TH0[k].copy(), np.empty(0), np.empty((0, d)), np.empty((0, d))))
+    acc, num = cnt["nacc"].astype(np.int64), cnt["num"].astype(np.int64)
+    if single:
+        return traces[0], (fs["t"][0], fs["x"][0], fs["theta"][0]), (int(acc[0]), int(num[0])), fs["c"][0]
+    return traces, (fs["t"], fs["x"], fs["theta"]), (acc, num), fs["c"]
 
 
 def _bps(t0, x0, θ0, T, c, B, factor, adapt, seed, device, trace_capacity, trace, target=None, subsample=False, moments=False, sticky=None):
