@@ -7,7 +7,12 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
+import bps_width_cases as BW
+
 pytestmark = pytest.mark.gpu
+
+
+WIDTHS = (129, 256, 257, 513)  # NS = 4 and 8 with empty trailing slots, FULL of NS = 4, NS = 16 with seven empty slots
 
 
 def _case(pkg, name, d, rng):
@@ -21,7 +26,10 @@ def _case(pkg, name, d, rng):
     if name == "diag":  # Γ = I, μ ≠ 0: diagonal, not IDENT
         B = pkg.BouncyParticle(I, rng.standard_normal(d), 1.0)
         return (lambda e: e.set_flow_bps(B)), 1e-3, False, B, {}
-    G = pkg.problems.gmrf_precision(int(round(np.sqrt(d)))) if d >= 64 else pkg.problems.maintest_precision(d)
+    if d in WIDTHS:  # no square: the Γ of the slot-count matrix (tests/bps_width_cases.py), which couples slots and lanes
+        G = BW.coupling_gamma(d)
+    else:
+        G = pkg.problems.gmrf_precision(int(round(np.sqrt(d)))) if d >= 64 else pkg.problems.maintest_precision(d)
     if name == "csc":  # general Γ with the identity mass: the CSC gather without the extended instantiation
         B = pkg.BouncyParticle(G, z, 0.7, L=I)
         return (lambda e: e.set_flow_bps(B)), 1.0, False, B, {}
@@ -108,6 +116,7 @@ def _check_against_host(pkg, traces, moms, d):
 CASES = [("iso", 1), ("iso", 63), ("iso", 64), ("iso", 100), ("iso", 1024), ("iso", 4096), ("diag", 100), ("diag", 1024),
          ("csc", 8), ("csc", 100), ("mass", 8), ("mass", 100), ("own_target", 100), ("adapt", 100), ("local", 100), ("subsample", 100),
          ("boom_diag", 8), ("boom_diag", 1024), ("boom_csc", 100), ("boom_mass", 100)]
+CASES += [(name, d) for d in WIDTHS for name in ("iso", "csc", "mass", "boom_csc")]  # the moment-keeping forms at 4, 8 and 16 slots per lane
 
 
 @pytest.mark.parametrize("name,d", CASES)

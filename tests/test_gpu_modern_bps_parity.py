@@ -30,11 +30,11 @@ def tridiag(d):
     return sp.csc_matrix(G)
 
 
-def problem(d, seed, form="I", L=None, oscn=False, rho=0.9, lam=1.0, nch=3, gamma=None):
+def problem(d, seed, form="I", L=None, oscn=False, rho=0.9, lam=1.0, nch=3, gamma=None, t0=0.0):
     """form "I": the L form with L = I; "L": the L form with the factor L; "U": the diagonal-U form with a non-constant u."""
     rng = np.random.default_rng(seed)
     P = dict(d=d, G=tridiag(d) if gamma is None else gamma, mu=0.3 * rng.standard_normal(d), form=form, L=L if form == "L" else None,
-             u=(0.5 + rng.random(d) * 1.5) if form == "U" else None, oscn=oscn, rho=rho, lam=lam,
+             u=(0.5 + rng.random(d) * 1.5) if form == "U" else None, oscn=oscn, rho=rho, lam=lam, t0=t0,
              x0=rng.standard_normal((nch, d)), th0=rng.standard_normal((nch, d)), seeds=np.uint64(1000 + seed) + np.arange(nch, dtype=np.uint64))
     return P
 
@@ -42,7 +42,7 @@ def problem(d, seed, form="I", L=None, oscn=False, rho=0.9, lam=1.0, nch=3, gamm
 def ref_runs(P, T, c, adapt=False, factor=2.0, chains=None):
     out = []
     for k in (range(len(P["x0"])) if chains is None else chains):
-        out.append(M.pdmp(0.0, P["x0"][k], P["th0"][k], T, c, gamma=P["G"], mu=P["mu"], lambda_ref=P["lam"], rho=P["rho"], L=P["L"],
+        out.append(M.pdmp(P["t0"], P["x0"][k], P["th0"][k], T, c, gamma=P["G"], mu=P["mu"], lambda_ref=P["lam"], rho=P["rho"], L=P["L"],
                           u_diag=P["u"], oscn=P["oscn"], adapt=adapt, factor=factor, seed=int(P["seeds"][k]), ev_cap=4096))
     return out
 
@@ -55,7 +55,7 @@ def open_ensemble(pkg, P, c, cap=64, adapt=False, factor=2.0):
         ens.set_target(pkg.GaussianTarget(P["G"], P["mu"]))
         if P["L"] is not None:
             ens.set_mass_cholesky(sp.csc_matrix(np.tril(P["L"])) if not sp.issparse(P["L"]) else P["L"])
-        ens.set_state_bps(0.0, P["x0"], P["th0"], c, P["seeds"])
+        ens.set_state_bps(P["t0"], P["x0"], P["th0"], c, P["seeds"])
     except Exception:
         ens.close()
         raise
@@ -121,9 +121,10 @@ def one_run(pkg, P, n, c, adapt=False, factor=2.0, cap=64):
 
 
 @pytest.mark.parametrize("form", ["I", "U"])
-@pytest.mark.parametrize("d", [1, 7, 64, 100, 1024])
+@pytest.mark.parametrize("d", [1, 7, 64, 100, 129, 257, 1024])
 def test_every_width_and_tail(gpu_pkg, d, form):
-    """1, 2 and 16 slots per lane, full and partial last slots, a tridiagonal target with a mean: 40 records of 3 chains."""
+    """1, 2 and 16 slots per lane, full and partial last slots, and 4 and 8 with wholly empty trailing slots (d = 129, 257); a tridiagonal target
+    with a mean: 40 records of 3 chains.  Every slot count with a Γ that couples slots, `oscn` and a factor: tests/test_gpu_bps_widths.py."""
     P = problem(d, d, form=form, rho=0.9 if d != 64 else 0.0)
     c = 5.0
     refs = ref_runs(P, 40, c)

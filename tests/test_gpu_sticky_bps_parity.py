@@ -46,14 +46,15 @@ def problem(pkg, flow, d, seed, gamma="I", own_target=False, rho=0.0, lam=0.8):
     return P
 
 
-def ref_run(P, x0, th0, T, c, kappa, seed, strong=False, adapt=False, factor=2.0):
+def ref_run(P, x0, th0, T, c, kappa, seed, strong=False, adapt=False, factor=2.0, t0=0.0):
+    """kappa: a scalar or one value per coordinate."""
     kw = dict(flow_kind=0 if P["flow"] == "bps" else 1, gamma=P["G"], mu=P["mu"], lambda_ref=P["lam"], rho=P["rho"], strong_upperbounds=strong,
               adapt=adapt, factor=factor, seed=seed, ev_cap=400000)
     if P["flow"] == "bps":
         kw["target"] = P["target"]
     else:
         kw["mu_flow"] = P["mu_flow"]
-    return R.sspdmp_notfact(0.0, x0, th0, T, c, kappa, **kw)
+    return R.sspdmp_notfact(t0, x0, th0, T, c, kappa, **kw)
 
 
 def dev_target(pkg, P):
@@ -62,18 +63,20 @@ def dev_target(pkg, P):
     return None if P["target"] is None else pkg.GaussianTarget(P["target"][0], P["target"][1])
 
 
-def check(pkg, P, T, c, kappa, nch=2, seed=5, strong=False, adapt=False, trace_capacity=None):
+def check(pkg, P, T, c, kappa, nch=2, seed=5, strong=False, adapt=False, trace_capacity=None, t0=0.0, state=None, refs=None):
     """The Python sspdmp against the restatement: events (t, x, θ, f), (acc, num), final (t, x, θ, c).  Then the same chains on an ensemble
-    of their own (check_counters_and_final): nrefresh, ndraw_main, nevents, final f and θf, which sspdmp does not return."""
+    of their own (check_counters_and_final): nrefresh, ndraw_main, nevents, final f and θf, which sspdmp does not return.
+    kappa: a scalar or [d]; state: (x0, θ0), each [nch x d], instead of the seeded draw; refs: the restatement's runs where the caller has them."""
     d = P["d"]
     rng = np.random.default_rng(seed)
-    x0, th0 = rng.standard_normal((nch, d)), rng.standard_normal((nch, d))
-    tr, (t, x, th), (acc, num), cout = pkg.sspdmp(dev_target(pkg, P), 0.0, x0, th0, T, c, P["F"], kappa, strong_upperbounds=strong, adapt=adapt,
+    x0, th0 = (rng.standard_normal((nch, d)), rng.standard_normal((nch, d))) if state is None else state
+    nch = x0.shape[0]
+    tr, (t, x, th), (acc, num), cout = pkg.sspdmp(dev_target(pkg, P), t0, x0, th0, T, c, P["F"], kappa, strong_upperbounds=strong, adapt=adapt,
                                                   seed=seed, trace_capacity=trace_capacity)
     nfz = 0
-    refs = []
+    given, refs = refs, []
     for k in range(nch):
-        r = ref_run(P, x0[k], th0[k], T, c, kappa, seed + k, strong=strong, adapt=adapt)
+        r = ref_run(P, x0[k], th0[k], T, c, kappa, seed + k, strong=strong, adapt=adapt, t0=t0) if given is None else given[k]
         refs.append(r)
         assert r["status"] == R.REF_OK and r["nevents"] == len(r["t"])
         assert len(tr[k].t) == r["nevents"], (k, len(tr[k].t), r["nevents"])
@@ -82,18 +85,18 @@ def check(pkg, P, T, c, kappa, nch=2, seed=5, strong=False, adapt=False, trace_c
         assert (int(acc[k]), int(num[k])) == (r["nacc"], r["num"])
         assert t[k] == r["t_final"] and same(x[k], r["x_final"]) and same(th[k], r["theta_final"]) and cout[k] == r["c_final"]
         nfz += int((~r["f"]).any(1).sum())
-    check_counters_and_final(pkg, P, T, c, kappa, x0, th0, seed, strong, adapt, refs)
+    check_counters_and_final(pkg, P, T, c, kappa, x0, th0, seed, strong, adapt, refs, t0=t0)
     return tr, nfz
 
 
-def check_counters_and_final(pkg, P, T, c, kappa, x0, th0, seed, strong, adapt, refs):
+def check_counters_and_final(pkg, P, T, c, kappa, x0, th0, seed, strong, adapt, refs, t0=0.0):
     """The chains of check() once more on an Ensemble (seeds seed + k as sspdmp gives them): every counter the restatement keeps, the final
     state, the final free mask and the saved speeds θf, bit for bit; a frozen coordinate carries θf ≠ 0 and a free one θf = 0."""
     L = pkg._lib
     nch, d = x0.shape
     with raw_ensemble(pkg, P, nch, 4096, adapt=adapt) as ens:
         ens.set_bps_sticky(kappa, strong)
-        ens.set_state_bps(0.0, x0, th0, c, np.uint64(seed) + np.arange(nch, dtype=np.uint64))
+        ens.set_state_bps(t0, x0, th0, c, np.uint64(seed) + np.arange(nch, dtype=np.uint64))
         for _ in range(100000):
             ens.run(T, L.RUN_REFERENCE_TAIL)
             cnt = ens.counters()
@@ -113,10 +116,11 @@ def check_counters_and_final(pkg, P, T, c, kappa, x0, th0, seed, strong, adapt, 
         assert np.all(fin["theta_f"][k][~fin["f"][k]] != 0) and np.all(fin["theta_f"][k][fin["f"][k]] == 0)
 
 
-@pytest.mark.parametrize("d", [1, 7, 64, 100, 1024])
+@pytest.mark.parametrize("d", [1, 7, 64, 100, 129, 257, 1024])
 @pytest.mark.parametrize("flow", ["bps", "boom"])
 def test_identity_precision_every_width(gpu_pkg, flow, d):
-    """Γ = I at every slot count (1, 2 and 16 slots per lane, partial last slot); κ = 1.5 so that coordinates freeze and thaw all the time."""
+    """Γ = I at 1, 2 and 16 slots per lane (partial last slot), and at 4 and 8 with wholly empty trailing slots (d = 129, 257); κ = 1.5 so that
+    coordinates freeze and thaw all the time.  Every slot count with a Γ that couples slots: tests/test_gpu_bps_widths.py."""
     P = problem(gpu_pkg, flow, d, 100 + d, rho=0.0 if d % 2 else 0.95)
     T = 20.0 if d <= 100 else 3.0
     # (Γ = I makes the BouncyParticle's bound exact: no adaptation needed; the Boomerang's c adapts to |μ_flow − μ_target|)
