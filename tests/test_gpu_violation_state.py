@@ -54,3 +54,29 @@ def test_violation_state_small_lattice(gpu_pkg, monkeypatch, sticky):
             r = O.spdmp_zigzag(0.4 * G, None, G, x0[k], th0[k], c, 50.0, seed=300 + int(k))
         assert r["status"] != 0 and int(cnt_s["num"][k]) == r["num"] and len(ev_s[k]) == len(r["events"])
         assert np.array_equal(fs_s["x"][k], r["x"]) and np.array_equal(fs_s["t"][k], r["t"])
+
+
+@pytest.mark.parametrize("name", ["a", "d"])
+def test_violation_state_logistic(gpu_pkg, name):
+    """The same for the logistic target of config C4 (tests/logistic_cases.py, cases a and d at a uniform c where chains are violated late --
+    tests/test_logistic_cases_ref.py checks that c): the LDS-resident kernel, the kernel with its records in HBM and the oracle."""
+    import logistic_cases as LC
+    pkg = gpu_pkg
+    P = LC.violation_problem(name)
+    refs = LC.violation_refs(name)
+    LC.guard_violation(refs)
+    lds = LC.device_run(pkg, P, adapt=False)
+    hbm = LC.device_run(pkg, P, adapt=False, kernel="seq")
+    assert (lds["kernel"], hbm["kernel"]) == (LC.LDS_KERNEL, LC.GENERAL_KERNEL)
+    cnt = lds["cnt"]
+    assert np.array_equal(cnt["status"], [r["status"] for r in refs])  # (CHAIN_OK / CHAIN_BOUND_VIOLATED are the oracle's 0 / 1)
+    for f in ("status", "num", "nacc", "nevents", "ndraw_main", "t_last"):
+        assert np.array_equal(cnt[f], hbm["cnt"][f]), f
+    for k in range(LC.VIOLATION_NCH):
+        assert np.array_equal(lds["evs"][k], hbm["evs"][k]), k
+    for f in ("t", "x", "theta"):
+        assert np.array_equal(lds["fs"][f], hbm["fs"][f]), f
+    for k in np.flatnonzero(cnt["status"] == pkg._lib.CHAIN_BOUND_VIOLATED):
+        r = refs[k]
+        assert r["status"] == O.ORC_BOUND_VIOLATED and int(cnt["num"][k]) == r["num"] and len(lds["evs"][k]) == len(r["events"])
+        assert np.array_equal(lds["fs"]["x"][k], r["x"]) and np.array_equal(lds["fs"]["t"][k], r["t"])
