@@ -26,6 +26,7 @@ HEADERS = [os.path.join(CSRC, "pdmp_engine.hpp"),
            os.path.join(CSRC, "pdmp_device.hpp"),  # (the scalar and wave-level helpers every event-loop unit shares)
            os.path.join(CSRC, "pdmp_spec8_common.hpp"),  # (the 8-event loop's machinery, shared by pdmp_kernels.hip's three kernels of it)
            os.path.join(CSRC, "pdmp_spec8g.inc"),  # (included by pdmp_kernels.hip)
+           os.path.join(CSRC, "pdmp_bps_common.hpp"),  # (the Bouncy Particle family's wave-level machinery, shared by pdmp_bps.hip's six kernels)
            os.path.join(CSRC, "pdmp_bps_sticky.inc"),  # (included by pdmp_bps.hip)
            os.path.join(CSRC, "pdmp_bps_modern.inc"),  # (included by pdmp_bps.hip)
            os.path.join(PKG_DIR, "..", "include", "pdmp_mi355.h"),

@@ -15,24 +15,13 @@
 #include <cstdint>
 
 #include "../../include/pdmp_detmath.h"
+#include "pdmp_bps_common.hpp"  // wave_sum_f64, the layout's primitives (BpsWave), the header helpers, the slot-count dispatcher
 #include "pdmp_device.hpp"
 #include "pdmp_engine.hpp"
 
 namespace pdmp {
 
-// all-lanes sum in the oracle's order: xor 1, 2 (quads), 4, 8 (row of 16), then (r0+r1)+(r2+r3)
-__device__ __forceinline__ double wave_sum_f64(double v) {
-    v = v + dpp_f64<0xB1>(v);   // lane ^ 1
-    v = v + dpp_f64<0x4E>(v);   // lane ^ 2
-    v = v + dpp_f64<0x141>(v);  // other quad of the half row (same value in every lane of a quad: == lane ^ 4)
-    v = v + dpp_f64<0x140>(v);  // other half row (== lane ^ 8)
-    const double r0 = readlane_f64(v, 0), r1 = readlane_f64(v, 16), r2 = readlane_f64(v, 32), r3 = readlane_f64(v, 48);
-    return (r0 + r1) + (r2 + r3);  // lane ^ 16, then lane ^ 32
-}
-
-// IDENT: Γ = I and μ = 0 exactly (config C2, the isotropic target): ∇ϕ!(y, x) = 0 + 1·(x − 0) is x itself, so the gradient array,
-// μ and the diagonal leave the register file (256 -> about 100 VGPRs at NS = 16: 1 -> 4 waves per SIMD) and Γθ = θ.
-// t′ − t = poisson_time(a, b, rand(rng)) behind a call as well (log polynomial, two divisions, sqrt: constants and temporaries)
+// t′ − t = poisson_time(a, b, rand(rng)) behind a call (log polynomial, two divisions, sqrt: constants and temporaries)
 __device__ __attribute__((noinline)) double bps_next_dt(uint64_t seed, uint64_t n, double a, double b) {
     return poisson_time(a, b, pdmp_u01(seed, PDMP_STREAM_MAIN, n));
 }
@@ -56,14 +45,20 @@ __device__ __forceinline__ void bps_seg_moments(double x, double th, double m, d
     }
 }
 
+// IDENT: Γ = I and μ = 0 exactly (config C2, the isotropic target): ∇ϕ!(y, x) = 0 + 1·(x − 0) is x itself, so the gradient array,
+// μ and the diagonal leave the register file (DESIGN.md §4 has the register counts) and Γθ = θ.
 // FULL: d == 64 NS exactly, so the `element < d` guards (and their exec-mask bookkeeping) are compile-time true.
 // EXT: the extended instantiation (general Γ only) adds what the fast ones leave out -- a caller-supplied mass factor L
 // (reflect!, refresh!, Boomerang's grad_correct!: column-oriented substitution through LDS, the order oracle/pdmp_oracle.c
-// fixes), c::LocalBound with its horizon and the renew branch (src/not_fact_samplers.jl:29-31,65-71), and `subsample` (:90).
+// fixes), c::LocalBound with its horizon and the renew branch
+// (src/not_fact_samplers.jl:29-31,65-71), and `subsample` (:90).
 // MOM (path moments, pdmp_ensemble_set_bps_moments): 0 none; 1 J1 = ∫x ds, 2 also J2 = ∫x² ds, per element from the chain's t0, kept in
 // registers beside x and θ and advanced in move() by the closed form of the segment (bps_seg_moments).  They never feed back into the
 // chain: with MOM > 0 the events, counters and state are bit for bit those of MOM = 0.
 // (Mom: one BpsMomParams where MOM > 0, nothing where MOM = 0)
+// This kernel writes the layout's primitives out itself (dot, the staging and gather, the substitutions, the Box-Muller fill) instead of
+// calling BpsWave's: it is the one kernel of the family compiled at NS = 32 and 64, where the register file is full and every change of its
+// text, a one-line wrapper included, moves scratch and spills up in some instantiation.
 __device__ __forceinline__ BpsMomParams bps_mom_arg(BpsMomParams m) { return m; }
 template <int NS, bool DIAG, bool BOOM, bool IDENT, bool FULL = false, bool EXT = false, int MOM = 0, class... Mom>
 __global__ __launch_bounds__(64) void bps_run_kernel(BpsRunParams P, Mom... M) {
@@ -71,7 +66,7 @@ __global__ __launch_bounds__(64) void bps_run_kernel(BpsRunParams P, Mom... M) {
     const int64_t chain = blockIdx.x;
     const int64_t d = P.d;
     extern __shared__ __align__(16) unsigned char smem[];
-    double* tmp = reinterpret_cast<double*>(smem);  // [d] operand of the CSC gather (general Γ); the normals of a refresh
+    double* tmp = reinterpret_cast<double*>(smem);
 
     double* gx = P.x + chain * d;
     double* gth = P.th + chain * d;
@@ -364,7 +359,7 @@ __global__ __launch_bounds__(64) void bps_run_kernel(BpsRunParams P, Mom... M) {
             // refresh!, src/dynamics.jl:112-118 with L = I: θ .*= ρ; θ .+= ρ̄ randn(rng, d)  (draw nm + e for element e)
             // The d normals go through LDS: a ROLLED loop holds one Box-Muller body (its constants and temporaries are live only
             // here, next to x and θ), the unrolled update then reads them back -- 16 inlined bodies, or a call, cost ~40 VGPRs
-            // across the whole event loop (161 -> 123 at NS = 16: 3 -> 4 waves per SIMD).
+            // across the whole event loop.
             // (element 128a + 64b + lane is Box-Muller branch b of block nm + 64a + lane: one evaluation serves two slots)
             asm volatile("" ::: "memory");
 #pragma unroll 1
@@ -529,6 +524,7 @@ __global__ __launch_bounds__(64) void bps_init_kernel(BpsRunParams P, const uint
     const int64_t d = P.d;
     extern __shared__ __align__(16) unsigned char smem[];
     double* tmp = reinterpret_cast<double*>(smem);
+    const BpsWave<NS> wv{lane, d, tmp};
     const double* gx = P.x + chain * d;
     const double* gth = P.th + chain * d;
     const uint64_t seed = seeds[chain];
@@ -540,49 +536,11 @@ __global__ __launch_bounds__(64) void bps_init_kernel(BpsRunParams P, const uint
         th[s] = (e < d) ? gth[e] : 0.0;
     }
     auto apply_gamma = [&](const double (&in)[NS], bool sub_mu, double (&out)[NS]) {
-        asm volatile("" ::: "memory");
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const int64_t e = (int64_t)s * 64 + lane;
-            if (e < d) tmp[e] = sub_mu ? (in[s] - P.mu[e]) : in[s];
-        }
-        asm volatile("" ::: "memory");
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const int64_t e = (int64_t)s * 64 + lane;
-            double y = 0.0;
-            if (e < d) {
-                for (int64_t p = P.colptr[e]; p < P.colptr[e + 1]; ++p) y += P.nzval[p] * tmp[P.rowval[p]];
-            }
-            out[s] = y;
-        }
+        wv.csc_gather(P.colptr, P.rowval, P.nzval, P.mu, in, sub_mu, out);
     };
-    auto dot = [&](const double (&u)[NS], const double (&v)[NS]) -> double {
-        double part = 0.0;
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const int64_t e = (int64_t)s * 64 + lane;
-            if (e < d) part += u[s] * v[s];
-        }
-        return wave_sum_f64(part);
-    };
+    auto dot = [&](const double (&u)[NS], const double (&v)[NS]) -> double { return wv.dot(u, v); };
     auto apply_target = [&](const double (&in)[NS], bool sub_mu, double (&out)[NS]) {  // the ensemble's own target Γt, μt
-        asm volatile("" ::: "memory");
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const int64_t e = (int64_t)s * 64 + lane;
-            if (e < d) tmp[e] = sub_mu ? (in[s] - P.t_mu[e]) : in[s];
-        }
-        asm volatile("" ::: "memory");
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const int64_t e = (int64_t)s * 64 + lane;
-            double y = 0.0;
-            if (e < d) {
-                for (int64_t p = P.t_colptr[e]; p < P.t_colptr[e + 1]; ++p) y += P.t_nzval[p] * tmp[P.t_rowval[p]];
-            }
-            out[s] = y;
-        }
+        wv.csc_gather(P.t_colptr, P.t_rowval, P.t_nzval, P.t_mu, in, sub_mu, out);
     };
     const bool own_target = !BOOM && P.t_colptr != nullptr;
     const double tau_ref = -pdmp_log(pdmp_u01(seed, PDMP_STREAM_MAIN, 0)) / P.lambda_ref;  // :121
@@ -591,11 +549,7 @@ __global__ __launch_bounds__(64) void bps_init_kernel(BpsRunParams P, const uint
     double a, b;
     if (BOOM) {  // grad_correct! only shifts g (unused by the Boomerang bound); ab, src/not_fact_samplers.jl:34-36
         double dx[NS];
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const int64_t e = (int64_t)s * 64 + lane;
-            dx[s] = (e < d) ? (x[s] - P.mu_flow[e]) : 0.0;
-        }
+        wv.sub_mu_flow(x, P.mu_flow, dx);
         a = sqrt(dot(th, th) + dot(dx, dx)) * c0;
         b = 0.0;
     } else {
@@ -621,31 +575,10 @@ __global__ __launch_bounds__(64) void bps_init_kernel(BpsRunParams P, const uint
     }
     if (lane == 0) {
         double* sc = P.scal + chain * 8;
-        sc[0] = t0;
-        sc[1] = a;
-        sc[2] = b;
-        sc[3] = tp;
-        sc[4] = tau_ref;
-        sc[5] = c0;
+        store_scal6(sc, t0, a, b, tp, tau_ref, c0);
         sc[6] = renew ? 1.0 : 0.0;
         sc[7] = hz;
-        DevChain h;
-        h.c.t_last = t0;
-        h.c.num = 0;
-        h.c.nacc = 0;
-        h.c.nrefresh = 0;
-        h.c.ntrace = 0;
-        h.c.nevents = 0;
-        h.c.ndraw_main = 2;
-        h.c.ndraw_global = 0;
-        h.c.status = PDMP_CHAIN_OK;
-        h.c.reserved = 0;
-        h.seed = seed;
-        h.t0 = t0;
-        h.t_event = t0;
-        h.tl_scale = 0.0;
-        for (int k = 0; k < 3; ++k) h.pad[k] = 0;
-        P.hdr[chain] = h;
+        P.hdr[chain] = devchain_fresh(seed, t0, 0, 0, 2);
     }
 }
 
@@ -657,6 +590,8 @@ static void launch_run(const BpsRunParams& p, const BpsMomParams& m, dim3 grid, 
     else hipLaunchKernelGGL((bps_run_kernel<NS, DIAG, BOOM, IDENT, FULL, EXT, 0>), grid, block, lds, s, p);
 }
 
+// Beyond 1024 coordinates (NS = 32, 64) the vectors no longer fit the register file as they are used here: only the general instantiation
+// (every option) is compiled there, the compiler keeping what does not fit in AGPRs and scratch -- a capability, not a fast path.
 template <int NS>
 static int launch_ns(const BpsRunParams& p, const BpsMomParams& m, int64_t nchains, bool diag, bool init, const uint64_t* seeds, double t0,
                      double c0, void* stream) {
@@ -667,54 +602,29 @@ static int launch_ns(const BpsRunParams& p, const BpsMomParams& m, int64_t nchai
     if (init) {
         if (boom) hipLaunchKernelGGL((bps_init_kernel<NS, true>), grid, block, lds, s, p, seeds, t0, c0);
         else hipLaunchKernelGGL((bps_init_kernel<NS, false>), grid, block, lds, s, p, seeds, t0, c0);
-    } else if (p.ext) {
+    } else if (NS > 16 || p.ext) {
         if (boom) launch_run<NS, false, true, false, false, true>(p, m, grid, block, lds, s);
         else launch_run<NS, false, false, false, false, true>(p, m, grid, block, lds, s);
-    } else if (boom) {
-        if (diag) launch_run<NS, true, true, false>(p, m, grid, block, lds, s);
-        else launch_run<NS, false, true, false>(p, m, grid, block, lds, s);
-    } else if (diag && p.ident && p.d == (int64_t)NS * 64) {
-        launch_run<NS, true, false, true, true>(p, m, grid, block, lds, s);
-    } else if (diag && p.ident) {
-        launch_run<NS, true, false, true>(p, m, grid, block, lds, s);
-    } else if (diag) {
-        launch_run<NS, true, false, false>(p, m, grid, block, lds, s);
-    } else {
-        launch_run<NS, false, false, false>(p, m, grid, block, lds, s);
-    }
-    return (int)hipGetLastError();
-}
-
-template <int NS>
-static int launch_big(const BpsRunParams& p, const BpsMomParams& m, int64_t nchains, bool init, const uint64_t* seeds, double t0, double c0, void* stream) {
-    const size_t lds = (size_t)p.d * 8;
-    dim3 grid((unsigned)nchains), block(64);
-    const bool boom = p.flow_kind == 1;
-    const hipStream_t s = (hipStream_t)stream;
-    if (init) {
-        if (boom) hipLaunchKernelGGL((bps_init_kernel<NS, true>), grid, block, lds, s, p, seeds, t0, c0);
-        else hipLaunchKernelGGL((bps_init_kernel<NS, false>), grid, block, lds, s, p, seeds, t0, c0);
-    } else if (boom) {
-        launch_run<NS, false, true, false, false, true>(p, m, grid, block, lds, s);
-    } else {
-        launch_run<NS, false, false, false, false, true>(p, m, grid, block, lds, s);
+    } else if constexpr (NS <= 16) {
+        if (boom) {
+            if (diag) launch_run<NS, true, true, false>(p, m, grid, block, lds, s);
+            else launch_run<NS, false, true, false>(p, m, grid, block, lds, s);
+        } else if (diag && p.ident && p.d == (int64_t)NS * 64) {
+            launch_run<NS, true, false, true, true>(p, m, grid, block, lds, s);
+        } else if (diag && p.ident) {
+            launch_run<NS, true, false, true>(p, m, grid, block, lds, s);
+        } else if (diag) {
+            launch_run<NS, true, false, false>(p, m, grid, block, lds, s);
+        } else {
+            launch_run<NS, false, false, false>(p, m, grid, block, lds, s);
+        }
     }
     return (int)hipGetLastError();
 }
 
 static int dispatch(const BpsRunParams& p, const BpsMomParams& m, int64_t nchains, bool diag, bool init, const uint64_t* seeds, double t0,
                     double c0, void* stream) {
-    const int64_t ns = (p.d + 63) / 64;
-    if (ns <= 1) return launch_ns<1>(p, m, nchains, diag, init, seeds, t0, c0, stream);
-    if (ns <= 2) return launch_ns<2>(p, m, nchains, diag, init, seeds, t0, c0, stream);
-    if (ns <= 4) return launch_ns<4>(p, m, nchains, diag, init, seeds, t0, c0, stream);
-    if (ns <= 8) return launch_ns<8>(p, m, nchains, diag, init, seeds, t0, c0, stream);
-    if (ns <= 16) return launch_ns<16>(p, m, nchains, diag, init, seeds, t0, c0, stream);
-    // beyond 1024 coordinates the vectors no longer fit the register file as they are used here: the general instantiation (every option) is
-    // compiled for 32 and 64 slots per lane, the compiler keeping what does not fit in AGPRs and scratch -- a capability, not a fast path
-    if (ns <= 32) return launch_big<32>(p, m, nchains, init, seeds, t0, c0, stream);
-    if (ns <= 64) return launch_big<64>(p, m, nchains, init, seeds, t0, c0, stream);
-    return -1;
+    return bps_dispatch_ns<64>(p.d, [&](auto ns) { return launch_ns<decltype(ns)::value>(p, m, nchains, diag, init, seeds, t0, c0, stream); });
 }
 
 // Write-only probe with the event-record store pattern of bps_run_kernel (one wave per chain, `nrec` records of x(d) and θ(d)

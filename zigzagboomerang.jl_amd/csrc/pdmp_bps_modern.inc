@@ -14,35 +14,9 @@
 // Kept as the reference has them: the record branch checks l > lb with τ = Δrec/V (:224-232); acc += 1 before the bound check; the coin is
 // <=; the first trace element is the first record; `@assert Δrec > 0` (:239) failing ends the chain as PDMP_CHAIN_STALLED.
 // Chain state between launches: scal {t, a, b, t′, -, c, -, -} as the plain kernels keep it, and BpsModernParams::mstate {Δ, action, V, Δrec}.
-
-__device__ __forceinline__ void bps_modern_solve_lower(const BpsRunParams& P, double* tmp, int lane, int64_t d) {
-    for (int64_t j = 0; j < d; ++j) {
-        asm volatile("" ::: "memory");
-        const int32_t p0 = P.Lcp[j], p1 = P.Lcp[j + 1];
-        const double yj = tmp[j] / P.Lnz[p0];
-        asm volatile("" ::: "memory");
-        if (lane == 0) tmp[j] = yj;
-        for (int32_t p = p0 + 1 + lane; p < p1; p += 64) {
-            const int32_t r = P.Lrv[p];
-            tmp[r] = tmp[r] - P.Lnz[p] * yj;
-        }
-    }
-    asm volatile("" ::: "memory");
-}
-__device__ __forceinline__ void bps_modern_solve_upper(const BpsRunParams& P, double* tmp, int lane, int64_t d) {
-    for (int64_t j = d - 1; j >= 0; --j) {
-        asm volatile("" ::: "memory");
-        const int32_t p0 = P.Ucp[j], p1 = P.Ucp[j + 1] - 1;
-        const double zj = tmp[j] / P.Unz[p1];
-        asm volatile("" ::: "memory");
-        if (lane == 0) tmp[j] = zj;
-        for (int32_t p = p0 + lane; p < p1; p += 64) {
-            const int32_t r = P.Urv[p];
-            tmp[r] = tmp[r] - P.Unz[p] * zj;
-        }
-    }
-    asm volatile("" ::: "memory");
-}
+// From pdmp_bps_common.hpp: the gather, the staging, dot and the substitutions (BpsWave), the status gate, the fresh header, the
+// dispatcher.  The run kernel keeps its own Box-Muller fill, fused θ'Γ sum, record store, counters and state load / store: with the
+// shared forms its code is no longer the measured one, and it timed 0.4 % slower (DESIGN.md §4).
 
 // What the init and the run kernel share: dϕ, ab and next_event1, record_rate.
 template <int NS, bool UDIAG>
@@ -53,44 +27,16 @@ struct BpsModernOps {
     int lane;
     int64_t d;
     uint64_t seed;
+    __device__ __forceinline__ BpsWave<NS> wv() const { return {lane, d, tmp}; }
     // y = Γt(in − μt) or Γt in: the CSC gather through LDS, idot order
     __device__ __forceinline__ void gamma(const double (&in)[NS], bool sub_mu, double (&out)[NS]) const {
-        asm volatile("" ::: "memory");
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const int64_t e = (int64_t)s * 64 + lane;
-            if (e < d) tmp[e] = sub_mu ? (in[s] - P.t_mu[e]) : in[s];
-        }
-        asm volatile("" ::: "memory");
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const int64_t e = (int64_t)s * 64 + lane;
-            double y = 0.0;
-            if (e < d) {
-                for (int64_t p = P.t_colptr[e]; p < P.t_colptr[e + 1]; ++p) y += P.t_nzval[p] * tmp[P.t_rowval[p]];
-            }
-            out[s] = y;
-        }
+        wv().csc_gather(P.t_colptr, P.t_rowval, P.t_nzval, P.t_mu, in, sub_mu, out);
     }
-    __device__ __forceinline__ double dot(const double (&u)[NS], const double (&v)[NS]) const {
-        double part = 0.0;
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const int64_t e = (int64_t)s * 64 + lane;
-            if (e < d) part += u[s] * v[s];
-        }
-        return wave_sum_f64(part);
-    }
+    __device__ __forceinline__ double dot(const double (&u)[NS], const double (&v)[NS]) const { return wv().dot(u, v); }
     // θdϕ, v = dϕ(t, x, θ, flow)
     // (each product's elements go straight into the lane's partial sum, slot by slot as dot() adds them: no d-vector is kept)
     __device__ __forceinline__ double th_gamma(const double (&in)[NS], bool sub_mu, const double (&th)[NS]) const {
-        asm volatile("" ::: "memory");
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const int64_t e = (int64_t)s * 64 + lane;
-            if (e < d) tmp[e] = sub_mu ? (in[s] - P.t_mu[e]) : in[s];
-        }
-        asm volatile("" ::: "memory");
+        wv().stage(in, P.t_mu, sub_mu);
         double part = 0.0;
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
@@ -174,7 +120,7 @@ __global__ __launch_bounds__(64) void bps_modern_run_kernel(BpsRunParams P, BpsM
     DevChain* hdr = P.hdr + chain;
 
     uint32_t status = hdr->c.status;
-    if (status == PDMP_CHAIN_BOUND_VIOLATED || status == PDMP_CHAIN_STALLED) return;
+    if (bps_chain_ended(status)) return;
     status = PDMP_CHAIN_OK;
     const uint64_t seed = hdr->seed;
     uint64_t nm = hdr->c.ndraw_main;
@@ -265,7 +211,7 @@ __global__ __launch_bounds__(64) void bps_modern_run_kernel(BpsRunParams P, BpsM
         if (action == 2) {  // :240-246
             ops.normals(nm);
             nm += (uint64_t)(((d + 127) >> 7) << 6);
-            if (has_mass) bps_modern_solve_upper(P, tmp, lane, d);  // L'\randn(rng, d), :177
+            if (has_mass) ops.wv().solve_upper(P);  // L'\randn(rng, d), :177
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
                 const int64_t e = (int64_t)s * 64 + lane;
@@ -341,14 +287,14 @@ __global__ __launch_bounds__(64) void bps_modern_run_kernel(BpsRunParams P, BpsM
                         const int64_t e = (int64_t)s * 64 + lane;
                         if (e < d) tmp[e] = g[s];
                     }
-                    bps_modern_solve_lower(P, tmp, lane, d);
+                    ops.wv().solve_lower(P);
 #pragma unroll
                     for (int s = 0; s < NS; ++s) {
                         const int64_t e = (int64_t)s * 64 + lane;
                         g[s] = (e < d) ? tmp[e] : 0.0;
                     }
                     const double nrm = ops.dot(g, g);
-                    bps_modern_solve_upper(P, tmp, lane, d);
+                    ops.wv().solve_upper(P);
                     const double coef = 2 * gt / nrm;
 #pragma unroll
                     for (int s = 0; s < NS; ++s) {
@@ -425,12 +371,7 @@ __global__ __launch_bounds__(64) void bps_modern_init_kernel(BpsRunParams P, Bps
     ops.rebound(t0, c0, V, d1, d2, nm, a, b, Delta, tp, action);
     if (lane == 0) {
         double* sc = P.scal + chain * 8;
-        sc[0] = t0;
-        sc[1] = a;
-        sc[2] = b;
-        sc[3] = tp;
-        sc[4] = 0.0;
-        sc[5] = c0;
+        store_scal6(sc, t0, a, b, tp, 0.0, c0);
         sc[6] = 0.0;
         sc[7] = 0.0;
         double* ms = Q.mstate + chain * 4;
@@ -438,23 +379,7 @@ __global__ __launch_bounds__(64) void bps_modern_init_kernel(BpsRunParams P, Bps
         ms[1] = (double)action;
         ms[2] = V;
         ms[3] = 1 / P.lambda_ref;
-        DevChain h;
-        h.c.t_last = t0;
-        h.c.num = 0;
-        h.c.nacc = 0;
-        h.c.nrefresh = 0;
-        h.c.ntrace = 0;
-        h.c.nevents = 0;
-        h.c.ndraw_main = nm;
-        h.c.ndraw_global = 0;
-        h.c.status = PDMP_CHAIN_OK;
-        h.c.reserved = 0;
-        h.seed = seed;
-        h.t0 = t0;
-        h.t_event = t0;
-        h.tl_scale = 0.0;
-        for (int k = 0; k < 3; ++k) h.pad[k] = 0;
-        P.hdr[chain] = h;
+        P.hdr[chain] = devchain_fresh(seed, t0, 0, 0, nm);
     }
 }
 
@@ -479,13 +404,8 @@ static int launch_modern_ns(const BpsRunParams& p, const BpsModernParams& q, int
 }
 static int dispatch_modern(const BpsRunParams& p, const BpsModernParams& q, int64_t nchains, bool init, const uint64_t* seeds, double t0, double c0,
                            void* stream) {
-    const int64_t ns = (p.d + 63) / 64;
-    if (ns <= 1) return launch_modern_ns<1>(p, q, nchains, init, seeds, t0, c0, stream);
-    if (ns <= 2) return launch_modern_ns<2>(p, q, nchains, init, seeds, t0, c0, stream);
-    if (ns <= 4) return launch_modern_ns<4>(p, q, nchains, init, seeds, t0, c0, stream);
-    if (ns <= 8) return launch_modern_ns<8>(p, q, nchains, init, seeds, t0, c0, stream);
-    if (ns <= 16) return launch_modern_ns<16>(p, q, nchains, init, seeds, t0, c0, stream);
-    return -1;  // (set_state_bps refuses d > 1024 on this flow)
+    // (past NS = 16: set_state_bps refuses d > 1024 on this flow)
+    return bps_dispatch_ns<16>(p.d, [&](auto ns) { return launch_modern_ns<decltype(ns)::value>(p, q, nchains, init, seeds, t0, c0, stream); });
 }
 int launch_bps_modern_init(const BpsRunParams& p, const BpsModernParams& q, int64_t nchains, const uint64_t* seeds, double t0, double c0, void* stream) {
     return dispatch_modern(p, q, nchains, true, seeds, t0, c0, stream);

@@ -2,10 +2,10 @@
 // `while t < T` (:182-201).  Included by pdmp_bps.hip (inside namespace pdmp): one chain per wavefront, x, θ, ∇ϕ in registers as in
 // bps_run_kernel (element e = slot*64 + lane), plus the per-coordinate clock tfrez (freezing time where free, thaw time where frozen) and the
 // free mask f (one bit per slot and lane).  The saved speeds θf and the thaw rates κ are touched at freezes, thaws and refreshments only, each
-// element by the lane that owns it: they stay in HBM / L2 (no LDS beyond the d-vector staging buffer of bps_run_kernel, no extra registers).
+// element by the lane that owns it: they stay in HBM / L2 (no LDS beyond BpsWave's d-vector staging buffer, no extra registers).
 // The general CSC Γ path only (gather through LDS, idot order); the sums are wave_sum_f64's order, the draws PDMP_STREAM_MAIN in program order:
 //   driver   draw 0 -> tref = -log(u)/λref (t0 not added, :190), draw 1 -> t′ (:195)
-//   refresh  ((d+127)>>7)<<6 Box-Muller blocks (the mapping of bps_run_kernel's refresh), 1 for tref, 1 for t′, then one per FROZEN i ascending
+//   refresh  ((d+127)>>7)<<6 Box-Muller blocks (BpsWave::normals' mapping), 1 for tref, 1 for t′, then one per FROZEN i ascending
 //   freeze   1 for the thaw time, and 1 for t′ unless strong_upperbounds;   thaw  1 for t′;   proposal  the coin, then 1 for t′
 // Ties: findmin(tfrez) and findmin([tref, tᶠ, t′]) take the first minimum (lowest index; tref before tᶠ before t′).
 // Fixed differently from the reference: a NaN clock never wins findmin (Julia's findmin returns the NaN); a clock is NaN only for a free
@@ -49,70 +49,36 @@ __device__ __attribute__((noinline)) double bps_thaw_term(uint64_t seed, uint64_
     return pdmp_log(pdmp_u01(seed, PDMP_STREAM_MAIN, n)) / (kappa * fabs(thf));
 }
 
-// The pieces both sticky kernels share: y = Γ(v − μ) by the CSC gather through LDS, the dot product, ab(x, θ, c, Flow) (:37 of
-// src/not_fact_samplers.jl: GlobalBound(c) with the FLOW's Γ, μ), the freezing times of the free coordinates.
+// The pieces both sticky kernels share: y = Γ(v − μ), ab(x, θ, c, Flow) (:37 of src/not_fact_samplers.jl: GlobalBound(c) with the FLOW's Γ, μ),
+// the freezing times of the free coordinates.
 template <int NS, bool BOOM>
 struct BpsStickyOps {
     const BpsRunParams& P;
-    double* tmp;
-    int lane;
-    int64_t d;
+    BpsWave<NS> wv;
+    // (target: the ensemble's own Γt, μt where it has one, else the flow's)
     __device__ __forceinline__ void gamma(const double (&in)[NS], bool sub_mu, double (&out)[NS], bool target) const {
         const bool own = target && P.t_colptr != nullptr;
-        const int64_t* cp = own ? P.t_colptr : P.colptr;
-        const int64_t* rv = own ? P.t_rowval : P.rowval;
-        const double* nz = own ? P.t_nzval : P.nzval;
-        const double* mu = own ? P.t_mu : P.mu;
-        asm volatile("" ::: "memory");
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const int64_t e = (int64_t)s * 64 + lane;
-            if (e < d) tmp[e] = sub_mu ? (in[s] - mu[e]) : in[s];
-        }
-        asm volatile("" ::: "memory");
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const int64_t e = (int64_t)s * 64 + lane;
-            double y = 0.0;
-            if (e < d) {
-                for (int64_t p = cp[e]; p < cp[e + 1]; ++p) y += nz[p] * tmp[rv[p]];
-            }
-            out[s] = y;
-        }
-    }
-    __device__ __forceinline__ double dot(const double (&u)[NS], const double (&v)[NS]) const {
-        double part = 0.0;
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const int64_t e = (int64_t)s * 64 + lane;
-            if (e < d) part += u[s] * v[s];
-        }
-        return wave_sum_f64(part);
+        wv.csc_gather(own ? P.t_colptr : P.colptr, own ? P.t_rowval : P.rowval, own ? P.t_nzval : P.nzval, own ? P.t_mu : P.mu, in, sub_mu, out);
     }
     __device__ __forceinline__ void ab(const double (&x)[NS], const double (&th)[NS], double c, double& a, double& b) const {
         if constexpr (BOOM) {  // (sqrt(normsq(θ) + normsq(x − μ))·c, 0), src/not_fact_samplers.jl:34-36
             double dx[NS];
-#pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                const int64_t e = (int64_t)s * 64 + lane;
-                dx[s] = (e < d) ? (x[s] - P.mu_flow[e]) : 0.0;
-            }
-            a = sqrt(dot(th, th) + dot(dx, dx)) * c;
+            wv.sub_mu_flow(x, P.mu_flow, dx);
+            a = sqrt(wv.dot(th, th) + wv.dot(dx, dx)) * c;
             b = 0.0;
         } else {  // (c + θ'(Γ(x−μ)), θ'(Γθ)), :26-28
             double w[NS];
             gamma(x, true, w, false);
-            a = c + dot(th, w);
+            a = c + wv.dot(th, w);
             gamma(th, false, w, false);
-            b = dot(th, w);
+            b = wv.dot(th, w);
         }
     }
     // freezing_time!(tfrez, t, x, θ, f, Z), src/ss_not_fact.jl:22-29
     __device__ __forceinline__ void freeze_times(double t, const double (&x)[NS], const double (&th)[NS], uint32_t fm, double (&tf)[NS]) const {
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
-            const int64_t e = (int64_t)s * 64 + lane;
-            if ((fm >> s) & 1u) tf[s] = t + bps_freeze_dt<BOOM>(x[s], th[s], BOOM ? P.mu_flow[e] : 0.0);
+            if ((fm >> s) & 1u) tf[s] = t + bps_freeze_dt<BOOM>(x[s], th[s], BOOM ? P.mu_flow[wv.elem(s)] : 0.0);
         }
     }
 };
@@ -123,7 +89,8 @@ __global__ __launch_bounds__(64) void bps_sticky_run_kernel(BpsRunParams P, BpsS
     const int64_t chain = blockIdx.x;
     const int64_t d = P.d;
     extern __shared__ __align__(16) unsigned char smem[];
-    double* tmp = reinterpret_cast<double*>(smem);  // [d] operand of the CSC gather; the normals of a refresh
+    double* tmp = reinterpret_cast<double*>(smem);
+    const BpsWave<NS> wv{lane, d, tmp};
 
     double* gx = P.x + chain * d;
     double* gth = P.th + chain * d;
@@ -133,42 +100,38 @@ __global__ __launch_bounds__(64) void bps_sticky_run_kernel(BpsRunParams P, BpsS
     double* sc = P.scal + chain * 8;  // {t, a, b, tp, tau_ref, c, told, -}
     DevChain* hdr = P.hdr + chain;
 
-    uint32_t status = hdr->c.status;
-    if (status == PDMP_CHAIN_BOUND_VIOLATED || status == PDMP_CHAIN_STALLED) return;
-    status = PDMP_CHAIN_OK;
+    if (bps_chain_ended(hdr->c.status)) return;
+    uint32_t status = PDMP_CHAIN_OK;
     const uint64_t seed = hdr->seed;
-    uint64_t nm = hdr->c.ndraw_main;
-    uint64_t num = hdr->c.num, nacc = hdr->c.nacc, nrefresh = hdr->c.nrefresh, ntrace = hdr->c.ntrace, nevents = hdr->c.nevents;
+    BpsCounters k;
+    k.load(hdr);
     double t = sc[0], a = sc[1], b = sc[2], tp = sc[3], tau_ref = sc[4], c = sc[5], told = sc[6];
 
     double x[NS], th[NS], g[NS], tf[NS];
     uint32_t fm = 0;  // bit s: element s*64 + lane is free (padding elements: not free, tfrez = Inf, x = θ = 0)
+    wv.load_state(gx, gth, x, th);
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
-        const int64_t e = (int64_t)s * 64 + lane;
-        const bool in = e < d;
-        x[s] = in ? gx[e] : 0.0;
-        th[s] = in ? gth[e] : 0.0;
-        tf[s] = in ? gtf[e] : PDMP_INF;
+        tf[s] = wv.has(s) ? gtf[wv.elem(s)] : PDMP_INF;
         g[s] = 0.0;
         fm |= (uint32_t)((gfm[s] >> lane) & 1ull) << s;
     }
     const double rho = P.rho, rhobar = sqrt(1 - rho * rho);  // :32
     const double T = P.T;
     const bool stop_before = (P.flags & PDMP_RUN_STOP_BEFORE) != 0;
-    const BpsStickyOps<NS, BOOM> ops{P, tmp, lane, d};
+    const BpsStickyOps<NS, BOOM> ops{P, wv};
 
     // b = ab(x, θ, c, Flow); told = t; t′, _ = next_time(t, b, rand())
     auto rebound = [&]() {
         ops.ab(x, th, c, a, b);
         told = t;
-        tp = t + bps_next_dt(seed, nm, a, b);
-        nm += 1;
+        tp = t + bps_next_dt(seed, k.nm, a, b);
+        k.nm += 1;
     };
 
     bool running = stop_before || (t < T);  // `while t < T`, :196
     while (running) {
-        if (P.trace_cap > 0 && ntrace >= (uint64_t)P.trace_cap) {
+        if (P.trace_cap > 0 && k.ntrace >= (uint64_t)P.trace_cap) {
             status = PDMP_CHAIN_TRACE_FULL;
             break;
         }
@@ -201,7 +164,7 @@ __global__ __launch_bounds__(64) void bps_sticky_run_kernel(BpsRunParams P, BpsS
             pdmp_sincos(tau, &sn, &cs);
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
-                const int64_t e = (int64_t)s * 64 + lane;
+                const int64_t e = wv.elem(s);
                 if ((fm >> s) & 1u) {
                     const double m = P.mu_flow[e];
                     const double xn = (x[s] - m) * cs + th[s] * sn + m;
@@ -218,48 +181,39 @@ __global__ __launch_bounds__(64) void bps_sticky_run_kernel(BpsRunParams P, BpsS
         }
         if (is_ref) {
             // refresh_sticky_vel!, :31-41: θ[i] = ρθ[i] + ρ̄ randn() where free, θf[i] = abs(ρθf[i] + ρ̄ randn())*sign(θf[i]) where frozen
-            asm volatile("" ::: "memory");
-#pragma unroll 1
-            for (int a2 = 0; a2 < (NS + 1) / 2; ++a2) {
-                const int64_t e0 = (int64_t)a2 * 128 + lane, e1 = e0 + 64;
-                double z0, z1;
-                pdmp_randn2(seed, PDMP_STREAM_MAIN, nm + (uint64_t)(a2 * 64 + lane), &z0, &z1);
-                if (e0 < d) tmp[e0] = z0;
-                if (e1 < d) tmp[e1] = z1;
-            }
-            asm volatile("" ::: "memory");
+            wv.normals(seed, k.nm);
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
-                const int64_t e = (int64_t)s * 64 + lane;
+                const int64_t e = wv.elem(s);
                 if ((fm >> s) & 1u) {
                     th[s] = rho * th[s] + rhobar * tmp[e];
-                } else if (e < d) {
+                } else if (wv.has(s)) {
                     const double f0 = gthf[e];
                     const double v = rho * f0 + rhobar * tmp[e];
                     gthf[e] = fabs(v) * ((f0 > 0) ? 1.0 : ((f0 < 0) ? -1.0 : f0));
                 }
             }
             asm volatile("" ::: "memory");
-            nm += (uint64_t)(((d + 127) >> 7) << 6);
-            tau_ref = t + (-pdmp_log(pdmp_u01(seed, PDMP_STREAM_MAIN, nm)) / P.lambda_ref);  // :117
-            nm += 1;
+            k.nm += normal_draws(d);
+            tau_ref = t + (-pdmp_log(pdmp_u01(seed, PDMP_STREAM_MAIN, k.nm)) / P.lambda_ref);  // :117
+            k.nm += 1;
             rebound();                          // :118-120
             ops.freeze_times(t, x, th, fm, tf);  // :121
             // :122-126: tfrez[i] = t - log(rand())/(κ[i]*abs(θf[i])) for the frozen i in ascending order
             uint32_t base = 0;
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
-                const int64_t e = (int64_t)s * 64 + lane;
-                const bool fz = e < d && !((fm >> s) & 1u);
+                const int64_t e = wv.elem(s);
+                const bool fz = wv.has(s) && !((fm >> s) & 1u);
                 const uint64_t bal = __ballot(fz);
                 if (fz) {
                     const uint32_t r = base + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
-                    tf[s] = t - bps_thaw_term(seed, nm + r, Q.kappa[e], gthf[e]);
+                    tf[s] = t - bps_thaw_term(seed, k.nm + r, Q.kappa[e], gthf[e]);
                 }
                 base += (uint32_t)__popcll(bal);
             }
-            nm += base;
-            nrefresh += 1;
+            k.nm += base;
+            k.nrefresh += 1;
         } else if (is_frz) {
             const int si = (int)(i >> 6);
             const bool mine = lane == (int)(i & 63u);
@@ -282,10 +236,10 @@ __global__ __launch_bounds__(64) void bps_sticky_run_kernel(BpsRunParams P, BpsS
                         const double sp = th[s];
                         th[s] = 0.0;
                         fm &= ~(1u << s);
-                        tf[s] = t - bps_thaw_term(seed, nm, Q.kappa[i], sp);  // :136
+                        tf[s] = t - bps_thaw_term(seed, k.nm, Q.kappa[i], sp);  // :136
                     }
                 }
-                nm += 1;
+                k.nm += 1;
                 if (!Q.strong_upperbounds) rebound();  // :138-142
             } else {  // :143-151 (x[i] == 0 && θ[i] == 0 hold by construction)
 #pragma unroll
@@ -300,22 +254,16 @@ __global__ __launch_bounds__(64) void bps_sticky_run_kernel(BpsRunParams P, BpsS
                 rebound();
             }
         } else {
-            const double coin = pdmp_u01(seed, PDMP_STREAM_MAIN, nm);
+            const double coin = pdmp_u01(seed, PDMP_STREAM_MAIN, k.nm);
             // ∇ϕx = ∇ϕ!(∇ϕx, x); grad_correct!: the Boomerang subtracts x − μ (L = I), :153-154
             ops.gamma(x, true, g, true);
-            if constexpr (BOOM) {
-#pragma unroll
-                for (int s = 0; s < NS; ++s) {
-                    const int64_t e = (int64_t)s * 64 + lane;
-                    if (e < d) g[s] -= x[s] - P.mu_flow[e];
-                }
-            }
-            const double l = pos_part(ops.dot(g, th));             // λ(∇ϕx, θ, Flow)
+            if constexpr (BOOM) wv.each([&](int s, int64_t e) { g[s] -= x[s] - P.mu_flow[e]; });
+            const double l = pos_part(wv.dot(g, th));             // λ(∇ϕx, θ, Flow)
             const double lb = pos_part(a + b * (t - told));         // sλ̄(b, t - told), :155
-            num += 1;
-            nm += 1;
+            k.num += 1;
+            k.nm += 1;
             if (coin * lb <= l) {  // :157
-                nacc += 1;
+                k.nacc += 1;
                 if (l > lb) {
                     if (!P.adapt) {
                         status = PDMP_CHAIN_BOUND_VIOLATED;  // error("Tuning parameter `c` too small."), :160
@@ -325,14 +273,12 @@ __global__ __launch_bounds__(64) void bps_sticky_run_kernel(BpsRunParams P, BpsS
                 }
                 // reflect_sticky!, :68-76: c = 2*sdot(∇ϕx, θ, θ)/subnormsq(∇ϕx, θ), both skipping θ[i] == 0
                 double p1 = 0.0, p2 = 0.0;
-#pragma unroll
-                for (int s = 0; s < NS; ++s) {
-                    const int64_t e = (int64_t)s * 64 + lane;
-                    if (e < d && !(th[s] == 0.0)) {
+                wv.each([&](int s, int64_t) {
+                    if (!(th[s] == 0.0)) {
                         p1 += g[s] * th[s];
                         p2 += g[s] * g[s];
                     }
-                }
+                });
                 const double coef = 2 * wave_sum_f64(p1) / wave_sum_f64(p2);
 #pragma unroll
                 for (int s = 0; s < NS; ++s) {
@@ -346,56 +292,34 @@ __global__ __launch_bounds__(64) void bps_sticky_run_kernel(BpsRunParams P, BpsS
             }
         }
         // push!(Ξ, sevent(t, x, θ, f, Flow)), :175
+        wv.emit_record(P, chain, k.ntrace, t, x, th);
         if (P.trace_cap > 0) {
-            const int64_t slot = chain * P.trace_cap + (int64_t)ntrace;
-            if (lane == 0) P.ev_t[slot] = t;
-            double* ex = P.ev_x + slot * d;
-            double* eth = P.ev_th + slot * d;
-            uint64_t* ef = Q.ev_f + slot * BPS_STICKY_WORDS;
+            uint64_t* ef = Q.ev_f + (chain * P.trace_cap + (int64_t)k.ntrace) * BPS_STICKY_WORDS;
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
-                const int64_t e = (int64_t)s * 64 + lane;
-                if (e < d) {
-                    ex[e] = x[s];
-                    eth[e] = th[s];
-                }
                 const uint64_t w = __ballot((fm >> s) & 1u);
                 if (lane == 0) ef[s] = w;
             }
         }
-        ntrace += 1;
-        nevents += 1;
+        k.ntrace += 1;
+        k.nevents += 1;
         if (!stop_before && !(t < T)) running = false;
     }
 
+    wv.each([&](int s, int64_t e) {
+        gx[e] = x[s];
+        gth[e] = th[s];
+        gtf[e] = tf[s];
+    });
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
-        const int64_t e = (int64_t)s * 64 + lane;
-        if (e < d) {
-            gx[e] = x[s];
-            gth[e] = th[s];
-            gtf[e] = tf[s];
-        }
         const uint64_t w = __ballot((fm >> s) & 1u);
         if (lane == 0) gfm[s] = w;
     }
     if (lane == 0) {
-        sc[0] = t;
-        sc[1] = a;
-        sc[2] = b;
-        sc[3] = tp;
-        sc[4] = tau_ref;
-        sc[5] = c;
+        store_scal6(sc, t, a, b, tp, tau_ref, c);
         sc[6] = told;
-        hdr->c.t_last = t;
-        hdr->t_event = t;
-        hdr->c.num = num;
-        hdr->c.nacc = nacc;
-        hdr->c.nrefresh = nrefresh;
-        hdr->c.ntrace = ntrace;
-        hdr->c.nevents = nevents;
-        hdr->c.ndraw_main = nm;
-        hdr->c.status = status;
+        k.store(hdr, t, status);
     }
 }
 
@@ -406,21 +330,17 @@ __global__ __launch_bounds__(64) void bps_sticky_init_kernel(BpsRunParams P, Bps
     const int64_t chain = blockIdx.x;
     const int64_t d = P.d;
     extern __shared__ __align__(16) unsigned char smem[];
-    double* tmp = reinterpret_cast<double*>(smem);
-    const double* gx = P.x + chain * d;
-    const double* gth = P.th + chain * d;
+    const BpsWave<NS> wv{lane, d, reinterpret_cast<double*>(smem)};
     const uint64_t seed = seeds[chain];
     double x[NS], th[NS], tf[NS];
     uint32_t fm = 0;
+    wv.load_state(P.x + chain * d, P.th + chain * d, x, th);
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
-        const int64_t e = (int64_t)s * 64 + lane;
-        x[s] = (e < d) ? gx[e] : 0.0;
-        th[s] = (e < d) ? gth[e] : 0.0;
         tf[s] = PDMP_INF;
-        if (e < d) fm |= 1u << s;
+        if (wv.has(s)) fm |= 1u << s;
     }
-    const BpsStickyOps<NS, BOOM> ops{P, tmp, lane, d};
+    const BpsStickyOps<NS, BOOM> ops{P, wv};
     const double tau_ref = -pdmp_log(pdmp_u01(seed, PDMP_STREAM_MAIN, 0)) / P.lambda_ref;  // :190
     ops.freeze_times(t0, x, th, fm, tf);                                                   // :192
     double a, b;
@@ -428,17 +348,13 @@ __global__ __launch_bounds__(64) void bps_sticky_init_kernel(BpsRunParams P, Bps
     const double tp = t0 + bps_next_dt(seed, 1, a, b);                                     // :195
     const bool traced = P.trace_cap > 0;
     const int64_t slot = chain * P.trace_cap;
+    wv.each([&](int s, int64_t e) {
+        Q.thf[chain * d + e] = 0.0 * th[s];  // θf = 0*θ, :186
+        Q.tfrez[chain * d + e] = tf[s];
+    });
+    wv.emit_record(P, chain, 0, t0, x, th);  // :189
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
-        const int64_t e = (int64_t)s * 64 + lane;
-        if (e < d) {
-            Q.thf[chain * d + e] = 0.0 * th[s];  // θf = 0*θ, :186
-            Q.tfrez[chain * d + e] = tf[s];
-            if (traced) {
-                P.ev_x[slot * d + e] = x[s];
-                P.ev_th[slot * d + e] = th[s];
-            }
-        }
         const uint64_t w = __ballot((fm >> s) & 1u);
         if (lane == 0) {
             Q.fmask[chain * BPS_STICKY_WORDS + s] = w;
@@ -447,33 +363,11 @@ __global__ __launch_bounds__(64) void bps_sticky_init_kernel(BpsRunParams P, Bps
     }
     if (lane == 0) {
         for (int s = NS; s < BPS_STICKY_WORDS; ++s) Q.fmask[chain * BPS_STICKY_WORDS + s] = 0ull;
-        if (traced) P.ev_t[slot] = t0;
         double* sc = P.scal + chain * 8;
-        sc[0] = t0;
-        sc[1] = a;
-        sc[2] = b;
-        sc[3] = tp;
-        sc[4] = tau_ref;
-        sc[5] = c0;
+        store_scal6(sc, t0, a, b, tp, tau_ref, c0);
         sc[6] = t0;  // told
         sc[7] = 0.0;
-        DevChain h;
-        h.c.t_last = t0;
-        h.c.num = 0;
-        h.c.nacc = 0;
-        h.c.nrefresh = 0;
-        h.c.ntrace = 1;
-        h.c.nevents = 1;
-        h.c.ndraw_main = 2;
-        h.c.ndraw_global = 0;
-        h.c.status = PDMP_CHAIN_OK;
-        h.c.reserved = 0;
-        h.seed = seed;
-        h.t0 = t0;
-        h.t_event = t0;
-        h.tl_scale = 0.0;
-        for (int k = 0; k < 3; ++k) h.pad[k] = 0;
-        P.hdr[chain] = h;
+        P.hdr[chain] = devchain_fresh(seed, t0, 1, 1, 2);
     }
 }
 
@@ -494,13 +388,8 @@ static int launch_sticky_ns(const BpsRunParams& p, const BpsStickyParams& q, int
 }
 static int dispatch_sticky(const BpsRunParams& p, const BpsStickyParams& q, int64_t nchains, bool init, const uint64_t* seeds, double t0, double c0,
                            void* stream) {
-    const int64_t ns = (p.d + 63) / 64;
-    if (ns <= 1) return launch_sticky_ns<1>(p, q, nchains, init, seeds, t0, c0, stream);
-    if (ns <= 2) return launch_sticky_ns<2>(p, q, nchains, init, seeds, t0, c0, stream);
-    if (ns <= 4) return launch_sticky_ns<4>(p, q, nchains, init, seeds, t0, c0, stream);
-    if (ns <= 8) return launch_sticky_ns<8>(p, q, nchains, init, seeds, t0, c0, stream);
-    if (ns <= 16) return launch_sticky_ns<16>(p, q, nchains, init, seeds, t0, c0, stream);
-    return -1;  // (set_state_bps refuses d > 1024 on a sticky ensemble)
+    // (past NS = 16: set_state_bps refuses d > 1024 on a sticky ensemble)
+    return bps_dispatch_ns<16>(p.d, [&](auto ns) { return launch_sticky_ns<decltype(ns)::value>(p, q, nchains, init, seeds, t0, c0, stream); });
 }
 int launch_bps_sticky_init(const BpsRunParams& p, const BpsStickyParams& q, int64_t nchains, const uint64_t* seeds, double t0, double c0, void* stream) {
     return dispatch_sticky(p, q, nchains, true, seeds, t0, c0, stream);

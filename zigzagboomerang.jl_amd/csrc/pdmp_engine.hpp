@@ -97,6 +97,27 @@ struct alignas(128) DevChain {
 static_assert(sizeof(DevChain) == 128, "chain header is 128 bytes");
 
 #if defined(__HIPCC__)
+// The header an init kernel writes: a chain at t0 with nothing counted but what its setup itself recorded and drew.
+__device__ __forceinline__ DevChain devchain_fresh(uint64_t seed, double t0, uint64_t ntrace, uint64_t nevents, uint64_t ndraw_main) {
+    DevChain h;
+    h.c.t_last = t0;
+    h.c.num = 0;
+    h.c.nacc = 0;
+    h.c.nrefresh = 0;
+    h.c.ntrace = ntrace;
+    h.c.nevents = nevents;
+    h.c.ndraw_main = ndraw_main;
+    h.c.ndraw_global = 0;
+    h.c.status = PDMP_CHAIN_OK;
+    h.c.reserved = 0;
+    h.seed = seed;
+    h.t0 = t0;
+    h.t_event = t0;
+    h.tl_scale = 0.0;
+    for (int k = 0; k < 3; ++k) h.pad[k] = 0;
+    return h;
+}
+
 // Wave priority in turns.  A SIMD's arbiter serves its OLDEST wave first: of the chains that share a SIMD for a whole launch (one chain per
 // wave, 4 or more per SIMD) the oldest finishes well before the youngest, which then runs out the launch alone.  Every event loop calls
 // prio_turn(iteration) at its top: the waves of a SIMD take turns at the top priority (a turn = PDMP_PRIO_TURN iterations; measured on the

@@ -156,25 +156,7 @@ __global__ __launch_bounds__(256) void zz_init_kernel(ZzInitParams P) {
         }
         keys[i] = key;
     }
-    if (i == 0) {
-        DevChain h;
-        h.c.t_last = P.t0;
-        h.c.num = 0;
-        h.c.nacc = 0;
-        h.c.nrefresh = 0;
-        h.c.ntrace = 0;
-        h.c.nevents = 0;
-        h.c.ndraw_main = (uint64_t)d + (P.has_refresh ? 1u : 0u);
-        h.c.ndraw_global = 0;
-        h.c.status = PDMP_CHAIN_OK;
-        h.c.reserved = 0;
-        h.seed = seed;
-        h.t0 = P.t0;
-        h.t_event = P.t0;
-        h.tl_scale = 0.0;
-        for (int k = 0; k < 3; ++k) h.pad[k] = 0;
-        P.hdr[chain] = h;
-    }
+    if (i == 0) P.hdr[chain] = devchain_fresh(seed, P.t0, 0, 0, (uint64_t)d + (P.has_refresh ? 1u : 0u));
 }
 
 // ------------------------------------------------------------------------------------------ event loop
