@@ -148,6 +148,16 @@ pdmp_status pdmp_debug_math_eval(int device, int fn, int64_t n, const double* a,
 pdmp_status pdmp_debug_sticky_eval(int device, int fn, int64_t n, const double* a, const double* b, const double* c, double* out);
 
 /*
+ * Test hook: puts a given trace segment in front of the device consumers (csrc/pdmp_consume.hip; tests/test_gpu_consumers_synthetic.py).  Waits for
+ * the device (pending asynchronous consumers included), copies the n events into slots [ntrace, ntrace + n) of `chain`'s CURRENT trace buffer and
+ * adds n to the chain's ntrace and nevents -- no event-loop kernel runs, no record changes.  PDMP_ERR_INVALID for a bad chain, n < 0,
+ * ntrace + n > trace_capacity, a call before pdmp_ensemble_consume_begin and a non-factorised ensemble.  trace_copy, trace_reset, consume,
+ * consume_async, subtrace_copy and the consume_* readers work as after a run.  From the first append on the records no longer match the trace:
+ * pdmp_ensemble_run on that ensemble is refused with PDMP_ERR_INVALID (until the next set_state).
+ */
+pdmp_status pdmp_debug_trace_append(pdmp_ensemble* ens, int64_t chain, const pdmp_event* ev, int64_t n);
+
+/*
  * Measurement hook: time (ms per launch, HIP events) of a write-only kernel with the event-record store pattern of the bouncy
  * particle kernel -- one wavefront per chain writing `nrec` records of x[d] and θ[d] -- i.e. the HBM write ceiling that the C2
  * roofline fraction is read against (tools/bench_c2.py).

@@ -198,6 +198,7 @@ struct pdmp_ensemble {
     DevBuf<double> d_ccm;      // pdmp_ensemble_consume_cummean: (t, y / (2 t)) per event slot of the last consumed segment [nchains x cap x 2], or empty
     bool cons_cummean = false;
     bool consuming = false, cons_z = false;
+    bool trace_appended = false;  // pdmp_debug_trace_append put events into the trace that no record knows of: run is refused until the next set_state
     // pdmp_ensemble_consume_async: a second trace buffer (the event loop writes one while the consumer reads the other), the consumer's stream,
     // the (ntrace, nevents) snapshots of the two most recent slices and the events that order the two streams
     DevBuf<pdmp_event> d_ev2;
@@ -1572,6 +1573,7 @@ static pdmp_status init_state(pdmp_ensemble* e, double t0, const double* x0, con
     e->ran = false;
     e->timed = false;
     e->consuming = false;
+    e->trace_appended = false;
     return PDMP_OK;
 }
 
@@ -1894,6 +1896,7 @@ pdmp_status pdmp_ensemble_run(pdmp_ensemble* e, double T, int flags, void* strea
 static pdmp_status ensemble_run_impl(pdmp_ensemble* e, double T, int flags, void* stream) {
     if (!e) return fail(PDMP_ERR_INVALID, "null argument");
     if (!e->has_state) return fail(PDMP_ERR_INVALID, "set_state must be called before run");
+    if (e->trace_appended) return fail(PDMP_ERR_INVALID, "pdmp_debug_trace_append was used on this ensemble: its records no longer match its trace (set_state first)");
     if (flags != PDMP_RUN_REFERENCE_TAIL && flags != PDMP_RUN_STOP_BEFORE) return fail(PDMP_ERR_INVALID, "bad flags");
     HIP_TRY(hipSetDevice(e->cfg.device));
     e->ran = true;
@@ -2410,6 +2413,30 @@ pdmp_status pdmp_ensemble_consume_async(pdmp_ensemble* e, void* stream) {
     return PDMP_OK;
 }
 
+// Test hook (include/pdmp_debug.h): n given events behind what `chain`'s current trace segment holds, counted in its header as a run would have
+// counted them -- the consumers, trace_copy, trace_reset and subtrace_copy see a segment a sampler could never have produced (events exactly at
+// grid times, chains of one coordinate, chosen hash clashes: tests/consumer_cases.py).  No kernel is launched and no record is touched, so the
+// ensemble cannot run afterwards.
+pdmp_status pdmp_debug_trace_append(pdmp_ensemble* e, int64_t chain, const pdmp_event* ev, int64_t n) {
+    if (!e || (n > 0 && !ev)) return fail(PDMP_ERR_INVALID, "null argument");
+    NEED_FACTORISED(e);
+    if (!e->consuming || !e->has_state) return fail(PDMP_ERR_INVALID, "pdmp_ensemble_consume_begin first");
+    if (chain < 0 || chain >= e->cfg.nchains || n < 0) return fail(PDMP_ERR_INVALID, "bad argument");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(device_sync(e));  // (a deferred asynchronous consumer is launched and waited for: it reads the other buffer and the headers' snapshot)
+    pdmp::DevChain h;
+    HIP_TRY(hipMemcpy(&h, e->d_hdr.p + chain, sizeof h, hipMemcpyDeviceToHost));
+    const int64_t cap = e->cfg.trace_capacity;
+    if (h.c.ntrace > (uint64_t)cap || n > cap - (int64_t)h.c.ntrace)
+        return fail(PDMP_ERR_INVALID, "trace_append: %lld events behind %llu do not fit trace_capacity = %lld", (long long)n, (unsigned long long)h.c.ntrace, (long long)cap);
+    if (n > 0) HIP_TRY(hipMemcpy(e->d_ev.p + chain * cap + (int64_t)h.c.ntrace, ev, (size_t)n * sizeof(pdmp_event), hipMemcpyHostToDevice));
+    h.c.ntrace += (uint64_t)n;
+    h.c.nevents += (uint64_t)n;
+    HIP_TRY(hipMemcpy(&e->d_hdr.p[chain].c, &h.c, sizeof h.c, hipMemcpyHostToDevice));
+    e->trace_appended = true;
+    return PDMP_OK;
+}
+
 // What the host could drain instead: `bytes` of the trace buffer copied to pinned host memory, in GB/s (a measurement for bench.py's pipeline
 // object, not a code path of the engine)
 pdmp_status pdmp_debug_host_drain_probe(pdmp_ensemble* e, int64_t bytes, double* gbps) {
@@ -2572,6 +2599,7 @@ pdmp_status pdmp_ensemble_run_partitioned(pdmp_ensemble* e, double T, int K, dou
         return fail(PDMP_ERR_UNSUPPORTED,
                     "parallel_spdmp (src/parallel.jl) is built for the local ZigZag on a Gaussian target without refresh clock, "
                     "adaptscale, LocalBound or gradient tracking");
+    if (e->trace_appended) return fail(PDMP_ERR_INVALID, "pdmp_debug_trace_append was used on this ensemble: its records no longer match its trace (set_state first)");
     if (e->ran) return fail(PDMP_ERR_UNSUPPORTED, "a partitioned run starts from a fresh state (call set_state first)");
     if (e->has_g1mask) return fail(PDMP_ERR_UNSUPPORTED, "parallel_spdmp takes G as the flow's pattern + g1_mask, not pdmp_ensemble_set_neighbourhood");
     const int64_t d = e->cfg.d;

@@ -438,6 +438,12 @@ class Ensemble:
         _lib.check(self._L.pdmp_debug_host_drain_probe(self._h, int(nbytes), C.byref(g)))
         return float(g.value)
 
+    def debug_trace_append(self, chain, events):
+        """Test hook (pdmp_debug_trace_append, include/pdmp_debug.h): the given EVENT_DTYPE events behind what `chain`'s trace segment holds, counted
+        like sampled ones; after consume_begin.  The ensemble refuses to run afterwards."""
+        ev = np.ascontiguousarray(events, dtype=_lib.EVENT_DTYPE)
+        _lib.check(self._L.pdmp_debug_trace_append(self._h, int(chain), ev.ctypes.data if ev.size else None, int(ev.size)))
+
     def consume_mean(self, chain_first=0, n=None):
         """(mean [n x d], T_last [n]): mean(Ξ) of src/trace.jl:182-200 per chain, from the device-side cursors."""
         if n is None:

@@ -292,9 +292,11 @@ def path_moments(tr: PDMPTrace, T):
 
 def subtrace(tr: FactTrace, J):
     """subtrace(Ξ, J): trace of the subvector x[J] -- src/trace.jl:275-290."""
-    J = np.asarray(J)
+    J = np.asarray(J, dtype=np.int64)
     assert np.all(np.diff(J) > 0)
     ev = tr.events
+    if len(J) == 0:  # (nothing to look up in: no event is kept)
+        return FactTrace(tr.F, tr.t0, tr.x0[J].copy(), tr.θ0[J].copy(), ev[:0].copy())
     loc = np.searchsorted(J, ev["i"])
     loc_c = np.minimum(loc, len(J) - 1)
     keep = J[loc_c] == ev["i"]
