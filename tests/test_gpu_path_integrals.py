@@ -7,7 +7,7 @@ the events drained so far (rationals: no tolerance in the reference), every coor
 exact_path.py's docstring.  Each event-loop case asserts the kernel that ran, >= 1000 events per chain and >= 1 refill.
 
 The reductions (zz_batch_means_kernel, zz_ess_kernel) are held to the same sums formed in Fraction from the device's own per-chain J;
-the validity rule of T (pdmp_capi.hip: fact_integrals_at) to the statuses it must refuse.
+the validity rule of T (pdmp_capi_stats.hip: fact_integrals_at) to the statuses it must refuse.
 
 Digits lost in S_w = ΣY² − B·ΣM² at |mean| >> spread (B = 3, mean 5; every reduction case measures and prints it): with 63 chains or more
 ΣY² is 1.1e2 (d = 3) to 1.1e3 .. 4.3e3 (d = 255, 257 and the lattice) times S_w, i.e. 2.0 to 3.7 decimal digits of the sums are given

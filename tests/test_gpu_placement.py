@@ -1,5 +1,5 @@
 """set_state's placement probes (-m gpu): a device-filling ZigZag ensemble is timed on a short launch, its pairs / keys and records are re-allocated
-and the fastest combination kept (csrc/pdmp_capi.hip: init_state_tuned; DESIGN.md 5 "The timing modes are a property of the allocation").  What the
+and the fastest combination kept (csrc/pdmp_capi_tune.hip: init_state_tuned; DESIGN.md 5 "The timing modes are a property of the allocation").  What the
 caller gets must be bit for bit the ensemble set_state alone makes."""
 import numpy as np
 import pytest

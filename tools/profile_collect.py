@@ -113,7 +113,7 @@ def main():
             if d and min(d) < 0.5 * max(d):
                 small = [v for v in d if v < 0.5 * max(d)]
                 f.write(f"\n# {kern}: the row above includes {len(small)} short launches ({min(small):.2f}-{max(small):.2f} ms): set_state's placement probes "
-                        "(every chain pauses after 12 000 draws; csrc/pdmp_capi.hip init_state_tuned) -- not slices")
+                        "(every chain pauses after 12 000 draws; csrc/pdmp_capi_tune.hip init_state_tuned) -- not slices")
             if d:
                 f.write(f"\n# {kern}: average over the {min(nl, len(d))} timed launches {sum(d[-nl:]) / len(d[-nl:]):.4f} ms "
                         f"(all {len(d)} launches incl. warm-up: {sum(d) / len(d):.4f} ms)\n")

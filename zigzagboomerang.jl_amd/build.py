@@ -14,7 +14,8 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_DIR = os.path.join(PKG_DIR, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libpdmp_mi355.so")
-SOURCES = ["pdmp_capi.hip", "pdmp_kernels.hip", "pdmp_bps.hip", "pdmp_general.hip", "pdmp_partition.hip", "pdmp_trackp.hip", "pdmp_trackl.hip",
+SOURCES = ["pdmp_capi.hip", "pdmp_capi_zigzag.hip", "pdmp_capi_bps.hip", "pdmp_capi_stats.hip", "pdmp_capi_tune.hip", "pdmp_capi_debug.hip",
+           "pdmp_kernels.hip", "pdmp_bps.hip", "pdmp_general.hip", "pdmp_partition.hip", "pdmp_trackp.hip", "pdmp_trackl.hip",
            "pdmp_consume.hip", "pdmp_logistic.hip", "pdmp_comm.hip", "pdmp_1d.hip", "pdmp_place.hip"]
 # Measured-slower cross-implementations of two event loops (zz_local_exactp_kernel: the moving evaluation with one proposal per lane;
 # zz_logistic_rows_kernel: several chains of config C4 per wavefront).  They are NOT in the default library: `build.py --variant parity`
@@ -23,6 +24,7 @@ SOURCES = ["pdmp_capi.hip", "pdmp_kernels.hip", "pdmp_bps.hip", "pdmp_general.hi
 EXTRA_SOURCES = ["pdmp_exactp.hip", "pdmp_logrows.hip"]
 PARITY_DEFINES = ("PDMP_EXTRA_KERNELS",)
 HEADERS = [os.path.join(CSRC, "pdmp_engine.hpp"),
+           os.path.join(CSRC, "pdmp_ensemble.hpp"),  # (the host units pdmp_capi*.hip: error reporting, the device buffer, the ensemble)
            os.path.join(CSRC, "pdmp_device.hpp"),  # (the scalar and wave-level helpers every event-loop unit shares)
            os.path.join(CSRC, "pdmp_spec8_common.hpp"),  # (the 8-event loop's machinery, shared by pdmp_kernels.hip's three kernels of it)
            os.path.join(CSRC, "pdmp_spec8g.inc"),  # (included by pdmp_kernels.hip)

@@ -1,0 +1,329 @@
+// pdmp_capi_debug.hip -- the entry points of include/pdmp_debug.h: probes, kernel selectors, test hooks.
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstring>
+
+#include "pdmp_ensemble.hpp"
+
+// the mean time of one launch on the null stream: a warm-up (page faults, TLB), then `iters` timed ones
+template <class Launch>
+static pdmp_status time_launches(const char* name, int iters, double* ms_out, Launch launch) {
+    hipEvent_t e0, e1;
+    HIP_TRY(hipEventCreate(&e0));
+    HIP_TRY(hipEventCreate(&e1));
+    (void)launch();
+    HIP_TRY(hipEventRecord(e0, nullptr));
+    for (int k = 0; k < iters; ++k) LAUNCH_TRY_CODE(name, launch());
+    HIP_TRY(hipEventRecord(e1, nullptr));
+    HIP_TRY(hipEventSynchronize(e1));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+    *ms_out = (double)ms / iters;
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    return PDMP_OK;
+}
+
+// the three argument vectors of a math probe side by side in `in` [3 x n]
+static pdmp_status upload_abc(DevBuf<double>& in, int64_t n, const double* a, const double* b, const double* c) {
+    PDMP_TRY(in.alloc((size_t)(3 * n)));
+    HIP_TRY(hipMemcpy(in.p, a, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(in.p + n, b, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(in.p + 2 * n, c, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    return PDMP_OK;
+}
+
+extern "C" {
+
+pdmp_status pdmp_debug_write_probe(int device, int64_t nchains, int64_t d, int64_t nrec, int iters, double* ms_out) {
+    if (!ms_out || nchains <= 0 || d <= 0 || nrec <= 0 || iters <= 0) return fail(PDMP_ERR_INVALID, "bad argument");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
+        return fail(PDMP_ERR_NO_DEVICE, "no HIP device visible: libpdmp_mi355 has no CPU fallback");
+    HIP_TRY(hipSetDevice(device));
+    DevBuf<double> bx, bt;
+    PDMP_TRY(bx.alloc((size_t)(nchains * nrec * d)));
+    PDMP_TRY(bt.alloc((size_t)(nchains * nrec * d)));
+    return time_launches("write probe", iters, ms_out, [&]() { return pdmp::launch_bps_write_probe(bx.p, bt.p, d, nrec, nrec, nchains, nullptr); });
+}
+
+pdmp_status pdmp_debug_sector_probe(int device, int64_t nchains, int64_t d, int rounds, int write, int iters, double* ms_out) {
+    if (!ms_out || nchains <= 0 || d <= 0 || rounds <= 0 || iters <= 0) return fail(PDMP_ERR_INVALID, "bad argument");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
+        return fail(PDMP_ERR_NO_DEVICE, "no HIP device visible: libpdmp_mi355 has no CPU fallback");
+    HIP_TRY(hipSetDevice(device));
+    DevBuf<double> rec, sink;
+    PDMP_TRY(rec.alloc((size_t)(nchains * d * 8)));
+    PDMP_TRY(sink.alloc(8));
+    HIP_TRY(hipMemset(rec.p, 0, (size_t)(nchains * d * 8) * sizeof(double)));
+    return time_launches("sector probe", iters, ms_out, [&]() { return pdmp::launch_sector_probe(rec.p, d, nchains, rounds, write, sink.p, nullptr); });
+}
+
+pdmp_status pdmp_debug_math_probe(int device, uint64_t seed, int64_t n, double* out) {
+    if (!out || n <= 0) return fail(PDMP_ERR_INVALID, "bad argument");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(PDMP_ERR_NO_DEVICE, "no HIP device visible");
+    HIP_TRY(hipSetDevice(device));
+    DevBuf<double> buf;
+    PDMP_TRY(buf.alloc((size_t)(8 * n)));
+    LAUNCH_TRY("math probe", pdmp::launch_math_probe(seed, n, buf.p, nullptr));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, buf.p, (size_t)(8 * n) * sizeof(double), hipMemcpyDeviceToHost));
+    return PDMP_OK;
+}
+
+pdmp_status pdmp_debug_math_eval(int device, int fn, int64_t n, const double* a, const double* b, const double* c, double* out) {
+#ifndef PDMP_EXTRA_KERNELS
+    (void)device, (void)fn, (void)n, (void)a, (void)b, (void)c, (void)out;
+    return fail(PDMP_ERR_UNSUPPORTED, "pdmp_debug_math_eval: the probe kernels live in the parity build (build.py --variant parity, -DPDMP_EXTRA_KERNELS)");
+#else
+    if (!a || !b || !c || !out || n <= 0 || n > ((int64_t)1 << 30)) return fail(PDMP_ERR_INVALID, "bad argument");
+    decltype(&pdmp::launch_math_eval_kernels) launch = nullptr;
+    switch (fn) {
+    case PDMP_MATH_U01: case PDMP_MATH_LOG: case PDMP_MATH_EXP: case PDMP_MATH_SINCOS: case PDMP_MATH_SINCOS2PI: case PDMP_MATH_RANDN:
+    case PDMP_MATH_RANDN2: case PDMP_MATH_RANDINT: case PDMP_MATH_DIV: case PDMP_MATH_SQRT:
+    case PDMP_MATH_PT_DEV: case PDMP_MATH_PT_DEV_L: case PDMP_MATH_POS_DEV: launch = pdmp::launch_math_eval_kernels; break;
+    case PDMP_MATH_PT_BPS: case PDMP_MATH_PT_BPS_L: case PDMP_MATH_POS_BPS: launch = pdmp::launch_math_eval_bps; break;
+    case PDMP_MATH_PT_D1: case PDMP_MATH_POS_D1: launch = pdmp::launch_math_eval_1d; break;
+    case PDMP_MATH_PT_G: case PDMP_MATH_PT_G_L: case PDMP_MATH_SIGMOID_G: case PDMP_MATH_POS_G: launch = pdmp::launch_math_eval_general; break;
+    case PDMP_MATH_PT_Q: case PDMP_MATH_POS_Q: launch = pdmp::launch_math_eval_partition; break;
+    case PDMP_MATH_PT_W_L: case PDMP_MATH_POS_W: launch = pdmp::launch_math_eval_trackp; break;
+    case PDMP_MATH_PT_LOGISTIC_L: case PDMP_MATH_SIGMOID_LOGISTIC: case PDMP_MATH_POS_LOGISTIC: launch = pdmp::launch_math_eval_logistic; break;
+    case PDMP_MATH_PT_TRACKL_L: case PDMP_MATH_POS_TRACKL: launch = pdmp::launch_math_eval_trackl; break;
+    case PDMP_MATH_PT_X_L: case PDMP_MATH_POS_X: launch = pdmp::launch_math_eval_exactp; break;
+    case PDMP_MATH_PT_R_L: case PDMP_MATH_SIGMOID_R: case PDMP_MATH_POS_R: launch = pdmp::launch_math_eval_logrows; break;
+    default: return fail(PDMP_ERR_INVALID, "pdmp_debug_math_eval: unknown function id %d", fn);
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(PDMP_ERR_NO_DEVICE, "no HIP device visible");
+    HIP_TRY(hipSetDevice(device));
+    DevBuf<double> in, res;
+    PDMP_TRY(upload_abc(in, n, a, b, c));
+    PDMP_TRY(res.alloc((size_t)(2 * n)));
+    int rc = launch(fn, n, in.p, in.p + n, in.p + 2 * n, res.p, nullptr);
+    LAUNCH_TRY("math eval", rc);
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, res.p, (size_t)(2 * n) * sizeof(double), hipMemcpyDeviceToHost));
+    return PDMP_OK;
+#endif
+}
+
+pdmp_status pdmp_debug_set_kernel(pdmp_ensemble* e, int kernel) {
+    if (!e) return fail(PDMP_ERR_INVALID, "null argument");
+    if (kernel != PDMP_DEBUG_KERNEL_AUTO && kernel != PDMP_DEBUG_KERNEL_SEQ && kernel != PDMP_DEBUG_KERNEL_SPEC4 && kernel != PDMP_DEBUG_KERNEL_SPEC8 &&
+        kernel != PDMP_DEBUG_KERNEL_EXACTP)
+        return fail(PDMP_ERR_INVALID, "unknown kernel selector %d", kernel);
+    if (e->has_flow) return fail(PDMP_ERR_INVALID, "pdmp_debug_set_kernel must precede set_flow_*");
+    e->dbg_kernel = kernel;
+    return PDMP_OK;
+}
+pdmp_status pdmp_debug_set_spec_g2(pdmp_ensemble* e, int on) {
+    if (!e) return fail(PDMP_ERR_INVALID, "null argument");
+    e->dbg_spec_g2 = on ? 1 : 0;
+    return PDMP_OK;
+}
+pdmp_status pdmp_debug_set_phase_profile(pdmp_ensemble* e, int on) {
+    if (!e) return fail(PDMP_ERR_INVALID, "null argument");
+    e->dbg_phase = on ? 1 : 0;
+    e->dbg_phase_valid = 0;
+    return PDMP_OK;
+}
+pdmp_status pdmp_debug_phase_profile(pdmp_ensemble* e, double* out16, int* kind) {
+    if (!e || !out16) return fail(PDMP_ERR_INVALID, "null argument");
+    if (!e->dbg_phase_valid) return fail(PDMP_ERR_INVALID, "no phase profile recorded by the last run");
+    memcpy(out16, e->dbg_phase_out, sizeof e->dbg_phase_out);
+    if (kind) *kind = e->dbg_phase_valid;
+    return PDMP_OK;
+}
+pdmp_status pdmp_debug_last_kernel(pdmp_ensemble* e, char* out, int64_t cap) {
+    if (!e || !out || cap < 1) return fail(PDMP_ERR_INVALID, "null argument");
+    snprintf(out, (size_t)cap, "%s", e->last_kernel);
+    return PDMP_OK;
+}
+pdmp_status pdmp_debug_set_track_groups(pdmp_ensemble* e, int on) {
+    if (!e) return fail(PDMP_ERR_INVALID, "null argument");
+    e->dbg_track_groups = (on == 1) ? 1 : 0;
+    return PDMP_OK;
+}
+pdmp_status pdmp_debug_set_track_lines(pdmp_ensemble* e, int mode) {
+    if (!e || mode < -1 || mode > 1) return fail(PDMP_ERR_INVALID, "track lines: -1 (by ensemble width), 0 (never), 1 (wherever the layout serves)");
+    e->dbg_track_lines = mode;
+    return PDMP_OK;
+}
+pdmp_status pdmp_debug_buffer_addresses(pdmp_ensemble* e, uint64_t* out8) {
+    // where the state lives: tracked records, (key, t_old) pairs, trace slots, chain headers, canonical records, keys, the consts, the blob
+    if (!e || !out8) return fail(PDMP_ERR_INVALID, "null argument");
+    out8[0] = (uint64_t)(uintptr_t)e->d_trk.p;
+    out8[1] = (uint64_t)(uintptr_t)e->d_kp.p;
+    out8[2] = (uint64_t)(uintptr_t)e->d_ev.p;
+    out8[3] = (uint64_t)(uintptr_t)e->d_hdr.p;
+    out8[4] = (uint64_t)(uintptr_t)e->d_rec.p;
+    out8[5] = (uint64_t)(uintptr_t)e->d_keys.p;
+    out8[6] = (uint64_t)(uintptr_t)e->d_cc.p;
+    out8[7] = (uint64_t)(uintptr_t)e->d_blob.p;
+    return PDMP_OK;
+}
+pdmp_status pdmp_debug_set_placement(pdmp_ensemble* e, int tune, int place, const char* rec, const char* kp, const char* ev) {
+    if (!e || tune < -1 || tune > 1 || place < 0 || place > 1) return fail(PDMP_ERR_INVALID, "placement: tune -1 (keep) / 0 / 1, place 0 / 1");
+    for (const char* ptn : {rec, kp, ev})
+        for (const char* q = ptn; q && *q; ++q)
+            if (*q < '0' || *q > '2') return fail(PDMP_ERR_INVALID, "placement: a class pattern is a string of the digits 0, 1, 2");
+    if (tune >= 0) e->place_tune = tune;
+    e->place_cfg.enabled = place;
+    e->place_cfg.rec = rec ? rec : "";
+    e->place_cfg.kp = kp ? kp : "";
+    e->place_cfg.ev = ev ? ev : "";
+    return PDMP_OK;
+}
+pdmp_status pdmp_debug_placement(pdmp_ensemble* e, char* buf, size_t nbuf) {
+    // how the large arrays were laid over the device's memory classes (pdmp_place.hip): "records 012012012 (31 chunks walked, 0.92 s); ..."
+    if (!e || !buf || nbuf == 0) return fail(PDMP_ERR_INVALID, "null argument");
+    std::string r;
+    auto add = [&](const char* name, const pdmp::Placement& p, size_t bytes) {
+        if (bytes < ((size_t)256 << 20)) return;
+        char t[160];
+        if (p.va) snprintf(t, sizeof t, "%s%s %s (%zu chunks walked, %.2f s)", r.empty() ? "" : "; ", name, p.classes.c_str(), p.walked, p.seconds);
+        else snprintf(t, sizeof t, "%s%s hipMalloc (%.1f GB)", r.empty() ? "" : "; ", name, bytes / 1073741824.0);
+        r += t;
+    };
+    add("records", e->d_rec.placed, e->d_rec.n * sizeof(pdmp::ZzRec));
+    add("pairs", e->d_kp.placed, e->d_kp.n * sizeof(double));
+    add("keys", e->d_keys.placed, e->d_keys.n * sizeof(double));
+    add("trace", e->d_ev.placed, e->d_ev.n * sizeof(pdmp_event));
+    add("lines", e->d_tl_lines.placed, e->d_tl_lines.n * sizeof(pdmp::TrLine));
+    if (!e->tune_log.empty()) r += (r.empty() ? "" : "; ") + e->tune_log;
+    snprintf(buf, nbuf, "%s", r.c_str());
+    return PDMP_OK;
+}
+pdmp_status pdmp_debug_move_buffer(pdmp_ensemble* e, int which) {
+    if (!e || !e->has_state) return fail(PDMP_ERR_INVALID, "move buffer: an ensemble with a state");
+    if ((which >= 6) != (e->cfg.sampler == PDMP_SAMPLER_BPS)) return fail(PDMP_ERR_INVALID, "move buffer: 6-10 are the Bouncy Particle's arrays, 0-5 the ZigZag's");
+    HIP_TRY(device_sync(e));
+    // a copy of the array in newly allocated memory; the old allocation is KEPT (so the copy cannot land on the same pages) until the process ends
+    auto move_buf = [](auto& b) -> hipError_t {
+        if (!b.p || b.n == 0) return hipSuccess;
+        void* np = nullptr;
+        const size_t bytes = b.n * sizeof(*b.p);
+        hipError_t r = hipMalloc(&np, bytes);
+        if (r != hipSuccess) return r;
+        r = hipMemcpy(np, b.p, bytes, hipMemcpyDeviceToDevice);
+        if (r != hipSuccess) return r;
+        b.p = static_cast<decltype(b.p)>(np);
+        return hipSuccess;
+    };
+    switch (which) {
+        case 0: HIP_TRY(move_buf(e->d_rec)); break;
+        case 1: HIP_TRY(move_buf(e->d_kp)); break;
+        case 2: HIP_TRY(move_buf(e->d_ev)); break;
+        case 3: HIP_TRY(move_buf(e->d_hdr)); break;
+        case 4: HIP_TRY(move_buf(e->d_cc)); break;
+        case 5: HIP_TRY(move_buf(e->d_keys)); break;
+        case 6: HIP_TRY(move_buf(e->b_ev_x)); break;
+        case 7: HIP_TRY(move_buf(e->b_ev_th)); break;
+        case 8: HIP_TRY(move_buf(e->b_x)); break;
+        case 9: HIP_TRY(move_buf(e->b_th)); break;
+        case 10: HIP_TRY(move_buf(e->b_ev_t)); break;
+        default: return fail(PDMP_ERR_INVALID, "move buffer: 0 records, 1 pairs, 2 trace, 3 headers, 4 constants, 5 keys; BPS: 6 / 7 event x / theta, 8 / 9 x / theta, 10 event t");
+    }
+    return PDMP_OK;
+}
+pdmp_status pdmp_debug_set_helper_wave(pdmp_ensemble* e, int mode) {
+    if (!e || mode < -1 || mode > 1) return fail(PDMP_ERR_INVALID, "helper wave: -1 (by occupancy), 0 (never), 1 (always)");
+    e->dbg_helper_wave = mode;
+    return PDMP_OK;
+}
+pdmp_status pdmp_debug_set_consumer_overlap(pdmp_ensemble* e, int mode) {
+    if (!e || mode < -1 || mode > 1) return fail(PDMP_ERR_INVALID, "consumer overlap: -1 (by width), 0 (between slices), 1 (beside the next slice)");
+    e->dbg_cons_overlap = mode;
+    return PDMP_OK;
+}
+pdmp_status pdmp_debug_set_launch_count_limit(pdmp_ensemble* e, uint32_t n) {
+    if (!e) return fail(PDMP_ERR_INVALID, "null argument");
+    e->dbg_count_limit = n;
+    return PDMP_OK;
+}
+pdmp_status pdmp_debug_set_helper_steering(pdmp_ensemble* e, double gain, int target, double ahead) {
+    // (zz_local_trackl reads them as block minima per quantum and events per window: hence the wide range of the first)
+    if (!e || !(gain > 0.0 && gain <= 4096.0) || target < 1 || target > 64 || !(ahead >= 0.0))
+        return fail(PDMP_ERR_INVALID, "helper steering: 0 < gain <= 4096 (<= 1 for the two-wave form), 1 <= target <= 64, ahead >= 0");
+    e->dbg_hw_steer[0] = gain;
+    e->dbg_hw_steer[1] = (double)target;
+    e->dbg_hw_steer[2] = ahead;
+    return PDMP_OK;
+}
+pdmp_status pdmp_debug_set_logistic_rows(pdmp_ensemble* e, int w) {
+    if (!e || (w != -1 && w != 0 && w != 16 && w != 32)) return fail(PDMP_ERR_INVALID, "row width: -1 (default), 0 (one chain per wavefront), 16 or 32");
+#ifndef PDMP_EXTRA_KERNELS
+    if (w > 0) return fail(PDMP_ERR_UNSUPPORTED, "zz_logistic_rows_kernel is not part of this library: it lives in the parity build (build.py --variant parity, -DPDMP_EXTRA_KERNELS)");
+#endif
+    e->dbg_lg_rows = w;
+    return PDMP_OK;
+}
+pdmp_status pdmp_debug_set_proposal_dump(pdmp_ensemble* e, int64_t n) {
+    if (!e || n < 0) return fail(PDMP_ERR_INVALID, "bad argument");
+    e->dbg_dump = n;
+    return PDMP_OK;
+}
+
+// Test hook (include/pdmp_debug.h): n given events behind what `chain`'s current trace segment holds, counted in its header as a run would have
+// counted them -- the consumers, trace_copy, trace_reset and subtrace_copy see a segment a sampler could never have produced (events exactly at
+// grid times, chains of one coordinate, chosen hash clashes: tests/consumer_cases.py).  No kernel is launched and no record is touched, so the
+// ensemble cannot run afterwards.
+pdmp_status pdmp_debug_trace_append(pdmp_ensemble* e, int64_t chain, const pdmp_event* ev, int64_t n) {
+    if (!e || (n > 0 && !ev)) return fail(PDMP_ERR_INVALID, "null argument");
+    NEED_FACTORISED(e);
+    if (!e->consuming || !e->has_state) return fail(PDMP_ERR_INVALID, "pdmp_ensemble_consume_begin first");
+    if (chain < 0 || chain >= e->cfg.nchains || n < 0) return fail(PDMP_ERR_INVALID, "bad argument");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(device_sync(e));  // (a deferred asynchronous consumer is launched and waited for: it reads the other buffer and the headers' snapshot)
+    pdmp::DevChain h;
+    HIP_TRY(hipMemcpy(&h, e->d_hdr.p + chain, sizeof h, hipMemcpyDeviceToHost));
+    const int64_t cap = e->cfg.trace_capacity;
+    if (h.c.ntrace > (uint64_t)cap || n > cap - (int64_t)h.c.ntrace)
+        return fail(PDMP_ERR_INVALID, "trace_append: %lld events behind %llu do not fit trace_capacity = %lld", (long long)n, (unsigned long long)h.c.ntrace, (long long)cap);
+    if (n > 0) HIP_TRY(hipMemcpy(e->d_ev.p + chain * cap + (int64_t)h.c.ntrace, ev, (size_t)n * sizeof(pdmp_event), hipMemcpyHostToDevice));
+    h.c.ntrace += (uint64_t)n;
+    h.c.nevents += (uint64_t)n;
+    HIP_TRY(hipMemcpy(&e->d_hdr.p[chain].c, &h.c, sizeof h.c, hipMemcpyHostToDevice));
+    e->trace_appended = true;
+    return PDMP_OK;
+}
+
+// What the host could drain instead: `bytes` of the trace buffer copied to pinned host memory, in GB/s (a measurement for bench.py's pipeline
+// object, not a code path of the engine)
+pdmp_status pdmp_debug_host_drain_probe(pdmp_ensemble* e, int64_t bytes, double* gbps) {
+    if (!e || !gbps || bytes <= 0) return fail(PDMP_ERR_INVALID, "bad argument");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    const size_t have = e->d_ev.n * sizeof(pdmp_event);
+    const size_t nb = std::min<size_t>((size_t)bytes, have);
+    if (nb == 0) return fail(PDMP_ERR_INVALID, "ensemble was created with trace_capacity = 0");
+    void* host = nullptr;
+    HIP_TRY(hipHostMalloc(&host, nb, hipHostMallocDefault));
+    hipError_t err = device_sync(e);
+    if (err == hipSuccess) err = hipMemcpy(host, e->d_ev.p, nb, hipMemcpyDeviceToHost);  // (warm-up: page tables, the copy engine's first touch)
+    const auto t0 = std::chrono::steady_clock::now();
+    if (err == hipSuccess) err = hipMemcpy(host, e->d_ev.p, nb, hipMemcpyDeviceToHost);
+    const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    (void)hipHostFree(host);
+    if (err != hipSuccess) return fail(PDMP_ERR_HIP, "hipMemcpy: %s", hipGetErrorString(err));
+    *gbps = (double)nb / secs / 1e9;
+    return PDMP_OK;
+}
+
+pdmp_status pdmp_debug_sticky_eval(int device, int fn, int64_t n, const double* a, const double* b, const double* c, double* out) {
+    if (!a || !b || !c || !out || n <= 0 || n > ((int64_t)1 << 30)) return fail(PDMP_ERR_INVALID, "bad argument");
+    if (fn < 0 || fn > 2) return fail(PDMP_ERR_INVALID, "pdmp_debug_sticky_eval: fn 0 (atan), 1 (linear freezing time) or 2 (Boomerang freezing time)");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(PDMP_ERR_NO_DEVICE, "no HIP device visible");
+    HIP_TRY(hipSetDevice(device));
+    DevBuf<double> in, res;
+    PDMP_TRY(upload_abc(in, n, a, b, c));
+    PDMP_TRY(res.alloc((size_t)n));
+    LAUNCH_TRY("sticky eval", pdmp::launch_bps_sticky_eval(fn, n, in.p, in.p + n, in.p + 2 * n, res.p, nullptr));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, res.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    return PDMP_OK;
+}
+}  // extern "C"

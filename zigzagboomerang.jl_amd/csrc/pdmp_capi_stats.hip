@@ -1,0 +1,413 @@
+// pdmp_capi_stats.hip -- what is computed from a run on the device: batch means, ESS sums, path integrals, the trace consumers.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "pdmp_ensemble.hpp"
+
+static pdmp_status ess_ready(pdmp_ensemble* e) {
+    if (!e) return fail(PDMP_ERR_INVALID, "null argument");
+    if (e->cfg.sampler == PDMP_SAMPLER_BPS && e->bps.mom < 1)
+        return fail(PDMP_ERR_INVALID, "path integrals are kept by the factorised samplers only");  // (and by a BPS ensemble with moments on)
+    if (!e->has_state) return fail(PDMP_ERR_INVALID, "no state");
+    if (e->cfg.sampler == PDMP_SAMPLER_BPS) return PDMP_OK;
+    if (!e->keep_integrals) return fail(PDMP_ERR_INVALID, "the path integrals were switched off (pdmp_ensemble_set_path_integrals)");
+    if (e->flow_kind != 0)
+        return fail(PDMP_ERR_UNSUPPORTED, "path integrals assume the linear flow of the ZigZag (FactBoomerang rotates between events)");
+    return PDMP_OK;
+}
+
+// The factorised counterpart of bps_moments_at's rule.  J_i(T) = I_i + dt (x_i + θ_i dt / 2), dt = T - t_i, is the integral of the sampled path
+// only where no event of the chain lies between a coordinate's clock and T: every chain PDMP_CHAIN_OK (a chain that stopped short of the
+// horizon -- TRACE_FULL, PAUSED, BOUND_VIOLATED, STALLED -- would be extrapolated through events it has not sampled yet), T not before the
+// latest proposal the chain has processed (a reference-tail run passes its horizon: the coordinate that reflected there would be extrapolated
+// backwards with its new velocity) and T not beyond the horizon of the last run (t0 before the first).  Without a refresh clock the
+// proposals come off the queue in time order and the header's t_last, the time of the last one, is the latest; with one they do not
+// (src/sfact.jl:84-85 re-bounds at stale clocks), t_last may lie below an earlier proposal, and the only T known to be at or past all of
+// them is the horizon of a run that stopped before it.  With t0 != 0 the first proposals lie before t0 (the reference draws the first
+// queue times without adding t0): t_last <= T holds for them as it must.  One copy of the chain headers per read; nothing on the hot path.
+static pdmp_status fact_integrals_at(pdmp_ensemble* e, double T) {
+    const int64_t n = e->cfg.nchains;
+    if (!(T <= e->run_T))
+        return fail(PDMP_ERR_INVALID, "T = %.17g lies past the horizon %.17g of the last run (t0 before the first): the path is not sampled there "
+                                      "(run to T with PDMP_RUN_STOP_BEFORE)", T, e->run_T);
+    if (e->lambda_ref > 0 && T != e->run_T)
+        return fail(PDMP_ERR_INVALID, "T = %.17g is not the horizon %.17g of the last run: with a refresh clock the proposals are not processed in "
+                                      "time order and the path integrals are read at the end of a PDMP_RUN_STOP_BEFORE run only", T, e->run_T);
+    std::vector<pdmp::DevChain> h((size_t)n);
+    HIP_TRY(hipMemcpy(h.data(), e->d_hdr.p, h.size() * sizeof(pdmp::DevChain), hipMemcpyDeviceToHost));
+    for (int64_t k = 0; k < n; ++k) {
+        const uint32_t cs = h[(size_t)k].c.status;
+        const double tl = h[(size_t)k].c.t_last;
+        if (cs != PDMP_CHAIN_OK)
+            return fail(PDMP_ERR_INVALID, "chain %lld: status %u at t = %.17g (trace full / paused / bound violated / stalled): it has not reached "
+                                          "T = %.17g, its path integrals are not defined there (drain and run again)", (long long)k, cs, tl, T);
+        if (!(tl <= T))
+            return fail(PDMP_ERR_INVALID, "chain %lld: T = %.17g lies before the chain's last proposal at %.17g (a reference-tail run passes T; "
+                                          "run to T with PDMP_RUN_STOP_BEFORE)", (long long)k, T, tl);
+    }
+    return PDMP_OK;
+}
+
+// one step (mode 0 begin, 1 batch, 2 end) of the ESS sums over [Ta, Tb]; J: where a BPS ensemble's moments at Tb lie (the factorised samplers read their records)
+static int launch_ess(pdmp_ensemble* e, const double* J, int mode, double Ta, double Tb) {
+    const int64_t d = e->cfg.d, n = e->cfg.nchains;
+    return e->cfg.sampler == PDMP_SAMPLER_BPS ? pdmp::launch_dense_ess(J, e->d_jprev.p, e->d_jstart.p, d, n, mode, Ta, Tb, e->d_essacc.p, e->stream)
+                                              : pdmp::launch_zz_ess(e->d_rec.p, e->track ? 128 : 64, e->d_jprev.p, e->d_jstart.p, d, n, mode, Ta, Tb, e->d_essacc.p, e->stream);
+}
+
+// consume_mean / consume_inclusion: one [n x d] reduction of the cursors of chains [chain_first, chain_first + n) and the chains' last event times;
+// `launch` fills the two device buffers it is given
+template <class Launch>
+static pdmp_status consume_reduce(pdmp_ensemble* e, int64_t chain_first, int64_t n, double* out, double* T_last, const char* name, Launch launch) {
+    if (!e || !out) return fail(PDMP_ERR_INVALID, "null argument");
+    if (!e->consuming) return fail(PDMP_ERR_INVALID, "pdmp_ensemble_consume_begin first");
+    if (chain_first < 0 || n <= 0 || chain_first + n > e->cfg.nchains) return fail(PDMP_ERR_INVALID, "chain range");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(device_sync(e));  // (asynchronous consumers run on a second stream)
+    const int64_t d = e->cfg.d;
+    DevBuf<double> bm, bt;
+    PDMP_TRY(bm.alloc((size_t)(n * d)));
+    PDMP_TRY(bt.alloc((size_t)n));
+    LAUNCH_TRY(name, launch(bm.p, bt.p));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipMemcpy(out, bm.p, (size_t)(n * d) * sizeof(double), hipMemcpyDeviceToHost));
+    if (T_last) HIP_TRY(hipMemcpy(T_last, bt.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    return PDMP_OK;
+}
+
+extern "C" {
+
+pdmp_status pdmp_ensemble_batch_means(pdmp_ensemble* e, double T_prev, double T, double* sum_y, double* sum_y2) {
+    PDMP_TRY(ess_ready(e));
+    if (!(T > T_prev)) return fail(PDMP_ERR_INVALID, "T must exceed T_prev");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(device_sync(e));
+    const int64_t d = e->cfg.d, n = e->cfg.nchains;
+    const bool bps = e->cfg.sampler == PDMP_SAMPLER_BPS;
+    if (bps) PDMP_TRY(bps_moments_at(e, T, 0, n, false));  // J1(T) of every chain into b_jT (the validity rule first)
+    if (!bps) PDMP_TRY(fact_integrals_at(e, T));  // (before jprev is allocated or touched)
+    if (e->d_jprev.n != (size_t)(n * d)) {
+        PDMP_TRY(e->d_jprev.alloc((size_t)(n * d)));
+        HIP_TRY(hipMemsetAsync(e->d_jprev.p, 0, (size_t)(n * d) * sizeof(double), e->stream));  // (same stream as the kernel: the ensemble's stream is non-blocking, the null stream does not order against it)
+    }
+    if (e->d_sum.n != (size_t)(2 * d)) PDMP_TRY(e->d_sum.alloc((size_t)(2 * d)));
+    if (!bps) PDMP_TRY(ensure_canon(e));
+    HIP_TRY(hipMemsetAsync(e->d_sum.p, 0, (size_t)(2 * d) * sizeof(double), e->stream));
+    int rc = bps ? pdmp::launch_dense_batch_means(e->b_jT.p, e->d_jprev.p, d, n, T_prev, T, e->d_sum.p, e->d_sum.p + d, e->stream)
+                 : pdmp::launch_zz_batch_means(e->d_rec.p, e->track ? 128 : 64, e->d_jprev.p, d, n, T_prev, T, e->d_sum.p, e->d_sum.p + d,
+                                               e->stream);
+    LAUNCH_TRY("batch_means", rc);
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (sum_y) HIP_TRY(hipMemcpy(sum_y, e->d_sum.p, (size_t)d * sizeof(double), hipMemcpyDeviceToHost));
+    if (sum_y2) HIP_TRY(hipMemcpy(sum_y2, e->d_sum.p + d, (size_t)d * sizeof(double), hipMemcpyDeviceToHost));
+    return PDMP_OK;
+}
+
+pdmp_status pdmp_ensemble_ess_begin(pdmp_ensemble* e, double T0) {
+    PDMP_TRY(ess_ready(e));
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(device_sync(e));
+    const int64_t d = e->cfg.d, n = e->cfg.nchains;
+    const bool bps = e->cfg.sampler == PDMP_SAMPLER_BPS;
+    if (bps) PDMP_TRY(bps_moments_at(e, T0, 0, n, false));
+    if (!bps) PDMP_TRY(fact_integrals_at(e, T0));
+    if (e->d_jprev.n != (size_t)(n * d)) PDMP_TRY(e->d_jprev.alloc((size_t)(n * d)));
+    if (e->d_jstart.n != (size_t)(n * d)) PDMP_TRY(e->d_jstart.alloc((size_t)(n * d)));
+    if (e->d_essacc.n != (size_t)(4 * d)) PDMP_TRY(e->d_essacc.alloc((size_t)(4 * d)));
+    if (!bps) PDMP_TRY(ensure_canon(e));
+    HIP_TRY(hipMemsetAsync(e->d_essacc.p, 0, (size_t)(4 * d) * sizeof(double), e->stream));
+    LAUNCH_TRY("ess", launch_ess(e, e->b_jT.p, 0, T0, T0));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->ess_T0 = e->ess_Tlast = T0;
+    e->ess_batches = 0;
+    return PDMP_OK;
+}
+
+pdmp_status pdmp_ensemble_ess_batch(pdmp_ensemble* e, double T) {
+    PDMP_TRY(ess_ready(e));
+    if (e->ess_batches < 0) return fail(PDMP_ERR_INVALID, "pdmp_ensemble_ess_begin first");
+    if (!(T > e->ess_Tlast)) return fail(PDMP_ERR_INVALID, "batch end %g does not exceed the previous one %g", T, e->ess_Tlast);
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(device_sync(e));
+    if (e->cfg.sampler == PDMP_SAMPLER_BPS) {
+        PDMP_TRY(bps_moments_at(e, T, 0, e->cfg.nchains, false));
+    } else {
+        PDMP_TRY(fact_integrals_at(e, T));
+        PDMP_TRY(ensure_canon(e));
+    }
+    LAUNCH_TRY("ess", launch_ess(e, e->b_jT.p, 1, e->ess_Tlast, T));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->ess_Tlast = T;
+    e->ess_batches += 1;
+    return PDMP_OK;
+}
+
+pdmp_status pdmp_ensemble_ess_end(pdmp_ensemble* e, double* sum_y, double* sum_y2, double* sum_m, double* sum_m2,
+                                  int64_t* nbatches, double* T0, double* T1) {
+    PDMP_TRY(ess_ready(e));
+    if (e->ess_batches < 1) return fail(PDMP_ERR_INVALID, "no batch accumulated (ess_begin, then ess_batch)");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    const int64_t d = e->cfg.d;
+    const bool bps = e->cfg.sampler == PDMP_SAMPLER_BPS;
+    if (!bps) PDMP_TRY(ensure_canon(e));
+    HIP_TRY(hipMemsetAsync(e->d_essacc.p + 2 * d, 0, (size_t)(2 * d) * sizeof(double), e->stream));
+    // (BPS: J at the last batch end is the jprev that batch left -- the state may since have run past it)
+    LAUNCH_TRY("ess", launch_ess(e, e->d_jprev.p, 2, e->ess_T0, e->ess_Tlast));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    double* outs[4] = {sum_y, sum_y2, sum_m, sum_m2};
+    for (int k = 0; k < 4; ++k)
+        if (outs[k]) HIP_TRY(hipMemcpy(outs[k], e->d_essacc.p + k * d, (size_t)d * sizeof(double), hipMemcpyDeviceToHost));
+    if (nbatches) *nbatches = e->ess_batches;
+    if (T0) *T0 = e->ess_T0;
+    if (T1) *T1 = e->ess_Tlast;
+    return PDMP_OK;
+}
+
+pdmp_status pdmp_ensemble_consume_begin(pdmp_ensemble* e, double grid_dt, int64_t grid_points) {
+    if (!e) return fail(PDMP_ERR_INVALID, "null argument");
+    NEED_FACTORISED(e);
+    if (!e->has_state || e->ran) return fail(PDMP_ERR_INVALID, "consume_begin follows set_state and precedes the first run (it snapshots x0, θ0)");
+    if (e->cfg.trace_capacity <= 0) return fail(PDMP_ERR_INVALID, "ensemble was created with trace_capacity = 0");
+    if (e->flow_kind != 0 || e->lambda_ref > 0)
+        return fail(PDMP_ERR_UNSUPPORTED, "the device consumers take time-ordered traces of piecewise-linear paths: ZigZag without refresh clock");
+    if (grid_points < 0 || (grid_points > 0 && !(grid_dt > 0))) return fail(PDMP_ERR_INVALID, "grid_dt must be positive");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    const int64_t d = e->cfg.d, n = e->cfg.nchains;
+    e->cons_z = e->cfg.sampler == PDMP_SAMPLER_STICKY_ZIGZAG;  // (the time away from 0, inclusion_prob: a sum of its own where coordinates can freeze)
+    PDMP_TRY(e->d_ccur.alloc((size_t)(n * d) * pdmp::consume_cursor_bytes(e->cons_z)));
+    PDMP_TRY(e->d_cmeta.alloc((size_t)n * pdmp::consume_meta_bytes()));
+    e->d_cgrid.release();
+    if (grid_points > 0) {
+        PDMP_TRY(e->d_cgrid.alloc((size_t)(n * grid_points * d)));
+        HIP_TRY(hipMemsetAsync(e->d_cgrid.p, 0, (size_t)(n * grid_points * d) * sizeof(double), e->stream));
+    }
+    PDMP_TRY(ensure_canon(e));
+    discard_async_consumer(e);
+    e->cons_cummean = false;
+    LAUNCH_TRY("consume_init", pdmp::launch_consume_init(e->d_rec.p, e->track ? 128 : 64, d, n, e->t0_state, e->d_ccur.p, e->cons_z, e->d_cmeta.p,
+                                       grid_points > 0 ? e->d_cgrid.p : nullptr, grid_points, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->consuming = true;
+    e->cons_dt = grid_dt;
+    e->cons_K = grid_points;
+    return PDMP_OK;
+}
+
+pdmp_status pdmp_ensemble_consume(pdmp_ensemble* e) {
+    if (!e) return fail(PDMP_ERR_INVALID, "null argument");
+    if (!e->consuming || !e->has_state) return fail(PDMP_ERR_INVALID, "pdmp_ensemble_consume_begin first");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(device_sync(e));
+    LAUNCH_TRY("consume", pdmp::launch_consume_events(e->d_ev.p, e->cfg.trace_capacity, e->d_hdr.p, nullptr, e->cfg.d, e->cfg.nchains, e->d_ccur.p, e->cons_z, e->d_cmeta.p,
+                                         e->d_cgrid.p, e->cons_K, e->t0_state, e->cons_dt, e->stream, e->cons_cummean ? e->d_ccm.p : nullptr));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return PDMP_OK;
+}
+
+// cummean(Ξ) on the device (src/trace.jl:203-226): with it enabled, pdmp_ensemble_consume also leaves, for every event of the segment it consumes, the
+// running pair (t_i, Σ (x_prev + x_k)(t_k − t_prev) / (2 t_i)) of the event's coordinate -- the cursors carry the sums from segment to segment, so the
+// pairs are those of the whole run's trace.  Enable after consume_begin (the synchronous consumer only).
+pdmp_status pdmp_ensemble_consume_cummean(pdmp_ensemble* e, int enable) {
+    if (!e) return fail(PDMP_ERR_INVALID, "null argument");
+    if (!e->consuming) return fail(PDMP_ERR_INVALID, "pdmp_ensemble_consume_begin first");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    if (enable) {
+        const size_t n = (size_t)e->cfg.nchains * (size_t)e->cfg.trace_capacity * 2;
+        if (e->d_ccm.n != n) PDMP_TRY(e->d_ccm.alloc(n));
+    }
+    e->cons_cummean = enable != 0;
+    return PDMP_OK;
+}
+// ... the pairs of slots [first, first + count) of `chain`'s segment (the same slots pdmp_ensemble_trace_copy returns the events of)
+pdmp_status pdmp_ensemble_consume_cummean_copy(pdmp_ensemble* e, int64_t chain, int64_t first, int64_t count, double* t_out, double* y_out) {
+    if (!e || !t_out || !y_out) return fail(PDMP_ERR_INVALID, "null argument");
+    if (!e->cons_cummean) return fail(PDMP_ERR_INVALID, "pdmp_ensemble_consume_cummean(ens, 1) first");
+    if (chain < 0 || chain >= e->cfg.nchains || first < 0 || count < 0 || first + count > e->cfg.trace_capacity) return fail(PDMP_ERR_INVALID, "range out of bounds");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(device_sync(e));
+    std::vector<double> pairs((size_t)count * 2);
+    if (count) HIP_TRY(hipMemcpy(pairs.data(), e->d_ccm.p + 2 * (chain * e->cfg.trace_capacity + first), (size_t)count * 2 * sizeof(double), hipMemcpyDeviceToHost));
+    for (int64_t k = 0; k < count; ++k) {
+        t_out[k] = pairs[(size_t)(2 * k)];
+        y_out[k] = pairs[(size_t)(2 * k + 1)];
+    }
+    return PDMP_OK;
+}
+
+// subtrace(Ξ, J) on the device (src/trace.jl:275-290): the events of `chain`'s current segment whose coordinate lies in the ascending index set J,
+// renumbered by their position in J, compacted by a kernel and copied out (n_out: how many there are; at most out_cap are written)
+pdmp_status pdmp_ensemble_subtrace_copy(pdmp_ensemble* e, int64_t chain, const int64_t* J, int64_t nJ, pdmp_event* out, int64_t out_cap, int64_t* n_out) {
+    if (!e || !J || !n_out || (out_cap > 0 && !out)) return fail(PDMP_ERR_INVALID, "null argument");
+    NEED_FACTORISED(e);
+    if (e->cfg.trace_capacity <= 0) return fail(PDMP_ERR_INVALID, "ensemble was created with trace_capacity = 0");
+    if (chain < 0 || chain >= e->cfg.nchains || nJ < 0 || out_cap < 0) return fail(PDMP_ERR_INVALID, "bad argument");
+    const int64_t d = e->cfg.d;
+    std::vector<int32_t> loc((size_t)d, -1);
+    for (int64_t k = 0; k < nJ; ++k) {
+        if (J[k] < 0 || J[k] >= d || (k > 0 && J[k] <= J[k - 1])) return fail(PDMP_ERR_INVALID, "J must be ascending coordinates in [0, d) (@assert issorted(J), src/trace.jl:276)");
+        loc[(size_t)J[k]] = (int32_t)k;
+    }
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(device_sync(e));
+    pdmp::DevChain h;
+    HIP_TRY(hipMemcpy(&h, e->d_hdr.p + chain, sizeof h, hipMemcpyDeviceToHost));
+    const int64_t n = (int64_t)std::min<uint64_t>(h.c.ntrace, (uint64_t)e->cfg.trace_capacity);
+    DevBuf<int32_t> dloc;
+    DevBuf<pdmp_event> dout;
+    DevBuf<unsigned long long> dn;
+    PDMP_TRY(dloc.upload(loc));
+    PDMP_TRY(dout.alloc((size_t)std::max<int64_t>(out_cap, 1)));
+    PDMP_TRY(dn.alloc(1));
+    LAUNCH_TRY("trace_subtrace", pdmp::launch_trace_subtrace(e->d_ev.p + chain * e->cfg.trace_capacity, n, dloc.p, dout.p, out_cap, dn.p, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    unsigned long long cnt = 0;
+    HIP_TRY(hipMemcpy(&cnt, dn.p, sizeof cnt, hipMemcpyDeviceToHost));
+    *n_out = (int64_t)cnt;
+    const int64_t ncopy = std::min<int64_t>((int64_t)cnt, out_cap);
+    if (ncopy > 0) HIP_TRY(hipMemcpy(out, dout.p, (size_t)ncopy * sizeof(pdmp_event), hipMemcpyDeviceToHost));
+    return PDMP_OK;
+}
+
+// The consumer beside the sampler: what the last launch wrote is handed to the consumers on a SECOND stream, and the segments come back empty at
+// once -- the next pdmp_ensemble_run writes the other of two trace buffers while this slice is consumed (a C3 slice is 1.7 GB of events: at the
+// sampler's rate the host could not drain it over PCIe; src/sfact.jl:211 returns Ξ, and discretize / mean are what every caller does with it next,
+// src/trace.jl:106-125,182-200).  Stream order: [run k] -> snapshot of the per-chain counts + reset (run stream) -> consumer k (second stream,
+// after the snapshot); run k + 1 waits for consumer k − 1, which read the buffer it is about to write.  Returns without waiting.
+pdmp_status pdmp_ensemble_consume_async(pdmp_ensemble* e, void* stream) {
+    if (!e) return fail(PDMP_ERR_INVALID, "null argument");
+    if (!e->consuming || !e->has_state) return fail(PDMP_ERR_INVALID, "pdmp_ensemble_consume_begin first");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+    const int64_t n = e->cfg.nchains;
+    PDMP_TRY(launch_deferred_consumer(e));  // (two calls without a run between them)
+    if (!e->stream2) {
+        // created into locals and committed to the ensemble together: a failure half-way leaves nothing behind that a later call would trust
+        int least = 0, greatest = 0;
+        HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
+        hipStream_t s2 = nullptr;
+        hipEvent_t evs[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+        hipError_t err = hipStreamCreateWithPriority(&s2, hipStreamNonBlocking, least);  // (the event loop's launches go first)
+        for (int q = 0; q < 5 && err == hipSuccess; ++q) err = hipEventCreate(&evs[q]);
+        if (err != hipSuccess) {
+            for (hipEvent_t ev : evs)
+                if (ev) (void)hipEventDestroy(ev);
+            if (s2) (void)hipStreamDestroy(s2);
+            return fail(PDMP_ERR_HIP, "consume_async: stream / event creation failed: %s", hipGetErrorString(err));
+        }
+        e->stream2 = s2;
+        e->ev_run_done = evs[0];
+        e->ev_cons_done[0] = evs[1];
+        e->ev_cons_done[1] = evs[2];
+        e->ev_c0 = evs[3];
+        e->ev_c1 = evs[4];
+    }
+    if (e->d_ev2.n != e->d_ev.n) PDMP_TRY(e->d_ev2.alloc(e->d_ev.n));
+    const int k = e->async_k;
+    if (e->d_snap[k].n != (size_t)(2 * n)) PDMP_TRY(e->d_snap[k].alloc((size_t)(2 * n)));
+    LAUNCH_TRY("consume_snapshot", pdmp::launch_consume_snapshot(e->d_hdr.p, n, e->d_snap[k].p, s));
+    HIP_TRY(hipEventRecord(e->ev_run_done, s));
+    pdmp_event* const filled = e->d_ev.p;
+    std::swap(e->d_ev.p, e->d_ev2.p);  // (same sizes) the next launch writes the other buffer ...
+    if (e->cons_pending[k ^ 1]) HIP_TRY(hipStreamWaitEvent(s, e->ev_cons_done[k ^ 1], 0));  // ... once the consumer that read it is done
+    HIP_TRY(hipStreamWaitEvent(e->stream2, e->ev_run_done, 0));
+    e->deferred_buf = filled;
+    e->deferred_k = k;  // (launched behind the next event-loop launch: launch_deferred_consumer)
+    // An ensemble that fills the device is bound by the memory system, and a consumer beside it costs it more than the consumer's own time
+    // (measured on C3, 4096 chains: 39 -> 56 ms per slice beside a 7 ms consumer): there the consumer runs BETWEEN the slices -- the next launch
+    // waits for it -- and the second trace buffer only saves the reset.  Narrower ensembles leave SIMDs idle: the consumer runs beside the next slice.
+    const bool beside = e->dbg_cons_overlap == 1 || (e->dbg_cons_overlap == -1 && e->cfg.nchains <= 2048);
+    if (!beside) {
+        PDMP_TRY(launch_deferred_consumer(e));
+        HIP_TRY(hipStreamWaitEvent(s, e->ev_cons_done[k], 0));
+    }
+    e->async_k = k ^ 1;
+    return PDMP_OK;
+}
+
+// kernel time of the last asynchronous consumer (waits for it)
+pdmp_status pdmp_ensemble_last_consume_ms(pdmp_ensemble* e, float* ms) {
+    if (!e || !ms) return fail(PDMP_ERR_INVALID, "null argument");
+    if (!e->cons_timed && e->deferred_k < 0) return fail(PDMP_ERR_INVALID, "no asynchronous consumer has run");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    PDMP_TRY(launch_deferred_consumer(e));
+    return elapsed_ms(e->ev_c0, e->ev_c1, ms);
+}
+
+pdmp_status pdmp_ensemble_consume_mean(pdmp_ensemble* e, int64_t chain_first, int64_t n, double* mean, double* T_last) {
+    return consume_reduce(e, chain_first, n, mean, T_last, "consume_mean", [&](double* bm, double* bt) {
+        return pdmp::launch_consume_mean(e->cfg.d, chain_first, n, e->d_ccur.p, e->d_cmeta.p, bm, bt, e->stream);
+    });
+}
+
+pdmp_status pdmp_ensemble_consume_inclusion(pdmp_ensemble* e, int64_t chain_first, int64_t n, double* prob, double* T_last) {
+    return consume_reduce(e, chain_first, n, prob, T_last, "consume_inclusion", [&](double* bm, double* bt) {
+        return pdmp::launch_consume_inclusion(e->cfg.d, e->cfg.nchains, e->cons_z, e->t0_state, chain_first, n, e->d_ccur.p, e->d_cmeta.p, bm, bt, e->stream);
+    });
+}
+
+pdmp_status pdmp_ensemble_consume_discretized(pdmp_ensemble* e, int64_t chain, int64_t k_first, int64_t k_count, double* out, int64_t* npoints,
+                                              void** grid_dev) {
+    if (!e) return fail(PDMP_ERR_INVALID, "null argument");
+    if (!e->consuming || e->cons_K <= 0) return fail(PDMP_ERR_INVALID, "pdmp_ensemble_consume_begin with a grid first");
+    if (chain < 0 || chain >= e->cfg.nchains || k_first < 0 || k_count < 0 || k_first + k_count > e->cons_K)
+        return fail(PDMP_ERR_INVALID, "chain / grid range");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(device_sync(e));  // (asynchronous consumers run on a second stream)
+    const int64_t d = e->cfg.d;
+    // the points after every coordinate's last event, up to the chain's last event time (idempotent)
+    LAUNCH_TRY("consume_flush", pdmp::launch_consume_flush(d, e->cfg.nchains, e->d_ccur.p, e->d_cmeta.p, e->d_cgrid.p, e->cons_K, e->t0_state, e->cons_dt, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (out && k_count)
+        HIP_TRY(hipMemcpy(out, e->d_cgrid.p + (chain * e->cons_K + k_first) * d, (size_t)(k_count * d) * sizeof(double), hipMemcpyDeviceToHost));
+    if (npoints) {
+        // collect(discretize(Ξ, dt)) emits a grid time while it lies before the last event (src/trace.jl:111-113); at least t0 itself
+        std::vector<unsigned char> mh(pdmp::consume_meta_bytes());
+        HIP_TRY(hipMemcpy(mh.data(), e->d_cmeta.p + (size_t)chain * pdmp::consume_meta_bytes(), mh.size(), hipMemcpyDeviceToHost));
+        double tl;
+        memcpy(&tl, mh.data() + 8, sizeof tl);
+        // NOT clamped to the grid: a value above grid_points tells the caller that the grid was too short for the run (rows beyond it do not exist)
+        int64_t np = (int64_t)floor((tl - e->t0_state) / e->cons_dt);
+        np = np > 1 ? np - 1 : 0;
+        while (e->t0_state + e->cons_dt * (double)np < tl) ++np;
+        *npoints = np > 0 ? np : 1;
+    }
+    if (grid_dev) *grid_dev = e->d_cgrid.p;
+    return PDMP_OK;
+}
+
+pdmp_status pdmp_ensemble_set_path_integrals(pdmp_ensemble* e, int enable) {
+    if (!e) return fail(PDMP_ERR_INVALID, "null argument");
+    NEED_FACTORISED(e);
+    e->keep_integrals = enable != 0;
+    e->has_state = false;
+    return PDMP_OK;
+}
+
+pdmp_status pdmp_ensemble_path_integrals(pdmp_ensemble* e, double T, int64_t nprobe, const int64_t* probes, double* out) {
+    PDMP_TRY(ess_ready(e));
+    if (!probes || !out || nprobe <= 0) return fail(PDMP_ERR_INVALID, "bad argument");
+    const int64_t d = e->cfg.d, n = e->cfg.nchains;
+    for (int64_t k = 0; k < nprobe; ++k)
+        if (probes[k] < 0 || probes[k] >= d) return fail(PDMP_ERR_INVALID, "probe coordinate %lld out of range", (long long)probes[k]);
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(device_sync(e));
+    DevBuf<int64_t> dp;
+    DevBuf<double> dout;
+    PDMP_TRY(dp.upload(std::vector<int64_t>(probes, probes + nprobe)));
+    PDMP_TRY(dout.alloc((size_t)(n * nprobe)));
+    int rc;
+    if (e->cfg.sampler == PDMP_SAMPLER_BPS) {
+        PDMP_TRY(bps_moments_at(e, T, 0, n, false));
+        rc = pdmp::launch_dense_gather(e->b_jT.p, d, n, dp.p, nprobe, dout.p, e->stream);
+    } else {
+        PDMP_TRY(fact_integrals_at(e, T));
+        PDMP_TRY(ensure_canon(e));
+        rc = pdmp::launch_zz_path_integrals(e->d_rec.p, e->track ? 128 : 64, d, n, dp.p, nprobe, T, dout.p, e->stream);
+    }
+    LAUNCH_TRY("path_integrals", rc);
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipMemcpy(out, dout.p, (size_t)(n * nprobe) * sizeof(double), hipMemcpyDeviceToHost));
+    return PDMP_OK;
+}
+}  // extern "C"
