@@ -78,16 +78,18 @@ struct WL {
     static constexpr uint32_t XO = (NBLK - 2048) * 4;      // (everything behind the bounds moves up by what they take more)
     static constexpr uint32_t LB = 0;                      // [NBLK] u32 lower bounds of the block minima (+ argument position), key blocks of 8
     static constexpr uint32_t EX = XO + 8192;              // [64] f64 what event e exposes; before that the candidates' keys where the ranks need them exactly
-    // (XO + 8704 .. SLB: the candidate / event slots of the forms before the record was pushed from lane to lane: free)
-    static constexpr uint32_t SLB = XO + (HW ? 9792 : 9664);  // [64] u16 event blocks, rank order
-    static constexpr uint32_t TB = XO + (HW ? 9920 : 9792);   // [64] u16 candidate blocks, compaction order
-    static constexpr uint32_t ACL = XO + (HW ? 10048 : 9920); // [8] u16 the accepted events
+    // (XO + 8704 .. SLB: the candidate / event slots of the forms before the record was pushed from lane to lane: free in the two-wave form,
+    // the ring of draws in the one-wave forms)
+    static constexpr uint32_t URING = XO + 8704;              // (!HW) [W_WIN] f64: draw n of the launch at slot n % W_WIN
+    static constexpr uint32_t SLB = XO + (HW ? 9792 : 9728);  // [64] u16 event blocks, rank order
+    static constexpr uint32_t TB = XO + (HW ? 9920 : 9856);   // [64] u16 candidate blocks, compaction order
+    static constexpr uint32_t ACL = XO + (HW ? 10048 : 9984); // [8] u16 the accepted events (32 bytes allotted)
     static constexpr uint32_t NB = XO + (HW ? 10144 : 10016); // (LAT = false) [8][8] u16 G1 of the accepted events, in event order
     static constexpr uint32_t CTL = 10272;                 // (HW) control words shared by the two waves (struct WCtl)
     static constexpr uint32_t HPF = 10336;                 // (HW) [64] u16 the helper wave's list of coordinates whose lines it requests
     static constexpr uint32_t RING = 10464;                // (HW) [W_NR] (u, log u): draw n of the launch at slot n % W_NR
     static constexpr int CMAX = HW ? 64 : 56;              // candidates per iteration (block-scan passes of 8)
-    static constexpr uint32_t WIN = HW ? 256u : 128u;      // draws an iteration may consume (single wave: two per lane in registers)
+    static constexpr uint32_t WIN = HW ? 256u : 128u;      // draws an iteration may consume (single wave: the whole of its ring)
     static constexpr uint32_t BYTES = HW ? RING + 512 * 16 : NB + 128;  // dynamic LDS of a chain
 };
 constexpr uint32_t W_NR = 512;  // (HW) ring slots
@@ -107,9 +109,12 @@ constexpr int W_AMAX = 8;            // accepted events per iteration (one group
 #define W_TARGET_1W 44u                // ... of the one-wave forms where they use a target (56 candidate lanes, a window of 128 draws)
 #define W_TARGET_1W_MAX_PER_CU 12      // ... which they do up to three chains per SIMD (3072 chains on 256 CUs)
 #define W_NHYP 8     // hypotheses of the accept chain's first guess, two-wave form (a draw is one LDS read)
-#define W_NHYP_1W 4  // ... single-wave form (a draw is two ds_bpermute pairs; A/B at 2048 chains: 4 is 0.6 % faster than none, 8 is 2 % slower)
+#define W_NHYP_1W 4  // ... single-wave form (A/B at 2048 chains, when a draw was two ds_bpermute pairs: 4 is 0.6 % faster than none, 8 is 2 % slower)
 #define W_PF_AHEAD 1.0  // the helper wave requests the lines of every block within this many window lengths beyond the window (1, 2, 4 measured: 1)
 static_assert(WL<false>::BYTES <= 10240, "16 chains per CU: 160 KB / 16");
+static_assert(WL<false>::URING + WL<false>::WIN * 8 <= WL<false>::SLB && WL<false, true>::URING + WL<false, true>::WIN * 8 <= WL<false, true>::SLB &&
+                  WL<false>::ACL + W_AMAX * 2 <= WL<false>::NB,
+              "the one-wave forms' ring of draws ends where the event blocks begin");
 static_assert(WL<false, true>::BYTES <= 40960, "d <= 65536: 4 chains per CU (one per SIMD), 160 KB / 4");
 static_assert(W_BYTES_HW == WL<true>::RING + W_NR * 16 && W_BYTES_HW <= 20480, "8 chains per CU: 160 KB / 8");
 struct WCtl {  // (HW) written by one wave, polled by the other: DS operations of a wave execute in order, so data written before a word is visible with it
@@ -248,6 +253,7 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
     uint16_t* const NB16 = reinterpret_cast<uint16_t*>(smem + L::NB);
     const WCtlPtr ctl = w_ctl(smem, L::CTL);                                                   // (HW only)
     const double2* const ring = reinterpret_cast<const double2*>(smem + L::RING);              // (HW only)
+    double* const uring = reinterpret_cast<double*>(smem + L::URING);                          // (one-wave forms only)
 
     TrRecP* const rec = reinterpret_cast<TrRecP*>(P.rec) + chain * d;
     double2* const kp = reinterpret_cast<double2*>(P.keys) + chain * P.dk;  // (key, t_old) per coordinate
@@ -276,9 +282,12 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
         }
     }
     uint32_t dnm = 0, dnum = 0, dnacc = 0, vnacc = 0;
-    // ring of uniforms in registers: ureg[q] holds draw nm0 + uidx[q], the unique index n in [dnm, dnm + 128) with n % 64 == lane and (n / 64) % 2 == q
-    double ureg[2] = {0.0, 0.0};
-    uint32_t uidx[2] = {0xffffffffu, 0xffffffffu};
+    // ring of uniforms in LDS (one-wave forms): draw nm0 + n of the launch at slot n % 128.  Draws [0, ufilled) are in the ring or used up; the
+    // block [ufilled, ufilled + 64) -- lane l: draw ufilled + l -- waits in unext once uhave is set, its draws below uflushed stored already.
+    // Every draw is computed once per launch, by a full wave (all wave-uniform but unext)
+    double unext = 0.0;
+    uint32_t ufilled = 0, uflushed = 0;
+    bool uhave = false;
     double t_last = hdr->c.t_last;
     double t_event = hdr->t_event;
     status = PDMP_CHAIN_OK;
@@ -353,36 +362,33 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
             status = PDMP_CHAIN_PAUSED;
             break;
         }
-        // ---------------- ring of uniforms: draws dnm .. dnm + 127, two per lane (HW: dnm .. dnm + 255 from the helper wave's ring in LDS)
+        // ---------------- ring of uniforms: draws dnm .. dnm + 127 (HW: dnm .. dnm + 255 from the helper wave's ring in LDS)
         if (HW) {
             if (lane == 0) ctl->consumed = dnm;
             while (ctl->filled < dnm + W_WIN) __builtin_amdgcn_s_sleep(1);
             PDMP_LDS_ORDER();
         } else {
-            const uint32_t n0 = dnm + (((uint32_t)lane - dnm) & 63u);  // the smallest n >= dnm with n % 64 == lane
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const uint32_t n = n0 + 64u * (uint32_t)h;
-                const int q = (int)((n >> 6) & 1u);
-                const bool need0 = (q == 0) && uidx[0] != n, need1 = (q == 1) && uidx[1] != n;
-                if (__ballot(need0 || need1) != 0) {
-                    const double u = pdmp_u01(seed, PDMP_STREAM_MAIN, nm0 + (uint64_t)n);
-                    if (need0) {
-                        ureg[0] = u;
-                        uidx[0] = n;
-                    }
-                    if (need1) {
-                        ureg[1] = u;
-                        uidx[1] = n;
-                    }
+            // a block goes into the ring as far as the window reaches: the slot of draw n < dnm + 128 held draw n - 128 < dnm, which is used up
+            const uint32_t ulim = dnm + W_WIN;
+            while (ufilled < ulim) {
+                const uint32_t n = ufilled + (uint32_t)lane;
+                if (!uhave) {
+                    unext = pdmp_u01(seed, PDMP_STREAM_MAIN, nm0 + (uint64_t)n);
+                    uhave = true;
                 }
+                const uint32_t uend = (ufilled + 64u < ulim) ? ufilled + 64u : ulim;
+                if (n >= uflushed && n < uend) uring[n & (W_WIN - 1u)] = unext;
+                uflushed = uend;
+                if (uend != ufilled + 64u) break;
+                ufilled += 64u;
+                uhave = false;
             }
+            PDMP_LDS_ORDER();
         }
         WPHASE(7);
-        auto draw = [&](uint32_t n) -> double {  // draw nm0 + n for dnm <= n < dnm + W_WIN (every lane calls it: ds_bpermute)
+        auto draw = [&](uint32_t n) -> double {  // draw nm0 + n for dnm <= n < dnm + W_WIN (one LDS read)
             if (HW) return ring[n & (W_NR - 1u)].x;
-            const double v0 = bperm_f64(ureg[0], n & 63u), v1 = bperm_f64(ureg[1], n & 63u);
-            return ((n >> 6) & 1u) ? v1 : v0;
+            return uring[n & (W_WIN - 1u)];
         };
         auto drawlog = [&](uint32_t n) -> double {  // its logarithm (HW: computed once, by the helper wave, with the same pdmp_log)
             if (HW) return ring[n & (W_NR - 1u)].y;
