@@ -336,6 +336,9 @@ pdmp_status pdmp_ensemble_set_gradient_tracking(pdmp_ensemble* ens, int enable);
  * Ties: coordinates with equal c_i/|θ_i| re-bounded at the same instant get EXACTLY equal horizon keys; the reference pops tied
  * keys in heap order (src/priorityqueue.jl:46-77), this engine by lowest index.  Both are valid orders of simultaneous events of
  * independent clocks, but the random streams then pair differently: bit parity with the reference needs distinct c_i/|θ_i|.
+ * With pdmp_ensemble_set_neighbourhood: PDMP_ERR_UNSUPPORTED from set_state.  src/local.jl:95-149 knows ONE graph -- its argument G is moved,
+ * re-bounded member by member and gives G2 -- while the neighbourhood tables re-bound G1 = the pattern of F.Γ only: pass a flow matrix that
+ * carries G's pattern (explicit zeros) instead.
  */
 pdmp_status pdmp_ensemble_set_local_bound(pdmp_ensemble* ens, int enable);
 

@@ -792,7 +792,12 @@ int orc_spdmp_zigzag(int64_t d, const orc_zz_params* p, double t0, double T, dou
     zz_ctx cx;
     cx.d = d;
     cx.p = p;
-    cx.g1 = graph_g1(p->bound_gamma);
+    /* C::LocalBound with G = All() (src/local.jl:103-105,149) re-bounds all n coordinates at every event: not restated here */
+    if (p->local_bound && p->move_all) return ORC_BAD_INPUT;
+    /* C::LocalBound knows ONE graph (src/local.jl:95,107-108,148): the argument G -- the pattern of F.Γ when none is given -- is what a
+     * proposal moves (:43), what an accepted event re-bounds, one draw per member (:61-67), and G2 = two-hop(G) \ G[i] (:108); F.Γ's own
+     * pattern plays no part and nothing asserts G ⊇ G1.  So G takes G1's place below. */
+    cx.g1 = graph_g1((p->local_bound && p->nbr_G) ? p->nbr_G : p->bound_gamma);
     /* the optional argument G (src/sfact.jl:162,171-179): what a proposal moves (:82); Matched() = G1 */
     nbr_graph gG = p->nbr_G ? graph_g1(p->nbr_G) : cx.g1;
     if (p->nbr_G && !graph_contains(&gG, &cx.g1, d)) {

@@ -126,7 +126,9 @@ typedef struct {
      * floats until a rounding difference flips a thinning test (measured: ~6e-10 per proposal on config C3). */
     int tracked;
     /* the optional argument G of spdmp / sspdmp (src/sfact.jl:162,171-179; src/ss_fact.jl:159,167-172): column patterns = the G[i] (values
-     * unused); NULL = Matched().  G[i] ⊇ G1[i] or the call returns ORC_BAD_INPUT (the reference's @assert). */
+     * unused); NULL = Matched().  G[i] ⊇ G1[i] or the call returns ORC_BAD_INPUT (the reference's @assert).
+     * With local_bound (src/local.jl:95,107-108,148) G is the ONE graph: moved, re-bounded member by member, and the source of G2; the pattern of
+     * bound_gamma plays that part only when nbr_G is NULL, and nothing is asserted.  local_bound with move_all (All(), :103-105) is ORC_BAD_INPUT. */
     const orc_csc* nbr_G;
 } orc_zz_params;
 

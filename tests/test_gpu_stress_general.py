@@ -1,33 +1,13 @@
 """Randomised stress of the general kernel (-m gpu): FactBoomerang (mandatory refresh, rotation, ρ, means, speeds) on random graphs, and the ZigZag
-on graphs whose neighbourhoods exceed one wavefront, with random slice boundaries and tiny trace buffers -- bit for bit the oracle.  Fixed seeds."""
+on graphs whose neighbourhoods exceed one wavefront, with random slice boundaries and tiny trace buffers -- bit for bit the oracle.  Fixed seeds.  The draws and the oracle's chains live in
+tests/stress_cases.py (tests/test_stress_cases_ref.py: every reference chain is healthy, so no draw is skipped here); FactBoomerang draws 14..
+are appended ones whose horizon gives every chain 100 events.  tests/test_gpu_general_modes.py holds the kernel's other modes to the oracle."""
 import numpy as np
 import pytest
-import scipy.sparse as sp
 
-import oracle_lib as O
+import stress_cases as S
 
 pytestmark = pytest.mark.gpu
-
-
-def _graph(pkg, rng, dense):
-    if dense:  # two-hop sets beyond 64 members: R R' of a sparse R
-        d = int(rng.integers(90, 180))
-        R = sp.random(d, d, density=float(rng.uniform(0.04, 0.09)), random_state=rng, data_rvs=rng.standard_normal, format="csc")
-        G = sp.csc_matrix(R @ R.T + 2.0 * sp.identity(d))
-    else:
-        kind = rng.integers(0, 3)
-        if kind == 0:
-            G = pkg.problems.gmrf_precision(int(rng.integers(3, 12)), eps=float(rng.uniform(0.05, 1.0)))
-        elif kind == 1:
-            G = pkg.problems.maintest_precision(int(rng.integers(4, 40)))
-        else:
-            d = int(rng.integers(8, 100))
-            R = sp.random(d, d, density=min(1.5 / d, 0.5), random_state=rng, data_rvs=rng.standard_normal, format="csc")
-            A = R + R.T
-            G = A + sp.diags(np.asarray(abs(A).sum(axis=0)).ravel() + 1.0)
-    G = sp.csc_matrix(G)
-    G.sort_indices()
-    return G
 
 
 def _run_sliced(pkg, ens, nch, T, cuts, ok_violation=False):
@@ -58,37 +38,23 @@ def _compare(what, evs, fs, cnt, refs, adapt):
             assert np.array_equal(fs["c"][k], r["c"]), what
 
 
-@pytest.mark.parametrize("case", range(14))
+@pytest.mark.parametrize("case", range(S.FACTBOOMERANG_N))
 def test_random_factboomerang(gpu_pkg, case):
     """src/fact_samplers.jl:37-39,58-65 (λ, ab), src/sfact.jl:29-36 (rotation), :103 (refresh draw) on random graphs, means, speeds, ρ and λref."""
     pkg = gpu_pkg
-    rng = np.random.default_rng(8000 + case)
-    G = _graph(pkg, rng, dense=False)
-    d = G.shape[0]
-    nch = 2
-    mu = 0.3 * rng.standard_normal(d) if rng.integers(0, 2) else np.zeros(d)
-    sig = 0.5 + rng.random(d) if rng.integers(0, 2) else np.ones(d)
-    lam = float(rng.uniform(0.1, 1.0))
-    rho = float(rng.uniform(0.0, 0.9)) if rng.integers(0, 2) else 0.0
+    P, refs = S.factboomerang_draw(case), S.factboomerang_refs(case)
+    G, d, nch, mu, sig, lam, rho, x0, th0 = (P[k] for k in ("G", "d", "nch", "mu", "sig", "lam", "rho", "x0", "th0"))
+    adapt, c, T, cap, seed, cuts = (P[k] for k in ("adapt", "c", "T", "cap", "seed", "cuts"))
     F = pkg.FactBoomerang(G, mu, lam, σ=sig, ρ=rho)
-    x0 = rng.standard_normal((nch, d))
-    th0 = sig * rng.standard_normal((nch, d))
-    adapt = bool(rng.integers(0, 2))
-    c = pkg.problems.column_norms(G) * (float(rng.uniform(2.0, 4.0)) if not adapt else float(rng.uniform(0.2, 1.0)))
-    T = float(rng.uniform(4.0, 20.0)) * min(1.0, 40.0 / d)
-    cap = int(rng.integers(16, 96))
-    seed = 8100 + 10 * case
-    cuts = np.sort(rng.uniform(0, T, size=int(rng.integers(0, 4))))
-    refs = [O.spdmp_zigzag(G, mu, G, x0[k], th0[k], c, T, seed=seed + k, lambda_ref=lam, rho=rho, sigma=sig, adapt=adapt, factor=1.7,
-                           factboomerang=True) for k in range(nch)]
-    if any(r["status"] != 0 for r in refs):
-        pytest.skip("bound too small for this draw without adapt")
+    assert all(r["status"] == 0 for r in refs)
     with pkg.Ensemble(nch, d, adapt=adapt, factor=1.7, trace_capacity=cap) as ens:
         ens.set_flow(F)
         ens.set_target(pkg.GaussianTarget(G))
         ens.set_state(0.0, x0, th0, c, np.arange(nch, dtype=np.uint64) + seed)
         evs, fs, cnt = _run_sliced(pkg, ens, nch, T, cuts)
-    what = dict(case=case, d=d, mu=bool(np.any(mu)), rho=rho, lam=lam, adapt=adapt, cap=cap, cuts=len(cuts))
+        kname = ens.kernel_name()
+    what = dict(case=case, d=d, mu=bool(np.any(mu)), rho=rho, lam=lam, adapt=adapt, cap=cap, cuts=len(cuts), kernel=kname)
+    assert kname == "zz_general_run_kernel", what
     assert sum(len(r["events"]) for r in refs) > 20, what
     _compare(what, evs, fs, cnt, refs, adapt)
 
@@ -97,28 +63,10 @@ def test_random_factboomerang(gpu_pkg, case):
 def test_random_wide_neighbourhoods_zigzag(gpu_pkg, case):
     """The ZigZag where |S[i]| exceeds a wavefront (the general kernel's chunked re-bound), with its options drawn at random."""
     pkg = gpu_pkg
-    rng = np.random.default_rng(8500 + case)
-    G = _graph(pkg, rng, dense=True)
-    d = G.shape[0]
-    nch = 2
-    Gb = sp.csc_matrix(0.85 * G) if rng.integers(0, 2) else G
-    mu_b = 0.3 * rng.standard_normal(d) if rng.integers(0, 2) else None
-    sig = 0.5 + rng.random(d)
-    lam = float(rng.uniform(0.2, 1.0)) if rng.integers(0, 2) else 0.0
-    x0 = rng.standard_normal((nch, d))
-    th0 = sig * rng.choice([-1.0, 1.0], (nch, d))
-    adapt = bool(rng.integers(0, 2))
-    c = pkg.problems.column_norms(G) * (float(rng.uniform(2.5, 4.0)) if not adapt else float(rng.uniform(0.3, 1.5)))
-    T = float(rng.uniform(1.0, 4.0))
-    cap = int(rng.integers(16, 128))
-    seed = 8600 + 10 * case
-    cuts = np.sort(rng.uniform(0, T, size=int(rng.integers(0, 4))))
-    kw = dict(adapt=adapt, factor=1.6, sigma=sig)
-    if lam > 0:
-        kw["lambda_ref"] = lam
-    refs = [O.spdmp_zigzag(Gb, mu_b, G, x0[k], th0[k], c, T, seed=seed + k, **kw) for k in range(nch)]
-    if any(r["status"] != 0 for r in refs):
-        pytest.skip("bound too small for this draw without adapt")
+    P, refs = S.wide_zigzag_draw(case), S.wide_zigzag_refs(case)
+    G, Gb, d, nch, mu_b, sig, lam, x0, th0 = (P[k] for k in ("G", "Gb", "d", "nch", "mu_b", "sig", "lam", "x0", "th0"))
+    adapt, c, T, cap, seed, cuts = (P[k] for k in ("adapt", "c", "T", "cap", "seed", "cuts"))
+    assert all(r["status"] == 0 for r in refs)
     with pkg.Ensemble(nch, d, adapt=adapt, factor=1.6, trace_capacity=cap) as ens:
         ens.set_flow(pkg.ZigZag(Gb, np.zeros(d) if mu_b is None else mu_b, sig, λref=lam))
         ens.set_target(pkg.GaussianTarget(G))
@@ -126,4 +74,5 @@ def test_random_wide_neighbourhoods_zigzag(gpu_pkg, case):
         evs, fs, cnt = _run_sliced(pkg, ens, nch, T, cuts)
         kname = ens.kernel_name()
     what = dict(case=case, d=d, own_bound=Gb is not G, mu_b=mu_b is not None, lam=lam, adapt=adapt, cap=cap, kernel=kname)
+    assert kname == S.zigzag_kernel(G) == "zz_general_run_kernel", what
     _compare(what, evs, fs, cnt, refs, adapt)

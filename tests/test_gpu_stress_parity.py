@@ -1,53 +1,21 @@
 """Randomised stress of the speculative kernels (-m gpu): random lattices / random sparse precisions, random slice boundaries,
 tiny trace buffers (TRACE_FULL in the middle of a multi-event commit), adapt on/off -- every chain must equal the oracle bit
-for bit.  Seeds are fixed: the cases are reproducible."""
+for bit.  Seeds are fixed: the cases are reproducible.  The draws and the oracle's chains live in tests/stress_cases.py;
+tests/test_stress_cases_ref.py shows on the CPU that every reference chain is healthy, so no draw is skipped here."""
 import numpy as np
 import pytest
-import scipy.sparse as sp
 
-import oracle_lib as O
+import stress_cases as S
 
 pytestmark = pytest.mark.gpu
-
-
-def _random_problem(pkg, rng):
-    kind = rng.integers(0, 3)
-    if kind == 0:
-        n = int(rng.integers(3, 14))
-        G = pkg.problems.gmrf_precision(n, eps=float(rng.uniform(0.01, 1.0)))
-    elif kind == 1:  # banded: k up to 7, two-hop zone up to 13
-        d = int(rng.integers(5, 200))
-        w = int(rng.integers(1, 4))
-        diags = [np.full(d, 2.0 * w + 1.0 + rng.random())] + [np.full(d - o, -rng.uniform(0.2, 1.0)) for o in range(1, w + 1)]
-        G = sp.diags(diags + diags[1:], [0] + list(range(1, w + 1)) + [-o for o in range(1, w + 1)], format="csc")
-    else:  # random sparse symmetric, diagonally dominant, small degree
-        d = int(rng.integers(8, 120))
-        R = sp.random(d, d, density=min(1.5 / d, 0.5), random_state=rng, data_rvs=rng.standard_normal, format="csc")
-        A = R + R.T
-        G = sp.csc_matrix(A + sp.diags(np.asarray(abs(A).sum(axis=0)).ravel() + 1.0))
-    G = sp.csc_matrix(G)
-    G.sort_indices()
-    return G
 
 
 @pytest.mark.parametrize("case", range(12))
 def test_random_slices_and_tiny_traces_zigzag(gpu_pkg, case):
     pkg = gpu_pkg
-    rng = np.random.default_rng(1000 + case)
-    G = _random_problem(pkg, rng)
-    d = G.shape[0]
-    nch = 3
-    x0 = rng.standard_normal((nch, d))
-    th0 = rng.choice([-1.0, -0.5, 0.5, 1.0], (nch, d))
-    adapt = bool(rng.integers(0, 2))
-    c = pkg.problems.column_norms(G) * (1.2 if not adapt else float(rng.uniform(0.3, 1.0)))
-    T = float(rng.uniform(2.0, 12.0)) * min(1.0, 60.0 / d)
-    cap = int(rng.integers(8, 64))
-    seed = 5000 + case
-    cuts = np.sort(rng.uniform(0, T, size=int(rng.integers(1, 6))))
-    refs = [O.spdmp_zigzag(G, None, G, x0[k], th0[k], c, T, seed=seed + k, adapt=adapt) for k in range(nch)]
-    if any(r["status"] != 0 for r in refs):
-        pytest.skip("bound too small for this draw without adapt")
+    P, refs = S.parity_slices_draw(case), S.parity_slices_refs(case)
+    G, d, nch, x0, th0, adapt, c, T, cap, seed, cuts = (P[k] for k in ("G", "d", "nch", "x0", "th0", "adapt", "c", "T", "cap", "seed", "cuts"))
+    assert all(r["status"] == 0 for r in refs)
     events = [[] for _ in range(nch)]
     with pkg.Ensemble(nch, d, adapt=adapt, trace_capacity=cap) as ens:
         ens.set_flow(pkg.ZigZag(G, np.zeros(d)))
@@ -66,6 +34,8 @@ def test_random_slices_and_tiny_traces_zigzag(gpu_pkg, case):
                     break
         fs = ens.final_state()
         cnt = ens.counters()
+        kname = ens.kernel_name()
+    assert kname.startswith(S.zigzag_kernel(G)), (case, kname)
     for k, r in enumerate(refs):
         ev = np.concatenate(events[k]) if events[k] else np.empty(0, dtype=pkg._lib.EVENT_DTYPE)
         assert len(ev) == len(r["events"]), (case, k, len(ev), len(r["events"]))
@@ -87,29 +57,10 @@ def test_random_means_bounds_and_refresh_zigzag(gpu_pkg, monkeypatch, case, kern
         monkeypatch.setenv("PDMP_KERNEL", "seq")
     else:
         monkeypatch.delenv("PDMP_KERNEL", raising=False)
-    rng = np.random.default_rng(3000 + case)
-    G = _random_problem(pkg, rng)
-    d = G.shape[0]
-    nch = 2
-    Gb = sp.csc_matrix(0.9 * G) if rng.integers(0, 2) else G
-    mu_b = 0.4 * rng.standard_normal(d) if rng.integers(0, 2) else None
-    mu_t = (mu_b if (mu_b is not None and rng.integers(0, 2)) else 0.4 * rng.standard_normal(d)) if rng.integers(0, 2) else None
-    sig = 0.5 + rng.random(d)
-    lam = float(rng.uniform(0.2, 1.5)) if rng.integers(0, 2) else 0.0
-    t0 = float(rng.uniform(0.0, 2.0)) if rng.integers(0, 2) else 0.0
-    x0 = rng.standard_normal((nch, d))
-    th0 = sig * rng.choice([-1.0, 1.0], (nch, d))
-    adapt = bool(rng.integers(0, 2))
-    c = pkg.problems.column_norms(G) * (float(rng.uniform(2.5, 4.0)) if not adapt else float(rng.uniform(0.3, 1.5)))
-    T = t0 + float(rng.uniform(2.0, 12.0)) * min(1.0, 60.0 / d)
-    cap = int(rng.integers(16, 128))
-    seed = 3500 + 10 * case
-    kw = dict(t0=t0, target_mu=mu_t, adapt=adapt, factor=1.8, sigma=sig)
-    if lam > 0:
-        kw["lambda_ref"] = lam
-    refs = [O.spdmp_zigzag(Gb, mu_b, G, x0[k], th0[k], c, T, seed=seed + k, **kw) for k in range(nch)]
-    if any(r["status"] != 0 for r in refs):
-        pytest.skip("bound too small for this draw without adapt")
+    P, refs = S.parity_options_draw(case), S.parity_options_refs(case)
+    G, Gb, d, nch, mu_b, mu_t, sig, lam, t0 = (P[k] for k in ("G", "Gb", "d", "nch", "mu_b", "mu_t", "sig", "lam", "t0"))
+    x0, th0, adapt, c, T, cap, seed = (P[k] for k in ("x0", "th0", "adapt", "c", "T", "cap", "seed"))
+    assert all(r["status"] == 0 for r in refs)
     events = [[] for _ in range(nch)]
     with pkg.Ensemble(nch, d, adapt=adapt, factor=1.8, trace_capacity=cap) as ens:
         ens.set_flow(pkg.ZigZag(Gb, np.zeros(d) if mu_b is None else mu_b, sig, λref=lam))
@@ -127,7 +78,9 @@ def test_random_means_bounds_and_refresh_zigzag(gpu_pkg, monkeypatch, case, kern
                 break
         fs = ens.final_state()
         cnt = ens.counters()
-    what = dict(case=case, kern=kern, d=d, own_bound=Gb is not G, mu_b=mu_b is not None, mu_t=mu_t is not None, lam=lam, t0=t0, adapt=adapt)
+        kname = ens.kernel_name()
+    what = dict(case=case, kern=kern, d=d, own_bound=Gb is not G, mu_b=mu_b is not None, mu_t=mu_t is not None, lam=lam, t0=t0, adapt=adapt, kernel=kname)
+    assert kname.startswith(S.zigzag_kernel(G, kern)), what
     for k, r in enumerate(refs):
         ev = np.concatenate(events[k]) if events[k] else np.empty(0, dtype=pkg._lib.EVENT_DTYPE)
         assert len(ev) == len(r["events"]), (what, k, len(ev), len(r["events"]))
@@ -142,21 +95,9 @@ def test_random_means_bounds_and_refresh_zigzag(gpu_pkg, monkeypatch, case, kern
 @pytest.mark.parametrize("case", range(8))
 def test_random_slices_and_tiny_traces_sticky(gpu_pkg, case):
     pkg = gpu_pkg
-    rng = np.random.default_rng(2000 + case)
-    G = _random_problem(pkg, rng)
-    d = G.shape[0]
-    nch = 2
-    x0 = rng.standard_normal((nch, d))
-    th0 = rng.choice([-1.0, 1.0], (nch, d))
-    c = 1.5 * pkg.problems.column_norms(G)
-    kappa = rng.uniform(0.1, 2.0, d)
-    reversible, strong = bool(rng.integers(0, 2)), bool(rng.integers(0, 2))
-    T = float(rng.uniform(2.0, 10.0)) * min(1.0, 60.0 / d)
-    cap = int(rng.integers(8, 64))
-    seed = 7000 + case
-    cuts = np.sort(rng.uniform(0, T, size=int(rng.integers(1, 5))))
-    refs = [O.sspdmp_zigzag(G, None, G, x0[k], th0[k], c, kappa, T, seed=seed + k, adapt=True, reversible=reversible,
-                            strong_upperbounds=strong) for k in range(nch)]
+    P, refs = S.parity_sticky_draw(case), S.parity_sticky_refs(case)
+    G, d, nch, x0, th0, c, kappa, reversible, strong = (P[k] for k in ("G", "d", "nch", "x0", "th0", "c", "kappa", "reversible", "strong"))
+    T, cap, seed, cuts = (P[k] for k in ("T", "cap", "seed", "cuts"))
     assert all(r["status"] == 0 for r in refs)
     events = [[] for _ in range(nch)]
     with pkg.Ensemble(nch, d, sampler=pkg._lib.SAMPLER_STICKY_ZIGZAG, adapt=True, factor=1.5, trace_capacity=cap) as ens:
@@ -176,6 +117,8 @@ def test_random_slices_and_tiny_traces_sticky(gpu_pkg, case):
                     break
         fs = ens.final_state()
         cnt = ens.counters()
+        kname = ens.kernel_name()
+    assert kname == S.sticky_kernel(G), (case, kname)
     for k, r in enumerate(refs):
         ev = np.concatenate(events[k]) if events[k] else np.empty(0, dtype=pkg._lib.EVENT_DTYPE)
         assert len(ev) == len(r["events"]), (case, k, len(ev), len(r["events"]))

@@ -479,6 +479,11 @@ pdmp_status init_state(pdmp_ensemble* e, double t0, const double* x0, const doub
             if (e->cfg.sampler != PDMP_SAMPLER_ZIGZAG_LOCAL || e->flow_kind != 0 || e->lambda_ref > 0 || e->target_kind != 0)
                 return fail(PDMP_ERR_UNSUPPORTED,
                             "LocalBound (src/local.jl) is implemented for spdmp with a ZigZag flow without refresh and the Gaussian target");
+            // src/local.jl:95,107-108 knows one graph: with an argument G it re-bounds ALL of G[i] and takes G2 from G's two-hop sets, while the
+            // tables of pdmp_ensemble_set_neighbourhood re-bound G1[i] = the pattern of F.Γ only.  Give the flow's Γ the pattern of G instead.
+            if (e->has_g1mask)
+                return fail(PDMP_ERR_UNSUPPORTED,
+                            "LocalBound with pdmp_ensemble_set_neighbourhood: src/local.jl re-bounds all of G[i]; pass a flow matrix with G's pattern");
             // the target's Γ values in the (member j of G1[i], entry of column j) layout of the re-bound tables
             std::vector<double> qtval;
             qtval.reserve(e->h_qptr.empty() ? 0 : e->h_qptr.back());
@@ -532,6 +537,7 @@ pdmp_status init_state(pdmp_ensemble* e, double t0, const double* x0, const doub
     P.diag = e->d_diag.p;
     P.sticky = sticky ? 1 : 0;
     P.local_bound = e->local_bound ? 1 : 0;
+    P.g1_member = e->has_g1mask ? reinterpret_cast<const uint4*>(e->d_member.p) : nullptr;
     e->track_generic = false;
     bool trackp_ok = false;
     if (e->track) {

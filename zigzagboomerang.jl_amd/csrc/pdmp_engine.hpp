@@ -247,6 +247,8 @@ struct ZzInitParams {
     const double* __restrict__ diag; // [d]
     int32_t local_bound;             // c::LocalBound (src/local.jl): bounds from the target's derivatives + expiry horizon; thf = renew flags
     int32_t track;                   // records are TrRec (tracked-gradient kernel): also g = Γt[:,i]·x0, gd = Γt[:,i]·θ0 and the bound's sums
+    const uint4* __restrict__ g1_member;  // the tables' pattern is G ⊋ G1 (pdmp_ensemble_set_neighbourhood): [nnz] member records, .w flags the entries of G1;
+                                          // nullptr: every entry belongs to G1.  FactBoomerang's bound sums over G1[i] alone (src/fact_samplers.jl:59)
 };
 
 // One chain over K wavefronts (pdmp_partition.hip): the reference's parallel_spdmp (src/parallel.jl)

@@ -63,6 +63,7 @@ __global__ __launch_bounds__(256) void zz_init_kernel(ZzInitParams P) {
         if (P.flow_kind == 1) {  // ab(G, i, x, θ, c, Z::FactBoomerang), src/fact_samplers.jl:58-65
             double zz = 0.0;
             for (uint32_t p = P.tb.colptr[i]; p < P.tb.colptr[i + 1]; ++p) {
+                if (P.g1_member && P.g1_member[p].w == 0u) continue;  // a member of G[i] \ G1[i]: nhd = neighbours(G1, i), :59
                 const uint32_t r = P.tb.rowval[p];
                 const double dx = x_of(r) - P.mu[r];
                 const double tr = th_of(r);
