@@ -148,6 +148,16 @@ pdmp_status pdmp_debug_math_eval(int device, int fn, int64_t n, const double* a,
 pdmp_status pdmp_debug_sticky_eval(int device, int fn, int64_t n, const double* a, const double* b, const double* c, double* out);
 
 /*
+ * Test hook (parity build only, like pdmp_debug_math_eval; PDMP_ERR_UNSUPPORTED elsewhere): the scalars of the barrier ZigZag as compiled inside
+ * pdmp_barrier.hip, at (a[k], b[k], c[k]); out is [2 x n] (second row: a second output, else 0).  The host restatements (orc_poisson_time3 of
+ * the oracle, tests/ref/stickyzz_ref.c) must agree bit for bit.
+ */
+#define PDMP_BARRIER_FN_PT3_L 0 /* poisson_time3_L(a, b, 0.01, pdmp_log(c)): poisson_time((a, b, 0.01), u = c), src/poissontime.jl:39-65 */
+#define PDMP_BARRIER_FN_HIT 1   /* barrier_hitting_time(x = a, v = b, barrier = c), src/stickyzz.jl:119-127 */
+#define PDMP_BARRIER_FN_RATES 2 /* barrier_rates(a, b, c, 1.0): pos(a), pos(b + c), src/stickyzz.jl:129-135 */
+pdmp_status pdmp_debug_barrier_eval(int device, int fn, int64_t n, const double* a, const double* b, const double* c, double* out);
+
+/*
  * Test hook: puts a given trace segment in front of the device consumers (csrc/pdmp_consume.hip; tests/test_gpu_consumers_synthetic.py).  Waits for
  * the device (pending asynchronous consumers included), copies the n events into slots [ntrace, ntrace + n) of `chain`'s CURRENT trace buffer and
  * adds n to the chain's ntrace and nevents -- no event-loop kernel runs, no record changes.  PDMP_ERR_INVALID for a bad chain, n < 0,

@@ -59,6 +59,7 @@ typedef enum {
 #define PDMP_SAMPLER_ZIGZAG_ALL 1   /* pdmp,  G = All()          src/sfact.jl:236        */
 #define PDMP_SAMPLER_BPS 2          /* pdmp,  BouncyParticle     src/not_fact_samplers.jl:52-147 */
 #define PDMP_SAMPLER_STICKY_ZIGZAG 3 /* sspdmp                   src/ss_fact.jl:78-215   */
+#define PDMP_SAMPLER_BARRIER_ZIGZAG 4 /* stickyzz                src/stickyzz.jl:176-319 */
 
 /* per-chain status words */
 #define PDMP_CHAIN_OK 0
@@ -288,6 +289,37 @@ pdmp_status pdmp_ensemble_path_integrals(pdmp_ensemble* ens, double T, int64_t n
  * are the reference's scalar (acc, num) (:175,214).  The refresh clock is not implemented by the reference (:86).
  */
 pdmp_status pdmp_ensemble_set_sticky(pdmp_ensemble* ens, const double* kappa, int reversible, int strong_upperbounds);
+
+/* ------------------------------------------------------------------ ZigZag with sticky and reflecting barriers (PDMP_SAMPLER_BARRIER_ZIGZAG)
+ *
+ * stickyzz(u0, target::StructuredTarget, flow::StickyFlow, upper_bounds::StickyUpperBounds, barriers::Vector{<:StickyBarriers}, end_condition)
+ * (src/stickyzz.jl:176-319): every coordinate has a lower and an upper barrier at arbitrary levels (StickyBarriers, :19-25), each with a rule
+ * acting when the coordinate thaws -- PDMP_BARRIER_STICKY keeps the saved speed, _REFLECT negates it, _REVERSIBLE flips its sign by a coin -- and a
+ * thaw rate kappa > 0; kappa = +Inf is an instantaneous wall.  All arrays are [d], shared by the chains; lo = -Inf or hi = +Inf means no barrier on
+ * that side.  Box constraints, truncated Gaussians, positivity constraints, sticking at levels other than 0.
+ *
+ * Call after set_flow_zigzag and set_target_gaussian_csc, before set_state.  Refusals, never a silent fall-back:
+ *   set_barriers  PDMP_ERR_INVALID for lo > hi, kappa <= 0 or NaN, a rule outside 0..2.
+ *   set_flow_zigzag on such an ensemble: PDMP_ERR_INVALID for a Γ without a diagonal entry.
+ *   set_state     PDMP_ERR_INVALID for theta0[i] == 0 (the reference's dir() would index out of bounds) and for x0[i] outside a box [lo, hi]
+ *                 with lo < hi.  lo == hi is one level met from either side, as sspdmp2's (0, 0): any start is allowed.
+ *   set_state     PDMP_ERR_UNSUPPORTED for anything but: a ZigZag flow without refresh, the Gaussian target, G = G1 (no set_neighbourhood),
+ *                 no gradient tracking / LocalBound, neighbourhoods of at most 64 members (what the one-event sticky kernel takes) with
+ *                 |G1[i]| <= 63, an explicit state.  pdmp_ensemble_set_adaptscale itself returns PDMP_ERR_UNSUPPORTED on such an ensemble.
+ * pdmp_ensemble_consume_begin returns PDMP_ERR_UNSUPPORTED (the device consumers' "time away from 0" has no meaning here); the host consumers work
+ * on the returned trace.  One event after every hit, thaw and accepted reflection; the counters' nacc / num are the reference's scalar acc.
+ * The path integrals (pdmp_ensemble_path_integrals, batch_means, ess_*) are kept: a frozen coordinate contributes its barrier level.
+ * pdmp_ensemble_final_state's acc then holds action[i] (0 hit, 1 reflect, 2 unfreeze, :170-175).
+ *
+ * pdmp_ensemble_final_barrier: frozen [n x d] (1 where v[i] == 0 && v_old[i] != 0, :266) and theta_saved [n x d] = v_old (the ensemble's own
+ * array of saved speeds, which no other getter returns); either may be NULL.
+ */
+#define PDMP_BARRIER_STICKY 0
+#define PDMP_BARRIER_REFLECT 1
+#define PDMP_BARRIER_REVERSIBLE 2
+pdmp_status pdmp_ensemble_set_barriers(pdmp_ensemble* ens, const double* lo, const double* hi, const int32_t* rule_lo, const int32_t* rule_hi,
+                                       const double* kappa_lo, const double* kappa_hi, int strong_upperbounds);
+pdmp_status pdmp_ensemble_final_barrier(pdmp_ensemble* ens, int64_t chain_first, int64_t n, uint8_t* frozen, double* theta_saved);
 
 /* ------------------------------------------------------------------ adaptscale (σ tuning in the refresh branch)
  *

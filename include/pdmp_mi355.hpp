@@ -8,6 +8,8 @@
 //                                                   -> Ξ::PDMPTrace, (t, x, θ), (acc, num), c      (src/not_fact_samplers.jl:117,146)
 //     sspdmp(∇ϕ, t0, x0, θ0, T, c, F::ZigZag, κ, args...; reversible, strong_upperbounds, factor=1.5, adapt)
 //                                                                                                  (src/ss_fact.jl:159-160,217)
+//     stickyzz(u0, target, StickyFlow(F::ZigZag), StickyUpperBounds(G, G1, Γ, c; adapt, strong, multiplier), barriers, EndTime(T))
+//                                                   -> Ξ, t′, (t, x, θ), (acc, num)                 (src/stickyzz.jl:176-218)
 // Same names, argument order, keyword meaning (struct Options), return shape (struct Result) and error behaviour (the
 // reference's `error("Tuning parameter `c` too small.")`, src/sfact.jl:124, becomes std::runtime_error with that text).
 // Differences forced by the C ABI: `∇ϕ, args...` is an enumerated target (GaussianTarget, LogisticTarget); coordinates are
@@ -113,6 +115,15 @@ struct Options {  // the reference's keyword arguments
     SparseCSC G;
 };
 
+// StickyBarriers(x, rule, κ), src/stickyzz.jl:19-25: the lower and the upper barrier of one coordinate -- levels (∓Inf: none on that side), the
+// rule each applies to the restored speed at thaw time (PDMP_BARRIER_STICKY keeps it, _REFLECT negates it, _REVERSIBLE flips its sign by a
+// coin) and thaw rates κ (+Inf: an instantaneous wall).  Barrier{} is StickyBarriers(): no barrier at all.
+struct Barrier {
+    double lo = -std::numeric_limits<double>::infinity(), hi = std::numeric_limits<double>::infinity();
+    int rule_lo = PDMP_BARRIER_REFLECT, rule_hi = PDMP_BARRIER_REFLECT;
+    double kappa_lo = std::numeric_limits<double>::infinity(), kappa_hi = std::numeric_limits<double>::infinity();
+};
+
 using Event = pdmp_event;  // (t, i, x, θ), src/trace.jl:38; i 0-based
 
 struct FactTrace {  // FactTrace(F, t0, x0, θ0, events), src/trace.jl:7-13
@@ -135,6 +146,10 @@ struct Result {  // Ξ, (t, x, θ), (acc, num), c
     int64_t num = 0;
     std::vector<double> c;
     std::vector<double> sigma;  // tuned F.σ when adaptscale (the reference mutates F.σ in place)
+    // stickyzz: t′ of the last event, and per coordinate whether it ended frozen (v == 0 && v_old != 0) and its saved speed v_old
+    double t_prime = 0.0;
+    std::vector<uint8_t> frozen;
+    std::vector<double> theta_saved;
 };
 
 // RAII handle on pdmp_ensemble
@@ -221,7 +236,7 @@ inline void set_flow(Ensemble& e, const FactBoomerang& F) {
 template <class Target, class Flow>
 Result<FactTrace> factorised(int sampler, const Target& target, double t0, const std::vector<double>& x0,
                              const std::vector<double>& theta0, double T, const std::vector<double>& c, const Flow& F,
-                             const std::vector<double>* kappa, const Options& o) {
+                             const std::vector<double>* kappa, const Options& o, const std::vector<Barrier>* barriers = nullptr) {
     const int64_t d = (int64_t)x0.size();
     const int64_t cap = o.trace_capacity > 0 ? o.trace_capacity : default_capacity(d, t0, T);
     Ensemble e(1, d, sampler, o, cap);
@@ -229,6 +244,20 @@ Result<FactTrace> factorised(int sampler, const Target& target, double t0, const
     if (o.G.n > 0) check(pdmp_ensemble_set_neighbourhood(e.get(), o.G.colptr.data(), o.G.rowval.data()));
     set_target(e, target);
     if (kappa) check(pdmp_ensemble_set_sticky(e.get(), kappa->data(), o.reversible ? 1 : 0, o.strong_upperbounds ? 1 : 0));
+    if (barriers) {
+        if ((int64_t)barriers->size() != d) throw std::invalid_argument("stickyzz: one Barrier per coordinate");
+        std::vector<double> lo, hi, kl, kh;
+        std::vector<int32_t> rl, rh;
+        for (const Barrier& b : *barriers) {
+            lo.push_back(b.lo);
+            hi.push_back(b.hi);
+            rl.push_back(b.rule_lo);
+            rh.push_back(b.rule_hi);
+            kl.push_back(b.kappa_lo);
+            kh.push_back(b.kappa_hi);
+        }
+        check(pdmp_ensemble_set_barriers(e.get(), lo.data(), hi.data(), rl.data(), rh.data(), kl.data(), kh.data(), o.strong_upperbounds ? 1 : 0));
+    }
     if (o.adaptscale) check(pdmp_ensemble_set_adaptscale(e.get(), 1));
     if (o.local_bound) check(pdmp_ensemble_set_local_bound(e.get(), 1));
     if (o.tracked) check(pdmp_ensemble_set_gradient_tracking(e.get(), 1));
@@ -255,6 +284,13 @@ Result<FactTrace> factorised(int sampler, const Target& target, double t0, const
     check(pdmp_ensemble_final_state(e.get(), 0, 1, R.t.data(), R.x.data(), R.theta.data(), R.acc.data(), R.c.data()));
     if (!o.adapt) R.c = c;
     if (kappa) R.acc.assign(1, (int64_t)cnt[0].nacc);  // sticky: scalar acc, src/ss_fact.jl:175
+    if (barriers) {  // Ξ, t′, u, acc, src/stickyzz.jl:217
+        R.acc.assign(1, (int64_t)cnt[0].nacc);
+        R.t_prime = cnt[0].t_last;
+        R.frozen.resize((size_t)d);
+        R.theta_saved.resize((size_t)d);
+        check(pdmp_ensemble_final_barrier(e.get(), 0, 1, R.frozen.data(), R.theta_saved.data()));
+    }
     R.num = (int64_t)cnt[0].num;
     if (o.adaptscale) {
         R.sigma.resize((size_t)d);
@@ -351,6 +387,15 @@ Result<FactTrace> sspdmp(const Target& target, double t0, const std::vector<doub
                          Options o = {}) {
     if (o.factor == 1.8) o.factor = 1.5;
     return detail::factorised(PDMP_SAMPLER_STICKY_ZIGZAG, target, t0, x0, theta0, T, c, F, &kappa, o);
+}
+// stickyzz (src/stickyzz.jl:176-218) in the call shape of the other samplers, G = G1 = the pattern of F.Γ: barriers holds one Barrier per
+// coordinate; Options::strong_upperbounds, adapt and factor (multiplier, 1.5) are StickyUpperBounds' keywords.  The result's t_prime, frozen and
+// theta_saved are filled; acc is the scalar of AcceptanceDiagnostics.
+template <class Target>
+Result<FactTrace> stickyzz(const Target& target, double t0, const std::vector<double>& x0, const std::vector<double>& theta0, double T,
+                           const std::vector<double>& c, const ZigZag& F, const std::vector<Barrier>& barriers, Options o = {}) {
+    if (o.factor == 1.8) o.factor = 1.5;
+    return detail::factorised(PDMP_SAMPLER_BARRIER_ZIGZAG, target, t0, x0, theta0, T, c, F, nullptr, o, &barriers);
 }
 // pdmp(∇ϕ!, t0, x0, θ0, T, c, B::BouncyParticle; adapt, factor=2.0) with ∇ϕ!(y, x) = B.Γ(x − B.μ)  -- src/not_fact_samplers.jl:117-147
 inline Result<PDMPTrace> pdmp(double t0, const std::vector<double>& x0, const std::vector<double>& theta0, double T, double c,

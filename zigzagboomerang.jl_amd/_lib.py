@@ -16,7 +16,9 @@ ERR_NAMES = {0: "PDMP_OK", 1: "PDMP_ERR_INVALID", 2: "PDMP_ERR_NO_DEVICE", 3: "P
              4: "PDMP_ERR_UNSUPPORTED", 5: "PDMP_ERR_NOMEM"}
 
 PDMP_ERR_INVALID, PDMP_ERR_NO_DEVICE, PDMP_ERR_HIP, PDMP_ERR_UNSUPPORTED, PDMP_ERR_NOMEM = 1, 2, 3, 4, 5
-SAMPLER_ZIGZAG_LOCAL, SAMPLER_ZIGZAG_ALL, SAMPLER_BPS, SAMPLER_STICKY_ZIGZAG = 0, 1, 2, 3
+SAMPLER_ZIGZAG_LOCAL, SAMPLER_ZIGZAG_ALL, SAMPLER_BPS, SAMPLER_STICKY_ZIGZAG, SAMPLER_BARRIER_ZIGZAG = 0, 1, 2, 3, 4
+BARRIER_RULES = {"sticky": 0, "reflect": 1, "reversible": 2}  # PDMP_BARRIER_*
+BARRIER_FN_PT3_L, BARRIER_FN_HIT, BARRIER_FN_RATES = 0, 1, 2  # include/pdmp_debug.h: pdmp_debug_barrier_eval
 CHAIN_OK, CHAIN_BOUND_VIOLATED, CHAIN_STALLED, CHAIN_TRACE_FULL, CHAIN_PAUSED = 0, 1, 2, 3, 4
 
 
@@ -46,6 +48,7 @@ EXPORTED_SYMBOLS = [
     "pdmp_ensemble_set_mass_cholesky", "pdmp_ensemble_set_bps_options", "pdmp_ensemble_set_bps_moments", "pdmp_ensemble_bps_moments",
     "pdmp_ensemble_set_bps_sticky", "pdmp_ensemble_bps_trace_free_copy", "pdmp_ensemble_bps_final_sticky",
     "pdmp_ensemble_set_flow_bps_modern", "pdmp_ensemble_set_bps_record_limit",
+    "pdmp_ensemble_set_barriers", "pdmp_ensemble_final_barrier",
     "pdmp_ensemble_ess_begin", "pdmp_ensemble_ess_batch", "pdmp_ensemble_ess_end", "pdmp_ensemble_set_gradient_tracking",
     "pdmp_ensemble_path_integrals", "pdmp_ensemble_set_path_integrals", "pdmp_ensemble_set_neighbourhood", "pdmp_ensemble_info",
     "pdmp_ensemble_consume_begin", "pdmp_ensemble_consume", "pdmp_ensemble_consume_async", "pdmp_ensemble_last_consume_ms", "pdmp_ensemble_consume_mean", "pdmp_ensemble_consume_inclusion", "pdmp_ensemble_consume_discretized", "pdmp_ensemble_consume_cummean", "pdmp_ensemble_consume_cummean_copy", "pdmp_ensemble_subtrace_copy", "pdmp_1d_run",
@@ -56,7 +59,7 @@ EXPORTED_SYMBOLS = [
 # include/pdmp_debug.h: diagnostics, not part of the drop-in boundary
 DEBUG_SYMBOLS = ["pdmp_debug_set_kernel", "pdmp_debug_set_spec_g2", "pdmp_debug_set_phase_profile", "pdmp_debug_phase_profile",
                  "pdmp_debug_set_proposal_dump", "pdmp_debug_set_track_groups", "pdmp_debug_set_helper_wave", "pdmp_debug_set_track_lines", "pdmp_debug_buffer_addresses", "pdmp_debug_placement", "pdmp_debug_set_placement", "pdmp_debug_move_buffer", "pdmp_debug_set_helper_steering", "pdmp_debug_set_launch_count_limit", "pdmp_debug_host_drain_probe", "pdmp_debug_set_consumer_overlap", "pdmp_debug_last_kernel", "pdmp_debug_set_logistic_rows", "pdmp_debug_math_probe", "pdmp_debug_math_eval", "pdmp_debug_write_probe", "pdmp_debug_sector_probe",
-                 "pdmp_debug_sticky_eval", "pdmp_debug_trace_append"]
+                 "pdmp_debug_sticky_eval", "pdmp_debug_trace_append", "pdmp_debug_barrier_eval"]
 DEBUG_KERNELS = {"auto": 0, "seq": 1, "spec4": 2, "spec8": 3, "exactp": 4}
 
 
@@ -180,6 +183,9 @@ def load():
     L.pdmp_ensemble_set_flow_bps_modern.argtypes = [vp, C.c_double, C.c_double, vp, C.c_int]
     L.pdmp_ensemble_set_bps_record_limit.argtypes = [vp, i64]
     L.pdmp_debug_sticky_eval.argtypes = [C.c_int, C.c_int, i64, vp, vp, vp, vp]
+    L.pdmp_debug_barrier_eval.argtypes = [C.c_int, C.c_int, i64, vp, vp, vp, vp]
+    L.pdmp_ensemble_set_barriers.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int]
+    L.pdmp_ensemble_final_barrier.argtypes = [vp, i64, i64, vp, vp]
     L.pdmp_debug_trace_append.argtypes = [vp, i64, vp, i64]
     L.pdmp_ensemble_bps_trace_copy.argtypes = [vp, i64, i64, i64, vp, vp, vp]
     L.pdmp_ensemble_bps_final_state.argtypes = [vp, i64, i64, vp, vp, vp, vp]
@@ -251,6 +257,16 @@ def math_eval(fn, a, b=None, c=None, device=0):
     c = np.zeros_like(a) if c is None else np.ascontiguousarray(np.broadcast_to(c, a.shape), dtype=np.float64)
     out = np.empty((2, a.size))
     check(load().pdmp_debug_math_eval(int(device), int(fn), int(a.size), a.ctypes.data, b.ctypes.data, c.ctypes.data, out.ctypes.data))
+    return out
+
+
+def barrier_eval(fn, a, b=None, c=None, device=0):
+    """[2 x n] outputs of the barrier sampler's scalar `fn` (BARRIER_FN_* of include/pdmp_debug.h) as compiled inside pdmp_barrier.hip; parity library only."""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    b = np.zeros_like(a) if b is None else np.ascontiguousarray(np.broadcast_to(b, a.shape), dtype=np.float64)
+    c = np.zeros_like(a) if c is None else np.ascontiguousarray(np.broadcast_to(c, a.shape), dtype=np.float64)
+    out = np.empty((2, a.size))
+    check(load().pdmp_debug_barrier_eval(int(device), int(fn), int(a.size), a.ctypes.data, b.ctypes.data, c.ctypes.data, out.ctypes.data))
     return out
 
 

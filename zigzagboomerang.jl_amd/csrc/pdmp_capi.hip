@@ -58,6 +58,7 @@ static const FamilyInfo FAMILY[] = {
     /* FAM_STICKY_RUN    */ {0, "zz_local_run", true},
     /* FAM_SPEC          */ {1, "zz_local_run", true},     // speculative kernels: [0..8] = cycles per phase, [10] = iterations
     /* FAM_ONE_EVENT     */ {0, "zz_local_run", true},
+    /* FAM_BARRIER       */ {0, "zz_barrier_run", true},
 };
 
 pdmp_status launch_deferred_consumer(pdmp_ensemble* e) {
@@ -179,6 +180,7 @@ pdmp::ZzRunParams run_params(const pdmp_ensemble* e, double T, int flags) {
     P.thf = e->d_thf.p;
     P.reversible = e->reversible;
     P.strong_upperbounds = e->strong_upperbounds;
+    P.barriers = e->d_barriers.p;
     if (general_path(e)) return P;
     if (e->track || e->exactp) {  // the kernels that take a coordinate's neighbours from its index on the plain lattice
         P.lattice_n = e->lattice_n;
@@ -268,6 +270,11 @@ pdmp_status select_family(const pdmp_ensemble* e, const pdmp::ZzRunParams& P, co
     *fam = FAM_BPS;
     if (e->cfg.sampler == PDMP_SAMPLER_BPS) return PDMP_OK;
     const bool sticky = e->cfg.sampler == PDMP_SAMPLER_STICKY_ZIGZAG, dump = e->dbg_dump > 0, profile = e->dbg_phase != 0;
+    if (e->cfg.sampler == PDMP_SAMPLER_BARRIER_ZIGZAG) {  // (set_state has refused everything zz_barrier_run_kernel does not take)
+        *fam = FAM_BARRIER;
+        if (dump) return fail(PDMP_ERR_UNSUPPORTED, "the proposal dump belongs to the one-event kernel");
+        return PDMP_OK;
+    }
     if (general_path(e)) {
         // small d: the chain's state lives in LDS for the whole slice (PDMP_DEBUG_KERNEL_SEQ keeps the records in HBM: A/B runs, parity tests)
         const bool lds_resident = e->dbg_kernel != PDMP_DEBUG_KERNEL_SEQ && pdmp::zz_logistic_lds_supported(P, Q, LT);
@@ -373,6 +380,7 @@ pdmp_status ensemble_run_impl(pdmp_ensemble* e, double T, int flags, void* strea
     case FAM_STICKY_RUN: e->last_kernel = "zz_sticky_run_kernel"; rc = pdmp::launch_zz_sticky_run(P, n, s); break;
     case FAM_SPEC: rc = pdmp::launch_zz_local_spec(P, n, s, &e->last_kernel); break;
     case FAM_ONE_EVENT: e->last_kernel = "zz_local_run_kernel"; rc = pdmp::launch_zz_local_run(P, n, s); break;
+    case FAM_BARRIER: e->last_kernel = "zz_barrier_run_kernel"; rc = pdmp::launch_zz_barrier_run(P, n, s); break;
 #ifdef PDMP_EXTRA_KERNELS
     case FAM_LOGISTIC_ROWS: e->last_kernel = "zz_logistic_rows_kernel"; rc = pdmp::launch_zz_logistic_rows(P, Q, LT, e->keep_integrals, logistic_rows_width(e), n, s); break;
     case FAM_EXACTP: e->last_kernel = "zz_local_exactp_kernel"; rc = pdmp::launch_zz_local_exactp(P, n, s); break;
@@ -442,7 +450,7 @@ pdmp_status pdmp_ensemble_create(const pdmp_config* cfg, pdmp_ensemble** out) {
     if (cfg->nchains <= 0 || cfg->d <= 0) return fail(PDMP_ERR_INVALID, "nchains and d must be positive");
     if (cfg->d >= (int64_t)1 << 31) return fail(PDMP_ERR_UNSUPPORTED, "d must be < 2^31");
     if (cfg->sampler != PDMP_SAMPLER_ZIGZAG_LOCAL && cfg->sampler != PDMP_SAMPLER_ZIGZAG_ALL &&
-        cfg->sampler != PDMP_SAMPLER_BPS && cfg->sampler != PDMP_SAMPLER_STICKY_ZIGZAG)
+        cfg->sampler != PDMP_SAMPLER_BPS && cfg->sampler != PDMP_SAMPLER_STICKY_ZIGZAG && cfg->sampler != PDMP_SAMPLER_BARRIER_ZIGZAG)
         return fail(PDMP_ERR_UNSUPPORTED, "sampler %d has no device kernel yet", cfg->sampler);
     if (cfg->sampler == PDMP_SAMPLER_BPS && cfg->d > 4096)
         return fail(PDMP_ERR_UNSUPPORTED, "BPS keeps x, θ, ∇ϕ in registers (d <= 1024) or registers + scratch (d <= 4096): got %lld", (long long)cfg->d);

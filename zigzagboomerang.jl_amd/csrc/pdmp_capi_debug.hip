@@ -326,4 +326,24 @@ pdmp_status pdmp_debug_sticky_eval(int device, int fn, int64_t n, const double* 
     HIP_TRY(hipMemcpy(out, res.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
     return PDMP_OK;
 }
+
+pdmp_status pdmp_debug_barrier_eval(int device, int fn, int64_t n, const double* a, const double* b, const double* c, double* out) {
+#ifndef PDMP_EXTRA_KERNELS
+    (void)device, (void)fn, (void)n, (void)a, (void)b, (void)c, (void)out;
+    return fail(PDMP_ERR_UNSUPPORTED, "pdmp_debug_barrier_eval: the probe kernel lives in the parity build (build.py --variant parity, -DPDMP_EXTRA_KERNELS)");
+#else
+    if (!a || !b || !c || !out || n <= 0 || n > ((int64_t)1 << 30)) return fail(PDMP_ERR_INVALID, "bad argument");
+    if (fn < PDMP_BARRIER_FN_PT3_L || fn > PDMP_BARRIER_FN_RATES) return fail(PDMP_ERR_INVALID, "pdmp_debug_barrier_eval: unknown function id %d", fn);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(PDMP_ERR_NO_DEVICE, "no HIP device visible");
+    HIP_TRY(hipSetDevice(device));
+    DevBuf<double> in, res;
+    PDMP_TRY(upload_abc(in, n, a, b, c));
+    PDMP_TRY(res.alloc((size_t)n * 2));
+    LAUNCH_TRY("barrier eval", pdmp::launch_barrier_eval(fn, n, in.p, in.p + n, in.p + 2 * n, res.p, nullptr));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, res.p, (size_t)n * 2 * sizeof(double), hipMemcpyDeviceToHost));
+    return PDMP_OK;
+#endif
+}
 }  // extern "C"

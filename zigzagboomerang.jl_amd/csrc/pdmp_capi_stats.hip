@@ -168,6 +168,8 @@ pdmp_status pdmp_ensemble_consume_begin(pdmp_ensemble* e, double grid_dt, int64_
     if (!e) return fail(PDMP_ERR_INVALID, "null argument");
     NEED_FACTORISED(e);
     if (!e->has_state || e->ran) return fail(PDMP_ERR_INVALID, "consume_begin follows set_state and precedes the first run (it snapshots x0, θ0)");
+    if (e->cfg.sampler == PDMP_SAMPLER_BARRIER_ZIGZAG)
+        return fail(PDMP_ERR_UNSUPPORTED, "the device consumers' time away from 0 has no meaning between barriers at other levels: consume the returned trace on the host");
     if (e->cfg.trace_capacity <= 0) return fail(PDMP_ERR_INVALID, "ensemble was created with trace_capacity = 0");
     if (e->flow_kind != 0 || e->lambda_ref > 0)
         return fail(PDMP_ERR_UNSUPPORTED, "the device consumers take time-ordered traces of piecewise-linear paths: ZigZag without refresh clock");

@@ -41,9 +41,9 @@ static pdmp_status set_flow_common(pdmp_ensemble* e, const int64_t* colptr, cons
             }
             e->rowval[p] = (uint32_t)r;
         }
-        if (!has_diag)
-            return fail(PDMP_ERR_UNSUPPORTED, "Γ[%lld,%lld] is structurally zero: i must belong to G1[i]", (long long)i,
-                        (long long)i);
+        if (!has_diag)  // (stickyzz re-bounds i itself at its thaw, src/stickyzz.jl:277-283: a call error there)
+            return fail(e->cfg.sampler == PDMP_SAMPLER_BARRIER_ZIGZAG ? PDMP_ERR_INVALID : PDMP_ERR_UNSUPPORTED,
+                        "Γ[%lld,%lld] is structurally zero: i must belong to G1[i]", (long long)i, (long long)i);
     }
     e->nnz = nnz;
     e->mu.assign(d, 0.0);
@@ -405,6 +405,32 @@ pdmp_status init_state(pdmp_ensemble* e, double t0, const double* x0, const doub
     if (!c) return fail(PDMP_ERR_INVALID, "c is required");
     HIP_TRY(hipSetDevice(e->cfg.device));
     const int64_t d = e->cfg.d, n = e->cfg.nchains;
+    const bool barrier = e->cfg.sampler == PDMP_SAMPLER_BARRIER_ZIGZAG;
+    if (barrier) {
+        // stickyzz (src/stickyzz.jl) runs on zz_barrier_run_kernel alone: everything that kernel does not take is refused here, never served by another
+        if (!e->has_barriers) return fail(PDMP_ERR_INVALID, "pdmp_ensemble_set_barriers must be called before the state");
+        if (e->flow_kind != 0 || e->lambda_ref > 0)
+            return fail(PDMP_ERR_UNSUPPORTED, "stickyzz: a ZigZag flow without refreshment (src/stickyzz.jl has no refresh clock)");
+        if (e->target_kind != 0) return fail(PDMP_ERR_UNSUPPORTED, "stickyzz: the Gaussian target only");
+        if (e->has_g1mask) return fail(PDMP_ERR_UNSUPPORTED, "stickyzz: G = G1 only (no pdmp_ensemble_set_neighbourhood)");
+        if (e->track_requested || e->local_bound)  // (adaptscale: pdmp_ensemble_set_adaptscale itself refuses every sampler but spdmp, PDMP_ERR_UNSUPPORTED)
+            return fail(PDMP_ERR_UNSUPPORTED, "stickyzz: no gradient tracking or LocalBound");
+        if (e->needs_general)
+            return fail(PDMP_ERR_UNSUPPORTED, "stickyzz: neighbourhoods of at most 64 members (|G1[i]| and |G1[i] ∪ G2[i]|), as zz_sticky_run_kernel takes");
+        for (int64_t i = 0; i < d; ++i)  // (the head draw and one draw per re-bounded member come from the 64 candidates of an iteration)
+            if (e->colptr[(size_t)i + 1] - e->colptr[(size_t)i] > 63u)
+                return fail(PDMP_ERR_UNSUPPORTED, "stickyzz: |G1[%lld]| = %u > 63", (long long)i, e->colptr[(size_t)i + 1] - e->colptr[(size_t)i]);
+        if (!x0 || !th0) return fail(PDMP_ERR_UNSUPPORTED, "stickyzz: an explicit state (x0 must lie inside the barriers)");
+        for (int64_t q = 0; q < n * d; ++q) {
+            const pdmp::BarrierEntry& be = e->h_barriers[(size_t)(q % d)];
+            if (!(th0[q] != 0.0) || th0[q] != th0[q])  // dir(ui) = 0 indexes barrier.x[0], src/stickyzz.jl:115,121
+                return fail(PDMP_ERR_INVALID, "stickyzz: θ0[%lld] of chain %lld is %g: every coordinate needs a direction", (long long)(q % d), (long long)(q / d), th0[q]);
+            // a box (lo < hi) holds its coordinate: a start outside it is the reference's own "fix me" (src/stickyzz.jl:121).  lo == hi is one
+            // level met from either side (sspdmp2's (0, 0), :330): any start is inside
+            if (be.lo < be.hi && !(x0[q] >= be.lo && x0[q] <= be.hi))
+                return fail(PDMP_ERR_INVALID, "stickyzz: x0[%lld] = %g of chain %lld lies outside its barriers [%g, %g]", (long long)(q % d), x0[q], (long long)(q / d), be.lo, be.hi);
+        }
+    }
     e->track = false;
     e->track_lg = false;
     if (e->track_requested && e->target_kind == 1) {
@@ -587,10 +613,11 @@ pdmp_status init_state(pdmp_ensemble* e, double t0, const double* x0, const doub
     P.track = e->track ? 1 : 0;
     e->t0_state = t0;
     e->run_T = t0;
-    if (sticky || e->local_bound) {
+    if (sticky || e->local_bound || barrier) {
         if (e->d_thf.n != (size_t)(n * d)) PDMP_TRY(e->d_thf.alloc((size_t)(n * d)));
         P.thf = e->d_thf.p;
     }
+    P.barriers = barrier ? e->d_barriers.p : nullptr;
     LAUNCH_TRY("zz_init", pdmp::launch_zz_init(P, e->stream));
     if (e->track_lg) {
         if (e->d_trk.n != (size_t)(n * d * 4)) PDMP_TRY(e->d_trk.alloc((size_t)(n * d * 4)));
@@ -853,6 +880,56 @@ pdmp_status pdmp_ensemble_set_sticky(pdmp_ensemble* e, const double* kappa, int 
     e->strong_upperbounds = strong_upperbounds;
     e->has_kappa = true;
     e->has_state = false;
+    return PDMP_OK;
+}
+
+pdmp_status pdmp_ensemble_set_barriers(pdmp_ensemble* e, const double* lo, const double* hi, const int32_t* rule_lo, const int32_t* rule_hi,
+                                       const double* kappa_lo, const double* kappa_hi, int strong_upperbounds) {
+    if (!e || !lo || !hi || !rule_lo || !rule_hi || !kappa_lo || !kappa_hi) return fail(PDMP_ERR_INVALID, "null argument");
+    if (e->cfg.sampler != PDMP_SAMPLER_BARRIER_ZIGZAG) return fail(PDMP_ERR_INVALID, "ensemble is not a barrier ZigZag (PDMP_SAMPLER_BARRIER_ZIGZAG)");
+    if (!e->has_flow) return fail(PDMP_ERR_INVALID, "set_flow_zigzag must be called first");
+    const int64_t d = e->cfg.d;
+    std::vector<pdmp::BarrierEntry> tab((size_t)d);
+    for (int64_t i = 0; i < d; ++i) {
+        if (!(lo[i] <= hi[i])) return fail(PDMP_ERR_INVALID, "barriers of coordinate %lld: lo = %g > hi = %g (or NaN)", (long long)i, lo[i], hi[i]);
+        if (!(kappa_lo[i] > 0) || !(kappa_hi[i] > 0))
+            return fail(PDMP_ERR_INVALID, "barriers of coordinate %lld: κ = (%g, %g) must be positive (+Inf: a wall)", (long long)i, kappa_lo[i], kappa_hi[i]);
+        if (rule_lo[i] < 0 || rule_lo[i] > 2 || rule_hi[i] < 0 || rule_hi[i] > 2)
+            return fail(PDMP_ERR_INVALID, "barriers of coordinate %lld: rules (%d, %d) must be PDMP_BARRIER_STICKY / _REFLECT / _REVERSIBLE", (long long)i, rule_lo[i], rule_hi[i]);
+        pdmp::BarrierEntry& be = tab[(size_t)i];
+        be.lo = lo[i];
+        be.hi = hi[i];
+        be.klo = kappa_lo[i];
+        be.khi = kappa_hi[i];
+        be.rules = (uint32_t)rule_lo[i] | ((uint32_t)rule_hi[i] << 8);
+        be.pad = 0;
+    }
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    PDMP_TRY(e->d_barriers.upload(tab));
+    e->h_barriers.swap(tab);
+    e->strong_upperbounds = strong_upperbounds;
+    e->has_barriers = true;
+    e->has_state = false;
+    return PDMP_OK;
+}
+
+pdmp_status pdmp_ensemble_final_barrier(pdmp_ensemble* e, int64_t chain_first, int64_t n, uint8_t* frozen, double* theta_saved) {
+    if (!e) return fail(PDMP_ERR_INVALID, "null argument");
+    if (e->cfg.sampler != PDMP_SAMPLER_BARRIER_ZIGZAG) return fail(PDMP_ERR_INVALID, "ensemble is not a barrier ZigZag (PDMP_SAMPLER_BARRIER_ZIGZAG)");
+    if (!e->has_state) return fail(PDMP_ERR_INVALID, "no state");
+    PDMP_TRY(check_chain_range(e, chain_first, n));
+    if (n == 0) return PDMP_OK;
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(device_sync(e));
+    const int64_t d = e->cfg.d;
+    std::vector<double> vold((size_t)(n * d));
+    HIP_TRY(hipMemcpy(vold.data(), e->d_thf.p + chain_first * d, vold.size() * sizeof(double), hipMemcpyDeviceToHost));
+    if (frozen) {  // v[i] == 0 && v_old[i] != 0, src/stickyzz.jl:266
+        std::vector<double> th((size_t)(n * d));
+        PDMP_TRY(pdmp_ensemble_final_state(e, chain_first, n, nullptr, nullptr, th.data(), nullptr, nullptr));
+        for (size_t q = 0; q < th.size(); ++q) frozen[q] = (th[q] == 0.0 && vold[q] != 0.0) ? 1 : 0;
+    }
+    if (theta_saved) std::copy(vold.begin(), vold.end(), theta_saved);
     return PDMP_OK;
 }
 

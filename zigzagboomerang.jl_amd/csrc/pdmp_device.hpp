@@ -168,6 +168,32 @@ __device__ __forceinline__ double scan_min_f64(double v) {  // inclusive
     return x;
 }
 
+// ------------------------------------------------------------------------------------------ two-level queue
+
+// Level-1 entry (block minimum, argmin) of the block of coordinate j after keys[j] became kj: smaller than the entry -> replace;
+// j WAS the entry and grew -> rescan the 64 keys of the block (lowest index on ties); otherwise nothing to do.
+__device__ __forceinline__ void level1_update(double* bk, uint32_t* bi, const double* keys, int lane, uint32_t j, double kj) {
+    const uint32_t bj = j >> 6;
+    PDMP_LDS_ORDER();
+    const double cur = bk[bj];
+    const uint32_t ci = bi[bj];
+    if (kj < cur || (kj == cur && j < ci)) {
+        if (lane == 0) {
+            bk[bj] = kj;
+            bi[bj] = j;
+        }
+    } else if (ci == j) {
+        const double kv = __hip_atomic_load(keys + (size_t)bj * 64 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const double mn = wave_min_f64(kv);
+        const uint64_t bl = __ballot(kv == mn);
+        const int arg = bl ? (__ffsll((unsigned long long)bl) - 1) : 0;
+        if (lane == 0) {
+            bk[bj] = mn;
+            bi[bj] = bj * 64 + (uint32_t)arg;
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------ contract scalars
 
 // pos(x) = max(zero(x), x), src/common.jl:8
@@ -222,6 +248,41 @@ __device__ __forceinline__ double poisson_time_L(double a, double b, double L) {
     if (a <= 0) return PDMP_INF;
     if (-L <= -(a * a) / b + (a * a) / (2 * b)) return -sq - r;
     return PDMP_INF;
+}
+
+// poisson_time((a, b, c), u) with L = log(u) supplied, src/poissontime.jl:39-65: the waiting time of the rate c + (a + b t)^+, c > 0 -- never
+// infinite.  The same operations on the same operands, in the same order, as the host restatements (oracle/pdmp_oracle.c orc_poisson_time3,
+// tests/ref/stickyzz_ref.c), branch by branch.  (const parameters: tests/test_abi.py counts the two-parameter contract scalars by signature;
+// this one has its own probe, pdmp_debug_barrier_eval.)
+__device__ __forceinline__ double poisson_time3_L(const double a, const double b, const double c, const double L) {
+    if (b > 0) {
+        if (a < 0) {
+            if (-c * a / b + L < 0.0) return sqrt(-2 * b * L + c * c + 2 * a * c) / b - (a + c) / b;  // :43
+            return -L / c;                                                                             // :45
+        }
+        return sqrt(-L * 2.0 * b + (a + c) * (a + c)) / b - (a + c) / b;  // :48
+    } else if (b == 0) {
+        return (a > 0) ? -L / (a + c) : -L / c;  // :52, :54
+    }
+    if (a <= 0.0) return -L / c;  // :58
+    if (-c * a / b - (a * a) / (2 * b) + L > 0.0) return +sqrt((a + c) * (a + c) - 2.0 * L * b) / b - (a + c) / b;  // :60
+    return (-L + (a * a) / (2 * b)) / c;  // :62
+}
+// hitting_time(barrier, ui, flow), src/stickyzz.jl:119-127, with the barrier level of the direction of travel: Inf when v (x - bar) >= 0 (the
+// reference's "sic": a coordinate that sits ON its barrier, a thawed :sticky one, passes through it), else -(x - bar) / v
+__device__ __forceinline__ double barrier_hitting_time(const double x, const double v, const double bar) {
+    return (v * (x - bar) >= 0) ? PDMP_INF : (-(x - bar) / v);
+}
+// λ(i, u, ∇ϕi, b, ::NewFlow), src/stickyzz.jl:129-135: the rate pos(∇ϕi θi) and its bound pos(a + b (t_i - t_old)) -- the bound WITHOUT the
+// 0.01 the proposal time was drawn with (the reference's arithmetic, kept as it is)
+struct RateAndBound {
+    double l, lb;
+};
+__device__ __forceinline__ RateAndBound barrier_rates(const double gth, const double a, const double b, const double dt) {
+    RateAndBound r;
+    r.l = pos_part(gth);
+    r.lb = pos_part(a + b * dt);
+    return r;
 }
 
 // One batch mean and its square to ONE rounding each.  y = (J − Jprev)/(T − T_prev) formed as written costs three roundings (the

@@ -148,6 +148,18 @@ struct CoordConst {
 };
 static_assert(sizeof(CoordConst) == 64, "half a line");
 
+// stickyzz (src/stickyzz.jl): the two barriers of a coordinate, shared by all chains -- StickyBarriers' x, κ and rule (:19-25), index 1 = lower,
+// 2 = upper.  40 bytes, read once per hit, thaw or re-bounded member.
+struct BarrierEntry {
+    double lo, hi;    // levels (-Inf / +Inf: no barrier on that side)
+    double klo, khi;  // thaw rates κ (+Inf: an instantaneous wall)
+    uint32_t rules;   // PDMP_BARRIER_* of the lower barrier | of the upper one << 8
+    uint32_t pad;
+};
+static_assert(sizeof(BarrierEntry) == 40, "barrier table entry");
+// Action (src/stickyzz.jl:170-175) of a coordinate's queued time, kept in the record's `acc` word by the barrier sampler
+constexpr uint64_t BARRIER_ACT_HIT = 0, BARRIER_ACT_REFLECT = 1, BARRIER_ACT_UNFREEZE = 2;
+
 // Read-only tables of the local ZigZag kernels (device pointers).
 struct ZzTables {
     const uint32_t* __restrict__ colptr;
@@ -222,6 +234,8 @@ struct ZzRunParams {
     const double* __restrict__ kappa;  // [d] thaw rates
     double* thf;                       // [nchains x d] saved speeds θf
     int32_t reversible, strong_upperbounds;
+    // stickyzz (src/stickyzz.jl, pdmp_barrier.hip): thf holds v_old, strong_upperbounds as above
+    const BarrierEntry* __restrict__ barriers;  // [d]
 };
 
 struct ZzInitParams {
@@ -247,6 +261,7 @@ struct ZzInitParams {
     const double* __restrict__ diag; // [d]
     int32_t local_bound;             // c::LocalBound (src/local.jl): bounds from the target's derivatives + expiry horizon; thf = renew flags
     int32_t track;                   // records are TrRec (tracked-gradient kernel): also g = Γt[:,i]·x0, gd = Γt[:,i]·θ0 and the bound's sums
+    const BarrierEntry* __restrict__ barriers;  // stickyzz's setup (src/stickyzz.jl:198-208), or nullptr; thf then receives v_old = θ0
     const uint4* __restrict__ g1_member;  // the tables' pattern is G ⊋ G1 (pdmp_ensemble_set_neighbourhood): [nnz] member records, .w flags the entries of G1;
                                           // nullptr: every entry belongs to G1.  FactBoomerang's bound sums over G1[i] alone (src/fact_samplers.jl:59)
 };
@@ -435,6 +450,10 @@ int launch_zz_local_run(const ZzRunParams& p, int64_t nchains, void* stream);
 int launch_zz_local_spec(const ZzRunParams& p, int64_t nchains, void* stream, const char** kname = nullptr);
 int launch_zz_sticky_run(const ZzRunParams& p, int64_t nchains, void* stream);
 int launch_zz_sticky_spec(const ZzRunParams& p, int64_t nchains, void* stream);
+// pdmp_barrier.hip: stickyzz, one event per iteration (the LDS layout is zz_sticky_run_kernel's)
+size_t zz_barrier_lds_bytes(uint32_t nblk_pad, uint32_t blob_w_pad);
+int launch_zz_barrier_run(const ZzRunParams& p, int64_t nchains, void* stream);
+int launch_barrier_eval(int fn, int64_t n, const double* a, const double* b, const double* c, double* out, void* stream);  // (parity build: pdmp_debug_barrier_eval)
 bool zz_spec_supported(uint32_t nblk, uint32_t mmax, uint32_t kmax);
 size_t zz_spec_lds_bytes(uint32_t nblk_pad, uint32_t blob_w_pad);
 size_t zz_spec_wide_lds_bytes(uint32_t nblk_pad, uint32_t blob_w_pad);  // 17 <= |S[i]| <= 32

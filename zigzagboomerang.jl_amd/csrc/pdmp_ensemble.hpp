@@ -197,6 +197,12 @@ struct pdmp_ensemble {
     bool has_kappa = false;
     int reversible = 0, strong_upperbounds = 0;
 
+    // stickyzz (PDMP_SAMPLER_BARRIER_ZIGZAG, pdmp_ensemble_set_barriers): the table on the device and its host copy (set_state checks x0, θ0 against it);
+    // d_thf holds v_old, strong_upperbounds is the member above
+    DevBuf<pdmp::BarrierEntry> d_barriers;
+    std::vector<pdmp::BarrierEntry> h_barriers;
+    bool has_barriers = false;
+
     // consumers and async: streaming trace consumers (pdmp_ensemble_consume_*) -- cursor per (chain, coordinate), per-chain progress, the grid
     DevBuf<unsigned char> d_ccur, d_cmeta;
     DevBuf<double> d_cgrid;
@@ -284,7 +290,7 @@ struct pdmp_ensemble {
 // The event-loop kernel families of pdmp_ensemble_run.  select_family alone decides which one serves an ensemble; what a family does with the phase
 // profile (pdmp_debug_set_phase_profile) and how its launcher's failure reads is stated once, in pdmp_capi.hip's table of FamilyInfo.
 enum KernelFamily { FAM_BPS, FAM_GENERAL, FAM_LOGISTIC_LDS, FAM_LOGISTIC_ROWS, FAM_TRACKL, FAM_TRACKP, FAM_TRACK_GROUPS, FAM_EXACTP,
-                    FAM_STICKY_SPEC, FAM_STICKY_RUN, FAM_SPEC, FAM_ONE_EVENT };
+                    FAM_STICKY_SPEC, FAM_STICKY_RUN, FAM_SPEC, FAM_ONE_EVENT, FAM_BARRIER };
 struct FamilyInfo {
     int phase_kind;        // the `kind` of pdmp_debug_phase_profile its kernels record (pdmp_debug.h), 0: they have no profiling form -- no buffer, no read-back
     const char* launcher;  // "<launcher> launch failed ..."

@@ -108,6 +108,37 @@ __global__ __launch_bounds__(256) void zz_init_kernel(ZzInitParams P) {
             }
             if (P.thf) P.thf[chain * d + i] = 0.0;
         }
+        double th_rec = thi;
+        if (P.barriers) {
+            // src/stickyzz.jl:198-208: a coordinate that starts ON the barrier of its direction of travel starts frozen (speed saved, thaw clock
+            // queued); every other one queues the earlier of its reflection proposal and its hitting time (enqueue_time!, :144-168 -- t0 IS added, :152,159)
+            const BarrierEntry be = P.barriers[i];
+            const bool up = thi > 0;  // dir, :115
+            const double bar = up ? be.hi : be.lo;
+            const double L = pdmp_log(pdmp_u01(seed, PDMP_STREAM_MAIN, (uint64_t)i));
+            P.thf[chain * d + i] = thi;  // v0_old = copy(v0), :182
+            // the loop runs i = 1..d in order and stops coordinates as it goes: b[i] = ab(...) (:199) sees θ = 0 at the members r < i that started frozen
+            auto barrier_of = [&](int64_t r, double thr) { return thr > 0 ? P.barriers[r].hi : P.barriers[r].lo; };
+            gt = 0.0;
+            for (uint32_t p = P.tb.colptr[i]; p < P.tb.colptr[i + 1]; ++p) {
+                const int64_t r = P.tb.rowval[p];
+                const double thr = th_of(r);
+                gt += P.tb.bval[p] * ((r < i && x_of(r) == barrier_of(r, thr)) ? 0.0 : thr);
+            }
+            b = ci / 100 + thi * gt;
+            if (xi != bar) {
+                const double dt0 = P.t0 - P.t0;  // poisson_time(t, b::Tuple, r), src/poissontime.jl:86-92
+                const double trefl = (P.t0 + poisson_time3_L(a + dt0 * b, b, 0.01, L)) - P.t0;  // :147
+                const double thit = barrier_hitting_time(xi, thi, bar);
+                const bool hit = thit <= trefl;  // :149
+                fflag = hit ? BARRIER_ACT_HIT : BARRIER_ACT_REFLECT;
+                key = P.t0 + (hit ? thit : trefl);
+            } else {
+                th_rec = 0.0;  // v0_old[i], v0[i] = v0[i], 0.0, :204
+                fflag = BARRIER_ACT_UNFREEZE;
+                key = P.t0 - L / (up ? be.khi : be.klo);  // :206
+            }
+        }
         if (P.track) {
             // tracked-gradient records: the target's sums next to the bound's (gx, gt above ARE the bound's sums at t0)
             double hx = 0.0, ht = 0.0;
@@ -139,13 +170,13 @@ __global__ __launch_bounds__(256) void zz_init_kernel(ZzInitParams P) {
         } else {
         ZzRec r;
         r.x = xi;
-        r.th = thi;
+        r.th = th_rec;
         r.t = P.t0;
         r.I = 0.0;
         r.t_old = P.t0;
         r.a = a;
         r.b = b;
-        r.acc = fflag;  // sticky: f[i] ("the next event of i is a freeze"), src/ss_fact.jl:165; otherwise acc[i] = 0
+        r.acc = fflag;  // sticky: f[i] ("the next event of i is a freeze"), src/ss_fact.jl:165; stickyzz: action[i]; otherwise acc[i] = 0
         rec[i] = r;
         keys[i] = key;
         }
@@ -174,30 +205,7 @@ size_t zz_local_lds_bytes(uint32_t nblk_pad, uint32_t blob_w_pad) {
     return (size_t)nblk_pad * 8 + 3 * 64 * 8 + (size_t)blob_w_pad * 8 + (size_t)nblk_pad * 4;
 }
 
-// Level-1 entry (block minimum, argmin) of the block of coordinate j after keys[j] became kj: smaller than the entry -> replace;
-// j WAS the entry and grew -> rescan the 64 keys of the block (lowest index on ties); otherwise nothing to do.
-__device__ __forceinline__ void level1_update(double* bk, uint32_t* bi, const double* keys, int lane, uint32_t j, double kj) {
-    const uint32_t bj = j >> 6;
-    PDMP_LDS_ORDER();
-    const double cur = bk[bj];
-    const uint32_t ci = bi[bj];
-    if (kj < cur || (kj == cur && j < ci)) {
-        if (lane == 0) {
-            bk[bj] = kj;
-            bi[bj] = j;
-        }
-    } else if (ci == j) {
-        const double kv = __hip_atomic_load(keys + (size_t)bj * 64 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const double mn = wave_min_f64(kv);
-        const uint64_t bl = __ballot(kv == mn);
-        const int arg = bl ? (__ffsll((unsigned long long)bl) - 1) : 0;
-        if (lane == 0) {
-            bk[bj] = mn;
-            bi[bj] = bj * 64 + (uint32_t)arg;
-        }
-    }
-}
-
+// (level1_update, the level-1 entry of a changed key: pdmp_device.hpp -- pdmp_barrier.hip shares it)
 
 __global__ __launch_bounds__(64) void zz_local_run_kernel(ZzRunParams P) {
     const int lane = threadIdx.x;

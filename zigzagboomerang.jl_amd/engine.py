@@ -162,6 +162,25 @@ class Ensemble:
         kappa = _f64(kappa).reshape(self.d)
         _lib.check(self._L.pdmp_ensemble_set_sticky(self._h, _ptr(kappa), int(bool(reversible)), int(bool(strong_upperbounds))))
 
+    def set_barriers(self, lo, hi, rule_lo, rule_hi, kappa_lo, kappa_hi, strong_upperbounds=False):
+        """stickyzz's barriers (pdmp_ensemble_set_barriers): [d] levels, rules (PDMP_BARRIER_* codes) and thaw rates of the lower and the
+        upper barrier of every coordinate.  After set_flow and set_target, before set_state."""
+        lo, hi = _f64(lo).reshape(self.d), _f64(hi).reshape(self.d)
+        kl, kh = _f64(kappa_lo).reshape(self.d), _f64(kappa_hi).reshape(self.d)
+        rl = np.ascontiguousarray(rule_lo, dtype=np.int32).reshape(self.d)
+        rh = np.ascontiguousarray(rule_hi, dtype=np.int32).reshape(self.d)
+        _lib.check(self._L.pdmp_ensemble_set_barriers(self._h, _ptr(lo), _ptr(hi), _ptr(rl), _ptr(rh), _ptr(kl), _ptr(kh),
+                                                     int(bool(strong_upperbounds))))
+
+    def final_barrier(self, chain_first=0, n=None):
+        """Frozen flags ([n x d] bool: v == 0 and v_old != 0) and saved speeds v_old ([n x d]) of a barrier ensemble (pdmp_ensemble_final_barrier)."""
+        if n is None:
+            n = self.nchains - chain_first
+        fr = np.empty((n, self.d), dtype=np.uint8)
+        vo = np.empty((n, self.d))
+        _lib.check(self._L.pdmp_ensemble_final_barrier(self._h, int(chain_first), int(n), _ptr(fr), _ptr(vo)))
+        return dict(frozen=fr.astype(bool), theta_saved=vo)
+
     def set_local_bound(self, enable=True):
         """c::LocalBound, src/local.jl: bounds from the target's own derivatives with an expiry horizon."""
         _lib.check(self._L.pdmp_ensemble_set_local_bound(self._h, int(bool(enable))))

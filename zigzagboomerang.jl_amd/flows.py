@@ -44,6 +44,25 @@ class ZigZag:
 
 
 @dataclass
+class StickyBarriers:
+    """StickyBarriers(x, rule, κ) -- src/stickyzz.jl:19-25: the lower and the upper barrier of one coordinate.  x: their levels (−inf / inf:
+    no barrier on that side); rule: what each does to the restored speed when the coordinate thaws ("sticky" keeps it, "reflect" negates it,
+    "reversible" flips its sign by a coin); κ: their thaw rates (inf: an instantaneous wall).  StickyBarriers() is the reference's default:
+    no barriers at all."""
+    x: tuple = (-np.inf, np.inf)
+    rule: tuple = ("reflect", "reflect")
+    κ: tuple = (np.inf, np.inf)
+
+    def __post_init__(self):
+        self.x = (float(self.x[0]), float(self.x[1]))
+        self.rule = (str(self.rule[0]).lstrip(":"), str(self.rule[1]).lstrip(":"))
+        self.κ = (float(self.κ[0]), float(self.κ[1]))
+        for r in self.rule:
+            if r not in ("sticky", "reflect", "reversible"):
+                raise ValueError("rule must be 'sticky', 'reflect' or 'reversible', got %r" % (r,))
+
+
+@dataclass
 class FactBoomerang:
     """FactBoomerang(Γ, μ, λ, σ=diag(Γ).^(-0.5); ρ=0.0) -- src/types.jl:71-79: factorised Boomerang dynamics preserving
     N(μ, inv(Diagonal(Γ))), refreshment rate λ > 0."""

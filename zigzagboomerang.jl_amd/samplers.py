@@ -16,7 +16,7 @@ import scipy.sparse as sp
 from . import _lib
 from .engine import Ensemble
 from .flows import (Boomerang, Boomerang1d, BouncyParticle, FactBoomerang, LocalBound, FactTrace, GaussianTarget, GaussianTarget1d, LogisticTarget,
-                    PDMPTrace, ZigZag, ZigZag1d)
+                    PDMPTrace, StickyBarriers, ZigZag, ZigZag1d)
 
 DEFAULT_SEED = 0x5EED0000
 
@@ -193,6 +193,46 @@ def sspdmp(target, t0, x0, θ0, T, c, *GFκ, reversible=False, strong_upperbound
                    trace_capacity, trace, sticky=(np.asarray(κ, dtype=np.float64), reversible, strong_upperbounds), G=G)
 
 
+def stickyzz(target, t0, x0, θ0, T, c, F, barriers, *, strong_upperbounds=False, adapt=False, factor=1.5, seed=DEFAULT_SEED, device=0,
+             trace_capacity=None, trace=True, details=False):
+    """The ZigZag with sticky and reflecting barriers: stickyzz(u0, target::StructuredTarget, flow::StickyFlow(F), upper_bounds::
+    StickyUpperBounds(G, G1, Γ, c; adapt, strong, multiplier=factor), barriers, EndTime(T)) (src/stickyzz.jl:176-218) with G = G1 = the pattern of
+    F.Γ, in the call shape of the other samplers.  barriers: a list of d StickyBarriers, or one for all coordinates.  Returns
+    Ξ, t′, (t, x, θ), (acc, num) like the reference (:217); x0 / θ0 may be [nchains, d] (outputs then carry a leading chain axis).  Box
+    constraints, truncated Gaussians, positivity constraints, sticking at any level with its own stickiness on either side.
+
+    details=True (engine-only keyword) appends a dict: c (the bounds after adaptation), frozen (v == 0 and v_old != 0) and θ_saved (v_old)."""
+    if not isinstance(F, ZigZag) or isinstance(F, FactBoomerang):
+        raise TypeError("stickyzz takes F::ZigZag (StickyFlow(F), src/stickyzz.jl:28-30)")
+    d = np.asarray(x0).shape[-1]
+    if isinstance(barriers, StickyBarriers):
+        barriers = [barriers] * d
+    barriers = list(barriers)
+    if len(barriers) != d or not all(isinstance(b, StickyBarriers) for b in barriers):
+        raise TypeError("barriers: a list of d StickyBarriers, or one for all coordinates")
+    tab = (np.array([b.x[0] for b in barriers]), np.array([b.x[1] for b in barriers]),
+           np.array([_lib.BARRIER_RULES[b.rule[0]] for b in barriers], dtype=np.int32),
+           np.array([_lib.BARRIER_RULES[b.rule[1]] for b in barriers], dtype=np.int32),
+           np.array([b.κ[0] for b in barriers]), np.array([b.κ[1] for b in barriers]), strong_upperbounds)
+    return _zigzag(_lib.SAMPLER_BARRIER_ZIGZAG, target, t0, x0, θ0, T, c, F, factor, adapt, seed, device, trace_capacity, trace,
+                   barriers=tab, details=details)
+
+
+def sspdmp2(target, t0, x0, θ0, T, c, G, Z, κ, *, strong_upperbounds=False, adapt=False, factor=1.5, seed=DEFAULT_SEED, device=0,
+            trace_capacity=None, trace=True):
+    """sspdmp2(∇ϕ2, t, x0, v0, T, c, ::Nothing, Z, κ, args...; strong_upperbounds, adapt, factor=1.5) (src/stickyzz.jl:323-339): the sticky
+    ZigZag written with the barrier framework -- barriers (0, 0), (:sticky, :sticky), (κ[i], κ[i]) on every coordinate.  Returns (trace, acc)
+    like the reference (:338), acc being the pair (acc, num)."""
+    if G is not None:
+        raise TypeError("sspdmp2(∇ϕ2, t, x0, v0, T, c, ::Nothing, Z, κ, ...): the seventh argument is None (src/stickyzz.jl:323)")
+    d = np.asarray(x0).shape[-1]
+    κ = np.broadcast_to(np.asarray(κ, dtype=np.float64), (d,))
+    barriers = [StickyBarriers((0.0, 0.0), ("sticky", "sticky"), (κ[i], κ[i])) for i in range(d)]
+    Ξ, _, _, acc = stickyzz(target, t0, x0, θ0, T, c, Z, barriers, strong_upperbounds=strong_upperbounds, adapt=adapt, factor=factor, seed=seed,
+                            device=device, trace_capacity=trace_capacity, trace=trace)
+    return Ξ, acc
+
+
 class Partition:
     """Partition(nt, n) (src/parallel.jl:4-31): n coordinates in nt chunks of k = n ÷ nt; pt(i) -> (chunk, offset), pt(chunk, offset) -> i
     (0-based here)."""
@@ -300,7 +340,7 @@ def _pattern_of(G, d):
 
 
 def _zigzag(sampler, target, t0, x0, θ0, T, c, F, factor, adapt, seed, device, trace_capacity, trace, sticky=None,
-            adaptscale=False, tracked=False, G=None):
+            adaptscale=False, tracked=False, G=None, barriers=None, details=False):
     if not isinstance(F, (ZigZag, FactBoomerang)):
         raise TypeError("the device path supports F::ZigZag and F::FactBoomerang")
     if not isinstance(target, (GaussianTarget, LogisticTarget)):
@@ -332,6 +372,8 @@ def _zigzag(sampler, target, t0, x0, θ0, T, c, F, factor, adapt, seed, device, 
         ens.set_target(target)
         if sticky is not None:
             ens.set_sticky(*sticky)
+        if barriers is not None:
+            ens.set_barriers(*barriers)
         if adaptscale:
             ens.set_adaptscale(True)
         if local_bound:
@@ -352,6 +394,7 @@ def _zigzag(sampler, target, t0, x0, θ0, T, c, F, factor, adapt, seed, device, 
         fs = ens.final_state()
         cnt = ens.counters()
         sig = ens.final_sigma() if adaptscale else None
+        fb = ens.final_barrier() if barriers is not None else None
     finally:
         ens.close()
     traces = []
@@ -368,6 +411,14 @@ def _zigzag(sampler, target, t0, x0, θ0, T, c, F, factor, adapt, seed, device, 
     num = cnt["num"].astype(np.int64)
     c_out = fs["c"] if adapt else np.broadcast_to(c, (nch, d)).copy()
     acc = cnt["nacc"].astype(np.int64) if sticky is not None else fs["acc"]  # sticky: scalar acc (src/ss_fact.jl:175)
+    if barriers is not None:  # Ξ, t′, u, acc (src/stickyzz.jl:217): acc::AcceptanceDiagnostics is the scalar pair
+        acc = cnt["nacc"].astype(np.int64)
+        tp = cnt["t_last"].astype(np.float64)
+        extra = dict(c=c_out, frozen=fb["frozen"], θ_saved=fb["theta_saved"])
+        if single:
+            out = traces[0], float(tp[0]), (fs["t"][0], fs["x"][0], fs["theta"][0]), (int(acc[0]), int(num[0]))
+            return out + (({k: v[0] for k, v in extra.items()},) if details else ())
+        return (traces, tp, (fs["t"], fs["x"], fs["theta"]), (acc, num)) + ((extra,) if details else ())
     if single:
         return traces[0], (fs["t"][0], fs["x"][0], fs["theta"][0]), (acc[0], int(num[0])), c_out[0]
     return traces, (fs["t"], fs["x"], fs["theta"]), (acc, num), c_out
