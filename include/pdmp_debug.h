@@ -166,6 +166,13 @@ pdmp_status pdmp_debug_barrier_eval(int device, int fn, int64_t n, const double*
  * pdmp_ensemble_run on that ensemble is refused with PDMP_ERR_INVALID (until the next set_state).
  */
 pdmp_status pdmp_debug_trace_append(pdmp_ensemble* ens, int64_t chain, const pdmp_event* ev, int64_t n);
+/* Its twin for a PDMP_SAMPLER_BPS ensemble (csrc/pdmp_consume_bps.hip; tests/test_gpu_bps_consumers.py): n events -- t [n], x and theta [n x d], and
+ * for a sticky ensemble f [n x d] bytes (non-zero = free; NULL otherwise) -- into slots [ntrace, ntrace + n) of the BPS trace buffers, ntrace and
+ * nevents bumped by n.  PDMP_ERR_INVALID for a call before pdmp_ensemble_bps_consume_begin, a bad chain, n < 0, ntrace + n > trace_capacity, f given
+ * on an ensemble that is not sticky or missing on one that is, and a factorised ensemble.  pdmp_ensemble_run is then refused until the next
+ * set_state_bps. */
+pdmp_status pdmp_debug_bps_trace_append(pdmp_ensemble* ens, int64_t chain, const double* t, const double* x, const double* theta, const uint8_t* f,
+                                        int64_t n);
 
 /*
  * Measurement hook: time (ms per launch, HIP events) of a write-only kernel with the event-record store pattern of the bouncy

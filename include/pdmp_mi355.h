@@ -539,6 +539,37 @@ pdmp_status pdmp_ensemble_consume_cummean_copy(pdmp_ensemble* ens, int64_t chain
 pdmp_status pdmp_ensemble_subtrace_copy(pdmp_ensemble* ens, int64_t chain, const int64_t* J, int64_t nJ, pdmp_event* out, int64_t out_cap,
                                         int64_t* n_out);
 
+/* ------------------------------------------------------------------ trace consumers of the Bouncy Particle family (PDMPTrace)
+ *
+ * mean(Ξ), cummean(Ξ) and collect(discretize(Ξ, dt)) of a PDMPTrace (src/trace.jl:129-150, 229-266) -- event-recorded BouncyParticle and
+ * Boomerang, their sticky forms, the speed-recorded BouncyParticle -- computed from the BPS trace buffers slice by slice, in the manner of the
+ * calls above: one event of this family is 8(2d + 1) bytes, and these three are what callers copy the trace to the host for.
+ *   bps_consume_begin(grid_dt, grid_points)  after set_state_bps, before the first run: (t0, x0, θ0) become every coordinate's cursor, a sticky
+ *                                        ensemble starts all free; grid_points > 0 reserves [nchains x grid_points x d] doubles, row 0 = x0;
+ *   bps_consume()                        after EVERY run slice and before trace_reset; per event (t2, x2, θ2[, f2]): the grid rows t0 + k·grid_dt < t2
+ *                                        from the cursor (x + θ·τ; a Boomerang (x − μ)·cos τ + θ·sin τ + μ with pdmp_sincos of pdmp_detmath.h; a
+ *                                        coordinate that is not free keeps x), then y += (x + x2)(t2 − t), then the cursor moves to the event;
+ *                                        its kernel time is what pdmp_ensemble_last_consume_ms returns afterwards;
+ *   bps_consume_mean(chain_first, n, ...)  y / T_last [n x d] as the reference writes it (:229-246: no ½) and T_last [n] (t0 before any event);
+ *   bps_consume_inclusion(...)           sticky ensembles only (PDMP_ERR_INVALID otherwise): the fraction of [t0, T_last] each coordinate was free
+ *                                        (1, the initial mask, where T_last <= t0);
+ *   bps_consume_discretized(...)         the contract of pdmp_ensemble_consume_discretized: rows [k_first, k_first + k_count) of a chain;
+ *                                        *npoints = the number of k with t0 + k·grid_dt < T_last, at least 1, NOT clamped to grid_points;
+ *   bps_consume_cummean(enable)          bps_consume also leaves y / (2·t2) [d] at every consumed event's slot (:263; 0/0 = NaN at t2 = 0);
+ *   bps_consume_cummean_copy(chain, first, count, y)   those rows [count x d], the slots pdmp_ensemble_bps_trace_copy returns the events of.
+ * Values are those of zigzagboomerang.jl_amd/trace.py up to the order of summation and, for a Boomerang, pdmp_sincos against libm's sin / cos;
+ * tests/ref/pdmp_trace_ref.c states the arithmetic sequentially and the device agrees with it bit for bit.  PDMP_ERR_INVALID on an ensemble that
+ * is not PDMP_SAMPLER_BPS, for begin after a run / with trace_capacity = 0 / with grid_points > 0 and grid_dt <= 0, for the others before begin.
+ */
+pdmp_status pdmp_ensemble_bps_consume_begin(pdmp_ensemble* ens, double grid_dt, int64_t grid_points);
+pdmp_status pdmp_ensemble_bps_consume(pdmp_ensemble* ens);
+pdmp_status pdmp_ensemble_bps_consume_mean(pdmp_ensemble* ens, int64_t chain_first, int64_t n, double* mean, double* T_last);
+pdmp_status pdmp_ensemble_bps_consume_inclusion(pdmp_ensemble* ens, int64_t chain_first, int64_t n, double* prob, double* T_last);
+pdmp_status pdmp_ensemble_bps_consume_discretized(pdmp_ensemble* ens, int64_t chain, int64_t k_first, int64_t k_count, double* out,
+                                                  int64_t* npoints, void** grid_dev);
+pdmp_status pdmp_ensemble_bps_consume_cummean(pdmp_ensemble* ens, int enable);
+pdmp_status pdmp_ensemble_bps_consume_cummean_copy(pdmp_ensemble* ens, int64_t chain, int64_t first, int64_t count, double* y);
+
 /* what the ensemble was created with (any pointer may be NULL) */
 pdmp_status pdmp_ensemble_info(pdmp_ensemble* ens, int64_t* nchains, int64_t* d, int64_t* trace_capacity, int* device);
 

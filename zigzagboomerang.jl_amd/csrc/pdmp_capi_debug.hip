@@ -291,6 +291,44 @@ pdmp_status pdmp_debug_trace_append(pdmp_ensemble* e, int64_t chain, const pdmp_
     return PDMP_OK;
 }
 
+// Test hook (include/pdmp_debug.h): the BPS twin of pdmp_debug_trace_append.  n given events (t [n], x and θ [n x d], f [n x d] bytes for a sticky
+// ensemble) behind what `chain`'s segment holds, counted in its header as a run would have counted them; no kernel is launched and no state changes,
+// so the ensemble cannot run afterwards.
+pdmp_status pdmp_debug_bps_trace_append(pdmp_ensemble* e, int64_t chain, const double* t, const double* x, const double* theta, const uint8_t* f, int64_t n) {
+    if (!e) return fail(PDMP_ERR_INVALID, "null argument");
+    if (e->cfg.sampler != PDMP_SAMPLER_BPS) return fail(PDMP_ERR_INVALID, "bps_trace_append: the ensemble was not created with PDMP_SAMPLER_BPS (pdmp_debug_trace_append)");
+    if (!e->bc_on || !e->has_state) return fail(PDMP_ERR_INVALID, "pdmp_ensemble_bps_consume_begin first");
+    if (chain < 0 || chain >= e->cfg.nchains || n < 0) return fail(PDMP_ERR_INVALID, "bad argument");
+    if (n > 0 && (!t || !x || !theta)) return fail(PDMP_ERR_INVALID, "null argument");
+    if (f && !e->bps.sticky) return fail(PDMP_ERR_INVALID, "bps_trace_append: free masks given to an ensemble that is not sticky");
+    if (!f && e->bps.sticky && n > 0) return fail(PDMP_ERR_INVALID, "bps_trace_append: a sticky ensemble's events carry free masks");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(device_sync(e));
+    pdmp::DevChain h;
+    HIP_TRY(hipMemcpy(&h, e->d_hdr.p + chain, sizeof h, hipMemcpyDeviceToHost));
+    const int64_t cap = e->cfg.trace_capacity, d = e->cfg.d, W = pdmp::BPS_STICKY_WORDS;
+    if (h.c.ntrace > (uint64_t)cap || n > cap - (int64_t)h.c.ntrace)
+        return fail(PDMP_ERR_INVALID, "bps_trace_append: %lld events behind %llu do not fit trace_capacity = %lld", (long long)n, (unsigned long long)h.c.ntrace, (long long)cap);
+    const int64_t slot = chain * cap + (int64_t)h.c.ntrace;
+    if (n > 0) {
+        HIP_TRY(hipMemcpy(e->b_ev_t.p + slot, t, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(e->b_ev_x.p + slot * d, x, (size_t)(n * d) * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(e->b_ev_th.p + slot * d, theta, (size_t)(n * d) * sizeof(double), hipMemcpyHostToDevice));
+        if (f) {
+            std::vector<uint64_t> w((size_t)(n * W), 0ull);  // bit i & 63 of word i >> 6
+            for (int64_t k = 0; k < n; ++k)
+                for (int64_t i = 0; i < d; ++i)
+                    if (f[k * d + i]) w[(size_t)(k * W + (i >> 6))] |= 1ull << (i & 63);
+            HIP_TRY(hipMemcpy(e->b_ev_f.p + slot * W, w.data(), w.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+        }
+    }
+    h.c.ntrace += (uint64_t)n;
+    h.c.nevents += (uint64_t)n;
+    HIP_TRY(hipMemcpy(&e->d_hdr.p[chain].c, &h.c, sizeof h.c, hipMemcpyHostToDevice));
+    e->trace_appended = true;
+    return PDMP_OK;
+}
+
 // What the host could drain instead: `bytes` of the trace buffer copied to pinned host memory, in GB/s (a measurement for bench.py's pipeline
 // object, not a code path of the engine)
 pdmp_status pdmp_debug_host_drain_probe(pdmp_ensemble* e, int64_t bytes, double* gbps) {

@@ -515,6 +515,26 @@ int launch_consume_inclusion(int64_t d, int64_t nchains, bool with_z, double t0,
 int launch_zz_path_integrals(const ZzRec* rec, int64_t rec_stride, int64_t d, int64_t nchains, const int64_t* probes, int64_t nprobe,
                              double T, double* out, void* stream);
 int launch_math_probe(uint64_t seed, int64_t n, double* out, void* stream);
+// pdmp_consume_bps.hip: the streaming consumers of the Bouncy Particle family's trace buffers.  One block of pointers and numbers for its three
+// kernels: the trace (ev_f: a sticky ensemble's masks, else nullptr), the chain headers, the Boomerang's centre (nullptr: linear flow), the state
+// begin snapshots, the cursors [nchains x d] (cft: sticky only), the per-(chain, strip) progress, the grid [nchains x K x d] and the cummean
+// slots [nchains x cap x d] (either may be nullptr)
+struct BpsConsumeArgs {
+    const double *ev_t, *ev_x, *ev_th;
+    const uint64_t* ev_f;
+    const DevChain* hdr;
+    const double* mu;
+    const double *x0, *th0;
+    double *cx, *cth, *cy, *cft;
+    void* meta;
+    double *grid, *cm;
+    int64_t d, cap, nchains, nstrips, K;
+    double t0, dt;
+};
+size_t bps_consume_meta_bytes();
+int launch_bps_consume_init(const BpsConsumeArgs& p, void* stream);
+int launch_bps_consume_events(const BpsConsumeArgs& p, void* stream);
+int launch_bps_consume_read(const BpsConsumeArgs& p, int inclusion, int64_t chain_first, int64_t n, double* out, double* T_out, void* stream);
 
 #ifdef PDMP_EXTRA_KERNELS
 // pdmp_debug_math_eval (include/pdmp_debug.h, parity library only): a translation unit that calls the shared scalar functions of pdmp_device.hpp

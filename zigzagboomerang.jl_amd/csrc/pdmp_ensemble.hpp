@@ -262,6 +262,14 @@ struct pdmp_ensemble {
     DevBuf<double> b_kappa, b_thf, b_tfrez;  // sticky: [d]; [nchains x d] saved speeds; [nchains x d] freezing / thaw times
     DevBuf<uint64_t> b_fmask, b_ev_f;        // sticky: [nchains x 16], [nchains x cap x 16] free masks (bit e & 63 of word e >> 6)
     DevBuf<double> b_udiag, b_sudiag, b_mstate;  // speed-recorded: [d] u, [d] sqrt(u), [nchains x 4] {Δ, action, V, Δrec}
+    // the consumers of the BPS trace (pdmp_ensemble_bps_consume_*, pdmp_consume_bps.hip): the cursors x, θ, y -- and a sticky ensemble's free time --
+    // [nchains x d] each, the per-(chain, strip) progress, the grid [nchains x K x d], the cummean slots [nchains x cap x d] (empty: not enabled).
+    // t0 is t0_state; pdmp_debug_bps_trace_append sets trace_appended like its factorised twin
+    DevBuf<double> bc_cur, bc_grid, bc_cm;
+    DevBuf<unsigned char> bc_meta;
+    bool bc_on = false, bc_cummean = false;
+    double bc_dt = 0.0;
+    int64_t bc_K = 0;
 
     pdmp::ZzTables tables() const {
         pdmp::ZzTables tb{};

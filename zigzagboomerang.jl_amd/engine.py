@@ -311,6 +311,7 @@ class Ensemble:
         theta0 = _f64(theta0).reshape(self.nchains, self.d)
         seeds = np.ascontiguousarray(seeds, dtype=np.uint64).reshape(self.nchains)
         _lib.check(self._L.pdmp_ensemble_set_state_bps(self._h, float(t0), _ptr(x0), _ptr(theta0), float(c), _ptr(seeds)))
+        self.t0 = float(t0)
 
     def bps_trace(self, chain, first=0, count=None, counters=None):
         if counters is None:
@@ -511,6 +512,69 @@ class Ensemble:
         if k_count > 0:
             _lib.check(self._L.pdmp_ensemble_consume_discretized(self._h, int(chain), int(k_first), k_count, _ptr(out), None, None))
         return self.t0 + dt * (k_first + np.arange(max(k_count, 0))), out
+
+    # ---- trace consumers of the Bouncy Particle family on the device (pdmp_ensemble_bps_consume_*)
+    def bps_consume_begin(self, grid_dt=0.0, grid_points=0):
+        """After set_state_bps, before the first run: (t0, x0, θ0) become the cursors; grid_points > 0 reserves the grid t0 + k·grid_dt."""
+        _lib.check(self._L.pdmp_ensemble_bps_consume_begin(self._h, float(grid_dt), int(grid_points)))
+        self._bps_grid = (float(grid_dt), int(grid_points))
+
+    def bps_consume(self):
+        """After every run slice, before trace_reset: applies the buffered events to the cursors, the sums and the grid."""
+        _lib.check(self._L.pdmp_ensemble_bps_consume(self._h))
+
+    def bps_consume_mean(self, chain_first=0, n=None):
+        """(mean [n x d], T_last [n]): mean(Ξ::PDMPTrace) of src/trace.jl:229-246 per chain -- Σ (x + x₂)(t₂ − t) / T_last, without a ½, as trace.mean."""
+        if n is None:
+            n = self.nchains - chain_first
+        m, T = np.empty((n, self.d)), np.empty(n)
+        _lib.check(self._L.pdmp_ensemble_bps_consume_mean(self._h, int(chain_first), int(n), _ptr(m), _ptr(T)))
+        return m, T
+
+    def bps_consume_inclusion(self, chain_first=0, n=None):
+        """(fraction of [t0, T_last] each coordinate was free [n x d], T_last [n]) of a sticky ensemble, as trace.inclusion_prob."""
+        if n is None:
+            n = self.nchains - chain_first
+        p, T = np.empty((n, self.d)), np.empty(n)
+        _lib.check(self._L.pdmp_ensemble_bps_consume_inclusion(self._h, int(chain_first), int(n), _ptr(p), _ptr(T)))
+        return p, T
+
+    def bps_consume_discretized(self, chain, k_first=0, k_count=None):
+        """(grid times [npoints], positions [npoints x d]) of collect(discretize(Ξ::PDMPTrace, dt)) for one chain (src/trace.jl:129-150); the first
+        row is t0 => x0.  Raises if the run went past the grid given to bps_consume_begin (the later points were dropped on the device)."""
+        npts = C.c_int64()
+        _lib.check(self._L.pdmp_ensemble_bps_consume_discretized(self._h, int(chain), 0, 0, None, C.byref(npts), None))
+        dt, K = self._bps_grid
+        if int(npts.value) > K:
+            raise ValueError("bps_consume_discretized: the chain's trace reaches grid point %d, bps_consume_begin was given %d points" % (int(npts.value), K))
+        k_count = int(npts.value) - k_first if k_count is None else int(k_count)
+        out = np.empty((max(k_count, 0), self.d))
+        if k_count > 0:
+            _lib.check(self._L.pdmp_ensemble_bps_consume_discretized(self._h, int(chain), int(k_first), k_count, _ptr(out), None, None))
+        return self.t0 + dt * (k_first + np.arange(max(k_count, 0))), out
+
+    def bps_consume_cummean(self, enable=True):
+        """cummean(Ξ::PDMPTrace) on the device (src/trace.jl:248-266): with it on, bps_consume() also leaves y / (2 t) [d] at every event's slot."""
+        _lib.check(self._L.pdmp_ensemble_bps_consume_cummean(self._h, int(bool(enable))))
+
+    def bps_consume_cummean_rows(self, chain, count, first=0):
+        """Rows [first, first + count) of `chain`'s last consumed segment, [count x d], aligned with bps_trace(chain)."""
+        y = np.empty((int(count), self.d))
+        _lib.check(self._L.pdmp_ensemble_bps_consume_cummean_copy(self._h, int(chain), int(first), int(count), _ptr(y) if y.size else None))
+        return y
+
+    def debug_bps_trace_append(self, chain, t, x, theta, f=None):
+        """Test hook (pdmp_debug_bps_trace_append, include/pdmp_debug.h): events t [n], x and theta [n x d] -- and f [n x d] bool on a sticky
+        ensemble -- behind what `chain`'s trace segment holds, counted like sampled ones; after bps_consume_begin.  The ensemble refuses to run
+        afterwards."""
+        t = _f64(t).reshape(-1)
+        n = t.size
+        x = _f64(x).reshape(n, self.d)
+        theta = _f64(theta).reshape(n, self.d)
+        fb = None if f is None else np.ascontiguousarray(np.asarray(f).reshape(n, self.d) != 0, dtype=np.uint8)
+        some = n > 0
+        _lib.check(self._L.pdmp_debug_bps_trace_append(self._h, int(chain), _ptr(t) if some else None, _ptr(x) if some else None,
+                                                      _ptr(theta) if some else None, None if fb is None else fb.ctypes.data, int(n)))
 
     def set_path_integrals(self, enable=True):
         """Keep ∫x_i dt next to the state (default) or not (pdmp_ensemble_set_path_integrals); before set_state."""

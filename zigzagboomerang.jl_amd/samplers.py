@@ -30,6 +30,32 @@ def _drain(ens, events):
     ens.trace_reset()
 
 
+def _consume_capacity(consume, trace, trace_capacity):
+    """The trace capacity of a Bouncy Particle run: with consume=... the events are written to the device buffer even where trace=False."""
+    if consume is None:
+        return trace_capacity if trace else 0
+    if not isinstance(consume, dict) or set(consume) - {"dt", "points"}:
+        raise TypeError("consume=dict(dt=..., points=...)")
+    if trace_capacity <= 0:
+        raise ValueError("consume=... reads the device trace buffer: trace_capacity must be positive")
+    return trace_capacity
+
+
+def _consume_result(ens, consume, single, sticky):
+    """The extra element of a consume=... run: dict(mean, T, grid_t, grid_x[, inclusion]) from the device consumers; grid_t / grid_x are per
+    chain (a chain's grid ends before ITS last event), None without points."""
+    mean, T = ens.bps_consume_mean()
+    out = dict(mean=mean, T=T, grid_t=None, grid_x=None)
+    if sticky:
+        out["inclusion"] = ens.bps_consume_inclusion()[0]
+    if int(consume.get("points", 0)) > 0:
+        grids = [ens.bps_consume_discretized(k) for k in range(ens.nchains)]
+        out["grid_t"], out["grid_x"] = [g[0] for g in grids], [g[1] for g in grids]
+    if single:
+        out = {k: (v if v is None else v[0]) for k, v in out.items()}
+    return out
+
+
 def _split_G(GF, G):
     """spdmp(∇ϕ, t0, x0, θ0, T, c, F) or spdmp(∇ϕ, t0, x0, θ0, T, c, G, F) as in the reference (src/sfact.jl:162,214); G may also be a keyword."""
     if len(GF) == 1:
@@ -65,18 +91,18 @@ def spdmp(target, t0, x0, θ0, T, c, *GF, factor=1.8, adapt=False, adaptscale=Fa
 
 
 def pdmp(target, *args, factor=1.8, adapt=False, subsample=None, seed=DEFAULT_SEED, device=0, trace_capacity=None, trace=True,
-         moments=False, oscn=False):
+         moments=False, oscn=False, consume=None):
     """pdmp(∇ϕ, t0, x0, θ0, T, c, F, ...) -- the d-dimensional drivers, see _pdmp_nd -- or, with a 1-d flow as the sixth argument,
     pdmp(∇ϕ, x, θ, T, c, Flow::Union{ZigZag1d, Boomerang1d}; adapt=false, factor=2.0) -> Ξ, acc/num  (src/zigzagboom1d.jl:34-67)."""
     if len(args) == 5 and isinstance(args[4], (ZigZag1d, Boomerang1d)):
-        if subsample or moments or oscn:
-            raise TypeError("subsample and moments are keywords of the non-factorised pdmp (BouncyParticle / Boomerang)")
+        if subsample or moments or oscn or consume is not None:
+            raise TypeError("subsample, moments and consume are keywords of the non-factorised pdmp (BouncyParticle / Boomerang)")
         x0, θ0, T, c, Flow = args
         return _pdmp_1d(target, x0, θ0, T, c, Flow, 2.0 if factor == 1.8 else factor, adapt, seed, device, trace_capacity)
     if len(args) != 6:
         raise TypeError("expected pdmp(target, t0, x0, θ0, T, c, F, ...) or pdmp(target, x, θ, T, c, Flow1d, ...)")
     return _pdmp_nd(target, *args, factor=factor, adapt=adapt, subsample=subsample, seed=seed, device=device, trace_capacity=trace_capacity,
-                    trace=trace, moments=moments, oscn=oscn)
+                    trace=trace, moments=moments, oscn=oscn, consume=consume)
 
 
 def _pdmp_1d(target, x0, θ0, T, c, Flow, factor, adapt, seed, device, trace_capacity):
@@ -117,7 +143,7 @@ def _pdmp_1d(target, x0, θ0, T, c, Flow, factor, adapt, seed, device, trace_cap
 
 
 def _pdmp_nd(target, t0, x0, θ0, T, c, F, *, factor=1.8, adapt=False, subsample=None, seed=DEFAULT_SEED, device=0,
-             trace_capacity=None, trace=True, moments=False, oscn=False):
+             trace_capacity=None, trace=True, moments=False, oscn=False, consume=None):
     """pdmp(∇ϕ, t0, x0, θ0, T, c, F::ZigZag, args...) = spdmp(..., All(), ...) (src/sfact.jl:236): every proposal moves
     ALL coordinates (no sparsity assumption on ∇ϕ); same return value as spdmp.
 
@@ -130,6 +156,13 @@ def _pdmp_nd(target, t0, x0, θ0, T, c, F, *, factor=1.8, adapt=False, subsample
     moments=True (BouncyParticle / Boomerang, engine-only keyword): a fifth element dict(mean, var, T) -- the exact time averages
     ∫x dt/(T − t0) and ∫x² dt/(T − t0) − mean² over [t0, T] kept by the event loop (pdmp_ensemble_set_bps_moments), [n x d] or [d]; the
     first four elements are bit for bit those of moments=False.  With trace=False no event is written at all.
+
+    consume=dict(dt=..., points=...) (BouncyParticle / Boomerang, the speed-recorded form included; engine-only keyword): the device consumers
+    (pdmp_ensemble_bps_consume_*) run over every slice before its buffer is recycled, and one more element is returned: dict(mean, T, grid_t,
+    grid_x) -- trace.mean(Ξ), the last event time, and trace.discretize(Ξ, dt) on a grid of at most `points` rows (ValueError if the run
+    passes it; grid_t / grid_x are None without points), [n x ...] or squeezed for a single chain, the grids one array per chain.  The
+    earlier elements are bit for bit those without the keyword.  With trace=False the events are still written to the device buffer and
+    consumed, but never copied to the host; trace_capacity=0 raises.
 
     pdmp(dϕ, ∇ϕ!, t0, x0, θ0, T, c::LocalBound, B::BouncyParticle; oscn=false, adapt=false, factor=2.0) (src/not_fact_samplers.jl:336-384),
     the speed-recorded driver: B.Γ is None (BouncyParticle(None, None, λref, ρ, L=..., U=...)), target is a GaussianTarget (dϕ and ∇ϕ! are
@@ -145,7 +178,8 @@ def _pdmp_nd(target, t0, x0, θ0, T, c, F, *, factor=1.8, adapt=False, subsample
             raise ValueError("`subsample=true` required.")  # ArgumentError, :338
         if moments:
             raise TypeError("moments is a keyword of the event-recorded pdmp (a BouncyParticle with a Γ, or a Boomerang)")
-        return _bps_modern(target, t0, x0, θ0, T, c, F, 2.0 if factor == 1.8 else factor, adapt, seed, device, trace_capacity, trace, oscn)
+        return _bps_modern(target, t0, x0, θ0, T, c, F, 2.0 if factor == 1.8 else factor, adapt, seed, device, trace_capacity, trace, oscn,
+                           consume=consume)
     if oscn:
         raise TypeError("oscn is a keyword of the speed-recorded pdmp (BouncyParticle(None, None, ...), c::LocalBound)")
     subsample = bool(subsample)
@@ -153,19 +187,19 @@ def _pdmp_nd(target, t0, x0, θ0, T, c, F, *, factor=1.8, adapt=False, subsample
         if target is not None and not isinstance(target, GaussianTarget):
             raise TypeError("BouncyParticle: target is None (∇ϕ!(y, x) = B.Γ(x − B.μ)) or a GaussianTarget of its own")
         return _bps(t0, x0, θ0, T, c, F, 2.0 if factor == 1.8 else factor, adapt, seed, device, trace_capacity, trace,
-                    target=target, subsample=subsample, moments=moments)
+                    target=target, subsample=subsample, moments=moments, consume=consume)
     if isinstance(F, Boomerang):  # pdmp(∇ϕ!, t0, x0, θ0, T, c, B::Boomerang) (test/maintest.jl:139-154); target = GaussianTarget
         if not isinstance(target, GaussianTarget):
             raise TypeError("Boomerang: target must be a GaussianTarget (∇ϕ!(y, x) = Γ(x − μ))")
         return _bps(t0, x0, θ0, T, c, F, 2.0 if factor == 1.8 else factor, adapt, seed, device, trace_capacity, trace,
-                    target=target, subsample=subsample, moments=moments)
-    if subsample or moments:
-        raise TypeError("subsample and moments are keywords of the non-factorised pdmp (BouncyParticle / Boomerang)")
+                    target=target, subsample=subsample, moments=moments, consume=consume)
+    if subsample or moments or consume is not None:
+        raise TypeError("subsample, moments and consume are keywords of the non-factorised pdmp (BouncyParticle / Boomerang)")
     return _zigzag(_lib.SAMPLER_ZIGZAG_ALL, target, t0, x0, θ0, T, c, F, factor, adapt, seed, device, trace_capacity, trace)
 
 
 def sspdmp(target, t0, x0, θ0, T, c, *GFκ, reversible=False, strong_upperbounds=False, factor=None, adapt=False,
-           seed=DEFAULT_SEED, device=0, trace_capacity=None, trace=True, G=None):
+           seed=DEFAULT_SEED, device=0, trace_capacity=None, trace=True, G=None, consume=None):
     """Sticky ZigZag: sspdmp(∇ϕ, t0, x0, θ0, T, c, [G,] F::ZigZag, κ, args...; reversible, strong_upperbounds, factor=1.5,
     adapt) (src/ss_fact.jl:159-160,217) -> Ξ, (t, x, θ), (acc, num), c with scalar acc, num (:175,214).  G as in spdmp (:167-172).
 
@@ -173,6 +207,7 @@ def sspdmp(target, t0, x0, θ0, T, c, *GFκ, reversible=False, strong_upperbound
     strong_upperbounds, adapt, factor=2.0) (src/ss_not_fact.jl:182-201) -> Ξ, (t, x, θ), (acc, num), c.  Ξ is a PDMPTrace carrying f0 and f
     ([events x d] bool, True = free); its first event is (t0, x0, θ0, all free) (:189).  target as in pdmp: None (∇ϕ!(y, x) = B.Γ(x − B.μ))
     or a GaussianTarget for a BouncyParticle, a GaussianTarget for a Boomerang.  κ: [d] or a scalar.  No G, no `reversible`.
+    consume=dict(dt=..., points=...) as in pdmp; the extra element also holds `inclusion`, trace.inclusion_prob(Ξ).
 
     factor=None is each signature's own default: 1.5 for a ZigZag, 2.0 for a BouncyParticle / Boomerang; a value given is used as given."""
     if len(GFκ) == 2 and isinstance(GFκ[0], (BouncyParticle, Boomerang)):
@@ -184,7 +219,9 @@ def sspdmp(target, t0, x0, θ0, T, c, *GFκ, reversible=False, strong_upperbound
         if isinstance(F, BouncyParticle) and target is not None and not isinstance(target, GaussianTarget):
             raise TypeError("BouncyParticle: target is None (∇ϕ!(y, x) = B.Γ(x − B.μ)) or a GaussianTarget of its own")
         return _bps(t0, x0, θ0, T, c, F, 2.0 if factor is None else factor, adapt, seed, device, trace_capacity, trace, target=target,
-                    sticky=(GFκ[1], strong_upperbounds))
+                    sticky=(GFκ[1], strong_upperbounds), consume=consume)
+    if consume is not None:
+        raise TypeError("consume is a keyword of the sticky BouncyParticle / Boomerang (the ZigZag's device consumers are Ensemble.consume_*)")
     if len(GFκ) not in (2, 3):
         raise TypeError("expected sspdmp(target, t0, x0, θ0, T, c, [G,] F, κ, ...)")
     G, F = _split_G(GFκ[:-1], G)
@@ -424,7 +461,7 @@ def _zigzag(sampler, target, t0, x0, θ0, T, c, F, factor, adapt, seed, device, 
     return traces, (fs["t"], fs["x"], fs["theta"]), (acc, num), c_out
 
 
-def _bps_modern(target, t0, x0, θ0, T, c, B, factor, adapt, seed, device, trace_capacity, trace, oscn):
+def _bps_modern(target, t0, x0, θ0, T, c, B, factor, adapt, seed, device, trace_capacity, trace, oscn, consume=None):
     """The speed-recorded Bouncy Particle on the device (pdmp_ensemble_set_flow_bps_modern): one chain per row of x0."""
     c = float(np.asarray(c.c, dtype=np.float64).reshape(-1)[0])
     x0 = np.asarray(x0, dtype=np.float64)
@@ -439,7 +476,7 @@ def _bps_modern(target, t0, x0, θ0, T, c, B, factor, adapt, seed, device, trace
     if trace_capacity is None:
         want = int(T) if count else int(4 * B.λref * max(float(T) - t0, 1.0))
         trace_capacity = int(min(max(64, want), (1 << 28) // max(2 * d, 1)))
-    cap = trace_capacity if trace else 0
+    cap = _consume_capacity(consume, trace, trace_capacity)
     ens = Ensemble(nch, d, sampler=_lib.SAMPLER_BPS, adapt=adapt, factor=factor, device=device, trace_capacity=cap)
     ts, xs, ths = [[] for _ in range(nch)], [[] for _ in range(nch)], [[] for _ in range(nch)]
     try:
@@ -448,6 +485,8 @@ def _bps_modern(target, t0, x0, θ0, T, c, B, factor, adapt, seed, device, trace
         if B.L is not None:
             ens.set_mass_cholesky(B.L)
         ens.set_state_bps(t0, X0, TH0, c, seeds)
+        if consume is not None:
+            ens.bps_consume_begin(consume.get("dt", 0.0), consume.get("points", 0))
         if count:
             ens.set_bps_record_limit(int(T))
         T_end = float("inf") if count else float(T)
@@ -458,6 +497,8 @@ def _bps_modern(target, t0, x0, θ0, T, c, B, factor, adapt, seed, device, trace
                 raise RuntimeError("Tuning parameter `c` too small.")  # :230, :262
             if np.any(cnt["status"] == _lib.CHAIN_STALLED):
                 raise AssertionError("Δrec > 0.0")  # :239
+            if consume is not None:
+                ens.bps_consume()
             if trace:
                 for k in range(nch):
                     if cnt["ntrace"][k]:
@@ -465,11 +506,13 @@ def _bps_modern(target, t0, x0, θ0, T, c, B, factor, adapt, seed, device, trace
                         ts[k].append(a)
                         xs[k].append(b_)
                         ths[k].append(c_)
+            if trace or consume is not None:
                 ens.trace_reset()
             if not _lib.needs_rerun(cnt["status"]):
                 break
         fs = ens.bps_final_state()
         cnt = ens.counters()
+        consumed = None if consume is None else _consume_result(ens, consume, single, False)
     finally:
         ens.close()
     traces = []
@@ -480,11 +523,14 @@ def _bps_modern(target, t0, x0, θ0, T, c, B, factor, adapt, seed, device, trace
             traces.append(PDMPTrace(B, t0, X0[k].copy(), TH0[k].copy(), np.empty(0), np.empty((0, d)), np.empty((0, d))))
     acc, num = cnt["nacc"].astype(np.int64), cnt["num"].astype(np.int64)
     if single:
-        return traces[0], (fs["t"][0], fs["x"][0], fs["theta"][0]), (int(acc[0]), int(num[0])), fs["c"][0]
-    return traces, (fs["t"], fs["x"], fs["theta"]), (acc, num), fs["c"]
+        out = traces[0], (fs["t"][0], fs["x"][0], fs["theta"][0]), (int(acc[0]), int(num[0])), fs["c"][0]
+    else:
+        out = traces, (fs["t"], fs["x"], fs["theta"]), (acc, num), fs["c"]
+    return out if consume is None else out + (consumed,)
 
 
-def _bps(t0, x0, θ0, T, c, B, factor, adapt, seed, device, trace_capacity, trace, target=None, subsample=False, moments=False, sticky=None):
+def _bps(t0, x0, θ0, T, c, B, factor, adapt, seed, device, trace_capacity, trace, target=None, subsample=False, moments=False, sticky=None,
+         consume=None):
     local_bound = isinstance(c, LocalBound)
     if local_bound:
         c = float(np.asarray(c.c, dtype=np.float64).reshape(-1)[0])
@@ -496,7 +542,7 @@ def _bps(t0, x0, θ0, T, c, B, factor, adapt, seed, device, trace_capacity, trac
     seeds = (np.uint64(seed) + np.arange(nch, dtype=np.uint64)) if np.isscalar(seed) else np.asarray(seed, np.uint64)
     if trace_capacity is None:
         trace_capacity = int(min(max(256, 64 * max(T - t0, 1.0)), (1 << 28) // max(2 * d, 1)))
-    cap = trace_capacity if trace else 0
+    cap = _consume_capacity(consume, trace, trace_capacity)
     ens = Ensemble(nch, d, sampler=_lib.SAMPLER_BPS, adapt=adapt, factor=factor, device=device, trace_capacity=cap)
     try:
         if isinstance(B, Boomerang):
@@ -512,6 +558,8 @@ def _bps(t0, x0, θ0, T, c, B, factor, adapt, seed, device, trace_capacity, trac
         if sticky is not None:
             ens.set_bps_sticky(*sticky)
         ens.set_state_bps(t0, X0, TH0, float(c), seeds)
+        if consume is not None:
+            ens.bps_consume_begin(consume.get("dt", 0.0), consume.get("points", 0))
         fs_ = [[] for _ in range(nch)]
         ts = [[] for _ in range(nch)]
         xs = [[] for _ in range(nch)]
@@ -527,6 +575,8 @@ def _bps(t0, x0, θ0, T, c, B, factor, adapt, seed, device, trace_capacity, trac
                     if sticky is not None:  # (either error(...) of src/ss_not_fact.jl:129-132,160)
                         raise RuntimeError("Tuning parameter `c` too small, or a coordinate froze away from 0 (|x[i]| > 1e-8).")
                     raise RuntimeError("Tuning parameter `c` too small.")  # src/not_fact_samplers.jl:82
+                if consume is not None:
+                    ens.bps_consume()
                 if trace:
                     for k in range(nch):
                         if cnt["ntrace"][k]:
@@ -536,6 +586,7 @@ def _bps(t0, x0, θ0, T, c, B, factor, adapt, seed, device, trace_capacity, trac
                             ths[k].append(c_)
                             if sticky is not None:
                                 fs_[k].append(ens.bps_trace_free(k, counters=cnt))
+                if trace or consume is not None:
                     ens.trace_reset()
                 if not _lib.needs_rerun(cnt["status"]):  # (both resume with the next run)
                     break
@@ -543,6 +594,7 @@ def _bps(t0, x0, θ0, T, c, B, factor, adapt, seed, device, trace_capacity, trac
                 J = ens.bps_moments(T)
         fs = ens.bps_final_state()
         cnt = ens.counters()
+        consumed = None if consume is None else _consume_result(ens, consume, single, sticky is not None)
     finally:
         ens.close()
     traces = []
@@ -560,10 +612,10 @@ def _bps(t0, x0, θ0, T, c, B, factor, adapt, seed, device, trace_capacity, trac
         out = traces[0], (fs["t"][0], fs["x"][0], fs["theta"][0]), (int(acc[0]), int(num[0])), fs["c"][0]
     else:
         out = traces, (fs["t"], fs["x"], fs["theta"]), (acc, num), fs["c"]
-    if not moments:
-        return out
-    mean = J[0] / (T - t0)
-    var = J[1] / (T - t0) - mean * mean
-    if single:
-        mean, var = mean[0], var[0]
-    return out + (dict(mean=mean, var=var, T=T),)
+    if moments:
+        mean = J[0] / (T - t0)
+        var = J[1] / (T - t0) - mean * mean
+        if single:
+            mean, var = mean[0], var[0]
+        out = out + (dict(mean=mean, var=var, T=T),)
+    return out if consume is None else out + (consumed,)

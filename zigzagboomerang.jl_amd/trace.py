@@ -100,7 +100,7 @@ def _discretize_pdmp(tr: PDMPTrace, dt):
     d = len(tr.x0)
     if len(tr.t) == 0:
         return np.array([tr.t0]), tr.x0[None].copy()
-    n = int(np.ceil((tr.t[-1] - tr.t0) / dt))
+    n = int(np.ceil((tr.t[-1] - tr.t0) / dt)) + 1  # (+ 1: the quotient of a last event an ulp past a grid time rounds to that grid point's index)
     grid = tr.t0 + dt * np.arange(n)
     grid = grid[grid < tr.t[-1]]
     te = np.concatenate([[tr.t0], tr.t])
