@@ -473,8 +473,8 @@ pdmp_status pdmp_ensemble_bps_final_sticky(pdmp_ensemble* ens, int64_t chain_fir
  *           :161-164, refresh! :173-180);  [d] > 0: the diagonal-U form, U = PDiagMat(u): reflect! with z = u .* ∇ϕx, refresh! with
  *           unwhiten = √u .* z, V = ‖θ ./ √u‖ (:156-172, :197).
  *   oscn    the orthogonal-subspace Crank-Nicolson bounce of src/oscn.jl (normalize = false) instead of reflect!; L = I only.
- * Call order, on a PDMP_SAMPLER_BPS ensemble: set_flow_bps_modern; pdmp_ensemble_set_target_gaussian_csc (REQUIRED: this flow has no Γ of
- * its own); optionally pdmp_ensemble_set_mass_cholesky (L form only); pdmp_ensemble_set_state_bps(t0, x0, θ0, c, seeds) with c = LocalBound(c).c.
+ * Call order, on a PDMP_SAMPLER_BPS ensemble: set_flow_bps_modern; pdmp_ensemble_set_target_gaussian_csc or
+ * pdmp_ensemble_set_target_bps_logistic (a target is REQUIRED: this flow has no Γ of its own); optionally pdmp_ensemble_set_mass_cholesky (L form only); pdmp_ensemble_set_state_bps(t0, x0, θ0, c, seeds) with c = LocalBound(c).c.
  * adapt / factor are the ensemble configuration's.  d <= 1024.
  * set_state_bps returns PDMP_ERR_UNSUPPORTED naming the option for: d > 1024; set_bps_moments(order >= 1); set_bps_sticky; set_bps_options
  * (subsample or local_bound: they belong to the other driver, this one always bounds locally and always subsamples); oscn with u_diag or with
@@ -492,6 +492,26 @@ pdmp_status pdmp_ensemble_set_flow_bps_modern(pdmp_ensemble* ens, double lambda_
  * T and n comes first (pass T = +Inf for the count alone).  After set_flow_bps_modern (which resets it to 0); PDMP_ERR_INVALID otherwise or for n < 0.
  */
 pdmp_status pdmp_ensemble_set_bps_record_limit(pdmp_ensemble* ens, int64_t n);
+/*
+ * A Bayesian logistic regression as the target of the speed-recorded driver: the reference's own application of it (turing/lr.jl:105-139,
+ * tilde/lr.jl:55-98, the docstring at src/not_fact_samplers.jl:285-334).  A is the n x d design in CSC (column = coordinate, rows ascending,
+ * explicit zeros allowed), At its transpose in CSC (column = observation), y[n] successes and m[n] trials with 0 <= y_i <= m_i, gamma0 >= 0 a
+ * scalar prior precision.  With η = A x, ζ = A θ and p_i = 1 / (1 + pdmp_exp(−η_i)):
+ *   ϕ(x)    = Σ_i [ m_i log(1 + e^{η_i}) − y_i η_i ] + (γ0/2)‖x‖²
+ *   ∇ϕ!(x)  = Aᵀ r + γ0 x,                   r_i = m_i p_i − y_i
+ *   dϕ(x,θ) = ( Σ_i r_i ζ_i + γ0 θ·x ,  Σ_i m_i p_i (1 − p_i) ζ_i² + γ0 θ·θ )
+ * Call order, on a PDMP_SAMPLER_BPS ensemble: set_flow_bps_modern; this call IN PLACE OF pdmp_ensemble_set_target_gaussian_csc (the later of
+ * the two wins); optionally set_mass_cholesky; set_bps_record_limit; set_state_bps.  u_diag, oscn, adapt / factor, the counters, bps_trace_copy,
+ * bps_final_state, trace_reset, the BPS trace gather and pdmp_ensemble_bps_consume_* serve it unchanged; sliced, drained and paused runs
+ * continue bit for bit (every chain carries η from launch to launch).
+ * PDMP_ERR_INVALID: NULL; n <= 0; A / At inconsistent (nnz differ, colptr[0] != 0, rows out of range or not ascending, At not the transpose
+ * pattern of A); y / m out of range or not finite; gamma0 < 0 or not finite; another sampler; a state exists.
+ * set_state_bps returns PDMP_ERR_UNSUPPORTED naming the cause for a flow other than set_flow_bps_modern (plain set_flow_bps, Boomerang,
+ * sticky) and where 8 d + 16 n bytes (the [d] staging buffer, η and ζ in LDS) exceed 160 KiB.
+ */
+pdmp_status pdmp_ensemble_set_target_bps_logistic(pdmp_ensemble* ens, int64_t n, const int64_t* A_colptr, const int64_t* A_rowval,
+                                                  const double* A_nzval, const int64_t* At_colptr, const int64_t* At_rowval,
+                                                  const double* At_nzval, const double* y, const double* m, double gamma0);
 
 /* ------------------------------------------------------------------ trace consumers on the device (what callers do next with Ξ)
  *

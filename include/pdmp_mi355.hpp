@@ -92,6 +92,15 @@ struct LogisticTarget {
     double gamma0 = 0.01;
     int64_t k_sub = 10;
 };
+// dϕ, ∇ϕ! of a Bayesian logistic regression for the speed-recorded pdmp (turing/lr.jl:105-139, tilde/lr.jl:55-98):
+// ϕ(x) = Σ_i [m_i log(1 + e^{η_i}) − y_i η_i] + (γ0/2)‖x‖², η = A x.  A is n x d (A.n = d columns), At its transpose (At.n = n columns),
+// y successes, m trials (empty: ones); pdmp_ensemble_set_target_bps_logistic
+struct LogisticRegression {
+    int64_t n = 0;  // observations
+    SparseCSC A, At;
+    std::vector<double> y, m;
+    double gamma0 = 0.0;
+};
 
 struct Options {  // the reference's keyword arguments
     double factor = 1.8;
@@ -223,6 +232,12 @@ inline void set_target(Ensemble& e, const LogisticTarget& g) {
     check(pdmp_ensemble_set_target_logistic(e.get(), g.n, g.A.colptr.data(), g.A.rowval.data(), g.A.nzval.data(),
                                             g.At.colptr.data(), g.At.rowval.data(), g.At.nzval.data(), g.y.data(), g.ny.data(),
                                             g.mu.data(), g.gamma0, g.k_sub));
+}
+inline void set_target(Ensemble& e, const LogisticRegression& g) {
+    const std::vector<double> ones(g.m.empty() ? (size_t)g.n : 0, 1.0);
+    check(pdmp_ensemble_set_target_bps_logistic(e.get(), g.n, g.A.colptr.data(), g.A.rowval.data(), g.A.nzval.data(), g.At.colptr.data(),
+                                                g.At.rowval.data(), g.At.nzval.data(), g.y.data(), g.m.empty() ? ones.data() : g.m.data(),
+                                                g.gamma0));
 }
 inline void set_flow(Ensemble& e, const ZigZag& F) {
     check(pdmp_ensemble_set_flow_zigzag(e.get(), F.Gamma.colptr.data(), F.Gamma.rowval.data(), F.Gamma.nzval.data(), opt(F.mu),
@@ -450,11 +465,12 @@ inline Result<PDMPTrace> pdmp(const GaussianTarget& target, double t0, const std
 }
 
 // pdmp(dϕ, ∇ϕ!, t0, x0, θ0, T, c::LocalBound, flow::BouncyParticle; oscn, adapt, factor=2.0)  -- src/not_fact_samplers.jl:336-384, the
-// speed-recorded Bouncy Particle: dϕ = (θ'Γt(x−μt), θ'Γtθ) and ∇ϕ! = Γt(x−μt) of the Gaussian target; B.Gamma is empty.  The trace holds one
-// record per 1/λref of speed-time and does not begin with (t0, x0, θ0).  T is an end time (the last record has t >= T); the overload taking
-// an int64_t is the reference's `T::Int`, a number of samples.
+// speed-recorded Bouncy Particle: dϕ = (θ'Γt(x−μt), θ'Γtθ) and ∇ϕ! = Γt(x−μt) of the Gaussian target, or those of a LogisticRegression;
+// B.Gamma is empty.  The trace holds one record per 1/λref of speed-time and does not begin with (t0, x0, θ0).  T is an end time (the last
+// record has t >= T); the overload taking an int64_t is the reference's `T::Int`, a number of samples.
 namespace detail {
-inline Result<PDMPTrace> modern(const GaussianTarget& target, double t0, const std::vector<double>& x0, const std::vector<double>& theta0,
+template <class Target>
+inline Result<PDMPTrace> modern(const Target& target, double t0, const std::vector<double>& x0, const std::vector<double>& theta0,
                                 double T, int64_t nsamples, LocalBound c, const BouncyParticle& B, Options o) {
     if (o.factor == 1.8) o.factor = 2.0;
     if (B.Gamma.n != 0) throw std::invalid_argument("pdmp(..., c::LocalBound, B): the speed-recorded driver takes BouncyParticle(missing, missing, ...): B.Gamma must be empty");
@@ -477,6 +493,16 @@ inline Result<PDMPTrace> pdmp(const GaussianTarget& target, double t0, const std
     return detail::modern(target, t0, x0, theta0, T, 0, c, B, o);
 }
 inline Result<PDMPTrace> pdmp(const GaussianTarget& target, double t0, const std::vector<double>& x0, const std::vector<double>& theta0,
+                              int64_t nsamples, LocalBound c, const BouncyParticle& B, Options o = {}) {
+    if (nsamples <= 0) throw std::invalid_argument("pdmp(..., T::Int, ...): a positive number of samples");
+    return detail::modern(target, t0, x0, theta0, std::numeric_limits<double>::infinity(), nsamples, c, B, o);
+}
+
+inline Result<PDMPTrace> pdmp(const LogisticRegression& target, double t0, const std::vector<double>& x0, const std::vector<double>& theta0,
+                              double T, LocalBound c, const BouncyParticle& B, Options o = {}) {
+    return detail::modern(target, t0, x0, theta0, T, 0, c, B, o);
+}
+inline Result<PDMPTrace> pdmp(const LogisticRegression& target, double t0, const std::vector<double>& x0, const std::vector<double>& theta0,
                               int64_t nsamples, LocalBound c, const BouncyParticle& B, Options o = {}) {
     if (nsamples <= 0) throw std::invalid_argument("pdmp(..., T::Int, ...): a positive number of samples");
     return detail::modern(target, t0, x0, theta0, std::numeric_limits<double>::infinity(), nsamples, c, B, o);

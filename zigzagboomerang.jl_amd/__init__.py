@@ -9,4 +9,4 @@ from . import _lib, benchlib, build, ess, parallel, problems, trace  # noqa: F40
 from .engine import Ensemble  # noqa: F401
 from .samplers import Partition, parallel_spdmp, pdmp, spdmp, sspdmp, sspdmp2, stickyzz  # noqa: F401
 from .flows import (Boomerang, Boomerang1d, BouncyParticle, LocalBound, FactBoomerang, FactTrace, GaussianTarget, GaussianTarget1d,  # noqa: F401
-                    LogisticTarget, PDMPTrace, StickyBarriers, ZigZag, ZigZag1d)
+                    LogisticRegressionTarget, LogisticTarget, PDMPTrace, StickyBarriers, ZigZag, ZigZag1d)

@@ -47,7 +47,7 @@ EXPORTED_SYMBOLS = [
     "pdmp_ensemble_bps_final_state", "pdmp_ensemble_set_sticky", "pdmp_ensemble_set_adaptscale", "pdmp_ensemble_final_sigma", "pdmp_ensemble_set_flow_boomerang", "pdmp_ensemble_set_local_bound", "pdmp_ensemble_set_target_logistic", "pdmp_ensemble_set_flow_factboomerang",
     "pdmp_ensemble_set_mass_cholesky", "pdmp_ensemble_set_bps_options", "pdmp_ensemble_set_bps_moments", "pdmp_ensemble_bps_moments",
     "pdmp_ensemble_set_bps_sticky", "pdmp_ensemble_bps_trace_free_copy", "pdmp_ensemble_bps_final_sticky",
-    "pdmp_ensemble_set_flow_bps_modern", "pdmp_ensemble_set_bps_record_limit",
+    "pdmp_ensemble_set_flow_bps_modern", "pdmp_ensemble_set_bps_record_limit", "pdmp_ensemble_set_target_bps_logistic",
     "pdmp_ensemble_set_barriers", "pdmp_ensemble_final_barrier",
     "pdmp_ensemble_ess_begin", "pdmp_ensemble_ess_batch", "pdmp_ensemble_ess_end", "pdmp_ensemble_set_gradient_tracking",
     "pdmp_ensemble_path_integrals", "pdmp_ensemble_set_path_integrals", "pdmp_ensemble_set_neighbourhood", "pdmp_ensemble_info",
@@ -191,6 +191,7 @@ def load():
     L.pdmp_ensemble_bps_trace_free_copy.argtypes = [vp, i64, i64, i64, vp]
     L.pdmp_ensemble_bps_final_sticky.argtypes = [vp, i64, i64, vp, vp]
     L.pdmp_ensemble_set_flow_bps_modern.argtypes = [vp, C.c_double, C.c_double, vp, C.c_int]
+    L.pdmp_ensemble_set_target_bps_logistic.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, f64]
     L.pdmp_ensemble_set_bps_record_limit.argtypes = [vp, i64]
     L.pdmp_debug_sticky_eval.argtypes = [C.c_int, C.c_int, i64, vp, vp, vp, vp]
     L.pdmp_debug_barrier_eval.argtypes = [C.c_int, C.c_int, i64, vp, vp, vp, vp]

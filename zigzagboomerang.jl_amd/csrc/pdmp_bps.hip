@@ -942,6 +942,7 @@ int launch_bps_run(const BpsRunParams& p, int64_t nchains, bool diag, void* stre
 
 #include "pdmp_bps_sticky.inc"  // the sticky Bouncy Particle / Boomerang (src/ss_not_fact.jl): kernels of their own, nothing above changes
 #include "pdmp_bps_modern.inc"  // the speed-recorded Bouncy Particle (src/not_fact_samplers.jl:151-384): kernels of its own as well
+#include "pdmp_bps_logit.inc"   // the same driver on the logistic-regression target (pdmp_ensemble_set_target_bps_logistic): η and ζ in LDS
 
 #ifdef PDMP_EXTRA_KERNELS
 // pdmp_debug_math_eval: the shared scalars (pdmp_device.hpp) this unit calls, as compiled here

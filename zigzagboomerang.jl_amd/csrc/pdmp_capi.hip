@@ -360,7 +360,10 @@ pdmp_status ensemble_run_impl(pdmp_ensemble* e, double T, int flags, void* strea
     int rc = 0;
     switch (fam) {
     case FAM_BPS:
-        if (e->bps.modern) {
+        if (e->bps.modern && e->bps.logit) {
+            e->last_kernel = "bps_logit_run_kernel";
+            rc = pdmp::launch_bps_logit_run(B, bps_modern_params(e), bps_logit_params(e), n, s);
+        } else if (e->bps.modern) {
             e->last_kernel = "bps_modern_run_kernel";
             rc = pdmp::launch_bps_modern_run(B, bps_modern_params(e), n, s);
         } else if (e->bps.sticky) {

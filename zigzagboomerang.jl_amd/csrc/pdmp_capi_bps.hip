@@ -15,6 +15,22 @@ pdmp::BpsModernParams bps_modern_params(const pdmp_ensemble* e) {
     return q;
 }
 
+pdmp::BpsLogitParams bps_logit_params(const pdmp_ensemble* e) {
+    pdmp::BpsLogitParams g{};
+    g.A_colptr = e->bl_Acp.p;
+    g.A_rowval = e->bl_Arv.p;
+    g.A_nzval = e->bl_Anz.p;
+    g.At_colptr = e->bl_Atcp.p;
+    g.At_rowval = e->bl_Atrv.p;
+    g.At_nzval = e->bl_Atnz.p;
+    g.y = e->bl_y.p;
+    g.m = e->bl_m.p;
+    g.eta = e->bl_eta.p;
+    g.n = e->bl_n;
+    g.gamma0 = e->bl_gamma0;
+    return g;
+}
+
 static void fill_bps_ext(const pdmp_ensemble* e, pdmp::BpsRunParams& B) {
     B.local_bound = e->bps.local_bound;
     B.subsample = e->bps.subsample;
@@ -169,10 +185,15 @@ pdmp_status init_state_bps(pdmp_ensemble* e, double t0, const double* x0, const 
         if (e->bps.flow_kind == 1 && e->bps.mass_tables)
             return fail(PDMP_ERR_UNSUPPORTED, "set_bps_sticky: a Boomerang with a general mass factor L (set_mass_cholesky) is not implemented: identity only");
     }
+    if (e->bps.logit && (!e->bps.modern || e->bps.sticky))
+        return fail(PDMP_ERR_UNSUPPORTED, "set_target_bps_logistic: the logistic-regression target belongs to the speed-recorded driver "
+                    "(pdmp_ensemble_set_flow_bps_modern), not to %s", e->bps.sticky ? "a sticky ensemble (set_bps_sticky)"
+                    : e->bps.flow_kind == 1 ? "a Boomerang (set_flow_boomerang)" : "the event-recorded set_flow_bps");
     if (e->bps.modern) {
         // the speed-recorded driver always bounds locally and always subsamples; its options are its own
-        if (!e->bps.own_target)
-            return fail(PDMP_ERR_INVALID, "set_flow_bps_modern: the flow has no Γ of its own, pdmp_ensemble_set_target_gaussian_csc must follow it");
+        if (!e->bps.own_target && !e->bps.logit)
+            return fail(PDMP_ERR_INVALID, "set_flow_bps_modern: the flow has no Γ of its own, pdmp_ensemble_set_target_gaussian_csc or "
+                        "pdmp_ensemble_set_target_bps_logistic must follow it");
         if (e->cfg.d > 1024)
             return fail(PDMP_ERR_UNSUPPORTED, "set_flow_bps_modern keeps d <= 1024 coordinates in registers: got d = %lld", (long long)e->cfg.d);
         if (e->bps.mom >= 1) return fail(PDMP_ERR_UNSUPPORTED, "set_flow_bps_modern: not together with set_bps_moments(order >= 1)");
@@ -184,6 +205,9 @@ pdmp_status init_state_bps(pdmp_ensemble* e, double t0, const double* x0, const 
             return fail(PDMP_ERR_UNSUPPORTED, "set_flow_bps_modern: oscn with a mass factor (set_mass_cholesky) that is not the identity (src/not_fact_samplers.jl:267)");
         if (e->bps.udiag && e->bps.has_mass) return fail(PDMP_ERR_UNSUPPORTED, "set_flow_bps_modern: u_diag together with a mass factor (set_mass_cholesky): one metric only");
         if (!(c > 0) || !std::isfinite(c)) return fail(PDMP_ERR_INVALID, "LocalBound(c) needs a finite c > 0 (the bound expires after 2√d/c/V): got %g", c);
+        if (e->bps.logit && pdmp::bps_logit_lds_bytes(e->cfg.d, e->bl_n) > pdmp::BPS_LOGIT_LDS_MAX)
+            return fail(PDMP_ERR_UNSUPPORTED, "set_target_bps_logistic keeps η and ζ of n = %lld observations in LDS beside the [d] staging buffer: "
+                        "8 d + 16 n = %zu bytes, the limit is %zu", (long long)e->bl_n, pdmp::bps_logit_lds_bytes(e->cfg.d, e->bl_n), pdmp::BPS_LOGIT_LDS_MAX);
     }
     if (!e->bps.modern && !e->bps.sticky && e->bps.flow_kind == 0 && !e->bps.gamma_is_I && !e->bps.has_mass)
         return fail(PDMP_ERR_UNSUPPORTED,
@@ -216,7 +240,12 @@ pdmp_status init_state_bps(pdmp_ensemble* e, double t0, const double* x0, const 
     if (e->bps.mom >= 2) HIP_TRY(hipMemsetAsync(e->b_j2.p, 0, (size_t)(n * d) * sizeof(double), e->stream));
     if (e->bps.modern) {
         if (e->b_mstate.n != (size_t)(n * 4)) PDMP_TRY(e->b_mstate.alloc((size_t)(n * 4)));
-        LAUNCH_TRY_CODE("bps_modern_init", pdmp::launch_bps_modern_init(B, bps_modern_params(e), n, sseed.p, t0, c, e->stream));
+        if (e->bps.logit) {
+            if (e->bl_eta.n != (size_t)(n * e->bl_n)) PDMP_TRY(e->bl_eta.alloc((size_t)(n * e->bl_n)));
+            LAUNCH_TRY_CODE("bps_logit_init", pdmp::launch_bps_logit_init(B, bps_modern_params(e), bps_logit_params(e), n, sseed.p, t0, c, e->stream));
+        } else {
+            LAUNCH_TRY_CODE("bps_modern_init", pdmp::launch_bps_modern_init(B, bps_modern_params(e), n, sseed.p, t0, c, e->stream));
+        }
     } else if (e->bps.sticky) {
         const size_t W = (size_t)pdmp::BPS_STICKY_WORDS;
         if (e->b_thf.n != (size_t)(n * d)) PDMP_TRY(e->b_thf.alloc((size_t)(n * d)));
@@ -296,6 +325,52 @@ pdmp_status pdmp_ensemble_set_flow_bps_modern(pdmp_ensemble* e, double lambda_re
     e->has_flow = true;
     e->has_target = false;
     e->has_state = false;
+    return PDMP_OK;
+}
+
+// dϕ and ∇ϕ! of a Bayesian logistic regression for the speed-recorded driver (pdmp_bps_logit.inc): takes the place of set_target_gaussian_csc.
+pdmp_status pdmp_ensemble_set_target_bps_logistic(pdmp_ensemble* e, int64_t n, const int64_t* A_colptr, const int64_t* A_rowval, const double* A_nzval,
+                                                  const int64_t* At_colptr, const int64_t* At_rowval, const double* At_nzval, const double* y,
+                                                  const double* m, double gamma0) {
+    if (!e || !A_colptr || !A_rowval || !A_nzval || !At_colptr || !At_rowval || !At_nzval || !y || !m) return fail(PDMP_ERR_INVALID, "null argument");
+    if (e->cfg.sampler != PDMP_SAMPLER_BPS) return fail(PDMP_ERR_INVALID, "set_target_bps_logistic: the ensemble was not created with PDMP_SAMPLER_BPS");
+    if (!e->has_flow) return fail(PDMP_ERR_INVALID, "set_target_bps_logistic follows pdmp_ensemble_set_flow_bps_modern");
+    if (e->has_state) return fail(PDMP_ERR_INVALID, "set_target_bps_logistic goes before set_state_bps");
+    if (n <= 0) return fail(PDMP_ERR_INVALID, "set_target_bps_logistic: n = %lld observations, need n > 0", (long long)n);
+    if (!(gamma0 >= 0) || !std::isfinite(gamma0)) return fail(PDMP_ERR_INVALID, "set_target_bps_logistic: gamma0 = %g, the prior precision is finite and >= 0", gamma0);
+    const int64_t d = e->cfg.d;
+    PDMP_TRY(check_csc("design A", A_colptr, A_rowval, n, d));
+    PDMP_TRY(check_csc("design At", At_colptr, At_rowval, d, n));
+    const int64_t nnz = A_colptr[d];
+    if (At_colptr[n] != nnz) return fail(PDMP_ERR_INVALID, "A / At are inconsistent: nnz %lld and %lld", (long long)nnz, (long long)At_colptr[n]);
+    {  // At is the transpose PATTERN of A: column by column of A, the next unread entry of At's column `row` is this coordinate
+        std::vector<int64_t> next(At_colptr, At_colptr + n);
+        for (int64_t j = 0; j < d; ++j)
+            for (int64_t p = A_colptr[j]; p < A_colptr[j + 1]; ++p) {
+                const int64_t r = A_rowval[p];
+                if (next[(size_t)r] >= At_colptr[r + 1] || At_rowval[next[(size_t)r]] != j)
+                    return fail(PDMP_ERR_INVALID, "A / At are inconsistent: At is not the transpose pattern of A at A[%lld, %lld]", (long long)r, (long long)j);
+                next[(size_t)r]++;
+            }
+    }
+    for (int64_t i = 0; i < n; ++i) {
+        if (!std::isfinite(m[i]) || !(m[i] >= 0)) return fail(PDMP_ERR_INVALID, "m[%lld] = %g: trial counts are finite and >= 0", (long long)i, m[i]);
+        if (!std::isfinite(y[i]) || !(y[i] >= 0) || !(y[i] <= m[i]))
+            return fail(PDMP_ERR_INVALID, "y[%lld] = %g: successes are finite and lie in [0, m] (m = %g)", (long long)i, y[i], m[i]);
+    }
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    PDMP_TRY(e->bl_Acp.upload(std::vector<int64_t>(A_colptr, A_colptr + d + 1)));
+    PDMP_TRY(e->bl_Arv.upload(std::vector<int64_t>(A_rowval, A_rowval + nnz)));
+    PDMP_TRY(e->bl_Anz.upload(std::vector<double>(A_nzval, A_nzval + nnz)));
+    PDMP_TRY(e->bl_Atcp.upload(std::vector<int64_t>(At_colptr, At_colptr + n + 1)));
+    PDMP_TRY(e->bl_Atrv.upload(std::vector<int64_t>(At_rowval, At_rowval + nnz)));
+    PDMP_TRY(e->bl_Atnz.upload(std::vector<double>(At_nzval, At_nzval + nnz)));
+    PDMP_TRY(e->bl_y.upload(std::vector<double>(y, y + n)));
+    PDMP_TRY(e->bl_m.upload(std::vector<double>(m, m + n)));
+    e->bl_n = n;
+    e->bl_gamma0 = gamma0;
+    e->bps.logit = true;
+    e->bps.own_target = false;  // (the later of the two target calls wins)
     return PDMP_OK;
 }
 

@@ -722,6 +722,7 @@ pdmp_status pdmp_ensemble_set_target_gaussian_csc(pdmp_ensemble* e, const int64_
         if (mu) tm.assign(mu, mu + dd);
         PDMP_TRY(e->bt_mu.upload(tm));
         e->bps.own_target = true;
+        e->bps.logit = false;  // (the later of the two target calls wins)
         e->has_state = false;
         return PDMP_OK;
     }

@@ -204,6 +204,14 @@ __device__ __forceinline__ double pos_part(double x) {
 __device__ __forceinline__ double sigmoid(double x) {
     return 1.0 / (1.0 + pdmp_exp(-x));
 }
+// The logistic link and its variance at a linear predictor η, for the non-factorised logistic target (pdmp_bps_logit.inc):
+// p = inv(1 + exp(-η)) and w = p (1 − p).  |η| past exp's range gives p = 0 or 1 exactly and w = 0, never a NaN.  Held to
+// tests/ref/bps_logistic_ref.c bit for bit through the parity tests of that kernel.
+__device__ __forceinline__ void logit_link(const double eta, double* p, double* w) {
+    const double q = 1.0 / (1.0 + pdmp_exp(-eta));
+    *p = q;
+    *w = q * (1.0 - q);
+}
 // the largest double below a finite x (x > 0, or x < 0, or x == 0 all handled by the integer image)
 __device__ __forceinline__ double pdmp_below(double x) {
     long long b = __double_as_longlong(x);

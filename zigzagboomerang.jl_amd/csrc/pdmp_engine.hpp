@@ -431,6 +431,26 @@ struct BpsModernParams {
 };
 int launch_bps_modern_init(const BpsRunParams& p, const BpsModernParams& q, int64_t nchains, const uint64_t* seeds, double t0, double c0, void* stream);
 int launch_bps_modern_run(const BpsRunParams& p, const BpsModernParams& q, int64_t nchains, void* stream);
+// the speed-recorded Bouncy Particle on a logistic-regression target (pdmp_bps_logit.inc, pdmp_ensemble_set_target_bps_logistic): the design
+// A [n x d] and its transpose in CSC, the data, and the linear predictor η = A x every chain carries from one launch to the next.
+struct BpsLogitParams {
+    const int64_t* __restrict__ A_colptr;   // [d + 1] column = coordinate
+    const int64_t* __restrict__ A_rowval;
+    const double* __restrict__ A_nzval;
+    const int64_t* __restrict__ At_colptr;  // [n + 1] column = observation
+    const int64_t* __restrict__ At_rowval;
+    const double* __restrict__ At_nzval;
+    const double* __restrict__ y;           // [n] successes
+    const double* __restrict__ m;           // [n] trials
+    double* eta;                            // [nchains x n]
+    int64_t n;
+    double gamma0;
+};
+constexpr size_t BPS_LOGIT_LDS_MAX = 160 * 1024;  // the LDS of a gfx950 compute unit: one wavefront of this kernel may take all of it
+inline size_t bps_logit_lds_bytes(int64_t d, int64_t n) { return (size_t)d * 8 + (size_t)n * 16; }
+int launch_bps_logit_init(const BpsRunParams& p, const BpsModernParams& q, const BpsLogitParams& g, int64_t nchains, const uint64_t* seeds, double t0,
+                          double c0, void* stream);
+int launch_bps_logit_run(const BpsRunParams& p, const BpsModernParams& q, const BpsLogitParams& g, int64_t nchains, void* stream);
 int launch_bps_write_probe(double* ev_x, double* ev_th, int64_t d, int64_t cap, int64_t nrec, int64_t nchains, void* stream);
 int launch_sector_probe(double* rec, int64_t d, int64_t nchains, int rounds, int write, double* sink, void* stream);
 int launch_bps_init(const BpsRunParams& p, int64_t nchains, const uint64_t* seeds, double t0, double c0, void* stream);

@@ -100,6 +100,7 @@ struct BpsOptions {
     bool udiag = false;
     int oscn = 0;
     int64_t record_limit = 0;
+    bool logit = false;       // pdmp_ensemble_set_target_bps_logistic: the speed-recorded driver's logistic-regression target (pdmp_bps_logit.inc)
 };
 
 // Members by concern.  pdmp_ensemble_destroy synchronises the device before it deletes the ensemble, so no member's release depends on another's:
@@ -262,6 +263,11 @@ struct pdmp_ensemble {
     DevBuf<double> b_kappa, b_thf, b_tfrez;  // sticky: [d]; [nchains x d] saved speeds; [nchains x d] freezing / thaw times
     DevBuf<uint64_t> b_fmask, b_ev_f;        // sticky: [nchains x 16], [nchains x cap x 16] free masks (bit e & 63 of word e >> 6)
     DevBuf<double> b_udiag, b_sudiag, b_mstate;  // speed-recorded: [d] u, [d] sqrt(u), [nchains x 4] {Δ, action, V, Δrec}
+    // speed-recorded, logistic-regression target: A and At in CSC, y, m, and the carried η = A x [nchains x n]
+    DevBuf<int64_t> bl_Acp, bl_Arv, bl_Atcp, bl_Atrv;
+    DevBuf<double> bl_Anz, bl_Atnz, bl_y, bl_m, bl_eta;
+    int64_t bl_n = 0;
+    double bl_gamma0 = 0.0;
     // the consumers of the BPS trace (pdmp_ensemble_bps_consume_*, pdmp_consume_bps.hip): the cursors x, θ, y -- and a sticky ensemble's free time --
     // [nchains x d] each, the per-(chain, strip) progress, the grid [nchains x K x d], the cummean slots [nchains x cap x d] (empty: not enabled).
     // t0 is t0_state; pdmp_debug_bps_trace_append sets trace_appended like its factorised twin
@@ -330,6 +336,7 @@ pdmp::BpsRunParams bps_run_params(const pdmp_ensemble* e, double T, int flags);
 pdmp::BpsMomParams bps_moments_params(const pdmp_ensemble* e);
 pdmp::BpsStickyParams bps_sticky_params(const pdmp_ensemble* e);
 pdmp::BpsModernParams bps_modern_params(const pdmp_ensemble* e);
+pdmp::BpsLogitParams bps_logit_params(const pdmp_ensemble* e);
 pdmp_status bps_moments_at(pdmp_ensemble* e, double T, int64_t chain_first, int64_t n, bool two);
 // pdmp_capi_tune.hip: set_state with the placement probes
 pdmp_status init_state_tuned(pdmp_ensemble* e, double t0, const double* x0, const double* th0, const double* c, const uint64_t* seeds, uint64_t seed0);

@@ -218,6 +218,31 @@ class LogisticTarget:
 
 
 @dataclass
+class LogisticRegressionTarget:
+    """dϕ and ∇ϕ! of a Bayesian logistic regression for the speed-recorded Bouncy Particle (turing/lr.jl:105-139, tilde/lr.jl:55-98):
+    ϕ(x) = Σ_i [m_i log(1 + e^{η_i}) − y_i η_i] + (γ0/2)‖x‖² with η = A x.  A: n x d design (explicit zeros are kept), y: [n] successes,
+    m: [n] trials (None: ones), γ0 >= 0 a scalar prior precision.  The device-resident stand-in for the closures `dϕ`, `∇ϕ!` of
+    pdmp(dϕ, ∇ϕ!, t0, x0, θ0, T, c::LocalBound, flow::BouncyParticle) (pdmp_ensemble_set_target_bps_logistic)."""
+    A: sp.csc_matrix
+    y: np.ndarray
+    m: Optional[np.ndarray] = None
+    γ0: float = 0.0
+
+    def __post_init__(self):
+        A = sp.csc_matrix(self.A, dtype=np.float64)
+        A.sort_indices()
+        self.A = A
+        At = sp.csc_matrix(sp.csr_matrix((A.data, A.indices, A.indptr), shape=(A.shape[1], A.shape[0])))  # (no entry dropped or merged)
+        At.sort_indices()
+        self.At = At
+        self.y = np.ascontiguousarray(self.y, dtype=np.float64)
+        self.m = np.ones_like(self.y) if self.m is None else np.ascontiguousarray(self.m, dtype=np.float64)
+        if self.y.shape != (A.shape[0],) or self.m.shape != self.y.shape:
+            raise ValueError("y and m have one entry per row of A")
+        self.γ0 = float(self.γ0)
+
+
+@dataclass
 class FactTrace:
     """FactTrace(F, t0, x0, θ0, events) -- src/trace.jl:7-13; events are (t, i, x_i, θ_i), i 0-based."""
     F: object

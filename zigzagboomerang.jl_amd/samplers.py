@@ -15,8 +15,8 @@ import scipy.sparse as sp
 
 from . import _lib
 from .engine import Ensemble
-from .flows import (Boomerang, Boomerang1d, BouncyParticle, FactBoomerang, LocalBound, FactTrace, GaussianTarget, GaussianTarget1d, LogisticTarget,
-                    PDMPTrace, StickyBarriers, ZigZag, ZigZag1d)
+from .flows import (Boomerang, Boomerang1d, BouncyParticle, FactBoomerang, LocalBound, FactTrace, GaussianTarget, GaussianTarget1d, LogisticRegressionTarget,
+                    LogisticTarget, PDMPTrace, StickyBarriers, ZigZag, ZigZag1d)
 
 DEFAULT_SEED = 0x5EED0000
 
@@ -165,13 +165,14 @@ def _pdmp_nd(target, t0, x0, θ0, T, c, F, *, factor=1.8, adapt=False, subsample
     consumed, but never copied to the host; trace_capacity=0 raises.
 
     pdmp(dϕ, ∇ϕ!, t0, x0, θ0, T, c::LocalBound, B::BouncyParticle; oscn=false, adapt=false, factor=2.0) (src/not_fact_samplers.jl:336-384),
-    the speed-recorded driver: B.Γ is None (BouncyParticle(None, None, λref, ρ, L=..., U=...)), target is a GaussianTarget (dϕ and ∇ϕ! are
-    its two directional derivatives and its gradient), c a LocalBound.  An integer T is a number of samples, a float an end time.  The
-    trace holds one record per 1/λref of speed-time and does not begin with (t0, x0, θ0); subsample defaults to True here and
+    the speed-recorded driver: B.Γ is None (BouncyParticle(None, None, λref, ρ, L=..., U=...)), target is a GaussianTarget or a
+    LogisticRegressionTarget (dϕ and ∇ϕ! are its two directional derivatives and its gradient), c a LocalBound.  An integer T is a number of
+    samples, a float an end time.  The trace holds one record per 1/λref of speed-time and does not begin with (t0, x0, θ0); subsample defaults to True here and
     subsample=False raises the reference's ArgumentError (:338)."""
     if isinstance(F, BouncyParticle) and F.Γ is None:
-        if not isinstance(target, GaussianTarget):
-            raise TypeError("BouncyParticle(missing, missing, ...): target must be a GaussianTarget (dϕ, ∇ϕ! of Γt(x − μt))")
+        if not isinstance(target, (GaussianTarget, LogisticRegressionTarget)):
+            raise TypeError("BouncyParticle(missing, missing, ...): target must be a GaussianTarget (dϕ, ∇ϕ! of Γt(x − μt)) or a "
+                            "LogisticRegressionTarget")
         if not isinstance(c, LocalBound):
             raise TypeError("pdmp(dϕ, ∇ϕ!, ..., c::LocalBound, flow::BouncyParticle): pass c as LocalBound(c)")
         if subsample is not None and not subsample:
