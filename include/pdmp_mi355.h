@@ -169,6 +169,25 @@ pdmp_status pdmp_ensemble_set_target_logistic(pdmp_ensemble* ens, int64_t n, con
                                               const double* ny, const double* mu, double gamma0, int64_t k_sub);
 
 /*
+ * Target of the reference's diffusion-bridge example (research/diffusion_bridge/diffbridge.jl, faberschauder.jl): the bridge of
+ *   dX = b(X) ds + dW on [0, T],  b(x) = −beta x + alpha sin(omega x),
+ * expanded in the Faber-Schauder basis up to level L: d = (2 << L) + 1 coefficients ξ, ξ[0] = u/√T and ξ[d−1] = v/√T being the fixed end
+ * points.  The gradient is ∇ϕmoving (faberschauder.jl:137-144), evaluated with SelfMoving() / ExtendedForm (src/sfact.jl:57-68): it draws a time
+ * s in the support of basis function i -- draw ndraw_global of PDMP_STREAM_GLOBAL, taken before the thinning coin --, moves the L + 1
+ * coefficients whose basis functions cover s to the proposal time, and returns an unbiased estimate of ∂ϕ/∂ξ_i.  b′ and b″ are the true
+ * derivatives of b (the script's carry a stray factor 2).  Runs on zz_bridge_run_kernel, bit for bit tests/ref/bridge_ref.c.
+ * Valid on PDMP_SAMPLER_ZIGZAG_LOCAL after set_flow_zigzag, in place of another target (the later target call wins).
+ * PDMP_ERR_INVALID: d != (2 << L) + 1, L < 0, T <= 0, a parameter that is not finite, another sampler, a state that already exists.
+ * PDMP_ERR_UNSUPPORTED: L > 10 (d > 2049).  pdmp_ensemble_set_state then answers PDMP_ERR_UNSUPPORTED, naming the cause, to a flow Γ that is
+ * not the identity, μ != 0, a refresh clock, a FactBoomerang, pdmp_ensemble_set_neighbourhood, gradient tracking, LocalBound, adaptscale, a
+ * synthetic state, and θ0 != 0 at either end point of any chain (free end points are not implemented; give the end points c = 0 as the script does).
+ * A chain whose |omega X_s| exceeds 2^30, or whose sampled s rounds up to T, ends as PDMP_CHAIN_STALLED.  The trace consumers
+ * (pdmp_ensemble_consume_*) serve these traces; pdmp_ensemble_batch_means, _ess_* and _path_integrals answer PDMP_ERR_UNSUPPORTED (this loop
+ * keeps no ∫ξ dt).  (Added under ABI version 3: nothing that existed changed, a binding that wants it looks the symbol up.)
+ */
+pdmp_status pdmp_ensemble_set_target_diffusion_bridge(pdmp_ensemble* ens, int32_t L, double T, double alpha, double beta, double omega);
+
+/*
  * Initial state (src/sfact.jl:164-190): x0, theta0 are [nchains x d] row-major; c is [d] (copied; with
  * adapt each chain gets its own copy, returned by final_state -- no hidden mutation of caller memory,
  * unlike src/fact_samplers.jl:68); seeds is [nchains].  Computes b[i] = ab(...) and the initial queue

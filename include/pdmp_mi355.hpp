@@ -12,13 +12,14 @@
 //                                                   -> Ξ, t′, (t, x, θ), (acc, num)                 (src/stickyzz.jl:176-218)
 // Same names, argument order, keyword meaning (struct Options), return shape (struct Result) and error behaviour (the
 // reference's `error("Tuning parameter `c` too small.")`, src/sfact.jl:124, becomes std::runtime_error with that text).
-// Differences forced by the C ABI: `∇ϕ, args...` is an enumerated target (GaussianTarget, LogisticTarget); coordinates are
+// Differences forced by the C ABI: `∇ϕ, args...` is an enumerated target (GaussianTarget, LogisticTarget, DiffusionBridge); coordinates are
 // 0-based; one call runs ONE chain (pass nchains > 1 through pdmp::Ensemble directly for ensembles).
 // Header-only; link with -lpdmp_mi355.  There is no CPU fallback: without a gfx950 device every call throws.
 #ifndef PDMP_MI355_HPP
 #define PDMP_MI355_HPP
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <limits>
 #include <stdexcept>
@@ -100,6 +101,25 @@ struct LogisticRegression {
     SparseCSC A, At;
     std::vector<double> y, m;
     double gamma0 = 0.0;
+};
+// ∇ϕmoving(t, ξ, θ, i, t′, F, L, T), SelfMoving() (research/diffusion_bridge/faberschauder.jl:128-145, diffbridge.jl:32-33): the bridge of
+// dX = b(X) ds + dW on [0, T], b(x) = −βx + α sin(ωx), in the Faber-Schauder basis up to level L: d = (2 << L) + 1 coefficients, the first and
+// the last being the fixed end points u/√T and v/√T (θ0 = 0 and c = 0 there).  The flow is ZigZag(I, 0); pdmp_ensemble_set_target_diffusion_bridge
+struct DiffusionBridge {
+    int32_t L = 7;
+    double T = 2.0, alpha = 1.5, beta = 0.1, omega = 6.283185307179586;
+    int64_t d() const { return ((int64_t)2 << L) + 1; }
+    // dotψ(ξ, s, L, T), faberschauder.jl:16-24: the bridge at time 0 <= s < T of the coefficients ξ
+    double path(const std::vector<double>& xi, double s) const {
+        const double sT = std::sqrt(T);
+        double r = s / sT * xi.back() + sT * (1 - s / T) * xi.front();
+        for (int lev = 0; lev <= L; ++lev) {
+            const double p2 = (double)((int64_t)1 << (L - lev));
+            const int64_t j = (int64_t)std::floor(s / T * p2) * ((int64_t)2 << lev) + ((int64_t)1 << lev);
+            r += xi[(size_t)j] * ((sT * 0.5 - std::fabs(std::fmod(s * p2, T) / sT - sT * 0.5)) / std::sqrt(p2));
+        }
+        return r;
+    }
 };
 
 struct Options {  // the reference's keyword arguments
@@ -238,6 +258,9 @@ inline void set_target(Ensemble& e, const LogisticRegression& g) {
     check(pdmp_ensemble_set_target_bps_logistic(e.get(), g.n, g.A.colptr.data(), g.A.rowval.data(), g.A.nzval.data(), g.At.colptr.data(),
                                                 g.At.rowval.data(), g.At.nzval.data(), g.y.data(), g.m.empty() ? ones.data() : g.m.data(),
                                                 g.gamma0));
+}
+inline void set_target(Ensemble& e, const DiffusionBridge& g) {
+    check(pdmp_ensemble_set_target_diffusion_bridge(e.get(), g.L, g.T, g.alpha, g.beta, g.omega));
 }
 inline void set_flow(Ensemble& e, const ZigZag& F) {
     check(pdmp_ensemble_set_flow_zigzag(e.get(), F.Gamma.colptr.data(), F.Gamma.rowval.data(), F.Gamma.nzval.data(), opt(F.mu),

@@ -8,5 +8,5 @@ through `__graft_entry__.load_package()` under the module name `zigzagboomerang_
 from . import _lib, benchlib, build, ess, parallel, problems, trace  # noqa: F401
 from .engine import Ensemble  # noqa: F401
 from .samplers import Partition, parallel_spdmp, pdmp, spdmp, sspdmp, sspdmp2, stickyzz  # noqa: F401
-from .flows import (Boomerang, Boomerang1d, BouncyParticle, LocalBound, FactBoomerang, FactTrace, GaussianTarget, GaussianTarget1d,  # noqa: F401
-                    LogisticRegressionTarget, LogisticTarget, PDMPTrace, StickyBarriers, ZigZag, ZigZag1d)
+from .flows import (Boomerang, Boomerang1d, BouncyParticle, DiffusionBridgeTarget, ExtendedForm, LocalBound, FactBoomerang, FactTrace, GaussianTarget,  # noqa: F401
+                    GaussianTarget1d, LogisticRegressionTarget, LogisticTarget, PDMPTrace, SelfMoving, StickyBarriers, ZigZag, ZigZag1d)

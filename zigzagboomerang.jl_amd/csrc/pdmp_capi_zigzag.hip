@@ -431,6 +431,29 @@ pdmp_status init_state(pdmp_ensemble* e, double t0, const double* x0, const doub
                 return fail(PDMP_ERR_INVALID, "stickyzz: x0[%lld] = %g of chain %lld lies outside its barriers [%g, %g]", (long long)(q % d), x0[q], (long long)(q / d), be.lo, be.hi);
         }
     }
+    if (e->target_kind == TARGET_BRIDGE) {
+        // the diffusion bridge runs on zz_bridge_run_kernel alone (pdmp_bridge.inc): the script's configuration (research/diffusion_bridge/diffbridge.jl:
+        // ZigZag(sparse(I), 0), fixed end points), everything else is refused here, never served by another kernel
+        if (e->cfg.sampler != PDMP_SAMPLER_ZIGZAG_LOCAL) return fail(PDMP_ERR_UNSUPPORTED, "diffusion bridge: spdmp only (PDMP_SAMPLER_ZIGZAG_LOCAL)");
+        if (e->flow_kind != 0) return fail(PDMP_ERR_UNSUPPORTED, "diffusion bridge: a ZigZag flow, not a FactBoomerang");
+        if (e->has_g1mask) return fail(PDMP_ERR_UNSUPPORTED, "diffusion bridge: no pdmp_ensemble_set_neighbourhood (the gradient moves what it reads; G = G1 = {i})");
+        if (e->adaptscale) return fail(PDMP_ERR_UNSUPPORTED, "diffusion bridge: no adaptscale");  // (it comes with a refresh clock: named first)
+        if (e->lambda_ref > 0) return fail(PDMP_ERR_UNSUPPORTED, "diffusion bridge: no refresh clock (lambda_ref = %g)", e->lambda_ref);
+        bool ident = e->nnz == d;
+        for (int64_t i = 0; ident && i < d; ++i) ident = e->rowval[(size_t)i] == (uint32_t)i && e->bval[(size_t)i] == 1.0;
+        if (!ident) return fail(PDMP_ERR_UNSUPPORTED, "diffusion bridge: the flow's Γ must be the identity (ZigZag(sparse(I), 0))");
+        for (int64_t i = 0; i < d; ++i)
+            if (e->mu[(size_t)i] != 0.0) return fail(PDMP_ERR_UNSUPPORTED, "diffusion bridge: the flow's μ must be 0 (μ[%lld] = %g)", (long long)i, e->mu[(size_t)i]);
+        if (e->track_requested) return fail(PDMP_ERR_UNSUPPORTED, "diffusion bridge: no gradient tracking (the gradient is a fresh Monte Carlo estimate at every proposal)");
+        if (e->local_bound) return fail(PDMP_ERR_UNSUPPORTED, "diffusion bridge: no LocalBound (pdmp_ensemble_set_local_bound)");
+        if (!x0 || !th0) return fail(PDMP_ERR_UNSUPPORTED, "diffusion bridge: an explicit state (the end points ξ[0], ξ[d-1] are data)");
+        // the reference's end-point gradients (faberschauder.jl:129-136) read coefficients they did not move: fixed end points are what is served
+        for (int64_t k = 0; k < n; ++k)
+            for (int64_t i : {(int64_t)0, d - 1})
+                if (th0[k * d + i] != 0.0)
+                    return fail(PDMP_ERR_UNSUPPORTED, "diffusion bridge: θ0[%lld] = %g of chain %lld: the end points are fixed (θ0 = 0 at both; free end points are not implemented)",
+                                (long long)i, th0[k * d + i], (long long)k);
+    }
     e->track = false;
     e->track_lg = false;
     if (e->track_requested && e->target_kind == 1) {
@@ -527,6 +550,8 @@ pdmp_status init_state(pdmp_ensemble* e, double t0, const double* x0, const doub
             PDMP_TRY(e->d_sig_chain.upload(sg));
         }
         e->use_spec = false;
+    } else if (e->target_kind == TARGET_BRIDGE) {
+        e->use_spec = false;  // (no neighbourhood program: zz_bridge_run_kernel computes what it reads from i and its draw)
     } else {
         PDMP_TRY(build_blob(e, c));
     }
@@ -854,6 +879,38 @@ pdmp_status pdmp_ensemble_set_target_logistic(pdmp_ensemble* e, int64_t n, const
     e->target_kind = 1;
     e->has_target = true;
     e->has_state = false;
+    return PDMP_OK;
+}
+
+pdmp_status pdmp_ensemble_set_target_diffusion_bridge(pdmp_ensemble* e, int32_t L, double T, double alpha, double beta, double omega) {
+    if (!e) return fail(PDMP_ERR_INVALID, "null argument");
+    if (e->cfg.sampler != PDMP_SAMPLER_ZIGZAG_LOCAL)
+        return fail(PDMP_ERR_INVALID, "%s: the diffusion-bridge target belongs to spdmp (PDMP_SAMPLER_ZIGZAG_LOCAL)", __func__);
+    if (!e->has_flow) return fail(PDMP_ERR_INVALID, "set_flow_zigzag must be called first");
+    if (e->has_state) return fail(PDMP_ERR_INVALID, "a state exists already: the target is set before pdmp_ensemble_set_state (set the flow again to start over)");
+    if (L < 0) return fail(PDMP_ERR_INVALID, "diffusion bridge: L = %d < 0", (int)L);
+    if (!(T > 0) || !std::isfinite(T)) return fail(PDMP_ERR_INVALID, "diffusion bridge: T = %g must be positive and finite", T);
+    if (!std::isfinite(alpha) || !std::isfinite(beta) || !std::isfinite(omega))
+        return fail(PDMP_ERR_INVALID, "diffusion bridge: alpha = %g, beta = %g, omega = %g must be finite", alpha, beta, omega);
+    if (L > 40 || e->cfg.d != ((int64_t)2 << L) + 1)
+        return fail(PDMP_ERR_INVALID, "diffusion bridge: d = %lld is not (2 << L) + 1 for L = %d", (long long)e->cfg.d, (int)L);
+    if (L > pdmp::PDMP_BRIDGE_LMAX)
+        return fail(PDMP_ERR_UNSUPPORTED, "diffusion bridge: L = %d > %d (one level per lane and one block of 64 keys per lane: d <= 2049)", (int)L,
+                    pdmp::PDMP_BRIDGE_LMAX);
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    // the kernels' table struct wants tval / gmu_t allocated even if unused
+    e->h_tval.assign((size_t)e->nnz, 0.0);
+    PDMP_TRY(e->d_tval.upload(e->h_tval));
+    PDMP_TRY(e->d_gmu_t.upload(std::vector<double>((size_t)e->cfg.d, 0.0)));
+    e->has_tmu = false;
+    e->bridge.L = L;
+    e->bridge.pad_ = 0;
+    e->bridge.T = T;
+    e->bridge.alpha = alpha;
+    e->bridge.beta = beta;
+    e->bridge.omega = omega;
+    e->target_kind = TARGET_BRIDGE;  // (the later of two target calls wins: the Gaussian and the logistic setters put their own kind back)
+    e->has_target = true;
     return PDMP_OK;
 }
 

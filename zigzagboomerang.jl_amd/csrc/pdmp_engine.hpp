@@ -327,6 +327,15 @@ struct ZzGeneralParams {
 };
 int launch_zz_general_run(const ZzRunParams& p, const ZzGeneralParams& q, int64_t nchains, void* stream);
 
+// The diffusion bridge in the Faber-Schauder basis (pdmp_bridge.inc, pdmp_ensemble_set_target_diffusion_bridge): d = (2 << L) + 1 coefficients,
+// drift b(x) = −βx + α sin(ωx) on [0, T].  One level per lane and one block minimum per lane: L <= PDMP_BRIDGE_LMAX (d = 2049, 33 key blocks).
+constexpr int PDMP_BRIDGE_LMAX = 10;
+struct ZzBridgeParams {
+    int32_t L, pad_;
+    double T, alpha, beta, omega;
+};
+int launch_zz_bridge_run(const ZzRunParams& p, const ZzBridgeParams& b, int64_t nchains, void* stream);
+
 // Small-d subsampled logistic ZigZag with the chain state resident in LDS (pdmp_logistic.hip): packed read-only tables
 struct LgCoord {  // everything a proposal needs that depends on the coordinate alone
     uint32_t cp0, k;    // column of the bounding Γ: G1[i] = rowval[cp0 .. cp0 + k)

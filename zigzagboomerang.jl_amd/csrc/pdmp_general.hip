@@ -943,6 +943,8 @@ int launch_zz_general_run(const ZzRunParams& p, const ZzGeneralParams& q_in, int
     return (int)hipGetLastError();
 }
 
+#include "pdmp_bridge.inc"  // the diffusion bridge's self-moving Faber-Schauder gradient (research/diffusion_bridge): a kernel of its own, nothing above changes
+
 #ifdef PDMP_EXTRA_KERNELS
 // pdmp_debug_math_eval: the shared scalars (pdmp_device.hpp) this unit calls, as compiled here
 namespace {

@@ -8,7 +8,7 @@ import os
 import numpy as np
 
 from . import _lib
-from .flows import BouncyParticle, FactBoomerang, GaussianTarget, LogisticRegressionTarget, LogisticTarget, ZigZag
+from .flows import BouncyParticle, DiffusionBridgeTarget, FactBoomerang, GaussianTarget, LogisticRegressionTarget, LogisticTarget, ZigZag
 
 
 def _i64(a):
@@ -335,6 +335,10 @@ class Ensemble:
         return dict(t=t, x=x, theta=th, c=c)
 
     def set_target(self, target):
+        if isinstance(target, DiffusionBridgeTarget):
+            _lib.check(self._L.pdmp_ensemble_set_target_diffusion_bridge(self._h, int(target.L), float(target.T), float(target.α), float(target.β),
+                                                                         float(target.ω)))
+            return
         if isinstance(target, LogisticTarget):
             A, At = target.A, target.At
             if A.shape[1] != self.d:

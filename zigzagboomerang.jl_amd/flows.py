@@ -218,6 +218,45 @@ class LogisticTarget:
 
 
 @dataclass
+class DiffusionBridgeTarget:
+    """∇ϕmoving(t, ξ, θ, i, t′, F, L, T) of research/diffusion_bridge/faberschauder.jl:128-145 with its `args = (SelfMoving(), L, T)`: the
+    bridge of dX = b(X) ds + dW on [0, T], b(x) = −βx + α sin(ωx), in the Faber-Schauder basis up to level L -- d = (2 << L) + 1
+    coefficients, the first and last being the fixed end points u/√T, v/√T (problems.diffusion_bridge_problem builds ξ0, θ0, c).  b′, b″
+    are the true derivatives (the script's carry a stray factor 2).  pdmp_ensemble_set_target_diffusion_bridge."""
+    L: int
+    T: float
+    α: float = 1.5
+    β: float = 0.1
+    ω: float = 2 * np.pi
+
+    def __post_init__(self):
+        self.L = int(self.L)
+        self.T, self.α, self.β, self.ω = float(self.T), float(self.α), float(self.β), float(self.ω)
+
+    @property
+    def d(self):
+        return (2 << self.L) + 1
+
+
+class ExtendedForm:
+    """ExtendedForm() / SelfMoving() (src/types.jl:103-119, src/sfact.jl:57-68): as the first of spdmp's `args...` it says that ∇ϕ takes
+    (t, x, θ, i, t′, F, args...) and moves the coordinates it reads itself.  The device targets that work this way (LogisticTarget,
+    DiffusionBridgeTarget) carry the fact in their type: the marker is accepted, and required by nothing."""
+
+    def __eq__(self, other):
+        return isinstance(other, ExtendedForm)
+
+    def __hash__(self):
+        return hash(ExtendedForm)
+
+    def __repr__(self):
+        return "ExtendedForm()"
+
+
+SelfMoving = ExtendedForm  # const SelfMoving = ExtendedForm, src/sfact.jl:64
+
+
+@dataclass
 class LogisticRegressionTarget:
     """dϕ and ∇ϕ! of a Bayesian logistic regression for the speed-recorded Bouncy Particle (turing/lr.jl:105-139, tilde/lr.jl:55-98):
     ϕ(x) = Σ_i [m_i log(1 + e^{η_i}) − y_i η_i] + (γ0/2)‖x‖² with η = A x.  A: n x d design (explicit zeros are kept), y: [n] successes,

@@ -254,3 +254,23 @@ def spike_slab_logistic_problem(p=10_000, num_rows=2000, gamma0=0.25, w=0.5, see
     kappa = np.full(p, (gamma0 / np.sqrt(2 * np.pi)) / (1 / w - 1))
     return dict(A=A, At=At, y=y, ny=ny, mu=mu, gamma0=gamma0, kappa=kappa, G=sp.identity(p, format="csc"), sigma=np.ones(p),
                 c=np.ones(p), xtrue=xtrue, n=n, p=p, w=w)
+
+
+def diffusion_bridge_problem(L, T, u, v, nchains=None, rng=None):
+    """ξ0, θ0, c of research/diffusion_bridge/diffbridge.jl:17-26 for the bridge from u at time 0 to v at time T, truncated at level L:
+    d = (2 << L) + 1 coefficients, ξ0 = 0 but for the end points ξ0[0] = u/√T, ξ0[d−1] = v/√T; θ0 uniform on {−1, +1} with θ0 = 0 at the
+    end points (they are fixed); c = 1 with c = 0 at the end points (their bound is then (0, 0) and they never pop).  nchains: None for
+    one chain ([d] arrays), else [nchains x d] with independent θ0 rows; rng: a numpy Generator (default_rng(0) when None)."""
+    d = (2 << int(L)) + 1
+    rng = np.random.default_rng(0) if rng is None else rng
+    n = 1 if nchains is None else int(nchains)
+    xi0 = np.zeros((n, d))
+    xi0[:, 0] = u / np.sqrt(T)
+    xi0[:, -1] = v / np.sqrt(T)
+    th0 = rng.choice([-1.0, 1.0], size=(n, d))
+    th0[:, 0] = th0[:, -1] = 0.0
+    c = np.ones(d)
+    c[0] = c[-1] = 0.0
+    if nchains is None:
+        return xi0[0], th0[0], c
+    return xi0, th0, c

@@ -15,8 +15,8 @@ import scipy.sparse as sp
 
 from . import _lib
 from .engine import Ensemble
-from .flows import (Boomerang, Boomerang1d, BouncyParticle, FactBoomerang, LocalBound, FactTrace, GaussianTarget, GaussianTarget1d, LogisticRegressionTarget,
-                    LogisticTarget, PDMPTrace, StickyBarriers, ZigZag, ZigZag1d)
+from .flows import (Boomerang, Boomerang1d, BouncyParticle, DiffusionBridgeTarget, ExtendedForm, FactBoomerang, LocalBound, FactTrace, GaussianTarget,
+                    GaussianTarget1d, LogisticRegressionTarget, LogisticTarget, PDMPTrace, StickyBarriers, ZigZag, ZigZag1d)
 
 DEFAULT_SEED = 0x5EED0000
 
@@ -58,17 +58,27 @@ def _consume_result(ens, consume, single, sticky):
 
 def _split_G(GF, G):
     """spdmp(∇ϕ, t0, x0, θ0, T, c, F) or spdmp(∇ϕ, t0, x0, θ0, T, c, G, F) as in the reference (src/sfact.jl:162,214); G may also be a keyword."""
+    if GF and isinstance(GF[-1], ExtendedForm):  # SelfMoving() as args[1] (src/sfact.jl:57-68): the device targets that need it carry it in their type
+        GF = GF[:-1]
     if len(GF) == 1:
         return G, GF[0]
     if len(GF) == 2 and G is None:
         return GF[0], GF[1]
-    raise TypeError("expected spdmp(target, t0, x0, θ0, T, c, [G,] F, ...)")
+    raise TypeError("expected spdmp(target, t0, x0, θ0, T, c, [G,] F[, SelfMoving()], ...)")
 
 
 def spdmp(target, t0, x0, θ0, T, c, *GF, factor=1.8, adapt=False, adaptscale=False, seed=DEFAULT_SEED, device=0,
-          trace_capacity=None, trace=True, tracked=False, G=None):
+          trace_capacity=None, trace=True, tracked=False, G=None, consume=None):
     """Local ZigZag: spdmp(∇ϕ, t0, x0, θ0, T, c, [G,] F::ZigZag, args...) (src/sfact.jl:162,214); without G: G = Matched().
     Returns Ξ, (t, x, θ), (acc, num), c like the reference (:211).
+
+    A trailing SelfMoving() / ExtendedForm() is accepted as in spdmp(∇ϕmoving, ..., F, SelfMoving(), args...) (:68).  With a
+    DiffusionBridgeTarget this is research/diffusion_bridge/diffbridge.jl:32-33: spdmp(target, 0.0, ξ0, θ0, T′, c, ZigZag(I, 0), SelfMoving(),
+    adapt=True) with ξ0, θ0, c of problems.diffusion_bridge_problem.
+
+    consume=dict(dt=..., points=...) (DiffusionBridgeTarget; engine-only keyword): the device consumers (pdmp_ensemble_consume_*) run over
+    every slice before its buffer is recycled and a fifth element is returned: dict(mean, T, grid_t, grid_x) -- trace.mean(Ξ), the last
+    event time and trace.discretize(Ξ, dt) on at most `points` rows (grid_t / grid_x None without points), per chain as in pdmp.
 
     G: the neighbourhoods a proposal moves before its gradient is taken (:82,171-179) -- a sparse matrix whose column patterns are the
     G[i] (e.g. the target's Γ when the bounding F.Γ is sparser) or a sequence of index arrays; G[i] ⊇ G1[i] = pattern of F.Γ[:, i] is
@@ -87,7 +97,7 @@ def spdmp(target, t0, x0, θ0, T, c, *GF, factor=1.8, adapt=False, adaptscale=Fa
     kernel serves the graph / options."""
     G, F = _split_G(GF, G)
     return _zigzag(_lib.SAMPLER_ZIGZAG_LOCAL, target, t0, x0, θ0, T, c, F, factor, adapt, seed, device, trace_capacity, trace,
-                   adaptscale=adaptscale, tracked=tracked, G=G)
+                   adaptscale=adaptscale, tracked=tracked, G=G, consume=consume)
 
 
 def pdmp(target, *args, factor=1.8, adapt=False, subsample=None, seed=DEFAULT_SEED, device=0, trace_capacity=None, trace=True,
@@ -378,11 +388,13 @@ def _pattern_of(G, d):
 
 
 def _zigzag(sampler, target, t0, x0, θ0, T, c, F, factor, adapt, seed, device, trace_capacity, trace, sticky=None,
-            adaptscale=False, tracked=False, G=None, barriers=None, details=False):
+            adaptscale=False, tracked=False, G=None, barriers=None, details=False, consume=None):
     if not isinstance(F, (ZigZag, FactBoomerang)):
         raise TypeError("the device path supports F::ZigZag and F::FactBoomerang")
-    if not isinstance(target, (GaussianTarget, LogisticTarget)):
-        raise TypeError("target must be one of the device-resident families (GaussianTarget, LogisticTarget)")
+    if not isinstance(target, (GaussianTarget, LogisticTarget, DiffusionBridgeTarget)):
+        raise TypeError("target must be one of the device-resident families (GaussianTarget, LogisticTarget, DiffusionBridgeTarget)")
+    if consume is not None and not isinstance(target, DiffusionBridgeTarget):
+        raise TypeError("consume is a keyword of spdmp with a DiffusionBridgeTarget (elsewhere the ZigZag's device consumers are Ensemble.consume_*)")
     x0 = np.asarray(x0, dtype=np.float64)
     θ0 = np.asarray(θ0, dtype=np.float64)
     single = x0.ndim == 1
@@ -395,7 +407,7 @@ def _zigzag(sampler, target, t0, x0, θ0, T, c, F, factor, adapt, seed, device, 
     if trace_capacity is None:
         # ~0.8 reflections per coordinate per unit time on the GMRF; generous first guess, refilled on demand
         trace_capacity = int(min(max(1024, 2.0 * d * max(T - t0, 1.0)), 1 << 22))
-    cap = trace_capacity if trace else 0
+    cap = _consume_capacity(consume, trace, trace_capacity)
     ens = Ensemble(nch, d, sampler=sampler, adapt=adapt, factor=factor, device=device,
                    trace_capacity=cap)
     try:
@@ -419,16 +431,31 @@ def _zigzag(sampler, target, t0, x0, θ0, T, c, F, factor, adapt, seed, device, 
         if tracked:
             ens.set_gradient_tracking(True)
         ens.set_state(t0, X0, TH0, c, seeds)
+        if consume is not None:
+            ens.consume_begin(float(consume.get("dt", 0.0)), int(consume.get("points", 0)))
         events = [[] for _ in range(nch)]
         while True:
             ens.run(T, _lib.RUN_REFERENCE_TAIL)
             cnt = ens.counters()
             if np.any(cnt["status"] == _lib.CHAIN_BOUND_VIOLATED):
                 raise RuntimeError("Tuning parameter `c` too small.")  # src/sfact.jl:124
+            if consume is not None:
+                ens.consume()
             if trace:
                 _drain(ens, events)
+            elif consume is not None:
+                ens.trace_reset()
             if not _lib.needs_rerun(cnt["status"]):  # (both resume with the next run)
                 break
+        consumed = None
+        if consume is not None:
+            mean, Tl = ens.consume_mean()
+            consumed = dict(mean=mean, T=Tl, grid_t=None, grid_x=None)
+            if int(consume.get("points", 0)) > 0:
+                grids = [ens.consume_discretized(k) for k in range(nch)]
+                consumed["grid_t"], consumed["grid_x"] = [g[0] for g in grids], [g[1] for g in grids]
+            if single:
+                consumed = {k: (v if v is None else v[0]) for k, v in consumed.items()}
         fs = ens.final_state()
         cnt = ens.counters()
         sig = ens.final_sigma() if adaptscale else None
@@ -457,9 +484,10 @@ def _zigzag(sampler, target, t0, x0, θ0, T, c, F, factor, adapt, seed, device, 
             out = traces[0], float(tp[0]), (fs["t"][0], fs["x"][0], fs["theta"][0]), (int(acc[0]), int(num[0]))
             return out + (({k: v[0] for k, v in extra.items()},) if details else ())
         return (traces, tp, (fs["t"], fs["x"], fs["theta"]), (acc, num)) + ((extra,) if details else ())
+    tail = () if consumed is None else (consumed,)
     if single:
-        return traces[0], (fs["t"][0], fs["x"][0], fs["theta"][0]), (acc[0], int(num[0])), c_out[0]
-    return traces, (fs["t"], fs["x"], fs["theta"]), (acc, num), c_out
+        return (traces[0], (fs["t"][0], fs["x"][0], fs["theta"][0]), (acc[0], int(num[0])), c_out[0]) + tail
+    return (traces, (fs["t"], fs["x"], fs["theta"]), (acc, num), c_out) + tail
 
 
 def _bps_modern(target, t0, x0, θ0, T, c, B, factor, adapt, seed, device, trace_capacity, trace, oscn, consume=None):

@@ -321,3 +321,28 @@ def inclusion_prob(tr: FactTrace):
     i, dt, _, xp = _segment_integrals(tr)
     T = ev["t"][-1]
     return np.bincount(i, weights=((xp != 0) | (ev["x"] != 0)) * dt / T, minlength=tr.x0.size)
+
+
+def faber_schauder_path(ξ, s, L, T):
+    """dotψ(ξ, s, L, T) of research/diffusion_bridge/faberschauder.jl:16-24, vectorised: the bridge X_s of the Faber-Schauder coefficients ξ
+    ([d] or [n x d], d = (2 << L) + 1, e.g. the rows of discretize(Ξ, dt)) at the times s (scalar or [m], 0 <= s < T).  Returns [m], or
+    [n x m] for a stack of coefficient vectors."""
+    ξ = np.asarray(ξ, dtype=np.float64)
+    s = np.asarray(s, dtype=np.float64)
+    L = int(L)
+    if ξ.shape[-1] != (2 << L) + 1:
+        raise ValueError("ξ has %d coefficients, level L = %d has %d" % (ξ.shape[-1], L, (2 << L) + 1))
+    sv = np.atleast_1d(s)
+    if np.any(sv < 0) or np.any(sv >= T):
+        raise ValueError("out of bounds")  # faberschauder.jl:17
+    X = np.atleast_2d(ξ)
+    sT = np.sqrt(T)
+    r = (sv / sT)[None, :] * X[:, -1:] + (sT * (1 - sv / T))[None, :] * X[:, :1]
+    for lev in range(L + 1):
+        p2 = float(1 << (L - lev))
+        j = np.floor(sv / T * p2).astype(np.int64) * (2 << lev) + (1 << lev)
+        lam = (sT * 0.5 - np.abs(np.fmod(sv * p2, T) / sT - sT * 0.5)) / np.sqrt(p2)  # Λ(s, L − lev, T), :3-6
+        r = r + X[:, j] * lam[None, :]
+    if ξ.ndim == 1:
+        return r[0] if s.ndim else r[0, 0]
+    return r if s.ndim else r[:, 0]
