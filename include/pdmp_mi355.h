@@ -609,6 +609,37 @@ pdmp_status pdmp_ensemble_bps_consume_discretized(pdmp_ensemble* ens, int64_t ch
 pdmp_status pdmp_ensemble_bps_consume_cummean(pdmp_ensemble* ens, int enable);
 pdmp_status pdmp_ensemble_bps_consume_cummean_copy(pdmp_ensemble* ens, int64_t chain, int64_t first, int64_t count, double* y);
 
+/* ------------------------------------------------------------------ conditional trace on the device (src/condition.jl)
+ *
+ * collect(conditional_trace(Ξ, (p, n))): the points where the sampled path crosses the hyperplane H = {x : <x − p, n> = 0}; the crossing times
+ * weighted by |<θ, n>| sample the target restricted to H (x_i = a, x_i = x_j, a contrast over a block, a diffusion bridge through a point:
+ * problems.bridge_point_condition).  Collected by the synchronous consumers above, slice by slice, without the trace leaving the device.
+ * The contract is the closed form from the cursors, at most ONE hit per linear piece (the reference recomputes the hitting time from the point it
+ * just put on the plane and may emit a crossing twice; DESIGN.md "Conditional trace"); every dot product in the 64-lane order of the
+ * device's wave sum; tests/ref/condition_ref.c states it sequentially and the device agrees with it bit for bit.
+ *   FactTrace (whatever consume_begin accepts).  S = the indices with n_j != 0, 1 <= |S| <= 1024.  A piece opens at t_b: t0, afterwards the time
+ *     of the latest event of a coordinate of S.  With the cursors of S as of t_b: xs_k = x_c + θ_c (t_b − t_c), g = Σ n_k (p_k − xs_k),
+ *     h = Σ n_k θ_c,k, τ = g / h, s = t_b + τ.  A candidate iff τ > 0; a hit, once, when the next event of S arrives at t_e >= s or the chain's
+ *     last consumed event time T_last >= s.  Row: x_c + θ_c (s − t_c) for every j from j's last event with t < s, else from (t0, x0_j, θ0_j).
+ *   PDMPTrace (event-recorded BouncyParticle and its sticky form).  Per event (t_k, ...) with the cursor (t_c, x_c, θ_c, f_c) before it:
+ *     τ = <p − x_c, n> / <θ_c, n>; a hit iff τ > 0 and t_c + τ < t_k, at t_c + τ, row_j = f_c,j ? x_c,j + θ_c,j τ : x_c,j.
+ *   [bps_]consume_condition(p, n, max_hits)   after [bps_]consume_begin and before the first [bps_]consume: reserves [nchains x max_hits] times
+ *     and [nchains x max_hits x d] rows (the factorised family also 24 bytes of cursor per chain and coordinate).  Without this call nothing
+ *     changes: no allocation, no kernel.  pdmp_ensemble_consume_async on such an ensemble: PDMP_ERR_UNSUPPORTED.
+ *   [bps_]consume_conditioned(chain, first, count, t, x, nhits, rows_dev)   rows [first, first + count) of a chain, first + count <= max_hits;
+ *     *nhits is NOT clamped to max_hits (a value above it: later rows were dropped); *rows_dev = the whole device array; any output may be NULL.
+ * PDMP_ERR_INVALID: NULL / non-finite p or n, n = 0, max_hits < 1 or rows beyond 256 GiB, before begin, after the first consume (a
+ * consume_async that handed a slice over counts), the other family's ensemble.
+ * PDMP_ERR_UNSUPPORTED: |S| > 1024 on a FactTrace (a PDMPTrace has no such limit); a Boomerang flow (hittingtime has no method, src/condition.jl:18); the speed-recorded flow or subsample
+ * (their records are not the corners of the path).
+ */
+pdmp_status pdmp_ensemble_consume_condition(pdmp_ensemble* ens, const double* p, const double* n, int64_t max_hits);
+pdmp_status pdmp_ensemble_consume_conditioned(pdmp_ensemble* ens, int64_t chain, int64_t first, int64_t count, double* t, double* x,
+                                              int64_t* nhits, void** rows_dev);
+pdmp_status pdmp_ensemble_bps_consume_condition(pdmp_ensemble* ens, const double* p, const double* n, int64_t max_hits);
+pdmp_status pdmp_ensemble_bps_consume_conditioned(pdmp_ensemble* ens, int64_t chain, int64_t first, int64_t count, double* t, double* x,
+                                                  int64_t* nhits, void** rows_dev);
+
 /* what the ensemble was created with (any pointer may be NULL) */
 pdmp_status pdmp_ensemble_info(pdmp_ensemble* ens, int64_t* nchains, int64_t* d, int64_t* trace_capacity, int* device);
 

@@ -46,6 +46,18 @@ static pdmp::BpsConsumeArgs consume_args(const pdmp_ensemble* e) {
     return a;
 }
 
+static pdmp::BpsCondArgs cond_args(const pdmp_ensemble* e) {
+    pdmp::BpsCondArgs q{};
+    q.p = e->bcn_pn.p;
+    q.n = e->bcn_pn.p + e->cfg.d;
+    q.tau = e->bcn_tau.p;
+    q.hit_t = e->bcn_t.p;
+    q.hit_x = e->bcn_x.p;
+    q.nhits = e->bcn_nh.p;
+    q.max_hits = e->bcn_max_hits;
+    return q;
+}
+
 // bps_consume_mean / _inclusion: one [n x d] read of the cursors of chains [chain_first, chain_first + n) and the chains' last event times
 static pdmp_status consume_read(pdmp_ensemble* e, int inclusion, int64_t chain_first, int64_t n, double* out, double* T_last, const char* who) {
     PDMP_TRY(need_begun(e, who));
@@ -85,6 +97,8 @@ pdmp_status pdmp_ensemble_bps_consume_begin(pdmp_ensemble* e, double grid_dt, in
         HIP_TRY(hipMemsetAsync(e->bc_grid.p, 0, (size_t)(n * grid_points * d) * sizeof(double), e->stream));
     }
     e->bc_cummean = false;
+    e->bcn_on = e->bc_started = false;
+    e->bcn_tau.release(), e->bcn_t.release(), e->bcn_x.release(), e->bcn_pn.release(), e->bcn_nh.release();
     e->bc_dt = grid_dt;
     e->bc_K = grid_points;
     LAUNCH_TRY("bps_consume_init", pdmp::launch_bps_consume_init(consume_args(e), e->stream));
@@ -100,7 +114,10 @@ pdmp_status pdmp_ensemble_bps_consume(pdmp_ensemble* e) {
     HIP_TRY(device_sync(e));
     if (!e->ev_c0) HIP_TRY(hipEventCreate(&e->ev_c0));
     if (!e->ev_c1) HIP_TRY(hipEventCreate(&e->ev_c1));
+    e->bc_started = true;
     HIP_TRY(hipEventRecord(e->ev_c0, e->stream));
+    if (e->bcn_on)  // (before the consumer: it reads the cursors and the progress the consumer is about to advance)
+        LAUNCH_TRY("bps_consume_condition", pdmp::launch_bps_cond(consume_args(e), cond_args(e), e->stream));
     LAUNCH_TRY("bps_consume", pdmp::launch_bps_consume_events(consume_args(e), e->stream));
     HIP_TRY(hipEventRecord(e->ev_c1, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
@@ -165,6 +182,64 @@ pdmp_status pdmp_ensemble_bps_consume_cummean_copy(pdmp_ensemble* e, int64_t cha
     HIP_TRY(device_sync(e));
     const int64_t d = e->cfg.d;
     if (count) HIP_TRY(hipMemcpy(y, e->bc_cm.p + (chain * e->cfg.trace_capacity + first) * d, (size_t)(count * d) * sizeof(double), hipMemcpyDeviceToHost));
+    return PDMP_OK;
+}
+
+// conditional_trace(Ξ::PDMPTrace, (p, n)) on the device (src/condition.jl:56-76; DESIGN.md "Conditional trace"): after bps_consume_begin and before the
+// first bps_consume; from then on bps_consume also collects the hyperplane hits of every slice
+pdmp_status pdmp_ensemble_bps_consume_condition(pdmp_ensemble* e, const double* p, const double* n, int64_t max_hits) {
+    PDMP_TRY(need_bps(e, __func__));
+    if (e->bps.flow_kind == 1)
+        return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_condition: the hitting time of a hyperplane has no method for the Boomerang flows (src/condition.jl:18)");
+    if (e->bps.modern)
+        return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_condition: the records of the speed-recorded flow are not the corners of the path (a straight line "
+                                          "between two of them is not the path)");
+    if (e->bps.subsample)
+        return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_condition: with subsample the records are not the corners of the path (a straight line between two of "
+                                          "them is not the path)");
+    PDMP_TRY(need_begun(e, __func__));
+    if (e->bc_started) return fail(PDMP_ERR_INVALID, "bps_consume_condition precedes the first bps_consume (its first segment starts from t0, x0, θ0)");
+    const int64_t d = e->cfg.d, nch = e->cfg.nchains, cap = e->cfg.trace_capacity;
+    std::vector<int32_t> S;
+    PDMP_TRY(condition_plane("bps_consume_condition", d, p, n, max_hits, &S));
+    PDMP_TRY(condition_rows_fit("bps_consume_condition", nch, d, max_hits));  // (no limit on |supp n|: a wavefront sums all d entries of a segment)
+    std::vector<double> pn((size_t)(2 * d));
+    std::copy(p, p + d, pn.begin());
+    std::copy(n, n + d, pn.begin() + d);
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(device_sync(e));
+    e->bcn_on = false;
+    PDMP_TRY(e->bcn_pn.upload(pn));
+    PDMP_TRY(e->bcn_tau.alloc((size_t)(nch * cap)));
+    PDMP_TRY(e->bcn_nh.alloc((size_t)nch));
+    PDMP_TRY(e->bcn_t.alloc((size_t)(nch * max_hits)));
+    PDMP_TRY(e->bcn_x.alloc((size_t)(nch * max_hits) * (size_t)d));
+    HIP_TRY(hipMemsetAsync(e->bcn_nh.p, 0, (size_t)nch * sizeof(unsigned long long), e->stream));
+    HIP_TRY(hipMemsetAsync(e->bcn_t.p, 0, (size_t)(nch * max_hits) * sizeof(double), e->stream));
+    HIP_TRY(hipMemsetAsync(e->bcn_x.p, 0, (size_t)(nch * max_hits) * (size_t)d * sizeof(double), e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->bcn_max_hits = max_hits;
+    e->bcn_on = true;
+    return PDMP_OK;
+}
+
+pdmp_status pdmp_ensemble_bps_consume_conditioned(pdmp_ensemble* e, int64_t chain, int64_t first, int64_t count, double* t, double* x, int64_t* nhits,
+                                                  void** rows_dev) {
+    PDMP_TRY(need_bps(e, __func__));
+    if (!e->bc_on || !e->bcn_on) return fail(PDMP_ERR_INVALID, "bps_consume_conditioned: pdmp_ensemble_bps_consume_condition first");
+    if (chain < 0 || chain >= e->cfg.nchains || first < 0 || count < 0 || first + count > e->bcn_max_hits)
+        return fail(PDMP_ERR_INVALID, "bps_consume_conditioned: chain / row range (max_hits = %lld)", (long long)e->bcn_max_hits);
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(device_sync(e));
+    const int64_t d = e->cfg.d, at = chain * e->bcn_max_hits + first;
+    if (t && count) HIP_TRY(hipMemcpy(t, e->bcn_t.p + at, (size_t)count * sizeof(double), hipMemcpyDeviceToHost));
+    if (x && count) HIP_TRY(hipMemcpy(x, e->bcn_x.p + at * d, (size_t)(count * d) * sizeof(double), hipMemcpyDeviceToHost));
+    if (nhits) {  // NOT clamped to max_hits: a value above it means that later rows were dropped
+        unsigned long long nh;
+        HIP_TRY(hipMemcpy(&nh, e->bcn_nh.p + chain, sizeof nh, hipMemcpyDeviceToHost));
+        *nhits = (int64_t)nh;
+    }
+    if (rows_dev) *rows_dev = e->bcn_x.p;
     return PDMP_OK;
 }
 }  // extern "C"

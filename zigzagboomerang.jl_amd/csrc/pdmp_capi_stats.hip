@@ -79,6 +79,29 @@ static pdmp_status consume_reduce(pdmp_ensemble* e, int64_t chain_first, int64_t
     return PDMP_OK;
 }
 
+constexpr uint64_t COND_MAX_ROW_BYTES = 1ull << 38;  // 256 GiB: the device's memory, about
+
+// what both families check of the (p, n, max_hits) of a conditional trace: the support of n comes back as the ascending list S
+pdmp_status condition_plane(const char* who, int64_t d, const double* p, const double* n, int64_t max_hits, std::vector<int32_t>* S) {
+    if (!p || !n) return fail(PDMP_ERR_INVALID, "%s: null argument", who);
+    if (max_hits < 1) return fail(PDMP_ERR_INVALID, "%s: max_hits = %lld must be at least 1", who, (long long)max_hits);
+    for (int64_t j = 0; j < d; ++j) {
+        if (!std::isfinite(p[j]) || !std::isfinite(n[j])) return fail(PDMP_ERR_INVALID, "%s: p and n must be finite (entry %lld is not)", who, (long long)j);
+        if (n[j] != 0.0) S->push_back((int32_t)j);
+    }
+    if (S->empty()) return fail(PDMP_ERR_INVALID, "%s: the normal n is zero", who);
+    return PDMP_OK;
+}
+
+// the rows of a conditional trace, [nchains x max_hits x d] doubles, must fit a reservation one device can hold: checked before any product is taken
+pdmp_status condition_rows_fit(const char* who, int64_t nchains, int64_t d, int64_t max_hits) {
+    const uint64_t per_hit = (uint64_t)nchains * (uint64_t)d * sizeof(double);  // (nchains x d x 8 fits: the cursors are that size)
+    if ((uint64_t)max_hits > COND_MAX_ROW_BYTES / per_hit)
+        return fail(PDMP_ERR_INVALID, "%s: max_hits = %lld rows of %llu bytes exceed the %llu GiB a condition may reserve", who, (long long)max_hits,
+                    (unsigned long long)per_hit, (unsigned long long)(COND_MAX_ROW_BYTES >> 30));
+    return PDMP_OK;
+}
+
 extern "C" {
 
 pdmp_status pdmp_ensemble_batch_means(pdmp_ensemble* e, double T_prev, double T, double* sum_y, double* sum_y2) {
@@ -190,6 +213,9 @@ pdmp_status pdmp_ensemble_consume_begin(pdmp_ensemble* e, double grid_dt, int64_
     PDMP_TRY(ensure_canon(e));
     discard_async_consumer(e);
     e->cons_cummean = false;
+    e->cn_on = e->cons_started = false;
+    e->d_cn_cur.release(), e->d_cn_t.release(), e->d_cn_x.release(), e->d_cn_pn.release();
+    e->d_cn_loc.release(), e->d_cn_idx.release(), e->d_cn_meta.release();
     LAUNCH_TRY("consume_init", pdmp::launch_consume_init(e->d_rec.p, e->track ? 128 : 64, d, n, e->t0_state, e->d_ccur.p, e->cons_z, e->d_cmeta.p,
                                        grid_points > 0 ? e->d_cgrid.p : nullptr, grid_points, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
@@ -204,6 +230,11 @@ pdmp_status pdmp_ensemble_consume(pdmp_ensemble* e) {
     if (!e->consuming || !e->has_state) return fail(PDMP_ERR_INVALID, "pdmp_ensemble_consume_begin first");
     HIP_TRY(hipSetDevice(e->cfg.device));
     HIP_TRY(device_sync(e));
+    e->cons_started = true;
+    if (e->cn_on)  // (cursors of its own: its place beside consume_events_kernel does not matter)
+        LAUNCH_TRY("consume_condition", pdmp::launch_cond_events(e->d_ev.p, e->cfg.trace_capacity, e->d_hdr.p, e->cfg.d, e->cfg.nchains, e->d_cn_loc.p, e->d_cn_idx.p,
+                                                                 e->cn_nS, e->d_cn_pn.p, e->d_cn_cur.p, e->d_cn_meta.p, e->d_cn_t.p, e->d_cn_x.p, e->cn_max_hits,
+                                                                 e->stream));
     LAUNCH_TRY("consume", pdmp::launch_consume_events(e->d_ev.p, e->cfg.trace_capacity, e->d_hdr.p, nullptr, e->cfg.d, e->cfg.nchains, e->d_ccur.p, e->cons_z, e->d_cmeta.p,
                                          e->d_cgrid.p, e->cons_K, e->t0_state, e->cons_dt, e->stream, e->cons_cummean ? e->d_ccm.p : nullptr));
     HIP_TRY(hipStreamSynchronize(e->stream));
@@ -282,6 +313,9 @@ pdmp_status pdmp_ensemble_subtrace_copy(pdmp_ensemble* e, int64_t chain, const i
 pdmp_status pdmp_ensemble_consume_async(pdmp_ensemble* e, void* stream) {
     if (!e) return fail(PDMP_ERR_INVALID, "null argument");
     if (!e->consuming || !e->has_state) return fail(PDMP_ERR_INVALID, "pdmp_ensemble_consume_begin first");
+    if (e->cn_on)
+        return fail(PDMP_ERR_UNSUPPORTED, "consume_async: the conditional trace (pdmp_ensemble_consume_condition) is served by the synchronous consumer, "
+                                          "pdmp_ensemble_consume");
     HIP_TRY(hipSetDevice(e->cfg.device));
     hipStream_t s = stream ? (hipStream_t)stream : e->stream;
     const int64_t n = e->cfg.nchains;
@@ -327,6 +361,7 @@ pdmp_status pdmp_ensemble_consume_async(pdmp_ensemble* e, void* stream) {
         HIP_TRY(hipStreamWaitEvent(s, e->ev_cons_done[k], 0));
     }
     e->async_k = k ^ 1;
+    e->cons_started = true;  // (the slice is handed to the consumer: a condition can no longer start from t0)
     return PDMP_OK;
 }
 
@@ -378,6 +413,69 @@ pdmp_status pdmp_ensemble_consume_discretized(pdmp_ensemble* e, int64_t chain, i
         *npoints = np > 0 ? np : 1;
     }
     if (grid_dev) *grid_dev = e->d_cgrid.p;
+    return PDMP_OK;
+}
+
+// conditional_trace(Ξ, (p, n)) on the device (src/condition.jl; DESIGN.md "Conditional trace"): after consume_begin and before the first consume
+pdmp_status pdmp_ensemble_consume_condition(pdmp_ensemble* e, const double* p, const double* n, int64_t max_hits) {
+    if (!e) return fail(PDMP_ERR_INVALID, "null argument");
+    NEED_FACTORISED(e);
+    if (e->flow_kind != 0)
+        return fail(PDMP_ERR_UNSUPPORTED, "consume_condition: the hitting time of a hyperplane has no method for the Boomerang flows (src/condition.jl:18)");
+    if (!e->consuming || !e->has_state) return fail(PDMP_ERR_INVALID, "consume_condition: pdmp_ensemble_consume_begin first");
+    if (e->cons_started) return fail(PDMP_ERR_INVALID, "consume_condition precedes the first consume (its cursors start from t0, x0, θ0)");
+    const int64_t d = e->cfg.d, nch = e->cfg.nchains;
+    std::vector<int32_t> S;
+    PDMP_TRY(condition_plane("consume_condition", d, p, n, max_hits, &S));
+    PDMP_TRY(condition_rows_fit("consume_condition", nch, d, max_hits));
+    if ((int64_t)S.size() > pdmp::COND_MAX_S)
+        return fail(PDMP_ERR_UNSUPPORTED, "consume_condition: n has %zu non-zero entries, the device walks at most %d (condition the returned trace on the host)",
+                    S.size(), pdmp::COND_MAX_S);
+    std::vector<int32_t> loc((size_t)d, -1);
+    std::vector<double> pn(2 * S.size());
+    for (size_t k = 0; k < S.size(); ++k) {
+        loc[(size_t)S[k]] = (int32_t)k;
+        pn[k] = p[S[k]];
+        pn[S.size() + k] = n[S[k]];
+    }
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(device_sync(e));
+    e->cn_on = false;
+    PDMP_TRY(e->d_cn_loc.upload(loc));
+    PDMP_TRY(e->d_cn_idx.upload(S));
+    PDMP_TRY(e->d_cn_pn.upload(pn));
+    PDMP_TRY(e->d_cn_cur.alloc((size_t)(3 * nch * d)));
+    PDMP_TRY(e->d_cn_meta.alloc((size_t)nch * pdmp::cond_meta_bytes()));
+    PDMP_TRY(e->d_cn_t.alloc((size_t)(nch * max_hits)));
+    PDMP_TRY(e->d_cn_x.alloc((size_t)(nch * max_hits) * (size_t)d));
+    HIP_TRY(hipMemsetAsync(e->d_cn_t.p, 0, (size_t)(nch * max_hits) * sizeof(double), e->stream));
+    HIP_TRY(hipMemsetAsync(e->d_cn_x.p, 0, (size_t)(nch * max_hits) * (size_t)d * sizeof(double), e->stream));
+    LAUNCH_TRY("consume_condition_init", pdmp::launch_cond_init(e->d_ccur.p, d, nch, e->t0_state, e->d_cn_cur.p, e->d_cn_meta.p, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->cn_nS = (int)S.size();
+    e->cn_max_hits = max_hits;
+    e->cn_on = true;
+    return PDMP_OK;
+}
+
+pdmp_status pdmp_ensemble_consume_conditioned(pdmp_ensemble* e, int64_t chain, int64_t first, int64_t count, double* t, double* x, int64_t* nhits,
+                                              void** rows_dev) {
+    if (!e) return fail(PDMP_ERR_INVALID, "null argument");
+    NEED_FACTORISED(e);
+    if (!e->consuming || !e->cn_on) return fail(PDMP_ERR_INVALID, "consume_conditioned: pdmp_ensemble_consume_condition first");
+    if (chain < 0 || chain >= e->cfg.nchains || first < 0 || count < 0 || first + count > e->cn_max_hits)
+        return fail(PDMP_ERR_INVALID, "consume_conditioned: chain / row range (max_hits = %lld)", (long long)e->cn_max_hits);
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(device_sync(e));
+    const int64_t d = e->cfg.d, at = chain * e->cn_max_hits + first;
+    if (t && count) HIP_TRY(hipMemcpy(t, e->d_cn_t.p + at, (size_t)count * sizeof(double), hipMemcpyDeviceToHost));
+    if (x && count) HIP_TRY(hipMemcpy(x, e->d_cn_x.p + at * d, (size_t)(count * d) * sizeof(double), hipMemcpyDeviceToHost));
+    if (nhits) {  // { consumed, t_b, nhits, done }: NOT clamped to max_hits -- a value above it means that later rows were dropped
+        uint64_t nh;
+        HIP_TRY(hipMemcpy(&nh, e->d_cn_meta.p + (size_t)chain * pdmp::cond_meta_bytes() + 16, sizeof nh, hipMemcpyDeviceToHost));
+        *nhits = (int64_t)nh;
+    }
+    if (rows_dev) *rows_dev = e->d_cn_x.p;
     return PDMP_OK;
 }
 

@@ -4,6 +4,7 @@
 
 #include <cstdint>
 
+#include "pdmp_bps_common.hpp"
 #include "pdmp_engine.hpp"
 
 namespace pdmp {
@@ -336,6 +337,237 @@ int launch_consume_mean(int64_t d, int64_t chain_first, int64_t n, const void* c
     const int64_t tot = n * d;
     hipLaunchKernelGGL(consume_mean_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d, chain_first, n,
                        static_cast<const ConsumeCursor*>(cur), static_cast<const ConsumeMeta*>(meta), mean_out, T_out);
+    return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------ conditional trace (src/condition.jl)
+//
+// collect(conditional_trace(Ξ, (p, n))) of a FactTrace: the points where the path crosses the hyperplane {x : ⟨x − p, n⟩ = 0}, slice by slice like
+// the consumers above (DESIGN.md "Conditional trace" has the contract and why the reference's own loop cannot be it).  S = the coordinates with
+// n_j ≠ 0, at most COND_MAX_S, as a list (idx, and loc[] = position in the list or −1).  A PIECE runs between two events of S; from the cursors
+// of S as of its start t_b:  xs_k = x_c + θ_c (t_b − t_c),  g = Σ n_k (p_k − xs_k),  h = Σ n_k θ_c,k  in the order of dot_wave64 (list position =
+// element index),  τ = g / h,  s = t_b + τ;  a candidate iff τ > 0;  a hit, once per piece, when the next event of S arrives at t_e >= s or the
+// last consumed event time T_last >= s.  s depends on (t_b, cursors) only, so the hits do not depend on how the run was sliced.
+// One workgroup per chain, per slice, in two passes over the slice:
+//   1. chunks of 256 events are compacted to their events of S (block prefix count, as trace_subtrace_kernel) in LDS and walked by wavefront 0,
+//      which holds the cursors of S, n and p in LDS: lane l sums list entries l, l + 64, ..., then wave_sum_f64.  Hit times go to the hit list.
+//   2. the rows of this slice's new hits, for all d coordinates: the events with t < s (strictly: the reference emits before it applies the event)
+//      are applied to the condition's OWN cursors (t, x, θ per (chain, coordinate), 24 bytes: the consumers' cursors above are neither read nor
+//      written after the init, so mean / discretize stay what they were), then row_j = x_c + θ_c (s − t_c), thread by thread.  Only a coordinate's
+//      LAST event of a range counts -- no sums are kept --, so of two events of one coordinate inside a chunk the earlier one is dropped.
+struct CondMeta {
+    uint64_t consumed;  // events of this chain consumed so far (global event index)
+    double t_b;         // where the open piece began
+    uint64_t nhits;     // hits so far, NOT clamped to max_hits
+    uint64_t done;      // the open piece has had its hit
+};
+size_t cond_meta_bytes() { return sizeof(CondMeta); }
+
+__global__ __launch_bounds__(256) void cond_init_kernel(const ConsumeCursor* __restrict__ cur, int64_t d, int64_t nchains, double t0, double* ct, double* cx,
+                                                        double* cth, CondMeta* meta) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k < nchains) {
+        CondMeta m;
+        m.consumed = 0;
+        m.t_b = t0;
+        m.nhits = 0;
+        m.done = 0;
+        meta[k] = m;
+    }
+    if (k >= nchains * d) return;
+    const ConsumeCursor c = cur[k];  // (before the first consume: t0, x0, θ0)
+    ct[k] = c.t;
+    cx[k] = c.x;
+    cth[k] = c.th;
+}
+
+// the events [lo, hi) of a chain's segment applied to the condition's cursors: per coordinate the last one of the range
+__device__ __forceinline__ void cond_apply(const pdmp_event* __restrict__ ev, uint64_t lo, uint64_t hi, int64_t d, double* ct, double* cx, double* cth,
+                                           uint32_t* s_i, uint8_t* s_own) {
+    const int tid = threadIdx.x;
+    for (uint64_t base = lo; base < hi; base += 256) {
+        const uint64_t e = base + (uint64_t)tid;
+        const bool valid = e < hi;
+        pdmp_event evt;
+        evt.t = 0.0;
+        evt.i = 0;
+        evt.x = evt.theta = 0.0;
+        if (valid) evt = ev[e];
+        const bool inside = valid && (uint64_t)evt.i < (uint64_t)d;
+        const uint32_t hs = ((uint32_t)evt.i * 0x9E3779B1u) >> 20;  // (12 bits: the table of consume_events_kernel)
+        s_i[tid] = inside ? (uint32_t)evt.i : 0xffffffffu;
+        if (inside) s_own[hs] = (uint8_t)tid;
+        __syncthreads();
+        const bool clash = inside && s_own[hs] != (uint8_t)tid;
+        __syncthreads();
+        if (clash) s_own[hs] = 0xff;
+        __syncthreads();
+        bool write = inside;
+        if (inside && (clash || s_own[hs] == 0xff))  // another event of this chunk hashes alike: a later one of the same coordinate wins
+            for (int q = tid + 1; q < 256; ++q)
+                if (s_i[q] == (uint32_t)evt.i) {
+                    write = false;
+                    break;
+                }
+        if (write) {
+            ct[evt.i] = evt.t;
+            cx[evt.i] = evt.x;
+            cth[evt.i] = evt.theta;
+        }
+        __threadfence_block();
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(256) void cond_events_kernel(const pdmp_event* ev0, int64_t cap, const DevChain* hdr, int64_t d, const int32_t* __restrict__ loc,
+                                                          const int32_t* __restrict__ idx, int nS, const double* __restrict__ pn, double* ct0, double* cx0,
+                                                          double* cth0, CondMeta* meta, double* hit_t0, double* hit_x0, int64_t max_hits) {
+    const int64_t chain = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63;
+    __shared__ double s_t[COND_MAX_S], s_x[COND_MAX_S], s_th[COND_MAX_S], s_n[COND_MAX_S], s_p[COND_MAX_S];  // the cursors of S as of t_b; n, p over S
+    __shared__ double c_t[256], c_x[256], c_th[256];  // a chunk's events of S, compacted
+    __shared__ int32_t c_l[256];
+    __shared__ uint32_t s_cnt[256], s_i[256];
+    __shared__ uint8_t s_own[CONSUME_HASH];
+    __shared__ uint64_t s_split, s_nh;
+    const uint64_t ntrace = hdr[chain].c.ntrace, nevents = hdr[chain].c.nevents;
+    const uint64_t n = ntrace < (uint64_t)cap ? ntrace : (uint64_t)cap;
+    CondMeta m = meta[chain];
+    const uint64_t first_global = nevents - ntrace;  // global index of buffer slot 0
+    const uint64_t pos0 = (m.consumed > first_global) ? (m.consumed - first_global) : 0;  // first unconsumed slot
+    if (pos0 >= n) return;
+    const pdmp_event* ev = ev0 + chain * cap;
+    double *ct = ct0 + chain * d, *cx = cx0 + chain * d, *cth = cth0 + chain * d;
+    double* hit_t = hit_t0 + chain * max_hits;
+    for (int k = tid; k < nS; k += 256) {  // (every earlier event is applied: the condition's cursors ARE the cursors of S as of t_b)
+        const int32_t j = idx[k];
+        s_t[k] = ct[j];
+        s_x[k] = cx[j];
+        s_th[k] = cth[j];
+        s_p[k] = pn[k];
+        s_n[k] = pn[nS + k];
+    }
+    __syncthreads();
+
+    // ---- pass 1: the hit times
+    const bool walker = tid < 64;  // wavefront 0
+    double t_b = m.t_b, s = 0.0;
+    bool cand = false, done = m.done != 0;
+    uint64_t nh = m.nhits;
+    const uint64_t nh0 = nh;
+    auto open_piece = [&]() {
+        double pg = 0.0, ph = 0.0;
+        for (int k = lane; k < nS; k += 64) {
+            const double xs = s_x[k] + s_th[k] * (t_b - s_t[k]);
+            pg += s_n[k] * (s_p[k] - xs);
+            ph += s_n[k] * s_th[k];
+        }
+        const double tau = wave_sum_f64(pg) / wave_sum_f64(ph);
+        s = t_b + tau;
+        cand = tau > 0;  // (false for NaN; s = +Inf is never reached by an event)
+    };
+    auto emit = [&]() {
+        if (lane == 0 && nh < (uint64_t)max_hits) hit_t[nh] = s;
+        nh += 1;
+        done = true;
+    };
+    if (walker) open_piece();
+    for (uint64_t base = pos0; base < n; base += 256) {
+        const uint64_t e = base + (uint64_t)tid;
+        pdmp_event evt;
+        evt.t = 0.0;
+        evt.i = 0;
+        evt.x = evt.theta = 0.0;
+        int32_t l = -1;
+        if (e < n) {
+            evt = ev[e];
+            if ((uint64_t)evt.i < (uint64_t)d) l = loc[evt.i];
+        }
+        s_cnt[tid] = (l >= 0) ? 1u : 0u;
+        __syncthreads();
+        for (int off = 1; off < 256; off <<= 1) {  // inclusive prefix sum
+            const uint32_t v = (tid >= off) ? s_cnt[tid - off] : 0u;
+            __syncthreads();
+            s_cnt[tid] += v;
+            __syncthreads();
+        }
+        if (l >= 0) {
+            const uint32_t at = s_cnt[tid] - 1u;
+            c_t[at] = evt.t;
+            c_x[at] = evt.x;
+            c_th[at] = evt.theta;
+            c_l[at] = l;
+        }
+        __syncthreads();
+        if (walker) {
+            const uint32_t cnt = s_cnt[255];
+            for (uint32_t q = 0; q < cnt; ++q) {
+                const double te = c_t[q];
+                const int32_t lq = c_l[q];
+                if (!done && cand && te >= s) emit();  // (inclusive, src/condition.jl:42)
+                if (lane == (lq & 63)) {
+                    s_t[lq] = te;
+                    s_x[lq] = c_x[q];
+                    s_th[lq] = c_th[q];
+                }
+                asm volatile("" ::: "memory");  // (one wavefront: its DS operations retire in order)
+                t_b = te;
+                done = false;
+                open_piece();
+            }
+        }
+        __syncthreads();
+    }
+    if (walker && !done && cand && ev[n - 1].t >= s) emit();  // T_last >= s
+    if (tid == 0) s_nh = nh;
+    __threadfence_block();
+    __syncthreads();
+
+    // ---- pass 2: the rows of this slice's hits, and the condition's cursors brought to the end of the slice
+    const uint64_t nh1 = s_nh;
+    const uint64_t stored = nh1 < (uint64_t)max_hits ? nh1 : (uint64_t)max_hits;
+    uint64_t pos = pos0;
+    for (uint64_t q = nh0; q < stored; ++q) {
+        const double sq = hit_t[q];
+        if (tid == 0) {  // first slot in [pos, n) whose time is not before sq (the trace is sorted by time)
+            uint64_t lo = pos, hi = n;
+            while (lo < hi) {
+                const uint64_t mid = lo + ((hi - lo) >> 1);
+                if (ev[mid].t < sq) lo = mid + 1;
+                else hi = mid;
+            }
+            s_split = lo;
+        }
+        __syncthreads();
+        const uint64_t split = s_split;
+        cond_apply(ev, pos, split, d, ct, cx, cth, s_i, s_own);
+        __syncthreads();
+        double* const row = hit_x0 + (chain * max_hits + (int64_t)q) * d;
+        for (int64_t j = tid; j < d; j += 256) row[j] = cx[j] + cth[j] * (sq - ct[j]);
+        pos = split;
+        __syncthreads();
+    }
+    cond_apply(ev, pos, n, d, ct, cx, cth, s_i, s_own);
+    if (tid == 0) {
+        m.consumed = nevents;
+        m.t_b = t_b;
+        m.nhits = nh1;
+        m.done = done ? 1 : 0;
+        meta[chain] = m;
+    }
+}
+
+int launch_cond_init(const void* cur, int64_t d, int64_t nchains, double t0, double* ccur, void* meta, void* stream) {
+    const int64_t n = nchains * d;
+    hipLaunchKernelGGL(cond_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, static_cast<const ConsumeCursor*>(cur), d, nchains,
+                       t0, ccur, ccur + n, ccur + 2 * n, static_cast<CondMeta*>(meta));
+    return (int)hipGetLastError();
+}
+int launch_cond_events(const pdmp_event* ev, int64_t cap, const DevChain* hdr, int64_t d, int64_t nchains, const int32_t* loc, const int32_t* idx, int nS,
+                       const double* pn, double* ccur, void* meta, double* hit_t, double* hit_x, int64_t max_hits, void* stream) {
+    const int64_t n = nchains * d;
+    hipLaunchKernelGGL(cond_events_kernel, dim3((unsigned)nchains), dim3(256), 0, (hipStream_t)stream, ev, cap, hdr, d, loc, idx, nS, pn, ccur, ccur + n,
+                       ccur + 2 * n, static_cast<CondMeta*>(meta), hit_t, hit_x, max_hits);
     return (int)hipGetLastError();
 }
 

@@ -22,6 +22,7 @@
 
 #include <cstdint>
 
+#include "pdmp_bps_common.hpp"
 #include "pdmp_device.hpp"
 #include "pdmp_engine.hpp"
 
@@ -183,6 +184,122 @@ int launch_bps_consume_read(const BpsConsumeArgs& p, int inclusion, int64_t chai
     const int64_t tot = n * p.d;
     hipLaunchKernelGGL(bps_consume_read_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, inclusion, chain_first, n, out,
                        T_out);
+    return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------ conditional trace (src/condition.jl:56-76)
+//
+// collect(conditional_trace(Ξ, (p, n))) of a PDMPTrace with the linear flow: per event (t_k, x_k, θ_k[, f_k]) with the cursor (t_c, x_c, θ_c, f_c)
+// before it,  g = dot_wave64(p − x_c, n),  h = dot_wave64(θ_c, n),  τ = g / h;  a hit iff τ > 0 and t_c + τ < t_k (strictly), at t_c + τ, with
+// row_j = f_c,j ? x_c,j + θ_c,j τ : x_c,j; one hit per segment, nothing behind the last event (DESIGN.md "Conditional trace").  An event replaces the
+// whole state, so the segments are independent: the cursor of a segment is the event before it, the carried cursor for the first of a slice.  Both
+// kernels run BEFORE bps_consume_kernel of the same slice and only read what it carries (cursors, clock, free bits, events consumed).
+//   bps_cond_scan_kernel  one wavefront per (chain, segment): 512 contiguous bytes of x_c and of θ_c per load, p and n alongside; lane l sums
+//                         elements l, l + 64, ..., then wave_sum_f64; τ of a hit (−1 otherwise) to the segment's slot of a [nchains x cap] array.
+//   bps_cond_rows_kernel  one workgroup per chain: chunks of 256 slots compacted in order by a block prefix count, every hit's time and row written by
+//                         the whole workgroup, four strips at a time.  The hit count is NOT clamped to max_hits; rows behind it are dropped.
+struct BpsCondSlice {
+    uint64_t pos, n;  // the unconsumed slots [pos, n) of the chain's segment
+    double t_cur;
+};
+__device__ __forceinline__ BpsCondSlice bps_cond_slice(const BpsConsumeArgs& P, int64_t chain) {
+    const BpsConsumeMeta m = static_cast<const BpsConsumeMeta*>(P.meta)[chain * P.nstrips];  // (strip 0's copy of the chain's progress)
+    const uint64_t ntrace = P.hdr[chain].c.ntrace, nevents = P.hdr[chain].c.nevents;
+    BpsCondSlice s;
+    s.n = ntrace < (uint64_t)P.cap ? ntrace : (uint64_t)P.cap;
+    const uint64_t first_global = nevents - ntrace;
+    s.pos = (m.consumed > first_global) ? (m.consumed - first_global) : 0;
+    s.t_cur = m.t_cur;
+    return s;
+}
+
+__global__ __launch_bounds__(256) void bps_cond_scan_kernel(BpsConsumeArgs P, BpsCondArgs Q) {
+    const int lane = threadIdx.x & 63;
+    const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (w >= P.nchains * P.cap) return;
+    const int64_t chain = w / P.cap;
+    const uint64_t e = (uint64_t)(w - chain * P.cap);
+    const BpsCondSlice sl = bps_cond_slice(P, chain);
+    if (e < sl.pos || e >= sl.n) return;
+    const int64_t d = P.d, slot0 = chain * P.cap;
+    const bool first = e == sl.pos;
+    const double* const xc = first ? P.cx + chain * d : P.ev_x + (slot0 + (int64_t)e - 1) * d;
+    const double* const thc = first ? P.cth + chain * d : P.ev_th + (slot0 + (int64_t)e - 1) * d;
+    const double t_c = first ? sl.t_cur : P.ev_t[slot0 + (int64_t)e - 1];
+    const double t_k = P.ev_t[slot0 + (int64_t)e];
+    double pg = 0.0, ph = 0.0;
+    for (int64_t k = lane; k < d; k += 64) {
+        const double nk = Q.n[k];
+        pg += (Q.p[k] - xc[k]) * nk;
+        ph += thc[k] * nk;
+    }
+    const double tau = wave_sum_f64(pg) / wave_sum_f64(ph);
+    const bool hit = tau > 0 && t_c + tau < t_k;  // (strict, src/condition.jl:63; false for NaN)
+    if (lane == 0) Q.tau[slot0 + (int64_t)e] = hit ? tau : -1.0;
+}
+
+template <bool STICKY>
+__global__ __launch_bounds__(256) void bps_cond_rows_kernel(BpsConsumeArgs P, BpsCondArgs Q) {
+    __shared__ uint32_t s_cnt[256];
+    __shared__ uint32_t s_e[256];
+    __shared__ double s_tau[256];
+    const int tid = threadIdx.x;
+    const int64_t chain = blockIdx.x;
+    const BpsCondSlice sl = bps_cond_slice(P, chain);
+    if (sl.pos >= sl.n) return;
+    const int64_t d = P.d, slot0 = chain * P.cap;
+    const BpsConsumeMeta* const meta = static_cast<const BpsConsumeMeta*>(P.meta) + chain * P.nstrips;
+    uint64_t nh = Q.nhits[chain];
+    for (uint64_t base = sl.pos; base < sl.n; base += 256) {
+        const uint64_t e = base + (uint64_t)tid;
+        const double tau = e < sl.n ? Q.tau[slot0 + (int64_t)e] : -1.0;
+        const bool hit = tau > 0;
+        s_cnt[tid] = hit ? 1u : 0u;
+        __syncthreads();
+        for (int off = 1; off < 256; off <<= 1) {  // inclusive prefix sum
+            const uint32_t v = (tid >= off) ? s_cnt[tid - off] : 0u;
+            __syncthreads();
+            s_cnt[tid] += v;
+            __syncthreads();
+        }
+        if (hit) {
+            s_e[s_cnt[tid] - 1u] = (uint32_t)tid;
+            s_tau[s_cnt[tid] - 1u] = tau;
+        }
+        __syncthreads();
+        const uint32_t cnt = s_cnt[255];
+        for (uint32_t r = 0; r < cnt; ++r) {
+            const uint64_t q = nh + r;
+            if (q >= (uint64_t)Q.max_hits) break;
+            const uint64_t eh = base + s_e[r];
+            const double th = s_tau[r];
+            const bool first = eh == sl.pos;
+            const double* const xc = first ? P.cx + chain * d : P.ev_x + (slot0 + (int64_t)eh - 1) * d;
+            const double* const thc = first ? P.cth + chain * d : P.ev_th + (slot0 + (int64_t)eh - 1) * d;
+            if (tid == 0) Q.hit_t[chain * Q.max_hits + (int64_t)q] = (first ? sl.t_cur : P.ev_t[slot0 + (int64_t)eh - 1]) + th;
+            double* const row = Q.hit_x + (chain * Q.max_hits + (int64_t)q) * d;
+            for (int64_t j = tid; j < d; j += 256) {
+                bool free = true;
+                if (STICKY) {
+                    const uint64_t w = first ? meta[j >> 6].free : P.ev_f[(slot0 + (int64_t)eh - 1) * BPS_STICKY_WORDS + (j >> 6)];
+                    free = (w >> (j & 63)) & 1ull;
+                }
+                const double x = xc[j];
+                row[j] = free ? x + thc[j] * th : x;  // smove_forward!, src/ss_not_fact.jl:78-86
+            }
+        }
+        nh += cnt;
+        __syncthreads();
+    }
+    if (tid == 0) Q.nhits[chain] = nh;
+}
+
+int launch_bps_cond(const BpsConsumeArgs& p, const BpsCondArgs& q, void* stream) {
+    hipLaunchKernelGGL(bps_cond_scan_kernel, dim3((unsigned)((p.nchains * p.cap + 3) / 4)), dim3(256), 0, (hipStream_t)stream, p, q);
+    int rc = (int)hipGetLastError();
+    if (rc) return rc;
+    if (p.ev_f) hipLaunchKernelGGL((bps_cond_rows_kernel<true>), dim3((unsigned)p.nchains), dim3(256), 0, (hipStream_t)stream, p, q);
+    else hipLaunchKernelGGL((bps_cond_rows_kernel<false>), dim3((unsigned)p.nchains), dim3(256), 0, (hipStream_t)stream, p, q);
     return (int)hipGetLastError();
 }
 

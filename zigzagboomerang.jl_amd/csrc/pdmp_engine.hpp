@@ -543,6 +543,13 @@ int launch_consume_inclusion(int64_t d, int64_t nchains, bool with_z, double t0,
                              double* T_out, void* stream);
 int launch_zz_path_integrals(const ZzRec* rec, int64_t rec_stride, int64_t d, int64_t nchains, const int64_t* probes, int64_t nprobe,
                              double T, double* out, void* stream);
+// ... the conditional trace (pdmp_ensemble_consume_condition): cursors of its own ccur = t, x, θ [nchains x d] each, the list of S = supp n (idx, and
+// loc[] = position in the list or −1), pn = p then n over the list, the hit times [nchains x max_hits] and rows [nchains x max_hits x d]
+constexpr int COND_MAX_S = 1024;
+size_t cond_meta_bytes();
+int launch_cond_init(const void* cur, int64_t d, int64_t nchains, double t0, double* ccur, void* meta, void* stream);
+int launch_cond_events(const pdmp_event* ev, int64_t cap, const DevChain* hdr, int64_t d, int64_t nchains, const int32_t* loc, const int32_t* idx, int nS,
+                       const double* pn, double* ccur, void* meta, double* hit_t, double* hit_x, int64_t max_hits, void* stream);
 int launch_math_probe(uint64_t seed, int64_t n, double* out, void* stream);
 // pdmp_consume_bps.hip: the streaming consumers of the Bouncy Particle family's trace buffers.  One block of pointers and numbers for its three
 // kernels: the trace (ev_f: a sticky ensemble's masks, else nullptr), the chain headers, the Boomerang's centre (nullptr: linear flow), the state
@@ -564,6 +571,15 @@ size_t bps_consume_meta_bytes();
 int launch_bps_consume_init(const BpsConsumeArgs& p, void* stream);
 int launch_bps_consume_events(const BpsConsumeArgs& p, void* stream);
 int launch_bps_consume_read(const BpsConsumeArgs& p, int inclusion, int64_t chain_first, int64_t n, double* out, double* T_out, void* stream);
+// ... the conditional trace (pdmp_ensemble_bps_consume_condition): p and n [d], τ of a hit per segment slot [nchains x cap], the hit times
+// [nchains x max_hits], rows [nchains x max_hits x d] and counts [nchains]; launched before launch_bps_consume_events of the same slice
+struct BpsCondArgs {
+    const double *p, *n;
+    double *tau, *hit_t, *hit_x;
+    unsigned long long* nhits;
+    int64_t max_hits;
+};
+int launch_bps_cond(const BpsConsumeArgs& p, const BpsCondArgs& q, void* stream);
 
 #ifdef PDMP_EXTRA_KERNELS
 // pdmp_debug_math_eval (include/pdmp_debug.h, parity library only): a translation unit that calls the shared scalar functions of pdmp_device.hpp

@@ -214,6 +214,15 @@ struct pdmp_ensemble {
     bool consuming = false, cons_z = false;
     double cons_dt = 0.0;
     int64_t cons_K = 0;
+    // pdmp_ensemble_consume_condition: the conditional trace's own cursors (t, x, θ) [3 x nchains x d], the list of supp n (cn_idx; cn_loc[] =
+    // position in it or −1), p then n over the list, per-chain progress, hit times [nchains x max_hits] and rows [nchains x max_hits x d]
+    DevBuf<double> d_cn_cur, d_cn_pn, d_cn_t, d_cn_x;
+    DevBuf<int32_t> d_cn_loc, d_cn_idx;
+    DevBuf<unsigned char> d_cn_meta;
+    bool cn_on = false;
+    bool cons_started = false;  // a consume / consume_async happened since consume_begin
+    int cn_nS = 0;
+    int64_t cn_max_hits = 0;
     bool trace_appended = false;  // pdmp_debug_trace_append put events into the trace that no record knows of: run is refused until the next set_state
     // pdmp_ensemble_consume_async: a second trace buffer (the event loop writes one while the consumer reads the other), the consumer's stream,
     // the (ntrace, nevents) snapshots of the two most recent slices and the events that order the two streams
@@ -278,6 +287,11 @@ struct pdmp_ensemble {
     bool bc_on = false, bc_cummean = false;
     double bc_dt = 0.0;
     int64_t bc_K = 0;
+    // pdmp_ensemble_bps_consume_condition: p then n [2 x d], τ per segment slot [nchains x cap], hit times, rows and counts (pdmp::BpsCondArgs)
+    DevBuf<double> bcn_pn, bcn_tau, bcn_t, bcn_x;
+    DevBuf<unsigned long long> bcn_nh;
+    bool bcn_on = false, bc_started = false;  // bc_started: a bps_consume happened since bps_consume_begin
+    int64_t bcn_max_hits = 0;
 
     pdmp::ZzTables tables() const {
         pdmp::ZzTables tb{};
@@ -341,6 +355,9 @@ pdmp::BpsStickyParams bps_sticky_params(const pdmp_ensemble* e);
 pdmp::BpsModernParams bps_modern_params(const pdmp_ensemble* e);
 pdmp::BpsLogitParams bps_logit_params(const pdmp_ensemble* e);
 pdmp_status bps_moments_at(pdmp_ensemble* e, double T, int64_t chain_first, int64_t n, bool two);
+// pdmp_capi_stats.hip
+pdmp_status condition_plane(const char* who, int64_t d, const double* p, const double* n, int64_t max_hits, std::vector<int32_t>* S);
+pdmp_status condition_rows_fit(const char* who, int64_t nchains, int64_t d, int64_t max_hits);
 // pdmp_capi_tune.hip: set_state with the placement probes
 pdmp_status init_state_tuned(pdmp_ensemble* e, double t0, const double* x0, const double* th0, const double* c, const uint64_t* seeds, uint64_t seed0);
 pdmp_status init_state_bps_tuned(pdmp_ensemble* e, double t0, const double* x0, const double* theta0, double c, const uint64_t* seeds);

@@ -527,6 +527,44 @@ class Ensemble:
             _lib.check(self._L.pdmp_ensemble_consume_discretized(self._h, int(chain), int(k_first), k_count, _ptr(out), None, None))
         return self.t0 + dt * (k_first + np.arange(max(k_count, 0))), out
 
+    # ---- the conditional trace on the device (pdmp_ensemble_[bps_]consume_condition, src/condition.jl)
+    def _condition(self, fn, p, n, max_hits):
+        p, n = _f64(p).reshape(-1), _f64(n).reshape(-1)
+        if p.size != self.d or n.size != self.d:
+            raise ValueError("p and n have the ensemble's dimension %d" % self.d)
+        _lib.check(fn(self._h, _ptr(p), _ptr(n), int(max_hits)))
+
+    def _conditioned(self, fn, chain, first, count):
+        nh = C.c_int64()
+        _lib.check(fn(self._h, int(chain), 0, 0, None, None, C.byref(nh), None))
+        if count is None:
+            count = max(min(int(nh.value), self._max_hits) - int(first), 0)
+        t, x = np.empty(int(count)), np.empty((int(count), self.d))
+        if count > 0:
+            _lib.check(fn(self._h, int(chain), int(first), int(count), _ptr(t), _ptr(x), None, None))
+        return t, x, int(nh.value)
+
+    def consume_condition(self, p, n, max_hits):
+        """collect(conditional_trace(Ξ, (p, n))) on the device (src/condition.jl): after consume_begin and before the first consume(); from then
+        on consume() also collects the points where the path crosses the hyperplane {x : ⟨x − p, n⟩ = 0}, at most max_hits per chain."""
+        self._condition(self._L.pdmp_ensemble_consume_condition, p, n, max_hits)
+        self._max_hits = int(max_hits)
+
+    def consume_conditioned(self, chain, first=0, count=None):
+        """(t [m], x [m x d], nhits) of one chain: the stored hits [first, first + count) -- all of them by default -- as trace.conditional_trace
+        returns them; nhits is not clamped: a value above max_hits means that later hits were dropped."""
+        return self._conditioned(self._L.pdmp_ensemble_consume_conditioned, chain, first, count)
+
+    def bps_consume_condition(self, p, n, max_hits):
+        """consume_condition for the Bouncy Particle family (event-recorded BouncyParticle and its sticky form): after bps_consume_begin and
+        before the first bps_consume()."""
+        self._condition(self._L.pdmp_ensemble_bps_consume_condition, p, n, max_hits)
+        self._max_hits = int(max_hits)
+
+    def bps_consume_conditioned(self, chain, first=0, count=None):
+        """consume_conditioned for the Bouncy Particle family."""
+        return self._conditioned(self._L.pdmp_ensemble_bps_consume_conditioned, chain, first, count)
+
     # ---- trace consumers of the Bouncy Particle family on the device (pdmp_ensemble_bps_consume_*)
     def bps_consume_begin(self, grid_dt=0.0, grid_points=0):
         """After set_state_bps, before the first run: (t0, x0, θ0) become the cursors; grid_points > 0 reserves the grid t0 + k·grid_dt."""

@@ -274,3 +274,23 @@ def diffusion_bridge_problem(L, T, u, v, nchains=None, rng=None):
     if nchains is None:
         return xi0[0], th0[0], c
     return xi0, th0, c
+
+
+def bridge_point_condition(L, T, s, a):
+    """(p, n) of the hyperplane {ξ : X_s(ξ) = a} in the Faber-Schauder coefficients of level L on [0, T] (0 <= s < T): the bridge value
+    X_s = dotψ(ξ, s, L, T) (research/diffusion_bridge/faberschauder.jl:16-24, trace.faber_schauder_path) is linear in ξ, so n is its row -- the
+    two end-point weights and one hat per level, L + 3 entries -- and p = a·n/⟨n, n⟩ lies on the plane.  For trace.conditional_trace and the
+    device's consume_condition: the bridge forced through the point (s, a)."""
+    L = int(L)
+    if not 0 <= s < T:
+        raise ValueError("out of bounds")  # faberschauder.jl:17
+    d = (2 << L) + 1
+    sT = np.sqrt(T)
+    n = np.zeros(d)
+    n[-1] = s / sT
+    n[0] = sT * (1 - s / T)
+    for lev in range(L + 1):
+        p2 = float(1 << (L - lev))
+        j = int(np.floor(s / T * p2)) * (2 << lev) + (1 << lev)
+        n[j] += (sT * 0.5 - abs(np.fmod(s * p2, T) / sT - sT * 0.5)) / np.sqrt(p2)  # Λ(s, L − lev, T), :3-6
+    return a * n / (n @ n), n

@@ -34,20 +34,42 @@ def _consume_capacity(consume, trace, trace_capacity):
     """The trace capacity of a Bouncy Particle run: with consume=... the events are written to the device buffer even where trace=False."""
     if consume is None:
         return trace_capacity if trace else 0
-    if not isinstance(consume, dict) or set(consume) - {"dt", "points"}:
-        raise TypeError("consume=dict(dt=..., points=...)")
+    if not isinstance(consume, dict) or set(consume) - {"dt", "points", "condition", "hits"}:
+        raise TypeError("consume=dict(dt=..., points=...[, condition=(p, n), hits=K])")
     if trace_capacity <= 0:
         raise ValueError("consume=... reads the device trace buffer: trace_capacity must be positive")
     return trace_capacity
 
 
+def _condition_of(consume):
+    """(p, n, K) of consume=dict(..., condition=(p, n), hits=K) -- the conditional trace on the device, K rows reserved per chain -- or None."""
+    if consume is None or "condition" not in consume:
+        if consume is not None and "hits" in consume:
+            raise TypeError("consume=dict(hits=K) goes with condition=(p, n)")
+        return None
+    p, n = consume["condition"]
+    hits = int(consume.get("hits", 0))
+    if hits < 1:
+        raise ValueError("consume=dict(condition=(p, n), hits=K) reserves K >= 1 rows per chain")
+    return p, n, hits
+
+
+def _condition_result(out, conditioned, nchains):
+    """hit_t, hit_x (per chain: a chain has its own number of hits) and nhits [nchains] -- a value above hits=K: later hits were dropped"""
+    res = [conditioned(k) for k in range(nchains)]
+    out["hit_t"], out["hit_x"] = [r[0] for r in res], [r[1] for r in res]
+    out["nhits"] = np.array([r[2] for r in res], dtype=np.int64)
+
+
 def _consume_result(ens, consume, single, sticky):
-    """The extra element of a consume=... run: dict(mean, T, grid_t, grid_x[, inclusion]) from the device consumers; grid_t / grid_x are per
-    chain (a chain's grid ends before ITS last event), None without points."""
+    """The extra element of a consume=... run: dict(mean, T, grid_t, grid_x[, inclusion][, hit_t, hit_x, nhits]) from the device consumers;
+    grid_t / grid_x (and hit_t / hit_x) are per chain (a chain's grid ends before ITS last event), None without points."""
     mean, T = ens.bps_consume_mean()
     out = dict(mean=mean, T=T, grid_t=None, grid_x=None)
     if sticky:
         out["inclusion"] = ens.bps_consume_inclusion()[0]
+    if _condition_of(consume) is not None:
+        _condition_result(out, ens.bps_consume_conditioned, ens.nchains)
     if int(consume.get("points", 0)) > 0:
         grids = [ens.bps_consume_discretized(k) for k in range(ens.nchains)]
         out["grid_t"], out["grid_x"] = [g[0] for g in grids], [g[1] for g in grids]
@@ -78,7 +100,9 @@ def spdmp(target, t0, x0, θ0, T, c, *GF, factor=1.8, adapt=False, adaptscale=Fa
 
     consume=dict(dt=..., points=...) (DiffusionBridgeTarget; engine-only keyword): the device consumers (pdmp_ensemble_consume_*) run over
     every slice before its buffer is recycled and a fifth element is returned: dict(mean, T, grid_t, grid_x) -- trace.mean(Ξ), the last
-    event time and trace.discretize(Ξ, dt) on at most `points` rows (grid_t / grid_x None without points), per chain as in pdmp.
+    event time and trace.discretize(Ξ, dt) on at most `points` rows (grid_t / grid_x None without points), per chain as in pdmp.  With
+    condition=(p, n), hits=K in the dict it also holds hit_t, hit_x, nhits: trace.conditional_trace(Ξ, p, n), at most K rows per chain
+    (problems.bridge_point_condition gives the (p, n) of a bridge through a point).
 
     G: the neighbourhoods a proposal moves before its gradient is taken (:82,171-179) -- a sparse matrix whose column patterns are the
     G[i] (e.g. the target's Γ when the bounding F.Γ is sparser) or a sequence of index arrays; G[i] ⊇ G1[i] = pattern of F.Γ[:, i] is
@@ -172,7 +196,9 @@ def _pdmp_nd(target, t0, x0, θ0, T, c, F, *, factor=1.8, adapt=False, subsample
     grid_x) -- trace.mean(Ξ), the last event time, and trace.discretize(Ξ, dt) on a grid of at most `points` rows (ValueError if the run
     passes it; grid_t / grid_x are None without points), [n x ...] or squeezed for a single chain, the grids one array per chain.  The
     earlier elements are bit for bit those without the keyword.  With trace=False the events are still written to the device buffer and
-    consumed, but never copied to the host; trace_capacity=0 raises.
+    consumed, but never copied to the host; trace_capacity=0 raises.  With condition=(p, n), hits=K in the dict (event-recorded
+    BouncyParticle and its sticky form) the element also holds hit_t, hit_x -- trace.conditional_trace(Ξ, p, n), at most K rows per chain --
+    and nhits, the number of hits found (above K: the later ones were dropped).
 
     pdmp(dϕ, ∇ϕ!, t0, x0, θ0, T, c::LocalBound, B::BouncyParticle; oscn=false, adapt=false, factor=2.0) (src/not_fact_samplers.jl:336-384),
     the speed-recorded driver: B.Γ is None (BouncyParticle(None, None, λref, ρ, L=..., U=...)), target is a GaussianTarget or a
@@ -433,6 +459,8 @@ def _zigzag(sampler, target, t0, x0, θ0, T, c, F, factor, adapt, seed, device, 
         ens.set_state(t0, X0, TH0, c, seeds)
         if consume is not None:
             ens.consume_begin(float(consume.get("dt", 0.0)), int(consume.get("points", 0)))
+            if _condition_of(consume) is not None:
+                ens.consume_condition(*_condition_of(consume))
         events = [[] for _ in range(nch)]
         while True:
             ens.run(T, _lib.RUN_REFERENCE_TAIL)
@@ -454,6 +482,8 @@ def _zigzag(sampler, target, t0, x0, θ0, T, c, F, factor, adapt, seed, device, 
             if int(consume.get("points", 0)) > 0:
                 grids = [ens.consume_discretized(k) for k in range(nch)]
                 consumed["grid_t"], consumed["grid_x"] = [g[0] for g in grids], [g[1] for g in grids]
+            if _condition_of(consume) is not None:
+                _condition_result(consumed, ens.consume_conditioned, nch)
             if single:
                 consumed = {k: (v if v is None else v[0]) for k, v in consumed.items()}
         fs = ens.final_state()
@@ -516,6 +546,8 @@ def _bps_modern(target, t0, x0, θ0, T, c, B, factor, adapt, seed, device, trace
         ens.set_state_bps(t0, X0, TH0, c, seeds)
         if consume is not None:
             ens.bps_consume_begin(consume.get("dt", 0.0), consume.get("points", 0))
+            if _condition_of(consume) is not None:
+                ens.bps_consume_condition(*_condition_of(consume))
         if count:
             ens.set_bps_record_limit(int(T))
         T_end = float("inf") if count else float(T)
@@ -589,6 +621,8 @@ def _bps(t0, x0, θ0, T, c, B, factor, adapt, seed, device, trace_capacity, trac
         ens.set_state_bps(t0, X0, TH0, float(c), seeds)
         if consume is not None:
             ens.bps_consume_begin(consume.get("dt", 0.0), consume.get("points", 0))
+            if _condition_of(consume) is not None:
+                ens.bps_consume_condition(*_condition_of(consume))
         fs_ = [[] for _ in range(nch)]
         ts = [[] for _ in range(nch)]
         xs = [[] for _ in range(nch)]

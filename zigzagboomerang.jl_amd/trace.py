@@ -323,6 +323,121 @@ def inclusion_prob(tr: FactTrace):
     return np.bincount(i, weights=((xp != 0) | (ev["x"] != 0)) * dt / T, minlength=tr.x0.size)
 
 
+def _dot_wave64(A, B):
+    """Row-wise dot(A[r], B[r]) in the one order the device and the oracle sum in (dot_wave64, oracle/pdmp_oracle.c): lane l adds the
+    products of elements l, l + 64, ... in order, then the lanes are combined by the xor butterfly 1, 2, 4, 8, 16, 32."""
+    A, B = np.broadcast_arrays(np.atleast_2d(A), np.atleast_2d(B))
+    m, k = A.shape
+    ns = max((k + 63) // 64, 1)
+    P = np.zeros((m, ns * 64))
+    P[:, :k] = A * B
+    P = P.reshape(m, ns, 64)
+    part = np.zeros((m, 64))
+    for s in range(ns):
+        part = part + P[:, s]
+    lanes = np.arange(64)
+    for off in (1, 2, 4, 8, 16, 32):
+        part = part + part[:, lanes ^ off]
+    return part[:, 0]
+
+
+def _states_before(tr, times):
+    """x_j(times[r]) for every coordinate j from j's last event with t < times[r] (strictly), else from (t0, x0_j, θ0_j): [len(times) x d]."""
+    ev = tr.events
+    d = tr.x0.size
+    order, ptr = _groups(tr)
+    out = np.empty((len(times), d))
+    for j in range(d):
+        own = order[ptr[j]:ptr[j + 1]]
+        tl, xl, thl = tr.t0, tr.x0[j], tr.θ0[j]
+        if len(own):
+            pos = np.searchsorted(ev["t"][own], times, side="left") - 1
+            has = pos >= 0
+            k = own[np.maximum(pos, 0)]
+            tl = np.where(has, ev["t"][k], tr.t0)
+            xl = np.where(has, ev["x"][k], tr.x0[j])
+            thl = np.where(has, ev["theta"][k], tr.θ0[j])
+        out[:, j] = xl + thl * (times - tl)
+    return out
+
+
+def _conditional_fact(tr, p, n):
+    ev = tr.events
+    d = tr.x0.size
+    S = np.flatnonzero(n != 0)
+    if len(ev) == 0:
+        return np.empty(0), np.empty((0, d))
+    loc = np.full(d, -1, dtype=np.int64)
+    loc[S] = np.arange(len(S))
+    l = loc[ev["i"].astype(np.int64)]
+    sel = np.flatnonzero(l >= 0)  # the events of S; piece m opens at the (m − 1)-th of them (piece 0 at t0)
+    M = len(sel)
+    last = np.zeros((M + 1, len(S)), dtype=np.int64)  # per piece and list position: 1 + the latest event of S that set it, 0: the initial state
+    last[np.arange(1, M + 1), l[sel]] = np.arange(1, M + 1)
+    last = np.maximum.accumulate(last, axis=0)
+    has = last > 0
+    k = sel[np.maximum(last - 1, 0)] if M else np.zeros_like(last)
+    Tc = np.where(has, ev["t"][k], tr.t0)
+    Xc = np.where(has, ev["x"][k], tr.x0[S][None])
+    THc = np.where(has, ev["theta"][k], tr.θ0[S][None])
+    t_b = np.concatenate([[tr.t0], ev["t"][sel]])
+    xs = Xc + THc * (t_b[:, None] - Tc)
+    g = _dot_wave64(n[S][None], p[S][None] - xs)
+    h = _dot_wave64(n[S][None], THc)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        tau = g / h
+    s = t_b + tau
+    t_close = np.concatenate([ev["t"][sel], [ev["t"][-1]]])  # the next event of S (inclusive, src/condition.jl:42), else the last event of the trace
+    hit = (tau > 0) & (t_close >= s)
+    return s[hit], _states_before(tr, s[hit])
+
+
+def _conditional_pdmp(tr, p, n):
+    d = len(tr.x0)
+    t = np.asarray(tr.t, dtype=np.float64)
+    if len(t) == 0:
+        return np.empty(0), np.empty((0, d))
+    tc = np.concatenate([[tr.t0], t[:-1]])
+    Xc = np.vstack([np.asarray(tr.x0, dtype=np.float64)[None], np.asarray(tr.x, dtype=np.float64).reshape(-1, d)[:-1]])
+    THc = np.vstack([np.asarray(tr.θ0, dtype=np.float64)[None], np.asarray(tr.θ, dtype=np.float64).reshape(-1, d)[:-1]])
+    g = _dot_wave64(p[None] - Xc, n[None])
+    h = _dot_wave64(THc, n[None])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        tau = g / h
+        hit = (tau > 0) & (tc + tau < t)  # (strict, src/condition.jl:63)
+    rows = Xc[hit] + THc[hit] * tau[hit, None]
+    if tr.f is not None:  # smove_forward!(τ, t, x, θ, f, F) moves the free coordinates only (src/ss_not_fact.jl:78-86)
+        f0 = np.ones(d, dtype=bool) if tr.f0 is None else np.asarray(tr.f0, dtype=bool)
+        Fm = np.vstack([f0[None], np.asarray(tr.f, dtype=bool).reshape(-1, d)[:-1]])
+        rows = np.where(Fm[hit], rows, Xc[hit])
+    return (tc + tau)[hit], rows
+
+
+def conditional_trace(tr, p, n):
+    """collect(conditional_trace(Ξ, (p, n))) -- src/condition.jl: the points (t [m], X [m x d]) where the path crosses the hyperplane
+    {x : ⟨x − p, n⟩ = 0}, in closed form and with at most one hit per linear piece (DESIGN.md "Conditional trace" states the contract; the
+    reference moves the state to every hit and event and agrees to rounding, apart from crossings it emits twice).
+
+    FactTrace (time-ordered: no refresh clock): a piece runs between two events of the coordinates S = supp n; from the cursors of S as of its
+    start t_b, τ = Σ n_k (p_k − x_k(t_b)) / Σ n_k θ_k and s = t_b + τ; a hit iff τ > 0 and the next event of S, or else the last event of the
+    trace, lies at or after s.  The row is every coordinate's line from its last event strictly before s.
+    PDMPTrace: per event, from the state before it, τ = ⟨p − x, n⟩ / ⟨θ, n⟩; a hit iff τ > 0 and t + τ lies strictly before the event; frozen
+    coordinates of a sticky trace stay where they are.  Sums run in the 64-lane order of the device.  Boomerang flows: TypeError (the
+    reference's hittingtime has no method for them, src/condition.jl:18)."""
+    if isinstance(tr.F, (Boomerang, FactBoomerang)):
+        raise TypeError("conditional_trace: hittingtime has no method for the Boomerang flows (src/condition.jl:18)")
+    d = len(tr.x0)
+    p = np.ascontiguousarray(p, dtype=np.float64).reshape(-1)
+    n = np.ascontiguousarray(n, dtype=np.float64).reshape(-1)
+    if p.size != d or n.size != d:
+        raise ValueError("conditional_trace: p and n have the trace's dimension %d" % d)
+    if not (np.all(np.isfinite(p)) and np.all(np.isfinite(n)) and np.any(n != 0)):
+        raise ValueError("conditional_trace: p and n are finite and n is not zero")
+    if isinstance(tr, PDMPTrace):
+        return _conditional_pdmp(tr, p, n)
+    return _conditional_fact(tr, p, n)
+
+
 def faber_schauder_path(ξ, s, L, T):
     """dotψ(ξ, s, L, T) of research/diffusion_bridge/faberschauder.jl:16-24, vectorised: the bridge X_s of the Faber-Schauder coefficients ξ
     ([d] or [n x d], d = (2 << L) + 1, e.g. the rows of discretize(Ξ, dt)) at the times s (scalar or [m], 0 <= s < T).  Returns [m], or
