@@ -640,6 +640,40 @@ pdmp_status pdmp_ensemble_bps_consume_condition(pdmp_ensemble* ens, const double
 pdmp_status pdmp_ensemble_bps_consume_conditioned(pdmp_ensemble* ens, int64_t chain, int64_t first, int64_t count, double* t, double* x,
                                                   int64_t* nhits, void** rows_dev);
 
+/* ------------------------------------------------------------------ pair integrals on the device: covariance of a sampled path
+ *
+ * S_ij = ∫ (x_i − c_i)(x_j − c_j) dt and J_i = ∫ (x_i − c_i) dt, exactly, over a caller-given sparse set of pairs (the diagonal, the pattern of
+ * Γ, a dense block): cov_ij = S_ij / L − (J_i / L)(J_j / L) with L = T_last − t0, the quantity the reference's own acceptance test reads
+ * (test/maintest.jl: mean|cov(xs) − Γ⁻¹| < 2.5/√T).  Kept by the synchronous consumers above, slice by slice; raw integrals pool exactly over
+ * chains and ranks.  Plain double arithmetic, no fused multiply-add; tests/ref/pairs_ref.c states the contract sequentially and the device
+ * agrees with it bit for bit (DESIGN.md "Pair integrals").
+ *   A piece of the pair (i, j) over [s0, s1] with the states a = x_i(s0) − c_i, b = x_j(s0) − c_j, the velocities vi, vj and τ = s1 − s0 adds
+ *     τ·(a·b + τ·(0.5·(a·vj + b·vi) + τ·((vi·vj)/3.0))) to S_ij; a coordinate's own piece adds τ·(a + 0.5·(vi·τ)) to J_i.  τ is taken signed.
+ *   FactTrace (whatever consume_begin accepts).  Cursors of its own (t, x, θ, J per chain and coordinate, from (t0, x0, θ0, 0)).  An event
+ *     (t, i, x, θ), in trace order: for every listed pair (i, j), s0 = max(t_i, t_j), a = (x_i − c_i) + θ_i·(s0 − t_i), b likewise from j's
+ *     cursor, the piece [s0, t]; then J_i gets [t_i, t] and i's cursor becomes (t, x, θ).  A read closes every pair from max(t_i, t_j) and
+ *     every J_i from t_i to the chain's last consumed event time T_last, without touching the accumulators: a run can be read midway.
+ *   PDMPTrace (event-recorded BouncyParticle and its sticky form).  Per event (t_k, ...) with the cursor (t_c, x_c, θ_c, f_c) before it every
+ *     pair's piece is [t_c, t_k] with a = x_c,i − c_i, vi = f_c,i ? θ_c,i : 0.  Nothing is added behind the last event.
+ *   [bps_]consume_pairs(npairs, pi, pj, center)   after [bps_]consume_begin and before the first [bps_]consume: pairs 0-based, in any
+ *     orientation, stored in the given order; center [d] or NULL = 0.  Reserves [nchains x npairs] doubles (the factorised family also 32 bytes
+ *     of cursor per chain and coordinate, the Bouncy Particle family [nchains x d] for J).  Without this call nothing changes: no allocation,
+ *     no kernel.  Coexists with consume_condition and consume_cummean.  pdmp_ensemble_consume_async on such an ensemble: PDMP_ERR_UNSUPPORTED.
+ *   [bps_]consume_pair_integrals(chain_first, n, S, J, T_last, S_dev)   S [n x npairs], J [n x d] (every coordinate, listed or not), T_last [n]
+ *     of chains [chain_first, chain_first + n); *S_dev = the device array the S just read lie in ([n x npairs]); any output may be NULL.
+ * PDMP_ERR_INVALID: npairs < 1 or >= 2^30, a NULL list, an index outside [0, d), a pair listed twice (either orientation), a non-finite
+ * centre, accumulators beyond 256 GiB, before begin, after the first consume (a consume_async that handed a slice over counts), the other
+ * family's ensemble.
+ * PDMP_ERR_UNSUPPORTED: the Bouncy Particle family on a Boomerang flow (the product of two rotations is another integral), on the
+ * speed-recorded flow or with subsample (their records are not the corners of the path).
+ */
+pdmp_status pdmp_ensemble_consume_pairs(pdmp_ensemble* ens, int64_t npairs, const int64_t* pi, const int64_t* pj, const double* center);
+pdmp_status pdmp_ensemble_consume_pair_integrals(pdmp_ensemble* ens, int64_t chain_first, int64_t n, double* S, double* J, double* T_last,
+                                                 void** S_dev);
+pdmp_status pdmp_ensemble_bps_consume_pairs(pdmp_ensemble* ens, int64_t npairs, const int64_t* pi, const int64_t* pj, const double* center);
+pdmp_status pdmp_ensemble_bps_consume_pair_integrals(pdmp_ensemble* ens, int64_t chain_first, int64_t n, double* S, double* J, double* T_last,
+                                                     void** S_dev);
+
 /* what the ensemble was created with (any pointer may be NULL) */
 pdmp_status pdmp_ensemble_info(pdmp_ensemble* ens, int64_t* nchains, int64_t* d, int64_t* trace_capacity, int* device);
 

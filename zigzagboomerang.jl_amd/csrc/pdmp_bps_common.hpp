@@ -27,6 +27,13 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
     return (r0 + r1) + (r2 + r3);  // lane ^ 16, then lane ^ 32
 }
 
+// the pair consumers' piece (pdmp_consume.hip, pdmp_consume_bps.hip; tests/ref/pairs_ref.c states it): ∫_0^τ (a + vi u)(b + vj u) du and
+// ∫_0^τ (a + vi u) du in ONE grouping, symmetric in (i, j) bit for bit (every product and the one sum of two products commute)
+__device__ __forceinline__ double pair_piece(double a, double b, double vi, double vj, double tau) {
+    return tau * (a * b + tau * (0.5 * (a * vj + b * vi) + tau * ((vi * vj) / 3.0)));
+}
+__device__ __forceinline__ double line_piece(double a, double vi, double tau) { return tau * (a + 0.5 * (vi * tau)); }
+
 // draw indices a randn(rng, d) takes (BpsWave::normals): one Box-Muller block per two elements, whole 64-lane rows of blocks
 __device__ __forceinline__ uint64_t normal_draws(int64_t d) { return (uint64_t)(((d + 127) >> 7) << 6); }
 

@@ -266,6 +266,7 @@ pdmp_status init_state_bps(pdmp_ensemble* e, double t0, const double* x0, const 
     e->t0_state = t0;  // (pdmp_ensemble_bps_consume_begin's grid starts here)
     e->bc_on = false;
     e->bcn_on = false;
+    e->bpr_on = false;
     e->trace_appended = false;
     return PDMP_OK;
 }

@@ -58,6 +58,17 @@ static pdmp::BpsCondArgs cond_args(const pdmp_ensemble* e) {
     return q;
 }
 
+static pdmp::BpsPairArgs pair_args(const pdmp_ensemble* e) {
+    pdmp::BpsPairArgs q{};
+    q.pi = e->bpr_pi.p;
+    q.pj = e->bpr_pj.p;
+    q.center = e->bpr_c.p;
+    q.S = e->bpr_S.p;
+    q.J = e->bpr_J.p;
+    q.npairs = e->bpr_np;
+    return q;
+}
+
 // bps_consume_mean / _inclusion: one [n x d] read of the cursors of chains [chain_first, chain_first + n) and the chains' last event times
 static pdmp_status consume_read(pdmp_ensemble* e, int inclusion, int64_t chain_first, int64_t n, double* out, double* T_last, const char* who) {
     PDMP_TRY(need_begun(e, who));
@@ -99,6 +110,8 @@ pdmp_status pdmp_ensemble_bps_consume_begin(pdmp_ensemble* e, double grid_dt, in
     e->bc_cummean = false;
     e->bcn_on = e->bc_started = false;
     e->bcn_tau.release(), e->bcn_t.release(), e->bcn_x.release(), e->bcn_pn.release(), e->bcn_nh.release();
+    e->bpr_on = false;
+    e->bpr_pi.release(), e->bpr_pj.release(), e->bpr_c.release(), e->bpr_S.release(), e->bpr_J.release(), e->bpr_T.release();
     e->bc_dt = grid_dt;
     e->bc_K = grid_points;
     LAUNCH_TRY("bps_consume_init", pdmp::launch_bps_consume_init(consume_args(e), e->stream));
@@ -118,6 +131,8 @@ pdmp_status pdmp_ensemble_bps_consume(pdmp_ensemble* e) {
     HIP_TRY(hipEventRecord(e->ev_c0, e->stream));
     if (e->bcn_on)  // (before the consumer: it reads the cursors and the progress the consumer is about to advance)
         LAUNCH_TRY("bps_consume_condition", pdmp::launch_bps_cond(consume_args(e), cond_args(e), e->stream));
+    if (e->bpr_on)  // (before the consumer, like the condition: it reads the cursors and the progress the consumer is about to advance)
+        LAUNCH_TRY("bps_consume_pairs", pdmp::launch_bps_pairs(consume_args(e), pair_args(e), e->stream));
     LAUNCH_TRY("bps_consume", pdmp::launch_bps_consume_events(consume_args(e), e->stream));
     HIP_TRY(hipEventRecord(e->ev_c1, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
@@ -240,6 +255,60 @@ pdmp_status pdmp_ensemble_bps_consume_conditioned(pdmp_ensemble* e, int64_t chai
         *nhits = (int64_t)nh;
     }
     if (rows_dev) *rows_dev = e->bcn_x.p;
+    return PDMP_OK;
+}
+
+// pair integrals S_ij = ∫ (x_i − c_i)(x_j − c_j) dt, J_i = ∫ (x_i − c_i) dt of a PDMPTrace on the device (DESIGN.md "Pair integrals"): after bps_consume_begin
+// and before the first bps_consume; from then on bps_consume also adds every slice's pieces
+pdmp_status pdmp_ensemble_bps_consume_pairs(pdmp_ensemble* e, int64_t npairs, const int64_t* pi, const int64_t* pj, const double* center) {
+    PDMP_TRY(need_bps(e, __func__));
+    if (e->bps.flow_kind == 1)
+        return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_pairs: on a Boomerang flow the product of two rotations is another integral than that of two lines");
+    if (e->bps.modern)
+        return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_pairs: the records of the speed-recorded flow are not the corners of the path (a straight line "
+                                          "between two of them is not the path)");
+    if (e->bps.subsample)
+        return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_pairs: with subsample the records are not the corners of the path (a straight line between two of "
+                                          "them is not the path)");
+    PDMP_TRY(need_begun(e, __func__));
+    if (e->bc_started) return fail(PDMP_ERR_INVALID, "bps_consume_pairs precedes the first bps_consume (its first piece starts from t0, x0, θ0)");
+    const int64_t d = e->cfg.d, nch = e->cfg.nchains;
+    std::vector<int32_t> vi, vj;
+    std::vector<double> c;
+    PDMP_TRY(pairs_list("bps_consume_pairs", nch, d, npairs, pi, pj, center, &vi, &vj, &c));
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(device_sync(e));
+    e->bpr_on = false;
+    PDMP_TRY(e->bpr_pi.upload(vi));
+    PDMP_TRY(e->bpr_pj.upload(vj));
+    PDMP_TRY(e->bpr_c.upload(c));
+    PDMP_TRY(e->bpr_S.alloc((size_t)(nch * npairs)));
+    PDMP_TRY(e->bpr_J.alloc((size_t)(nch * d)));
+    PDMP_TRY(e->bpr_T.alloc((size_t)nch));
+    HIP_TRY(hipMemsetAsync(e->bpr_S.p, 0, (size_t)(nch * npairs) * sizeof(double), e->stream));
+    HIP_TRY(hipMemsetAsync(e->bpr_J.p, 0, (size_t)(nch * d) * sizeof(double), e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->bpr_np = npairs;
+    e->bpr_on = true;
+    return PDMP_OK;
+}
+
+pdmp_status pdmp_ensemble_bps_consume_pair_integrals(pdmp_ensemble* e, int64_t chain_first, int64_t n, double* S, double* J, double* T_last, void** S_dev) {
+    PDMP_TRY(need_bps(e, __func__));
+    if (!e->bc_on || !e->bpr_on) return fail(PDMP_ERR_INVALID, "bps_consume_pair_integrals: pdmp_ensemble_bps_consume_pairs first");
+    if (chain_first < 0 || n < 0 || chain_first + n > e->cfg.nchains) return fail(PDMP_ERR_INVALID, "bps_consume_pair_integrals: chain range");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(device_sync(e));
+    const int64_t d = e->cfg.d, np = e->bpr_np;
+    if (S_dev) *S_dev = e->bpr_S.p + chain_first * np;  // (nothing lies behind the last event: the accumulators are the integrals)
+    if (n == 0) return PDMP_OK;
+    if (S) HIP_TRY(hipMemcpy(S, e->bpr_S.p + chain_first * np, (size_t)(n * np) * sizeof(double), hipMemcpyDeviceToHost));
+    if (J) HIP_TRY(hipMemcpy(J, e->bpr_J.p + chain_first * d, (size_t)(n * d) * sizeof(double), hipMemcpyDeviceToHost));
+    if (T_last) {
+        LAUNCH_TRY("bps_consume_pair_integrals", pdmp::launch_bps_pairs_tlast(consume_args(e), chain_first, n, e->bpr_T.p, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        HIP_TRY(hipMemcpy(T_last, e->bpr_T.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    }
     return PDMP_OK;
 }
 }  // extern "C"

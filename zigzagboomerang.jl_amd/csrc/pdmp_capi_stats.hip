@@ -102,6 +102,55 @@ pdmp_status condition_rows_fit(const char* who, int64_t nchains, int64_t d, int6
     return PDMP_OK;
 }
 
+// what both families check of a pair list: npairs, the two index lists, no pair twice in either orientation, a finite centre, and that the
+// accumulators [nchains x npairs] fit the reservation a condition may make (checked before the list is read)
+pdmp_status pairs_list(const char* who, int64_t nchains, int64_t d, int64_t npairs, const int64_t* pi, const int64_t* pj, const double* center,
+                       std::vector<int32_t>* vi, std::vector<int32_t>* vj, std::vector<double>* c) {
+    if (npairs < 1) return fail(PDMP_ERR_INVALID, "%s: npairs = %lld must be at least 1", who, (long long)npairs);
+    if (!pi || !pj) return fail(PDMP_ERR_INVALID, "%s: null pair list", who);
+    const uint64_t per_pair = (uint64_t)nchains * sizeof(double);
+    if ((uint64_t)npairs > COND_MAX_ROW_BYTES / per_pair || npairs >= (int64_t)1 << 30)  // (slots, and the 2 npairs entries of the adjacency table, are 32-bit)
+        return fail(PDMP_ERR_INVALID, "%s: npairs = %lld entries of %llu bytes exceed the %llu GiB a condition may reserve", who, (long long)npairs,
+                    (unsigned long long)per_pair, (unsigned long long)(COND_MAX_ROW_BYTES >> 30));
+    c->assign((size_t)d, 0.0);
+    if (center)
+        for (int64_t j = 0; j < d; ++j) {
+            if (!std::isfinite(center[j])) return fail(PDMP_ERR_INVALID, "%s: the centre must be finite (entry %lld is not)", who, (long long)j);
+            (*c)[(size_t)j] = center[j];
+        }
+    vi->resize((size_t)npairs), vj->resize((size_t)npairs);
+    std::vector<uint64_t> key((size_t)npairs);
+    for (int64_t k = 0; k < npairs; ++k) {
+        if (pi[k] < 0 || pi[k] >= d || pj[k] < 0 || pj[k] >= d)
+            return fail(PDMP_ERR_INVALID, "%s: pair %lld = (%lld, %lld) has an index outside [0, %lld)", who, (long long)k, (long long)pi[k], (long long)pj[k],
+                        (long long)d);
+        (*vi)[(size_t)k] = (int32_t)pi[k];
+        (*vj)[(size_t)k] = (int32_t)pj[k];
+        const uint64_t lo = (uint64_t)std::min(pi[k], pj[k]), hi = (uint64_t)std::max(pi[k], pj[k]);
+        key[(size_t)k] = lo * (uint64_t)d + hi;
+    }
+    std::sort(key.begin(), key.end());
+    const auto dup = std::adjacent_find(key.begin(), key.end());
+    if (dup != key.end())
+        return fail(PDMP_ERR_INVALID, "%s: the pair (%llu, %llu) is listed twice (either orientation counts)", who, (unsigned long long)(*dup / (uint64_t)d),
+                    (unsigned long long)(*dup % (uint64_t)d));
+    return PDMP_OK;
+}
+
+static pdmp::PairArgs pair_args(const pdmp_ensemble* e) {
+    pdmp::PairArgs a{};
+    a.adj_ptr = e->d_pr_ptr.p;
+    a.adj = e->d_pr_adj.p;
+    a.pi = e->d_pr_pi.p;
+    a.pj = e->d_pr_pj.p;
+    a.center = e->d_pr_c.p;
+    a.cur = e->d_pr_cur.p;
+    a.meta = e->d_pr_meta.p;
+    a.S = e->d_pr_S.p;
+    a.npairs = e->pr_np;
+    return a;
+}
+
 extern "C" {
 
 pdmp_status pdmp_ensemble_batch_means(pdmp_ensemble* e, double T_prev, double T, double* sum_y, double* sum_y2) {
@@ -216,6 +265,9 @@ pdmp_status pdmp_ensemble_consume_begin(pdmp_ensemble* e, double grid_dt, int64_
     e->cn_on = e->cons_started = false;
     e->d_cn_cur.release(), e->d_cn_t.release(), e->d_cn_x.release(), e->d_cn_pn.release();
     e->d_cn_loc.release(), e->d_cn_idx.release(), e->d_cn_meta.release();
+    e->pr_on = false;
+    e->d_pr_ptr.release(), e->d_pr_pi.release(), e->d_pr_pj.release(), e->d_pr_adj.release(), e->d_pr_c.release(), e->d_pr_S.release();
+    e->d_pr_out.release(), e->d_pr_cur.release(), e->d_pr_meta.release();
     LAUNCH_TRY("consume_init", pdmp::launch_consume_init(e->d_rec.p, e->track ? 128 : 64, d, n, e->t0_state, e->d_ccur.p, e->cons_z, e->d_cmeta.p,
                                        grid_points > 0 ? e->d_cgrid.p : nullptr, grid_points, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
@@ -235,6 +287,8 @@ pdmp_status pdmp_ensemble_consume(pdmp_ensemble* e) {
         LAUNCH_TRY("consume_condition", pdmp::launch_cond_events(e->d_ev.p, e->cfg.trace_capacity, e->d_hdr.p, e->cfg.d, e->cfg.nchains, e->d_cn_loc.p, e->d_cn_idx.p,
                                                                  e->cn_nS, e->d_cn_pn.p, e->d_cn_cur.p, e->d_cn_meta.p, e->d_cn_t.p, e->d_cn_x.p, e->cn_max_hits,
                                                                  e->stream));
+    if (e->pr_on)  // (cursors of its own, like the condition's)
+        LAUNCH_TRY("consume_pairs", pdmp::launch_pair_events(e->d_ev.p, e->cfg.trace_capacity, e->d_hdr.p, e->cfg.d, e->cfg.nchains, pair_args(e), e->stream));
     LAUNCH_TRY("consume", pdmp::launch_consume_events(e->d_ev.p, e->cfg.trace_capacity, e->d_hdr.p, nullptr, e->cfg.d, e->cfg.nchains, e->d_ccur.p, e->cons_z, e->d_cmeta.p,
                                          e->d_cgrid.p, e->cons_K, e->t0_state, e->cons_dt, e->stream, e->cons_cummean ? e->d_ccm.p : nullptr));
     HIP_TRY(hipStreamSynchronize(e->stream));
@@ -315,6 +369,9 @@ pdmp_status pdmp_ensemble_consume_async(pdmp_ensemble* e, void* stream) {
     if (!e->consuming || !e->has_state) return fail(PDMP_ERR_INVALID, "pdmp_ensemble_consume_begin first");
     if (e->cn_on)
         return fail(PDMP_ERR_UNSUPPORTED, "consume_async: the conditional trace (pdmp_ensemble_consume_condition) is served by the synchronous consumer, "
+                                          "pdmp_ensemble_consume");
+    if (e->pr_on)
+        return fail(PDMP_ERR_UNSUPPORTED, "consume_async: the pair integrals (pdmp_ensemble_consume_pairs) are served by the synchronous consumer, "
                                           "pdmp_ensemble_consume");
     HIP_TRY(hipSetDevice(e->cfg.device));
     hipStream_t s = stream ? (hipStream_t)stream : e->stream;
@@ -476,6 +533,71 @@ pdmp_status pdmp_ensemble_consume_conditioned(pdmp_ensemble* e, int64_t chain, i
         *nhits = (int64_t)nh;
     }
     if (rows_dev) *rows_dev = e->d_cn_x.p;
+    return PDMP_OK;
+}
+
+// pair integrals S_ij = ∫ (x_i − c_i)(x_j − c_j) dt, J_i = ∫ (x_i − c_i) dt on the device (DESIGN.md "Pair integrals"): after consume_begin and before the
+// first consume
+pdmp_status pdmp_ensemble_consume_pairs(pdmp_ensemble* e, int64_t npairs, const int64_t* pi, const int64_t* pj, const double* center) {
+    if (!e) return fail(PDMP_ERR_INVALID, "null argument");
+    NEED_FACTORISED(e);
+    if (!e->consuming || !e->has_state) return fail(PDMP_ERR_INVALID, "consume_pairs: pdmp_ensemble_consume_begin first");
+    if (e->cons_started) return fail(PDMP_ERR_INVALID, "consume_pairs precedes the first consume (its cursors start from t0, x0, θ0)");
+    const int64_t d = e->cfg.d, nch = e->cfg.nchains;
+    std::vector<int32_t> vi, vj;
+    std::vector<double> c;
+    PDMP_TRY(pairs_list("consume_pairs", nch, d, npairs, pi, pj, center, &vi, &vj, &c));
+    // coordinate -> (partner, slot): every pair under both of its coordinates, (i, i) once; a row keeps the order of the list
+    std::vector<int32_t> ptr((size_t)d + 1, 0);
+    for (int64_t k = 0; k < npairs; ++k) {
+        ptr[(size_t)vi[k] + 1] += 1;
+        if (vj[k] != vi[k]) ptr[(size_t)vj[k] + 1] += 1;
+    }
+    for (int64_t j = 0; j < d; ++j) ptr[(size_t)j + 1] += ptr[(size_t)j];
+    std::vector<pdmp::PairAdj> adj((size_t)ptr[(size_t)d]);
+    std::vector<int32_t> fill(ptr.begin(), ptr.end() - 1);
+    for (int64_t k = 0; k < npairs; ++k) {
+        adj[(size_t)fill[(size_t)vi[k]]++] = pdmp::PairAdj{vj[k], (int32_t)k};
+        if (vj[k] != vi[k]) adj[(size_t)fill[(size_t)vj[k]]++] = pdmp::PairAdj{vi[k], (int32_t)k};
+    }
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(device_sync(e));
+    e->pr_on = false;
+    PDMP_TRY(e->d_pr_ptr.upload(ptr));
+    PDMP_TRY(e->d_pr_adj.upload(adj));
+    PDMP_TRY(e->d_pr_pi.upload(vi));
+    PDMP_TRY(e->d_pr_pj.upload(vj));
+    PDMP_TRY(e->d_pr_c.upload(c));
+    PDMP_TRY(e->d_pr_cur.alloc((size_t)(nch * d) * pdmp::pair_cursor_bytes()));
+    PDMP_TRY(e->d_pr_meta.alloc((size_t)nch * pdmp::pair_meta_bytes()));
+    PDMP_TRY(e->d_pr_S.alloc((size_t)(nch * npairs)));
+    e->d_pr_out.release();
+    e->pr_np = npairs;
+    HIP_TRY(hipMemsetAsync(e->d_pr_S.p, 0, (size_t)(nch * npairs) * sizeof(double), e->stream));
+    LAUNCH_TRY("consume_pairs_init", pdmp::launch_pair_init(e->d_ccur.p, d, nch, e->t0_state, pair_args(e), e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->pr_on = true;
+    return PDMP_OK;
+}
+
+pdmp_status pdmp_ensemble_consume_pair_integrals(pdmp_ensemble* e, int64_t chain_first, int64_t n, double* S, double* J, double* T_last, void** S_dev) {
+    if (!e) return fail(PDMP_ERR_INVALID, "null argument");
+    NEED_FACTORISED(e);
+    if (!e->consuming || !e->pr_on) return fail(PDMP_ERR_INVALID, "consume_pair_integrals: pdmp_ensemble_consume_pairs first");
+    if (chain_first < 0 || n < 0 || chain_first + n > e->cfg.nchains) return fail(PDMP_ERR_INVALID, "consume_pair_integrals: chain range");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(device_sync(e));
+    const int64_t d = e->cfg.d, np = e->pr_np;
+    const size_t need = (size_t)(n * (np + d + 1));
+    if (e->d_pr_out.n < need) PDMP_TRY(e->d_pr_out.alloc(need));
+    if (S_dev) *S_dev = e->d_pr_out.p;
+    if (n == 0) return PDMP_OK;
+    double *oS = e->d_pr_out.p, *oJ = oS + n * np, *oT = oJ + n * d;
+    LAUNCH_TRY("consume_pair_integrals", pdmp::launch_pair_read(d, pair_args(e), chain_first, n, oS, oJ, oT, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (S) HIP_TRY(hipMemcpy(S, oS, (size_t)(n * np) * sizeof(double), hipMemcpyDeviceToHost));
+    if (J) HIP_TRY(hipMemcpy(J, oJ, (size_t)(n * d) * sizeof(double), hipMemcpyDeviceToHost));
+    if (T_last) HIP_TRY(hipMemcpy(T_last, oT, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
     return PDMP_OK;
 }
 

@@ -571,4 +571,222 @@ int launch_cond_events(const pdmp_event* ev, int64_t cap, const DevChain* hdr, i
     return (int)hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------ pair integrals (covariance of a FactTrace)
+//
+// S_ij = ∫ (x_i − c_i)(x_j − c_j) dt and J_i = ∫ (x_i − c_i) dt over a caller-given set of pairs, exactly, slice by slice (DESIGN.md "Pair
+// integrals" has the contract; tests/ref/pairs_ref.c states it sequentially).  Coordinates have clocks of their own, so the integrand of a pair is
+// a product of two lines whose pieces end at the events of EITHER coordinate: an event (t, i, x, θ) closes, for every listed partner j of i, the
+// piece [max(t_i, t_j), t] from the two cursors, then J_i gets [t_i, t] and i's cursor becomes (t, x, θ).  The cursors are the consumer's own
+// (t, x, θ, J: 32 bytes per chain and coordinate); those of consume_events_kernel are read once, by the init.
+//   pair_events_kernel  one wavefront per chain walks the slice in order.  64 records at a time are loaded one per lane, with the adjacency row
+//     of their coordinate (adj_ptr; adj = (partner, slot of S), every pair under both of its coordinates, (i, i) once), and handed round by
+//     readlane.  For an event of i lane l takes the l-th partner: j's cursor, c_j and S[slot] are gathered, the piece added and stored; rows
+//     longer than 64 go round in strides of 64; lane 0 then writes J_i and i's cursor.  Every lane has read i's old cursor by then: its load
+//     precedes the store in the order of the one wavefront.
+//   The walk is a chain of dependent round trips, so the gather of the NEXT event is issued before the arithmetic of the current one -- unless
+//     the two conflict: the same coordinate, or partners (the next coordinate is in the row held by the lanes: one ballot; a row longer than 64
+//     counts as a conflict).  Then the gather waits for the stores (s_waitcnt vmcnt(0): the workgroup is ONE wavefront, for which
+//     __threadfence_block() compiles to nothing).  Between events that do not conflict nothing is shared.  An event two or more back that
+//     wrote what this gather reads (A, B, A) is ordered by the wavefront itself: its vector memory operations execute in issue order.
+//     The adjacency entry of a lane is loaded TWO events ahead (read-only), so a gather is one round trip.
+//   pair_read_kernel  closes every pair from max(t_i, t_j) and every J_i from t_i to the chain's last consumed event time, in registers: the
+//     accumulators are not touched and the run can go on.
+struct PairCursor {
+    double t, x, th, J;  // clock, position, velocity after the coordinate's last consumed event; ∫ (x_i − c_i) dt up to t
+};
+static_assert(sizeof(PairCursor) == 32, "a cursor never straddles a 128-byte line");
+struct PairMeta {
+    uint64_t consumed;  // events of this chain consumed so far (global event index)
+    double t_last;      // time of the last of them (t0 before the first)
+};
+size_t pair_cursor_bytes() { return sizeof(PairCursor); }
+size_t pair_meta_bytes() { return sizeof(PairMeta); }
+
+__global__ __launch_bounds__(256) void pair_init_kernel(const ConsumeCursor* __restrict__ cur, int64_t d, int64_t nchains, double t0, PairCursor* pc,
+                                                        PairMeta* meta) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k < nchains) {
+        PairMeta m;
+        m.consumed = 0;
+        m.t_last = t0;
+        meta[k] = m;
+    }
+    if (k >= nchains * d) return;
+    const ConsumeCursor c = cur[k];  // (before the first consume: t0, x0, θ0)
+    PairCursor p;
+    p.t = c.t;
+    p.x = c.x;
+    p.th = c.th;
+    p.J = 0.0;
+    pc[k] = p;
+}
+
+struct PairGather {  // what a lane holds of its partner of an event's coordinate i
+    double ti, xi, thi;      // i's cursor
+    double tj, xj, thj, cj;  // the partner's, and its centre
+    double s;                // S[slot]
+    int32_t j, slot;         // slot < 0: the row has no partner for this lane
+};
+
+// the lane's entry of an adjacency row [p0, p1): read-only data, loaded ahead of the gather that needs it (slot < 0: no partner for this lane)
+__device__ __forceinline__ PairAdj pair_adj(const PairArgs& A, int32_t p, int32_t p1) {
+    PairAdj a;
+    a.j = a.slot = -1;
+    if (p < p1) a = A.adj[p];
+    return a;
+}
+
+__device__ __forceinline__ PairGather pair_gather(const PairArgs& A, const PairCursor* cur, const double* S, int32_t i, PairAdj a) {
+    PairGather g;
+    g.ti = cur[i].t;
+    g.xi = cur[i].x;
+    g.thi = cur[i].th;
+    g.tj = g.xj = g.thj = g.cj = g.s = 0.0;
+    g.j = a.j;
+    g.slot = a.slot;
+    if (a.slot >= 0) {
+        g.tj = cur[a.j].t;
+        g.xj = cur[a.j].x;
+        g.thj = cur[a.j].th;
+        g.cj = A.center[a.j];
+        g.s = S[a.slot];
+    }
+    return g;
+}
+
+// one wavefront: every store it issued has reached memory before a load behind this point is issued (vmcnt counts stores on gfx9)
+__device__ __forceinline__ void pair_wait_stores() {
+    __builtin_amdgcn_s_waitcnt(0);  // vmcnt(0) expcnt(0) lgkmcnt(0)
+    asm volatile("" ::: "memory");
+}
+
+// the piece of a pair from its two cursors to time t (the arithmetic of ref_pairs_fact, in its order)
+__device__ __forceinline__ double pair_close(double ti, double xi, double thi, double ci, double tj, double xj, double thj, double cj, double t) {
+    const double s0 = ti > tj ? ti : tj;
+    const double a = (xi - ci) + thi * (s0 - ti);
+    const double b = (xj - cj) + thj * (s0 - tj);
+    return pair_piece(a, b, thi, thj, t - s0);
+}
+
+__global__ __launch_bounds__(64) void pair_events_kernel(const pdmp_event* ev0, int64_t cap, const DevChain* hdr, int64_t d, PairArgs A) {
+    const int64_t chain = blockIdx.x;
+    const int lane = threadIdx.x;
+    PairMeta* const meta = static_cast<PairMeta*>(A.meta) + chain;
+    const uint64_t ntrace = hdr[chain].c.ntrace, nevents = hdr[chain].c.nevents;
+    const uint64_t n = ntrace < (uint64_t)cap ? ntrace : (uint64_t)cap;
+    const uint64_t consumed = meta->consumed;
+    const uint64_t first_global = nevents - ntrace;  // global index of buffer slot 0
+    const uint64_t pos0 = (consumed > first_global) ? (consumed - first_global) : 0;  // first unconsumed slot
+    if (pos0 >= n) return;
+    const pdmp_event* const ev = ev0 + chain * cap;
+    PairCursor* const cur = static_cast<PairCursor*>(A.cur) + chain * d;
+    double* const S = A.S + chain * A.npairs;
+    for (uint64_t base = pos0; base < n; base += 64) {
+        const int cnt = (n - base < 64) ? (int)(n - base) : 64;
+        // this lane's record of the chunk and the adjacency row of its coordinate (read-only data: nothing in flight conflicts with it)
+        double rt = 0.0, rx = 0.0, rth = 0.0;
+        int32_t ri = -1, rp0 = 0, rp1 = 0;
+        if (lane < cnt) {
+            const pdmp_event r = ev[base + (uint64_t)lane];
+            rt = r.t;
+            rx = r.x;
+            rth = r.theta;
+            if ((uint64_t)r.i < (uint64_t)d) {
+                ri = (int32_t)r.i;
+                rp0 = A.adj_ptr[ri];
+                rp1 = A.adj_ptr[ri + 1];
+            }
+        }
+        pair_wait_stores();  // (the stores of the chunk before)
+        int32_t i = (int32_t)readlane_u32((uint32_t)ri, 0), p0 = (int32_t)readlane_u32((uint32_t)rp0, 0), p1 = (int32_t)readlane_u32((uint32_t)rp1, 0);
+        const int q1 = cnt > 1 ? 1 : 0;
+        PairAdj an = pair_adj(A, (int32_t)readlane_u32((uint32_t)rp0, q1) + lane, (int32_t)readlane_u32((uint32_t)rp1, q1));  // event 1's entry
+        PairGather g{};
+        g.slot = -1;
+        if (i >= 0) g = pair_gather(A, cur, S, i, pair_adj(A, p0 + lane, p1));
+        for (int q = 0; q < cnt; ++q) {
+            const double t = readlane_f64(rt, q), x = readlane_f64(rx, q), th = readlane_f64(rth, q);
+            const bool have_next = q + 1 < cnt;
+            const int qn = have_next ? q + 1 : q, qnn = q + 2 < cnt ? q + 2 : q;
+            const int32_t in = have_next ? (int32_t)readlane_u32((uint32_t)ri, qn) : -1;
+            const int32_t np0 = (int32_t)readlane_u32((uint32_t)rp0, qn), np1 = (int32_t)readlane_u32((uint32_t)rp1, qn);
+            // the adjacency entry of the event after the next: two events ahead, so the next gather is ONE round trip, not two
+            const PairAdj ann = pair_adj(A, (int32_t)readlane_u32((uint32_t)rp0, qnn) + lane, (int32_t)readlane_u32((uint32_t)rp1, qnn));
+            // the next event conflicts with this one if it has the same coordinate or its coordinate is one of this one's partners
+            const bool conflict = in == i || p1 - p0 > 64 || __any(g.slot >= 0 && g.j == in) != 0;
+            PairGather gn{};
+            gn.slot = -1;
+            if (in >= 0 && !conflict) gn = pair_gather(A, cur, S, in, an);
+            if (i >= 0) {
+                const double ci = A.center[i];
+                if (g.slot >= 0) S[g.slot] = g.s + pair_close(g.ti, g.xi, g.thi, ci, g.tj, g.xj, g.thj, g.cj, t);
+                for (int32_t p = p0 + 64; p < p1; p += 64) {  // rows longer than a wavefront: the slots of a row are distinct, nothing to order
+                    const PairGather h = pair_gather(A, cur, S, i, pair_adj(A, p + lane, p1));
+                    if (h.slot >= 0) S[h.slot] = h.s + pair_close(h.ti, h.xi, h.thi, ci, h.tj, h.xj, h.thj, h.cj, t);
+                }
+                if (lane == 0) {  // (every lane's load of i's old cursor was issued before this store)
+                    PairCursor c;
+                    c.J = cur[i].J + line_piece(g.xi - ci, g.thi, t - g.ti);
+                    c.t = t;
+                    c.x = x;
+                    c.th = th;
+                    cur[i] = c;
+                }
+            }
+            if (in >= 0 && conflict) {
+                pair_wait_stores();  // the cursor and the S slots just written, before they are read again
+                gn = pair_gather(A, cur, S, in, an);
+            }
+            g = gn;
+            an = ann;
+            i = in;
+            p0 = np0;
+            p1 = np1;
+        }
+    }
+    if (lane == 0) {
+        PairMeta m;
+        m.consumed = nevents;
+        m.t_last = ev[n - 1].t;
+        *meta = m;
+    }
+}
+
+// S [n x npairs], J [n x d] and T_last [n] of chains [chain_first, chain_first + n), every open piece closed at T_last in registers
+__global__ __launch_bounds__(256) void pair_read_kernel(int64_t d, PairArgs A, int64_t chain_first, int64_t n, double* S_out, double* J_out, double* T_out) {
+    const int64_t per = A.npairs > d ? A.npairs : d;
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= n * per) return;
+    const int64_t q = k / per, r = k - q * per;
+    const int64_t chain = chain_first + q;
+    const PairCursor* const cur = static_cast<const PairCursor*>(A.cur) + chain * d;
+    const double T = static_cast<const PairMeta*>(A.meta)[chain].t_last;
+    if (r < A.npairs) {
+        const int32_t i = A.pi[r], j = A.pj[r];
+        const PairCursor a = cur[i], b = cur[j];
+        S_out[q * A.npairs + r] = A.S[chain * A.npairs + r] + pair_close(a.t, a.x, a.th, A.center[i], b.t, b.x, b.th, A.center[j], T);
+    }
+    if (r < d) {
+        const PairCursor a = cur[r];
+        J_out[q * d + r] = a.J + line_piece(a.x - A.center[r], a.th, T - a.t);
+    }
+    if (r == 0) T_out[q] = T;
+}
+
+int launch_pair_init(const void* cur, int64_t d, int64_t nchains, double t0, const PairArgs& a, void* stream) {
+    const int64_t n = nchains * d;
+    hipLaunchKernelGGL(pair_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, static_cast<const ConsumeCursor*>(cur), d, nchains,
+                       t0, static_cast<PairCursor*>(a.cur), static_cast<PairMeta*>(a.meta));
+    return (int)hipGetLastError();
+}
+int launch_pair_events(const pdmp_event* ev, int64_t cap, const DevChain* hdr, int64_t d, int64_t nchains, const PairArgs& a, void* stream) {
+    hipLaunchKernelGGL(pair_events_kernel, dim3((unsigned)nchains), dim3(64), 0, (hipStream_t)stream, ev, cap, hdr, d, a);
+    return (int)hipGetLastError();
+}
+int launch_pair_read(int64_t d, const PairArgs& a, int64_t chain_first, int64_t n, double* S_out, double* J_out, double* T_out, void* stream) {
+    const int64_t tot = n * (a.npairs > d ? a.npairs : d);
+    hipLaunchKernelGGL(pair_read_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d, a, chain_first, n, S_out, J_out, T_out);
+    return (int)hipGetLastError();
+}
+
 }  // namespace pdmp

@@ -303,4 +303,100 @@ int launch_bps_cond(const BpsConsumeArgs& p, const BpsCondArgs& q, void* stream)
     return (int)hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------ pair integrals (covariance of a PDMPTrace)
+//
+// S_ij = ∫ (x_i − c_i)(x_j − c_j) dt over a caller-given set of pairs and J_i = ∫ (x_i − c_i) dt for every coordinate, over [t0, T_last] exactly
+// (DESIGN.md "Pair integrals"; tests/ref/pairs_ref.c states the contract).  An event replaces the whole state, so every pair's piece of an event
+// (t_k, ...) runs over [t_c, t_k] from the cursor before it: a = x_c,i − c_i, v_i = f_c,i ? θ_c,i : 0 (a coordinate that is not free keeps x).
+// One thread per (chain, pair) walks the chain's segment with S in a register; behind the pairs of a chain one thread per coordinate keeps J in the
+// same way (so a coordinate in no pair has its J).  The threads of a workgroup belong to one chain: the event times are wave-uniform loads, the
+// positions and velocities gathers of the pair's two columns; the loads of the next BC_AHEAD events are issued before the arithmetic of the
+// current ones, as in bps_consume_kernel.  Runs BEFORE bps_consume_kernel of the same slice and only reads what that kernel carries.
+struct BpsPairEvent {
+    double t, xi, thi, xj, thj;
+    bool fi, fj;
+};
+
+template <bool STICKY>
+__device__ __forceinline__ BpsPairEvent bp_load(const BpsConsumeArgs& P, int64_t slot0, uint64_t e, uint64_t n, int64_t i, int64_t j) {
+    const int64_t s = slot0 + (int64_t)(e < n ? e : n - 1);  // (behind the segment: its last event once more, never applied)
+    BpsPairEvent ev;
+    ev.t = P.ev_t[s];
+    ev.xi = P.ev_x[s * P.d + i];
+    ev.thi = P.ev_th[s * P.d + i];
+    ev.fi = STICKY ? ((P.ev_f[s * BPS_STICKY_WORDS + (i >> 6)] >> (i & 63)) & 1ull) != 0 : true;
+    if (j == i) {  // (a diagonal pair, or a J thread: one column)
+        ev.xj = ev.xi;
+        ev.thj = ev.thi;
+        ev.fj = ev.fi;
+        return ev;
+    }
+    ev.xj = P.ev_x[s * P.d + j];
+    ev.thj = P.ev_th[s * P.d + j];
+    ev.fj = STICKY ? ((P.ev_f[s * BPS_STICKY_WORDS + (j >> 6)] >> (j & 63)) & 1ull) != 0 : true;
+    return ev;
+}
+
+template <bool STICKY>
+__global__ __launch_bounds__(256) void bps_pairs_kernel(BpsConsumeArgs P, BpsPairArgs Q, int64_t blocks_per_chain) {
+    const int64_t chain = (int64_t)blockIdx.x / blocks_per_chain;
+    const int64_t r = ((int64_t)blockIdx.x - chain * blocks_per_chain) * 256 + threadIdx.x;
+    const int64_t d = P.d;
+    if (r >= Q.npairs + d) return;
+    const BpsCondSlice sl = bps_cond_slice(P, chain);
+    if (sl.pos >= sl.n) return;
+    const bool is_pair = r < Q.npairs;
+    const int64_t i = is_pair ? Q.pi[r] : r - Q.npairs, j = is_pair ? Q.pj[r] : i;
+    double* const acc_at = is_pair ? Q.S + chain * Q.npairs + r : Q.J + chain * d + i;
+    const BpsConsumeMeta* const meta = static_cast<const BpsConsumeMeta*>(P.meta) + chain * P.nstrips;
+    const int64_t slot0 = chain * P.cap;
+    const double ci = Q.center[i], cj = Q.center[j];
+    double acc = *acc_at, t_cur = sl.t_cur;
+    double xi = P.cx[chain * d + i], thi = P.cth[chain * d + i], xj = P.cx[chain * d + j], thj = P.cth[chain * d + j];
+    bool fi = STICKY ? ((meta[i >> 6].free >> (i & 63)) & 1ull) != 0 : true, fj = STICKY ? ((meta[j >> 6].free >> (j & 63)) & 1ull) != 0 : true;
+
+    BpsPairEvent now[BC_AHEAD], next[BC_AHEAD];
+#pragma unroll
+    for (int q = 0; q < BC_AHEAD; ++q) now[q] = bp_load<STICKY>(P, slot0, sl.pos + q, sl.n, i, j);
+    for (uint64_t base = sl.pos; base < sl.n; base += BC_AHEAD) {
+#pragma unroll
+        for (int q = 0; q < BC_AHEAD; ++q) next[q] = bp_load<STICKY>(P, slot0, base + BC_AHEAD + q, sl.n, i, j);
+#pragma unroll
+        for (int q = 0; q < BC_AHEAD; ++q) {
+            if (base + q >= sl.n) break;
+            const double tau = now[q].t - t_cur;
+            const double vi = fi ? thi : 0.0, vj = fj ? thj : 0.0;
+            acc = acc + (is_pair ? pair_piece(xi - ci, xj - cj, vi, vj, tau) : line_piece(xi - ci, vi, tau));
+            xi = now[q].xi;
+            thi = now[q].thi;
+            xj = now[q].xj;
+            thj = now[q].thj;
+            fi = now[q].fi;
+            fj = now[q].fj;
+            t_cur = now[q].t;
+        }
+#pragma unroll
+        for (int q = 0; q < BC_AHEAD; ++q) now[q] = next[q];
+    }
+    *acc_at = acc;
+}
+
+__global__ __launch_bounds__(256) void bps_pairs_tlast_kernel(BpsConsumeArgs P, int64_t chain_first, int64_t n, double* T_out) {
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (q < n) T_out[q] = static_cast<const BpsConsumeMeta*>(P.meta)[(chain_first + q) * P.nstrips].t_last;
+}
+
+int launch_bps_pairs(const BpsConsumeArgs& p, const BpsPairArgs& q, void* stream) {
+    const int64_t bpc = (q.npairs + p.d + 255) / 256;
+    const dim3 grid((unsigned)(p.nchains * bpc)), block(256);
+    if (p.ev_f) hipLaunchKernelGGL((bps_pairs_kernel<true>), grid, block, 0, (hipStream_t)stream, p, q, bpc);
+    else hipLaunchKernelGGL((bps_pairs_kernel<false>), grid, block, 0, (hipStream_t)stream, p, q, bpc);
+    return (int)hipGetLastError();
+}
+
+int launch_bps_pairs_tlast(const BpsConsumeArgs& p, int64_t chain_first, int64_t n, double* T_out, void* stream) {
+    hipLaunchKernelGGL(bps_pairs_tlast_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, chain_first, n, T_out);
+    return (int)hipGetLastError();
+}
+
 }  // namespace pdmp

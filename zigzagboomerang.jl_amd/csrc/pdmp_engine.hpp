@@ -550,6 +550,26 @@ size_t cond_meta_bytes();
 int launch_cond_init(const void* cur, int64_t d, int64_t nchains, double t0, double* ccur, void* meta, void* stream);
 int launch_cond_events(const pdmp_event* ev, int64_t cap, const DevChain* hdr, int64_t d, int64_t nchains, const int32_t* loc, const int32_t* idx, int nS,
                        const double* pn, double* ccur, void* meta, double* hit_t, double* hit_x, int64_t max_hits, void* stream);
+// ... the pair integrals (pdmp_ensemble_consume_pairs): the pair list (pi, pj) [npairs], its adjacency table (adj_ptr [d + 1]; adj = (partner, slot of
+// S), every pair under both of its coordinates, (i, i) once), the centre [d], cursors of its own (32 bytes per chain and coordinate), per-chain progress
+// and the accumulators S [nchains x npairs]
+struct PairAdj {
+    int32_t j, slot;
+};
+struct PairArgs {
+    const int32_t* adj_ptr;
+    const PairAdj* adj;
+    const int32_t *pi, *pj;
+    const double* center;
+    void *cur, *meta;
+    double* S;
+    int64_t npairs;
+};
+size_t pair_cursor_bytes();
+size_t pair_meta_bytes();
+int launch_pair_init(const void* cur, int64_t d, int64_t nchains, double t0, const PairArgs& a, void* stream);
+int launch_pair_events(const pdmp_event* ev, int64_t cap, const DevChain* hdr, int64_t d, int64_t nchains, const PairArgs& a, void* stream);
+int launch_pair_read(int64_t d, const PairArgs& a, int64_t chain_first, int64_t n, double* S_out, double* J_out, double* T_out, void* stream);
 int launch_math_probe(uint64_t seed, int64_t n, double* out, void* stream);
 // pdmp_consume_bps.hip: the streaming consumers of the Bouncy Particle family's trace buffers.  One block of pointers and numbers for its three
 // kernels: the trace (ev_f: a sticky ensemble's masks, else nullptr), the chain headers, the Boomerang's centre (nullptr: linear flow), the state
@@ -580,6 +600,16 @@ struct BpsCondArgs {
     int64_t max_hits;
 };
 int launch_bps_cond(const BpsConsumeArgs& p, const BpsCondArgs& q, void* stream);
+// ... the pair integrals (pdmp_ensemble_bps_consume_pairs): the pair list, the centre [d], S [nchains x npairs] and J [nchains x d]; launched before
+// launch_bps_consume_events of the same slice
+struct BpsPairArgs {
+    const int32_t *pi, *pj;
+    const double* center;
+    double *S, *J;
+    int64_t npairs;
+};
+int launch_bps_pairs(const BpsConsumeArgs& p, const BpsPairArgs& q, void* stream);
+int launch_bps_pairs_tlast(const BpsConsumeArgs& p, int64_t chain_first, int64_t n, double* T_out, void* stream);
 
 #ifdef PDMP_EXTRA_KERNELS
 // pdmp_debug_math_eval (include/pdmp_debug.h, parity library only): a translation unit that calls the shared scalar functions of pdmp_device.hpp

@@ -223,6 +223,15 @@ struct pdmp_ensemble {
     bool cons_started = false;  // a consume / consume_async happened since consume_begin
     int cn_nS = 0;
     int64_t cn_max_hits = 0;
+    // pdmp_ensemble_consume_pairs: the pair list, its adjacency table (coordinate -> (partner, slot of S)), the centre [d], the pair consumer's own
+    // cursors (t, x, θ, J) [nchains x d] and progress, the accumulators S [nchains x npairs]; pr_out: what consume_pair_integrals last read
+    // (S [n x npairs], J [n x d], T_last [n]), reserved by the first read
+    DevBuf<int32_t> d_pr_ptr, d_pr_pi, d_pr_pj;
+    DevBuf<pdmp::PairAdj> d_pr_adj;
+    DevBuf<double> d_pr_c, d_pr_S, d_pr_out;
+    DevBuf<unsigned char> d_pr_cur, d_pr_meta;
+    bool pr_on = false;
+    int64_t pr_np = 0;
     bool trace_appended = false;  // pdmp_debug_trace_append put events into the trace that no record knows of: run is refused until the next set_state
     // pdmp_ensemble_consume_async: a second trace buffer (the event loop writes one while the consumer reads the other), the consumer's stream,
     // the (ntrace, nevents) snapshots of the two most recent slices and the events that order the two streams
@@ -293,6 +302,12 @@ struct pdmp_ensemble {
     bool bcn_on = false, bc_started = false;  // bc_started: a bps_consume happened since bps_consume_begin
     int64_t bcn_max_hits = 0;
 
+    // pdmp_ensemble_bps_consume_pairs: the pair list, the centre [d], S [nchains x npairs], J [nchains x d], the T_last of the last read
+    DevBuf<int32_t> bpr_pi, bpr_pj;
+    DevBuf<double> bpr_c, bpr_S, bpr_J, bpr_T;
+    bool bpr_on = false;
+    int64_t bpr_np = 0;
+
     pdmp::ZzTables tables() const {
         pdmp::ZzTables tb{};
         tb.colptr = d_colptr.p;
@@ -358,6 +373,9 @@ pdmp_status bps_moments_at(pdmp_ensemble* e, double T, int64_t chain_first, int6
 // pdmp_capi_stats.hip
 pdmp_status condition_plane(const char* who, int64_t d, const double* p, const double* n, int64_t max_hits, std::vector<int32_t>* S);
 pdmp_status condition_rows_fit(const char* who, int64_t nchains, int64_t d, int64_t max_hits);
+// ... what both families check of the pair list of pdmp_ensemble_[bps_]consume_pairs; the list and the centre (zeros for NULL) come back
+pdmp_status pairs_list(const char* who, int64_t nchains, int64_t d, int64_t npairs, const int64_t* pi, const int64_t* pj, const double* center,
+                       std::vector<int32_t>* vi, std::vector<int32_t>* vj, std::vector<double>* c);
 // pdmp_capi_tune.hip: set_state with the placement probes
 pdmp_status init_state_tuned(pdmp_ensemble* e, double t0, const double* x0, const double* th0, const double* c, const uint64_t* seeds, uint64_t seed0);
 pdmp_status init_state_bps_tuned(pdmp_ensemble* e, double t0, const double* x0, const double* theta0, double c, const uint64_t* seeds);

@@ -565,6 +565,47 @@ class Ensemble:
         """consume_conditioned for the Bouncy Particle family."""
         return self._conditioned(self._L.pdmp_ensemble_bps_consume_conditioned, chain, first, count)
 
+    # ---- pair integrals on the device (pdmp_ensemble_[bps_]consume_pairs): S_ij = ∫ (x_i − c_i)(x_j − c_j) dt, J_i = ∫ (x_i − c_i) dt
+    def _pairs(self, fn, pi, pj, center):
+        pi = np.ascontiguousarray(pi, dtype=np.int64).reshape(-1)
+        pj = np.ascontiguousarray(pj, dtype=np.int64).reshape(-1)
+        if pi.size != pj.size:
+            raise ValueError("pi and pj have one entry per pair")
+        c = None
+        if center is not None:
+            c = _f64(center).reshape(-1)
+            if c.size != self.d:
+                raise ValueError("center has the ensemble's dimension %d" % self.d)
+        _lib.check(fn(self._h, int(pi.size), _ptr(pi) if pi.size else None, _ptr(pj) if pj.size else None, _ptr(c)))
+        self._npairs = int(pi.size)
+
+    def _pair_integrals(self, fn, chain_first, n):
+        if n is None:
+            n = self.nchains - chain_first
+        S, J, T = np.empty((n, getattr(self, "_npairs", 0))), np.empty((n, self.d)), np.empty(n)
+        _lib.check(fn(self._h, int(chain_first), int(n), _ptr(S), _ptr(J), _ptr(T), None))
+        return S, J, T
+
+    def consume_pairs(self, pi, pj, center=None):
+        """After consume_begin and before the first consume(): from then on consume() also keeps the exact path integrals S_ij = ∫ (x_i − c_i)
+        (x_j − c_j) dt of the pairs (pi[k], pj[k]) -- 0-based, any orientation, stored in the given order -- and J_i = ∫ (x_i − c_i) dt of every
+        coordinate (trace.pair_integrals is the host mirror, trace.covariance what follows from them)."""
+        self._pairs(self._L.pdmp_ensemble_consume_pairs, pi, pj, center)
+
+    def consume_pair_integrals(self, chain_first=0, n=None):
+        """(S [n x npairs], J [n x d], T_last [n]) of chains [chain_first, chain_first + n): every open piece closed at the chain's last
+        consumed event time; the accumulators are not touched, so the run can go on."""
+        return self._pair_integrals(self._L.pdmp_ensemble_consume_pair_integrals, chain_first, n)
+
+    def bps_consume_pairs(self, pi, pj, center=None):
+        """consume_pairs for the Bouncy Particle family (event-recorded BouncyParticle and its sticky form): after bps_consume_begin and before
+        the first bps_consume()."""
+        self._pairs(self._L.pdmp_ensemble_bps_consume_pairs, pi, pj, center)
+
+    def bps_consume_pair_integrals(self, chain_first=0, n=None):
+        """consume_pair_integrals for the Bouncy Particle family: the integrals over [t0, T_last] exactly."""
+        return self._pair_integrals(self._L.pdmp_ensemble_bps_consume_pair_integrals, chain_first, n)
+
     # ---- trace consumers of the Bouncy Particle family on the device (pdmp_ensemble_bps_consume_*)
     def bps_consume_begin(self, grid_dt=0.0, grid_points=0):
         """After set_state_bps, before the first run: (t0, x0, θ0) become the cursors; grid_points > 0 reserves the grid t0 + k·grid_dt."""

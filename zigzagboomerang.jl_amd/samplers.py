@@ -34,8 +34,8 @@ def _consume_capacity(consume, trace, trace_capacity):
     """The trace capacity of a Bouncy Particle run: with consume=... the events are written to the device buffer even where trace=False."""
     if consume is None:
         return trace_capacity if trace else 0
-    if not isinstance(consume, dict) or set(consume) - {"dt", "points", "condition", "hits"}:
-        raise TypeError("consume=dict(dt=..., points=...[, condition=(p, n), hits=K])")
+    if not isinstance(consume, dict) or set(consume) - {"dt", "points", "condition", "hits", "cov", "center"}:
+        raise TypeError("consume=dict(dt=..., points=...[, condition=(p, n), hits=K][, cov=P, center=c])")
     if trace_capacity <= 0:
         raise ValueError("consume=... reads the device trace buffer: trace_capacity must be positive")
     return trace_capacity
@@ -54,6 +54,38 @@ def _condition_of(consume):
     return p, n, hits
 
 
+def _pairs_of(consume, d):
+    """(pi, pj, center) of consume=dict(..., cov=P[, center=c]) -- the pair integrals on the device -- or None.  P: a sparse matrix (its
+    structural lower triangle plus the whole diagonal), "diag", or a (pi, pj) tuple of 0-based index lists."""
+    if consume is None or "cov" not in consume:
+        if consume is not None and "center" in consume:
+            raise TypeError("consume=dict(center=c) goes with cov=P")
+        return None
+    P = consume["cov"]
+    if isinstance(P, str):
+        if P != "diag":
+            raise ValueError('consume=dict(cov=P): P is a sparse matrix, "diag" or a (pi, pj) tuple')
+        pi = pj = np.arange(d, dtype=np.int64)
+    elif isinstance(P, tuple):
+        pi, pj = (np.asarray(v, dtype=np.int64).reshape(-1) for v in P)
+    else:
+        import scipy.sparse as sp
+        A = sp.coo_matrix(P)
+        if A.shape != (d, d):
+            raise ValueError("consume=dict(cov=P): P is %d x %d" % (d, d))
+        low = A.row > A.col
+        key = np.unique(A.row[low].astype(np.int64) * d + A.col[low])  # (row-major, duplicates of an unsummed COO matrix once)
+        pi = np.concatenate([np.arange(d, dtype=np.int64), key // d])
+        pj = np.concatenate([np.arange(d, dtype=np.int64), key % d])
+    return pi, pj, consume.get("center")
+
+
+def _pairs_result(out, pairs, integrals):
+    """pairs = (pi, pj), pair_S [nchains x npairs], pair_J [nchains x d]: with out["T"] what trace.covariance takes"""
+    out["pairs"] = (pairs[0], pairs[1])
+    out["pair_S"], out["pair_J"], _ = integrals()
+
+
 def _condition_result(out, conditioned, nchains):
     """hit_t, hit_x (per chain: a chain has its own number of hits) and nhits [nchains] -- a value above hits=K: later hits were dropped"""
     res = [conditioned(k) for k in range(nchains)]
@@ -70,11 +102,16 @@ def _consume_result(ens, consume, single, sticky):
         out["inclusion"] = ens.bps_consume_inclusion()[0]
     if _condition_of(consume) is not None:
         _condition_result(out, ens.bps_consume_conditioned, ens.nchains)
+    pairs = _pairs_of(consume, ens.d)
     if int(consume.get("points", 0)) > 0:
         grids = [ens.bps_consume_discretized(k) for k in range(ens.nchains)]
         out["grid_t"], out["grid_x"] = [g[0] for g in grids], [g[1] for g in grids]
     if single:
         out = {k: (v if v is None else v[0]) for k, v in out.items()}
+    if pairs is not None:
+        _pairs_result(out, pairs, ens.bps_consume_pair_integrals)
+        if single:
+            out["pair_S"], out["pair_J"] = out["pair_S"][0], out["pair_J"][0]
     return out
 
 
@@ -103,6 +140,9 @@ def spdmp(target, t0, x0, θ0, T, c, *GF, factor=1.8, adapt=False, adaptscale=Fa
     event time and trace.discretize(Ξ, dt) on at most `points` rows (grid_t / grid_x None without points), per chain as in pdmp.  With
     condition=(p, n), hits=K in the dict it also holds hit_t, hit_x, nhits: trace.conditional_trace(Ξ, p, n), at most K rows per chain
     (problems.bridge_point_condition gives the (p, n) of a bridge through a point).
+    consume=dict(cov=P[, center=c]) (any device target with a ZigZag; also on sspdmp and pdmp): the exact pair integrals of the path, kept on the
+    device slice by slice -- P a sparse matrix (its structural lower triangle plus the diagonal), "diag" or a (pi, pj) tuple; the element gains
+    pairs = (pi, pj), pair_S [npairs] and pair_J [d] per chain, which with T (L = T − t0) is what trace.covariance takes.
 
     G: the neighbourhoods a proposal moves before its gradient is taken (:82,171-179) -- a sparse matrix whose column patterns are the
     G[i] (e.g. the target's Γ when the bounding F.Γ is sparser) or a sequence of index arrays; G[i] ⊇ G1[i] = pattern of F.Γ[:, i] is
@@ -257,14 +297,15 @@ def sspdmp(target, t0, x0, θ0, T, c, *GFκ, reversible=False, strong_upperbound
             raise TypeError("BouncyParticle: target is None (∇ϕ!(y, x) = B.Γ(x − B.μ)) or a GaussianTarget of its own")
         return _bps(t0, x0, θ0, T, c, F, 2.0 if factor is None else factor, adapt, seed, device, trace_capacity, trace, target=target,
                     sticky=(GFκ[1], strong_upperbounds), consume=consume)
-    if consume is not None:
-        raise TypeError("consume is a keyword of the sticky BouncyParticle / Boomerang (the ZigZag's device consumers are Ensemble.consume_*)")
+    if consume is not None and not (isinstance(consume, dict) and "cov" in consume):
+        raise TypeError("consume is a keyword of the sticky BouncyParticle / Boomerang, or with cov=P (elsewhere the ZigZag's device consumers are "
+                        "Ensemble.consume_*)")
     if len(GFκ) not in (2, 3):
         raise TypeError("expected sspdmp(target, t0, x0, θ0, T, c, [G,] F, κ, ...)")
     G, F = _split_G(GFκ[:-1], G)
     κ = GFκ[-1]
     return _zigzag(_lib.SAMPLER_STICKY_ZIGZAG, target, t0, x0, θ0, T, c, F, 1.5 if factor is None else factor, adapt, seed, device,
-                   trace_capacity, trace, sticky=(np.asarray(κ, dtype=np.float64), reversible, strong_upperbounds), G=G)
+                   trace_capacity, trace, sticky=(np.asarray(κ, dtype=np.float64), reversible, strong_upperbounds), G=G, consume=consume)
 
 
 def stickyzz(target, t0, x0, θ0, T, c, F, barriers, *, strong_upperbounds=False, adapt=False, factor=1.5, seed=DEFAULT_SEED, device=0,
@@ -419,8 +460,9 @@ def _zigzag(sampler, target, t0, x0, θ0, T, c, F, factor, adapt, seed, device, 
         raise TypeError("the device path supports F::ZigZag and F::FactBoomerang")
     if not isinstance(target, (GaussianTarget, LogisticTarget, DiffusionBridgeTarget)):
         raise TypeError("target must be one of the device-resident families (GaussianTarget, LogisticTarget, DiffusionBridgeTarget)")
-    if consume is not None and not isinstance(target, DiffusionBridgeTarget):
-        raise TypeError("consume is a keyword of spdmp with a DiffusionBridgeTarget (elsewhere the ZigZag's device consumers are Ensemble.consume_*)")
+    if consume is not None and not isinstance(target, DiffusionBridgeTarget) and not (isinstance(consume, dict) and "cov" in consume):
+        raise TypeError("consume is a keyword of spdmp with a DiffusionBridgeTarget, or with cov=P (elsewhere the ZigZag's device consumers are "
+                        "Ensemble.consume_*)")
     x0 = np.asarray(x0, dtype=np.float64)
     θ0 = np.asarray(θ0, dtype=np.float64)
     single = x0.ndim == 1
@@ -461,6 +503,8 @@ def _zigzag(sampler, target, t0, x0, θ0, T, c, F, factor, adapt, seed, device, 
             ens.consume_begin(float(consume.get("dt", 0.0)), int(consume.get("points", 0)))
             if _condition_of(consume) is not None:
                 ens.consume_condition(*_condition_of(consume))
+            if _pairs_of(consume, d) is not None:
+                ens.consume_pairs(*_pairs_of(consume, d))
         events = [[] for _ in range(nch)]
         while True:
             ens.run(T, _lib.RUN_REFERENCE_TAIL)
@@ -486,6 +530,10 @@ def _zigzag(sampler, target, t0, x0, θ0, T, c, F, factor, adapt, seed, device, 
                 _condition_result(consumed, ens.consume_conditioned, nch)
             if single:
                 consumed = {k: (v if v is None else v[0]) for k, v in consumed.items()}
+            if _pairs_of(consume, d) is not None:
+                _pairs_result(consumed, _pairs_of(consume, d), ens.consume_pair_integrals)
+                if single:
+                    consumed["pair_S"], consumed["pair_J"] = consumed["pair_S"][0], consumed["pair_J"][0]
         fs = ens.final_state()
         cnt = ens.counters()
         sig = ens.final_sigma() if adaptscale else None
@@ -548,6 +596,8 @@ def _bps_modern(target, t0, x0, θ0, T, c, B, factor, adapt, seed, device, trace
             ens.bps_consume_begin(consume.get("dt", 0.0), consume.get("points", 0))
             if _condition_of(consume) is not None:
                 ens.bps_consume_condition(*_condition_of(consume))
+            if _pairs_of(consume, ens.d) is not None:
+                ens.bps_consume_pairs(*_pairs_of(consume, ens.d))
         if count:
             ens.set_bps_record_limit(int(T))
         T_end = float("inf") if count else float(T)
@@ -623,6 +673,8 @@ def _bps(t0, x0, θ0, T, c, B, factor, adapt, seed, device, trace_capacity, trac
             ens.bps_consume_begin(consume.get("dt", 0.0), consume.get("points", 0))
             if _condition_of(consume) is not None:
                 ens.bps_consume_condition(*_condition_of(consume))
+            if _pairs_of(consume, ens.d) is not None:
+                ens.bps_consume_pairs(*_pairs_of(consume, ens.d))
         fs_ = [[] for _ in range(nch)]
         ts = [[] for _ in range(nch)]
         xs = [[] for _ in range(nch)]

@@ -438,6 +438,135 @@ def conditional_trace(tr, p, n):
     return _conditional_fact(tr, p, n)
 
 
+def _pair_piece(a, b, vi, vj, tau):
+    """∫_0^τ (a + vi·u)(b + vj·u) du in the one grouping of the contract (tests/ref/pairs_ref.c; symmetric in (i, j) bit for bit)."""
+    return tau * (a * b + tau * (0.5 * (a * vj + b * vi) + tau * ((vi * vj) / 3.0)))
+
+
+def _line_piece(a, vi, tau):
+    return tau * (a + 0.5 * (vi * tau))
+
+
+def _seq_sum(pieces):
+    """0.0 + p_0 + p_1 + ... added one after the other, as an accumulator does (np.cumsum is that loop; the leading 0.0 matters for −0.0)."""
+    return float(np.cumsum(np.concatenate([[0.0], pieces]))[-1])
+
+
+def _pairs_fact(tr, pi, pj, c):
+    ev = tr.events
+    d = tr.x0.size
+    order, ptr = _groups(tr)
+    T_last = float(ev["t"][-1]) if len(ev) else float(tr.t0)
+    own = [order[ptr[j]:ptr[j + 1]] for j in range(d)]
+
+    def cursors(j, cnt):
+        """t, x, θ of coordinate j after its first cnt[k] events (0: the initial state)"""
+        if not len(own[j]):
+            return np.full(len(cnt), float(tr.t0)), np.full(len(cnt), tr.x0[j]), np.full(len(cnt), tr.θ0[j])
+        has = cnt > 0
+        k = own[j][np.maximum(cnt - 1, 0)]
+        return np.where(has, ev["t"][k], tr.t0), np.where(has, ev["x"][k], tr.x0[j]), np.where(has, ev["theta"][k], tr.θ0[j])
+
+    S = np.empty(len(pi))
+    for k, (i, j) in enumerate(zip(pi, pj)):
+        idx = own[i] if i == j else np.sort(np.concatenate([own[i], own[j]]))  # the events of either coordinate, in trace order
+        is_i = ev["i"][idx] == i
+        ci_cnt = np.cumsum(is_i) - is_i  # events of i before each of them
+        cj_cnt = ci_cnt if i == j else np.cumsum(~is_i) - (~is_i)
+        # ... and once more behind the last, for the close at T_last
+        ci_cnt = np.concatenate([ci_cnt, [len(own[i])]]).astype(np.int64)
+        cj_cnt = np.concatenate([cj_cnt, [len(own[j])]]).astype(np.int64)
+        t1 = np.concatenate([ev["t"][idx], [T_last]])
+        ti, xi, thi = cursors(i, ci_cnt)
+        tj, xj, thj = cursors(j, cj_cnt)
+        s0 = np.where(ti > tj, ti, tj)
+        a = (xi - c[i]) + thi * (s0 - ti)
+        b = (xj - c[j]) + thj * (s0 - tj)
+        S[k] = _seq_sum(_pair_piece(a, b, thi, thj, t1 - s0))
+    J = np.empty(d)
+    for j in range(d):
+        cnt = np.arange(len(own[j]) + 1, dtype=np.int64)
+        tc, xc, thc = cursors(j, cnt)
+        t1 = np.concatenate([ev["t"][own[j]], [T_last]])
+        J[j] = _seq_sum(_line_piece(xc - c[j], thc, t1 - tc))
+    return S, J, T_last
+
+
+def _pairs_pdmp(tr, pi, pj, c):
+    d = len(tr.x0)
+    t = np.asarray(tr.t, dtype=np.float64).reshape(-1)
+    m = len(t)
+    T_last = float(t[-1]) if m else float(tr.t0)
+    tc = np.concatenate([[tr.t0], t[:-1]])[:m]
+    Xc = np.vstack([np.asarray(tr.x0, dtype=np.float64)[None], np.asarray(tr.x, dtype=np.float64).reshape(-1, d)[:-1]])[:m]
+    Vc = np.vstack([np.asarray(tr.θ0, dtype=np.float64)[None], np.asarray(tr.θ, dtype=np.float64).reshape(-1, d)[:-1]])[:m]
+    if tr.f is not None:  # a coordinate that is not free keeps x
+        f0 = np.ones(d, dtype=bool) if tr.f0 is None else np.asarray(tr.f0, dtype=bool)
+        Fm = np.vstack([f0[None], np.asarray(tr.f, dtype=bool).reshape(-1, d)[:-1]])[:m]
+        Vc = np.where(Fm, Vc, 0.0)
+    tau = t - tc
+    A = Xc - c[None]
+    S = np.array([_seq_sum(_pair_piece(A[:, i], A[:, j], Vc[:, i], Vc[:, j], tau)) for i, j in zip(pi, pj)])
+    J = np.array([_seq_sum(_line_piece(A[:, j], Vc[:, j], tau)) for j in range(d)])
+    return S, J, T_last
+
+
+def _pair_list(d, pi, pj, center):
+    pi = np.ascontiguousarray(pi, dtype=np.int64).reshape(-1)
+    pj = np.ascontiguousarray(pj, dtype=np.int64).reshape(-1)
+    if pi.size != pj.size or pi.size < 1:
+        raise ValueError("pair_integrals: pi and pj list at least one pair, one entry each")
+    if pi.min() < 0 or pj.min() < 0 or pi.max() >= d or pj.max() >= d:
+        raise ValueError("pair_integrals: a pair has an index outside [0, %d)" % d)
+    key = np.minimum(pi, pj) * d + np.maximum(pi, pj)
+    if len(np.unique(key)) != len(key):
+        raise ValueError("pair_integrals: a pair is listed twice (either orientation counts)")
+    c = np.zeros(d) if center is None else np.ascontiguousarray(center, dtype=np.float64).reshape(-1)
+    if c.size != d or not np.all(np.isfinite(c)):
+        raise ValueError("pair_integrals: the centre has the trace's dimension %d and is finite" % d)
+    return pi, pj, c
+
+
+def pair_integrals(tr, pi, pj, center=None):
+    """(S [npairs], J [d], T_last): the exact path integrals S_k = ∫ (x_i − c_i)(x_j − c_j) dt of the pairs (i, j) = (pi[k], pj[k]) and
+    J_i = ∫ (x_i − c_i) dt of every coordinate over [t0, T_last], T_last the trace's last event time -- the host mirror of the device's pair
+    consumers (Ensemble.consume_pairs / bps_consume_pairs), bit for bit the sequential statement tests/ref/pairs_ref.c (DESIGN.md "Pair
+    integrals").  A FactTrace (time-ordered: no refresh clock): the integrand of a pair is a product of two lines whose pieces end at the
+    events of either coordinate; a PDMPTrace: every event ends a piece of every pair, frozen coordinates of a sticky trace stay where they
+    are.  Boomerang flows: TypeError (the product of two rotations is another integral)."""
+    if isinstance(tr.F, (Boomerang, FactBoomerang)):
+        raise TypeError("pair_integrals: on a Boomerang flow the product of two rotations is another integral than that of two lines")
+    pi, pj, c = _pair_list(len(tr.x0), pi, pj, center)
+    if isinstance(tr, PDMPTrace):
+        return _pairs_pdmp(tr, pi, pj, c)
+    return _pairs_fact(tr, pi, pj, c)
+
+
+def covariance(pi, pj, S, J, L, pooled=True, center=None):
+    """(cov, mean) from pair integrals: cov a symmetric scipy.sparse matrix [d x d] with S_ij / L − (J_i / L)(J_j / L) at the listed pairs, mean
+    = J / L + center.  S [n x npairs], J [n x d], L [n] (the run lengths T_last − t0) of n chains -- or one chain's S [npairs], J [d], L.
+    pooled=True: one matrix from ΣS / ΣL − (ΣJ / ΣL)(ΣJ / ΣL)ᵀ (raw integrals pool exactly across chains and ranks); pooled=False: a list of
+    n (cov, mean) pairs."""
+    import scipy.sparse as sp
+    pi = np.asarray(pi, dtype=np.int64).reshape(-1)
+    pj = np.asarray(pj, dtype=np.int64).reshape(-1)
+    S, J = np.atleast_2d(np.asarray(S, dtype=np.float64)), np.atleast_2d(np.asarray(J, dtype=np.float64))
+    L = np.asarray(L, dtype=np.float64).reshape(-1)
+    d = J.shape[1]
+    c = np.zeros(d) if center is None else np.asarray(center, dtype=np.float64).reshape(-1)
+
+    def one(s, j, l):
+        m = j / l
+        v = s / l - m[pi] * m[pj]
+        off = pi != pj
+        M = sp.coo_matrix((np.concatenate([v, v[off]]), (np.concatenate([pi, pj[off]]), np.concatenate([pj, pi[off]]))), shape=(d, d))
+        return M.tocsr(), m + c
+
+    if pooled:
+        return one(S.sum(axis=0), J.sum(axis=0), L.sum())
+    return [one(S[k], J[k], L[k]) for k in range(S.shape[0])]
+
+
 def faber_schauder_path(ξ, s, L, T):
     """dotψ(ξ, s, L, T) of research/diffusion_bridge/faberschauder.jl:16-24, vectorised: the bridge X_s of the Faber-Schauder coefficients ξ
     ([d] or [n x d], d = (2 << L) + 1, e.g. the rows of discretize(Ξ, dt)) at the times s (scalar or [m], 0 <= s < T).  Returns [m], or
