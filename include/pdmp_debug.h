@@ -42,6 +42,11 @@ pdmp_status pdmp_debug_set_track_groups(pdmp_ensemble* ens, int which);
  * logarithms produced ahead into a ring in LDS, the next windows' lines requested early); same committed sequence and floats.  -1 = chosen by
  * the ensemble's width (at most seven chains per compute unit, 1792 on an MI355X), 0 = never, 1 = always.  Before the next run. */
 pdmp_status pdmp_debug_set_helper_wave(pdmp_ensemble* ens, int mode);
+/* zz_local_trackp_kernel: how the chains that share a SIMD for a whole launch set their wave priority.  0 = in turns of 256 iterations (every
+ * event loop's rule), 1 = by rank of progress: the waves of a SIMD post how far they are through the launch on a board in device memory and the
+ * one furthest behind issues first (the one-wave forms up to d = 16384; the two-wave form and the form beyond d = 16384 take turns whatever is
+ * set), -1 = the default, which is 1.  No result depends on it.  Before the next run. */
+pdmp_status pdmp_debug_set_prio_policy(pdmp_ensemble* ens, int mode);
 /* zz_local_trackl_kernel (round 6): the same event loop on the LINE layout -- a coordinate pair's (key, t_old) pairs, sums and constants in one
  * 128-byte line, nine-bit wheel images of the pair minima in LDS -- which is what ensembles of more than 12 chains per compute unit run on the
  * plain lattice with an even side (d <= 16384); same committed sequence and floats.  -1 = by the ensemble's width, 0 = never, 1 = wherever the

@@ -62,7 +62,7 @@ EXPORTED_SYMBOLS = [
 ]
 # include/pdmp_debug.h: diagnostics, not part of the drop-in boundary
 DEBUG_SYMBOLS = ["pdmp_debug_set_kernel", "pdmp_debug_set_spec_g2", "pdmp_debug_set_phase_profile", "pdmp_debug_phase_profile",
-                 "pdmp_debug_set_proposal_dump", "pdmp_debug_set_track_groups", "pdmp_debug_set_helper_wave", "pdmp_debug_set_track_lines", "pdmp_debug_buffer_addresses", "pdmp_debug_placement", "pdmp_debug_set_placement", "pdmp_debug_move_buffer", "pdmp_debug_set_helper_steering", "pdmp_debug_set_launch_count_limit", "pdmp_debug_host_drain_probe", "pdmp_debug_set_consumer_overlap", "pdmp_debug_last_kernel", "pdmp_debug_set_logistic_rows", "pdmp_debug_math_probe", "pdmp_debug_math_eval", "pdmp_debug_write_probe", "pdmp_debug_sector_probe",
+                 "pdmp_debug_set_proposal_dump", "pdmp_debug_set_track_groups", "pdmp_debug_set_helper_wave", "pdmp_debug_set_prio_policy", "pdmp_debug_set_track_lines", "pdmp_debug_buffer_addresses", "pdmp_debug_placement", "pdmp_debug_set_placement", "pdmp_debug_move_buffer", "pdmp_debug_set_helper_steering", "pdmp_debug_set_launch_count_limit", "pdmp_debug_host_drain_probe", "pdmp_debug_set_consumer_overlap", "pdmp_debug_last_kernel", "pdmp_debug_set_logistic_rows", "pdmp_debug_math_probe", "pdmp_debug_math_eval", "pdmp_debug_write_probe", "pdmp_debug_sector_probe",
                  "pdmp_debug_sticky_eval", "pdmp_debug_trace_append", "pdmp_debug_barrier_eval", "pdmp_debug_bps_trace_append"]
 DEBUG_KERNELS = {"auto": 0, "seq": 1, "spec4": 2, "spec8": 3, "exactp": 4}
 
@@ -218,6 +218,7 @@ def load():
     L.pdmp_debug_set_proposal_dump.argtypes = [vp, i64]
     L.pdmp_debug_set_track_groups.argtypes = [vp, C.c_int]
     L.pdmp_debug_set_helper_wave.argtypes = [vp, C.c_int]
+    L.pdmp_debug_set_prio_policy.argtypes = [vp, C.c_int]
     L.pdmp_debug_set_track_lines.argtypes = [vp, C.c_int]
     L.pdmp_debug_buffer_addresses.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.pdmp_debug_move_buffer.argtypes = [vp, C.c_int]

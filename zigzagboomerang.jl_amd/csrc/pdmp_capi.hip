@@ -355,6 +355,16 @@ pdmp_status ensemble_run_impl(pdmp_ensemble* e, double T, int flags, void* strea
         P.dbg = dbgbuf.p;
         P.dbg_cap = dbg_cap;
     }
+    if (fam == FAM_TRACKP && e->dbg_prio_policy != 0) {
+        // priority by rank of progress (pdmp_engine.hpp: PrioLag): the board is zeroed once -- epoch 0 is never a launch's -- and every launch takes the next epoch
+        if (!e->d_prio_board.p) {
+            PDMP_TRY(e->d_prio_board.alloc(pdmp::PDMP_PRIO_BOARD_WORDS));
+            HIP_TRY(hipMemsetAsync(e->d_prio_board.p, 0, (size_t)pdmp::PDMP_PRIO_BOARD_WORDS * sizeof(uint32_t), s));
+        }
+        e->prio_epoch = e->prio_epoch % 255u + 1u;
+        P.prio_board = e->d_prio_board.p;
+        P.prio_epoch = e->prio_epoch;
+    }
     HIP_TRY(hipEventRecord(e->ev0, s));
     const bool profiled = e->dbg_phase != 0 && F.phase_kind != 0;
     if (profiled) {

@@ -234,6 +234,11 @@ pdmp_status pdmp_debug_set_helper_wave(pdmp_ensemble* e, int mode) {
     e->dbg_helper_wave = mode;
     return PDMP_OK;
 }
+pdmp_status pdmp_debug_set_prio_policy(pdmp_ensemble* e, int mode) {
+    if (!e || mode < -1 || mode > 1) return fail(PDMP_ERR_INVALID, "priority policy: -1 (default: by rank of progress where it applies), 0 (in turns), 1 (by rank of progress)");
+    e->dbg_prio_policy = mode;
+    return PDMP_OK;
+}
 pdmp_status pdmp_debug_set_consumer_overlap(pdmp_ensemble* e, int mode) {
     if (!e || mode < -1 || mode > 1) return fail(PDMP_ERR_INVALID, "consumer overlap: -1 (by width), 0 (between slices), 1 (beside the next slice)");
     e->dbg_cons_overlap = mode;

@@ -139,6 +139,63 @@ struct PrioTurn {
         it += 1;
     }
 };
+
+// Wave priority by rank of progress.  The turns above are open-loop: whichever of a SIMD's waves has fallen behind still gets one turn in four.
+// Here the waves of a SIMD tell each other how far they are through the launch, on a BOARD in device memory -- one row of 16 words per SIMD (key:
+// XCC_ID and HW_ID's SIMD, pipe, CU, SH and SE fields, 2^15 rows), one word per wave slot (HW_ID.wave_id) -- and every PDMP_PRIO_LAG_K
+// iterations a wave stores its own word, reads the row and takes priority 3 - min(rank, 3), rank = the number of live waves of the row that
+// are further behind (ties to the lower wave_id): the wave furthest behind issues first.  A word is (epoch << 24) | q: the epoch is the
+// ensemble's launch counter (1 .. 255, never 0: zeroed or stale words are no entries), q the progress (t_last - t_begin) / (T - t_begin) as
+// 24-bit fixed point, 0xffffff once the wave has left its loop.  The words travel by vector loads and stores at device scope (past the
+// CU's L1).  Nothing a chain computes depends on any of this; a launch whose progress has no meaning (T - t_begin not positive or not finite, or
+// no board) takes turns as above.
+#ifndef PDMP_PRIO_LAG_K
+#define PDMP_PRIO_LAG_K 32u
+#endif
+constexpr uint32_t PDMP_PRIO_BOARD_ROWS = 1u << 15, PDMP_PRIO_BOARD_SLOTS = 16u;
+constexpr uint32_t PDMP_PRIO_BOARD_WORDS = PDMP_PRIO_BOARD_ROWS * PDMP_PRIO_BOARD_SLOTS;  // 2 MB
+struct PrioLag {
+    PrioTurn turn;
+    uint32_t* row;  // this SIMD's 16 words, or null: turns
+    uint32_t slot, tag, it;
+    double t_begin, scale;
+    __device__ __forceinline__ PrioLag(uint32_t* board, uint32_t epoch, double t_begin_, double T) : row(nullptr), slot(0), tag(epoch << 24), it(0), t_begin(t_begin_), scale(0.0) {
+        const double span = T - t_begin_;
+        if (board != nullptr && epoch != 0u && span > 0.0 && span < __builtin_inf()) {
+            const uint32_t xcc = (uint32_t)__builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11));  // XCC_ID, bits 0..3
+            const uint32_t hw = (uint32_t)__builtin_amdgcn_s_getreg(4 | (4 << 6) | (11 << 11));   // HW_ID, bits 4..15: SIMD, pipe, CU, SH, SE
+            slot = (uint32_t)__builtin_amdgcn_s_getreg(4 | (0 << 6) | (3 << 11)) & (PDMP_PRIO_BOARD_SLOTS - 1u);  // HW_ID.wave_id
+            row = board + (size_t)(((xcc << 12) | hw) & (PDMP_PRIO_BOARD_ROWS - 1u)) * PDMP_PRIO_BOARD_SLOTS;
+            scale = 16777216.0 / span;
+        }
+    }
+    __device__ __forceinline__ void step(double t_last, int lane) {
+        if (row == nullptr) {
+            turn.step();
+            return;
+        }
+        if ((it & (PDMP_PRIO_LAG_K - 1u)) == 0u) {
+            const double f = (t_last - t_begin) * scale;
+            const uint32_t q = (f > 0.0) ? ((f < 16777214.0) ? (uint32_t)f : 0xfffffeu) : 0u;
+            if (lane == 0) __hip_atomic_store(row + slot, tag | q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            uint32_t w = 0u;
+            if (lane < (int)PDMP_PRIO_BOARD_SLOTS) w = __hip_atomic_load(row + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const uint32_t wq = w & 0xffffffu;
+            const bool behind = lane < (int)PDMP_PRIO_BOARD_SLOTS && (w & 0xff000000u) == tag && wq != 0xffffffu && (wq < q || (wq == q && (uint32_t)lane < slot));
+            const uint32_t rank = (uint32_t)__popcll(__ballot(behind));
+            switch (rank) {
+                case 0: __builtin_amdgcn_s_setprio(3); break;
+                case 1: __builtin_amdgcn_s_setprio(2); break;
+                case 2: __builtin_amdgcn_s_setprio(1); break;
+                default: __builtin_amdgcn_s_setprio(0); break;
+            }
+        }
+        it += 1;
+    }
+    __device__ __forceinline__ void finish(int lane) {  // at every exit from the loop
+        if (row != nullptr && lane == 0) __hip_atomic_store(row + slot, tag | 0xffffffu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+};
 #endif
 
 struct CoordConst {
@@ -220,6 +277,8 @@ struct ZzRunParams {
     uint32_t hw_target;
     int32_t n_cu;            // (host side) compute units of the device: the launchers' width thresholds are per CU (0: 256)
     int32_t helper_wave;     // zz_local_trackp: the two-wave form (a helper wave per chain: ring of draws + prefetch), for under-occupied launches
+    uint32_t* prio_board;    // zz_local_trackp, one-wave forms: the progress board of PrioLag ([PDMP_PRIO_BOARD_WORDS], zeroed once), or null: priority in turns
+    uint32_t prio_epoch;     // ... this launch's epoch on it, 1 .. 255
     // the line layout (pdmp_trackl.hip): [nchains x dk / 2] TrLine, [nchains x dk] TrCold; null elsewhere
     void* tl_lines;
     void* tl_cold;

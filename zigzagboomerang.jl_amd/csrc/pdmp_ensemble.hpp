@@ -270,6 +270,9 @@ struct pdmp_ensemble {
     uint32_t dbg_count_limit = 0;  // pdmp_debug_set_launch_count_limit (0: PDMP_LAUNCH_COUNT_LIMIT)
     int dbg_cons_overlap = -1;     // pdmp_debug_set_consumer_overlap: -1 by ensemble width, 0 the consumer runs between slices, 1 beside the next slice
     int dbg_helper_wave = -1;      // zz_local_trackp: -1 = the two-wave form where the launch leaves SIMDs idle (HELPER_WAVE_MAX_CHAINS_PER_CU), 0 = never, 1 = always
+    int dbg_prio_policy = -1;      // pdmp_debug_set_prio_policy: zz_local_trackp's wave priority: -1 = by rank of progress where it applies (one-wave forms of 2048 bounds), 0 = in turns, 1 = by rank
+    DevBuf<uint32_t> d_prio_board; // ... the progress board (pdmp_engine.hpp: PrioLag), allocated and zeroed by the first run that uses it
+    uint32_t prio_epoch = 0;       // ... the epoch of the last launch on it: 1 .. 255, wrapping
     int dbg_track_lines = -1;      // pdmp_debug_set_track_lines: 1 = the line layout wherever it serves; -1 / 0 = never (it lost the A/B: DESIGN.md §5)
 
     // BPS: the flow's and the target's tables, the state, the trace, the mass factor, and what each member of the family adds

@@ -102,6 +102,10 @@ constexpr int W_AMAX = 8;            // accepted events per iteration (one group
 #define W_SHRINK 0.98
 #define W_SLACK 5u
 #endif
+// the launch's head of the forms of 2048 bounds: one coalesced pass over the pairs (0: the two passes the form of 8192 bounds keeps -- A/B builds)
+#ifndef W_HEAD_ONE_PASS
+#define W_HEAD_ONE_PASS 1
+#endif
 // ... of the two-wave form: the raw candidate count is steered towards a target, by a gain (A/B at 512 / 1024 chains: 48 at 0.3 is 3 % faster than
 // the step rule above with 1.1 / 0.95 / 20, and than a target of 56)
 #define W_TARGET_HW 48u
@@ -300,7 +304,57 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
     double seldt = 1e-3;  // (wave-uniform) the selection threshold above the queue's minimum
     // base of the level-1 bounds: below every key (the initial keys of the reference carry no t0, src/sfact.jl:186)
     double tb;  // (wave-uniform; moves up with the front)
-    {
+    if (!BIG && W_HEAD_ONE_PASS) {
+        // 2048 bounds: ONE pass over the chain's pairs, whole lines per instruction.  Load k of 256 reads pairs 64 k .. 64 k + 63 -- lane (g, gl):
+        // pair gl of block 8 k + g, eight whole lines, 1 KB contiguous -- and a DPP minimum over the group of 8 gives the block's minimum and its
+        // position (the lowest on ties, as the comparison v < mk of the two-pass form below keeps it).  The lane with gl == (k & 7) keeps them in
+        // register slot k >> 3: 32 block minima per lane -- slot s of lane (g, gl) is block 64 s + 8 gl + g --, which wait there for the base
+        // (the minimum of them all), are encoded against it and are dead before the loop.  The bounds are word for word those of the two-pass form.
+        double bm[32];
+        uint32_t bpos[4] = {0u, 0u, 0u, 0u};  // the positions, four bits per slot
+        double mloc = t_last;
+        // (the loads of slot s + 1 are in flight while slot s is reduced, and no further: left to itself the scheduler lifts all 256 loads to
+        // the top and spills them)
+        double vn[8];
+        auto load8 = [&](int s) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const uint32_t k = 8u * (uint32_t)s + (uint32_t)j;
+                const bool in = 8u * k + (uint32_t)g < nblk;  // (a lane past the chain's last block reads pair `lane` of block g < 8 <= nblk instead: no branch)
+                const double v = kp[(in ? (size_t)64 * k : (size_t)0) + (size_t)lane].x;
+                vn[j] = in ? v : PDMP_INF;
+            }
+        };
+        load8(0);
+#pragma unroll
+        for (int s = 0; s < 32; ++s) {
+            double vc[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) vc[j] = vn[j];
+            __builtin_amdgcn_sched_barrier(0);
+            if (s + 1 < 32) load8(s + 1);
+            __builtin_amdgcn_sched_barrier(0);
+            double keep = PDMP_INF;
+            uint32_t kpos = 0u;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const double v = vc[j];
+                const double m = grp8_min_f64(v);
+                const uint32_t pos = w_grp8_min_u32((v == m) ? (uint32_t)gl : 8u);
+                keep = (gl == j) ? m : keep;
+                kpos = (gl == j) ? pos : kpos;
+            }
+            asm volatile("" : "+v"(keep), "+v"(kpos));  // (computed here: hipcc sank the last step of every reduction to the stores below, two live registers each)
+            bm[s] = keep;
+            bpos[s >> 3] |= (kpos & 7u) << (4 * (s & 7));
+            asm volatile("" : "+v"(bpos[s >> 3]));  // (packed here)
+            mloc = min_f64(mloc, keep);
+        }
+        tb = wave_min_f64(mloc);
+#pragma unroll
+        for (int s = 0; s < 32; ++s)
+            lbf[64 * s + 8 * gl + g] = (bm[s] < PDMP_INF) ? p_enc(bm[s], tb, (bpos[s >> 3] >> (4 * (s & 7))) & 7u) : P_INFBITS;
+    } else {
         double mloc = t_last;
         for (uint32_t b = lane; b < nblk; b += 64) {
             const double2* p = kp + (size_t)b * 8;
@@ -308,24 +362,25 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
             for (int q = 0; q < 8; ++q) mloc = min_f64(mloc, p[q].x);
         }
         tb = wave_min_f64(mloc);
-    }
-    for (uint32_t b = lane; b < W_NBLK; b += 64) {
-        uint32_t e = P_INFBITS;
-        if (b < nblk) {
-            const double2* p = kp + (size_t)b * 8;
-            double mk = p[0].x;
-            uint32_t mi = 0;
+        // (8192 bounds: 128 block minima per lane would not wait in registers -- a second pass, now that the base is known)
+        for (uint32_t b = lane; b < W_NBLK; b += 64) {
+            uint32_t e = P_INFBITS;
+            if (b < nblk) {
+                const double2* p = kp + (size_t)b * 8;
+                double mk = p[0].x;
+                uint32_t mi = 0;
 #pragma unroll
-            for (int q = 1; q < 8; ++q) {
-                const double v = p[q].x;
-                if (v < mk) {
-                    mk = v;
-                    mi = q;
+                for (int q = 1; q < 8; ++q) {
+                    const double v = p[q].x;
+                    if (v < mk) {
+                        mk = v;
+                        mi = q;
+                    }
                 }
+                e = (mk < PDMP_INF) ? p_enc(mk, tb, mi) : P_INFBITS;
             }
-            e = (mk < PDMP_INF) ? p_enc(mk, tb, mi) : P_INFBITS;
+            lbf[b] = e;
         }
-        lbf[b] = e;
     }
     PDMP_LDS_ORDER();
 
@@ -348,12 +403,14 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
         }                                                                 \
     } while (0)
 
-    PrioTurn prio;
+    // priority by rank of progress among the SIMD's waves (one-wave forms of 2048 bounds: four chains per SIMD from start to end of the launch);
+    // the two-wave form and the form of 8192 bounds take turns
+    PrioLag prio((!HW && !BIG) ? P.prio_board : nullptr, P.prio_epoch, t_last, T);
     bool need_rebase = false;
     uint32_t idle = 0;  // consecutive iterations without an event
     bool running = stop_before || (t_event < T);
     while (running) {
-        prio.step();
+        prio.step(t_last, lane);
         if (dnacc >= trace_room) {
             status = PDMP_CHAIN_TRACE_FULL;
             break;
@@ -1210,6 +1267,7 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
         P.dbg[15] = (double)ph_guess;
     }
 #undef WPHASE
+    prio.finish(lane);
     if (HW && lane == 0) ctl->exitf = 1u;
     if (lane == 0) {
         hdr->c.t_last = t_last;

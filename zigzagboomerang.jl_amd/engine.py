@@ -49,6 +49,8 @@ class Ensemble:
             _lib.check(self._L.pdmp_debug_set_track_groups(self._h, int(os.environ["PDMP_TRACK_GROUPS"])))
         if os.environ.get("PDMP_HELPER_WAVE"):
             self.debug_set_helper_wave(int(os.environ["PDMP_HELPER_WAVE"]))
+        if os.environ.get("PDMP_PRIO_POLICY"):
+            self.debug_set_prio_policy(int(os.environ["PDMP_PRIO_POLICY"]))
         if os.environ.get("PDMP_TRACK_LINES"):
             self.debug_set_track_lines(int(os.environ["PDMP_TRACK_LINES"]))
         if any(os.environ.get(v) for v in ("PDMP_PLACE_TUNE", "PDMP_PLACE", "PDMP_PLACE_rec", "PDMP_PLACE_kp", "PDMP_PLACE_ev")):
@@ -72,6 +74,10 @@ class Ensemble:
     def debug_set_helper_wave(self, mode):
         """zz_local_trackp: -1 the two-wave form by ensemble width (default), 0 never, 1 always (include/pdmp_debug.h)."""
         _lib.check(self._L.pdmp_debug_set_helper_wave(self._h, int(mode)))
+
+    def debug_set_prio_policy(self, mode):
+        """zz_local_trackp: wave priority -1 by rank of progress where it applies (default), 0 in turns, 1 by rank (include/pdmp_debug.h)."""
+        _lib.check(self._L.pdmp_debug_set_prio_policy(self._h, int(mode)))
 
     def debug_set_track_lines(self, mode):
         """zz_local_trackl (the line layout): -1 (default) and 0 never, 1 wherever it serves; before set_state (include/pdmp_debug.h)."""
