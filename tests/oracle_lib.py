@@ -295,7 +295,7 @@ class _ParResult(C.Structure):
 
 
 def parallel_spdmp(bound_gamma, bound_mu, target_gamma, x0, theta0, c, T, K, delta, *, t0=0.0, adapt=False, factor=1.8,
-                   seed=1, want_trace=True):
+                   seed=1, want_trace=True, target_mu=None):
     """src/parallel.jl parallel_spdmp restated with pthreads (CPU baseline and the checker of the device's partitioned mode).  The threads of a
     round share no data, so the result does not depend on their timing (tests/test_oracle_samplers.py checks it)."""
     L = lib()
@@ -304,8 +304,9 @@ def parallel_spdmp(bound_gamma, bound_mu, target_gamma, x0, theta0, c, T, K, del
     d = gb.n
     mu = _f64(bound_mu if bound_mu is not None else np.zeros(d))
     sg = np.ones(d)
-    p = _ZZParams(C.pointer(gb.c), mu.ctypes.data, sg.ctypes.data, 0.0, 0.0, C.pointer(gt.c), None, 0, int(adapt), factor, seed,
-                  0, 0)
+    mt = None if target_mu is None else _f64(target_mu)  # the target's μ: ∇ϕ(x, i) = Γt[:, i]·(x − μt)
+    p = _ZZParams(C.pointer(gb.c), mu.ctypes.data, sg.ctypes.data, 0.0, 0.0, C.pointer(gt.c), None if mt is None else mt.ctypes.data, 0,
+                  int(adapt), factor, seed, 0, 0)
     x = _f64(x0).copy()
     th = _f64(theta0).copy()
     cc = _f64(c).copy()

@@ -6,19 +6,9 @@ import pytest
 import scipy.sparse as sp
 
 import oracle_lib as O
+from partition_cases import chunk_diagonal
 
 pytestmark = pytest.mark.gpu
-
-
-def chunk_diagonal(G, K):
-    """The bounding Γ of test/testparallel.jl:40-47: the target's Γ without the entries that couple two chunks."""
-    d = G.shape[0]
-    k = d // K
-    coo = sp.coo_matrix(G)
-    keep = (coo.row // k) == (coo.col // k)
-    G2 = sp.csc_matrix((coo.data[keep], (coo.row[keep], coo.col[keep])), shape=G.shape)
-    G2.sort_indices()
-    return G2
 
 
 def run_both(pkg, G, K, T, delta, c, seed, x0, th0, adapt=False, factor=1.8):

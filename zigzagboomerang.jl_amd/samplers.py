@@ -364,6 +364,36 @@ class Partition:
         return int(a[0]) * self.k + int(a[1])
 
 
+def partition_tables(F, target, G=None):
+    """The flow tables of a partitioned run: (Fu, mask).  Fu is F with its bounding Γ spread over G's pattern (explicit zeros where Γ has no
+    entry) and mask [nnz] uint8 flags Γ's own structural entries, G1, among them -- what Ensemble.set_flow and Ensemble.run_partitioned take.
+    G: None = the pattern of F.Γ (src/parallel.jl:113-115), or a sparse matrix whose pattern ⊇ F.Γ's (G ⊇ G1, :119) and ⊇ the target's."""
+    def pattern(A):  # structural pattern (explicit zeros count, as in Julia's rowvals / nzrange)
+        A = sp.csc_matrix(A)
+        B = sp.csc_matrix((np.ones(A.nnz), A.indices.copy(), A.indptr.copy()), shape=A.shape)
+        B.sort_indices()
+        B.sum_duplicates()
+        B.data[:] = 1.0
+        return B
+
+    Gb = F.Γ
+    d = Gb.shape[0]
+    own = pattern(Gb)
+    pg = own if G is None else pattern(G)
+    U = (pg + own + pattern(target.Γ)).tocsc()
+    U.sort_indices()
+    if U.nnz != pg.nnz:
+        raise ValueError("G must contain the patterns of F.Γ (G ⊇ G1, src/parallel.jl:119) and of the target")
+    cols = np.repeat(np.arange(d), np.diff(U.indptr))
+    rows = U.indices
+    mask = np.asarray(own[rows, cols]).reshape(-1) != 0
+    vals = np.asarray(sp.csc_matrix(Gb)[rows, cols]).reshape(-1)
+    Γu = sp.csc_matrix((vals, rows.copy(), U.indptr.copy()), shape=Gb.shape)
+    Fu = copy.copy(F)
+    Fu.Γ = Γu  # (not through __post_init__: explicit zeros must stay)
+    return Fu, mask.astype(np.uint8)
+
+
 def parallel_spdmp(partition, target, t0, x0, θ0, T, c, G, F, *, factor=1.8, adapt=False, Δ=0.1, seed=DEFAULT_SEED, device=0,
                    trace_capacity=None, trace=True):
     """parallel_spdmp(partition, ∇ϕ, t0, x0, θ0, T, c, G, F::ZigZag; factor=1.8, adapt=false, Δ=0.1) (src/parallel.jl:104-175):
@@ -382,29 +412,7 @@ def parallel_spdmp(partition, target, t0, x0, θ0, T, c, G, F, *, factor=1.8, ad
     single = x0.ndim == 1
     X0, TH0 = np.atleast_2d(x0), np.atleast_2d(θ0)
     nch, d = X0.shape
-    # the flow tables carry G: the bounding Γ on G's pattern with explicit zeros, and the mask of its own structural entries
-    def pattern(A):  # structural pattern (explicit zeros count, as in Julia's rowvals / nzrange)
-        A = sp.csc_matrix(A)
-        B = sp.csc_matrix((np.ones(A.nnz), A.indices.copy(), A.indptr.copy()), shape=A.shape)
-        B.sort_indices()
-        B.sum_duplicates()
-        B.data[:] = 1.0
-        return B
-
-    Gb = F.Γ
-    own = pattern(Gb)
-    pg = own if G is None else pattern(G)
-    U = (pg + own + pattern(target.Γ)).tocsc()
-    U.sort_indices()
-    if U.nnz != pg.nnz:
-        raise ValueError("G must contain the patterns of F.Γ (G ⊇ G1, src/parallel.jl:119) and of the target")
-    cols = np.repeat(np.arange(d), np.diff(U.indptr))
-    rows = U.indices
-    mask = np.asarray(own[rows, cols]).reshape(-1) != 0
-    vals = np.asarray(sp.csc_matrix(Gb)[rows, cols]).reshape(-1)
-    Γu = sp.csc_matrix((vals, rows.copy(), U.indptr.copy()), shape=Gb.shape)
-    Fu = copy.copy(F)
-    Fu.Γ = Γu  # (not through __post_init__: explicit zeros must stay)
+    Fu, mask = partition_tables(F, target, G)
     cc = np.asarray(c, dtype=np.float64)
     seeds = (np.uint64(seed) + np.arange(nch, dtype=np.uint64)) if np.isscalar(seed) else np.asarray(seed, np.uint64)
     if trace_capacity is None:
@@ -415,7 +423,7 @@ def parallel_spdmp(partition, target, t0, x0, θ0, T, c, G, F, *, factor=1.8, ad
         ens.set_flow(Fu)
         ens.set_target(target)
         ens.set_state(t0, X0, TH0, cc, seeds)
-        ens.run_partitioned(T, K, Δ, mask.astype(np.uint8))
+        ens.run_partitioned(T, K, Δ, mask)
         cnt = ens.counters()
         if np.any(cnt["status"] == _lib.CHAIN_BOUND_VIOLATED):
             raise RuntimeError("Tuning parameter `c` too small.")  # src/parallel.jl:42
