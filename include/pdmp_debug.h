@@ -166,7 +166,8 @@ pdmp_status pdmp_debug_barrier_eval(int device, int fn, int64_t n, const double*
  * Test hook: puts a given trace segment in front of the device consumers (csrc/pdmp_consume.hip; tests/test_gpu_consumers_synthetic.py).  Waits for
  * the device (pending asynchronous consumers included), copies the n events into slots [ntrace, ntrace + n) of `chain`'s CURRENT trace buffer and
  * adds n to the chain's ntrace and nevents -- no event-loop kernel runs, no record changes.  PDMP_ERR_INVALID for a bad chain, n < 0,
- * ntrace + n > trace_capacity, a call before pdmp_ensemble_consume_begin and a non-factorised ensemble.  trace_copy, trace_reset, consume,
+ * ntrace + n > trace_capacity, a call before pdmp_ensemble_consume_begin (a barrier ensemble: pdmp_ensemble_barrier_consume_begin,
+ * tests/test_gpu_barrier_consumers.py) and a non-factorised ensemble.  trace_copy, trace_reset, consume,
  * consume_async, subtrace_copy and the consume_* readers work as after a run.  From the first append on the records no longer match the trace:
  * pdmp_ensemble_run on that ensemble is refused with PDMP_ERR_INVALID (until the next set_state).
  */

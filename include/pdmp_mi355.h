@@ -325,8 +325,9 @@ pdmp_status pdmp_ensemble_set_sticky(pdmp_ensemble* ens, const double* kappa, in
  *   set_state     PDMP_ERR_UNSUPPORTED for anything but: a ZigZag flow without refresh, the Gaussian target, G = G1 (no set_neighbourhood),
  *                 no gradient tracking / LocalBound, neighbourhoods of at most 64 members (what the one-event sticky kernel takes) with
  *                 |G1[i]| <= 63, an explicit state.  pdmp_ensemble_set_adaptscale itself returns PDMP_ERR_UNSUPPORTED on such an ensemble.
- * pdmp_ensemble_consume_begin returns PDMP_ERR_UNSUPPORTED (the device consumers' "time away from 0" has no meaning here); the host consumers work
- * on the returned trace.  One event after every hit, thaw and accepted reflection; the counters' nacc / num are the reference's scalar acc.
+ * pdmp_ensemble_consume_begin returns PDMP_ERR_UNSUPPORTED (the device consumers' "time away from 0" has no meaning here):
+ * pdmp_ensemble_barrier_consume_begin, below with the trace consumers, is the entry for such an ensemble; the host consumers work on the
+ * returned trace as before.  One event after every hit, thaw and accepted reflection; the counters' nacc / num are the reference's scalar acc.
  * The path integrals (pdmp_ensemble_path_integrals, batch_means, ess_*) are kept: a frozen coordinate contributes its barrier level.
  * pdmp_ensemble_final_state's acc then holds action[i] (0 hit, 1 reflect, 2 unfreeze, :170-175).
  *
@@ -577,6 +578,22 @@ pdmp_status pdmp_ensemble_consume_cummean_copy(pdmp_ensemble* ens, int64_t chain
  * 0-based index set J, renumbered by their position in J, compacted on the device; n_out = how many there are (at most out_cap are written to `out`). */
 pdmp_status pdmp_ensemble_subtrace_copy(pdmp_ensemble* ens, int64_t chain, const int64_t* J, int64_t nJ, pdmp_event* out, int64_t out_cap,
                                         int64_t* n_out);
+/* The same consumers for a PDMP_SAMPLER_BARRIER_ZIGZAG ensemble (stickyzz, sspdmp2), with the barrier OCCUPATION in place of inclusion_prob.
+ *   barrier_consume_begin(grid_dt, grid_points)  call order, argument checks and allocation of consume_begin; PDMP_ERR_INVALID on any other
+ *       sampler.  Afterwards consume, consume_mean, consume_discretized, consume_cummean(_copy), subtrace_copy, consume_condition(ed),
+ *       consume_pairs / consume_pair_integrals and pdmp_debug_trace_append serve the ensemble unchanged.  consume_async and consume_inclusion
+ *       return PDMP_ERR_UNSUPPORTED.  The cursors start from the path the chain travels: θ = 0 for a coordinate that starts frozen on the
+ *       barrier of its θ0 (src/stickyzz.jl:198-208), not the θ0 a returned trace records.
+ *   barrier_consume_occupation(chain_first, n, z_lo, z_hi, n_lo, n_hi, T_last)  per chain and coordinate, [n x d] each: the time spent frozen
+ *       (θ = 0) at the lower / upper barrier and the number of hits of each, as raw sums over [t0, T_last] (they pool exactly over chains);
+ *       T_last [n] is the time of the chain's last consumed event, to which a coordinate still frozen is extended.  A coordinate is frozen
+ *       from an event with θ = 0 to its next event; the side is that of its speed before the hit (upper iff > 0), at t0 that of θ0.  A wall
+ *       (kappa = +Inf) counts one hit and no time.  1 − (z_lo + z_hi) / (T_last − t0) is sspdmp2's posterior inclusion probability.  Any
+ *       output may be NULL; the stored sums are not modified.  PDMP_ERR_INVALID before barrier_consume_begin or for a chain range outside the
+ *       ensemble.  zigzagboomerang.jl_amd/trace.py: barrier_occupation is the host mirror, bit for bit. */
+pdmp_status pdmp_ensemble_barrier_consume_begin(pdmp_ensemble* ens, double grid_dt, int64_t grid_points);
+pdmp_status pdmp_ensemble_barrier_consume_occupation(pdmp_ensemble* ens, int64_t chain_first, int64_t n, double* z_lo, double* z_hi,
+                                                     uint64_t* n_lo, uint64_t* n_hi, double* T_last);
 
 /* ------------------------------------------------------------------ trace consumers of the Bouncy Particle family (PDMPTrace)
  *

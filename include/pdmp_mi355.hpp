@@ -142,6 +142,23 @@ struct Options {  // the reference's keyword arguments
     // the optional argument G of spdmp(∇ϕ, t0, x0, θ0, T, c, G, F, ...) / sspdmp(..., c, G, F, κ, ...) (src/sfact.jl:162, src/ss_fact.jl:159):
     // column patterns = the G[i] (values unused); empty = Matched().  G ⊇ G1 or the call throws (the reference's @assert, src/sfact.jl:177)
     SparseCSC G;
+    // stickyzz only, engine-only: consume every slice of the trace on the device before its buffer is recycled (pdmp_ensemble_barrier_consume_begin)
+    // and fill Result::consumed -- mean, the path on the grid t0 + k·consume_dt (consume_points rows reserved; 0: no grid) and the barrier
+    // occupation.  The consumers follow the path the chain travelled: a coordinate that starts on the barrier of its θ0 starts with θ = 0
+    bool consume = false;
+    double consume_dt = 0.0;
+    int64_t consume_points = 0;
+    bool consume_only = false;  // ... and copy no event to the host: Result::trace.events stays empty (the Python mirror's trace=False)
+};
+
+// What the device consumers of a stickyzz run return (Options::consume): mean(Ξ) [d] and the last event time T; the rows of
+// collect(discretize(Ξ, dt)) [npoints x d], row k at t0 + k dt; per coordinate the time it sat frozen on its lower / upper barrier over [t0, T]
+// and the hits of each, raw sums (1 − (frozen_lo + frozen_hi) / (T − t0) is sspdmp2's posterior inclusion probability)
+struct BarrierConsumed {
+    std::vector<double> mean, grid_x, frozen_lo, frozen_hi;
+    std::vector<uint64_t> hits_lo, hits_hi;
+    double T = 0.0;
+    int64_t npoints = 0;
 };
 
 // StickyBarriers(x, rule, κ), src/stickyzz.jl:19-25: the lower and the upper barrier of one coordinate -- levels (∓Inf: none on that side), the
@@ -179,6 +196,7 @@ struct Result {  // Ξ, (t, x, θ), (acc, num), c
     double t_prime = 0.0;
     std::vector<uint8_t> frozen;
     std::vector<double> theta_saved;
+    BarrierConsumed consumed;  // stickyzz with Options::consume
 };
 
 // RAII handle on pdmp_ensemble
@@ -210,6 +228,22 @@ class Ensemble {
     void set_bps_sticky(const std::vector<double>& kappa, bool strong_upperbounds = false) {
         if ((int64_t)kappa.size() != d_) throw std::invalid_argument("set_bps_sticky: kappa needs d entries");
         check(pdmp_ensemble_set_bps_sticky(h_, kappa.data(), strong_upperbounds ? 1 : 0));
+    }
+
+    // the device trace consumers of a barrier ensemble (stickyzz): after set_state and before the first run; then pdmp_ensemble_consume after
+    // every slice.  occupation: [n x d] each, any output may be nullptr
+    void barrier_consume_begin(double grid_dt = 0.0, int64_t grid_points = 0) { check(pdmp_ensemble_barrier_consume_begin(h_, grid_dt, grid_points)); }
+    void barrier_consume_occupation(int64_t chain_first, int64_t n, std::vector<double>* frozen_lo, std::vector<double>* frozen_hi,
+                                    std::vector<uint64_t>* hits_lo, std::vector<uint64_t>* hits_hi, std::vector<double>* T_last = nullptr) const {
+        const size_t nd = (size_t)(n * d_);
+        if (frozen_lo) frozen_lo->resize(nd);
+        if (frozen_hi) frozen_hi->resize(nd);
+        if (hits_lo) hits_lo->resize(nd);
+        if (hits_hi) hits_hi->resize(nd);
+        if (T_last) T_last->resize((size_t)n);
+        check(pdmp_ensemble_barrier_consume_occupation(h_, chain_first, n, frozen_lo ? frozen_lo->data() : nullptr, frozen_hi ? frozen_hi->data() : nullptr,
+                                                       hits_lo ? hits_lo->data() : nullptr, hits_hi ? hits_hi->data() : nullptr,
+                                                       T_last ? T_last->data() : nullptr));
     }
 
     std::vector<pdmp_chain_counters> counters() const {
@@ -301,13 +335,17 @@ Result<FactTrace> factorised(int sampler, const Target& target, double t0, const
     if (o.tracked) check(pdmp_ensemble_set_gradient_tracking(e.get(), 1));
     const uint64_t seed = o.seed;
     check(pdmp_ensemble_set_state(e.get(), t0, x0.data(), theta0.data(), c.data(), &seed));
+    const bool consume = o.consume;
+    if (consume && !barriers) throw std::invalid_argument("Options::consume is an option of stickyzz");
+    if (consume) e.barrier_consume_begin(o.consume_dt, o.consume_points);
     Result<FactTrace> R;
     R.trace.t0 = t0;
     R.trace.x0 = x0;
     R.trace.theta0 = theta0;
     auto cnt = e.run_and_drain(T, [&](const std::vector<pdmp_chain_counters>& k) {
+        if (consume) check(pdmp_ensemble_consume(e.get()));  // (every slice, before its buffer is recycled)
         const int64_t m = (int64_t)k[0].ntrace;
-        if (m > 0) {
+        if (m > 0 && !(consume && o.consume_only)) {
             const size_t old = R.trace.events.size();
             R.trace.events.resize(old + (size_t)m);
             check(pdmp_ensemble_trace_copy(e.get(), 0, 0, m, R.trace.events.data() + old));
@@ -328,6 +366,18 @@ Result<FactTrace> factorised(int sampler, const Target& target, double t0, const
         R.frozen.resize((size_t)d);
         R.theta_saved.resize((size_t)d);
         check(pdmp_ensemble_final_barrier(e.get(), 0, 1, R.frozen.data(), R.theta_saved.data()));
+    }
+    if (consume) {
+        BarrierConsumed& C = R.consumed;
+        C.mean.resize((size_t)d);
+        check(pdmp_ensemble_consume_mean(e.get(), 0, 1, C.mean.data(), &C.T));
+        e.barrier_consume_occupation(0, 1, &C.frozen_lo, &C.frozen_hi, &C.hits_lo, &C.hits_hi);
+        if (o.consume_points > 0) {
+            check(pdmp_ensemble_consume_discretized(e.get(), 0, 0, 0, nullptr, &C.npoints, nullptr));
+            if (C.npoints > o.consume_points) throw std::runtime_error("stickyzz: the trace runs past the grid of Options::consume_points");
+            C.grid_x.resize((size_t)(C.npoints * d));
+            check(pdmp_ensemble_consume_discretized(e.get(), 0, 0, C.npoints, C.grid_x.data(), nullptr, nullptr));
+        }
     }
     R.num = (int64_t)cnt[0].num;
     if (o.adaptscale) {

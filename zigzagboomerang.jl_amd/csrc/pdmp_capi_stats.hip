@@ -239,12 +239,12 @@ pdmp_status pdmp_ensemble_ess_end(pdmp_ensemble* e, double* sum_y, double* sum_y
     return PDMP_OK;
 }
 
-pdmp_status pdmp_ensemble_consume_begin(pdmp_ensemble* e, double grid_dt, int64_t grid_points) {
-    if (!e) return fail(PDMP_ERR_INVALID, "null argument");
-    NEED_FACTORISED(e);
+// consume_begin and barrier_consume_begin: one call order, one set of checks, one allocation; `barrier` adds the occupation state behind the cursors
+static pdmp_status consume_begin_impl(pdmp_ensemble* e, double grid_dt, int64_t grid_points, bool barrier) {
     if (!e->has_state || e->ran) return fail(PDMP_ERR_INVALID, "consume_begin follows set_state and precedes the first run (it snapshots x0, θ0)");
-    if (e->cfg.sampler == PDMP_SAMPLER_BARRIER_ZIGZAG)
-        return fail(PDMP_ERR_UNSUPPORTED, "the device consumers' time away from 0 has no meaning between barriers at other levels: consume the returned trace on the host");
+    if (!barrier && e->cfg.sampler == PDMP_SAMPLER_BARRIER_ZIGZAG)
+        return fail(PDMP_ERR_UNSUPPORTED, "the device consumers' time away from 0 has no meaning between barriers at other levels: "
+                                          "pdmp_ensemble_barrier_consume_begin serves a barrier ensemble (occupation per barrier instead)");
     if (e->cfg.trace_capacity <= 0) return fail(PDMP_ERR_INVALID, "ensemble was created with trace_capacity = 0");
     if (e->flow_kind != 0 || e->lambda_ref > 0)
         return fail(PDMP_ERR_UNSUPPORTED, "the device consumers take time-ordered traces of piecewise-linear paths: ZigZag without refresh clock");
@@ -252,7 +252,8 @@ pdmp_status pdmp_ensemble_consume_begin(pdmp_ensemble* e, double grid_dt, int64_
     HIP_TRY(hipSetDevice(e->cfg.device));
     const int64_t d = e->cfg.d, n = e->cfg.nchains;
     e->cons_z = e->cfg.sampler == PDMP_SAMPLER_STICKY_ZIGZAG;  // (the time away from 0, inclusion_prob: a sum of its own where coordinates can freeze)
-    PDMP_TRY(e->d_ccur.alloc((size_t)(n * d) * pdmp::consume_cursor_bytes(e->cons_z)));
+    e->cons_occ = barrier;
+    PDMP_TRY(e->d_ccur.alloc((size_t)(n * d) * (pdmp::consume_cursor_bytes(e->cons_z) + (barrier ? pdmp::consume_occ_bytes() : 0))));
     PDMP_TRY(e->d_cmeta.alloc((size_t)n * pdmp::consume_meta_bytes()));
     e->d_cgrid.release();
     if (grid_points > 0) {
@@ -270,10 +271,52 @@ pdmp_status pdmp_ensemble_consume_begin(pdmp_ensemble* e, double grid_dt, int64_
     e->d_pr_out.release(), e->d_pr_cur.release(), e->d_pr_meta.release();
     LAUNCH_TRY("consume_init", pdmp::launch_consume_init(e->d_rec.p, e->track ? 128 : 64, d, n, e->t0_state, e->d_ccur.p, e->cons_z, e->d_cmeta.p,
                                        grid_points > 0 ? e->d_cgrid.p : nullptr, grid_points, e->stream));
+    if (barrier)  // (the records at t0 hold θ = 0 for a coordinate that starts frozen; d_thf holds every coordinate's θ0 as v_old)
+        LAUNCH_TRY("barrier_occ_init", pdmp::launch_barrier_occ_init(e->d_thf.p, d, n, e->d_ccur.p, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->consuming = true;
     e->cons_dt = grid_dt;
     e->cons_K = grid_points;
+    return PDMP_OK;
+}
+
+pdmp_status pdmp_ensemble_consume_begin(pdmp_ensemble* e, double grid_dt, int64_t grid_points) {
+    if (!e) return fail(PDMP_ERR_INVALID, "null argument");
+    NEED_FACTORISED(e);
+    return consume_begin_impl(e, grid_dt, grid_points, false);
+}
+
+// The synchronous consumers of a barrier ensemble (stickyzz / sspdmp2): consume_begin plus the occupation state (DESIGN.md "Barrier occupation")
+pdmp_status pdmp_ensemble_barrier_consume_begin(pdmp_ensemble* e, double grid_dt, int64_t grid_points) {
+    if (!e) return fail(PDMP_ERR_INVALID, "null argument");
+    if (e->cfg.sampler != PDMP_SAMPLER_BARRIER_ZIGZAG)
+        return fail(PDMP_ERR_INVALID, "barrier_consume_begin: the ensemble is not a barrier ZigZag (PDMP_SAMPLER_BARRIER_ZIGZAG); pdmp_ensemble_consume_begin");
+    return consume_begin_impl(e, grid_dt, grid_points, true);
+}
+
+// time frozen at the lower / upper barrier [n x d] and hits of each [n x d] of chains [chain_first, chain_first + n), T_last [n]; any output may be NULL
+pdmp_status pdmp_ensemble_barrier_consume_occupation(pdmp_ensemble* e, int64_t chain_first, int64_t n, double* z_lo, double* z_hi, uint64_t* n_lo,
+                                                     uint64_t* n_hi, double* T_last) {
+    if (!e) return fail(PDMP_ERR_INVALID, "null argument");
+    if (!e->consuming || !e->cons_occ) return fail(PDMP_ERR_INVALID, "pdmp_ensemble_barrier_consume_begin first");
+    if (chain_first < 0 || n <= 0 || chain_first + n > e->cfg.nchains) return fail(PDMP_ERR_INVALID, "chain range");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(device_sync(e));
+    const int64_t d = e->cfg.d;
+    const size_t nd = (size_t)(n * d);
+    DevBuf<double> bz, bt;
+    DevBuf<uint64_t> bn;
+    PDMP_TRY(bz.alloc(2 * nd));
+    PDMP_TRY(bn.alloc(2 * nd));
+    PDMP_TRY(bt.alloc((size_t)n));
+    LAUNCH_TRY("barrier_occ_read", pdmp::launch_barrier_occ_read(d, e->cfg.nchains, chain_first, n, e->d_ccur.p, e->d_cmeta.p, bz.p, bz.p + nd, bn.p,
+                                                                  bn.p + nd, bt.p, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (z_lo) HIP_TRY(hipMemcpy(z_lo, bz.p, nd * sizeof(double), hipMemcpyDeviceToHost));
+    if (z_hi) HIP_TRY(hipMemcpy(z_hi, bz.p + nd, nd * sizeof(double), hipMemcpyDeviceToHost));
+    if (n_lo) HIP_TRY(hipMemcpy(n_lo, bn.p, nd * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (n_hi) HIP_TRY(hipMemcpy(n_hi, bn.p + nd, nd * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (T_last) HIP_TRY(hipMemcpy(T_last, bt.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
     return PDMP_OK;
 }
 
@@ -290,7 +333,7 @@ pdmp_status pdmp_ensemble_consume(pdmp_ensemble* e) {
     if (e->pr_on)  // (cursors of its own, like the condition's)
         LAUNCH_TRY("consume_pairs", pdmp::launch_pair_events(e->d_ev.p, e->cfg.trace_capacity, e->d_hdr.p, e->cfg.d, e->cfg.nchains, pair_args(e), e->stream));
     LAUNCH_TRY("consume", pdmp::launch_consume_events(e->d_ev.p, e->cfg.trace_capacity, e->d_hdr.p, nullptr, e->cfg.d, e->cfg.nchains, e->d_ccur.p, e->cons_z, e->d_cmeta.p,
-                                         e->d_cgrid.p, e->cons_K, e->t0_state, e->cons_dt, e->stream, e->cons_cummean ? e->d_ccm.p : nullptr));
+                                         e->d_cgrid.p, e->cons_K, e->t0_state, e->cons_dt, e->stream, e->cons_cummean ? e->d_ccm.p : nullptr, e->cons_occ));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return PDMP_OK;
 }
@@ -367,6 +410,9 @@ pdmp_status pdmp_ensemble_subtrace_copy(pdmp_ensemble* e, int64_t chain, const i
 pdmp_status pdmp_ensemble_consume_async(pdmp_ensemble* e, void* stream) {
     if (!e) return fail(PDMP_ERR_INVALID, "null argument");
     if (!e->consuming || !e->has_state) return fail(PDMP_ERR_INVALID, "pdmp_ensemble_consume_begin first");
+    if (e->cons_occ)
+        return fail(PDMP_ERR_UNSUPPORTED, "consume_async: a barrier ensemble (pdmp_ensemble_barrier_consume_begin) is served by the synchronous consumer, "
+                                          "pdmp_ensemble_consume");
     if (e->cn_on)
         return fail(PDMP_ERR_UNSUPPORTED, "consume_async: the conditional trace (pdmp_ensemble_consume_condition) is served by the synchronous consumer, "
                                           "pdmp_ensemble_consume");
@@ -438,6 +484,9 @@ pdmp_status pdmp_ensemble_consume_mean(pdmp_ensemble* e, int64_t chain_first, in
 }
 
 pdmp_status pdmp_ensemble_consume_inclusion(pdmp_ensemble* e, int64_t chain_first, int64_t n, double* prob, double* T_last) {
+    if (e && e->consuming && e->cons_occ)
+        return fail(PDMP_ERR_UNSUPPORTED, "consume_inclusion: the time away from 0 has no meaning between barriers at other levels: "
+                                          "pdmp_ensemble_barrier_consume_occupation returns the time frozen at each barrier (1 − z/T)");
     return consume_reduce(e, chain_first, n, prob, T_last, "consume_inclusion", [&](double* bm, double* bt) {
         return pdmp::launch_consume_inclusion(e->cfg.d, e->cfg.nchains, e->cons_z, e->t0_state, chain_first, n, e->d_ccur.p, e->d_cmeta.p, bm, bt, e->stream);
     });

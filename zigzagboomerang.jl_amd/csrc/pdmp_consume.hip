@@ -58,6 +58,14 @@ struct ConsumeMeta {
     uint64_t row_next;  // the first grid row not written yet by the streaming consumer
     uint64_t pad;
 };
+// (barrier ensembles keep the OCCUPATION of every coordinate instead, in an array of its own behind the cursors: the time it sat frozen on its lower
+// and on its upper barrier, how often it hit each, and the side it is -- or was last -- frozen on; DESIGN.md "Barrier occupation" has the definition)
+struct BarrierOcc {
+    double z[2];    // time frozen at the lower / upper barrier, over the consumed events
+    uint64_t n[2];  // hits of the lower / upper barrier
+    uint64_t side;  // 0 lower, 1 upper: where a frozen coordinate sits (from v_old at t0, then from the speed before each hit)
+};
+static_assert(sizeof(BarrierOcc) == 40, "z, n and the side of one coordinate");
 
 __global__ __launch_bounds__(256) void consume_init_kernel(const ZzRec* rec0, int64_t rec_stride, int64_t d, int64_t nchains, double t0,
                                                            ConsumeCursor* cur, double* zs, ConsumeMeta* meta, double* grid, int64_t K) {
@@ -101,6 +109,8 @@ __device__ __forceinline__ void consume_emit(double* grid_chain, int64_t d, int6
 // (snap: the (ntrace, nevents) pairs a finished launch left, taken by consume_snapshot_kernel -- the asynchronous consumer reads a buffer the
 // event loop no longer writes while the headers already count the next slice; nullptr: the headers themselves)
 constexpr int CONSUME_HASH = 4096;  // slots of the per-chunk table that finds two events of one coordinate
+// (OCC: the barrier ensembles' form -- zs0 is their BarrierOcc array, updated beside the cursor; every other ensemble runs OCC = false)
+template <bool OCC>
 __global__ __launch_bounds__(256) void consume_events_kernel(const pdmp_event* ev0, int64_t cap, const DevChain* hdr, const uint64_t* __restrict__ snap,
                                                              int64_t d, ConsumeCursor* cur0, double* zs0, ConsumeMeta* meta, double* grid0, int64_t K,
                                                              double t0, double dt, double2* cm0) {
@@ -117,7 +127,8 @@ __global__ __launch_bounds__(256) void consume_events_kernel(const pdmp_event* e
     if (pos >= ntrace) return;
     const pdmp_event* ev = ev0 + chain * cap;
     ConsumeCursor* cur = cur0 + chain * d;
-    double* zs = zs0 ? zs0 + chain * d : nullptr;
+    double* zs = (!OCC && zs0) ? zs0 + chain * d : nullptr;
+    BarrierOcc* occ = OCC ? reinterpret_cast<BarrierOcc*>(zs0) + chain * d : nullptr;
     double* grid = grid0 ? grid0 + chain * K * d : nullptr;
     uint64_t row = m.row_next;
     for (;;) {
@@ -174,6 +185,15 @@ __global__ __launch_bounds__(256) void consume_events_kernel(const pdmp_event* e
                     const uint32_t i = (uint32_t)evt.i;
                     ConsumeCursor c = cur[i];
                     c.y += (c.x + evt.x) * (evt.t - c.t);  // src/trace.jl:193 without the common factor 1/(2T)
+                    if constexpr (OCC) {  // (the same ordered rounds: two events of one coordinate -- a wall's hit and thaw at one time -- keep their order)
+                        BarrierOcc o = occ[i];
+                        if (c.th == 0.0) o.z[o.side & 1u] += evt.t - c.t;  // frozen since its last event (−0.0 counts as 0)
+                        if (evt.theta == 0.0 && c.th != 0.0) {             // a hit: the barrier in the direction it travelled
+                            o.side = c.th > 0.0 ? 1u : 0u;
+                            o.n[o.side] += 1;
+                        }
+                        occ[i] = o;
+                    }
                     if (zs && (c.x != 0.0 || evt.x != 0.0)) zs[i] += evt.t - c.t;  // :172 without the common factor 1/T (−0.0 of a freeze counts as 0)
                     c.t = evt.t;
                     c.x = evt.x;
@@ -245,6 +265,8 @@ __global__ __launch_bounds__(256) void consume_inclusion_kernel(int64_t d, int64
 // the cursors, and behind them the z sums of a sticky ensemble
 size_t consume_cursor_bytes(bool with_z) { return sizeof(ConsumeCursor) + (with_z ? sizeof(double) : 0); }
 size_t consume_meta_bytes() { return sizeof(ConsumeMeta); }
+size_t consume_occ_bytes() { return sizeof(BarrierOcc); }
+static BarrierOcc* occ_of(void* cur, int64_t d, int64_t nchains) { return reinterpret_cast<BarrierOcc*>(static_cast<ConsumeCursor*>(cur) + nchains * d); }
 static double* z_of(void* cur, int64_t d, int64_t nchains, bool with_z) {
     return with_z ? reinterpret_cast<double*>(static_cast<ConsumeCursor*>(cur) + nchains * d) : nullptr;
 }
@@ -265,10 +287,56 @@ int launch_consume_init(const ZzRec* rec, int64_t rec_stride, int64_t d, int64_t
     return (int)hipGetLastError();
 }
 int launch_consume_events(const pdmp_event* ev, int64_t cap, const DevChain* hdr, const uint64_t* snap, int64_t d, int64_t nchains, void* cur,
-                          bool with_z, void* meta, double* grid, int64_t K, double t0, double dt, void* stream, double* cummean_pairs) {
-    hipLaunchKernelGGL(consume_events_kernel, dim3((unsigned)nchains), dim3(256), 0, (hipStream_t)stream, ev, cap, hdr, snap, d,
-                       static_cast<ConsumeCursor*>(cur), z_of(cur, d, nchains, with_z), static_cast<ConsumeMeta*>(meta), grid, K, t0, dt,
-                       reinterpret_cast<double2*>(cummean_pairs));
+                          bool with_z, void* meta, double* grid, int64_t K, double t0, double dt, void* stream, double* cummean_pairs, bool with_occ) {
+    if (with_occ)
+        hipLaunchKernelGGL(consume_events_kernel<true>, dim3((unsigned)nchains), dim3(256), 0, (hipStream_t)stream, ev, cap, hdr, snap, d,
+                           static_cast<ConsumeCursor*>(cur), reinterpret_cast<double*>(occ_of(cur, d, nchains)), static_cast<ConsumeMeta*>(meta), grid, K,
+                           t0, dt, reinterpret_cast<double2*>(cummean_pairs));
+    else
+        hipLaunchKernelGGL(consume_events_kernel<false>, dim3((unsigned)nchains), dim3(256), 0, (hipStream_t)stream, ev, cap, hdr, snap, d,
+                           static_cast<ConsumeCursor*>(cur), z_of(cur, d, nchains, with_z), static_cast<ConsumeMeta*>(meta), grid, K, t0, dt,
+                           reinterpret_cast<double2*>(cummean_pairs));
+    return (int)hipGetLastError();
+}
+
+// occupation of a barrier ensemble: zeros, and the side a coordinate that starts frozen sits on -- the barrier of its saved speed v_old = θ0 (thf)
+__global__ __launch_bounds__(256) void barrier_occ_init_kernel(const double* __restrict__ thf, int64_t n, BarrierOcc* occ) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= n) return;
+    BarrierOcc o;
+    o.z[0] = o.z[1] = 0.0;
+    o.n[0] = o.n[1] = 0;
+    o.side = thf[k] > 0.0 ? 1u : 0u;
+    occ[k] = o;
+}
+// ... read: a coordinate still frozen is extended to the chain's last consumed event time in registers; the stored sums are not touched
+__global__ __launch_bounds__(256) void barrier_occ_read_kernel(int64_t d, int64_t chain_first, int64_t n, const ConsumeCursor* cur0, const BarrierOcc* occ0,
+                                                               const ConsumeMeta* meta, double* z_lo, double* z_hi, uint64_t* n_lo, uint64_t* n_hi,
+                                                               double* T_out) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= n * d) return;
+    const int64_t q = k / d, i = k - q * d;
+    const int64_t chain = chain_first + q;
+    const double T = meta[chain].t_last;
+    const ConsumeCursor c = cur0[chain * d + i];
+    const BarrierOcc o = occ0[chain * d + i];
+    const bool frozen = c.th == 0.0;
+    if (z_lo) z_lo[k] = o.z[0] + ((frozen && o.side == 0) ? T - c.t : 0.0);
+    if (z_hi) z_hi[k] = o.z[1] + ((frozen && o.side == 1) ? T - c.t : 0.0);
+    if (n_lo) n_lo[k] = o.n[0];
+    if (n_hi) n_hi[k] = o.n[1];
+    if (i == 0 && T_out) T_out[q] = T;
+}
+int launch_barrier_occ_init(const double* thf, int64_t d, int64_t nchains, void* cur, void* stream) {
+    const int64_t n = nchains * d;
+    hipLaunchKernelGGL(barrier_occ_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, thf, n, occ_of(cur, d, nchains));
+    return (int)hipGetLastError();
+}
+int launch_barrier_occ_read(int64_t d, int64_t nchains, int64_t chain_first, int64_t n, void* cur, const void* meta, double* z_lo, double* z_hi,
+                            uint64_t* n_lo, uint64_t* n_hi, double* T_out, void* stream) {
+    const int64_t tot = n * d;
+    hipLaunchKernelGGL(barrier_occ_read_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d, chain_first, n,
+                       static_cast<const ConsumeCursor*>(cur), occ_of(cur, d, nchains), static_cast<const ConsumeMeta*>(meta), z_lo, z_hi, n_lo, n_hi, T_out);
     return (int)hipGetLastError();
 }
 

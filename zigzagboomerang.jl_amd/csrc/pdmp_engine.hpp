@@ -575,11 +575,16 @@ size_t zz_local_lds_bytes(uint32_t nblk_pad, uint32_t blob_w_pad);
 // pdmp_consume.hip
 size_t consume_cursor_bytes(bool with_z);
 size_t consume_meta_bytes();
+size_t consume_occ_bytes();  // a barrier ensemble's occupation state per (chain, coordinate), behind the cursors
 int launch_consume_init(const ZzRec* rec, int64_t rec_stride, int64_t d, int64_t nchains, double t0, void* cur, bool with_z, void* meta, double* grid,
                         int64_t K, void* stream);
 int launch_consume_snapshot(DevChain* hdr, int64_t nchains, uint64_t* snap, void* stream);
 int launch_consume_events(const pdmp_event* ev, int64_t cap, const DevChain* hdr, const uint64_t* snap, int64_t d, int64_t nchains, void* cur,
-                          bool with_z, void* meta, double* grid, int64_t K, double t0, double dt, void* stream, double* cummean_pairs = nullptr);
+                          bool with_z, void* meta, double* grid, int64_t K, double t0, double dt, void* stream, double* cummean_pairs = nullptr,
+                          bool with_occ = false);
+int launch_barrier_occ_init(const double* thf, int64_t d, int64_t nchains, void* cur, void* stream);
+int launch_barrier_occ_read(int64_t d, int64_t nchains, int64_t chain_first, int64_t n, void* cur, const void* meta, double* z_lo, double* z_hi,
+                            uint64_t* n_lo, uint64_t* n_hi, double* T_out, void* stream);
 // pdmp_place.hip: an array of several GB built from chunks of the device's three memory classes in turn (one contiguous address range)
 struct Placement {
     void* va = nullptr;

@@ -212,6 +212,7 @@ struct pdmp_ensemble {
     DevBuf<double> d_ccm;      // pdmp_ensemble_consume_cummean: (t, y / (2 t)) per event slot of the last consumed segment [nchains x cap x 2], or empty
     bool cons_cummean = false;
     bool consuming = false, cons_z = false;
+    bool cons_occ = false;  // pdmp_ensemble_barrier_consume_begin: the occupation state (time frozen / hits per barrier) lies behind the cursors
     double cons_dt = 0.0;
     int64_t cons_K = 0;
     // pdmp_ensemble_consume_condition: the conditional trace's own cursors (t, x, θ) [3 x nchains x d], the list of supp n (cn_idx; cn_loc[] =

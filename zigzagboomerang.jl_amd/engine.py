@@ -455,6 +455,27 @@ class Ensemble:
         _lib.check(self._L.pdmp_ensemble_consume_begin(self._h, float(grid_dt), int(grid_points)))
         self._grid = (float(grid_dt), int(grid_points))
 
+    def barrier_consume_begin(self, dt=0.0, points=0):
+        """consume_begin for a barrier ensemble (SAMPLER_BARRIER_ZIGZAG: stickyzz, sspdmp2): afterwards consume(), consume_mean(),
+        consume_discretized(), consume_cummean(), subtrace(), consume_condition() and consume_pairs() serve it like any other ensemble, and
+        barrier_consume_occupation() replaces consume_inclusion().  The cursors follow the path the chain travels: a coordinate that starts on
+        the barrier of its θ0 starts frozen, with θ = 0 (trace.barrier_start gives that start for the host mirrors), not with the θ0 a
+        returned trace records."""
+        _lib.check(self._L.pdmp_ensemble_barrier_consume_begin(self._h, float(dt), int(points)))
+        self._grid = (float(dt), int(points))
+
+    def barrier_consume_occupation(self, chain_first=0, n=None):
+        """(frozen_lo, frozen_hi [n x d] float64, hits_lo, hits_hi [n x d] uint64, T_last [n]): the time each coordinate sat frozen on its lower /
+        upper barrier over [t0, T_last] and the hits of each, raw sums (trace.barrier_occupation is the host mirror, bit for bit).  A read
+        between two slices does not disturb the next one."""
+        if n is None:
+            n = self.nchains - chain_first
+        zl, zh = np.empty((n, self.d)), np.empty((n, self.d))
+        nl, nh = np.empty((n, self.d), dtype=np.uint64), np.empty((n, self.d), dtype=np.uint64)
+        T = np.empty(n)
+        _lib.check(self._L.pdmp_ensemble_barrier_consume_occupation(self._h, int(chain_first), int(n), _ptr(zl), _ptr(zh), _ptr(nl), _ptr(nh), _ptr(T)))
+        return zl, zh, nl, nh, T
+
     def consume(self):
         _lib.check(self._L.pdmp_ensemble_consume(self._h))
 

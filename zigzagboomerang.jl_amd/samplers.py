@@ -309,14 +309,23 @@ def sspdmp(target, t0, x0, θ0, T, c, *GFκ, reversible=False, strong_upperbound
 
 
 def stickyzz(target, t0, x0, θ0, T, c, F, barriers, *, strong_upperbounds=False, adapt=False, factor=1.5, seed=DEFAULT_SEED, device=0,
-             trace_capacity=None, trace=True, details=False):
+             trace_capacity=None, trace=True, details=False, consume=None):
     """The ZigZag with sticky and reflecting barriers: stickyzz(u0, target::StructuredTarget, flow::StickyFlow(F), upper_bounds::
     StickyUpperBounds(G, G1, Γ, c; adapt, strong, multiplier=factor), barriers, EndTime(T)) (src/stickyzz.jl:176-218) with G = G1 = the pattern of
     F.Γ, in the call shape of the other samplers.  barriers: a list of d StickyBarriers, or one for all coordinates.  Returns
     Ξ, t′, (t, x, θ), (acc, num) like the reference (:217); x0 / θ0 may be [nchains, d] (outputs then carry a leading chain axis).  Box
     constraints, truncated Gaussians, positivity constraints, sticking at any level with its own stickiness on either side.
 
-    details=True (engine-only keyword) appends a dict: c (the bounds after adaptation), frozen (v == 0 and v_old != 0) and θ_saved (v_old)."""
+    details=True (engine-only keyword) appends a dict: c (the bounds after adaptation), frozen (v == 0 and v_old != 0) and θ_saved (v_old).
+
+    consume=dict(dt=..., points=...[, cov=P, center=c][, condition=(p, n), hits=K]) (engine-only keyword): the device consumers
+    (Ensemble.barrier_consume_begin) run over every slice before its buffer is recycled, and a dict is appended behind everything else: mean,
+    T, grid_t, grid_x as in spdmp, frozen_lo / frozen_hi (the time each coordinate sat frozen on its lower / upper barrier) and hits_lo /
+    hits_hi (how often it hit each) -- trace.barrier_occupation, raw sums over [t0, T] --, plus pairs / pair_S / pair_J and hit_t / hit_x /
+    nhits where asked for.  The consumers follow the path the chain travelled -- a coordinate that starts on the barrier of its θ0 starts with
+    θ = 0 --, i.e. the host mirrors on FactTrace(F, t0, x0, trace.barrier_start(x0, θ0, barriers)[0], Ξ.events), not on the returned Ξ, which
+    records θ0 like the reference's Trace(t′, x0, v0).  With trace=False the events are written to the device buffer and consumed, never
+    copied to the host.  Without the keyword, returns and behaviour are unchanged."""
     if not isinstance(F, ZigZag) or isinstance(F, FactBoomerang):
         raise TypeError("stickyzz takes F::ZigZag (StickyFlow(F), src/stickyzz.jl:28-30)")
     d = np.asarray(x0).shape[-1]
@@ -330,22 +339,23 @@ def stickyzz(target, t0, x0, θ0, T, c, F, barriers, *, strong_upperbounds=False
            np.array([_lib.BARRIER_RULES[b.rule[1]] for b in barriers], dtype=np.int32),
            np.array([b.κ[0] for b in barriers]), np.array([b.κ[1] for b in barriers]), strong_upperbounds)
     return _zigzag(_lib.SAMPLER_BARRIER_ZIGZAG, target, t0, x0, θ0, T, c, F, factor, adapt, seed, device, trace_capacity, trace,
-                   barriers=tab, details=details)
+                   barriers=tab, details=details, consume=consume)
 
 
 def sspdmp2(target, t0, x0, θ0, T, c, G, Z, κ, *, strong_upperbounds=False, adapt=False, factor=1.5, seed=DEFAULT_SEED, device=0,
-            trace_capacity=None, trace=True):
+            trace_capacity=None, trace=True, consume=None):
     """sspdmp2(∇ϕ2, t, x0, v0, T, c, ::Nothing, Z, κ, args...; strong_upperbounds, adapt, factor=1.5) (src/stickyzz.jl:323-339): the sticky
     ZigZag written with the barrier framework -- barriers (0, 0), (:sticky, :sticky), (κ[i], κ[i]) on every coordinate.  Returns (trace, acc)
-    like the reference (:338), acc being the pair (acc, num)."""
+    like the reference (:338), acc being the pair (acc, num).  consume=... as in stickyzz: (trace, acc, consumed); the posterior inclusion
+    probability is 1 − (frozen_lo + frozen_hi) / (T − t0)."""
     if G is not None:
         raise TypeError("sspdmp2(∇ϕ2, t, x0, v0, T, c, ::Nothing, Z, κ, ...): the seventh argument is None (src/stickyzz.jl:323)")
     d = np.asarray(x0).shape[-1]
     κ = np.broadcast_to(np.asarray(κ, dtype=np.float64), (d,))
     barriers = [StickyBarriers((0.0, 0.0), ("sticky", "sticky"), (κ[i], κ[i])) for i in range(d)]
-    Ξ, _, _, acc = stickyzz(target, t0, x0, θ0, T, c, Z, barriers, strong_upperbounds=strong_upperbounds, adapt=adapt, factor=factor, seed=seed,
-                            device=device, trace_capacity=trace_capacity, trace=trace)
-    return Ξ, acc
+    Ξ, _, _, acc, *consumed = stickyzz(target, t0, x0, θ0, T, c, Z, barriers, strong_upperbounds=strong_upperbounds, adapt=adapt, factor=factor,
+                                       seed=seed, device=device, trace_capacity=trace_capacity, trace=trace, consume=consume)
+    return (Ξ, acc, *consumed)
 
 
 class Partition:
@@ -468,7 +478,7 @@ def _zigzag(sampler, target, t0, x0, θ0, T, c, F, factor, adapt, seed, device, 
         raise TypeError("the device path supports F::ZigZag and F::FactBoomerang")
     if not isinstance(target, (GaussianTarget, LogisticTarget, DiffusionBridgeTarget)):
         raise TypeError("target must be one of the device-resident families (GaussianTarget, LogisticTarget, DiffusionBridgeTarget)")
-    if consume is not None and not isinstance(target, DiffusionBridgeTarget) and not (isinstance(consume, dict) and "cov" in consume):
+    if consume is not None and barriers is None and not isinstance(target, DiffusionBridgeTarget) and not (isinstance(consume, dict) and "cov" in consume):
         raise TypeError("consume is a keyword of spdmp with a DiffusionBridgeTarget, or with cov=P (elsewhere the ZigZag's device consumers are "
                         "Ensemble.consume_*)")
     x0 = np.asarray(x0, dtype=np.float64)
@@ -508,7 +518,8 @@ def _zigzag(sampler, target, t0, x0, θ0, T, c, F, factor, adapt, seed, device, 
             ens.set_gradient_tracking(True)
         ens.set_state(t0, X0, TH0, c, seeds)
         if consume is not None:
-            ens.consume_begin(float(consume.get("dt", 0.0)), int(consume.get("points", 0)))
+            begin = ens.consume_begin if barriers is None else ens.barrier_consume_begin
+            begin(float(consume.get("dt", 0.0)), int(consume.get("points", 0)))
             if _condition_of(consume) is not None:
                 ens.consume_condition(*_condition_of(consume))
             if _pairs_of(consume, d) is not None:
@@ -531,6 +542,9 @@ def _zigzag(sampler, target, t0, x0, θ0, T, c, F, factor, adapt, seed, device, 
         if consume is not None:
             mean, Tl = ens.consume_mean()
             consumed = dict(mean=mean, T=Tl, grid_t=None, grid_x=None)
+            if barriers is not None:
+                occ = ens.barrier_consume_occupation()
+                consumed.update(frozen_lo=occ[0], frozen_hi=occ[1], hits_lo=occ[2], hits_hi=occ[3])
             if int(consume.get("points", 0)) > 0:
                 grids = [ens.consume_discretized(k) for k in range(nch)]
                 consumed["grid_t"], consumed["grid_x"] = [g[0] for g in grids], [g[1] for g in grids]
@@ -566,10 +580,11 @@ def _zigzag(sampler, target, t0, x0, θ0, T, c, F, factor, adapt, seed, device, 
         acc = cnt["nacc"].astype(np.int64)
         tp = cnt["t_last"].astype(np.float64)
         extra = dict(c=c_out, frozen=fb["frozen"], θ_saved=fb["theta_saved"])
+        tail = () if consumed is None else (consumed,)
         if single:
             out = traces[0], float(tp[0]), (fs["t"][0], fs["x"][0], fs["theta"][0]), (int(acc[0]), int(num[0]))
-            return out + (({k: v[0] for k, v in extra.items()},) if details else ())
-        return (traces, tp, (fs["t"], fs["x"], fs["theta"]), (acc, num)) + ((extra,) if details else ())
+            return out + (({k: v[0] for k, v in extra.items()},) if details else ()) + tail
+        return (traces, tp, (fs["t"], fs["x"], fs["theta"]), (acc, num)) + ((extra,) if details else ()) + tail
     tail = () if consumed is None else (consumed,)
     if single:
         return (traces[0], (fs["t"][0], fs["x"][0], fs["theta"][0]), (acc[0], int(num[0])), c_out[0]) + tail

@@ -323,6 +323,64 @@ def inclusion_prob(tr: FactTrace):
     return np.bincount(i, weights=((xp != 0) | (ev["x"] != 0)) * dt / T, minlength=tr.x0.size)
 
 
+def _barrier_levels(barriers, d):
+    """(lo, hi) [d] of a list of d StickyBarriers -- or plain ((lo, hi), rules, κ) triples --, or of one for all coordinates"""
+    def one(b):
+        return hasattr(b, "x") or (isinstance(b, tuple) and len(b) == 3 and isinstance(b[1], tuple) and isinstance(b[1][0], str))
+
+    bl = [barriers] * d if one(barriers) else list(barriers)
+    if len(bl) != d:
+        raise ValueError("barriers: a list of %d StickyBarriers, or one for all coordinates" % d)
+    x = [b.x if hasattr(b, "x") else b[0] for b in bl]
+    return np.array([float(v[0]) for v in x]), np.array([float(v[1]) for v in x])
+
+
+def barrier_start(x0, θ0, barriers):
+    """(θ_eff, side0) of a stickyzz start (src/stickyzz.jl:198-208): a coordinate whose x0[i] equals the barrier in the direction of θ0[i] -- the
+    upper one for θ0[i] > 0, else the lower one -- starts frozen.  θ_eff is θ0 with 0 there: the velocities of the path the chain travels, and
+    the start (t0, x0, θ_eff) the device consumers of a barrier ensemble work from (Ensemble.barrier_consume_begin).  The host mirrors (mean,
+    discretize, cummean, pair_integrals, conditional_trace) agree with them on FactTrace(F, t0, x0, θ_eff, events); on the trace a sampler
+    returns, which records θ0 like the reference's Trace(t′, x0, v0), they extrapolate a frozen start with a speed it never had.  side0 [.. x d]:
+    1 where θ0 > 0 (upper barrier), else 0.  x0 / θ0 may carry a leading chain axis."""
+    x0 = np.asarray(x0, dtype=np.float64)
+    θ0 = np.asarray(θ0, dtype=np.float64)
+    lo, hi = _barrier_levels(barriers, x0.shape[-1])
+    up = θ0 > 0
+    frozen = x0 == np.where(up, hi, lo)
+    return np.where(frozen, 0.0, θ0), up.astype(np.int64)
+
+
+def barrier_occupation(Ξ, t0, x0, θ0, barriers):
+    """(frozen_lo, frozen_hi [d] float64, hits_lo, hits_hi [d] uint64, T_last): how long each coordinate of a stickyzz / sspdmp2 trace sat
+    frozen (θ = 0) on its lower and on its upper barrier over [t0, T_last], and how often it hit each -- raw sums, the caller divides; the
+    host mirror of Ensemble.barrier_consume_occupation, bit for bit (DESIGN.md "Barrier occupation").  Ξ: a FactTrace or its events; (t0,
+    x0, θ0): the start as the sampler was given it (θ0 ≠ 0 everywhere; barrier_start tells which coordinates start frozen, and on which side).
+
+    Per coordinate, a cursor (t_c, θ_c) from (t0, θ_eff) and a side s from side0; for each of its events (t, x, θ) in trace order:
+    θ_c == 0: z[s] += t − t_c;  θ == 0 and θ_c ≠ 0 (a hit): s = upper iff θ_c > 0, n[s] += 1;  then the cursor takes (t, θ).  A θ == 0 event
+    behind θ_c == 0 counts nothing.  −0.0 counts as 0.  A coordinate still frozen at the end is extended to T_last, the last event time of the
+    whole trace (t0 without events).  A wall's hit and thaw at one time: one hit, no time.  Sums run sequentially per coordinate in float64."""
+    ev = Ξ.events if isinstance(Ξ, FactTrace) else Ξ
+    x0 = np.asarray(x0, dtype=np.float64).reshape(-1)
+    d = x0.size
+    th_eff, side0 = barrier_start(x0, np.asarray(θ0, dtype=np.float64).reshape(-1), barriers)
+    tc = [float(t0)] * d
+    thc = [float(v) for v in th_eff]
+    side = [int(s) for s in side0]
+    z = [[0.0, 0.0] for _ in range(d)]
+    n = np.zeros((d, 2), dtype=np.uint64)
+    for t, i, th in zip(ev["t"].tolist(), ev["i"].tolist(), ev["theta"].tolist()):
+        if thc[i] == 0.0:
+            z[i][side[i]] += t - tc[i]
+        if th == 0.0 and thc[i] != 0.0:
+            side[i] = 1 if thc[i] > 0.0 else 0
+            n[i, side[i]] += np.uint64(1)
+        tc[i], thc[i] = t, th
+    T_last = float(ev["t"][-1]) if len(ev) else float(t0)
+    out = np.array([[z[i][s] + ((T_last - tc[i]) if (thc[i] == 0.0 and s == side[i]) else 0.0) for s in (0, 1)] for i in range(d)]).reshape(d, 2)
+    return out[:, 0].copy(), out[:, 1].copy(), n[:, 0].copy(), n[:, 1].copy(), T_last
+
+
 def _dot_wave64(A, B):
     """Row-wise dot(A[r], B[r]) in the one order the device and the oracle sum in (dot_wave64, oracle/pdmp_oracle.c): lane l adds the
     products of elements l, l + 64, ... in order, then the lanes are combined by the xor butterfly 1, 2, 4, 8, 16, 32."""
