@@ -28,6 +28,8 @@ HEADERS = [os.path.join(CSRC, "pdmp_engine.hpp"),
            os.path.join(CSRC, "pdmp_ensemble.hpp"),  # (the host units pdmp_capi*.hip: error reporting, the device buffer, the ensemble)
            os.path.join(CSRC, "pdmp_device.hpp"),  # (the scalar and wave-level helpers every event-loop unit shares)
            os.path.join(CSRC, "pdmp_spec8_common.hpp"),  # (the 8-event loop's machinery, shared by pdmp_kernels.hip's three kernels of it)
+           os.path.join(CSRC, "pdmp_spec4_common.hpp"),  # (the 4-event loop's machinery, shared by pdmp_kernels.hip's ZigZag and sticky kernels of it)
+           os.path.join(CSRC, "pdmp_zz_refresh.hpp"),  # (the refresh-clock event, shared by the four blob-fed ZigZag loops)
            os.path.join(CSRC, "pdmp_spec8g.inc"),  # (included by pdmp_kernels.hip)
            os.path.join(CSRC, "pdmp_bps_common.hpp"),  # (the Bouncy Particle family's wave-level machinery, shared by pdmp_bps.hip's six kernels)
            os.path.join(CSRC, "pdmp_bps_sticky.inc"),  # (included by pdmp_bps.hip)

@@ -54,7 +54,7 @@ __global__ __launch_bounds__(64) void zz_barrier_run_kernel(ZzRunParams P) {
     double* cmut = P.c_chain ? (P.c_chain + chain * d) : nullptr;
 
     uint32_t status = hdr->c.status;
-    if (status == PDMP_CHAIN_BOUND_VIOLATED || status == PDMP_CHAIN_STALLED) return;
+    if (chain_ended(status)) return;
     const uint64_t seed = hdr->seed;
     const uint64_t nm0 = hdr->c.ndraw_main;
     uint64_t nm = nm0;
@@ -66,22 +66,7 @@ __global__ __launch_bounds__(64) void zz_barrier_run_kernel(ZzRunParams P) {
     const bool stop_before = (P.flags & PDMP_RUN_STOP_BEFORE) != 0;
     const bool adapt = P.adapt != 0;
 
-    // ---- level 1 of the queue from the keys in HBM (each lane scans whole blocks)
-    for (uint32_t b = lane; b < nblk; b += 64) {
-        const double* kp = keys + (size_t)b * 64;
-        double mk = kp[0];
-        uint32_t mi = 0;
-#pragma unroll 8
-        for (int q = 1; q < 64; ++q) {
-            const double v = kp[q];
-            if (v < mk) {
-                mk = v;
-                mi = q;
-            }
-        }
-        bk[b] = mk;
-        bi[b] = b * 64 + mi;
-    }
+    level1_build(bk, bi, keys, nblk, lane);
     PDMP_LDS_ORDER();
 
     auto queue_update = [&](uint32_t j, double kj) {
@@ -142,16 +127,9 @@ __global__ __launch_bounds__(64) void zz_barrier_run_kernel(ZzRunParams P) {
             LU[lane] = pdmp_log(u);
         }
         PDMP_LDS_ORDER();
-        const uint64_t hw = lb[0];
-        const int k = (int)uniform_u32((uint32_t)(hw & 0xff));
-        const int m = (int)uniform_u32((uint32_t)((hw >> 8) & 0xff));
-        const int self = (int)uniform_u32((uint32_t)((hw >> 16) & 0xff));
-        const int kjmax = (int)uniform_u32((uint32_t)((hw >> 24) & 0xff));
-        uint32_t s = i;
-        if (lane < m) {
-            const uint64_t sw = lb[1 + (lane >> 1)];
-            s = i + ((lane & 1) ? (uint32_t)(sw >> 32) : (uint32_t)sw);
-        }
+        const BlobHeader bh = blob_header_uniform(lb[0]);
+        const int k = bh.k, m = bh.m, self = bh.self, kjmax = bh.kjmax;
+        const uint32_t s = (lane < m) ? blob_member(lb, i, lane) : i;
         ZzRec* rs = rec + s;
         double x = 0.0, th = 0.0, t = 0.0, I = 0.0;
         if (lane < m) {

@@ -37,8 +37,8 @@ __device__ __forceinline__ double line_piece(double a, double vi, double tau) { 
 // draw indices a randn(rng, d) takes (BpsWave::normals): one Box-Muller block per two elements, whole 64-lane rows of blocks
 __device__ __forceinline__ uint64_t normal_draws(int64_t d) { return (uint64_t)(((d + 127) >> 7) << 6); }
 
-// a chain that ended for good (the reference's error(...), or no finite next event) is not run again
-__device__ __forceinline__ bool bps_chain_ended(uint32_t status) { return status == PDMP_CHAIN_BOUND_VIOLATED || status == PDMP_CHAIN_STALLED; }
+// (the status gate of every event loop: chain_ended, pdmp_device.hpp)
+__device__ __forceinline__ bool bps_chain_ended(uint32_t status) { return chain_ended(status); }
 
 // the header counters an event loop advances, in registers from its first line to its last
 struct BpsCounters {

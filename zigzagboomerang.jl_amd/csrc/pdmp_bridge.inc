@@ -30,7 +30,7 @@ __global__ __launch_bounds__(64) void zz_bridge_run_kernel(ZzRunParams P, ZzBrid
     const double* cvec = cmut ? cmut : P.tb.c_shared;
 
     uint32_t status = hdr->c.status;
-    if (status == PDMP_CHAIN_BOUND_VIOLATED || status == PDMP_CHAIN_STALLED) return;
+    if (chain_ended(status)) return;
     const uint64_t seed = hdr->seed;
     const uint64_t nm0 = hdr->c.ndraw_main;
     uint64_t nm = nm0, ng = hdr->c.ndraw_global;
@@ -53,22 +53,7 @@ __global__ __launch_bounds__(64) void zz_bridge_run_kernel(ZzRunParams P, ZzBrid
     // the end points are fixed (θ = 0, c = 0: pdmp_ensemble_set_state checks it): never moved, never popped, read once
     const double x_first = rec[0].x, x_last = rec[d - 1].x;
 
-    // ---- level 1 of the queue from the keys in HBM (each lane scans one block)
-    if ((uint32_t)lane < nblk) {
-        const double* kp = keys + (size_t)lane * 64;
-        double mk = kp[0];
-        uint32_t mi = 0;
-#pragma unroll 8
-        for (int q = 1; q < 64; ++q) {
-            const double v = kp[q];
-            if (v < mk) {
-                mk = v;
-                mi = q;
-            }
-        }
-        bk[lane] = mk;
-        bi[lane] = (uint32_t)lane * 64 + mi;
-    }
+    level1_build(bk, bi, keys, nblk, lane);  // (nblk <= 64 here: each lane scans one block)
     PDMP_LDS_ORDER();
 
     bool running = stop_before || (t_event < T);  // `while t′ < T′`, src/sfact.jl:199

@@ -9,6 +9,7 @@
 #include <type_traits>
 
 #include "../../include/pdmp_detmath.h"
+#include "../../include/pdmp_mi355.h"  // (the PDMP_CHAIN_* status words)
 
 #define PDMP_INF __builtin_inf()
 
@@ -192,6 +193,67 @@ __device__ __forceinline__ void level1_update(double* bk, uint32_t* bi, const do
             bi[bj] = bj * 64 + (uint32_t)arg;
         }
     }
+}
+
+// Level 1 from the keys in HBM, at the start of a launch: (min, argmin) of each 64-key block, lowest index on ties.  Each lane scans
+// whole blocks; the caller orders LDS (PDMP_LDS_ORDER) before it reads the entries.
+__device__ __forceinline__ void level1_build(double* bk, uint32_t* bi, const double* keys, uint32_t nblk, int lane) {
+    for (uint32_t b = lane; b < nblk; b += 64) {
+        const double* kp = keys + (size_t)b * 64;
+        double mk = kp[0];
+        uint32_t mi = 0;
+#pragma unroll 8
+        for (int q = 1; q < 64; ++q) {
+            const double v = kp[q];
+            if (v < mk) {
+                mk = v;
+                mi = q;
+            }
+        }
+        bk[b] = mk;
+        bi[b] = b * 64 + mi;
+    }
+}
+
+// ------------------------------------------------------------------------------------------ launch prologue
+
+// a chain that ended for good (the reference's error(...), or no finite next event) is not run again
+__device__ __forceinline__ bool chain_ended(uint32_t status) {
+    return status == PDMP_CHAIN_BOUND_VIOLATED || status == PDMP_CHAIN_STALLED;
+}
+// events a launch may still record: the room left in the chain's trace (trace_cap == 0: no trace, no limit)
+__device__ __forceinline__ uint32_t launch_trace_room(int64_t trace_cap, uint64_t ntrace0) {
+    return (trace_cap > 0) ? (uint32_t)(((uint64_t)trace_cap > ntrace0) ? ((uint64_t)trace_cap - ntrace0) : 0) : 0xffffffffu;
+}
+
+// ------------------------------------------------------------------------------------------ neighbourhood blob
+
+// Word 0 of a coordinate's blob (built on the host, pdmp_capi_zigzag.hip): k = |G1[i]|, m = |S[i]|, self = the position of i inside
+// S[i], kjmax = max |G1[j]| over j in G1[i], one byte each.
+struct BlobHeader {
+    int k, m, self, kjmax;
+};
+__device__ __forceinline__ BlobHeader blob_header(uint64_t hw) {
+    BlobHeader h;
+    h.k = (int)(hw & 0xff);
+    h.m = (int)((hw >> 8) & 0xff);
+    h.self = (int)((hw >> 16) & 0xff);
+    h.kjmax = (int)((hw >> 24) & 0xff);
+    return h;
+}
+// the same, wave-uniform (a kernel whose whole wave works on one event)
+__device__ __forceinline__ BlobHeader blob_header_uniform(uint64_t hw) {
+    BlobHeader h;
+    h.k = (int)uniform_u32((uint32_t)(hw & 0xff));
+    h.m = (int)uniform_u32((uint32_t)((hw >> 8) & 0xff));
+    h.self = (int)uniform_u32((uint32_t)((hw >> 16) & 0xff));
+    h.kjmax = (int)uniform_u32((uint32_t)((hw >> 24) & 0xff));
+    return h;
+}
+// Member `pos` of S[i]: the ids follow the header two to a word, stored relative to i.  lb = the blob.
+__device__ __forceinline__ uint32_t blob_member(const uint64_t* lb, uint32_t i, int pos) {
+    const uint64_t sw = lb[1 + (pos >> 1)];
+    return i + ((pos & 1) ? (uint32_t)(sw >> 32) : (uint32_t)sw);
 }
 
 // ------------------------------------------------------------------------------------------ contract scalars

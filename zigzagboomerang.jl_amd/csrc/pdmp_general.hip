@@ -88,7 +88,7 @@ __global__ __launch_bounds__(64) void zz_general_run_kernel(ZzRunParams P_in, Zz
     double* rnw = local ? (Q.renew_chain + chain * d) : nullptr;
 
     uint32_t status = hdr->c.status;
-    if (status == PDMP_CHAIN_BOUND_VIOLATED || status == PDMP_CHAIN_STALLED) return;
+    if (chain_ended(status)) return;
     const uint64_t seed = hdr->seed;
     uint64_t nm = hdr->c.ndraw_main, ng = hdr->c.ndraw_global;
     uint64_t num = hdr->c.num, nacc = hdr->c.nacc, ntrace = hdr->c.ntrace, nevents = hdr->c.nevents;
@@ -114,21 +114,7 @@ __global__ __launch_bounds__(64) void zz_general_run_kernel(ZzRunParams P_in, Zz
         }                                                                 \
     } while (0)
 
-    for (uint32_t b = lane; b < nblk; b += 64) {
-        const double* kp = keys + (size_t)b * 64;
-        double mk = kp[0];
-        uint32_t mi = 0;
-#pragma unroll 8
-        for (int q = 1; q < 64; ++q) {
-            const double v = kp[q];
-            if (v < mk) {
-                mk = v;
-                mi = q;
-            }
-        }
-        bk[b] = mk;
-        bi[b] = b * 64 + mi;
-    }
+    level1_build(bk, bi, keys, nblk, lane);
     PDMP_LDS_ORDER();
 
     // level 1 of the queue after keys[] of G1[i][jj0 .. jj1) (and optionally of one extra coordinate) changed: every 64-key

@@ -23,7 +23,9 @@
 #include "../../include/pdmp_detmath.h"
 #include "pdmp_device.hpp"
 #include "pdmp_engine.hpp"
+#include "pdmp_spec4_common.hpp"
 #include "pdmp_spec8_common.hpp"
+#include "pdmp_zz_refresh.hpp"
 
 namespace pdmp {
 
@@ -230,7 +232,7 @@ __global__ __launch_bounds__(64) void zz_local_run_kernel(ZzRunParams P) {
     double* cmut = P.c_chain ? (P.c_chain + chain * d) : nullptr;
 
     uint32_t status = hdr->c.status;
-    if (status == PDMP_CHAIN_BOUND_VIOLATED || status == PDMP_CHAIN_STALLED) return;
+    if (chain_ended(status)) return;
     const uint64_t seed = hdr->seed;
     uint64_t nm = hdr->c.ndraw_main, ng = hdr->c.ndraw_global;
     uint64_t num = hdr->c.num, nacc = hdr->c.nacc, ntrace = hdr->c.ntrace, nevents = hdr->c.nevents;
@@ -246,39 +248,10 @@ __global__ __launch_bounds__(64) void zz_local_run_kernel(ZzRunParams P) {
     const bool move_all = P.move_all != 0;
 
     // smove_forward!(::All, ...) = move every coordinate (src/sfact.jl:19,23-28): the `pdmp` driver, G = All()
-    auto sweep_all = [&](double tnew) {
-        for (int64_t q = lane; q < d; q += 64) {
-            ZzRec* r = rec + q;
-            const double x0 = r->x, th0 = r->th, t0 = r->t, I0 = r->I;
-            const double dt = tnew - t0;
-            const double xn = x0 + th0 * dt;
-            r->x = xn;
-            r->t = tnew;
-            r->I = I0 + dt * ((x0 + xn) * 0.5);
-        }
-    };
-    // generic level-1 update for one changed key (j, kj) whose new value is already stored in keys[]
-    auto queue_update = [&](uint32_t j, double kj) {
-        level1_update(bk, bi, keys, lane, j, kj);
-        PDMP_LDS_ORDER();
-    };
+    auto sweep_all = [&](double tnew) { zz_sweep_all(rec, d, lane, tnew); };
 
-    // ---- rebuild level 1 of the queue from the keys in HBM (each lane scans whole blocks)
-    for (uint32_t b = lane; b < nblk; b += 64) {
-        const double* kp = keys + (size_t)b * 64;
-        double mk = kp[0];
-        uint32_t mi = 0;
-#pragma unroll 8
-        for (int q = 1; q < 64; ++q) {
-            const double v = kp[q];
-            if (v < mk) {
-                mk = v;
-                mi = q;
-            }
-        }
-        bk[b] = mk;
-        bi[b] = b * 64 + mi;
-    }
+    // ---- rebuild level 1 of the queue from the keys in HBM
+    level1_build(bk, bi, keys, nblk, lane);
     PDMP_LDS_ORDER();
 
     bool running = stop_before || (t_event < T);  // `while t′ < T`, src/sfact.jl:199
@@ -316,123 +289,17 @@ __global__ __launch_bounds__(64) void zz_local_run_kernel(ZzRunParams P) {
         t_last = tp;
 
         if (has_refresh && i == (uint32_t)d) {
-            // ---------------- refresh clock popped: src/sfact.jl:78-114 (restated with its quirks: the coordinate whose
-            // neighbourhood is moved (:80) and the coordinate that is refreshed (:84) are two independent draws from the
-            // "global rng" stream, and G1[i] is re-bounded at the coordinates' own, possibly stale, clocks)
-            const uint32_t i1 = pdmp_randint(seed, PDMP_STREAM_GLOBAL, ng, (uint32_t)d);
-            ng += 1;
-            if (move_all) {
-                sweep_all(tp);
-            } else {
-                const uint64_t* bsrc = P.blob + (size_t)P.tix[i1] * P.blob_w_pad;
-                for (uint32_t w = lane; w < W; w += 64) lb[w] = bsrc[w];
-                PDMP_LDS_ORDER();
-                const int k1 = (int)uniform_u32((uint32_t)(lb[0] & 0xff));
-                if (lane < k1) {
-                    const uint64_t sw = lb[1 + (lane >> 1)];
-                    const uint32_t s1 = i1 + ((lane & 1) ? (uint32_t)(sw >> 32) : (uint32_t)sw);  // ids are stored relative to i
-                    ZzRec* r1 = rec + s1;
-                    const double x0 = r1->x, th0 = r1->th, t0 = r1->t, I0 = r1->I;
-                    const double dt = tp - t0;
-                    const double xn = x0 + th0 * dt;
-                    r1->x = xn;
-                    r1->t = tp;
-                    r1->I = I0 + dt * ((x0 + xn) * 0.5);
-                }
-                PDMP_LDS_ORDER();
-            }
-            const uint32_t i2 = pdmp_randint(seed, PDMP_STREAM_GLOBAL, ng, (uint32_t)d);
-            ng += 1;
-            {
-                const uint64_t* bsrc = P.blob + (size_t)P.tix[i2] * P.blob_w_pad;
-                for (uint32_t w = lane; w < W; w += 64) lb[w] = bsrc[w];
-            }
-            PDMP_LDS_ORDER();
-            const uint64_t hw = lb[0];
-            const int k = (int)uniform_u32((uint32_t)(hw & 0xff));
-            const int m = (int)uniform_u32((uint32_t)((hw >> 8) & 0xff));
-            const int self = (int)uniform_u32((uint32_t)((hw >> 16) & 0xff));
-            const int kjmax = (int)uniform_u32((uint32_t)((hw >> 24) & 0xff));
-            uint32_t s = i2;
-            if (lane < m) {
-                const uint64_t sw = lb[1 + (lane >> 1)];
-                s = i2 + ((lane & 1) ? (uint32_t)(sw >> 32) : (uint32_t)sw);
-            }
-            ZzRec* rs = rec + s;
-            double x = 0.0, th = 0.0, t = 0.0, I = 0.0;
-            if (lane < m) {
-                x = rs->x;
-                th = rs->th;
-                t = rs->t;
-                I = rs->I;
-            }
-            if (!move_all && lane >= k && lane < m) {  // smove_forward!(G2, i, ...), :85
-                const double dt = tp - t;
-                const double xn = x + th * dt;
-                I = I + dt * ((x + xn) * 0.5);
-                x = xn;
-                t = tp;
-            }
-            const double usign = pdmp_u01(seed, PDMP_STREAM_MAIN, nm);  // θ[i] = σ[i]*rand(rng, (-1,1)), :100-101
-            nm += 1;
-            if (lane == self) th = P.tb.sigma[i2] * ((usign < 0.5) ? -1.0 : 1.0);
-            // Q[n+1] = t′ + waiting_time_ref(F) = t′ + randexp()/λref from the global rng, :108
-            const double newref = tp + (-pdmp_log(pdmp_u01(seed, PDMP_STREAM_GLOBAL, ng))) / P.lambda_ref;
-            ng += 1;
-            if (lane < m) {
-                sx[lane] = x;
-                sth[lane] = th;
-            }
-            PDMP_LDS_ORDER();
-            const uint32_t sub = 1 + SW + (uint32_t)lane * R;
-            double key = PDMP_INF;
-            if (lane < k) {  // :110-114
-                const double gmu = __longlong_as_double((long long)lb[sub + 1]);
-                const double cj = cmut ? cmut[s] : __longlong_as_double((long long)lb[sub + 2]);
-                const int kj = (int)(lb[sub + 3] & 0xff);
-                double gx = 0.0, gt = 0.0;
-                for (int base = 0; base < kjmax; base += 8) {
-                    const uint64_t pw = lb[sub + 4 + (base >> 3)];
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) {
-                        const int pp = base + q;
-                        if (pp < kj) {
-                            const double v = __longlong_as_double((long long)lb[sub + 4 + PW + pp]);
-                            const int ps = (int)((pw >> (8 * q)) & 0xff);
-                            gx += v * sx[ps];
-                            gt += v * sth[ps];
-                        }
-                    }
-                }
-                const double a = cj + (gx - gmu) * th;
-                const double b = cj / 100 + th * gt;
-                const double L = pdmp_log(pdmp_u01(seed, PDMP_STREAM_MAIN, nm + (uint64_t)lane));
-                key = t + poisson_time_L(a, b, L);  // Q[j] = t[j] + poisson_time(...): t[j] is j's OWN clock here
-                rs->t_old = t;
-                rs->a = a;
-                rs->b = b;
-                keys[s] = key;
-            }
-            nm += (uint64_t)k;
-            if (lane < m) {
-                rs->x = x;
-                rs->th = th;
-                rs->t = t;
-                rs->I = I;
-            }
-            if (lane == 0) keys[d] = newref;
-            for (int jj = 0; jj <= k; ++jj) {
-                const uint32_t j = (jj < k) ? readlane_u32(s, jj) : (uint32_t)d;
-                const double kj = (jj < k) ? readlane_f64(key, jj < k ? jj : 0) : newref;
-                queue_update(j, kj);
-            }
-            const double t_i = readlane_f64(t, self), x_i = readlane_f64(x, self), th_i2 = readlane_f64(th, self);
+            // ---------------- refresh clock popped: src/sfact.jl:78-114 (zz_refresh_event; the clock is key d of the queue)
+            const ZzRefreshed rf = zz_refresh_event<true, 0>(P, BlobGeom{W, P.blob_w_pad, SW, PW, R}, rec, keys, cmut, d, seed, nm, ng, tp, lane, lb, sx,
+                                                          sth, move_all, Level1Blocks64{bk, bi});
+            nm += rf.ndraw;
+            ng = rf.ng;
             if (ev && lane == 0) {  // event(i, t, x, θ, F) = (t[i], i, x[i], θ[i]), :143
                 pdmp_event e;
-                e.t = t_i;
-                e.i = (int64_t)i2;
-                e.x = x_i;
-                e.theta = th_i2;
+                e.t = rf.t;
+                e.i = (int64_t)rf.i2;
+                e.x = rf.x;
+                e.theta = rf.th;
                 ev[ntrace] = e;
             }
             nrefresh += 1;
@@ -473,16 +340,9 @@ __global__ __launch_bounds__(64) void zz_local_run_kernel(ZzRunParams P) {
 
         // ---------------- neighbourhood header and member list from the blob (now in LDS)
         PDMP_LDS_ORDER();
-        const uint64_t hw = lb[0];
-        const int k = (int)uniform_u32((uint32_t)(hw & 0xff));
-        const int m = (int)uniform_u32((uint32_t)((hw >> 8) & 0xff));
-        const int self = (int)uniform_u32((uint32_t)((hw >> 16) & 0xff));
-        const int kjmax = (int)uniform_u32((uint32_t)((hw >> 24) & 0xff));
-        uint32_t s = i;
-        if (lane < m) {
-            const uint64_t sw = lb[1 + (lane >> 1)];
-            s = i + ((lane & 1) ? (uint32_t)(sw >> 32) : (uint32_t)sw);
-        }
+        const BlobHeader bh = blob_header_uniform(lb[0]);
+        const int k = bh.k, m = bh.m, self = bh.self, kjmax = bh.kjmax;
+        const uint32_t s = (lane < m) ? blob_member(lb, i, lane) : i;
         ZzRec* rs = rec + s;
         // ---------------- level-2 loads: positions of G[i] and (speculatively) of G2[i]
         double x = 0.0, th = 0.0, t = 0.0, I = 0.0;
@@ -718,7 +578,7 @@ __global__ __launch_bounds__(64) void zz_sticky_run_kernel(ZzRunParams P) {
     double* cmut = P.c_chain ? (P.c_chain + chain * d) : nullptr;
 
     uint32_t status = hdr->c.status;
-    if (status == PDMP_CHAIN_BOUND_VIOLATED || status == PDMP_CHAIN_STALLED) return;
+    if (chain_ended(status)) return;
     const uint64_t seed = hdr->seed;
     uint64_t nm = hdr->c.ndraw_main;
     uint64_t num = hdr->c.num, nacc = hdr->c.nacc, ntrace = hdr->c.ntrace, nevents = hdr->c.nevents;
@@ -729,21 +589,7 @@ __global__ __launch_bounds__(64) void zz_sticky_run_kernel(ZzRunParams P) {
     const bool stop_before = (P.flags & PDMP_RUN_STOP_BEFORE) != 0;
     const bool adapt = P.adapt != 0;
 
-    for (uint32_t b = lane; b < nblk; b += 64) {
-        const double* kp = keys + (size_t)b * 64;
-        double mk = kp[0];
-        uint32_t mi = 0;
-#pragma unroll 8
-        for (int q = 1; q < 64; ++q) {
-            const double v = kp[q];
-            if (v < mk) {
-                mk = v;
-                mi = q;
-            }
-        }
-        bk[b] = mk;
-        bi[b] = b * 64 + mi;
-    }
+    level1_build(bk, bi, keys, nblk, lane);
     PDMP_LDS_ORDER();
 
     auto queue_update = [&](uint32_t j, double kj) {
@@ -799,16 +645,9 @@ __global__ __launch_bounds__(64) void zz_sticky_run_kernel(ZzRunParams P) {
             LU[lane] = pdmp_log(u);
         }
         PDMP_LDS_ORDER();
-        const uint64_t hw = lb[0];
-        const int k = (int)uniform_u32((uint32_t)(hw & 0xff));
-        const int m = (int)uniform_u32((uint32_t)((hw >> 8) & 0xff));
-        const int self = (int)uniform_u32((uint32_t)((hw >> 16) & 0xff));
-        const int kjmax = (int)uniform_u32((uint32_t)((hw >> 24) & 0xff));
-        uint32_t s = i;
-        if (lane < m) {
-            const uint64_t sw = lb[1 + (lane >> 1)];
-            s = i + ((lane & 1) ? (uint32_t)(sw >> 32) : (uint32_t)sw);
-        }
+        const BlobHeader bh = blob_header_uniform(lb[0]);
+        const int k = bh.k, m = bh.m, self = bh.self, kjmax = bh.kjmax;
+        const uint32_t s = (lane < m) ? blob_member(lb, i, lane) : i;
         ZzRec* rs = rec + s;
         double x = 0.0, th = 0.0, t = 0.0, I = 0.0;
         if (lane < m) {
@@ -1023,201 +862,12 @@ __global__ __launch_bounds__(64) void zz_sticky_run_kernel(ZzRunParams P) {
 // memory-level parallelism per wavefront and one instruction stream for 4 events.
 // Requirements: |S[i]| <= 16, max column nnz <= 15, d + 1 <= 64 * 8 * 64; otherwise zz_local_run_kernel is used.
 
-// LDS layout of the speculative kernel: every fixed-size array sits at a compile-time offset (folds into the DS
-// instruction's immediate, no SGPR per array); the three size-dependent arrays come last.
-constexpr uint32_t SP_U = 0;        // [64] f64 draws rng_base + lane
-constexpr uint32_t SP_LU = 512;     // [64] f64 their logs
-constexpr uint32_t SP_SX = 1024;    // [4][16] f64
-constexpr uint32_t SP_STH = 1536;   // [4][16] f64
-constexpr uint32_t SP_PK = 2048;    // [4][64] f64 patched key blocks
-constexpr uint32_t SP_SLT = 4096;   // [4] f64 candidate keys
-constexpr uint32_t SP_SLH = 4128;   // [4] f64 second-best entry of the offering lanes
-constexpr uint32_t SP_LR = 4160;    // [4] f64 true rates
-constexpr uint32_t SP_LBR = 4192;   // [4] f64 bounds
-constexpr uint32_t SP_MR = 4224;    // [4] f64 what each event exposes (validation)
-constexpr uint32_t SP_Z = 4256;     // [64] u32 zone ids
-constexpr uint32_t SP_KR = 4512;    // [4] u32 k per event
-constexpr uint32_t SP_SLB = 4528;   // [4] u32 candidate blocks
-constexpr uint32_t SP_OFR = 4544;   // [8] u32 draw offsets after 0..4 events
-constexpr uint32_t SP_LB = 4576;    // [4][Wpad] u64 blobs, then bk[nblk_pad] f64, bi[nblk_pad] u32
-
-// WIDE (17 <= |S[i]| <= 32: two zone members per lane of a 16-lane row; the second one is always G2-only because |G1| <= 15): the same
-// arrays with 32 slots per group where a slot is a zone member
-// arrays with 32 slots per group where a slot is a zone member.  The patched key blocks take the place of sx / sth once the re-bound has read
-// them (as in the 8-event kernel), so that a chain stays inside 10 KB: 16 chains per CU, all 4096 chains of the ensemble resident at once.
-constexpr uint32_t SPW_SX = 1024;    // [4][32] f64
-constexpr uint32_t SPW_STH = 2048;   // [4][32] f64
-constexpr uint32_t SPW_PK = 1024;    // [4][64] f64 (over sx / sth)
-constexpr uint32_t SPW_SLT = 3072, SPW_SLH = 3104, SPW_LR = 3136, SPW_LBR = 3168, SPW_MR = 3200;
-constexpr uint32_t SPW_Z = 3232;     // [4][32] u32 zone ids
-constexpr uint32_t SPW_KR = 3744, SPW_SLB = 3760, SPW_OFR = 3776;
-constexpr uint32_t SPW_LB = 3808;
-
+// (the LDS layout SP_* / SPW_* and the shared pieces of the scheme: pdmp_spec4_common.hpp)
 size_t zz_spec_lds_bytes(uint32_t nblk_pad, uint32_t blob_w_pad) {
     return (size_t)SP_LB + (size_t)4 * blob_w_pad * 8 + (size_t)nblk_pad * 8 + (size_t)nblk_pad * 4;
 }
 size_t zz_spec_wide_lds_bytes(uint32_t nblk_pad, uint32_t blob_w_pad) {
     return (size_t)SPW_LB + (size_t)4 * blob_w_pad * 8 + (size_t)nblk_pad * 8 + (size_t)nblk_pad * 4;
-}
-
-
-// ---- pieces shared by the two speculative kernels (always inlined: same code as written in place) ----
-
-// Select up to E candidate events: lane l owns the level-1 entries l, l+64, ...; it offers its best entry and remembers its
-// second best.  A lane offers only ONE entry per iteration, so the candidates are the E smallest entries only if no lane holds
-// two of them -- the lane's second best therefore enters the validation bound of every later event, which keeps the commit rule
-// exact.  Winners publish (key, second best, block) straight into the LDS slots.  Returns the number selected.
-// FULLQ: the first level has exactly 4 * 64 entries (the launcher's promise for the 128 x 128 lattice): no bounds predicate, and
-// (best, second best, argmin) of the lane's four entries come out of a 5-comparator network instead of a compare-select chain.
-template <int NE, int E, bool FULLQ = false>
-__device__ __forceinline__ int spec_select(const double* bk, uint32_t nblk, int lane, bool stop_before, double T, double* SLT,
-                                           double* SLH, uint32_t* SLB, bool& first_inf) {
-    double best = PDMP_INF, second = PDMP_INF;
-    uint32_t bestb = 0;
-    if constexpr (FULLQ && NE == 4) {
-        const double k0 = bk[lane], k1 = bk[lane + 64], k2 = bk[lane + 128], k3 = bk[lane + 192];
-        const double m01 = min_f64(k0, k1), x01 = max_f64(k0, k1), m23 = min_f64(k2, k3), x23 = max_f64(k2, k3);
-        best = min_f64(m01, m23);
-        second = min_f64(max_f64(m01, m23), min_f64(x01, x23));
-        bestb = (uint32_t)lane + ((k0 == best) ? 0u : (k1 == best) ? 64u : (k2 == best) ? 128u : 192u);  // lowest block on ties
-    } else {
-#pragma unroll
-        for (int q = 0; q < NE; ++q) {
-            const uint32_t b = (uint32_t)lane + 64u * q;
-            const double v = (b < nblk) ? bk[b] : PDMP_INF;
-            const bool lt = v < best;
-            second = min_f64(second, lt ? best : v);
-            bestb = lt ? b : bestb;
-            best = lt ? v : best;
-        }
-    }
-    int Esel = 0;
-    first_inf = false;
-#pragma unroll
-    for (int r = 0; r < E; ++r) {
-        if (Esel == r) {
-            const double tpr = wave_min_f64(best);
-            if (!(tpr < PDMP_INF)) {
-                if (r == 0) first_inf = true;
-            } else if (!(stop_before && !(tpr < T))) {
-                const uint64_t ball = __ballot(best == tpr);
-                const int wl = __ffsll((unsigned long long)ball) - 1;
-                if (lane == wl) {
-                    SLT[r] = best;
-                    SLH[r] = second;
-                    SLB[r] = bestb;
-                    best = PDMP_INF;
-                }
-                Esel = r + 1;
-            }
-        }
-    }
-    return Esel;
-}
-
-// Zone conflicts with earlier groups (exact: compare member ids through LDS): does this lane's member id occur in the zone of
-// a group q < g?  A cheap necessary condition runs first -- the id must lie inside the [min, max] id span of an earlier group's
-// zone (two u32 row reductions, six scalar reads) -- and only if some lane of the wave passes it (about one iteration in three
-// on the 128 x 128 lattice) are the 48 id comparisons made.
-template <int E>
-__device__ __forceinline__ bool spec_zone_conflict(const uint32_t* Z, uint32_t s, int g, bool member) {
-    uint32_t lo = member ? s : 0xffffffffu, hi = member ? s : 0u;
-    {
-        uint32_t o;
-        o = dpp_u32<0xB1>(lo);   lo = (o < lo) ? o : lo;
-        o = dpp_u32<0x4E>(lo);   lo = (o < lo) ? o : lo;
-        o = dpp_u32<0x141>(lo);  lo = (o < lo) ? o : lo;
-        o = dpp_u32<0x140>(lo);  lo = (o < lo) ? o : lo;
-        o = dpp_u32<0xB1>(hi);   hi = (o > hi) ? o : hi;
-        o = dpp_u32<0x4E>(hi);   hi = (o > hi) ? o : hi;
-        o = dpp_u32<0x141>(hi);  hi = (o > hi) ? o : hi;
-        o = dpp_u32<0x140>(hi);  hi = (o > hi) ? o : hi;
-    }
-    bool maybe = false;
-#pragma unroll
-    for (int q = 0; q < E - 1; ++q) {
-        const uint32_t lq = readlane_u32(lo, 16 * q), hq = readlane_u32(hi, 16 * q);
-        maybe = maybe || ((q < g) && s >= lq && s <= hq);
-    }
-    maybe = maybe && member;
-    if (__ballot(maybe) == 0) return false;
-    const uint2* Z2 = reinterpret_cast<const uint2*>(Z);
-    bool myconf = false;
-#pragma unroll
-    for (int q = 0; q < E - 1; ++q) {
-        bool hit = false;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const uint2 zz = Z2[q * 8 + j];
-            hit = hit || (zz.x == s) || (zz.y == s);
-        }
-        myconf = myconf || (hit && (q < g));
-    }
-    return myconf && member;
-}
-
-// WIDE: two ids per lane (s, s2), 32 per group: Z[q][32]
-template <int E>
-__device__ __forceinline__ bool spec_zone_conflict_wide(const uint32_t* Z, uint32_t s, uint32_t s2, int g, bool member, bool member2) {
-    uint32_t lo = member ? s : 0xffffffffu, hi = member ? s : 0u;
-    lo = (member2 && s2 < lo) ? s2 : lo;
-    hi = (member2 && s2 > hi) ? s2 : hi;
-    {
-        uint32_t o;
-        o = dpp_u32<0xB1>(lo);   lo = (o < lo) ? o : lo;
-        o = dpp_u32<0x4E>(lo);   lo = (o < lo) ? o : lo;
-        o = dpp_u32<0x141>(lo);  lo = (o < lo) ? o : lo;
-        o = dpp_u32<0x140>(lo);  lo = (o < lo) ? o : lo;
-        o = dpp_u32<0xB1>(hi);   hi = (o > hi) ? o : hi;
-        o = dpp_u32<0x4E>(hi);   hi = (o > hi) ? o : hi;
-        o = dpp_u32<0x141>(hi);  hi = (o > hi) ? o : hi;
-        o = dpp_u32<0x140>(hi);  hi = (o > hi) ? o : hi;
-    }
-    bool maybe = false;
-#pragma unroll
-    for (int q = 0; q < E - 1; ++q) {
-        const uint32_t lq = readlane_u32(lo, 16 * q), hq = readlane_u32(hi, 16 * q);
-        maybe = maybe || ((q < g) && ((member && s >= lq && s <= hq) || (member2 && s2 >= lq && s2 <= hq)));
-    }
-    if (__ballot(maybe) == 0) return false;
-    const uint4* Z4 = reinterpret_cast<const uint4*>(Z);
-    bool myconf = false;
-#pragma unroll
-    for (int q = 0; q < E - 1; ++q) {
-        bool hit = false;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const uint4 zz = Z4[q * 8 + j];
-            hit = hit || (member && (zz.x == s || zz.y == s || zz.z == s || zz.w == s)) ||
-                  (member2 && (zz.x == s2 || zz.y == s2 || zz.z == s2 || zz.w == s2));
-        }
-        myconf = myconf || (hit && (q < g));
-    }
-    return myconf;
-}
-
-// Minimum of the group's patched copy of the popped key block (4 keys per lane): row minimum, this lane's candidate.
-__device__ __forceinline__ void spec_patched_min(const double* pk, int gl, uint32_t blk, double& rowmin, double& candmin,
-                                                 uint32_t& cand) {
-    const double2* pk2 = reinterpret_cast<const double2*>(pk + gl * 4);
-    const double2 p01 = pk2[0], p23 = pk2[1];
-    double lm = p01.x;
-    uint32_t li = 0;
-    if (p01.y < lm) {
-        lm = p01.y;
-        li = 1;
-    }
-    if (p23.x < lm) {
-        lm = p23.x;
-        li = 2;
-    }
-    if (p23.y < lm) {
-        lm = p23.y;
-        li = 3;
-    }
-    candmin = lm;
-    cand = blk * 64u + (uint32_t)gl * 4u + li;
-    rowmin = row_min_f64(lm);
 }
 
 // PLAIN: the configuration of the north-star workload -- adapt = false, target without a mean shift, G2 fetched on accept --
@@ -1336,9 +986,8 @@ __device__ __forceinline__ void zz_local_spec_body(const ZzRunParams& P_in) {
         PDMP_LDS_ORDER();
         if (P.has_refresh) {
             // ---------------- the refresh clock (key d, src/sfact.jl:78-114) among the candidates: the events before it go through the speculative
-            // iteration as usual; once it is the chain's NEXT event it is processed by itself, the whole wave on one event, exactly as
-            // zz_local_run_kernel does (a refresh moves the neighbourhood of one random coordinate and re-bounds that of another: no zone
-            // test covers it, and at rate λref against thousands of proposals per unit time it need not be fast)
+            // iteration as usual; once it is the chain's NEXT event it is processed by itself, the whole wave on one event.  The event is
+            // zz_refresh_event's (pdmp_zz_refresh.hpp) WRITTEN OUT: a change to one is a change to the other (why: DESIGN.md §4)
             const uint64_t rfb = __ballot(g < Esel && gl == 0 && bi[SLB[g]] == (uint32_t)d);
             if (rfb) {
                 const int rg = (__ffsll((unsigned long long)rfb) - 1) >> 4;
@@ -1985,13 +1634,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     const bool adapt = FULL && P.adapt != 0;
 
     uint32_t status = hdr->c.status;
-    if (status == PDMP_CHAIN_BOUND_VIOLATED || status == PDMP_CHAIN_STALLED) return;
+    if (chain_ended(status)) return;
     const uint64_t seed = hdr->seed;
     const uint64_t nm0 = hdr->c.ndraw_main, ntrace0 = hdr->c.ntrace;
     uint32_t dnm = 0, dnum = 0, dnacc = 0;
     uint32_t vnacc = 0;  // 1 if the launch ends on a bound violation (acc is bumped before the check)
     // the flow's refresh clock (src/sfact.jl:78-114, round 6): its time is a wave-uniform scalar here, not a queue entry (key d lies behind the
-    // first level's 512 blocks); its events are processed by themselves between the speculative iterations, as zz_local_run_kernel does
+    // first level's 512 blocks); its events are processed by themselves between the speculative iterations (zz_refresh_event)
     const bool has_refresh = P.has_refresh != 0;
     double t_ref = has_refresh ? keys[d] : PDMP_INF;
     uint32_t dnref = 0;                 // refresh events of this launch (recorded in the trace like reflections, :143)
@@ -2002,9 +1651,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 
     const double T = P.T;
     const bool stop_before = (P.flags & PDMP_RUN_STOP_BEFORE) != 0;
-    const uint32_t trace_room = (P.trace_cap > 0)
-                                    ? (uint32_t)(((uint64_t)P.trace_cap > ntrace0) ? ((uint64_t)P.trace_cap - ntrace0) : 0)
-                                    : 0xffffffffu;
+    const uint32_t trace_room = launch_trace_room(P.trace_cap, ntrace0);
     const uint32_t common = P.common_tix;
 
     if (lane == 0) SELDT[0] = 1e-3;  // any positive start: the steering rule finds the scale within a few iterations
@@ -2037,120 +1684,22 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         bool first_inf, do_ref;
         s8_select<E, true, false>(bk, TK, TB, PR, SLT, SLB, SELDT, lane, stop_before, T, has_refresh, t_ref, Esel, first_inf, do_ref);
         if (do_ref) {
-            // ---------------- the refresh clock is the chain's next event: src/sfact.jl:78-114, restated with its quirks exactly as
-            // zz_local_run_kernel does (two independent coordinate draws from the global stream -- the neighbourhood that is moved, :80, and the
-            // coordinate that is refreshed, :84 --, G1[i] re-bounded at the coordinates' own, possibly stale, clocks); the whole wave on one event
+            // ---------------- the refresh clock is the chain's next event: src/sfact.jl:78-114 (zz_refresh_event), the whole wave on one event.
+            // Scratch: blob slot 1 (free between iterations) and the sx / sth area as [64]
             const double tp = t_ref;
-            uint64_t* const lb0 = LB + WPAD;  // (blob slot 1: free between iterations)
-            double* const sx0 = reinterpret_cast<double*>(smem + S8_SX);
-            double* const sth0 = reinterpret_cast<double*>(smem + S8_STH);
-            const uint64_t nm = nm0 + (uint64_t)dnm;
             t_last = tp;
-            const uint32_t i1 = pdmp_randint(seed, PDMP_STREAM_GLOBAL, ng, (uint32_t)d);
-            ng += 1;
-            {
-                const uint64_t* bsrc = P.blob + (size_t)P.tix[i1] * WPAD;
-                if (lane < (int)WPAD) lb0[lane] = bsrc[lane];
-                PDMP_LDS_ORDER();
-                const int k1 = (int)uniform_u32((uint32_t)(lb0[0] & 0xff));
-                if (lane < k1) {  // smove_forward!(G, i1, ...), :82
-                    const uint64_t sw = lb0[1 + (lane >> 1)];
-                    const uint32_t s1 = i1 + ((lane & 1) ? (uint32_t)(sw >> 32) : (uint32_t)sw);
-                    ZzRec* r1 = rec + s1;
-                    const double x0 = r1->x, th0 = r1->th, t0 = r1->t, I0 = r1->I;
-                    const double dt = tp - t0;
-                    const double xn = x0 + th0 * dt;
-                    r1->x = xn;
-                    r1->t = tp;
-                    r1->I = I0 + dt * ((x0 + xn) * 0.5);
-                }
-                PDMP_LDS_ORDER();
-            }
-            const uint32_t i2 = pdmp_randint(seed, PDMP_STREAM_GLOBAL, ng, (uint32_t)d);
-            ng += 1;
-            {
-                const uint64_t* bsrc = P.blob + (size_t)P.tix[i2] * WPAD;
-                if (lane < (int)WPAD) lb0[lane] = bsrc[lane];
-            }
-            PDMP_LDS_ORDER();
-            const uint64_t hw = lb0[0];
-            const int k = (int)uniform_u32((uint32_t)(hw & 0xff));
-            const int m = (int)uniform_u32((uint32_t)((hw >> 8) & 0xff));
-            const int self = (int)uniform_u32((uint32_t)((hw >> 16) & 0xff));
-            uint32_t s = i2;
-            if (lane < m) {
-                const uint64_t sw = lb0[1 + (lane >> 1)];
-                s = i2 + ((lane & 1) ? (uint32_t)(sw >> 32) : (uint32_t)sw);
-            }
-            ZzRec* rs = rec + s;
-            double x = 0.0, th = 0.0, t = 0.0, I = 0.0;
-            if (lane < m) {
-                x = rs->x;
-                th = rs->th;
-                t = rs->t;
-                I = rs->I;
-            }
-            if (lane >= k && lane < m) {  // smove_forward!(G2, i, ...), :85
-                const double dt = tp - t;
-                const double xn = x + th * dt;
-                I = I + dt * ((x + xn) * 0.5);
-                x = xn;
-                t = tp;
-            }
-            const double usign = pdmp_u01(seed, PDMP_STREAM_MAIN, nm);  // θ[i] = σ[i]*rand(rng, (-1,1)), :100-101
-            if (lane == self) th = P.tb.sigma[i2] * ((usign < 0.5) ? -1.0 : 1.0);
-            const double newref = tp + (-pdmp_log(pdmp_u01(seed, PDMP_STREAM_GLOBAL, ng))) / P.lambda_ref;  // :108
-            ng += 1;
-            if (lane < m) {
-                sx0[lane] = x;
-                sth0[lane] = th;
-            }
-            PDMP_LDS_ORDER();
-            const uint32_t sub0 = 1 + SW + (uint32_t)lane * R_;
-            double key = PDMP_INF;
-            if (lane < k) {  // :110-114
-                const double gmu = __longlong_as_double((long long)lb0[sub0 + 1]);
-                const double cj = cmut ? cmut[s] : __longlong_as_double((long long)lb0[sub0 + 2]);
-                const int kj = (int)(lb0[sub0 + 3] & 0xff);
-                const uint64_t pw = lb0[sub0 + 4];
-                double gx = 0.0, gt = 0.0;
-#pragma unroll
-                for (int q = 0; q < 5; ++q) {
-                    if (q < kj) {
-                        const double v = __longlong_as_double((long long)lb0[sub0 + 4 + PW + q]);
-                        const int ps = (int)((pw >> (8 * q)) & 0xff);
-                        gx += v * sx0[ps];
-                        gt += v * sth0[ps];
-                    }
-                }
-                const double a = cj + (gx - gmu) * th;
-                const double b = cj / 100 + th * gt;
-                const double L = pdmp_log(pdmp_u01(seed, PDMP_STREAM_MAIN, nm + 1 + (uint64_t)lane));
-                key = t + poisson_time_L(a, b, L);
-                rs->t_old = t;
-                rs->a = a;
-                rs->b = b;
-                keys[s] = key;
-            }
-            dnm += 1u + (uint32_t)k;
-            if (lane < m) {
-                rs->x = x;
-                rs->th = th;
-                rs->t = t;
-                rs->I = I;
-            }
-            t_ref = newref;  // (stored into keys[d] when the launch ends)
-            for (int jj = 0; jj < k; ++jj) {  // first level: blocks of 32 keys
-                s8_level1_update(bk, bi, keys, lane, readlane_u32(s, jj), readlane_f64(key, jj));
-                PDMP_LDS_ORDER();
-            }
-            const double t_i = readlane_f64(t, self), x_i = readlane_f64(x, self), th_i2 = readlane_f64(th, self);
+            const ZzRefreshed rf = zz_refresh_event<false, 5>(P, BlobGeom{WPAD, WPAD, SW, PW, R_}, rec, keys, cmut, d, seed, nm0 + (uint64_t)dnm, ng, tp, lane,
+                                                           LB + WPAD, reinterpret_cast<double*>(smem + S8_SX), reinterpret_cast<double*>(smem + S8_STH),
+                                                           false, S8Level1{bk, bi});
+            dnm += rf.ndraw;
+            ng = rf.ng;
+            t_ref = rf.t_ref;  // (stored into keys[d] when the launch ends)
             if (ev && lane == 0) {  // event(i, t, x, θ, F) = (t[i], i, x[i], θ[i]), :143
                 pdmp_event e;
-                e.t = t_i;
-                e.i = (int64_t)i2;
-                e.x = x_i;
-                e.theta = th_i2;
+                e.t = rf.t;
+                e.i = (int64_t)rf.i2;
+                e.x = rf.x;
+                e.theta = rf.th;
                 ev[ntrace0 + dnacc + dnref] = e;
             }
             dnref += 1;
@@ -2175,7 +1724,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         const uint32_t i = gvalid ? (uint32_t)bi[blk] : 0u;
         const uint32_t tixi = gvalid ? P.tix[i] : common;
 
-        // ---------------- candidate draws (window of 64 draws and their logs in LDS, as in zz_local_spec_kernel)
+        // ---------------- candidate draws (window of 64 draws; their logs in LDS: s8_draw_window)
         const uint32_t rng_off = s8_draw_window(E * (1u + KMAX), dnm, seed, nm0, lane, LU, rng_base, ureg);
         // ---------------- blob slots: 0 for the common template, 1 and 2 for the first two events that need another one
         const uint64_t* lb = LB + s8_blob_slot<WPAD>(P.blob, LB, tixi, common, g, gl, Esel, gvalid) * WPAD;
@@ -2449,7 +1998,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     const bool adapt = FULL && P.adapt != 0;
 
     uint32_t status = hdr->c.status;
-    if (status == PDMP_CHAIN_BOUND_VIOLATED || status == PDMP_CHAIN_STALLED) return;
+    if (chain_ended(status)) return;
     const uint64_t seed = hdr->seed;
     const uint64_t nm0 = hdr->c.ndraw_main, ntrace0 = hdr->c.ntrace;
     uint32_t dnm = 0, dnum = 0, dnacc = 0;
@@ -2460,9 +2009,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 
     const double T = P.T;
     const bool stop_before = (P.flags & PDMP_RUN_STOP_BEFORE) != 0;
-    const uint32_t trace_room = (P.trace_cap > 0)
-                                    ? (uint32_t)(((uint64_t)P.trace_cap > ntrace0) ? ((uint64_t)P.trace_cap - ntrace0) : 0)
-                                    : 0xffffffffu;
+    const uint32_t trace_room = launch_trace_room(P.trace_cap, ntrace0);
     const uint32_t common = P.common_tix;
 
     if (lane == 0) SELDT[0] = 1e-3;  // any positive start: the steering rule finds the scale within a few iterations
@@ -2507,7 +2054,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         const uint32_t i = gvalid ? (uint32_t)bi[blk] : 0u;
         const uint32_t tixi = gvalid ? P.tix[i] : common;
 
-        // ---------------- candidate draws (window of 64 draws and their logs in LDS, as in zz_local_spec_kernel)
+        // ---------------- candidate draws (window of 64 draws; their logs in LDS: s8_draw_window)
         const uint32_t rng_off = s8_draw_window(E * (1u + KMAX), dnm, seed, nm0, lane, LU, rng_base, ureg);
         // ---------------- blob slots: 0 for the common template, 1 and 2 for the first two events that need another one
         const uint64_t* lb = LB + s8_blob_slot<WPAD>(P.blob, LB, tixi, common, g, gl, Esel, gvalid) * WPAD;
@@ -2765,7 +2312,7 @@ __global__ __launch_bounds__(64) void zz_sticky_spec_kernel(ZzRunParams P_in) {
     const int64_t chain = blockIdx.x;
     const int64_t d = P.d;
     const uint32_t nblk = P.nblk;
-    const uint32_t W2 = P.blob_w_pad >> 1, SW = PLAIN ? 7u : P.blob_sw, PW = PLAIN ? 1u : P.blob_pw, KMAX = PLAIN ? 5u : P.blob_kmax;
+    const uint32_t SW = PLAIN ? 7u : P.blob_sw, PW = PLAIN ? 1u : P.blob_pw, KMAX = PLAIN ? 5u : P.blob_kmax;
     const uint32_t R_ = 4 + PW + KMAX;
 
     extern __shared__ __align__(16) unsigned char smem[];
@@ -2797,7 +2344,7 @@ __global__ __launch_bounds__(64) void zz_sticky_spec_kernel(ZzRunParams P_in) {
     double* cmut = P.c_chain ? (P.c_chain + chain * d) : nullptr;
 
     uint32_t status = hdr->c.status;
-    if (status == PDMP_CHAIN_BOUND_VIOLATED || status == PDMP_CHAIN_STALLED) return;
+    if (chain_ended(status)) return;
     const uint64_t seed = hdr->seed;
     const uint64_t nm0 = hdr->c.ndraw_main, ntrace0 = hdr->c.ntrace;
     uint64_t num = hdr->c.num, nacc = hdr->c.nacc;  // scalars with the reset quirk (:134): kept absolute
@@ -2811,25 +2358,9 @@ __global__ __launch_bounds__(64) void zz_sticky_spec_kernel(ZzRunParams P_in) {
     const bool adapt = P.adapt != 0;
     const bool strong = P.strong_upperbounds != 0;
     const bool reversible = P.reversible != 0;
-    const uint32_t trace_room = (P.trace_cap > 0)
-                                    ? (uint32_t)(((uint64_t)P.trace_cap > ntrace0) ? ((uint64_t)P.trace_cap - ntrace0) : 0)
-                                    : 0xffffffffu;
+    const uint32_t trace_room = launch_trace_room(P.trace_cap, ntrace0);
 
-    for (uint32_t b = lane; b < nblk; b += 64) {
-        const double* kp = keys + (size_t)b * 64;
-        double mk = kp[0];
-        uint32_t mi = 0;
-#pragma unroll 8
-        for (int q = 1; q < 64; ++q) {
-            const double v = kp[q];
-            if (v < mk) {
-                mk = v;
-                mi = q;
-            }
-        }
-        bk[b] = mk;
-        bi[b] = b * 64 + mi;
-    }
+    level1_build(bk, bi, keys, nblk, lane);
     PDMP_LDS_ORDER();
 
     uint32_t rng_base = 0xffffffffu;
@@ -2859,34 +2390,15 @@ __global__ __launch_bounds__(64) void zz_sticky_spec_kernel(ZzRunParams P_in) {
         const double hidg = gvalid ? SLH[g] : PDMP_INF;
         const uint32_t i = gvalid ? bi[blk] : 0u;
 
-        {
-            const uint32_t tixi = gvalid ? P.tix[i] : 0u;
-            const ulonglong2* bsrc = reinterpret_cast<const ulonglong2*>(P.blob + (size_t)tixi * P.blob_w_pad);
-            ulonglong2* bdst = reinterpret_cast<ulonglong2*>(lb);
-            if (gvalid) {
-                for (uint32_t w = gl; w < W2; w += 16) bdst[w] = bsrc[w];
-            }
-        }
-        if (dnm < rng_base || dnm + E * (1u + KMAX) > rng_base + 64u) {
-            rng_base = dnm;
-            const double u = pdmp_u01(seed, PDMP_STREAM_MAIN, nm0 + (uint64_t)dnm + (uint64_t)lane);
-            U[lane] = u;
-            LU[lane] = pdmp_log(u);
-        }
-        const uint32_t rng_off = dnm - rng_base;
+        spec_blob_fetch(P.blob, P.tix, P.blob_w_pad, lb, gvalid, i, gl);
+        const uint32_t rng_off = spec_draw_window(E * (1u + KMAX), dnm, seed, nm0, lane, U, LU, rng_base);
         PDMP_LDS_ORDER();
         int k = 0, m = 0, self = 0, kjmax = 0;
         uint32_t s = 0xffffff00u + (uint32_t)lane;
         if (gvalid) {
-            const uint64_t hw = lb[0];
-            k = (int)(hw & 0xff);
-            m = (int)((hw >> 8) & 0xff);
-            self = (int)((hw >> 16) & 0xff);
-            kjmax = (int)((hw >> 24) & 0xff);
-            if (gl < m) {
-                const uint64_t sw = lb[1 + (gl >> 1)];
-                s = i + ((gl & 1) ? (uint32_t)(sw >> 32) : (uint32_t)sw);
-            }
+            const BlobHeader bh = blob_header(lb[0]);
+            k = bh.k, m = bh.m, self = bh.self, kjmax = bh.kjmax;
+            if (gl < m) s = blob_member(lb, i, gl);
         }
         const bool member = gvalid && gl < m;
         ZzRec* rs = rec + (member ? s : i);
@@ -3071,73 +2583,26 @@ __global__ __launch_bounds__(64) void zz_sticky_spec_kernel(ZzRunParams P_in) {
         if (newkey && (s >> 6) == blk) pk[s & 63] = key;
         PDMP_LDS_ORDER();
         // ---------------- patched minimum of the popped block, exposure
-        double rowmin, candmin;
+        double rowmin;
         uint32_t cand;
-        spec_patched_min(pk, gl, blk, rowmin, candmin, cand);
-        const uint64_t winball = __ballot(gvalid && candmin == rowmin);
-        const int wl2 = __ffs((unsigned)((winball >> (16 * g)) & 0xffffu)) - 1;
-        const double keymin = row_min_f64(newkey ? key : PDMP_INF);
-        const double expose = min_f64(min_f64(rowmin, keymin), hidg);
-        if (gl == 0) Mr[g] = expose;
+        int wl2;
+        spec_expose(pk, g, gl, blk, gvalid, newkey ? key : PDMP_INF, hidg, Mr, rowmin, cand, wl2);
         PDMP_LDS_ORDER();
-        // ---------------- validate
+        // ---------------- validate (spec_validate): a violated bound without `adapt` and a freeze off 0 are the reference's error(...), :90,
+        // :133; freeze, thaw and accepted reflection are the trace events
+        bool okg;
         uint32_t Rc;
         uint32_t happb_c;  // bit r: committed event r is a trace event
-        int vsel = -1;       // the event that stops the chain with an error, if it is the chain's next one
-        bool vprop = false;  // ... and it is a proposal that violates its bound (not the x[i] != 0 check of a freeze)
-        {
-            const double m0 = Mr[0], m1 = Mr[1], m2 = Mr[2];
-            const double pref = (g == 0) ? PDMP_INF : (g == 1) ? m0 : (g == 2) ? min_f64(m0, m1) : min_f64(min_f64(m0, m1), m2);
-            const bool confg = ((confball >> (16 * g)) & 0xffffull) != 0;
-            const bool okg = gvalid && ((g == 0) || (!confg && pref > tp));
-            const bool xerrg = ((xerrball >> (16 * g)) & 0xffffull) != 0;
-            const bool vstop = (violated && !adapt) || xerrg;  // reference: error(...), :90, :133
-            const uint64_t okball = __ballot(okg && !vstop && gl == 0);
-            const uint64_t vball = __ballot(okg && vstop && gl == 0);
-            const uint64_t happball = __ballot(happens && gl == 0);
-            auto bits4 = [](uint64_t m_) -> uint32_t {
-                return (uint32_t)((m_ & 1ull) | ((m_ >> 15) & 2ull) | ((m_ >> 30) & 4ull) | ((m_ >> 45) & 8ull));
-            };
-            const uint32_t okb = bits4(okball), vb = bits4(vball), happb = bits4(happball);
-            const uint32_t gap = ~okb & 0xfu;  // the run of committable slots from slot 0 ends at the first zero bit
-            const uint32_t r_ok = gap ? (uint32_t)(__ffs((int)gap) - 1) : (uint32_t)E;
-            Rc = 0;
-            happb_c = 0;
-            uint32_t nev_c = 0;
-            bool stopped = false;
-            // the usual case needs no walk: the slice mode stops on time alone, and the trace has room for every event of the run
-            const uint32_t happ_run = happb & ((1u << r_ok) - 1u);
-            const bool plainrun = stop_before && !(P.trace_cap > 0 && dnev + (uint32_t)__popc(happ_run) >= trace_room);
-            if (plainrun) {
-                Rc = r_ok;
-                happb_c = happ_run;
-            }
-            for (uint32_t r = 0; !plainrun && r < r_ok && !stopped; ++r) {
-                Rc = r + 1;
-                if ((happb >> r) & 1u) {
-                    happb_c |= 1u << r;
-                    nev_c += 1;
-                    if (dnev + nev_c >= trace_room && P.trace_cap > 0) {
-                        status = PDMP_CHAIN_TRACE_FULL;
-                        stopped = true;
-                    }
-                    if (!stop_before && !(uniform_f64(SLT[r]) < T)) {
-                        running = false;
-                        stopped = true;
-                    }
-                }
-            }
-            if (!stopped && r_ok < (uint32_t)E && ((vb >> r_ok) & 1u)) {
-                status = PDMP_CHAIN_BOUND_VIOLATED;
-                vsel = (int)r_ok;
-                vprop = ((bits4(__ballot(okg && violated && !adapt && !xerrg && gl == 0)) >> r_ok) & 1u) != 0;
-            }
-        }
+        int vsel;          // the event that stops the chain with an error, if it is the chain's next one
+        const bool xerrg = ((xerrball >> (16 * g)) & 0xffffull) != 0;
+        spec_validate(Mr, SLT, confball, gvalid, (violated && !adapt) || xerrg, happens, tp, g, gl, stop_before, T, P.trace_cap > 0, dnev, trace_room,
+                      okg, Rc, happb_c, vsel, status, running);
+        // ... and it is a proposal that violates its bound (not the x[i] != 0 check of a freeze)
+        const bool vprop = vsel >= 0 && ((spec_bits4(__ballot(okg && violated && !adapt && !xerrg && gl == 0)) >> vsel) & 1u) != 0;
 
         // ---------------- commit the valid prefix
         const bool commit = gvalid && (uint32_t)g < Rc;
         const uint64_t happball2 = __ballot(commit && happens && gl == 0);
-        const uint64_t nkball = __ballot(commit && newkey);
         if (commit) {
             if (member && (happens || gl < k)) {  // what was (possibly) moved; frozen members write back their own values
                 rs->x = x;
@@ -3179,40 +2644,8 @@ __global__ __launch_bounds__(64) void zz_sticky_spec_kernel(ZzRunParams P_in) {
             }
         }
         PDMP_LDS_ORDER();
-        // ---------------- level-1 updates for new keys living in other blocks.  A block's final entry is the smallest
-        // (key, coordinate) among its old entry and the new keys, whatever the order: when no two of these lanes aim at one block
-        // (claims through the now idle zone-id array) and none has to rescan, every lane updates its block by itself in one LDS
-        // round trip; otherwise one by one in event order.
-        const bool upd = commit && newkey && (s >> 6) != blk;
-        if (__ballot(upd) != 0) {
-            PDMP_LDS_ORDER();
-            const uint32_t bjv = upd ? (s >> 6) : 0u;
-            const double curv = bk[bjv];
-            const uint32_t civ = bi[bjv];
-            const bool lower = upd && (key < curv || (key == curv && s < civ));
-            const bool resc = upd && !lower && civ == s;
-            if (lower) Z[bjv & 63u] = (uint32_t)lane;
-            PDMP_LDS_ORDER();
-            const bool lost = lower && Z[bjv & 63u] != (uint32_t)lane;
-            if (__ballot(lost || resc) == 0) {
-                if (lower) {
-                    bk[bjv] = key;
-                    bi[bjv] = s;
-                }
-            } else {
-            for (uint32_t r = 0; r < Rc; ++r) {
-                uint32_t lanes = (uint32_t)((nkball >> (16 * r)) & 0xffffull);
-                const uint32_t own = uniform_u32(SLB[r]);
-                while (lanes) {
-                    const int jj = __ffs((int)lanes) - 1;
-                    lanes &= lanes - 1u;
-                    const uint32_t j = readlane_u32(s, 16 * (int)r + jj);
-                    if ((j >> 6) == own) continue;
-                    level1_update(bk, bi, keys, lane, j, readlane_f64(key, 16 * (int)r + jj));
-                }
-            }
-            }
-        }
+        // ---------------- level-1 updates for new keys living in other blocks
+        spec_level1_commit(bk, bi, Z, keys, commit && newkey && (s >> 6) != blk, s, key, lane);
         // ---------------- counters (scalar acc, num with the reset of an adapted violation, :131-136)
         if (Rc > 0) {
             const uint64_t violball = __ballot(commit && violated && gl == 0);

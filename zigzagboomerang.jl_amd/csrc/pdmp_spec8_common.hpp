@@ -205,6 +205,17 @@ __device__ __forceinline__ void s8_level1_update(double* bk, uint16_t* bi, const
         }
     }
 }
+// ... as the level-1 form zz_refresh_event (pdmp_zz_refresh.hpp) takes its new keys through: the clock is no key here, its time is the
+// kernel's t_ref
+struct S8Level1 {
+    static constexpr bool clock_is_key = false;
+    double* bk;
+    uint16_t* bi;
+    __device__ __forceinline__ void operator()(const double* keys, int lane, uint32_t j, double kj) const {
+        s8_level1_update(bk, bi, keys, lane, j, kj);
+        PDMP_LDS_ORDER();
+    }
+};
 
 // ---------------- candidate draws: a window of 64 draws (one per lane, in ureg) and their logs (LU), refilled when an iteration's `need`
 // draws could leave it.  Returns the offset of draw dnm inside the window.

@@ -82,7 +82,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
     const double2* const member2 = reinterpret_cast<const double2*>(P.g8_member);     // [d][8] double2
 
     uint32_t status = hdr->c.status;
-    if (status == PDMP_CHAIN_BOUND_VIOLATED || status == PDMP_CHAIN_STALLED) return;
+    if (chain_ended(status)) return;
     const uint64_t seed = hdr->seed;
     const uint64_t nm0 = hdr->c.ndraw_main, ntrace0 = hdr->c.ntrace;
     uint32_t dnm = 0, dnum = 0, dnacc = 0;
@@ -99,9 +99,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
 
     const double T = P.T;
     const bool stop_before = (P.flags & PDMP_RUN_STOP_BEFORE) != 0;
-    const uint32_t trace_room = (P.trace_cap > 0)
-                                    ? (uint32_t)(((uint64_t)P.trace_cap > ntrace0) ? ((uint64_t)P.trace_cap - ntrace0) : 0)
-                                    : 0xffffffffu;
+    const uint32_t trace_room = launch_trace_room(P.trace_cap, ntrace0);
 
     if (lane0 == 0) SELDT[0] = 1e-3;
     s8_build_level1<true>(keys, bk, bi, nblk, d, has_refresh, lane0);
@@ -139,126 +137,27 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
         bool first_inf, do_ref;
         s8_select<E, true, true>(bk, TK, TB, PR, SLT, SLB, SELDT, lane, stop_before, T, has_refresh, t_ref, Esel, first_inf, do_ref);
         if (do_ref) {
-            // ---------------- the refresh clock is the chain's next event (src/sfact.jl:78-114, with its quirks: zz_local_run_kernel's restatement)
+            // ---------------- the refresh clock is the chain's next event: src/sfact.jl:78-114 (zz_refresh_event), from the neighbourhood blobs
+            // zz_local_run_kernel uses (the host builds them for every graph).  Scratch inside the shared area: the blob (<= 137 words: |S| <= 64,
+            // |G1| <= 8), then sx and sth as [64]
             const double tp = t_ref;
 #ifdef PDMP_G8_DEBUG
             if (chain == 0 && lane == 0) printf("g8 refresh: it %u tp %.17g dnum %u dnref %u blob_w %u sw %u pw %u kmax %u\n", (unsigned)prio.it, tp, dnum, dnref, P.blob_w, P.blob_sw, P.blob_pw, P.blob_kmax);
 #endif
-            const uint32_t W = P.blob_w, SW = P.blob_sw, PW = P.blob_pw, R_ = 4 + PW + P.blob_kmax;
-            uint64_t* const lb0 = reinterpret_cast<uint64_t*>(smem + G8_R);            // <= 137 words (|S| <= 64, |G1| <= 8)
-            double* const sx0 = reinterpret_cast<double*>(smem + G8_R + 1152);         // [64]
-            double* const sth0 = reinterpret_cast<double*>(smem + G8_R + 1152 + 512);  // [64]
-            const uint64_t nm = nm0 + (uint64_t)dnm;
             t_last = tp;
-            const uint32_t i1 = pdmp_randint(seed, PDMP_STREAM_GLOBAL, ng, (uint32_t)d);
-            ng += 1;
-            {
-                const uint64_t* bsrc = P.blob + (size_t)P.tix[i1] * P.blob_w_pad;
-                for (uint32_t w = lane; w < W; w += 64) lb0[w] = bsrc[w];
-                PDMP_LDS_ORDER();
-                const int k1 = (int)uniform_u32((uint32_t)(lb0[0] & 0xff));
-                if (lane < k1) {  // smove_forward!(G, i1, ...), :82
-                    const uint64_t sw = lb0[1 + (lane >> 1)];
-                    const uint32_t s1 = i1 + ((lane & 1) ? (uint32_t)(sw >> 32) : (uint32_t)sw);
-                    ZzRec* r1 = rec + s1;
-                    const double x0 = r1->x, th0 = r1->th, t0 = r1->t, I0 = r1->I;
-                    const double dt = tp - t0;
-                    const double xn = x0 + th0 * dt;
-                    r1->x = xn;
-                    r1->t = tp;
-                    r1->I = I0 + dt * ((x0 + xn) * 0.5);
-                }
-                PDMP_LDS_ORDER();
-            }
-            const uint32_t i2 = pdmp_randint(seed, PDMP_STREAM_GLOBAL, ng, (uint32_t)d);
-            ng += 1;
-            {
-                const uint64_t* bsrc = P.blob + (size_t)P.tix[i2] * P.blob_w_pad;
-                for (uint32_t w = lane; w < W; w += 64) lb0[w] = bsrc[w];
-            }
-            PDMP_LDS_ORDER();
-            const uint64_t hw = lb0[0];
-            const int k = (int)uniform_u32((uint32_t)(hw & 0xff));
-            const int m = (int)uniform_u32((uint32_t)((hw >> 8) & 0xff));
-            const int self = (int)uniform_u32((uint32_t)((hw >> 16) & 0xff));
-            const int kjmax = (int)uniform_u32((uint32_t)((hw >> 24) & 0xff));
-            uint32_t s = i2;
-            if (lane < m) {
-                const uint64_t sw = lb0[1 + (lane >> 1)];
-                s = i2 + ((lane & 1) ? (uint32_t)(sw >> 32) : (uint32_t)sw);
-            }
-            ZzRec* rs = rec + s;
-            double x = 0.0, th = 0.0, t = 0.0, I = 0.0;
-            if (lane < m) {
-                x = rs->x;
-                th = rs->th;
-                t = rs->t;
-                I = rs->I;
-            }
-            if (lane >= k && lane < m) {  // smove_forward!(G2, i, ...), :85
-                const double dt = tp - t;
-                const double xn = x + th * dt;
-                I = I + dt * ((x + xn) * 0.5);
-                x = xn;
-                t = tp;
-            }
-            const double usign = pdmp_u01(seed, PDMP_STREAM_MAIN, nm);  // θ[i] = σ[i]*rand(rng, (-1,1)), :100-101
-            if (lane == self) th = P.tb.sigma[i2] * ((usign < 0.5) ? -1.0 : 1.0);
-            const double newref = tp + (-pdmp_log(pdmp_u01(seed, PDMP_STREAM_GLOBAL, ng))) / P.lambda_ref;  // :108
-            ng += 1;
-            if (lane < m) {
-                sx0[lane] = x;
-                sth0[lane] = th;
-            }
-            PDMP_LDS_ORDER();
-            const uint32_t sub0 = 1 + SW + (uint32_t)lane * R_;
-            double key = PDMP_INF;
-            if (lane < k) {  // :110-114
-                const double gmu = __longlong_as_double((long long)lb0[sub0 + 1]);
-                const double cj = cmut ? cmut[s] : __longlong_as_double((long long)lb0[sub0 + 2]);
-                const int kj = (int)(lb0[sub0 + 3] & 0xff);
-                double gx = 0.0, gt = 0.0;
-                for (int base = 0; base < kjmax; base += 8) {
-                    const uint64_t pw = lb0[sub0 + 4 + (base >> 3)];
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) {
-                        const int pp = base + q;
-                        if (pp < kj) {
-                            const double v = __longlong_as_double((long long)lb0[sub0 + 4 + PW + pp]);
-                            const int ps = (int)((pw >> (8 * q)) & 0xff);
-                            gx += v * sx0[ps];
-                            gt += v * sth0[ps];
-                        }
-                    }
-                }
-                const double a = cj + (gx - gmu) * th;
-                const double b = cj / 100 + th * gt;
-                const double L = pdmp_log(pdmp_u01(seed, PDMP_STREAM_MAIN, nm + 1 + (uint64_t)lane));
-                key = t + poisson_time_L(a, b, L);
-                rs->t_old = t;
-                rs->a = a;
-                rs->b = b;
-                keys[s] = key;
-            }
-            dnm += 1u + (uint32_t)k;
-            if (lane < m) {
-                rs->x = x;
-                rs->th = th;
-                rs->t = t;
-                rs->I = I;
-            }
-            t_ref = newref;  // (stored into keys[d] when the launch ends)
-            for (int jj = 0; jj < k; ++jj) {  // first level: blocks of 32 keys
-                s8_level1_update(bk, bi, keys, lane, readlane_u32(s, jj), readlane_f64(key, jj));
-                PDMP_LDS_ORDER();
-            }
-            const double t_i = readlane_f64(t, self), x_i = readlane_f64(x, self), th_i2 = readlane_f64(th, self);
+            const ZzRefreshed rf = zz_refresh_event<false, 0>(P, BlobGeom{P.blob_w, P.blob_w_pad, P.blob_sw, P.blob_pw, 4 + P.blob_pw + P.blob_kmax}, rec, keys,
+                                                           cmut, d, seed, nm0 + (uint64_t)dnm, ng, tp, lane, reinterpret_cast<uint64_t*>(smem + G8_R),
+                                                           reinterpret_cast<double*>(smem + G8_R + 1152),
+                                                           reinterpret_cast<double*>(smem + G8_R + 1152 + 512), false, S8Level1{bk, bi});
+            dnm += rf.ndraw;
+            ng = rf.ng;
+            t_ref = rf.t_ref;  // (stored into keys[d] when the launch ends)
             if (ev && lane == 0) {  // event(i, t, x, θ, F) = (t[i], i, x[i], θ[i]), :143
                 pdmp_event e;
-                e.t = t_i;
-                e.i = (int64_t)i2;
-                e.x = x_i;
-                e.theta = th_i2;
+                e.t = rf.t;
+                e.i = (int64_t)rf.i2;
+                e.x = rf.x;
+                e.theta = rf.th;
                 ev[ntrace0 + dnacc + dnref] = e;
             }
             dnref += 1;
