@@ -691,6 +691,45 @@ pdmp_status pdmp_ensemble_bps_consume_pairs(pdmp_ensemble* ens, int64_t npairs, 
 pdmp_status pdmp_ensemble_bps_consume_pair_integrals(pdmp_ensemble* ens, int64_t chain_first, int64_t n, double* S, double* J, double* T_last,
                                                      void** S_dev);
 
+/* ------------------------------------------------------------------ marginal histograms on the device: occupation times of a sampled path
+ *
+ * The time each of m listed coordinates spends in each of `bins` bins of its own range [lo_s, hi_s), below the range and at or above it: the
+ * exact histogram of the path (between two events a coordinate is a line, so the time in a bin is a closed form; no grid, no discretisation
+ * error).  Medians, credible intervals and densities of a marginal follow on the host; the raw times pool exactly over chains and ranks.  Kept
+ * by the synchronous consumers above, slice by slice.  Plain double arithmetic, no fused multiply-add; tests/ref/hist_ref.c states the contract
+ * sequentially and the device agrees with it bit for bit (DESIGN.md "Marginal histograms").
+ *   Bins: w = (hi − lo) / bins, edges e_0 = lo, e_k = lo + w·k, e_bins = hi.  A row has bins + 2 numbers: slot 0 the time below lo, slots 1..bins
+ *     the bins [e_k, e_k+1), slot bins + 1 the time at or above hi.
+ *   A piece (a, v, τ) -- position at its start, velocity, duration; τ <= 0 adds nothing.  With b = a + v·τ: at rest (v == 0 or b == a) it adds τ
+ *     to the slot of a (and, if v == 0, to the coordinate's rest time Z); otherwise with xl = min(a, b), xh = max(a, b), r = τ / (xh − xl) every
+ *     bin between those of xl and xh gets (min(xh, e_k+1) − max(xl, e_k))·r where that is positive.
+ *   FactTrace (whatever consume_begin or barrier_consume_begin accepts).  Cursors of its own (t, x, θ per chain and listed coordinate, from
+ *     (t0, x0, θ0); θ = 0 where a barrier ensemble starts frozen).  An event (t, i, x, θ) of a listed coordinate adds the piece (x_c, θ_c, t − t_c),
+ *     then the cursor becomes the event.  A read closes every open piece at the chain's last consumed event time T_last, without touching the
+ *     rows: a run can be read midway, and reading twice returns the same bytes.
+ *   PDMPTrace (event-recorded BouncyParticle and its sticky form).  Per event (t_k, ...) with the cursor (t_c, x_c, θ_c, f_c) before it every
+ *     listed coordinate adds (x_c,i, f_c,i ? θ_c,i : 0, t_k − t_c).  Nothing is added behind the last event.
+ *   Σ_k H[k] = T_last − t0 to rounding for every listed coordinate; Z <= Σ_k H[k].
+ *   [bps_]consume_hist(m, coords, lo, hi, bins)   after [bps_]consume_begin (or barrier_consume_begin) and before the first [bps_]consume: m
+ *     distinct coordinates, 0-based, stored in the given order; lo, hi [m]; 1 <= bins <= 4096.  Reserves [nchains x m x (bins + 2)] doubles (the
+ *     factorised family also 32 bytes of cursor per chain and listed coordinate).  Without this call nothing changes: no allocation, no kernel.
+ *     Coexists with consume_condition, consume_pairs and consume_cummean.  pdmp_ensemble_consume_async on such an ensemble: PDMP_ERR_UNSUPPORTED.
+ *   [bps_]consume_histogram(chain_first, n, pooled, H, Z, T_last, H_dev)   of chains [chain_first, chain_first + n): pooled == 0: H [n x m x
+ *     (bins + 2)], Z [n x m]; pooled != 0: H [m x (bins + 2)], Z [m], the chains added in chain order, sequentially per entry.  T_last [n] is
+ *     always per chain.  *H_dev = the device array the H just read lie in; any output may be NULL.
+ * PDMP_ERR_INVALID: m < 1, a NULL list, an index outside [0, d), a coordinate listed twice, lo >= hi or a non-finite bound, bins outside
+ * 1..4096, rows beyond 256 GiB (refused before the lists are read), before begin, after the first consume, the other family's ensemble, a chain
+ * range outside the ensemble.
+ * PDMP_ERR_UNSUPPORTED: the Bouncy Particle family on a Boomerang flow (an arc is not a line), on the speed-recorded flow or with subsample
+ * (their records are not the corners of the path).
+ */
+pdmp_status pdmp_ensemble_consume_hist(pdmp_ensemble* ens, int64_t m, const int64_t* coords, const double* lo, const double* hi, int64_t bins);
+pdmp_status pdmp_ensemble_consume_histogram(pdmp_ensemble* ens, int64_t chain_first, int64_t n, int pooled, double* H, double* Z, double* T_last,
+                                            void** H_dev);
+pdmp_status pdmp_ensemble_bps_consume_hist(pdmp_ensemble* ens, int64_t m, const int64_t* coords, const double* lo, const double* hi, int64_t bins);
+pdmp_status pdmp_ensemble_bps_consume_histogram(pdmp_ensemble* ens, int64_t chain_first, int64_t n, int pooled, double* H, double* Z,
+                                                double* T_last, void** H_dev);
+
 /* what the ensemble was created with (any pointer may be NULL) */
 pdmp_status pdmp_ensemble_info(pdmp_ensemble* ens, int64_t* nchains, int64_t* d, int64_t* trace_capacity, int* device);
 

@@ -34,6 +34,63 @@ __device__ __forceinline__ double pair_piece(double a, double b, double vi, doub
 }
 __device__ __forceinline__ double line_piece(double a, double vi, double tau) { return tau * (a + 0.5 * (vi * tau)); }
 
+// the histogram consumers' bins and piece (pdmp_consume.hip, pdmp_consume_bps.hip; tests/ref/hist_ref.c states them): B bins on [lo, hi) of width
+// w = (hi − lo) / B, the edges e_−1 = −∞, e_0 = lo, e_k = lo + w·k, e_B = hi, e_B+1 = +∞; slot k + 1 of a row holds the time in [e_k, e_k+1)
+struct HistBins {
+    double lo, hi, w;
+    int B;
+};
+__device__ __forceinline__ double hist_edge(const HistBins& b, int k) {
+    if (k <= 0) return k < 0 ? -__builtin_inf() : b.lo;
+    if (k >= b.B) return k > b.B ? __builtin_inf() : b.hi;
+    return b.lo + b.w * (double)k;
+}
+// the k in {−1, ..., B} with e_k <= x < e_k+1 against the computed edges: a floor, then one step where rounding put it on the wrong side
+// (always inside [−1, B], whatever x is: the row has B + 2 slots)
+__device__ __forceinline__ int hist_bin_of(const HistBins& b, double x) {
+    if (!(x >= b.lo)) return -1;
+    if (x >= b.hi) return b.B;
+    const double q = floor((x - b.lo) / b.w);
+    int k = q < (double)(b.B - 1) ? (int)q : b.B - 1;
+    if (x < hist_edge(b, k)) k -= 1;
+    else if (x >= hist_edge(b, k + 1)) k += 1;
+    return k;
+}
+// a piece (a, v, τ) made ready: the ends of the interval it sweeps, the time per unit length r, the bins k0 .. k1 it touches.  At rest
+// (v == 0, or a + v·τ == a): xl == xh, r = τ, one bin.  τ <= 0 adds nothing: k0 > k1.
+struct HistPiece {
+    double xl, xh, r;
+    int k0, k1;
+};
+__device__ __forceinline__ HistPiece hist_piece_of(const HistBins& bn, double a, double v, double tau) {
+    HistPiece p;
+    p.xl = p.xh = a;
+    p.r = tau;
+    p.k0 = 0;
+    p.k1 = -1;
+    if (!(tau > 0.0)) return p;
+    const double b = a + v * tau;
+    if (v == 0.0 || b == a) {
+        p.k0 = p.k1 = hist_bin_of(bn, a);
+        return p;
+    }
+    p.xl = a < b ? a : b;
+    p.xh = a < b ? b : a;
+    p.r = tau / (p.xh - p.xl);
+    p.k0 = hist_bin_of(bn, p.xl);
+    p.k1 = hist_bin_of(bn, p.xh);
+    return p;
+}
+// THE function of (piece, k): the time the piece spends in [e_k, e_k+1), k in −1 .. B; the accumulation and the reads both call it
+__device__ __forceinline__ double hist_piece_at(const HistBins& bn, const HistPiece& p, int k) {
+    if (k < p.k0 || k > p.k1) return 0.0;
+    if (p.xl == p.xh) return p.r;
+    const double e0 = hist_edge(bn, k), e1 = hist_edge(bn, k + 1);
+    const double o = (p.xh < e1 ? p.xh : e1) - (p.xl > e0 ? p.xl : e0);
+    return o > 0.0 ? o * p.r : 0.0;
+}
+__device__ __forceinline__ double hist_piece_rest(double v, double tau) { return (tau > 0.0 && v == 0.0) ? tau : 0.0; }
+
 // draw indices a randn(rng, d) takes (BpsWave::normals): one Box-Muller block per two elements, whole 64-lane rows of blocks
 __device__ __forceinline__ uint64_t normal_draws(int64_t d) { return (uint64_t)(((d + 127) >> 7) << 6); }
 

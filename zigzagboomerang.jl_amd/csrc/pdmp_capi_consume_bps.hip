@@ -69,6 +69,19 @@ static pdmp::BpsPairArgs pair_args(const pdmp_ensemble* e) {
     return q;
 }
 
+static pdmp::BpsHistArgs hist_args(const pdmp_ensemble* e) {
+    pdmp::BpsHistArgs q{};
+    q.coords = e->bhs_coords.p;
+    q.lo = e->bhs_lo.p;
+    q.hi = e->bhs_hi.p;
+    q.w = e->bhs_w.p;
+    q.H = e->bhs_H.p;
+    q.Z = e->bhs_Z.p;
+    q.m = e->bhs_m;
+    q.B = e->bhs_B;
+    return q;
+}
+
 // bps_consume_mean / _inclusion: one [n x d] read of the cursors of chains [chain_first, chain_first + n) and the chains' last event times
 static pdmp_status consume_read(pdmp_ensemble* e, int inclusion, int64_t chain_first, int64_t n, double* out, double* T_last, const char* who) {
     PDMP_TRY(need_begun(e, who));
@@ -112,6 +125,8 @@ pdmp_status pdmp_ensemble_bps_consume_begin(pdmp_ensemble* e, double grid_dt, in
     e->bcn_tau.release(), e->bcn_t.release(), e->bcn_x.release(), e->bcn_pn.release(), e->bcn_nh.release();
     e->bpr_on = false;
     e->bpr_pi.release(), e->bpr_pj.release(), e->bpr_c.release(), e->bpr_S.release(), e->bpr_J.release(), e->bpr_T.release();
+    e->bhs_on = false;
+    e->bhs_coords.release(), e->bhs_lo.release(), e->bhs_hi.release(), e->bhs_w.release(), e->bhs_H.release(), e->bhs_Z.release(), e->bhs_out.release();
     e->bc_dt = grid_dt;
     e->bc_K = grid_points;
     LAUNCH_TRY("bps_consume_init", pdmp::launch_bps_consume_init(consume_args(e), e->stream));
@@ -133,6 +148,8 @@ pdmp_status pdmp_ensemble_bps_consume(pdmp_ensemble* e) {
         LAUNCH_TRY("bps_consume_condition", pdmp::launch_bps_cond(consume_args(e), cond_args(e), e->stream));
     if (e->bpr_on)  // (before the consumer, like the condition: it reads the cursors and the progress the consumer is about to advance)
         LAUNCH_TRY("bps_consume_pairs", pdmp::launch_bps_pairs(consume_args(e), pair_args(e), e->stream));
+    if (e->bhs_on)  // (before the consumer too, for the same reason)
+        LAUNCH_TRY("bps_consume_hist", pdmp::launch_bps_hist(consume_args(e), hist_args(e), e->stream));
     LAUNCH_TRY("bps_consume", pdmp::launch_bps_consume_events(consume_args(e), e->stream));
     HIP_TRY(hipEventRecord(e->ev_c1, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
@@ -309,6 +326,68 @@ pdmp_status pdmp_ensemble_bps_consume_pair_integrals(pdmp_ensemble* e, int64_t c
         HIP_TRY(hipStreamSynchronize(e->stream));
         HIP_TRY(hipMemcpy(T_last, e->bpr_T.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
     }
+    return PDMP_OK;
+}
+
+// marginal histograms of a PDMPTrace on the device (DESIGN.md "Marginal histograms"): after bps_consume_begin and before the first bps_consume; from
+// then on bps_consume also adds every slice's pieces
+pdmp_status pdmp_ensemble_bps_consume_hist(pdmp_ensemble* e, int64_t m, const int64_t* coords, const double* lo, const double* hi, int64_t bins) {
+    PDMP_TRY(need_bps(e, __func__));
+    if (e->bps.flow_kind == 1)
+        return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_hist: on a Boomerang flow a coordinate moves on an arc between two events, not on a line");
+    if (e->bps.modern)
+        return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_hist: the records of the speed-recorded flow are not the corners of the path (a straight line "
+                                          "between two of them is not the path)");
+    if (e->bps.subsample)
+        return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_hist: with subsample the records are not the corners of the path (a straight line between two of "
+                                          "them is not the path)");
+    PDMP_TRY(need_begun(e, __func__));
+    if (e->bc_started) return fail(PDMP_ERR_INVALID, "bps_consume_hist precedes the first bps_consume (its first piece starts from t0, x0, θ0)");
+    const int64_t d = e->cfg.d, nch = e->cfg.nchains;
+    std::vector<int32_t> vc;
+    std::vector<double> vlo, vhi, vw;
+    PDMP_TRY(hist_list("bps_consume_hist", nch, d, m, coords, lo, hi, bins, &vc, &vlo, &vhi, &vw));
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(device_sync(e));
+    e->bhs_on = false;
+    PDMP_TRY(e->bhs_coords.upload(vc));
+    PDMP_TRY(e->bhs_lo.upload(vlo));
+    PDMP_TRY(e->bhs_hi.upload(vhi));
+    PDMP_TRY(e->bhs_w.upload(vw));
+    PDMP_TRY(e->bhs_H.alloc((size_t)(nch * m * (bins + 2))));
+    PDMP_TRY(e->bhs_Z.alloc((size_t)(nch * m)));
+    e->bhs_out.release();
+    HIP_TRY(hipMemsetAsync(e->bhs_H.p, 0, (size_t)(nch * m * (bins + 2)) * sizeof(double), e->stream));
+    HIP_TRY(hipMemsetAsync(e->bhs_Z.p, 0, (size_t)(nch * m) * sizeof(double), e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->bhs_m = m;
+    e->bhs_B = (int32_t)bins;
+    e->bhs_on = true;
+    return PDMP_OK;
+}
+
+pdmp_status pdmp_ensemble_bps_consume_histogram(pdmp_ensemble* e, int64_t chain_first, int64_t n, int pooled, double* H, double* Z, double* T_last,
+                                                void** H_dev) {
+    PDMP_TRY(need_bps(e, __func__));
+    if (!e->bc_on || !e->bhs_on) return fail(PDMP_ERR_INVALID, "bps_consume_histogram: pdmp_ensemble_bps_consume_hist first");
+    if (chain_first < 0 || n < 0 || chain_first + n > e->cfg.nchains) return fail(PDMP_ERR_INVALID, "bps_consume_histogram: chain range");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(device_sync(e));
+    const int64_t m = e->bhs_m, len = m * (e->bhs_B + 2);
+    const size_t need = (size_t)(len + m + n);  // the pooled sums, T_last
+    if (e->bhs_out.n < need) PDMP_TRY(e->bhs_out.alloc(need));
+    double *oH = e->bhs_out.p, *oZ = oH + len, *oT = oZ + m;
+    // (nothing lies behind the last event: a chain's rows are its result, and only the pooled read computes)
+    const double *srcH = pooled ? oH : e->bhs_H.p + chain_first * len, *srcZ = pooled ? oZ : e->bhs_Z.p + chain_first * m;
+    if (H_dev) *H_dev = const_cast<double*>(srcH);
+    if (n == 0) return PDMP_OK;
+    if (pooled && (H || Z || H_dev)) LAUNCH_TRY("bps_consume_histogram", pdmp::launch_bps_hist_pool(hist_args(e), chain_first, n, oH, oZ, e->stream));
+    if (T_last) LAUNCH_TRY("bps_consume_histogram", pdmp::launch_bps_pairs_tlast(consume_args(e), chain_first, n, oT, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    const int64_t rows = pooled ? 1 : n;
+    if (H) HIP_TRY(hipMemcpy(H, srcH, (size_t)(rows * len) * sizeof(double), hipMemcpyDeviceToHost));
+    if (Z) HIP_TRY(hipMemcpy(Z, srcZ, (size_t)(rows * m) * sizeof(double), hipMemcpyDeviceToHost));
+    if (T_last) HIP_TRY(hipMemcpy(T_last, oT, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
     return PDMP_OK;
 }
 }  // extern "C"

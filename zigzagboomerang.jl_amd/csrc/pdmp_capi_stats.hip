@@ -137,6 +137,51 @@ pdmp_status pairs_list(const char* who, int64_t nchains, int64_t d, int64_t npai
     return PDMP_OK;
 }
 
+// what both families check of a histogram request: m, the bin count, that the rows [nchains x m x (bins + 2)] fit the reservation a condition
+// may make (checked before the lists are read), the lists, every coordinate once, finite ranges lo < hi with a finite positive width
+pdmp_status hist_list(const char* who, int64_t nchains, int64_t d, int64_t m, const int64_t* coords, const double* lo, const double* hi, int64_t bins,
+                      std::vector<int32_t>* vc, std::vector<double>* vlo, std::vector<double>* vhi, std::vector<double>* vw) {
+    if (m < 1) return fail(PDMP_ERR_INVALID, "%s: m = %lld must be at least 1", who, (long long)m);
+    if (bins < 1 || bins > 4096) return fail(PDMP_ERR_INVALID, "%s: bins = %lld is outside 1..4096", who, (long long)bins);
+    const uint64_t per_coord = (uint64_t)nchains * (uint64_t)(bins + 2) * sizeof(double);
+    if ((uint64_t)m > COND_MAX_ROW_BYTES / per_coord)
+        return fail(PDMP_ERR_INVALID, "%s: m = %lld rows of %llu bytes exceed the %llu GiB a condition may reserve", who, (long long)m,
+                    (unsigned long long)per_coord, (unsigned long long)(COND_MAX_ROW_BYTES >> 30));
+    if (!coords || !lo || !hi) return fail(PDMP_ERR_INVALID, "%s: null list", who);
+    if (m > d) return fail(PDMP_ERR_INVALID, "%s: m = %lld coordinates of %lld: one of them is listed twice", who, (long long)m, (long long)d);
+    vc->resize((size_t)m), vlo->resize((size_t)m), vhi->resize((size_t)m), vw->resize((size_t)m);
+    std::vector<char> seen((size_t)d, 0);
+    for (int64_t s = 0; s < m; ++s) {
+        if (coords[s] < 0 || coords[s] >= d)
+            return fail(PDMP_ERR_INVALID, "%s: coordinate %lld = %lld is outside [0, %lld)", who, (long long)s, (long long)coords[s], (long long)d);
+        if (seen[(size_t)coords[s]]) return fail(PDMP_ERR_INVALID, "%s: the coordinate %lld is listed twice", who, (long long)coords[s]);
+        seen[(size_t)coords[s]] = 1;
+        const double w = (hi[s] - lo[s]) / (double)bins;
+        if (!std::isfinite(lo[s]) || !std::isfinite(hi[s]) || !(lo[s] < hi[s]) || !std::isfinite(w) || !(w > 0))
+            return fail(PDMP_ERR_INVALID, "%s: the range of entry %lld must be finite with lo < hi (and a finite positive bin width)", who, (long long)s);
+        (*vc)[(size_t)s] = (int32_t)coords[s];
+        (*vlo)[(size_t)s] = lo[s];
+        (*vhi)[(size_t)s] = hi[s];
+        (*vw)[(size_t)s] = w;
+    }
+    return PDMP_OK;
+}
+
+static pdmp::HistArgs hist_args(const pdmp_ensemble* e) {
+    pdmp::HistArgs a{};
+    a.slot_of = e->d_hs_slot.p;
+    a.coords = e->d_hs_coords.p;
+    a.lo = e->d_hs_lo.p;
+    a.hi = e->d_hs_hi.p;
+    a.w = e->d_hs_w.p;
+    a.cur = e->d_hs_cur.p;
+    a.meta = e->d_hs_meta.p;
+    a.H = e->d_hs_H.p;
+    a.m = e->hs_m;
+    a.B = e->hs_B;
+    return a;
+}
+
 static pdmp::PairArgs pair_args(const pdmp_ensemble* e) {
     pdmp::PairArgs a{};
     a.adj_ptr = e->d_pr_ptr.p;
@@ -269,6 +314,9 @@ static pdmp_status consume_begin_impl(pdmp_ensemble* e, double grid_dt, int64_t 
     e->pr_on = false;
     e->d_pr_ptr.release(), e->d_pr_pi.release(), e->d_pr_pj.release(), e->d_pr_adj.release(), e->d_pr_c.release(), e->d_pr_S.release();
     e->d_pr_out.release(), e->d_pr_cur.release(), e->d_pr_meta.release();
+    e->hs_on = false;
+    e->d_hs_slot.release(), e->d_hs_coords.release(), e->d_hs_lo.release(), e->d_hs_hi.release(), e->d_hs_w.release(), e->d_hs_H.release();
+    e->d_hs_out.release(), e->d_hs_cur.release(), e->d_hs_meta.release();
     LAUNCH_TRY("consume_init", pdmp::launch_consume_init(e->d_rec.p, e->track ? 128 : 64, d, n, e->t0_state, e->d_ccur.p, e->cons_z, e->d_cmeta.p,
                                        grid_points > 0 ? e->d_cgrid.p : nullptr, grid_points, e->stream));
     if (barrier)  // (the records at t0 hold θ = 0 for a coordinate that starts frozen; d_thf holds every coordinate's θ0 as v_old)
@@ -332,6 +380,8 @@ pdmp_status pdmp_ensemble_consume(pdmp_ensemble* e) {
                                                                  e->stream));
     if (e->pr_on)  // (cursors of its own, like the condition's)
         LAUNCH_TRY("consume_pairs", pdmp::launch_pair_events(e->d_ev.p, e->cfg.trace_capacity, e->d_hdr.p, e->cfg.d, e->cfg.nchains, pair_args(e), e->stream));
+    if (e->hs_on)  // (cursors of its own too)
+        LAUNCH_TRY("consume_hist", pdmp::launch_hist_events(e->d_ev.p, e->cfg.trace_capacity, e->d_hdr.p, e->cfg.d, e->cfg.nchains, hist_args(e), e->stream));
     LAUNCH_TRY("consume", pdmp::launch_consume_events(e->d_ev.p, e->cfg.trace_capacity, e->d_hdr.p, nullptr, e->cfg.d, e->cfg.nchains, e->d_ccur.p, e->cons_z, e->d_cmeta.p,
                                          e->d_cgrid.p, e->cons_K, e->t0_state, e->cons_dt, e->stream, e->cons_cummean ? e->d_ccm.p : nullptr, e->cons_occ));
     HIP_TRY(hipStreamSynchronize(e->stream));
@@ -418,6 +468,9 @@ pdmp_status pdmp_ensemble_consume_async(pdmp_ensemble* e, void* stream) {
                                           "pdmp_ensemble_consume");
     if (e->pr_on)
         return fail(PDMP_ERR_UNSUPPORTED, "consume_async: the pair integrals (pdmp_ensemble_consume_pairs) are served by the synchronous consumer, "
+                                          "pdmp_ensemble_consume");
+    if (e->hs_on)
+        return fail(PDMP_ERR_UNSUPPORTED, "consume_async: the marginal histograms (pdmp_ensemble_consume_hist) are served by the synchronous consumer, "
                                           "pdmp_ensemble_consume");
     HIP_TRY(hipSetDevice(e->cfg.device));
     hipStream_t s = stream ? (hipStream_t)stream : e->stream;
@@ -646,6 +699,62 @@ pdmp_status pdmp_ensemble_consume_pair_integrals(pdmp_ensemble* e, int64_t chain
     HIP_TRY(hipStreamSynchronize(e->stream));
     if (S) HIP_TRY(hipMemcpy(S, oS, (size_t)(n * np) * sizeof(double), hipMemcpyDeviceToHost));
     if (J) HIP_TRY(hipMemcpy(J, oJ, (size_t)(n * d) * sizeof(double), hipMemcpyDeviceToHost));
+    if (T_last) HIP_TRY(hipMemcpy(T_last, oT, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    return PDMP_OK;
+}
+
+// marginal histograms on the device: the time each listed coordinate spends in each bin of its own range (DESIGN.md "Marginal histograms"): after
+// consume_begin / barrier_consume_begin and before the first consume
+pdmp_status pdmp_ensemble_consume_hist(pdmp_ensemble* e, int64_t m, const int64_t* coords, const double* lo, const double* hi, int64_t bins) {
+    if (!e) return fail(PDMP_ERR_INVALID, "null argument");
+    NEED_FACTORISED(e);
+    if (!e->consuming || !e->has_state) return fail(PDMP_ERR_INVALID, "consume_hist: pdmp_ensemble_consume_begin first");
+    if (e->cons_started) return fail(PDMP_ERR_INVALID, "consume_hist precedes the first consume (its cursors start from t0, x0, θ0)");
+    const int64_t d = e->cfg.d, nch = e->cfg.nchains;
+    std::vector<int32_t> vc;
+    std::vector<double> vlo, vhi, vw;
+    PDMP_TRY(hist_list("consume_hist", nch, d, m, coords, lo, hi, bins, &vc, &vlo, &vhi, &vw));
+    std::vector<int32_t> slot((size_t)d, -1);
+    for (int64_t s = 0; s < m; ++s) slot[(size_t)vc[(size_t)s]] = (int32_t)s;
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(device_sync(e));
+    e->hs_on = false;
+    PDMP_TRY(e->d_hs_slot.upload(slot));
+    PDMP_TRY(e->d_hs_coords.upload(vc));
+    PDMP_TRY(e->d_hs_lo.upload(vlo));
+    PDMP_TRY(e->d_hs_hi.upload(vhi));
+    PDMP_TRY(e->d_hs_w.upload(vw));
+    PDMP_TRY(e->d_hs_cur.alloc((size_t)(nch * m) * pdmp::hist_cursor_bytes()));
+    PDMP_TRY(e->d_hs_meta.alloc((size_t)nch * pdmp::hist_meta_bytes()));
+    PDMP_TRY(e->d_hs_H.alloc((size_t)(nch * m * (bins + 2))));
+    e->d_hs_out.release();
+    e->hs_m = m;
+    e->hs_B = (int32_t)bins;
+    HIP_TRY(hipMemsetAsync(e->d_hs_H.p, 0, (size_t)(nch * m * (bins + 2)) * sizeof(double), e->stream));
+    LAUNCH_TRY("consume_hist_init", pdmp::launch_hist_init(e->d_ccur.p, d, nch, e->t0_state, hist_args(e), e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->hs_on = true;
+    return PDMP_OK;
+}
+
+pdmp_status pdmp_ensemble_consume_histogram(pdmp_ensemble* e, int64_t chain_first, int64_t n, int pooled, double* H, double* Z, double* T_last,
+                                            void** H_dev) {
+    if (!e) return fail(PDMP_ERR_INVALID, "null argument");
+    NEED_FACTORISED(e);
+    if (!e->consuming || !e->hs_on) return fail(PDMP_ERR_INVALID, "consume_histogram: pdmp_ensemble_consume_hist first");
+    if (chain_first < 0 || n < 0 || chain_first + n > e->cfg.nchains) return fail(PDMP_ERR_INVALID, "consume_histogram: chain range");
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(device_sync(e));
+    const int64_t rows = (pooled ? 1 : n) * e->hs_m, len = rows * (e->hs_B + 2);
+    const size_t need = (size_t)(len + rows + n);
+    if (e->d_hs_out.n < need) PDMP_TRY(e->d_hs_out.alloc(need));
+    if (H_dev) *H_dev = e->d_hs_out.p;
+    if (n == 0) return PDMP_OK;
+    double *oH = e->d_hs_out.p, *oZ = oH + len, *oT = oZ + rows;
+    LAUNCH_TRY("consume_histogram", pdmp::launch_hist_read(hist_args(e), chain_first, n, pooled != 0, oH, oZ, oT, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (H) HIP_TRY(hipMemcpy(H, oH, (size_t)len * sizeof(double), hipMemcpyDeviceToHost));
+    if (Z) HIP_TRY(hipMemcpy(Z, oZ, (size_t)rows * sizeof(double), hipMemcpyDeviceToHost));
     if (T_last) HIP_TRY(hipMemcpy(T_last, oT, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
     return PDMP_OK;
 }

@@ -676,6 +676,7 @@ pdmp_status init_state(pdmp_ensemble* e, double t0, const double* x0, const doub
     e->consuming = false;
     e->cn_on = false;
     e->pr_on = false;
+    e->hs_on = false;
     e->trace_appended = false;
     return PDMP_OK;
 }

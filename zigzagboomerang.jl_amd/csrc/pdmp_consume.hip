@@ -857,4 +857,155 @@ int launch_pair_read(int64_t d, const PairArgs& a, int64_t chain_first, int64_t 
     return (int)hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------ marginal histograms (occupation times of a FactTrace)
+//
+// H[s][k + 1] = the time listed coordinate s spends in the bin [e_k, e_k+1) of its own range, k = −1 (below lo) .. B (at or above hi), exactly:
+// between two of its events a coordinate is a line, so the time in a bin is a closed form (DESIGN.md "Marginal histograms" has the contract;
+// tests/ref/hist_ref.c states it sequentially; hist_piece_of / hist_piece_at of pdmp_bps_common.hpp are the piece).  Cursors of its own (t, x, θ and
+// the rest time Z: 32 bytes per chain and LISTED coordinate); those of consume_events_kernel are read once, by the init.
+//   hist_events_kernel  one workgroup of one wavefront per chain walks the slice in order.  64 records at a time are loaded one per lane with the slot
+//     of their coordinate (slot_of [d], shared by the chains; −1 = not listed): one ballot drops the unlisted events of the chunk at once.  A listed
+//     event is handed round by readlane; every lane reads the cursor (one address), makes the piece ready and takes the bins k0 + lane, k0 + lane +
+//     64, ... of the k0 .. k1 it touches: a piece that crosses many bins is spread over the lanes, a row entry is owned by one lane.  Lane 0 then
+//     writes Z and the cursor (every lane's load of the old cursor was issued before that store).  Events of one coordinate keep their order -- the
+//     walk is sequential -- and the stores of an event have reached memory before the next listed event's loads are issued (s_waitcnt vmcnt(0): the
+//     next event may be the same coordinate's, with other lanes on the same entries).  So a row is updated in the event order of its coordinate and the
+//     result does not depend on how the run was sliced.  No atomics.
+//   hist_read_kernel  one thread per output entry: out = H + hist_piece_at(the open piece from the cursor to T_last, k), in registers; pooled: the
+//     chains of the range added in order.  The rows are not touched: a run can be read midway, and twice.
+struct HistCursor {
+    double t, x, th, Z;  // clock, position, velocity after the coordinate's last consumed event; the time it rested (θ = 0) up to t
+};
+static_assert(sizeof(HistCursor) == 32, "a cursor never straddles a 128-byte line");
+size_t hist_cursor_bytes() { return sizeof(HistCursor); }
+size_t hist_meta_bytes() { return sizeof(PairMeta); }  // (events consumed, T_last: the pair consumer's)
+
+__device__ __forceinline__ HistBins hist_bins(const HistArgs& A, int64_t s) {
+    HistBins b;
+    b.lo = A.lo[s];
+    b.hi = A.hi[s];
+    b.w = A.w[s];
+    b.B = A.B;
+    return b;
+}
+
+__global__ __launch_bounds__(256) void hist_init_kernel(const ConsumeCursor* __restrict__ cur, int64_t d, int64_t nchains, double t0, HistArgs A) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k < nchains) {
+        PairMeta m;
+        m.consumed = 0;
+        m.t_last = t0;
+        static_cast<PairMeta*>(A.meta)[k] = m;
+    }
+    if (k >= nchains * A.m) return;
+    const int64_t chain = k / A.m, s = k - chain * A.m;
+    const ConsumeCursor c = cur[chain * d + A.coords[s]];  // (before the first consume: t0, x0, θ0 -- θ = 0 where a barrier ensemble starts frozen)
+    HistCursor h;
+    h.t = c.t;
+    h.x = c.x;
+    h.th = c.th;
+    h.Z = 0.0;
+    static_cast<HistCursor*>(A.cur)[k] = h;
+}
+
+__global__ __launch_bounds__(64) void hist_events_kernel(const pdmp_event* ev0, int64_t cap, const DevChain* hdr, int64_t d, HistArgs A) {
+    const int64_t chain = blockIdx.x;
+    const int lane = threadIdx.x;
+    PairMeta* const meta = static_cast<PairMeta*>(A.meta) + chain;
+    const uint64_t ntrace = hdr[chain].c.ntrace, nevents = hdr[chain].c.nevents;
+    const uint64_t n = ntrace < (uint64_t)cap ? ntrace : (uint64_t)cap;
+    const uint64_t consumed = meta->consumed;
+    const uint64_t first_global = nevents - ntrace;  // global index of buffer slot 0
+    const uint64_t pos0 = (consumed > first_global) ? (consumed - first_global) : 0;  // first unconsumed slot
+    if (pos0 >= n) return;
+    const pdmp_event* const ev = ev0 + chain * cap;
+    HistCursor* const cur = static_cast<HistCursor*>(A.cur) + chain * A.m;
+    double* const H = A.H + chain * A.m * (int64_t)(A.B + 2);
+    for (uint64_t base = pos0; base < n; base += 64) {
+        const int cnt = (n - base < 64) ? (int)(n - base) : 64;
+        double rt = 0.0, rx = 0.0, rth = 0.0;
+        int32_t rs = -1;
+        if (lane < cnt) {
+            const pdmp_event r = ev[base + (uint64_t)lane];
+            rt = r.t;
+            rx = r.x;
+            rth = r.theta;
+            if ((uint64_t)r.i < (uint64_t)d) rs = A.slot_of[r.i];
+        }
+        uint64_t listed = __ballot(rs >= 0);  // (wave-uniform: the unlisted events of the chunk are gone)
+        while (listed) {
+            const int q = __builtin_ctzll(listed);
+            listed &= listed - 1;
+            const int64_t s = (int32_t)readlane_u32((uint32_t)rs, q);
+            const double t = readlane_f64(rt, q), x = readlane_f64(rx, q), th = readlane_f64(rth, q);
+            const HistCursor c = cur[s];
+            const HistBins bn = hist_bins(A, s);
+            const double tau = t - c.t;
+            const HistPiece p = hist_piece_of(bn, c.x, c.th, tau);
+            double* const row = H + s * (int64_t)(A.B + 2);
+            for (int k = p.k0 + lane; k <= p.k1; k += 64) row[k + 1] = row[k + 1] + hist_piece_at(bn, p, k);
+            if (lane == 0) {
+                HistCursor c2;
+                c2.Z = c.Z + hist_piece_rest(c.th, tau);
+                c2.t = t;
+                c2.x = x;
+                c2.th = th;
+                cur[s] = c2;
+            }
+            pair_wait_stores();  // the row and the cursor just written, before the next listed event reads them
+        }
+    }
+    if (lane == 0) {
+        PairMeta m;
+        m.consumed = nevents;
+        m.t_last = ev[n - 1].t;
+        *meta = m;
+    }
+}
+
+// one output entry of the read: row entry r < B + 2 of (chain, s) with the open piece closed at T, or (r == B + 2) the rest time Z
+__device__ __forceinline__ double hist_read_entry(const HistArgs& A, int64_t chain, int64_t s, int64_t r) {
+    const HistCursor c = static_cast<const HistCursor*>(A.cur)[chain * A.m + s];
+    const double tau = static_cast<const PairMeta*>(A.meta)[chain].t_last - c.t;
+    if (r == A.B + 2) return c.Z + hist_piece_rest(c.th, tau);
+    const HistBins bn = hist_bins(A, s);
+    const HistPiece p = hist_piece_of(bn, c.x, c.th, tau);
+    return A.H[(chain * A.m + s) * (int64_t)(A.B + 2) + r] + hist_piece_at(bn, p, (int)r - 1);
+}
+
+__global__ __launch_bounds__(256) void hist_read_kernel(HistArgs A, int64_t chain_first, int64_t n, int pooled, double* H_out, double* Z_out, double* T_out) {
+    const int64_t per = A.m * (int64_t)(A.B + 3);  // a chain's entries: m rows of B + 2, then (per row) Z
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k < n) T_out[k] = static_cast<const PairMeta*>(A.meta)[chain_first + k].t_last;
+    if (k >= (pooled ? 1 : n) * per) return;
+    const int64_t q = k / per, e = k - q * per;
+    const int64_t s = e / (A.B + 3), r = e - s * (A.B + 3);
+    double v;
+    if (pooled) {
+        v = 0.0;
+        for (int64_t c = 0; c < n; ++c) v = v + hist_read_entry(A, chain_first + c, s, r);
+    } else {
+        v = hist_read_entry(A, chain_first + q, s, r);
+    }
+    if (r == A.B + 2) Z_out[q * A.m + s] = v;
+    else H_out[(q * A.m + s) * (int64_t)(A.B + 2) + r] = v;
+}
+
+int launch_hist_init(const void* cur, int64_t d, int64_t nchains, double t0, const HistArgs& a, void* stream) {
+    const int64_t n = nchains * (a.m > 1 ? a.m : 1);
+    hipLaunchKernelGGL(hist_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, static_cast<const ConsumeCursor*>(cur), d, nchains,
+                       t0, a);
+    return (int)hipGetLastError();
+}
+int launch_hist_events(const pdmp_event* ev, int64_t cap, const DevChain* hdr, int64_t d, int64_t nchains, const HistArgs& a, void* stream) {
+    hipLaunchKernelGGL(hist_events_kernel, dim3((unsigned)nchains), dim3(64), 0, (hipStream_t)stream, ev, cap, hdr, d, a);
+    return (int)hipGetLastError();
+}
+int launch_hist_read(const HistArgs& a, int64_t chain_first, int64_t n, int pooled, double* H_out, double* Z_out, double* T_out, void* stream) {
+    const int64_t ent = (pooled ? 1 : n) * a.m * (int64_t)(a.B + 3);
+    const int64_t tot = ent > n ? ent : n;
+    hipLaunchKernelGGL(hist_read_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, chain_first, n, pooled, H_out, Z_out, T_out);
+    return (int)hipGetLastError();
+}
+
 }  // namespace pdmp

@@ -399,4 +399,101 @@ int launch_bps_pairs_tlast(const BpsConsumeArgs& p, int64_t chain_first, int64_t
     return (int)hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------ marginal histograms (occupation times of a PDMPTrace)
+//
+// H[s][k + 1] = the time listed coordinate s spends in the bin [e_k, e_k+1) of its own range over [t0, T_last], exactly (DESIGN.md "Marginal
+// histograms"; tests/ref/hist_ref.c states the contract; hist_piece_of / hist_piece_at of pdmp_bps_common.hpp are the piece).  An event replaces the
+// whole state, so the piece of an event (t_k, ...) is (x_c,i, f_c,i ? θ_c,i : 0, t_k − t_c) from the cursor before it, for every listed coordinate.
+// The listed coordinates of a chain lie across the lanes: one thread per (chain, listed coordinate) walks the chain's segment in event order and
+// adds each piece to the bins it touches.  A row belongs to one thread, so lanes never share an entry and nothing is atomic; the rest time Z stays
+// in a register.  The threads of a workgroup belong to one chain: the event times are wave-uniform loads; the loads of the next BC_AHEAD events are
+// issued before the arithmetic of the current ones, as in bps_consume_kernel.  Runs BEFORE bps_consume_kernel of the same slice and only reads what
+// that kernel carries.  Nothing is open behind the last event: the rows are the result, the pooled read only adds the chains in order.
+struct BpsHistEvent {
+    double t, x, th;
+    bool f;
+};
+
+template <bool STICKY>
+__device__ __forceinline__ BpsHistEvent bh_load(const BpsConsumeArgs& P, int64_t slot0, uint64_t e, uint64_t n, int64_t i) {
+    const int64_t s = slot0 + (int64_t)(e < n ? e : n - 1);  // (behind the segment: its last event once more, never applied)
+    BpsHistEvent ev;
+    ev.t = P.ev_t[s];
+    ev.x = P.ev_x[s * P.d + i];
+    ev.th = P.ev_th[s * P.d + i];
+    ev.f = STICKY ? ((P.ev_f[s * BPS_STICKY_WORDS + (i >> 6)] >> (i & 63)) & 1ull) != 0 : true;
+    return ev;
+}
+
+template <bool STICKY>
+__global__ __launch_bounds__(256) void bps_hist_kernel(BpsConsumeArgs P, BpsHistArgs Q, int64_t blocks_per_chain) {
+    const int64_t chain = (int64_t)blockIdx.x / blocks_per_chain;
+    const int64_t s = ((int64_t)blockIdx.x - chain * blocks_per_chain) * 256 + threadIdx.x;
+    if (s >= Q.m) return;
+    const BpsCondSlice sl = bps_cond_slice(P, chain);
+    if (sl.pos >= sl.n) return;
+    const int64_t d = P.d, i = Q.coords[s];
+    HistBins bn;
+    bn.lo = Q.lo[s];
+    bn.hi = Q.hi[s];
+    bn.w = Q.w[s];
+    bn.B = Q.B;
+    double* const row = Q.H + (chain * Q.m + s) * (int64_t)(Q.B + 2);
+    const BpsConsumeMeta* const meta = static_cast<const BpsConsumeMeta*>(P.meta) + chain * P.nstrips;
+    const int64_t slot0 = chain * P.cap;
+    double Z = Q.Z[chain * Q.m + s], t_cur = sl.t_cur;
+    double x = P.cx[chain * d + i], th = P.cth[chain * d + i];
+    bool f = STICKY ? ((meta[i >> 6].free >> (i & 63)) & 1ull) != 0 : true;
+
+    BpsHistEvent now[BC_AHEAD], next[BC_AHEAD];
+#pragma unroll
+    for (int q = 0; q < BC_AHEAD; ++q) now[q] = bh_load<STICKY>(P, slot0, sl.pos + q, sl.n, i);
+    for (uint64_t base = sl.pos; base < sl.n; base += BC_AHEAD) {
+#pragma unroll
+        for (int q = 0; q < BC_AHEAD; ++q) next[q] = bh_load<STICKY>(P, slot0, base + BC_AHEAD + q, sl.n, i);
+#pragma unroll
+        for (int q = 0; q < BC_AHEAD; ++q) {
+            if (base + q >= sl.n) break;
+            const double tau = now[q].t - t_cur, v = f ? th : 0.0;
+            const HistPiece p = hist_piece_of(bn, x, v, tau);
+            for (int k = p.k0; k <= p.k1; ++k) row[k + 1] = row[k + 1] + hist_piece_at(bn, p, k);
+            Z = Z + hist_piece_rest(v, tau);
+            x = now[q].x;
+            th = now[q].th;
+            f = now[q].f;
+            t_cur = now[q].t;
+        }
+#pragma unroll
+        for (int q = 0; q < BC_AHEAD; ++q) now[q] = next[q];
+    }
+    Q.Z[chain * Q.m + s] = Z;
+}
+
+__global__ __launch_bounds__(256) void bps_hist_pool_kernel(BpsHistArgs Q, int64_t chain_first, int64_t n, double* out_H, double* out_Z) {
+    const int64_t len = Q.m * (int64_t)(Q.B + 2);
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= len + Q.m) return;
+    const bool is_h = k < len;
+    const double* const src = is_h ? Q.H + chain_first * len + k : Q.Z + chain_first * Q.m + (k - len);
+    const int64_t stride = is_h ? len : Q.m;
+    double acc = 0.0;
+    for (int64_t c = 0; c < n; ++c) acc = acc + src[c * stride];
+    if (is_h) out_H[k] = acc;
+    else out_Z[k - len] = acc;
+}
+
+int launch_bps_hist(const BpsConsumeArgs& p, const BpsHistArgs& q, void* stream) {
+    const int64_t bpc = (q.m + 255) / 256;
+    const dim3 grid((unsigned)(p.nchains * bpc)), block(256);
+    if (p.ev_f) hipLaunchKernelGGL((bps_hist_kernel<true>), grid, block, 0, (hipStream_t)stream, p, q, bpc);
+    else hipLaunchKernelGGL((bps_hist_kernel<false>), grid, block, 0, (hipStream_t)stream, p, q, bpc);
+    return (int)hipGetLastError();
+}
+
+int launch_bps_hist_pool(const BpsHistArgs& q, int64_t chain_first, int64_t n, double* out_H, double* out_Z, void* stream) {
+    const int64_t tot = q.m * (int64_t)(q.B + 3);
+    hipLaunchKernelGGL(bps_hist_pool_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, q, chain_first, n, out_H, out_Z);
+    return (int)hipGetLastError();
+}
+
 }  // namespace pdmp

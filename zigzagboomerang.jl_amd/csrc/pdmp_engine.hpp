@@ -634,6 +634,23 @@ size_t pair_meta_bytes();
 int launch_pair_init(const void* cur, int64_t d, int64_t nchains, double t0, const PairArgs& a, void* stream);
 int launch_pair_events(const pdmp_event* ev, int64_t cap, const DevChain* hdr, int64_t d, int64_t nchains, const PairArgs& a, void* stream);
 int launch_pair_read(int64_t d, const PairArgs& a, int64_t chain_first, int64_t n, double* S_out, double* J_out, double* T_out, void* stream);
+// ... the marginal histograms (pdmp_ensemble_consume_hist): the map coordinate -> slot [d] (−1: not listed), the listed coordinates [m] with their
+// ranges and widths [m], cursors of its own (t, x, θ, Z: 32 bytes per chain and LISTED coordinate), per-chain progress and the rows H
+// [nchains x m x (B + 2)]
+struct HistArgs {
+    const int32_t *slot_of, *coords;
+    const double *lo, *hi, *w;
+    void *cur, *meta;
+    double* H;
+    int64_t m;
+    int32_t B;
+};
+size_t hist_cursor_bytes();
+size_t hist_meta_bytes();
+int launch_hist_init(const void* cur, int64_t d, int64_t nchains, double t0, const HistArgs& a, void* stream);
+int launch_hist_events(const pdmp_event* ev, int64_t cap, const DevChain* hdr, int64_t d, int64_t nchains, const HistArgs& a, void* stream);
+// H_out [n x m x (B + 2)], Z_out [n x m] (pooled: [m x (B + 2)], [m], the chains summed in order), T_out [n]
+int launch_hist_read(const HistArgs& a, int64_t chain_first, int64_t n, int pooled, double* H_out, double* Z_out, double* T_out, void* stream);
 int launch_math_probe(uint64_t seed, int64_t n, double* out, void* stream);
 // pdmp_consume_bps.hip: the streaming consumers of the Bouncy Particle family's trace buffers.  One block of pointers and numbers for its three
 // kernels: the trace (ev_f: a sticky ensemble's masks, else nullptr), the chain headers, the Boomerang's centre (nullptr: linear flow), the state
@@ -674,6 +691,18 @@ struct BpsPairArgs {
 };
 int launch_bps_pairs(const BpsConsumeArgs& p, const BpsPairArgs& q, void* stream);
 int launch_bps_pairs_tlast(const BpsConsumeArgs& p, int64_t chain_first, int64_t n, double* T_out, void* stream);
+// ... the marginal histograms (pdmp_ensemble_bps_consume_hist): the listed coordinates [m] with their ranges and widths, the rows H
+// [nchains x m x (B + 2)] and the rest times Z [nchains x m]; launched before launch_bps_consume_events of the same slice
+struct BpsHistArgs {
+    const int32_t* coords;
+    const double *lo, *hi, *w;
+    double *H, *Z;
+    int64_t m;
+    int32_t B;
+};
+int launch_bps_hist(const BpsConsumeArgs& p, const BpsHistArgs& q, void* stream);
+// the pooled read: out_H [m x (B + 2)] and out_Z [m], the chains [chain_first, chain_first + n) summed in order
+int launch_bps_hist_pool(const BpsHistArgs& q, int64_t chain_first, int64_t n, double* out_H, double* out_Z, void* stream);
 
 #ifdef PDMP_EXTRA_KERNELS
 // pdmp_debug_math_eval (include/pdmp_debug.h, parity library only): a translation unit that calls the shared scalar functions of pdmp_device.hpp

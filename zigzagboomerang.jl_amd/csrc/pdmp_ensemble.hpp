@@ -233,6 +233,15 @@ struct pdmp_ensemble {
     DevBuf<unsigned char> d_pr_cur, d_pr_meta;
     bool pr_on = false;
     int64_t pr_np = 0;
+    // pdmp_ensemble_consume_hist: the map coordinate -> slot [d], the listed coordinates with their ranges and widths [m], the histogram consumer's
+    // own cursors (t, x, θ, Z) [nchains x m] and progress, the rows H [nchains x m x (bins + 2)]; hs_out: what consume_histogram last read (H, Z,
+    // T_last), reserved by the first read
+    DevBuf<int32_t> d_hs_slot, d_hs_coords;
+    DevBuf<double> d_hs_lo, d_hs_hi, d_hs_w, d_hs_H, d_hs_out;
+    DevBuf<unsigned char> d_hs_cur, d_hs_meta;
+    bool hs_on = false;
+    int64_t hs_m = 0;
+    int32_t hs_B = 0;
     bool trace_appended = false;  // pdmp_debug_trace_append put events into the trace that no record knows of: run is refused until the next set_state
     // pdmp_ensemble_consume_async: a second trace buffer (the event loop writes one while the consumer reads the other), the consumer's stream,
     // the (ntrace, nevents) snapshots of the two most recent slices and the events that order the two streams
@@ -312,6 +321,14 @@ struct pdmp_ensemble {
     bool bpr_on = false;
     int64_t bpr_np = 0;
 
+    // pdmp_ensemble_bps_consume_hist: the listed coordinates with their ranges and widths [m], H [nchains x m x (bins + 2)], Z [nchains x m];
+    // bhs_out: the pooled sums and T_last of the last read
+    DevBuf<int32_t> bhs_coords;
+    DevBuf<double> bhs_lo, bhs_hi, bhs_w, bhs_H, bhs_Z, bhs_out;
+    bool bhs_on = false;
+    int64_t bhs_m = 0;
+    int32_t bhs_B = 0;
+
     pdmp::ZzTables tables() const {
         pdmp::ZzTables tb{};
         tb.colptr = d_colptr.p;
@@ -380,6 +397,9 @@ pdmp_status condition_rows_fit(const char* who, int64_t nchains, int64_t d, int6
 // ... what both families check of the pair list of pdmp_ensemble_[bps_]consume_pairs; the list and the centre (zeros for NULL) come back
 pdmp_status pairs_list(const char* who, int64_t nchains, int64_t d, int64_t npairs, const int64_t* pi, const int64_t* pj, const double* center,
                        std::vector<int32_t>* vi, std::vector<int32_t>* vj, std::vector<double>* c);
+// ... what both families check of the arguments of pdmp_ensemble_[bps_]consume_hist; the coordinates, ranges and widths come back
+pdmp_status hist_list(const char* who, int64_t nchains, int64_t d, int64_t m, const int64_t* coords, const double* lo, const double* hi, int64_t bins,
+                      std::vector<int32_t>* vc, std::vector<double>* vlo, std::vector<double>* vhi, std::vector<double>* vw);
 // pdmp_capi_tune.hip: set_state with the placement probes
 pdmp_status init_state_tuned(pdmp_ensemble* e, double t0, const double* x0, const double* th0, const double* c, const uint64_t* seeds, uint64_t seed0);
 pdmp_status init_state_bps_tuned(pdmp_ensemble* e, double t0, const double* x0, const double* theta0, double c, const uint64_t* seeds);

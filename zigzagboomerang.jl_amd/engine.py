@@ -633,6 +633,46 @@ class Ensemble:
         """consume_pair_integrals for the Bouncy Particle family: the integrals over [t0, T_last] exactly."""
         return self._pair_integrals(self._L.pdmp_ensemble_bps_consume_pair_integrals, chain_first, n)
 
+    # ---- marginal histograms on the device (pdmp_ensemble_[bps_]consume_hist): the time each listed coordinate spends in each bin of its range
+    def _hist(self, fn, coords, lo, hi, bins):
+        coords = np.arange(self.d, dtype=np.int64) if coords is None else np.ascontiguousarray(coords, dtype=np.int64).reshape(-1)
+        lo = np.ascontiguousarray(np.broadcast_to(np.asarray(lo, dtype=np.float64), coords.shape))
+        hi = np.ascontiguousarray(np.broadcast_to(np.asarray(hi, dtype=np.float64), coords.shape))
+        m = int(coords.size)
+        _lib.check(fn(self._h, m, _ptr(coords) if m else None, _ptr(lo) if m else None, _ptr(hi) if m else None, int(bins)))
+        self._hist_shape = (m, int(bins) + 2)
+
+    def _histogram(self, fn, chain_first, n, pooled):
+        if n is None:
+            n = self.nchains - chain_first
+        m, row = getattr(self, "_hist_shape", (0, 0))
+        lead = () if pooled else (n,)
+        H, Z, T = np.empty(lead + (m, row)), np.empty(lead + (m,)), np.empty(n)
+        _lib.check(fn(self._h, int(chain_first), int(n), int(bool(pooled)), _ptr(H), _ptr(Z), _ptr(T), None))
+        return H, Z, T
+
+    def consume_hist(self, coords, lo, hi, bins):
+        """After consume_begin (or barrier_consume_begin) and before the first consume(): from then on consume() also keeps, for every listed
+        coordinate (0-based, distinct, stored in the given order; None: all of d), the exact time the path spends in each of `bins` bins of
+        [lo, hi) (scalars broadcast), below lo and at or above hi (trace.marginal_histogram is the host mirror, trace.histogram_quantiles what
+        follows from it)."""
+        self._hist(self._L.pdmp_ensemble_consume_hist, coords, lo, hi, bins)
+
+    def consume_histogram(self, chain_first=0, n=None, pooled=False):
+        """(H [n x m x (bins + 2)], Z [n x m], T_last [n]) of chains [chain_first, chain_first + n): slot 0 the time below lo, slots 1..bins the
+        bins, slot bins + 1 the time at or above hi; Z the time at rest.  Every open piece is closed at the chain's last consumed event time;
+        the rows are not touched, so the run can go on.  pooled=True: H [m x (bins + 2)] and Z [m], the chains added in chain order."""
+        return self._histogram(self._L.pdmp_ensemble_consume_histogram, chain_first, n, pooled)
+
+    def bps_consume_hist(self, coords, lo, hi, bins):
+        """consume_hist for the Bouncy Particle family (event-recorded BouncyParticle and its sticky form): after bps_consume_begin and before
+        the first bps_consume()."""
+        self._hist(self._L.pdmp_ensemble_bps_consume_hist, coords, lo, hi, bins)
+
+    def bps_consume_histogram(self, chain_first=0, n=None, pooled=False):
+        """consume_histogram for the Bouncy Particle family: the times over [t0, T_last] exactly."""
+        return self._histogram(self._L.pdmp_ensemble_bps_consume_histogram, chain_first, n, pooled)
+
     # ---- trace consumers of the Bouncy Particle family on the device (pdmp_ensemble_bps_consume_*)
     def bps_consume_begin(self, grid_dt=0.0, grid_points=0):
         """After set_state_bps, before the first run: (t0, x0, θ0) become the cursors; grid_points > 0 reserves the grid t0 + k·grid_dt."""

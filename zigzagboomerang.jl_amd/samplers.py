@@ -34,8 +34,8 @@ def _consume_capacity(consume, trace, trace_capacity):
     """The trace capacity of a Bouncy Particle run: with consume=... the events are written to the device buffer even where trace=False."""
     if consume is None:
         return trace_capacity if trace else 0
-    if not isinstance(consume, dict) or set(consume) - {"dt", "points", "condition", "hits", "cov", "center"}:
-        raise TypeError("consume=dict(dt=..., points=...[, condition=(p, n), hits=K][, cov=P, center=c])")
+    if not isinstance(consume, dict) or set(consume) - {"dt", "points", "condition", "hits", "cov", "center", "hist"}:
+        raise TypeError("consume=dict(dt=..., points=...[, condition=(p, n), hits=K][, cov=P, center=c][, hist=dict(coords=..., lo=..., hi=..., bins=B)])")
     if trace_capacity <= 0:
         raise ValueError("consume=... reads the device trace buffer: trace_capacity must be positive")
     return trace_capacity
@@ -80,6 +80,36 @@ def _pairs_of(consume, d):
     return pi, pj, consume.get("center")
 
 
+def _hist_of(consume, d):
+    """(coords, lo, hi, bins) of consume=dict(..., hist=dict(coords=..., lo=..., hi=..., bins=B)) -- the marginal histograms on the device -- or
+    None.  coords=None: all of d; scalars for lo / hi broadcast over the listed coordinates."""
+    if consume is None or "hist" not in consume:
+        return None
+    h = consume["hist"]
+    if not isinstance(h, dict) or set(h) - {"coords", "lo", "hi", "bins"} or not {"lo", "hi", "bins"} <= set(h):
+        raise TypeError("consume=dict(hist=dict(coords=..., lo=..., hi=..., bins=B))")
+    coords = np.arange(d, dtype=np.int64) if h.get("coords") is None else np.asarray(h["coords"], dtype=np.int64).reshape(-1)
+    lo = np.ascontiguousarray(np.broadcast_to(np.asarray(h["lo"], dtype=np.float64), coords.shape))
+    hi = np.ascontiguousarray(np.broadcast_to(np.asarray(h["hi"], dtype=np.float64), coords.shape))
+    return coords, lo, hi, int(h["bins"])
+
+
+def _admits(consume):
+    """a consume= whose keys alone admit it on every target: cov=P or hist=dict(...)"""
+    return isinstance(consume, dict) and ("cov" in consume or "hist" in consume)
+
+
+def _hist_result(out, hist, histogram, single):
+    """hist_coords [m], hist_edges [m x (B + 1)], hist_H [nchains x m x (B + 2)], hist_Z [nchains x m]: with out["T"] what
+    trace.histogram_quantiles takes"""
+    from .trace import histogram_edges
+    coords, lo, hi, bins = hist
+    out["hist_coords"], out["hist_edges"] = coords, histogram_edges(lo, hi, bins)
+    out["hist_H"], out["hist_Z"], _ = histogram()
+    if single:
+        out["hist_H"], out["hist_Z"] = out["hist_H"][0], out["hist_Z"][0]
+
+
 def _pairs_result(out, pairs, integrals):
     """pairs = (pi, pj), pair_S [nchains x npairs], pair_J [nchains x d]: with out["T"] what trace.covariance takes"""
     out["pairs"] = (pairs[0], pairs[1])
@@ -112,6 +142,8 @@ def _consume_result(ens, consume, single, sticky):
         _pairs_result(out, pairs, ens.bps_consume_pair_integrals)
         if single:
             out["pair_S"], out["pair_J"] = out["pair_S"][0], out["pair_J"][0]
+    if _hist_of(consume, ens.d) is not None:
+        _hist_result(out, _hist_of(consume, ens.d), ens.bps_consume_histogram, single)
     return out
 
 
@@ -143,6 +175,10 @@ def spdmp(target, t0, x0, θ0, T, c, *GF, factor=1.8, adapt=False, adaptscale=Fa
     consume=dict(cov=P[, center=c]) (any device target with a ZigZag; also on sspdmp and pdmp): the exact pair integrals of the path, kept on the
     device slice by slice -- P a sparse matrix (its structural lower triangle plus the diagonal), "diag" or a (pi, pj) tuple; the element gains
     pairs = (pi, pj), pair_S [npairs] and pair_J [d] per chain, which with T (L = T − t0) is what trace.covariance takes.
+    consume=dict(hist=dict(coords=None, lo=..., hi=..., bins=B)) (any device target with a ZigZag; also on sspdmp, pdmp, stickyzz and sspdmp2): the
+    exact marginal histograms of the path -- the time each listed coordinate (None: all) spends in each of B bins of [lo, hi) (scalars broadcast),
+    below and above -- kept on the device slice by slice; the element gains hist_coords [m], hist_edges [m x (B + 1)], hist_H [m x (B + 2)] and
+    hist_Z [m] (the time at rest) per chain: trace.histogram_quantiles(hist_H, lo, hi, q) gives medians and credible intervals.
 
     G: the neighbourhoods a proposal moves before its gradient is taken (:82,171-179) -- a sparse matrix whose column patterns are the
     G[i] (e.g. the target's Γ when the bounding F.Γ is sparser) or a sequence of index arrays; G[i] ⊇ G1[i] = pattern of F.Γ[:, i] is
@@ -297,8 +333,8 @@ def sspdmp(target, t0, x0, θ0, T, c, *GFκ, reversible=False, strong_upperbound
             raise TypeError("BouncyParticle: target is None (∇ϕ!(y, x) = B.Γ(x − B.μ)) or a GaussianTarget of its own")
         return _bps(t0, x0, θ0, T, c, F, 2.0 if factor is None else factor, adapt, seed, device, trace_capacity, trace, target=target,
                     sticky=(GFκ[1], strong_upperbounds), consume=consume)
-    if consume is not None and not (isinstance(consume, dict) and "cov" in consume):
-        raise TypeError("consume is a keyword of the sticky BouncyParticle / Boomerang, or with cov=P (elsewhere the ZigZag's device consumers are "
+    if consume is not None and not _admits(consume):
+        raise TypeError("consume is a keyword of the sticky BouncyParticle / Boomerang, or with cov=P or hist=dict(...) (elsewhere the ZigZag's device consumers are "
                         "Ensemble.consume_*)")
     if len(GFκ) not in (2, 3):
         raise TypeError("expected sspdmp(target, t0, x0, θ0, T, c, [G,] F, κ, ...)")
@@ -478,8 +514,8 @@ def _zigzag(sampler, target, t0, x0, θ0, T, c, F, factor, adapt, seed, device, 
         raise TypeError("the device path supports F::ZigZag and F::FactBoomerang")
     if not isinstance(target, (GaussianTarget, LogisticTarget, DiffusionBridgeTarget)):
         raise TypeError("target must be one of the device-resident families (GaussianTarget, LogisticTarget, DiffusionBridgeTarget)")
-    if consume is not None and barriers is None and not isinstance(target, DiffusionBridgeTarget) and not (isinstance(consume, dict) and "cov" in consume):
-        raise TypeError("consume is a keyword of spdmp with a DiffusionBridgeTarget, or with cov=P (elsewhere the ZigZag's device consumers are "
+    if consume is not None and barriers is None and not isinstance(target, DiffusionBridgeTarget) and not _admits(consume):
+        raise TypeError("consume is a keyword of spdmp with a DiffusionBridgeTarget, or with cov=P or hist=dict(...) (elsewhere the ZigZag's device consumers are "
                         "Ensemble.consume_*)")
     x0 = np.asarray(x0, dtype=np.float64)
     θ0 = np.asarray(θ0, dtype=np.float64)
@@ -524,6 +560,8 @@ def _zigzag(sampler, target, t0, x0, θ0, T, c, F, factor, adapt, seed, device, 
                 ens.consume_condition(*_condition_of(consume))
             if _pairs_of(consume, d) is not None:
                 ens.consume_pairs(*_pairs_of(consume, d))
+            if _hist_of(consume, d) is not None:
+                ens.consume_hist(*_hist_of(consume, d))
         events = [[] for _ in range(nch)]
         while True:
             ens.run(T, _lib.RUN_REFERENCE_TAIL)
@@ -556,6 +594,8 @@ def _zigzag(sampler, target, t0, x0, θ0, T, c, F, factor, adapt, seed, device, 
                 _pairs_result(consumed, _pairs_of(consume, d), ens.consume_pair_integrals)
                 if single:
                     consumed["pair_S"], consumed["pair_J"] = consumed["pair_S"][0], consumed["pair_J"][0]
+            if _hist_of(consume, d) is not None:
+                _hist_result(consumed, _hist_of(consume, d), ens.consume_histogram, single)
         fs = ens.final_state()
         cnt = ens.counters()
         sig = ens.final_sigma() if adaptscale else None
@@ -621,6 +661,8 @@ def _bps_modern(target, t0, x0, θ0, T, c, B, factor, adapt, seed, device, trace
                 ens.bps_consume_condition(*_condition_of(consume))
             if _pairs_of(consume, ens.d) is not None:
                 ens.bps_consume_pairs(*_pairs_of(consume, ens.d))
+            if _hist_of(consume, ens.d) is not None:
+                ens.bps_consume_hist(*_hist_of(consume, ens.d))
         if count:
             ens.set_bps_record_limit(int(T))
         T_end = float("inf") if count else float(T)
@@ -698,6 +740,8 @@ def _bps(t0, x0, θ0, T, c, B, factor, adapt, seed, device, trace_capacity, trac
                 ens.bps_consume_condition(*_condition_of(consume))
             if _pairs_of(consume, ens.d) is not None:
                 ens.bps_consume_pairs(*_pairs_of(consume, ens.d))
+            if _hist_of(consume, ens.d) is not None:
+                ens.bps_consume_hist(*_hist_of(consume, ens.d))
         fs_ = [[] for _ in range(nch)]
         ts = [[] for _ in range(nch)]
         xs = [[] for _ in range(nch)]

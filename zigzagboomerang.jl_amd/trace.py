@@ -625,6 +625,132 @@ def covariance(pi, pj, S, J, L, pooled=True, center=None):
     return [one(S[k], J[k], L[k]) for k in range(S.shape[0])]
 
 
+def histogram_edges(lo, hi, bins):
+    """[m x (bins + 1)]: the edges e_0 = lo, e_k = lo + w·k, e_bins = hi, w = (hi − lo) / bins, of the contract (tests/ref/hist_ref.c)."""
+    lo = np.atleast_1d(np.asarray(lo, dtype=np.float64))
+    hi = np.atleast_1d(np.asarray(hi, dtype=np.float64))
+    w = (hi - lo) / float(bins)
+    E = lo[:, None] + w[:, None] * np.arange(bins + 1, dtype=np.float64)[None]
+    E[:, 0], E[:, bins] = lo, hi
+    return E
+
+
+def _hist_row(a, v, tau, E):
+    """(H [B + 2], Z) of the pieces (a, v, tau) [n] of one coordinate, in their order; E [B + 1] its edges.  The contract's piece: tau <= 0
+    adds nothing; at rest (v == 0 or a + v·tau == a) tau goes to the slot of a; otherwise every bin gets (min(xh, e_k+1) − max(xl, e_k))·r
+    where that is positive, r = tau / (xh − xl).  Sums run sequentially over the pieces."""
+    B = len(E) - 1
+    keep = tau > 0.0
+    a, v, tau = a[keep], v[keep], tau[keep]
+    b = a + v * tau
+    rest = (v == 0.0) | (b == a)
+    Ex = np.concatenate([[-np.inf], E, [np.inf]])
+    H = np.zeros(B + 2)
+    for s in range(0, len(a), 4096):  # (pieces x bins at a time)
+        sl = slice(s, s + 4096)
+        xl, xh = np.minimum(a[sl], b[sl]), np.maximum(a[sl], b[sl])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            r = tau[sl] / (xh - xl)
+            o = np.minimum(xh[:, None], Ex[None, 1:]) - np.maximum(xl[:, None], Ex[None, :-1])
+            C = np.where(o > 0.0, o * r[:, None], 0.0)
+        at = np.searchsorted(E, a[sl], side="right")  # slot of a: 0 below lo, B + 1 at or above hi (−0.0 compares as 0)
+        C[rest[sl]] = 0.0
+        C[np.flatnonzero(rest[sl]), at[rest[sl]]] = tau[sl][rest[sl]]
+        H = np.cumsum(np.vstack([H[None], C]), axis=0)[-1]
+    return H, _seq_sum(tau[v == 0.0])
+
+
+def _hist_fact(tr, coords, E):
+    ev = tr.events
+    order, ptr = _groups(tr)
+    T_last = float(ev["t"][-1]) if len(ev) else float(tr.t0)
+    H, Z = np.empty((len(coords), E.shape[1] + 1)), np.empty(len(coords))
+    for s, j in enumerate(coords):
+        own = order[ptr[j]:ptr[j + 1]]
+        tc = np.concatenate([[tr.t0], ev["t"][own]])
+        xc = np.concatenate([[tr.x0[j]], ev["x"][own]])
+        thc = np.concatenate([[tr.θ0[j]], ev["theta"][own]])
+        t1 = np.concatenate([ev["t"][own], [T_last]])  # (the last piece: closed at T_last)
+        H[s], Z[s] = _hist_row(xc, thc, t1 - tc, E[s])
+    return H, Z, T_last
+
+
+def _hist_pdmp(tr, coords, E):
+    d = len(tr.x0)
+    t = np.asarray(tr.t, dtype=np.float64).reshape(-1)
+    m = len(t)
+    T_last = float(t[-1]) if m else float(tr.t0)
+    tc = np.concatenate([[tr.t0], t[:-1]])[:m]
+    Xc = np.vstack([np.asarray(tr.x0, dtype=np.float64)[None], np.asarray(tr.x, dtype=np.float64).reshape(-1, d)[:-1]])[:m]
+    Vc = np.vstack([np.asarray(tr.θ0, dtype=np.float64)[None], np.asarray(tr.θ, dtype=np.float64).reshape(-1, d)[:-1]])[:m]
+    if tr.f is not None:  # a coordinate that is not free keeps x
+        f0 = np.ones(d, dtype=bool) if tr.f0 is None else np.asarray(tr.f0, dtype=bool)
+        Fm = np.vstack([f0[None], np.asarray(tr.f, dtype=bool).reshape(-1, d)[:-1]])[:m]
+        Vc = np.where(Fm, Vc, 0.0)
+    H, Z = np.empty((len(coords), E.shape[1] + 1)), np.empty(len(coords))
+    for s, j in enumerate(coords):
+        H[s], Z[s] = _hist_row(Xc[:, j], Vc[:, j], t - tc, E[s])
+    return H, Z, T_last
+
+
+def marginal_histogram(tr, coords, lo, hi, bins):
+    """(H [m x (bins + 2)], Z [m], T_last): the exact time each listed coordinate of the path spends in each of `bins` bins of its own range
+    [lo, hi) (scalars broadcast; coords None: all), with slot 0 the time below lo and slot bins + 1 the time at or above hi; Z the time it
+    rested (velocity 0) -- the host mirror of the device's histogram consumers (Ensemble.consume_hist / bps_consume_hist), the contract of
+    tests/ref/hist_ref.c in numpy (DESIGN.md "Marginal histograms").  A FactTrace (time-ordered: no refresh clock): a coordinate moves on a
+    line between ITS events, the last piece is closed at the trace's last event time T_last; a PDMPTrace: every coordinate moves on a line
+    between consecutive events, frozen coordinates of a sticky trace stay where they are, nothing behind the last event.  Σ_k H[s, k] =
+    T_last − t0 to rounding.  Boomerang flows: TypeError (an arc is not a line)."""
+    if isinstance(tr.F, (Boomerang, FactBoomerang)):
+        raise TypeError("marginal_histogram: on a Boomerang flow a coordinate moves on an arc between two events, not on a line")
+    d = len(tr.x0)
+    coords = np.arange(d, dtype=np.int64) if coords is None else np.ascontiguousarray(coords, dtype=np.int64).reshape(-1)
+    bins = int(bins)
+    if coords.size < 1 or coords.min() < 0 or coords.max() >= d or len(np.unique(coords)) != coords.size:
+        raise ValueError("marginal_histogram: coords lists at least one coordinate of [0, %d), each once" % d)
+    if not 1 <= bins <= 4096:
+        raise ValueError("marginal_histogram: bins is in 1..4096")
+    lo = np.broadcast_to(np.asarray(lo, dtype=np.float64), coords.shape)
+    hi = np.broadcast_to(np.asarray(hi, dtype=np.float64), coords.shape)
+    if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi)) and np.all(lo < hi)):
+        raise ValueError("marginal_histogram: the ranges are finite with lo < hi")
+    E = histogram_edges(lo, hi, bins)
+    if isinstance(tr, PDMPTrace):
+        return _hist_pdmp(tr, coords, E)
+    return _hist_fact(tr, coords, E)
+
+
+def histogram_quantiles(H, lo, hi, q):
+    """Quantiles of marginal histograms: H [.. x m x (B + 2)] rows as marginal_histogram / Ensemble.consume_histogram return them (per chain or
+    pooled), lo / hi [m] or scalars, q a probability or a list of them.  Returns [.. x m x len(q)] (the last axis dropped for a scalar q): the
+    piecewise-linear CDF of the bins -- the mass of a bin spread evenly over it, the outer slots counted but not resolved -- inverted at
+    q·Σ_k H[k].  nan where the requested mass lies in an outer slot (below lo or at or above hi: widen the range), or in a row without mass."""
+    H = np.asarray(H, dtype=np.float64)
+    B = H.shape[-1] - 2
+    scalar = np.ndim(q) == 0
+    qs = np.atleast_1d(np.asarray(q, dtype=np.float64))
+    rows = H.reshape(-1, B + 2)
+    m = H.shape[-2] if H.ndim > 1 else 1
+    E = histogram_edges(np.broadcast_to(np.asarray(lo, dtype=np.float64), (m,)), np.broadcast_to(np.asarray(hi, dtype=np.float64), (m,)), B)
+    out = np.full((rows.shape[0], qs.size), np.nan)
+    for r, row in enumerate(rows):
+        e = E[r % m]
+        cdf = np.concatenate([[0.0], np.cumsum(row)])  # cdf[k + 1]: the mass below e_k, k = 0 .. B; cdf[B + 2]: all of it
+        total = cdf[-1]
+        if not total > 0.0:
+            continue
+        inner = cdf[1:B + 2]  # the CDF at the edges e_0 .. e_B
+        if not inner[-1] > inner[0]:
+            continue
+        for c, p in enumerate(qs):
+            mass = p * total
+            if inner[0] <= mass <= inner[-1]:  # the smallest x with CDF(x) >= mass: in the bin k − 1 with inner[k − 1] < mass <= inner[k]
+                k = int(np.searchsorted(inner, mass, side="left"))
+                out[r, c] = e[0] if k == 0 else e[k - 1] + (e[k] - e[k - 1]) * ((mass - inner[k - 1]) / (inner[k] - inner[k - 1]))
+    out = out.reshape(H.shape[:-1] + (qs.size,))
+    return out[..., 0] if scalar else out
+
+
 def faber_schauder_path(ξ, s, L, T):
     """dotψ(ξ, s, L, T) of research/diffusion_bridge/faberschauder.jl:16-24, vectorised: the bridge X_s of the Faber-Schauder coefficients ξ
     ([d] or [n x d], d = (2 << L) + 1, e.g. the rows of discretize(Ξ, dt)) at the times s (scalar or [m], 0 <= s < T).  Returns [m], or
