@@ -594,6 +594,21 @@ pdmp_status pdmp_ensemble_subtrace_copy(pdmp_ensemble* ens, int64_t chain, const
 pdmp_status pdmp_ensemble_barrier_consume_begin(pdmp_ensemble* ens, double grid_dt, int64_t grid_points);
 pdmp_status pdmp_ensemble_barrier_consume_occupation(pdmp_ensemble* ens, int64_t chain_first, int64_t n, double* z_lo, double* z_hi,
                                                      uint64_t* n_lo, uint64_t* n_hi, double* T_last);
+/* The same consumers for the flows with a refresh clock: a ZigZag with λref > 0 and a FactBoomerang (whose refresh clock is mandatory), whatever
+ * kernel samples them.  A refresh records the refreshed coordinate at its own, stale clock (src/sfact.jl:84-85,143), so these traces are sorted
+ * within a coordinate only; the reference's consumers take them in trace order (src/trace.jl:106-125,182-226), and so does this form:
+ *   refresh_consume_begin(grid_dt, grid_points)  call order, argument checks and allocation of consume_begin.  PDMP_ERR_INVALID for a ZigZag
+ *       without refresh clock (pdmp_ensemble_consume_begin serves it), a BPS, sticky or barrier ensemble, trace_capacity = 0, a call before
+ *       set_state or after the first run, grid_points < 0 or grid_points > 0 with grid_dt <= 0.  Afterwards consume, consume_mean,
+ *       consume_discretized, consume_cummean(_copy), subtrace_copy and pdmp_debug_trace_append serve the ensemble unchanged; consume_async,
+ *       consume_condition, consume_pairs, consume_hist and consume_inclusion return PDMP_ERR_UNSUPPORTED (their cursors walk a sorted trace).
+ *   Row k (time g = t0 + k·grid_dt) shows the LEADING events of the trace applied, up to but not including the first one whose time exceeds g:
+ *       a stale event behind that one is not applied to row k although its time is <= g; it is applied to the next row.  Per coordinate the row
+ *       is x + θ·τ, τ = g − (the coordinate's cursor time); a FactBoomerang: (x − μ)·c + θ·s + μ, (s, c) = pdmp_sincos(τ) of pdmp_detmath.h.  A row
+ *       exists while g is below the running maximum of the event times: *npoints counts those (at least 1, NOT clamped to grid_points).
+ *   T_last of consume_mean -- the reference's scale 1/(2T) -- is the time of the last consumed event in trace order, which need not be the maximum.
+ * tests/ref/refresh_trace_ref.c states this sequentially and the device agrees with it bit for bit. */
+pdmp_status pdmp_ensemble_refresh_consume_begin(pdmp_ensemble* ens, double grid_dt, int64_t grid_points);
 
 /* ------------------------------------------------------------------ trace consumers of the Bouncy Particle family (PDMPTrace)
  *

@@ -233,6 +233,7 @@ class Ensemble {
     // the device trace consumers of a barrier ensemble (stickyzz): after set_state and before the first run; then pdmp_ensemble_consume after
     // every slice.  occupation: [n x d] each, any output may be nullptr
     void barrier_consume_begin(double grid_dt = 0.0, int64_t grid_points = 0) { check(pdmp_ensemble_barrier_consume_begin(h_, grid_dt, grid_points)); }
+    void refresh_consume_begin(double grid_dt = 0.0, int64_t grid_points = 0) { check(pdmp_ensemble_refresh_consume_begin(h_, grid_dt, grid_points)); }
     void barrier_consume_occupation(int64_t chain_first, int64_t n, std::vector<double>* frozen_lo, std::vector<double>* frozen_hi,
                                     std::vector<uint64_t>* hits_lo, std::vector<uint64_t>* hits_hi, std::vector<double>* T_last = nullptr) const {
         const size_t nd = (size_t)(n * d_);

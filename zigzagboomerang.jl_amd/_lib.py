@@ -52,7 +52,7 @@ EXPORTED_SYMBOLS = [
     "pdmp_ensemble_ess_begin", "pdmp_ensemble_ess_batch", "pdmp_ensemble_ess_end", "pdmp_ensemble_set_gradient_tracking",
     "pdmp_ensemble_path_integrals", "pdmp_ensemble_set_path_integrals", "pdmp_ensemble_set_neighbourhood", "pdmp_ensemble_info",
     "pdmp_ensemble_consume_begin", "pdmp_ensemble_consume", "pdmp_ensemble_consume_async", "pdmp_ensemble_last_consume_ms", "pdmp_ensemble_consume_mean", "pdmp_ensemble_consume_inclusion", "pdmp_ensemble_consume_discretized", "pdmp_ensemble_consume_cummean", "pdmp_ensemble_consume_cummean_copy", "pdmp_ensemble_subtrace_copy", "pdmp_1d_run",
-    "pdmp_ensemble_barrier_consume_begin", "pdmp_ensemble_barrier_consume_occupation",
+    "pdmp_ensemble_barrier_consume_begin", "pdmp_ensemble_barrier_consume_occupation", "pdmp_ensemble_refresh_consume_begin",
     "pdmp_ensemble_bps_consume_begin", "pdmp_ensemble_bps_consume", "pdmp_ensemble_bps_consume_mean", "pdmp_ensemble_bps_consume_inclusion",
     "pdmp_ensemble_bps_consume_discretized", "pdmp_ensemble_bps_consume_cummean", "pdmp_ensemble_bps_consume_cummean_copy",
     "pdmp_ensemble_consume_condition", "pdmp_ensemble_consume_conditioned", "pdmp_ensemble_bps_consume_condition", "pdmp_ensemble_bps_consume_conditioned",
@@ -147,6 +147,7 @@ def load():
     L.pdmp_ensemble_subtrace_copy.argtypes = [vp, i64, vp, i64, vp, i64, vp]
     L.pdmp_ensemble_consume_discretized.argtypes = [vp, i64, i64, i64, vp, C.POINTER(i64), C.POINTER(vp)]
     L.pdmp_ensemble_barrier_consume_begin.argtypes = [vp, f64, i64]
+    L.pdmp_ensemble_refresh_consume_begin.argtypes = [vp, f64, i64]
     L.pdmp_ensemble_barrier_consume_occupation.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp]
     L.pdmp_ensemble_bps_consume_begin.argtypes = [vp, f64, i64]
     L.pdmp_ensemble_bps_consume.argtypes = [vp]

@@ -284,20 +284,27 @@ pdmp_status pdmp_ensemble_ess_end(pdmp_ensemble* e, double* sum_y, double* sum_y
     return PDMP_OK;
 }
 
-// consume_begin and barrier_consume_begin: one call order, one set of checks, one allocation; `barrier` adds the occupation state behind the cursors
-static pdmp_status consume_begin_impl(pdmp_ensemble* e, double grid_dt, int64_t grid_points, bool barrier) {
+// consume_begin, barrier_consume_begin and refresh_consume_begin: one call order, one set of checks, one allocation; `barrier` adds the occupation
+// state behind the cursors, `refresh` selects the unordered walk (a trace sorted within a coordinate only: DESIGN.md §20)
+static pdmp_status consume_begin_impl(pdmp_ensemble* e, double grid_dt, int64_t grid_points, bool barrier, bool refresh = false) {
     if (!e->has_state || e->ran) return fail(PDMP_ERR_INVALID, "consume_begin follows set_state and precedes the first run (it snapshots x0, θ0)");
+    if (refresh && (e->cfg.sampler == PDMP_SAMPLER_BARRIER_ZIGZAG || e->cfg.sampler == PDMP_SAMPLER_STICKY_ZIGZAG))
+        return fail(PDMP_ERR_INVALID, "refresh_consume_begin: the ensemble is not a ZigZag with a refresh clock or a FactBoomerang (a barrier ensemble: "
+                                      "pdmp_ensemble_barrier_consume_begin; a sticky one: pdmp_ensemble_consume_begin)");
     if (!barrier && e->cfg.sampler == PDMP_SAMPLER_BARRIER_ZIGZAG)
         return fail(PDMP_ERR_UNSUPPORTED, "the device consumers' time away from 0 has no meaning between barriers at other levels: "
                                           "pdmp_ensemble_barrier_consume_begin serves a barrier ensemble (occupation per barrier instead)");
     if (e->cfg.trace_capacity <= 0) return fail(PDMP_ERR_INVALID, "ensemble was created with trace_capacity = 0");
-    if (e->flow_kind != 0 || e->lambda_ref > 0)
+    if (refresh && e->flow_kind == 0 && !(e->lambda_ref > 0))
+        return fail(PDMP_ERR_INVALID, "refresh_consume_begin: a ZigZag without refresh clock has a time-ordered trace: pdmp_ensemble_consume_begin serves it");
+    if (!refresh && (e->flow_kind != 0 || e->lambda_ref > 0))
         return fail(PDMP_ERR_UNSUPPORTED, "the device consumers take time-ordered traces of piecewise-linear paths: ZigZag without refresh clock");
     if (grid_points < 0 || (grid_points > 0 && !(grid_dt > 0))) return fail(PDMP_ERR_INVALID, "grid_dt must be positive");
     HIP_TRY(hipSetDevice(e->cfg.device));
     const int64_t d = e->cfg.d, n = e->cfg.nchains;
     e->cons_z = e->cfg.sampler == PDMP_SAMPLER_STICKY_ZIGZAG;  // (the time away from 0, inclusion_prob: a sum of its own where coordinates can freeze)
     e->cons_occ = barrier;
+    e->cons_unordered = refresh;
     PDMP_TRY(e->d_ccur.alloc((size_t)(n * d) * (pdmp::consume_cursor_bytes(e->cons_z) + (barrier ? pdmp::consume_occ_bytes() : 0))));
     PDMP_TRY(e->d_cmeta.alloc((size_t)n * pdmp::consume_meta_bytes()));
     e->d_cgrid.release();
@@ -342,6 +349,20 @@ pdmp_status pdmp_ensemble_barrier_consume_begin(pdmp_ensemble* e, double grid_dt
     return consume_begin_impl(e, grid_dt, grid_points, true);
 }
 
+// The synchronous consumers of a trace that is sorted within a coordinate only: a ZigZag with a refresh clock (λref > 0) or a FactBoomerang, whatever
+// kernel samples it.  consume_begin itself keeps refusing these flows.
+pdmp_status pdmp_ensemble_refresh_consume_begin(pdmp_ensemble* e, double grid_dt, int64_t grid_points) {
+    if (!e) return fail(PDMP_ERR_INVALID, "null argument");
+    NEED_FACTORISED(e);
+    return consume_begin_impl(e, grid_dt, grid_points, false, true);
+}
+
+// what the consumers with a time-ordered cursor answer after refresh_consume_begin
+static pdmp_status refuse_unordered(const char* who) {
+    return fail(PDMP_ERR_UNSUPPORTED, "%s: after pdmp_ensemble_refresh_consume_begin the trace is sorted within a coordinate only (a refresh is recorded at "
+                                      "the coordinate's own, stale clock); this consumer walks a time-ordered trace", who);
+}
+
 // time frozen at the lower / upper barrier [n x d] and hits of each [n x d] of chains [chain_first, chain_first + n), T_last [n]; any output may be NULL
 pdmp_status pdmp_ensemble_barrier_consume_occupation(pdmp_ensemble* e, int64_t chain_first, int64_t n, double* z_lo, double* z_hi, uint64_t* n_lo,
                                                      uint64_t* n_hi, double* T_last) {
@@ -382,8 +403,13 @@ pdmp_status pdmp_ensemble_consume(pdmp_ensemble* e) {
         LAUNCH_TRY("consume_pairs", pdmp::launch_pair_events(e->d_ev.p, e->cfg.trace_capacity, e->d_hdr.p, e->cfg.d, e->cfg.nchains, pair_args(e), e->stream));
     if (e->hs_on)  // (cursors of its own too)
         LAUNCH_TRY("consume_hist", pdmp::launch_hist_events(e->d_ev.p, e->cfg.trace_capacity, e->d_hdr.p, e->cfg.d, e->cfg.nchains, hist_args(e), e->stream));
-    LAUNCH_TRY("consume", pdmp::launch_consume_events(e->d_ev.p, e->cfg.trace_capacity, e->d_hdr.p, nullptr, e->cfg.d, e->cfg.nchains, e->d_ccur.p, e->cons_z, e->d_cmeta.p,
-                                         e->d_cgrid.p, e->cons_K, e->t0_state, e->cons_dt, e->stream, e->cons_cummean ? e->d_ccm.p : nullptr, e->cons_occ));
+    if (e->cons_unordered)
+        LAUNCH_TRY("consume", pdmp::launch_consume_events_unordered(e->d_ev.p, e->cfg.trace_capacity, e->d_hdr.p, e->cfg.d, e->cfg.nchains, e->d_ccur.p, e->d_cmeta.p,
+                                             e->d_cgrid.p, e->cons_K, e->t0_state, e->cons_dt, e->stream, e->cons_cummean ? e->d_ccm.p : nullptr,
+                                             e->flow_kind == 1 ? e->d_mu.p : nullptr));
+    else
+        LAUNCH_TRY("consume", pdmp::launch_consume_events(e->d_ev.p, e->cfg.trace_capacity, e->d_hdr.p, nullptr, e->cfg.d, e->cfg.nchains, e->d_ccur.p, e->cons_z, e->d_cmeta.p,
+                                             e->d_cgrid.p, e->cons_K, e->t0_state, e->cons_dt, e->stream, e->cons_cummean ? e->d_ccm.p : nullptr, e->cons_occ));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return PDMP_OK;
 }
@@ -460,6 +486,7 @@ pdmp_status pdmp_ensemble_subtrace_copy(pdmp_ensemble* e, int64_t chain, const i
 pdmp_status pdmp_ensemble_consume_async(pdmp_ensemble* e, void* stream) {
     if (!e) return fail(PDMP_ERR_INVALID, "null argument");
     if (!e->consuming || !e->has_state) return fail(PDMP_ERR_INVALID, "pdmp_ensemble_consume_begin first");
+    if (e->cons_unordered) return refuse_unordered("consume_async");
     if (e->cons_occ)
         return fail(PDMP_ERR_UNSUPPORTED, "consume_async: a barrier ensemble (pdmp_ensemble_barrier_consume_begin) is served by the synchronous consumer, "
                                           "pdmp_ensemble_consume");
@@ -540,6 +567,7 @@ pdmp_status pdmp_ensemble_consume_inclusion(pdmp_ensemble* e, int64_t chain_firs
     if (e && e->consuming && e->cons_occ)
         return fail(PDMP_ERR_UNSUPPORTED, "consume_inclusion: the time away from 0 has no meaning between barriers at other levels: "
                                           "pdmp_ensemble_barrier_consume_occupation returns the time frozen at each barrier (1 − z/T)");
+    if (e && e->consuming && e->cons_unordered) return refuse_unordered("consume_inclusion");
     return consume_reduce(e, chain_first, n, prob, T_last, "consume_inclusion", [&](double* bm, double* bt) {
         return pdmp::launch_consume_inclusion(e->cfg.d, e->cfg.nchains, e->cons_z, e->t0_state, chain_first, n, e->d_ccur.p, e->d_cmeta.p, bm, bt, e->stream);
     });
@@ -554,17 +582,20 @@ pdmp_status pdmp_ensemble_consume_discretized(pdmp_ensemble* e, int64_t chain, i
     HIP_TRY(hipSetDevice(e->cfg.device));
     HIP_TRY(device_sync(e));  // (asynchronous consumers run on a second stream)
     const int64_t d = e->cfg.d;
-    // the points after every coordinate's last event, up to the chain's last event time (idempotent)
-    LAUNCH_TRY("consume_flush", pdmp::launch_consume_flush(d, e->cfg.nchains, e->d_ccur.p, e->d_cmeta.p, e->d_cgrid.p, e->cons_K, e->t0_state, e->cons_dt, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
+    // the points after every coordinate's last event, up to the chain's last event time (idempotent); not for an unordered trace, whose rows are
+    // exactly the ones the walk wrote (the cursors behind a stale event are not the state the reference shows at an earlier row)
+    if (!e->cons_unordered) {
+        LAUNCH_TRY("consume_flush", pdmp::launch_consume_flush(d, e->cfg.nchains, e->d_ccur.p, e->d_cmeta.p, e->d_cgrid.p, e->cons_K, e->t0_state, e->cons_dt, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+    }
     if (out && k_count)
         HIP_TRY(hipMemcpy(out, e->d_cgrid.p + (chain * e->cons_K + k_first) * d, (size_t)(k_count * d) * sizeof(double), hipMemcpyDeviceToHost));
     if (npoints) {
         // collect(discretize(Ξ, dt)) emits a grid time while it lies before the last event (src/trace.jl:111-113); at least t0 itself
         std::vector<unsigned char> mh(pdmp::consume_meta_bytes());
         HIP_TRY(hipMemcpy(mh.data(), e->d_cmeta.p + (size_t)chain * pdmp::consume_meta_bytes(), mh.size(), hipMemcpyDeviceToHost));
-        double tl;
-        memcpy(&tl, mh.data() + 8, sizeof tl);
+        double tl;  // { consumed, t_last, row_next, t_max }: an unordered trace's grid extends to the running maximum of its event times
+        memcpy(&tl, mh.data() + (e->cons_unordered ? 24 : 8), sizeof tl);
         // NOT clamped to the grid: a value above grid_points tells the caller that the grid was too short for the run (rows beyond it do not exist)
         int64_t np = (int64_t)floor((tl - e->t0_state) / e->cons_dt);
         np = np > 1 ? np - 1 : 0;
@@ -582,6 +613,7 @@ pdmp_status pdmp_ensemble_consume_condition(pdmp_ensemble* e, const double* p, c
     if (e->flow_kind != 0)
         return fail(PDMP_ERR_UNSUPPORTED, "consume_condition: the hitting time of a hyperplane has no method for the Boomerang flows (src/condition.jl:18)");
     if (!e->consuming || !e->has_state) return fail(PDMP_ERR_INVALID, "consume_condition: pdmp_ensemble_consume_begin first");
+    if (e->cons_unordered) return refuse_unordered("consume_condition");
     if (e->cons_started) return fail(PDMP_ERR_INVALID, "consume_condition precedes the first consume (its cursors start from t0, x0, θ0)");
     const int64_t d = e->cfg.d, nch = e->cfg.nchains;
     std::vector<int32_t> S;
@@ -644,6 +676,7 @@ pdmp_status pdmp_ensemble_consume_pairs(pdmp_ensemble* e, int64_t npairs, const 
     if (!e) return fail(PDMP_ERR_INVALID, "null argument");
     NEED_FACTORISED(e);
     if (!e->consuming || !e->has_state) return fail(PDMP_ERR_INVALID, "consume_pairs: pdmp_ensemble_consume_begin first");
+    if (e->cons_unordered) return refuse_unordered("consume_pairs");
     if (e->cons_started) return fail(PDMP_ERR_INVALID, "consume_pairs precedes the first consume (its cursors start from t0, x0, θ0)");
     const int64_t d = e->cfg.d, nch = e->cfg.nchains;
     std::vector<int32_t> vi, vj;
@@ -709,6 +742,7 @@ pdmp_status pdmp_ensemble_consume_hist(pdmp_ensemble* e, int64_t m, const int64_
     if (!e) return fail(PDMP_ERR_INVALID, "null argument");
     NEED_FACTORISED(e);
     if (!e->consuming || !e->has_state) return fail(PDMP_ERR_INVALID, "consume_hist: pdmp_ensemble_consume_begin first");
+    if (e->cons_unordered) return refuse_unordered("consume_hist");
     if (e->cons_started) return fail(PDMP_ERR_INVALID, "consume_hist precedes the first consume (its cursors start from t0, x0, θ0)");
     const int64_t d = e->cfg.d, nch = e->cfg.nchains;
     std::vector<int32_t> vc;

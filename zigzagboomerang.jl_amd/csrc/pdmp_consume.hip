@@ -45,7 +45,9 @@ int launch_zz_path_integrals(const ZzRec* rec, int64_t rec_stride, int64_t d, in
 // workgroup for all d coordinates at once (coalesced: cursors read and positions written thread by thread), after the events with t <= g and
 // as soon as a later event shows that the run has passed g (:111: a point is emitted while it lies before the last event) -- round 5; before,
 // every event scattered the points of its own coordinate, 2.5 eight-byte stores per event at C3's rates, which cost more than the events.
-// Sorted traces only (ZigZag without refresh clock; the sticky sampler's traces included).
+// That walk takes SORTED traces (ZigZag without refresh clock; the sticky sampler's traces included).  A refresh clock records the refreshed
+// coordinate at its own, stale clock (src/sfact.jl:84-85), so the traces of a ZigZag with λref > 0 and of a FactBoomerang are sorted within a
+// coordinate only: the UNORDERED form of the walk (UNORD below) takes them in trace order, as the reference's iterator does.
 struct ConsumeCursor {
     double t, x, th, y;  // clock, position, velocity after the coordinate's last consumed event; Σ (x_prev + x_k)(t_k − t_prev)
 };
@@ -56,7 +58,7 @@ struct ConsumeMeta {
     uint64_t consumed;  // events of this chain consumed so far (global event index)
     double t_last;      // time of the last of them (t0 before the first)
     uint64_t row_next;  // the first grid row not written yet by the streaming consumer
-    uint64_t pad;
+    double t_max;       // the running maximum of their times (t0 before the first): bounds the grid of an unordered trace; the sorted walk carries it along unread
 };
 // (barrier ensembles keep the OCCUPATION of every coordinate instead, in an array of its own behind the cursors: the time it sat frozen on its lower
 // and on its upper barrier, how often it hit each, and the side it is -- or was last -- frozen on; DESIGN.md "Barrier occupation" has the definition)
@@ -75,7 +77,7 @@ __global__ __launch_bounds__(256) void consume_init_kernel(const ZzRec* rec0, in
         m.consumed = 0;
         m.t_last = t0;
         m.row_next = 0;
-        m.pad = 0;
+        m.t_max = t0;
         meta[k] = m;
     }
     if (k >= nchains * d) return;
@@ -110,7 +112,17 @@ __device__ __forceinline__ void consume_emit(double* grid_chain, int64_t d, int6
 // event loop no longer writes while the headers already count the next slice; nullptr: the headers themselves)
 constexpr int CONSUME_HASH = 4096;  // slots of the per-chunk table that finds two events of one coordinate
 // (OCC: the barrier ensembles' form -- zs0 is their BarrierOcc array, updated beside the cursor; every other ensemble runs OCC = false)
-template <bool OCC>
+// UNORD: 0 the sorted walk; 1 / 2 the walk of a trace that is sorted within a coordinate only, with the rows of the linear flow / of the
+// FactBoomerang's rotation about mu (pdmp_ensemble_refresh_consume_begin).  It differs from the sorted walk in four places, each marked UNORD:
+//   split   the first slot of [pos, ntrace) whose time exceeds g is found by a forward scan, 256 slots per step, the lowest hit taken (LDS minimum;
+//           the step ends on the count barrier, so every thread leaves the scan at the same step).  The scan starts at pos and pos only advances:
+//           O(events + rows) per slice.  Events behind the split are not applied to row g even where their time is <= g -- the reference's iterator
+//           stops at the first later event (src/trace.jl:111-113).
+//   clocks  t_last is the time of the last consumed event in trace order (T of mean); t_max the running maximum (the grid's extent, npoints)
+//   rows    the FactBoomerang rotates: (x − μ)·c + θ·s + μ, (s, c) = pdmp_sincos(g − t_cursor), plain doubles
+//   flush   none: consume_flush_kernel would re-emit rows from the current cursors, which after a stale event are not the state the reference shows
+//           there; every row with g < t_max has been written by the walk when the event that exceeds it is consumed
+template <bool OCC, int UNORD = 0>
 __global__ __launch_bounds__(256) void consume_events_kernel(const pdmp_event* ev0, int64_t cap, const DevChain* hdr, const uint64_t* __restrict__ snap,
                                                              int64_t d, ConsumeCursor* cur0, double* zs0, ConsumeMeta* meta, double* grid0, int64_t K,
                                                              double t0, double dt, double2* cm0) {
@@ -127,16 +139,29 @@ __global__ __launch_bounds__(256) void consume_events_kernel(const pdmp_event* e
     if (pos >= ntrace) return;
     const pdmp_event* ev = ev0 + chain * cap;
     ConsumeCursor* cur = cur0 + chain * d;
-    double* zs = (!OCC && zs0) ? zs0 + chain * d : nullptr;
+    double* zs = (!OCC && UNORD == 0 && zs0) ? zs0 + chain * d : nullptr;
+    const double* const mu = zs0;  // (UNORD = 2: the slot of the z sums carries the flow's μ [d], read only -- an unordered walk keeps no z sums, and the
+                                   // sorted instantiations keep their signature and with it every instruction)
     BarrierOcc* occ = OCC ? reinterpret_cast<BarrierOcc*>(zs0) + chain * d : nullptr;
     double* grid = grid0 ? grid0 + chain * K * d : nullptr;
     uint64_t row = m.row_next;
+    double tmx = m.t_max;  // (UNORD: this thread's share of the running maximum, reduced once behind the walk)
     for (;;) {
         // the events up to the next grid time g (t <= g: an event AT g belongs before the row), then the row -- if the slice goes on beyond g
         const bool want_row = grid && (int64_t)row < K;
         const double g = t0 + dt * (double)row;
         uint64_t split = ntrace;
-        if (want_row) {
+        if (UNORD != 0 && want_row) {  // first slot in [pos, ntrace) whose time exceeds g, by a forward scan from pos
+            if (tid == 0) s_split = ntrace;
+            __syncthreads();
+            for (uint64_t sb = pos;; sb += 256) {
+                const uint64_t e = sb + (uint64_t)tid;
+                const bool hit = e < ntrace && ev[e].t > g;
+                if (hit) atomicMin(reinterpret_cast<unsigned long long*>(&s_split), (unsigned long long)e);
+                if (__syncthreads_count(hit ? 1 : 0) != 0 || sb + 256 >= ntrace) break;  // (the same count in every thread)
+            }
+            split = s_split;
+        } else if (want_row) {
             if (tid == 0) {  // first slot in [pos, ntrace) whose time exceeds g (the trace is sorted by time)
                 uint64_t lo = pos, hi = ntrace;
                 while (lo < hi) {
@@ -157,6 +182,9 @@ __global__ __launch_bounds__(256) void consume_events_kernel(const pdmp_event* e
             evt.i = 0;
             evt.x = evt.theta = 0.0;
             if (valid) evt = ev[e];
+            if constexpr (UNORD != 0) {
+                if (valid && evt.t > tmx) tmx = evt.t;
+            }
             // two events of one coordinate in this chunk?  every event writes its thread into a slot of a hash table; an event that does not find
             // itself there after everybody wrote shares the slot with another one (the same coordinate, or -- ~8 times per chunk -- another that
             // hashes alike): those few sort themselves out by the ordered rounds below, everybody else is alone on its coordinate
@@ -218,9 +246,28 @@ __global__ __launch_bounds__(256) void consume_events_kernel(const pdmp_event* e
         double* const grow = grid + row * d;
         for (int64_t i = tid; i < d; i += 256) {
             const ConsumeCursor c = cur[i];
-            grow[i] = c.x + c.th * (g - c.t);
+            if constexpr (UNORD == 2) {
+                double sn, cs;
+                pdmp_sincos(g - c.t, &sn, &cs);
+                const double m_i = mu[i];
+                grow[i] = (c.x - m_i) * cs + c.th * sn + m_i;
+            } else {
+                grow[i] = c.x + c.th * (g - c.t);
+            }
         }
         row += 1;
+    }
+    if constexpr (UNORD != 0) {  // the maximum over the threads' shares: across each wavefront, then over the four
+        __shared__ double s_mx[4];
+        for (int off = 32; off > 0; off >>= 1) {
+            const double o = __shfl_xor(tmx, off, 64);
+            if (o > tmx) tmx = o;
+        }
+        if ((tid & 63) == 0) s_mx[tid >> 6] = tmx;
+        __syncthreads();
+        if (tid == 0)
+            for (int w = 0; w < 4; ++w)
+                if (s_mx[w] > m.t_max) m.t_max = s_mx[w];
     }
     if (tid == 0) {
         m.consumed = nevents;
@@ -295,6 +342,19 @@ int launch_consume_events(const pdmp_event* ev, int64_t cap, const DevChain* hdr
     else
         hipLaunchKernelGGL(consume_events_kernel<false>, dim3((unsigned)nchains), dim3(256), 0, (hipStream_t)stream, ev, cap, hdr, snap, d,
                            static_cast<ConsumeCursor*>(cur), z_of(cur, d, nchains, with_z), static_cast<ConsumeMeta*>(meta), grid, K, t0, dt,
+                           reinterpret_cast<double2*>(cummean_pairs));
+    return (int)hipGetLastError();
+}
+// the unordered walk (a ZigZag with refresh clock: mu = nullptr; a FactBoomerang: its per-coordinate μ); synchronous, no z sums, no occupation
+int launch_consume_events_unordered(const pdmp_event* ev, int64_t cap, const DevChain* hdr, int64_t d, int64_t nchains, void* cur, void* meta, double* grid,
+                                    int64_t K, double t0, double dt, void* stream, double* cummean_pairs, const double* mu) {
+    if (mu)
+        hipLaunchKernelGGL((consume_events_kernel<false, 2>), dim3((unsigned)nchains), dim3(256), 0, (hipStream_t)stream, ev, cap, hdr, nullptr, d,
+                           static_cast<ConsumeCursor*>(cur), const_cast<double*>(mu), static_cast<ConsumeMeta*>(meta), grid, K, t0, dt,
+                           reinterpret_cast<double2*>(cummean_pairs));
+    else
+        hipLaunchKernelGGL((consume_events_kernel<false, 1>), dim3((unsigned)nchains), dim3(256), 0, (hipStream_t)stream, ev, cap, hdr, nullptr, d,
+                           static_cast<ConsumeCursor*>(cur), nullptr, static_cast<ConsumeMeta*>(meta), grid, K, t0, dt,
                            reinterpret_cast<double2*>(cummean_pairs));
     return (int)hipGetLastError();
 }

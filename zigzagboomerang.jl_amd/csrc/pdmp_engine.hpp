@@ -582,6 +582,9 @@ int launch_consume_snapshot(DevChain* hdr, int64_t nchains, uint64_t* snap, void
 int launch_consume_events(const pdmp_event* ev, int64_t cap, const DevChain* hdr, const uint64_t* snap, int64_t d, int64_t nchains, void* cur,
                           bool with_z, void* meta, double* grid, int64_t K, double t0, double dt, void* stream, double* cummean_pairs = nullptr,
                           bool with_occ = false);
+// ... of a trace that is sorted within a coordinate only (refresh clock): mu = the FactBoomerang's per-coordinate μ, nullptr for the linear flow
+int launch_consume_events_unordered(const pdmp_event* ev, int64_t cap, const DevChain* hdr, int64_t d, int64_t nchains, void* cur, void* meta, double* grid,
+                                    int64_t K, double t0, double dt, void* stream, double* cummean_pairs, const double* mu);
 int launch_barrier_occ_init(const double* thf, int64_t d, int64_t nchains, void* cur, void* stream);
 int launch_barrier_occ_read(int64_t d, int64_t nchains, int64_t chain_first, int64_t n, void* cur, const void* meta, double* z_lo, double* z_hi,
                             uint64_t* n_lo, uint64_t* n_hi, double* T_out, void* stream);

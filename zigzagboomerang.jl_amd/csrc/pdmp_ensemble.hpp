@@ -213,6 +213,7 @@ struct pdmp_ensemble {
     bool cons_cummean = false;
     bool consuming = false, cons_z = false;
     bool cons_occ = false;  // pdmp_ensemble_barrier_consume_begin: the occupation state (time frozen / hits per barrier) lies behind the cursors
+    bool cons_unordered = false;  // pdmp_ensemble_refresh_consume_begin: the trace is sorted within a coordinate only (refresh clock); the unordered walk serves it
     double cons_dt = 0.0;
     int64_t cons_K = 0;
     // pdmp_ensemble_consume_condition: the conditional trace's own cursors (t, x, θ) [3 x nchains x d], the list of supp n (cn_idx; cn_loc[] =

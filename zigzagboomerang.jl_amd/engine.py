@@ -464,6 +464,14 @@ class Ensemble:
         _lib.check(self._L.pdmp_ensemble_barrier_consume_begin(self._h, float(dt), int(points)))
         self._grid = (float(dt), int(points))
 
+    def refresh_consume_begin(self, dt=0.0, points=0):
+        """consume_begin for a flow with a refresh clock (a ZigZag with λref > 0, a FactBoomerang): its trace is sorted within a coordinate only, and
+        the consumers take it in trace order like the reference's iterator (trace.discretize / mean / cummean are the host mirrors).  Afterwards
+        consume(), consume_mean(), consume_discretized(), consume_cummean() and subtrace() serve it; consume_async, consume_condition,
+        consume_pairs, consume_hist and consume_inclusion are refused (PDMP_ERR_UNSUPPORTED)."""
+        _lib.check(self._L.pdmp_ensemble_refresh_consume_begin(self._h, float(dt), int(points)))
+        self._grid = (float(dt), int(points))
+
     def barrier_consume_occupation(self, chain_first=0, n=None):
         """(frozen_lo, frozen_hi [n x d] float64, hits_lo, hits_hi [n x d] uint64, T_last [n]): the time each coordinate sat frozen on its lower /
         upper barrier over [t0, T_last] and the hits of each, raw sums (trace.barrier_occupation is the host mirror, bit for bit).  A read

@@ -172,7 +172,10 @@ def spdmp(target, t0, x0, θ0, T, c, *GF, factor=1.8, adapt=False, adaptscale=Fa
     event time and trace.discretize(Ξ, dt) on at most `points` rows (grid_t / grid_x None without points), per chain as in pdmp.  With
     condition=(p, n), hits=K in the dict it also holds hit_t, hit_x, nhits: trace.conditional_trace(Ξ, p, n), at most K rows per chain
     (problems.bridge_point_condition gives the (p, n) of a bridge through a point).
-    consume=dict(cov=P[, center=c]) (any device target with a ZigZag; also on sspdmp and pdmp): the exact pair integrals of the path, kept on the
+    consume=dict(dt=..., points=...) is also admitted where the flow has a refresh clock -- a ZigZag with λref > 0 or a FactBoomerang, on any device
+    target: the unordered device consumers (Ensemble.refresh_consume_begin) then run over every slice and the same dict(mean, T, grid_t, grid_x) is
+    returned; with trace=False the events are consumed without being copied.  cov, hist and condition in the dict raise TypeError on such a flow.
+    consume=dict(cov=P[, center=c]) (any device target with a ZigZag without refresh clock; also on sspdmp and pdmp): the exact pair integrals of the path, kept on the
     device slice by slice -- P a sparse matrix (its structural lower triangle plus the diagonal), "diag" or a (pi, pj) tuple; the element gains
     pairs = (pi, pj), pair_S [npairs] and pair_J [d] per chain, which with T (L = T − t0) is what trace.covariance takes.
     consume=dict(hist=dict(coords=None, lo=..., hi=..., bins=B)) (any device target with a ZigZag; also on sspdmp, pdmp, stickyzz and sspdmp2): the
@@ -514,7 +517,14 @@ def _zigzag(sampler, target, t0, x0, θ0, T, c, F, factor, adapt, seed, device, 
         raise TypeError("the device path supports F::ZigZag and F::FactBoomerang")
     if not isinstance(target, (GaussianTarget, LogisticTarget, DiffusionBridgeTarget)):
         raise TypeError("target must be one of the device-resident families (GaussianTarget, LogisticTarget, DiffusionBridgeTarget)")
-    if consume is not None and barriers is None and not isinstance(target, DiffusionBridgeTarget) and not _admits(consume):
+    # a flow with a refresh clock (a ZigZag with λref > 0, a FactBoomerang) leaves a trace that is sorted within a coordinate only: the unordered
+    # consumers (Ensemble.refresh_consume_begin) serve it, with mean and the grid alone
+    refresh = barriers is None and sticky is None and (isinstance(F, FactBoomerang) or F.λref > 0)
+    if consume is not None and refresh:
+        if not isinstance(consume, dict) or set(consume) & {"cov", "center", "hist", "condition", "hits"}:
+            raise TypeError("consume=dict(dt=..., points=...) on a flow with a refresh clock (a ZigZag with λref > 0, a FactBoomerang): cov, hist and "
+                            "condition walk a time-ordered trace and are not available there")
+    elif consume is not None and barriers is None and not isinstance(target, DiffusionBridgeTarget) and not _admits(consume):
         raise TypeError("consume is a keyword of spdmp with a DiffusionBridgeTarget, or with cov=P or hist=dict(...) (elsewhere the ZigZag's device consumers are "
                         "Ensemble.consume_*)")
     x0 = np.asarray(x0, dtype=np.float64)
@@ -554,7 +564,7 @@ def _zigzag(sampler, target, t0, x0, θ0, T, c, F, factor, adapt, seed, device, 
             ens.set_gradient_tracking(True)
         ens.set_state(t0, X0, TH0, c, seeds)
         if consume is not None:
-            begin = ens.consume_begin if barriers is None else ens.barrier_consume_begin
+            begin = ens.refresh_consume_begin if refresh else ens.consume_begin if barriers is None else ens.barrier_consume_begin
             begin(float(consume.get("dt", 0.0)), int(consume.get("points", 0)))
             if _condition_of(consume) is not None:
                 ens.consume_condition(*_condition_of(consume))

@@ -26,8 +26,8 @@ def _free_flow(tr, j, x, th, tau):
 
 
 def _prev_same_coordinate(tr):
-    """For every event k (in time order): time, position and velocity the coordinate had after ITS previous event (the initial
-    state for its first one)."""
+    """For every event k (in trace order; with a refresh clock the trace is sorted within a coordinate only, which is all this needs): time,
+    position and velocity the coordinate had after ITS previous event (the initial state for its first one)."""
     ev = tr.events
     n = len(ev)
     i = ev["i"].astype(np.int64)
@@ -48,7 +48,8 @@ def _prev_same_coordinate(tr):
 
 
 def _groups(tr):
-    """Events grouped per coordinate: (order, ptr) with order[ptr[j]:ptr[j+1]] the event indices of coordinate j in time order."""
+    """Events grouped per coordinate: (order, ptr) with order[ptr[j]:ptr[j+1]] the event indices of coordinate j in trace order (= its time
+    order, also where a refresh clock leaves the trace as a whole unsorted)."""
     i = tr.events["i"].astype(np.int64)
     order = np.argsort(i, kind="stable")
     ptr = np.zeros(tr.x0.size + 1, dtype=np.int64)
@@ -224,7 +225,10 @@ def cummean(tr):
 
 
 def mean(tr):
-    """mean(Ξ): time average of the piecewise-linear path per coordinate -- src/trace.jl:182-200 (FactTrace), :229-246 (PDMPTrace)."""
+    """mean(Ξ): time average of the piecewise-linear path per coordinate -- src/trace.jl:182-200 (FactTrace), :229-246 (PDMPTrace).  A FactTrace
+    is taken in trace order, so traces with a refresh clock (λref > 0, FactBoomerang) are served as the reference serves them: T is the time of
+    the LAST event, which need not be the largest; the FactBoomerang gets the same trapezoid between recorded positions (:194).  cummean and
+    discretize likewise; Ensemble.refresh_consume_begin opens their device twins."""
     if isinstance(tr, PDMPTrace):
         return _mean_pdmp(tr)
     ev = tr.events
