@@ -188,6 +188,31 @@ pdmp_status pdmp_ensemble_set_target_logistic(pdmp_ensemble* ens, int64_t n, con
 pdmp_status pdmp_ensemble_set_target_diffusion_bridge(pdmp_ensemble* ens, int32_t L, double T, double alpha, double beta, double omega);
 
 /*
+ * Target of the reference's precision case study (casestudies/precision/precision.jl; research/newsticky/precision/precision4.jl with
+ * gamma0 > 0): learning a sparse precision matrix through its Cholesky factor.  N observations Y_k ~ N(0, (L L')^-1) enter through
+ * YY = sum_k Y_k Y_k' ([n x n] row-major, symmetric) and N.  The d = n(n+1)/2 coordinates are the lower triangle of L packed column by column
+ * (0-based): u[i] = L[r, c], i = k0 + (r - c) with k0 = c n - c(c-1)/2; column c occupies [k0, k0 + n - c).
+ *   phi(u)     = 1/2 sum_c L[:,c]' YY L[:,c] - N sum_c log L[c,c] + gamma0/2 (sum_{r>c} L[r,c]^2 + sum_c (L[c,c] - 1)^2)
+ *   dphi/du_i  = sum_{q < n-c} YY[r, c+q] u[k0+q] + (r == c ? -N/u_i + gamma0 (u_i - 1) : gamma0 u_i)
+ * the sum being the 64-lane sum of the products in wave order (lane q holds product q, 0.0 past the column; xor butterfly 1, 2, .., 32) with
+ * the diagonal or prior term added to it.  Runs on zz_precision_run_kernel, bit for bit tests/ref/precision_ref.c: sspdmp (src/ss_fact.jl)
+ * with G1[i] = {i}, G[i] = the column of i, G2[i] empty.
+ * Valid on PDMP_SAMPLER_STICKY_ZIGZAG after set_flow_zigzag, in place of another target (the later target call wins); pdmp_ensemble_set_sticky
+ * (kappa, reversible, strong_upperbounds) as for every sticky ZigZag.
+ * PDMP_ERR_INVALID: d != n(n+1)/2, n < 1, N not finite or <= 0, gamma0 < 0 or not finite, a YY entry that is not finite, YY not symmetric bit
+ * for bit, another sampler, a state that already exists.  PDMP_ERR_UNSUPPORTED: n > 64 (d > 2080).  pdmp_ensemble_set_state then answers
+ * PDMP_ERR_UNSUPPORTED, naming the cause, to a flow matrix that is not diagonal with positive entries, pdmp_ensemble_set_neighbourhood, gradient
+ * tracking, LocalBound, a synthetic state, an x0 whose diagonal coordinates L[c, c] are not all > 0, and a refresh clock (one that arrives with
+ * a flow set again after pdmp_ensemble_set_sticky: that call itself refuses a flow with one).  adaptscale never gets as far:
+ * pdmp_ensemble_set_adaptscale answers PDMP_ERR_UNSUPPORTED on every sticky ensemble.
+ * A freeze popped for a diagonal coordinate ends its chain as PDMP_CHAIN_STALLED before any state changes (the next gradient would be N/0); so
+ * does a thaw that finds no saved speed (a coordinate started at x = 0 with theta = 0).  The trace consumers (pdmp_ensemble_consume_*) serve
+ * these traces; pdmp_ensemble_batch_means, _ess_* and _path_integrals answer PDMP_ERR_UNSUPPORTED (this loop keeps no integral of x dt).
+ * (Added under ABI version 3: nothing that existed changed, a binding that wants it looks the symbol up.)
+ */
+pdmp_status pdmp_ensemble_set_target_precision_cholesky(pdmp_ensemble* ens, int32_t n, const double* YY /* [n x n] */, double N, double gamma0);
+
+/*
  * Initial state (src/sfact.jl:164-190): x0, theta0 are [nchains x d] row-major; c is [d] (copied; with
  * adapt each chain gets its own copy, returned by final_state -- no hidden mutation of caller memory,
  * unlike src/fact_samplers.jl:68); seeds is [nchains].  Computes b[i] = ab(...) and the initial queue
@@ -340,6 +365,11 @@ pdmp_status pdmp_ensemble_set_sticky(pdmp_ensemble* ens, const double* kappa, in
 pdmp_status pdmp_ensemble_set_barriers(pdmp_ensemble* ens, const double* lo, const double* hi, const int32_t* rule_lo, const int32_t* rule_hi,
                                        const double* kappa_lo, const double* kappa_hi, int strong_upperbounds);
 pdmp_status pdmp_ensemble_final_barrier(pdmp_ensemble* ens, int64_t chain_first, int64_t n, uint8_t* frozen, double* theta_saved);
+/* The same for a sticky ZigZag (PDMP_SAMPLER_STICKY_ZIGZAG, src/ss_fact.jl): frozen [n x d] (1 where x[i] == 0 && theta[i] == 0, :108) and
+ * theta_saved [n x d], the ensemble's array of saved speeds: for a frozen coordinate the speed its thaw gives back (never 0).  What the array
+ * holds for a coordinate that is not frozen is the kernel's own business (zz_precision_run_kernel: 0).  Either may be NULL.  LocalBound, whose
+ * renewal flags share the array, is refused on a sticky ensemble.  (Added under ABI version 3.) */
+pdmp_status pdmp_ensemble_final_sticky(pdmp_ensemble* ens, int64_t chain_first, int64_t n, uint8_t* frozen, double* theta_saved);
 
 /* ------------------------------------------------------------------ adaptscale (σ tuning in the refresh branch)
  *

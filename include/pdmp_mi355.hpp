@@ -12,7 +12,7 @@
 //                                                   -> Ξ, t′, (t, x, θ), (acc, num)                 (src/stickyzz.jl:176-218)
 // Same names, argument order, keyword meaning (struct Options), return shape (struct Result) and error behaviour (the
 // reference's `error("Tuning parameter `c` too small.")`, src/sfact.jl:124, becomes std::runtime_error with that text).
-// Differences forced by the C ABI: `∇ϕ, args...` is an enumerated target (GaussianTarget, LogisticTarget, DiffusionBridge); coordinates are
+// Differences forced by the C ABI: `∇ϕ, args...` is an enumerated target (GaussianTarget, LogisticTarget, DiffusionBridge, PrecisionCholesky); coordinates are
 // 0-based; one call runs ONE chain (pass nchains > 1 through pdmp::Ensemble directly for ensembles).
 // Header-only; link with -lpdmp_mi355.  There is no CPU fallback: without a gfx950 device every call throws.
 #ifndef PDMP_MI355_HPP
@@ -23,6 +23,7 @@
 #include <cstdint>
 #include <limits>
 #include <stdexcept>
+#include <type_traits>
 #include <string>
 #include <utility>
 #include <vector>
@@ -119,6 +120,23 @@ struct DiffusionBridge {
             r += xi[(size_t)j] * ((sT * 0.5 - std::fabs(std::fmod(s * p2, T) / sT - sT * 0.5)) / std::sqrt(p2));
         }
         return r;
+    }
+};
+// ∇ϕ(u, i, YY, (𝕀, 𝕁), N) of casestudies/precision/precision.jl:42-53 (gamma0 = 0) and research/newsticky/precision/precision4.jl:82-93: N
+// observations Y_k ~ N(0, (L Lᵀ)⁻¹) through YY = Σ Y_k Y_kᵀ ([n x n] row-major, symmetric); the d = n(n+1)/2 coordinates are the lower triangle
+// of L packed column by column.  For sspdmp with a diagonal ZigZag(Γ̂, μ̂); n <= 64.  pdmp_ensemble_set_target_precision_cholesky
+struct PrecisionCholesky {
+    int32_t n = 0;
+    std::vector<double> YY;
+    double N = 1.0, gamma0 = 0.0;
+    int64_t d() const { return (int64_t)n * (n + 1) / 2; }
+    // transform / backform of the script (:11-18): the coordinate of L[r, c], r >= c (0-based)
+    int64_t index(int64_t r, int64_t c) const { return c * n - c * (c - 1) / 2 + (r - c); }
+    std::vector<double> unpack(const std::vector<double>& u) const {  // backform(u, 𝕀): L, [n x n] row-major
+        std::vector<double> L((size_t)n * (size_t)n, 0.0);
+        for (int64_t c = 0; c < n; ++c)
+            for (int64_t r = c; r < n; ++r) L[(size_t)(r * n + c)] = u[(size_t)index(r, c)];
+        return L;
     }
 };
 
@@ -297,6 +315,10 @@ inline void set_target(Ensemble& e, const LogisticRegression& g) {
 inline void set_target(Ensemble& e, const DiffusionBridge& g) {
     check(pdmp_ensemble_set_target_diffusion_bridge(e.get(), g.L, g.T, g.alpha, g.beta, g.omega));
 }
+inline void set_target(Ensemble& e, const PrecisionCholesky& g) {
+    if (g.YY.size() != (size_t)g.n * (size_t)g.n) throw std::invalid_argument("PrecisionCholesky: YY must hold n x n entries");
+    check(pdmp_ensemble_set_target_precision_cholesky(e.get(), g.n, g.YY.data(), g.N, g.gamma0));
+}
 inline void set_flow(Ensemble& e, const ZigZag& F) {
     check(pdmp_ensemble_set_flow_zigzag(e.get(), F.Gamma.colptr.data(), F.Gamma.rowval.data(), F.Gamma.nzval.data(), opt(F.mu),
                                         opt(F.sigma), F.lambda_ref, F.rho));
@@ -353,6 +375,10 @@ Result<FactTrace> factorised(int sampler, const Target& target, double t0, const
         }
         check(pdmp_ensemble_trace_reset(e.get()));
     });
+    // (the reference would go on to evaluate N/0: the affine bound let a diagonal of L run into 0 -- a tuning failure like `c` too small)
+    if (std::is_same<Target, PrecisionCholesky>::value && cnt[0].status == PDMP_CHAIN_STALLED)
+        throw std::runtime_error("PrecisionCholesky: the chain stalled: a diagonal coordinate L[c, c] reached 0 (or a coordinate was started at x = 0 "
+                                 "with theta = 0); the bound c is too small for the -N/L[c, c] term");
     R.t.resize((size_t)d);
     R.x.resize((size_t)d);
     R.theta.resize((size_t)d);

@@ -9,4 +9,4 @@ from . import _lib, benchlib, build, ess, parallel, problems, trace  # noqa: F40
 from .engine import Ensemble  # noqa: F401
 from .samplers import Partition, parallel_spdmp, pdmp, spdmp, sspdmp, sspdmp2, stickyzz  # noqa: F401
 from .flows import (Boomerang, Boomerang1d, BouncyParticle, DiffusionBridgeTarget, ExtendedForm, LocalBound, FactBoomerang, FactTrace, GaussianTarget,  # noqa: F401
-                    GaussianTarget1d, LogisticRegressionTarget, LogisticTarget, PDMPTrace, SelfMoving, StickyBarriers, ZigZag, ZigZag1d)
+                    GaussianTarget1d, LogisticRegressionTarget, LogisticTarget, PDMPTrace, PrecisionCholeskyTarget, SelfMoving, StickyBarriers, ZigZag, ZigZag1d)

@@ -49,6 +49,7 @@ EXPORTED_SYMBOLS = [
     "pdmp_ensemble_set_bps_sticky", "pdmp_ensemble_bps_trace_free_copy", "pdmp_ensemble_bps_final_sticky",
     "pdmp_ensemble_set_flow_bps_modern", "pdmp_ensemble_set_bps_record_limit", "pdmp_ensemble_set_target_bps_logistic",
     "pdmp_ensemble_set_barriers", "pdmp_ensemble_final_barrier", "pdmp_ensemble_set_target_diffusion_bridge",
+    "pdmp_ensemble_set_target_precision_cholesky", "pdmp_ensemble_final_sticky",
     "pdmp_ensemble_ess_begin", "pdmp_ensemble_ess_batch", "pdmp_ensemble_ess_end", "pdmp_ensemble_set_gradient_tracking",
     "pdmp_ensemble_path_integrals", "pdmp_ensemble_set_path_integrals", "pdmp_ensemble_set_neighbourhood", "pdmp_ensemble_info",
     "pdmp_ensemble_consume_begin", "pdmp_ensemble_consume", "pdmp_ensemble_consume_async", "pdmp_ensemble_last_consume_ms", "pdmp_ensemble_consume_mean", "pdmp_ensemble_consume_inclusion", "pdmp_ensemble_consume_discretized", "pdmp_ensemble_consume_cummean", "pdmp_ensemble_consume_cummean_copy", "pdmp_ensemble_subtrace_copy", "pdmp_1d_run",
@@ -192,6 +193,8 @@ def load():
     L.pdmp_debug_sector_probe.argtypes = [C.c_int, i64, i64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]
     L.pdmp_ensemble_set_target_logistic.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, f64, i64]
     L.pdmp_ensemble_set_target_diffusion_bridge.argtypes = [vp, C.c_int32, f64, f64, f64, f64]
+    L.pdmp_ensemble_set_target_precision_cholesky.argtypes = [vp, C.c_int32, vp, f64, f64]
+    L.pdmp_ensemble_final_sticky.argtypes = [vp, i64, i64, vp, vp]
     L.pdmp_ensemble_set_sticky.argtypes = [vp, vp, C.c_int, C.c_int]
     L.pdmp_ensemble_set_adaptscale.argtypes = [vp, C.c_int]
     L.pdmp_ensemble_set_local_bound.argtypes = [vp, C.c_int]

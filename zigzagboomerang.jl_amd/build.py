@@ -36,6 +36,7 @@ HEADERS = [os.path.join(CSRC, "pdmp_engine.hpp"),
            os.path.join(CSRC, "pdmp_bps_modern.inc"),  # (included by pdmp_bps.hip)
            os.path.join(CSRC, "pdmp_bps_logit.inc"),  # (included by pdmp_bps.hip)
            os.path.join(CSRC, "pdmp_bridge.inc"),  # (included by pdmp_general.hip)
+           os.path.join(CSRC, "pdmp_precision.inc"),  # (included by pdmp_general.hip)
            os.path.join(PKG_DIR, "..", "include", "pdmp_mi355.h"),
            os.path.join(PKG_DIR, "..", "include", "pdmp_debug.h"),
            os.path.join(PKG_DIR, "..", "include", "pdmp_detmath.h")]

@@ -60,6 +60,7 @@ static const FamilyInfo FAMILY[] = {
     /* FAM_ONE_EVENT     */ {0, "zz_local_run", true},
     /* FAM_BARRIER       */ {0, "zz_barrier_run", true},
     /* FAM_BRIDGE        */ {0, "zz_bridge_run", true},
+    /* FAM_PRECISION     */ {0, "zz_precision_run", true},
 };
 
 pdmp_status launch_deferred_consumer(pdmp_ensemble* e) {
@@ -281,6 +282,11 @@ pdmp_status select_family(const pdmp_ensemble* e, const pdmp::ZzRunParams& P, co
         if (dump) return fail(PDMP_ERR_UNSUPPORTED, "the proposal dump belongs to the one-event kernel");
         return PDMP_OK;
     }
+    if (e->target_kind == TARGET_PRECISION) {  // (set_state has refused everything zz_precision_run_kernel does not take)
+        *fam = FAM_PRECISION;
+        if (dump) return fail(PDMP_ERR_UNSUPPORTED, "the proposal dump belongs to the one-event kernel");
+        return PDMP_OK;
+    }
     if (general_path(e)) {
         // small d: the chain's state lives in LDS for the whole slice (PDMP_DEBUG_KERNEL_SEQ keeps the records in HBM: A/B runs, parity tests)
         const bool lds_resident = e->dbg_kernel != PDMP_DEBUG_KERNEL_SEQ && pdmp::zz_logistic_lds_supported(P, Q, LT);
@@ -401,6 +407,7 @@ pdmp_status ensemble_run_impl(pdmp_ensemble* e, double T, int flags, void* strea
     case FAM_ONE_EVENT: e->last_kernel = "zz_local_run_kernel"; rc = pdmp::launch_zz_local_run(P, n, s); break;
     case FAM_BARRIER: e->last_kernel = "zz_barrier_run_kernel"; rc = pdmp::launch_zz_barrier_run(P, n, s); break;
     case FAM_BRIDGE: e->last_kernel = "zz_bridge_run_kernel"; rc = pdmp::launch_zz_bridge_run(P, e->bridge, n, s); break;
+    case FAM_PRECISION: e->last_kernel = "zz_precision_run_kernel"; rc = pdmp::launch_zz_precision_run(P, e->precision, n, s); break;
 #ifdef PDMP_EXTRA_KERNELS
     case FAM_LOGISTIC_ROWS: e->last_kernel = "zz_logistic_rows_kernel"; rc = pdmp::launch_zz_logistic_rows(P, Q, LT, e->keep_integrals, logistic_rows_width(e), n, s); break;
     case FAM_EXACTP: e->last_kernel = "zz_local_exactp_kernel"; rc = pdmp::launch_zz_local_exactp(P, n, s); break;

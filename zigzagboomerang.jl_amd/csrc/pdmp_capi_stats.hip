@@ -14,6 +14,9 @@ static pdmp_status ess_ready(pdmp_ensemble* e) {
     if (e->target_kind == TARGET_BRIDGE)  // (zz_bridge_run_kernel moves coefficients without accumulating ∫ξ dt: no number rather than a wrong one)
         return fail(PDMP_ERR_UNSUPPORTED, "the diffusion-bridge target keeps no path integrals: batch means, ESS sums and path integrals come from the "
                                           "trace consumers (pdmp_ensemble_consume_*) or the returned trace");
+    if (e->target_kind == TARGET_PRECISION)  // (zz_precision_run_kernel moves a column without accumulating ∫x dt)
+        return fail(PDMP_ERR_UNSUPPORTED, "the precision-cholesky target keeps no path integrals: batch means, ESS sums and path integrals come from the "
+                                          "trace consumers (pdmp_ensemble_consume_*) or the returned trace");
     if (!e->keep_integrals) return fail(PDMP_ERR_INVALID, "the path integrals were switched off (pdmp_ensemble_set_path_integrals)");
     if (e->flow_kind != 0)
         return fail(PDMP_ERR_UNSUPPORTED, "path integrals assume the linear flow of the ZigZag (FactBoomerang rotates between events)");

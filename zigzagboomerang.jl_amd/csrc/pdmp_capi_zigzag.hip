@@ -454,6 +454,31 @@ pdmp_status init_state(pdmp_ensemble* e, double t0, const double* x0, const doub
                     return fail(PDMP_ERR_UNSUPPORTED, "diffusion bridge: θ0[%lld] = %g of chain %lld: the end points are fixed (θ0 = 0 at both; free end points are not implemented)",
                                 (long long)i, th0[k * d + i], (long long)k);
     }
+    if (e->target_kind == TARGET_PRECISION) {
+        // the Cholesky-factor precision target runs on zz_precision_run_kernel alone (pdmp_precision.inc): the case study's configuration
+        // (casestudies/precision/precision.jl: sspdmp with a diagonal Γ̂), everything else is refused here, never served by another kernel
+        if (!sticky) return fail(PDMP_ERR_UNSUPPORTED, "precision cholesky: sspdmp only (PDMP_SAMPLER_STICKY_ZIGZAG)");
+        if (e->flow_kind != 0) return fail(PDMP_ERR_UNSUPPORTED, "precision cholesky: a ZigZag flow, not a FactBoomerang");
+        if (e->has_g1mask)
+            return fail(PDMP_ERR_UNSUPPORTED, "precision cholesky: no pdmp_ensemble_set_neighbourhood (G[i] is the column of i, the target's own; G1[i] = {i})");
+        // (adaptscale: pdmp_ensemble_set_adaptscale itself refuses every sampler but spdmp, PDMP_ERR_UNSUPPORTED; a refresh clock gets here only
+        // where the flow was set again after pdmp_ensemble_set_sticky, which refuses one)
+        if (e->lambda_ref > 0) return fail(PDMP_ERR_UNSUPPORTED, "precision cholesky: no refresh clock (lambda_ref = %g)", e->lambda_ref);
+        bool diagonal = e->nnz == d;
+        for (int64_t i = 0; diagonal && i < d; ++i) diagonal = e->rowval[(size_t)i] == (uint32_t)i && e->bval[(size_t)i] > 0 && std::isfinite(e->bval[(size_t)i]);
+        if (!diagonal) return fail(PDMP_ERR_UNSUPPORTED, "precision cholesky: the flow's Γ must be diagonal with positive entries (ZigZag(diag Γ̂, μ̂))");
+        if (e->track_requested) return fail(PDMP_ERR_UNSUPPORTED, "precision cholesky: no gradient tracking (the diagonal's −N/u term is not linear in time)");
+        if (e->local_bound) return fail(PDMP_ERR_UNSUPPORTED, "precision cholesky: no LocalBound (pdmp_ensemble_set_local_bound)");
+        if (!x0 || !th0) return fail(PDMP_ERR_UNSUPPORTED, "precision cholesky: an explicit state (the diagonal of L must start positive)");
+        const int64_t pn = e->precision.n;
+        for (int64_t k = 0; k < n; ++k)
+            for (int64_t cc = 0; cc < pn; ++cc) {
+                const int64_t i = cc * pn - cc * (cc - 1) / 2;
+                if (!(x0[k * d + i] > 0))
+                    return fail(PDMP_ERR_UNSUPPORTED, "precision cholesky: x0[%lld] = %g of chain %lld: the diagonal coordinates L[c, c] must start > 0 (the potential has −N log L[c, c])",
+                                (long long)i, x0[k * d + i], (long long)k);
+            }
+    }
     e->track = false;
     e->track_lg = false;
     if (e->track_requested && e->target_kind == 1) {
@@ -550,8 +575,8 @@ pdmp_status init_state(pdmp_ensemble* e, double t0, const double* x0, const doub
             PDMP_TRY(e->d_sig_chain.upload(sg));
         }
         e->use_spec = false;
-    } else if (e->target_kind == TARGET_BRIDGE) {
-        e->use_spec = false;  // (no neighbourhood program: zz_bridge_run_kernel computes what it reads from i and its draw)
+    } else if (e->target_kind == TARGET_BRIDGE || e->target_kind == TARGET_PRECISION) {
+        e->use_spec = false;  // (no neighbourhood program: zz_bridge_run_kernel / zz_precision_run_kernel compute what they read from i)
     } else {
         PDMP_TRY(build_blob(e, c));
     }
@@ -917,6 +942,45 @@ pdmp_status pdmp_ensemble_set_target_diffusion_bridge(pdmp_ensemble* e, int32_t 
     return PDMP_OK;
 }
 
+pdmp_status pdmp_ensemble_set_target_precision_cholesky(pdmp_ensemble* e, int32_t n, const double* YY, double N, double gamma0) {
+    if (!e || !YY) return fail(PDMP_ERR_INVALID, "null argument");
+    if (e->cfg.sampler != PDMP_SAMPLER_STICKY_ZIGZAG)
+        return fail(PDMP_ERR_INVALID, "%s: the precision-cholesky target belongs to sspdmp (PDMP_SAMPLER_STICKY_ZIGZAG)", __func__);
+    if (!e->has_flow) return fail(PDMP_ERR_INVALID, "set_flow_zigzag must be called first");
+    if (e->has_state) return fail(PDMP_ERR_INVALID, "a state exists already: the target is set before pdmp_ensemble_set_state (set the flow again to start over)");
+    if (n < 1) return fail(PDMP_ERR_INVALID, "precision cholesky: n = %d < 1", (int)n);
+    if (e->cfg.d != (int64_t)n * ((int64_t)n + 1) / 2)
+        return fail(PDMP_ERR_INVALID, "precision cholesky: d = %lld is not n (n + 1)/2 for n = %d", (long long)e->cfg.d, (int)n);
+    if (!(N > 0) || !std::isfinite(N)) return fail(PDMP_ERR_INVALID, "precision cholesky: N = %g must be positive and finite", N);
+    if (!(gamma0 >= 0) || !std::isfinite(gamma0)) return fail(PDMP_ERR_INVALID, "precision cholesky: gamma0 = %g must be finite and not negative", gamma0);
+    if (n > pdmp::PDMP_PRECISION_NMAX)
+        return fail(PDMP_ERR_UNSUPPORTED, "precision cholesky: n = %d > %d (one column member per lane and one block of 64 keys per lane: d <= 2080)", (int)n,
+                    pdmp::PDMP_PRECISION_NMAX);
+    for (int64_t r = 0; r < n; ++r)
+        for (int64_t q = 0; q <= r; ++q) {
+            const double v = YY[r * n + q], w = YY[q * n + r];
+            if (!std::isfinite(v) || !std::isfinite(w)) return fail(PDMP_ERR_INVALID, "precision cholesky: YY[%lld, %lld] is not finite", (long long)r, (long long)q);
+            if (std::memcmp(&v, &w, sizeof v) != 0)
+                return fail(PDMP_ERR_INVALID, "precision cholesky: YY is not symmetric bit for bit (YY[%lld, %lld] = %.17g, YY[%lld, %lld] = %.17g)", (long long)r,
+                            (long long)q, v, (long long)q, (long long)r, w);
+        }
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    // the kernels' table struct wants tval / gmu_t allocated even if unused
+    e->h_tval.assign((size_t)e->nnz, 0.0);
+    PDMP_TRY(e->d_tval.upload(e->h_tval));
+    PDMP_TRY(e->d_gmu_t.upload(std::vector<double>((size_t)e->cfg.d, 0.0)));
+    e->has_tmu = false;
+    PDMP_TRY(e->d_prec_yy.upload(std::vector<double>(YY, YY + (size_t)n * (size_t)n)));
+    e->precision.n = n;
+    e->precision.pad_ = 0;
+    e->precision.N = N;
+    e->precision.gamma0 = gamma0;
+    e->precision.YY = e->d_prec_yy.p;
+    e->target_kind = TARGET_PRECISION;  // (the later of two target calls wins: the Gaussian and the logistic setters put their own kind back)
+    e->has_target = true;
+    return PDMP_OK;
+}
+
 pdmp_status pdmp_ensemble_set_state(pdmp_ensemble* e, double t0, const double* x0, const double* theta0,
                                     const double* c, const uint64_t* seeds) {
     if (!e || !x0 || !theta0 || !seeds) return fail(PDMP_ERR_INVALID, "null argument");
@@ -991,6 +1055,24 @@ pdmp_status pdmp_ensemble_final_barrier(pdmp_ensemble* e, int64_t chain_first, i
         for (size_t q = 0; q < th.size(); ++q) frozen[q] = (th[q] == 0.0 && vold[q] != 0.0) ? 1 : 0;
     }
     if (theta_saved) std::copy(vold.begin(), vold.end(), theta_saved);
+    return PDMP_OK;
+}
+
+pdmp_status pdmp_ensemble_final_sticky(pdmp_ensemble* e, int64_t chain_first, int64_t n, uint8_t* frozen, double* theta_saved) {
+    if (!e) return fail(PDMP_ERR_INVALID, "null argument");
+    if (e->cfg.sampler != PDMP_SAMPLER_STICKY_ZIGZAG) return fail(PDMP_ERR_INVALID, "ensemble is not a sticky ZigZag (PDMP_SAMPLER_STICKY_ZIGZAG)");
+    if (!e->has_state) return fail(PDMP_ERR_INVALID, "no state");
+    PDMP_TRY(check_chain_range(e, chain_first, n));
+    if (n == 0) return PDMP_OK;
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(device_sync(e));
+    const int64_t d = e->cfg.d;
+    if (frozen) {  // x[i] == 0 && θ[i] == 0, src/ss_fact.jl:108
+        std::vector<double> x((size_t)(n * d)), th((size_t)(n * d));
+        PDMP_TRY(pdmp_ensemble_final_state(e, chain_first, n, nullptr, x.data(), th.data(), nullptr, nullptr));
+        for (size_t q = 0; q < th.size(); ++q) frozen[q] = (x[q] == 0.0 && th[q] == 0.0) ? 1 : 0;
+    }
+    if (theta_saved) HIP_TRY(hipMemcpy(theta_saved, e->d_thf.p + chain_first * d, (size_t)(n * d) * sizeof(double), hipMemcpyDeviceToHost));
     return PDMP_OK;
 }
 

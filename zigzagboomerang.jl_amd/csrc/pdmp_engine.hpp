@@ -395,6 +395,17 @@ struct ZzBridgeParams {
 };
 int launch_zz_bridge_run(const ZzRunParams& p, const ZzBridgeParams& b, int64_t nchains, void* stream);
 
+// The Cholesky factor of a precision matrix under the sticky ZigZag (pdmp_precision.inc, pdmp_ensemble_set_target_precision_cholesky): the
+// d = n(n+1)/2 coordinates are the lower triangle of L packed column by column, the data enter through YY = Σ Y_k Y_kᵀ and N.  One column member
+// per lane and one block minimum per lane: n <= PDMP_PRECISION_NMAX (d = 2080, 33 key blocks).
+constexpr int PDMP_PRECISION_NMAX = 64;
+struct ZzPrecisionParams {
+    int32_t n, pad_;
+    double N, gamma0;
+    const double* __restrict__ YY;  // [n x n] row-major, shared by all chains
+};
+int launch_zz_precision_run(const ZzRunParams& p, const ZzPrecisionParams& b, int64_t nchains, void* stream);
+
 // Small-d subsampled logistic ZigZag with the chain state resident in LDS (pdmp_logistic.hip): packed read-only tables
 struct LgCoord {  // everything a proposal needs that depends on the coordinate alone
     uint32_t cp0, k;    // column of the bounding Γ: G1[i] = rowval[cp0 .. cp0 + k)

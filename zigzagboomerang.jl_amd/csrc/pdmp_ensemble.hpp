@@ -194,6 +194,9 @@ struct pdmp_ensemble {
     int64_t lg_k = 0, lg_nemax = 0;
     // the diffusion bridge (pdmp_ensemble_set_target_diffusion_bridge): target_kind == TARGET_BRIDGE, its parameters
     pdmp::ZzBridgeParams bridge{};
+    // the Cholesky-factor precision target (pdmp_ensemble_set_target_precision_cholesky): target_kind == TARGET_PRECISION, YY on the device
+    pdmp::ZzPrecisionParams precision{};
+    DevBuf<double> d_prec_yy;
 
     // sticky ZigZag
     DevBuf<double> d_kappa, d_thf;
@@ -357,8 +360,9 @@ struct pdmp_ensemble {
 // The event-loop kernel families of pdmp_ensemble_run.  select_family alone decides which one serves an ensemble; what a family does with the phase
 // profile (pdmp_debug_set_phase_profile) and how its launcher's failure reads is stated once, in pdmp_capi.hip's table of FamilyInfo.
 enum KernelFamily { FAM_BPS, FAM_GENERAL, FAM_LOGISTIC_LDS, FAM_LOGISTIC_ROWS, FAM_TRACKL, FAM_TRACKP, FAM_TRACK_GROUPS, FAM_EXACTP,
-                    FAM_STICKY_SPEC, FAM_STICKY_RUN, FAM_SPEC, FAM_ONE_EVENT, FAM_BARRIER, FAM_BRIDGE };
+                    FAM_STICKY_SPEC, FAM_STICKY_RUN, FAM_SPEC, FAM_ONE_EVENT, FAM_BARRIER, FAM_BRIDGE, FAM_PRECISION };
 constexpr int TARGET_BRIDGE = 2;  // pdmp_ensemble::target_kind beside 0 (Gaussian CSC) and 1 (subsampled logistic)
+constexpr int TARGET_PRECISION = 3;  // ... and the Cholesky factor of a precision matrix (sticky ZigZag)
 struct FamilyInfo {
     int phase_kind;        // the `kind` of pdmp_debug_phase_profile its kernels record (pdmp_debug.h), 0: they have no profiling form -- no buffer, no read-back
     const char* launcher;  // "<launcher> launch failed ..."

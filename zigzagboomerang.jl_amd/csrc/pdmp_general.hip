@@ -13,6 +13,7 @@
 #include <cstdint>
 
 #include "../../include/pdmp_detmath.h"
+#include "pdmp_bps_common.hpp"  // (wave_sum_f64, for pdmp_precision.inc)
 #include "pdmp_device.hpp"
 #include "pdmp_engine.hpp"
 
@@ -930,6 +931,7 @@ int launch_zz_general_run(const ZzRunParams& p, const ZzGeneralParams& q_in, int
 }
 
 #include "pdmp_bridge.inc"  // the diffusion bridge's self-moving Faber-Schauder gradient (research/diffusion_bridge): a kernel of its own, nothing above changes
+#include "pdmp_precision.inc"  // the Cholesky factor of a precision matrix under the sticky ZigZag (casestudies/precision): likewise
 
 #ifdef PDMP_EXTRA_KERNELS
 // pdmp_debug_math_eval: the shared scalars (pdmp_device.hpp) this unit calls, as compiled here

@@ -8,7 +8,7 @@ import os
 import numpy as np
 
 from . import _lib
-from .flows import BouncyParticle, DiffusionBridgeTarget, FactBoomerang, GaussianTarget, LogisticRegressionTarget, LogisticTarget, ZigZag
+from .flows import BouncyParticle, DiffusionBridgeTarget, FactBoomerang, GaussianTarget, LogisticRegressionTarget, LogisticTarget, PrecisionCholeskyTarget, ZigZag
 
 
 def _i64(a):
@@ -187,6 +187,15 @@ class Ensemble:
         _lib.check(self._L.pdmp_ensemble_final_barrier(self._h, int(chain_first), int(n), _ptr(fr), _ptr(vo)))
         return dict(frozen=fr.astype(bool), theta_saved=vo)
 
+    def final_sticky(self, chain_first=0, n=None):
+        """Frozen flags ([n x d] bool: x == 0 and θ == 0) and saved speeds θf ([n x d]) of a sticky ZigZag ensemble (pdmp_ensemble_final_sticky)."""
+        if n is None:
+            n = self.nchains - chain_first
+        fr = np.empty((n, self.d), dtype=np.uint8)
+        tf = np.empty((n, self.d))
+        _lib.check(self._L.pdmp_ensemble_final_sticky(self._h, int(chain_first), int(n), _ptr(fr), _ptr(tf)))
+        return dict(frozen=fr.astype(bool), theta_f=tf)
+
     def set_local_bound(self, enable=True):
         """c::LocalBound, src/local.jl: bounds from the target's own derivatives with an expiry horizon."""
         _lib.check(self._L.pdmp_ensemble_set_local_bound(self._h, int(bool(enable))))
@@ -344,6 +353,9 @@ class Ensemble:
         if isinstance(target, DiffusionBridgeTarget):
             _lib.check(self._L.pdmp_ensemble_set_target_diffusion_bridge(self._h, int(target.L), float(target.T), float(target.α), float(target.β),
                                                                          float(target.ω)))
+            return
+        if isinstance(target, PrecisionCholeskyTarget):
+            _lib.check(self._L.pdmp_ensemble_set_target_precision_cholesky(self._h, int(target.n), _ptr(target.YY), float(target.N), float(target.γ0)))
             return
         if isinstance(target, LogisticTarget):
             A, At = target.A, target.At

@@ -238,6 +238,32 @@ class DiffusionBridgeTarget:
         return (2 << self.L) + 1
 
 
+@dataclass
+class PrecisionCholeskyTarget:
+    """∇ϕ(u, i, YY, (𝕀, 𝕁), N) of casestudies/precision/precision.jl:42-53 (γ0 = 0) and research/newsticky/precision/precision4.jl:82-93
+    (γ0 > 0) with its `args = (YY, (𝕀, 𝕁), N)`: N observations Y_k ~ N(0, (L Lᵀ)⁻¹) through YY = Σ Y_k Y_kᵀ ([n x n], symmetric), the
+    coordinates being the lower triangle of L packed column by column (trace.pack_lower / unpack_lower; d = n(n+1)/2):
+    ∇ϕ_i = Σ_q YY[r, c+q] L[c+q, c] + (r == c ? −N/L[c,c] + γ0 (L[c,c] − 1) : γ0 L[r,c]).  For sspdmp with a diagonal ZigZag(Γ̂, μ̂)
+    (problems.precision_cholesky_problem builds it); n <= 64.  pdmp_ensemble_set_target_precision_cholesky."""
+    YY: np.ndarray
+    N: float
+    γ0: float = 0.0
+
+    def __post_init__(self):
+        self.YY = np.ascontiguousarray(self.YY, dtype=np.float64)
+        if self.YY.ndim != 2 or self.YY.shape[0] != self.YY.shape[1]:
+            raise ValueError("YY must be a square matrix")
+        self.N, self.γ0 = float(self.N), float(self.γ0)
+
+    @property
+    def n(self):
+        return self.YY.shape[0]
+
+    @property
+    def d(self):
+        return self.n * (self.n + 1) // 2
+
+
 class ExtendedForm:
     """ExtendedForm() / SelfMoving() (src/types.jl:103-119, src/sfact.jl:57-68): as the first of spdmp's `args...` it says that ∇ϕ takes
     (t, x, θ, i, t′, F, args...) and moves the coordinates it reads itself.  The device targets that work this way (LogisticTarget,

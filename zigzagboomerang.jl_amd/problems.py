@@ -294,3 +294,50 @@ def bridge_point_condition(L, T, s, a):
         j = int(np.floor(s / T * p2)) * (2 << lev) + (1 << lev)
         n[j] += (sT * 0.5 - abs(np.fmod(s * p2, T) / sT - sT * 0.5)) / np.sqrt(p2)  # Λ(s, L − lev, T), :3-6
     return a * n / (n @ n), n
+
+
+def precision_cholesky_problem(n, N, seed, γ0=0.0, w=0.5, nchains=None, jiggle=0.01, c=10.0):
+    """The inputs of casestudies/precision/precision.jl (research/newsticky/precision/precision4.jl with γ0 > 0): learning a sparse precision
+    matrix through its Cholesky factor.  Γtrue = SymTridiagonal(1, −0.3) (:22-23), Y = Ltrue⁻ᵀ-coloured N(0, I) draws so that
+    Y_k ~ N(0, Γtrue⁻¹) (:25-26), YY = Y Yᵀ (:27).  Returns a dict:
+      YY [n x n], N, γ0, n, d = n(n+1)/2, Γtrue, Ltrue, utrue = pack_lower(Ltrue);
+      μ̂ [d]: per column c the mode of the flat-prior posterior exp(−½ vᵀ A v + N log v₁), A = YY[c:, c:]: with s = A₁₁ − A₁₂ A₂₂⁻¹ A₂₁,
+             v₁ = √(N/s) and v_rest = −A₂₂⁻¹ A₂₁ v₁ (the script centres its flow at the Cholesky factor of the sample covariance, :75-76);
+      γ̂ [d]: the curvature of ϕ along coordinate (r, c) at μ̂: YY[r, r] + γ0 + (r == c ? N/μ̂² : 0), and Γ̂ = diag(γ̂) as a CSC matrix (the
+             script takes Γ̂ = I, :72);
+      x0, θ0: utrue + jiggle·randn (:59) with the diagonal kept positive, θ0 uniform on {−1, +1} (:64) -- [d], or [nchains x d];
+      c = 10 (:70); κ [d]: precision4.jl:196-197's κ = √(γ0/2π)/(1/w − 1) where γ0 > 0, the script's 0.01 (:79) where γ0 = 0."""
+    from .trace import lower_index, pack_lower
+    n, N = int(n), int(N)
+    rng = np.random.default_rng(seed)
+    G = np.eye(n) - 0.3 * (np.eye(n, k=1) + np.eye(n, k=-1))
+    Ltrue = np.linalg.cholesky(G)
+    Y = np.linalg.solve(Ltrue.T, rng.standard_normal((n, N)))  # cov(Y) = (Ltrue Ltrueᵀ)⁻¹
+    YY = Y @ Y.T
+    YY = 0.5 * (YY + YY.T)  # symmetric bit for bit
+    d = n * (n + 1) // 2
+    rows, cols = lower_index(n)
+    mu = np.empty(d)
+    k0 = 0
+    for col in range(n):
+        A = YY[col:, col:]
+        if n - col > 1:
+            w21 = np.linalg.solve(A[1:, 1:], A[1:, 0])
+            s = A[0, 0] - A[0, 1:] @ w21
+        else:
+            w21, s = np.empty(0), A[0, 0]
+        v1 = np.sqrt(N / s)
+        mu[k0] = v1
+        mu[k0 + 1:k0 + n - col] = -w21 * v1
+        k0 += n - col
+    gam = YY[rows, rows] + γ0 + np.where(rows == cols, N / mu**2, 0.0)
+    utrue = pack_lower(Ltrue)
+    m = 1 if nchains is None else int(nchains)
+    x0 = utrue[None, :] + jiggle * rng.standard_normal((m, d))
+    x0[:, rows == cols] = np.abs(x0[:, rows == cols])
+    th0 = rng.choice([-1.0, 1.0], size=(m, d))
+    kappa = np.full(d, (np.sqrt(γ0 / (2 * np.pi)) / (1 / w - 1)) if γ0 > 0 else 0.01)
+    out = dict(YY=YY, N=float(N), γ0=float(γ0), n=n, d=d, Γtrue=G, Ltrue=Ltrue, utrue=utrue, μ̂=mu, γ̂=gam, Γ̂=sp.diags(gam, format="csc"),
+               c=np.full(d, float(c)), κ=kappa)
+    out["x0"], out["θ0"] = (x0[0], th0[0]) if nchains is None else (x0, th0)
+    return out

@@ -16,7 +16,7 @@ import scipy.sparse as sp
 from . import _lib
 from .engine import Ensemble
 from .flows import (Boomerang, Boomerang1d, BouncyParticle, DiffusionBridgeTarget, ExtendedForm, FactBoomerang, LocalBound, FactTrace, GaussianTarget,
-                    GaussianTarget1d, LogisticRegressionTarget, LogisticTarget, PDMPTrace, StickyBarriers, ZigZag, ZigZag1d)
+                    GaussianTarget1d, LogisticRegressionTarget, LogisticTarget, PDMPTrace, PrecisionCholeskyTarget, StickyBarriers, ZigZag, ZigZag1d)
 
 DEFAULT_SEED = 0x5EED0000
 
@@ -319,6 +319,10 @@ def sspdmp(target, t0, x0, θ0, T, c, *GFκ, reversible=False, strong_upperbound
     """Sticky ZigZag: sspdmp(∇ϕ, t0, x0, θ0, T, c, [G,] F::ZigZag, κ, args...; reversible, strong_upperbounds, factor=1.5,
     adapt) (src/ss_fact.jl:159-160,217) -> Ξ, (t, x, θ), (acc, num), c with scalar acc, num (:175,214).  G as in spdmp (:167-172).
 
+    With a PrecisionCholeskyTarget this is casestudies/precision/precision.jl:82: sspdmp(target, t0, x0, θ0, T, c, ZigZag(diag Γ̂, μ̂), κ;
+    adapt=True) with the inputs of problems.precision_cholesky_problem (the column of a coordinate, the script's G, is the target's own);
+    consume=dict(dt=..., points=...) then appends dict(mean, T, grid_t, grid_x, inclusion) from the device consumers.
+
     Sticky Bouncy Particle / Boomerang: sspdmp(∇ϕ!, t0, x0, θ0, T, c, Flow::Union{BouncyParticle, Boomerang}, κ, args...;
     strong_upperbounds, adapt, factor=2.0) (src/ss_not_fact.jl:182-201) -> Ξ, (t, x, θ), (acc, num), c.  Ξ is a PDMPTrace carrying f0 and f
     ([events x d] bool, True = free); its first event is (t0, x0, θ0, all free) (:189).  target as in pdmp: None (∇ϕ!(y, x) = B.Γ(x − B.μ))
@@ -336,9 +340,9 @@ def sspdmp(target, t0, x0, θ0, T, c, *GFκ, reversible=False, strong_upperbound
             raise TypeError("BouncyParticle: target is None (∇ϕ!(y, x) = B.Γ(x − B.μ)) or a GaussianTarget of its own")
         return _bps(t0, x0, θ0, T, c, F, 2.0 if factor is None else factor, adapt, seed, device, trace_capacity, trace, target=target,
                     sticky=(GFκ[1], strong_upperbounds), consume=consume)
-    if consume is not None and not _admits(consume):
-        raise TypeError("consume is a keyword of the sticky BouncyParticle / Boomerang, or with cov=P or hist=dict(...) (elsewhere the ZigZag's device consumers are "
-                        "Ensemble.consume_*)")
+    if consume is not None and not _admits(consume) and not isinstance(target, PrecisionCholeskyTarget):
+        raise TypeError("consume is a keyword of the sticky BouncyParticle / Boomerang and of a PrecisionCholeskyTarget, or with cov=P or hist=dict(...) "
+                        "(elsewhere the ZigZag's device consumers are Ensemble.consume_*)")
     if len(GFκ) not in (2, 3):
         raise TypeError("expected sspdmp(target, t0, x0, θ0, T, c, [G,] F, κ, ...)")
     G, F = _split_G(GFκ[:-1], G)
@@ -515,8 +519,10 @@ def _zigzag(sampler, target, t0, x0, θ0, T, c, F, factor, adapt, seed, device, 
             adaptscale=False, tracked=False, G=None, barriers=None, details=False, consume=None):
     if not isinstance(F, (ZigZag, FactBoomerang)):
         raise TypeError("the device path supports F::ZigZag and F::FactBoomerang")
-    if not isinstance(target, (GaussianTarget, LogisticTarget, DiffusionBridgeTarget)):
-        raise TypeError("target must be one of the device-resident families (GaussianTarget, LogisticTarget, DiffusionBridgeTarget)")
+    if not isinstance(target, (GaussianTarget, LogisticTarget, DiffusionBridgeTarget, PrecisionCholeskyTarget)):
+        raise TypeError("target must be one of the device-resident families (GaussianTarget, LogisticTarget, DiffusionBridgeTarget, PrecisionCholeskyTarget)")
+    if isinstance(target, PrecisionCholeskyTarget) and sticky is None:
+        raise TypeError("PrecisionCholeskyTarget is a target of sspdmp (the sticky ZigZag of casestudies/precision/precision.jl)")
     # a flow with a refresh clock (a ZigZag with λref > 0, a FactBoomerang) leaves a trace that is sorted within a coordinate only: the unordered
     # consumers (Ensemble.refresh_consume_begin) serve it, with mean and the grid alone
     refresh = barriers is None and sticky is None and (isinstance(F, FactBoomerang) or F.λref > 0)
@@ -524,9 +530,9 @@ def _zigzag(sampler, target, t0, x0, θ0, T, c, F, factor, adapt, seed, device, 
         if not isinstance(consume, dict) or set(consume) & {"cov", "center", "hist", "condition", "hits"}:
             raise TypeError("consume=dict(dt=..., points=...) on a flow with a refresh clock (a ZigZag with λref > 0, a FactBoomerang): cov, hist and "
                             "condition walk a time-ordered trace and are not available there")
-    elif consume is not None and barriers is None and not isinstance(target, DiffusionBridgeTarget) and not _admits(consume):
-        raise TypeError("consume is a keyword of spdmp with a DiffusionBridgeTarget, or with cov=P or hist=dict(...) (elsewhere the ZigZag's device consumers are "
-                        "Ensemble.consume_*)")
+    elif consume is not None and barriers is None and not isinstance(target, (DiffusionBridgeTarget, PrecisionCholeskyTarget)) and not _admits(consume):
+        raise TypeError("consume is a keyword of spdmp with a DiffusionBridgeTarget and of sspdmp with a PrecisionCholeskyTarget, or with cov=P or "
+                        "hist=dict(...) (elsewhere the ZigZag's device consumers are Ensemble.consume_*)")
     x0 = np.asarray(x0, dtype=np.float64)
     θ0 = np.asarray(θ0, dtype=np.float64)
     single = x0.ndim == 1
@@ -578,6 +584,11 @@ def _zigzag(sampler, target, t0, x0, θ0, T, c, F, factor, adapt, seed, device, 
             cnt = ens.counters()
             if np.any(cnt["status"] == _lib.CHAIN_BOUND_VIOLATED):
                 raise RuntimeError("Tuning parameter `c` too small.")  # src/sfact.jl:124
+            if isinstance(target, PrecisionCholeskyTarget) and np.any(cnt["status"] == _lib.CHAIN_STALLED):
+                # (the reference would go on to evaluate N/0: the affine bound let a diagonal of L run into 0 -- a tuning failure like the one above)
+                k = int(np.flatnonzero(cnt["status"] == _lib.CHAIN_STALLED)[0])
+                raise RuntimeError("PrecisionCholeskyTarget: chain %d stalled at t = %g: a diagonal coordinate L[c, c] reached 0 (or a coordinate was "
+                                   "started at x = 0 with θ = 0); the bound c is too small for the −N/L[c, c] term" % (k, float(cnt["t_last"][k])))
             if consume is not None:
                 ens.consume()
             if trace:
@@ -590,6 +601,8 @@ def _zigzag(sampler, target, t0, x0, θ0, T, c, F, factor, adapt, seed, device, 
         if consume is not None:
             mean, Tl = ens.consume_mean()
             consumed = dict(mean=mean, T=Tl, grid_t=None, grid_x=None)
+            if isinstance(target, PrecisionCholeskyTarget):
+                consumed["inclusion"] = ens.consume_inclusion()[0]  # trace.inclusion_prob(Ξ): the posterior probability of L[r, c] != 0
             if barriers is not None:
                 occ = ens.barrier_consume_occupation()
                 consumed.update(frozen_lo=occ[0], frozen_hi=occ[1], hits_lo=occ[2], hits_hi=occ[3])

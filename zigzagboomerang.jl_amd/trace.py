@@ -778,3 +778,32 @@ def faber_schauder_path(ξ, s, L, T):
     if ξ.ndim == 1:
         return r[0] if s.ndim else r[0, 0]
     return r if s.ndim else r[:, 0]
+
+
+def lower_index(n):
+    """(rows, cols) of the packed lower triangle of an n x n matrix, column by column: 𝕀 of casestudies/precision/precision.jl:39 (0-based).
+    Coordinate i = c n − c (c − 1)/2 + (r − c) is entry (rows[i], cols[i]); d = n (n + 1)/2."""
+    n = int(n)
+    cols, rows = np.triu_indices(n)  # row-major upper triangle of the transpose == column-major lower triangle
+    return rows.astype(np.int64), cols.astype(np.int64)
+
+
+def pack_lower(L):
+    """transform(L, 𝕀) = L[𝕀] (precision.jl:18): the lower triangle of L ([n x n], or a stack [... x n x n]) as the coordinate vector u."""
+    L = np.asarray(L, dtype=np.float64)
+    r, c = lower_index(L.shape[-1])
+    return L[..., r, c]
+
+
+def unpack_lower(u, n=None):
+    """backform(u, 𝕀) (precision.jl:11-17): the lower-triangular matrix of the coordinate vector u ([d], or a stack [... x d])."""
+    u = np.asarray(u, dtype=np.float64)
+    d = u.shape[-1]
+    if n is None:
+        n = int(round((np.sqrt(8 * d + 1) - 1) / 2))
+    if n * (n + 1) // 2 != d:
+        raise ValueError("u has %d coordinates: not n (n + 1)/2 for n = %d" % (d, n))
+    r, c = lower_index(n)
+    L = np.zeros(u.shape[:-1] + (n, n))
+    L[..., r, c] = u
+    return L
