@@ -163,6 +163,58 @@ pdmp_status pdmp_debug_sticky_eval(int device, int fn, int64_t n, const double* 
 pdmp_status pdmp_debug_barrier_eval(int device, int fn, int64_t n, const double* a, const double* b, const double* c, double* out);
 
 /*
+ * Test hooks one layer above the scalars (parity build only, like pdmp_debug_math_eval; PDMP_ERR_UNSUPPORTED elsewhere): the 64-lane primitives
+ * and the first-level codes of the queues, each CALLED by a probe kernel of the unit that owns it (an anonymous-namespace helper can be reached
+ * from nowhere else).  tests/wave_tables.py and tests/queue_tables.py hold the edge tables and a plain reference of every id;
+ * tests/test_gpu_wave_primitives.py and tests/test_gpu_queue_codes.py hold the device to them.
+ *
+ * pdmp_debug_wave_eval: in0, in1 and out are [nrows x 64] 64-bit words -- the bit image of a double, or a u32 in the low half (the high half of
+ * such an output is 0).  One 64-lane workgroup per row; out[row][lane] is what that lane holds after the call.
+ */
+/* csrc/pdmp_device.hpp, probed in pdmp_kernels.hip */
+#define PDMP_WAVE_MIN_F64 0     /* wave_min_f64: every lane (wave-uniform) */
+#define PDMP_WAVE_GRP8_MIN_F64 1 /* grp8_min_f64: every lane of each group of 8 */
+#define PDMP_WAVE_ROW_MIN_F64 2 /* row_min_f64: every lane of each row of 16 */
+#define PDMP_WAVE_MIN_U32 3     /* wave_min_u32: every lane */
+#define PDMP_WAVE_MIN_U32_DPP 4 /* wave_min_u32_dpp: every lane */
+#define PDMP_WAVE_SCAN_ADD_U32 5 /* scan_add_u32: inclusive prefix sum mod 2^32, every lane */
+#define PDMP_WAVE_SCAN_MIN_F64 6 /* scan_min_f64: inclusive prefix minimum, every lane */
+#define PDMP_WAVE_BPERM_F64 7   /* bperm_f64(v = in0, src = the low half of in1, 0..63) */
+#define PDMP_WAVE_SUM_F64 8     /* pdmp_bps_common.hpp wave_sum_f64, probed in pdmp_bps.hip: every lane */
+#define PDMP_WAVE_GRP8_MIN_U32 9 /* pdmp_trackp.hip w_grp8_min_u32: every lane of each group of 8 */
+pdmp_status pdmp_debug_wave_eval(int device, int fn, int64_t nrows, const uint64_t* in0, const uint64_t* in1, uint64_t* out);
+
+/* pdmp_debug_queue_eval: one helper at the points (a[k], b[k], c[k]); out is [2 x n] as in pdmp_debug_math_eval.  Integer arguments are given and
+ * integer results returned as exactly representable doubles. */
+#define PDMP_QUEUE_P_ENC 0  /* pdmp_trackp.hip p_enc(key = a, tb = b, pos = c) */
+#define PDMP_QUEUE_P_THR 1  /* pdmp_trackp.hip p_thr(tau = a, tb = b) */
+#define PDMP_QUEUE_P_DEC 2  /* pdmp_trackp.hip p_dec(bits = a, tb = b) */
+#define PDMP_QUEUE_Q_ENC 3  /* pdmp_exactp.hip q_enc(key = a, tb = b, pos = c) */
+#define PDMP_QUEUE_Q_THR 4  /* pdmp_exactp.hip q_thr(tau = a, tb = b) */
+#define PDMP_QUEUE_Q_DEC 5  /* pdmp_exactp.hip q_dec(bits = a, tb = b) */
+#define PDMP_QUEUE_TL_Q 6   /* pdmp_trackl.hip tl_q(t = a, tref = b, s = c) */
+#define PDMP_QUEUE_BELOW 7  /* pdmp_device.hpp pdmp_below(a), probed in pdmp_kernels.hip */
+#define PDMP_QUEUE_HB 8     /* pdmp_trackl.hip hb_word(b = a) in row 0, hb_bit(b = a) in row 1 */
+#define PDMP_QUEUE_NB_HAS 9 /* pdmp_trackp.hip nb_has(nb = the bit images of a (x, y) and b (z, w), v = c given twice): 1 or 0 */
+#define PDMP_QUEUE_NB_COUNT 10 /* pdmp_trackp.hip nb_count(nb = the bit images of a and b) */
+pdmp_status pdmp_debug_queue_eval(int device, int fn, int64_t n, const double* a, const double* b, const double* c, double* out);
+
+/* pdmp_debug_state_eval: the helpers that keep a state in LDS, run by ONE wavefront on a given list of nchg changes (idx[k], val[k]) applied in order.
+ *   WHEEL     img_set / img_get: the planes are cleared, write k is img_set(b = idx[k] < 8192, w9 = val[k] < 512), out [8192] is img_get of every
+ *             block (keys, nkeys, d, has_refresh unused).
+ *   LEVEL1    level1_build over keys [nkeys = nblk x 64, nblk <= 512], then per change keys[idx[k]] = val[k] and level1_update;
+ *             out is [4 x nblk]: bk and bi after the build, bk and bi after the changes; then [nchg x 2]: the entry (bk, bi) of the changed key's
+ *             block right after each update.
+ *   S8_LEVEL1 s8_build_level1<true>(d, has_refresh) over keys [nkeys = nblk x 32], the refresh slot keys[d] (d < nkeys) parked at +Inf after the
+ *             build as the kernels do, then s8_level1_update per change; out is [4 x 512] (the entries past nblk are part of the contract), then [nchg x 2] as above.
+ * PDMP_ERR_INVALID for an index outside its array. */
+#define PDMP_STATE_WHEEL 0     /* pdmp_trackl.hip img_set, img_get */
+#define PDMP_STATE_LEVEL1 1    /* pdmp_device.hpp level1_build, level1_update, probed in pdmp_kernels.hip */
+#define PDMP_STATE_S8_LEVEL1 2 /* pdmp_spec8_common.hpp s8_build_level1, s8_level1_update, probed in pdmp_kernels.hip */
+pdmp_status pdmp_debug_state_eval(int device, int fn, int64_t nkeys, const double* keys, int64_t d, int has_refresh, int64_t nchg, const uint32_t* idx,
+                                  const double* val, double* out);
+
+/*
  * Test hook: puts a given trace segment in front of the device consumers (csrc/pdmp_consume.hip; tests/test_gpu_consumers_synthetic.py).  Waits for
  * the device (pending asynchronous consumers included), copies the n events into slots [ntrace, ntrace + n) of `chain`'s CURRENT trace buffer and
  * adds n to the chain's ntrace and nevents -- no event-loop kernel runs, no record changes.  PDMP_ERR_INVALID for a bad chain, n < 0,

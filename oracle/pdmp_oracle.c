@@ -2162,6 +2162,7 @@ void orc_randn2(uint64_t seed, uint32_t stream, uint64_t n, double* z0, double* 
 uint32_t orc_randint(uint64_t seed, uint32_t stream, uint64_t n_draw, uint32_t n) { return pdmp_randint(seed, stream, n_draw, n); }
 double orc_sigmoid(double x) { return lg_sigmoid(x); }
 double orc_pos(double x) { return pos(x); }
+double orc_dot_wave64(const double* a, const double* b, int64_t d) { return dot_wave64(a, b, d); }
 double orc_u01(uint64_t seed, uint32_t stream, uint64_t n) { return pdmp_u01(seed, stream, n); }
 double orc_randn(uint64_t seed, uint32_t stream, uint64_t n) { return pdmp_randn(seed, stream, n); }
 void orc_philox(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {

@@ -275,6 +275,7 @@ void orc_randn2(uint64_t seed, uint32_t stream, uint64_t n, double* z0, double* 
 uint32_t orc_randint(uint64_t seed, uint32_t stream, uint64_t n_draw, uint32_t n);
 double orc_sigmoid(double x); /* lg_sigmoid: sigmoid of the logistic targets */
 double orc_pos(double x);     /* pos(x) = max(0, x), NaN kept */
+double orc_dot_wave64(const double* a, const double* b, int64_t d); /* dot_wave64: the Bouncy Particle family's one summation order */
 double orc_u01(uint64_t seed, uint32_t stream, uint64_t n);
 double orc_randn(uint64_t seed, uint32_t stream, uint64_t n);
 void orc_philox(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);

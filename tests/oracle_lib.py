@@ -132,6 +132,8 @@ def lib():
         for name in ("orc_exp", "orc_sigmoid", "orc_pos"):
             getattr(L, name).restype = C.c_double
             getattr(L, name).argtypes = [C.c_double]
+        L.orc_dot_wave64.restype = C.c_double
+        L.orc_dot_wave64.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         L.orc_sincos.argtypes = [C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.orc_sincos2pi.argtypes = [C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.orc_bits_to_u01.restype = C.c_double

@@ -117,3 +117,12 @@ def test_scalar_probe_is_parity_library_only(pkg):
     out = (ctypes.c_double * 2)()
     st = pkg._lib.load().pdmp_debug_math_eval(0, 2, 1, a, a, a, out)
     assert st == pkg._lib.PDMP_ERR_UNSUPPORTED
+    # ... and so do the probes one layer up: the wave primitives, the queues' first-level codes, the LDS-state helpers
+    L = pkg._lib.load()
+    assert L.pdmp_debug_queue_eval(0, 0, 1, a, a, a, out) == pkg._lib.PDMP_ERR_UNSUPPORTED
+    w = (ctypes.c_uint64 * 64)()
+    assert L.pdmp_debug_wave_eval(0, 0, 1, w, w, w) == pkg._lib.PDMP_ERR_UNSUPPORTED
+    idx = (ctypes.c_uint32 * 1)(0)
+    img = (ctypes.c_double * 8192)()
+    assert L.pdmp_debug_state_eval(0, 0, 0, None, 0, 0, 1, idx, a, img) == pkg._lib.PDMP_ERR_UNSUPPORTED
+    assert b"parity build" in L.pdmp_last_error()

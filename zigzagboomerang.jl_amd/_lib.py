@@ -66,7 +66,8 @@ EXPORTED_SYMBOLS = [
 # include/pdmp_debug.h: diagnostics, not part of the drop-in boundary
 DEBUG_SYMBOLS = ["pdmp_debug_set_kernel", "pdmp_debug_set_spec_g2", "pdmp_debug_set_phase_profile", "pdmp_debug_phase_profile",
                  "pdmp_debug_set_proposal_dump", "pdmp_debug_set_track_groups", "pdmp_debug_set_helper_wave", "pdmp_debug_set_prio_policy", "pdmp_debug_set_track_lines", "pdmp_debug_buffer_addresses", "pdmp_debug_placement", "pdmp_debug_set_placement", "pdmp_debug_move_buffer", "pdmp_debug_set_helper_steering", "pdmp_debug_set_launch_count_limit", "pdmp_debug_host_drain_probe", "pdmp_debug_set_consumer_overlap", "pdmp_debug_last_kernel", "pdmp_debug_set_logistic_rows", "pdmp_debug_math_probe", "pdmp_debug_math_eval", "pdmp_debug_write_probe", "pdmp_debug_sector_probe",
-                 "pdmp_debug_sticky_eval", "pdmp_debug_trace_append", "pdmp_debug_barrier_eval", "pdmp_debug_bps_trace_append"]
+                 "pdmp_debug_sticky_eval", "pdmp_debug_trace_append", "pdmp_debug_barrier_eval", "pdmp_debug_bps_trace_append",
+                 "pdmp_debug_wave_eval", "pdmp_debug_queue_eval", "pdmp_debug_state_eval"]
 DEBUG_KERNELS = {"auto": 0, "seq": 1, "spec4": 2, "spec8": 3, "exactp": 4}
 
 
@@ -218,6 +219,9 @@ def load():
     L.pdmp_ensemble_set_bps_record_limit.argtypes = [vp, i64]
     L.pdmp_debug_sticky_eval.argtypes = [C.c_int, C.c_int, i64, vp, vp, vp, vp]
     L.pdmp_debug_barrier_eval.argtypes = [C.c_int, C.c_int, i64, vp, vp, vp, vp]
+    L.pdmp_debug_wave_eval.argtypes = [C.c_int, C.c_int, i64, vp, vp, vp]
+    L.pdmp_debug_queue_eval.argtypes = [C.c_int, C.c_int, i64, vp, vp, vp, vp]
+    L.pdmp_debug_state_eval.argtypes = [C.c_int, C.c_int, i64, vp, i64, C.c_int, i64, vp, vp, vp]
     L.pdmp_ensemble_set_barriers.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int]
     L.pdmp_ensemble_final_barrier.argtypes = [vp, i64, i64, vp, vp]
     L.pdmp_debug_trace_append.argtypes = [vp, i64, vp, i64]
@@ -293,6 +297,48 @@ def math_eval(fn, a, b=None, c=None, device=0):
     out = np.empty((2, a.size))
     check(load().pdmp_debug_math_eval(int(device), int(fn), int(a.size), a.ctypes.data, b.ctypes.data, c.ctypes.data, out.ctypes.data))
     return out
+
+
+def queue_eval(fn, a, b=None, c=None, device=0):
+    """[2 x n] outputs of the queue helper `fn` (PDMP_QUEUE_* of include/pdmp_debug.h) at (a[k], b[k], c[k]), called inside its own unit; parity library only."""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    b = np.zeros_like(a) if b is None else np.ascontiguousarray(np.broadcast_to(b, a.shape), dtype=np.float64)
+    c = np.zeros_like(a) if c is None else np.ascontiguousarray(np.broadcast_to(c, a.shape), dtype=np.float64)
+    out = np.empty((2, a.size))
+    check(load().pdmp_debug_queue_eval(int(device), int(fn), int(a.size), a.ctypes.data, b.ctypes.data, c.ctypes.data, out.ctypes.data))
+    return out
+
+
+def wave_eval(fn, in0, in1=None, device=0):
+    """[nrows x 64] u64 words: what each lane holds after the wave primitive `fn` (PDMP_WAVE_* of include/pdmp_debug.h) ran on a row of 64 words
+    (bit images of doubles, or u32 in the low half), one wavefront per row; parity library only."""
+    in0 = np.ascontiguousarray(in0, dtype=np.uint64)
+    assert in0.ndim == 2 and in0.shape[1] == 64, in0.shape
+    in1 = np.zeros_like(in0) if in1 is None else np.ascontiguousarray(np.broadcast_to(in1, in0.shape), dtype=np.uint64)
+    out = np.empty_like(in0)
+    check(load().pdmp_debug_wave_eval(int(device), int(fn), int(in0.shape[0]), in0.ctypes.data, in1.ctypes.data, out.ctypes.data))
+    return out
+
+
+STATE_WHEEL, STATE_LEVEL1, STATE_S8_LEVEL1 = 0, 1, 2  # PDMP_STATE_* of include/pdmp_debug.h
+
+
+def state_eval(fn, keys=None, changes=(), d=0, has_refresh=False, device=0):
+    """The LDS-state helpers (PDMP_STATE_* of include/pdmp_debug.h) on a list of changes [(index, value), ...] applied in order by one wavefront.
+    STATE_WHEEL: [8192] images after the img_set writes; STATE_LEVEL1 / STATE_S8_LEVEL1: ((bk0, bi0, bk1, bi1), steps) -- the first level after the
+    build and after the changes, [nblk] resp. [512] each, and [nchg x 2] the entry of the changed key's block after each update.  Parity library only."""
+    idx = np.ascontiguousarray([j for j, _ in changes], dtype=np.uint32)
+    val = np.ascontiguousarray([v for _, v in changes], dtype=np.float64)
+    if fn == STATE_WHEEL:
+        out = np.empty(8192)
+        check(load().pdmp_debug_state_eval(int(device), int(fn), 0, None, 0, 0, len(idx), idx.ctypes.data, val.ctypes.data, out.ctypes.data))
+        return out
+    keys = np.ascontiguousarray(keys, dtype=np.float64)
+    nout = keys.size // 64 if fn == STATE_LEVEL1 else 512
+    out = np.empty(4 * nout + 2 * len(idx))
+    check(load().pdmp_debug_state_eval(int(device), int(fn), int(keys.size), keys.ctypes.data, int(d), int(bool(has_refresh)), len(idx), idx.ctypes.data,
+                                       val.ctypes.data, out.ctypes.data))
+    return out[:4 * nout].reshape(4, nout), out[4 * nout:].reshape(len(idx), 2)
 
 
 def barrier_eval(fn, a, b=None, c=None, device=0):

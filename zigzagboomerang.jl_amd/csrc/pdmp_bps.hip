@@ -960,6 +960,15 @@ struct BpsMathEval {
 int launch_math_eval_bps(int fn, int64_t n, const double* a, const double* b, const double* c, double* out, void* stream) {
     return launch_math_eval<BpsMathEval>(fn, n, a, b, c, out, stream);
 }
+// pdmp_debug_wave_eval: the family's all-lanes sum (pdmp_bps_common.hpp), as compiled here
+namespace {
+struct BpsWaveEval {
+    __device__ uint64_t operator()(int, uint64_t w0, uint64_t) const { return pdmp_f2u(wave_sum_f64(pdmp_u2f(w0))); }  // PDMP_WAVE_SUM_F64
+};
+}  // namespace
+int launch_wave_eval_bps(int fn, int64_t nrows, const uint64_t* in0, const uint64_t* in1, uint64_t* out, void* stream) {
+    return launch_wave_eval<BpsWaveEval>(fn, nrows, in0, in1, out, stream);
+}
 #endif
 
 }  // namespace pdmp

@@ -389,4 +389,106 @@ pdmp_status pdmp_debug_barrier_eval(int device, int fn, int64_t n, const double*
     return PDMP_OK;
 #endif
 }
+
+pdmp_status pdmp_debug_wave_eval(int device, int fn, int64_t nrows, const uint64_t* in0, const uint64_t* in1, uint64_t* out) {
+#ifndef PDMP_EXTRA_KERNELS
+    (void)device, (void)fn, (void)nrows, (void)in0, (void)in1, (void)out;
+    return fail(PDMP_ERR_UNSUPPORTED, "pdmp_debug_wave_eval: the probe kernels live in the parity build (build.py --variant parity, -DPDMP_EXTRA_KERNELS)");
+#else
+    if (!in0 || !in1 || !out || nrows <= 0 || nrows > ((int64_t)1 << 20)) return fail(PDMP_ERR_INVALID, "bad argument");
+    decltype(&pdmp::launch_wave_eval_kernels) launch = nullptr;
+    switch (fn) {
+    case PDMP_WAVE_MIN_F64: case PDMP_WAVE_GRP8_MIN_F64: case PDMP_WAVE_ROW_MIN_F64: case PDMP_WAVE_MIN_U32: case PDMP_WAVE_MIN_U32_DPP:
+    case PDMP_WAVE_SCAN_ADD_U32: case PDMP_WAVE_SCAN_MIN_F64: case PDMP_WAVE_BPERM_F64: launch = pdmp::launch_wave_eval_kernels; break;
+    case PDMP_WAVE_SUM_F64: launch = pdmp::launch_wave_eval_bps; break;
+    case PDMP_WAVE_GRP8_MIN_U32: launch = pdmp::launch_wave_eval_trackp; break;
+    default: return fail(PDMP_ERR_INVALID, "pdmp_debug_wave_eval: unknown function id %d", fn);
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(PDMP_ERR_NO_DEVICE, "no HIP device visible");
+    HIP_TRY(hipSetDevice(device));
+    const size_t nw = (size_t)nrows * 64;
+    DevBuf<uint64_t> buf;  // in0, in1, out side by side
+    PDMP_TRY(buf.alloc(3 * nw));
+    HIP_TRY(hipMemcpy(buf.p, in0, nw * sizeof(uint64_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(buf.p + nw, in1, nw * sizeof(uint64_t), hipMemcpyHostToDevice));
+    LAUNCH_TRY("wave eval", launch(fn, nrows, buf.p, buf.p + nw, buf.p + 2 * nw, nullptr));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, buf.p + 2 * nw, nw * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return PDMP_OK;
+#endif
+}
+
+pdmp_status pdmp_debug_queue_eval(int device, int fn, int64_t n, const double* a, const double* b, const double* c, double* out) {
+#ifndef PDMP_EXTRA_KERNELS
+    (void)device, (void)fn, (void)n, (void)a, (void)b, (void)c, (void)out;
+    return fail(PDMP_ERR_UNSUPPORTED, "pdmp_debug_queue_eval: the probe kernels live in the parity build (build.py --variant parity, -DPDMP_EXTRA_KERNELS)");
+#else
+    if (!a || !b || !c || !out || n <= 0 || n > ((int64_t)1 << 30)) return fail(PDMP_ERR_INVALID, "bad argument");
+    decltype(&pdmp::launch_queue_eval_kernels) launch = nullptr;
+    switch (fn) {
+    case PDMP_QUEUE_P_ENC: case PDMP_QUEUE_P_THR: case PDMP_QUEUE_P_DEC: case PDMP_QUEUE_NB_HAS: case PDMP_QUEUE_NB_COUNT:
+        launch = pdmp::launch_queue_eval_trackp; break;
+    case PDMP_QUEUE_Q_ENC: case PDMP_QUEUE_Q_THR: case PDMP_QUEUE_Q_DEC: launch = pdmp::launch_queue_eval_exactp; break;
+    case PDMP_QUEUE_TL_Q: case PDMP_QUEUE_HB: launch = pdmp::launch_queue_eval_trackl; break;
+    case PDMP_QUEUE_BELOW: launch = pdmp::launch_queue_eval_kernels; break;
+    default: return fail(PDMP_ERR_INVALID, "pdmp_debug_queue_eval: unknown function id %d", fn);
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(PDMP_ERR_NO_DEVICE, "no HIP device visible");
+    HIP_TRY(hipSetDevice(device));
+    DevBuf<double> in, res;
+    PDMP_TRY(upload_abc(in, n, a, b, c));
+    PDMP_TRY(res.alloc((size_t)(2 * n)));
+    LAUNCH_TRY("queue eval", launch(fn, n, in.p, in.p + n, in.p + 2 * n, res.p, nullptr));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, res.p, (size_t)(2 * n) * sizeof(double), hipMemcpyDeviceToHost));
+    return PDMP_OK;
+#endif
+}
+
+pdmp_status pdmp_debug_state_eval(int device, int fn, int64_t nkeys, const double* keys, int64_t d, int has_refresh, int64_t nchg, const uint32_t* idx,
+                                  const double* val, double* out) {
+#ifndef PDMP_EXTRA_KERNELS
+    (void)device, (void)fn, (void)nkeys, (void)keys, (void)d, (void)has_refresh, (void)nchg, (void)idx, (void)val, (void)out;
+    return fail(PDMP_ERR_UNSUPPORTED, "pdmp_debug_state_eval: the probe kernels live in the parity build (build.py --variant parity, -DPDMP_EXTRA_KERNELS)");
+#else
+    if (!out || nchg < 0 || nchg > ((int64_t)1 << 20) || (nchg > 0 && (!idx || !val))) return fail(PDMP_ERR_INVALID, "bad argument");
+    if (fn != PDMP_STATE_WHEEL && fn != PDMP_STATE_LEVEL1 && fn != PDMP_STATE_S8_LEVEL1) return fail(PDMP_ERR_INVALID, "pdmp_debug_state_eval: unknown function id %d", fn);
+    const int64_t block = (fn == PDMP_STATE_LEVEL1) ? 64 : 32;
+    int64_t nout = 8192, limit = 8192;  // (the wheel: LL::NB2 blocks)
+    if (fn != PDMP_STATE_WHEEL) {
+        if (!keys || nkeys <= 0 || nkeys % block != 0 || nkeys / block > 512) return fail(PDMP_ERR_INVALID, "state eval: whole key blocks, at most 512 of them");
+        if (fn == PDMP_STATE_S8_LEVEL1 && has_refresh && (d < 0 || d >= nkeys)) return fail(PDMP_ERR_INVALID, "state eval: the refresh slot d lies inside the keys");
+        nout = 4 * ((fn == PDMP_STATE_LEVEL1) ? nkeys / 64 : 512) + 2 * nchg;
+        limit = nkeys;
+    }
+    for (int64_t k = 0; k < nchg; ++k) {  // every index stays inside its array; a wheel image has nine bits
+        if ((int64_t)idx[k] >= limit) return fail(PDMP_ERR_INVALID, "state eval: change %lld has index %u, the array has %lld entries", (long long)k, idx[k], (long long)limit);
+        if (fn == PDMP_STATE_WHEEL && !(val[k] >= 0.0 && val[k] < 512.0)) return fail(PDMP_ERR_INVALID, "state eval: a wheel image is 0 .. 511");
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(PDMP_ERR_NO_DEVICE, "no HIP device visible");
+    HIP_TRY(hipSetDevice(device));
+    DevBuf<double> dk, dv, res;
+    DevBuf<uint32_t> di;
+    PDMP_TRY(res.alloc((size_t)nout));
+    PDMP_TRY(dv.alloc((size_t)nchg + 1));
+    PDMP_TRY(di.alloc((size_t)nchg + 1));
+    if (nchg > 0) {
+        HIP_TRY(hipMemcpy(dv.p, val, (size_t)nchg * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(di.p, idx, (size_t)nchg * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    if (fn == PDMP_STATE_WHEEL) {
+        LAUNCH_TRY("wheel probe", pdmp::launch_wheel_probe(nchg, di.p, dv.p, res.p, nullptr));
+    } else {
+        PDMP_TRY(dk.alloc((size_t)nkeys));
+        HIP_TRY(hipMemcpy(dk.p, keys, (size_t)nkeys * sizeof(double), hipMemcpyHostToDevice));
+        LAUNCH_TRY("level-1 probe", pdmp::launch_level1_probe((int)block, dk.p, nkeys, d, has_refresh, nchg, di.p, dv.p, res.p, nullptr));
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, res.p, (size_t)nout * sizeof(double), hipMemcpyDeviceToHost));
+    return PDMP_OK;
+#endif
+}
 }  // extern "C"

@@ -747,6 +747,32 @@ PDMP_MATH_EVAL_DECL(logistic);
 PDMP_MATH_EVAL_DECL(trackl);
 PDMP_MATH_EVAL_DECL(exactp);
 PDMP_MATH_EVAL_DECL(logrows);
+// pdmp_debug_queue_eval: the same kernel and functor shape, one launcher per unit that owns a probed helper (ids PDMP_QUEUE_*)
+#define PDMP_QUEUE_EVAL_DECL(unit) int launch_queue_eval_##unit(int fn, int64_t n, const double* a, const double* b, const double* c, double* out, void* stream)
+PDMP_QUEUE_EVAL_DECL(kernels);
+PDMP_QUEUE_EVAL_DECL(trackp);
+PDMP_QUEUE_EVAL_DECL(trackl);
+PDMP_QUEUE_EVAL_DECL(exactp);
+// pdmp_debug_wave_eval: one 64-lane workgroup per row of 64 words; F{}(fn, w0, w1) makes the wave-level call of id fn with all 64 lanes active and
+// returns what this lane holds afterwards (fn is uniform, so the switch inside F is a uniform branch: the DPP moves see a full exec mask)
+template <class F>
+__global__ __launch_bounds__(64) void wave_eval_kernel(int fn, const uint64_t* in0, const uint64_t* in1, uint64_t* out) {
+    const size_t k = (size_t)blockIdx.x * 64 + threadIdx.x;
+    out[k] = F{}(fn, in0[k], in1[k]);
+}
+template <class F>
+int launch_wave_eval(int fn, int64_t nrows, const uint64_t* in0, const uint64_t* in1, uint64_t* out, void* stream) {
+    hipLaunchKernelGGL(wave_eval_kernel<F>, dim3((unsigned)nrows), dim3(64), 0, (hipStream_t)stream, fn, in0, in1, out);
+    return (int)hipGetLastError();
+}
+#define PDMP_WAVE_EVAL_DECL(unit) int launch_wave_eval_##unit(int fn, int64_t nrows, const uint64_t* in0, const uint64_t* in1, uint64_t* out, void* stream)
+PDMP_WAVE_EVAL_DECL(kernels);
+PDMP_WAVE_EVAL_DECL(bps);
+PDMP_WAVE_EVAL_DECL(trackp);
+// pdmp_debug_state_eval: one wavefront each (the arguments are those of the entry point; out is sized by the caller as pdmp_debug.h states)
+int launch_wheel_probe(int64_t nchg, const uint32_t* idx, const double* val, double* out, void* stream);
+int launch_level1_probe(int block, double* keys, int64_t nkeys, int64_t d, int has_refresh, int64_t nchg, const uint32_t* idx, const double* val, double* out,
+                        void* stream);
 #endif
 
 }  // namespace pdmp

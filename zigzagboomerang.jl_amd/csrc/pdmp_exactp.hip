@@ -47,10 +47,11 @@ __device__ __forceinline__ uint32_t q_enc(double key, double tb, uint32_t pos) {
     const uint32_t b = __float_as_uint((float)dlt);
     return (((b >= 16u) ? b - 16u : 0u) & ~15u) | pos;
 }
-__device__ __forceinline__ uint32_t q_thr(double tau, double tb) {  // the largest pattern a block with exact minimum <= tau can carry
+__device__ __forceinline__ uint32_t q_thr(double tau, double tb) {  // the largest pattern a block with exact minimum <= tau can carry -- or more, never less
     double dlt = tau - tb;
     dlt = (dlt > 0.0) ? dlt : 0.0;
-    return __float_as_uint((float)dlt) + 1u;
+    const uint32_t b = __float_as_uint((float)dlt) + 1u;
+    return (b > 15u) ? b : 15u;  // (a block AT the base carries its bare position bits, whatever tau is)
 }
 __device__ __forceinline__ double q_dec(uint32_t bits, double tb) {
     return pdmp_below(tb + (double)__uint_as_float(bits & ~15u));
@@ -876,6 +877,21 @@ struct ExactpMathEval {
 }  // namespace
 int launch_math_eval_exactp(int fn, int64_t n, const double* a, const double* b, const double* c, double* out, void* stream) {
     return launch_math_eval<ExactpMathEval>(fn, n, a, b, c, out, stream);
+}
+// pdmp_debug_queue_eval: this unit's own first-level code
+namespace {
+struct ExactpQueueEval {
+    __device__ double operator()(int fn, double a, double b, double c, double*) const {
+        switch (fn) {
+        case PDMP_QUEUE_Q_ENC: return (double)q_enc(a, b, (uint32_t)c);
+        case PDMP_QUEUE_Q_THR: return (double)q_thr(a, b);
+        default: return q_dec((uint32_t)a, b);  // PDMP_QUEUE_Q_DEC
+        }
+    }
+};
+}  // namespace
+int launch_queue_eval_exactp(int fn, int64_t n, const double* a, const double* b, const double* c, double* out, void* stream) {
+    return launch_math_eval<ExactpQueueEval>(fn, n, a, b, c, out, stream);
 }
 #endif
 

@@ -2864,6 +2864,90 @@ struct KernelsMathEval {
 int launch_math_eval_kernels(int fn, int64_t n, const double* a, const double* b, const double* c, double* out, void* stream) {
     return launch_math_eval<KernelsMathEval>(fn, n, a, b, c, out, stream);
 }
+
+// pdmp_debug_wave_eval / pdmp_debug_queue_eval / pdmp_debug_state_eval: the wave primitives and the two-level queue of pdmp_device.hpp and
+// pdmp_spec8_common.hpp, called as compiled here
+namespace {
+struct KernelsWaveEval {
+    __device__ uint64_t operator()(int fn, uint64_t w0, uint64_t w1) const {
+        const double v = pdmp_u2f(w0);
+        const uint32_t u = (uint32_t)w0;
+        switch (fn) {
+        case PDMP_WAVE_MIN_F64: return pdmp_f2u(wave_min_f64(v));
+        case PDMP_WAVE_GRP8_MIN_F64: return pdmp_f2u(grp8_min_f64(v));
+        case PDMP_WAVE_ROW_MIN_F64: return pdmp_f2u(row_min_f64(v));
+        case PDMP_WAVE_MIN_U32: return wave_min_u32(u);
+        case PDMP_WAVE_MIN_U32_DPP: return wave_min_u32_dpp(u);
+        case PDMP_WAVE_SCAN_ADD_U32: return scan_add_u32(u);
+        case PDMP_WAVE_SCAN_MIN_F64: return pdmp_f2u(scan_min_f64(v));
+        default: return pdmp_f2u(bperm_f64(v, (uint32_t)w1));  // PDMP_WAVE_BPERM_F64
+        }
+    }
+};
+struct KernelsQueueEval {
+    __device__ double operator()(int, double a, double, double, double*) const { return pdmp_below(a); }  // PDMP_QUEUE_BELOW
+};
+
+// BLOCK = 64: level1_build / level1_update; BLOCK = 32: s8_build_level1<true> / s8_level1_update.  One wavefront; nblk <= 512 and every idx[k] < nkeys
+// are the host's checks (pdmp_capi_debug.hip).  Writes out [4 x nout]: (bk, bi) after the build, (bk, bi) after the changes; behind them [nchg x 2]: the
+// entry of the changed key's block right after each update.
+template <int BLOCK>
+__global__ __launch_bounds__(64) void level1_probe_kernel(double* keys, uint32_t nblk, int64_t d, int has_refresh, int64_t nchg, const uint32_t* idx,
+                                                          const double* val, double* out) {
+    using Ix = std::conditional_t<BLOCK == 64, uint32_t, uint16_t>;
+    __shared__ double bk[S8_NBLK];
+    __shared__ Ix bi[S8_NBLK];
+    const int lane = threadIdx.x;
+    const uint32_t nout = (BLOCK == 64) ? nblk : S8_NBLK;
+    if constexpr (BLOCK == 64) {
+        level1_build(bk, bi, keys, nblk, lane);
+    } else {
+        s8_build_level1<true>(keys, bk, bi, nblk, d, has_refresh != 0, lane);
+    }
+    PDMP_LDS_ORDER();
+    if constexpr (BLOCK == 32) {  // (the slot of the refresh clock is parked at +Inf for the launch, as zz_local_spec8_kernel does after its build)
+        if (has_refresh && lane == 0) __hip_atomic_store(keys + d, PDMP_INF, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    for (uint32_t b = lane; b < nout; b += 64) {
+        out[b] = bk[b];
+        out[nout + b] = (double)bi[b];
+    }
+    for (int64_t k = 0; k < nchg; ++k) {
+        const uint32_t j = idx[k];
+        const double kj = val[k];
+        if (lane == 0) __hip_atomic_store(keys + j, kj, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __threadfence();  // (the rescan's other lanes read what lane 0 wrote)
+        if constexpr (BLOCK == 64) {
+            level1_update(bk, bi, keys, lane, j, kj);
+        } else {
+            s8_level1_update(bk, bi, keys, lane, j, kj);
+        }
+        PDMP_LDS_ORDER();
+        if (lane == 0) {
+            out[4 * nout + 2 * k] = bk[j / BLOCK];
+            out[4 * nout + 2 * k + 1] = (double)bi[j / BLOCK];
+        }
+    }
+    for (uint32_t b = lane; b < nout; b += 64) {
+        out[2 * nout + b] = bk[b];
+        out[3 * nout + b] = (double)bi[b];
+    }
+}
+}  // namespace
+int launch_wave_eval_kernels(int fn, int64_t nrows, const uint64_t* in0, const uint64_t* in1, uint64_t* out, void* stream) {
+    return launch_wave_eval<KernelsWaveEval>(fn, nrows, in0, in1, out, stream);
+}
+int launch_queue_eval_kernels(int fn, int64_t n, const double* a, const double* b, const double* c, double* out, void* stream) {
+    return launch_math_eval<KernelsQueueEval>(fn, n, a, b, c, out, stream);
+}
+int launch_level1_probe(int block, double* keys, int64_t nkeys, int64_t d, int has_refresh, int64_t nchg, const uint32_t* idx, const double* val, double* out,
+                        void* stream) {
+    if (block == 64)
+        hipLaunchKernelGGL(level1_probe_kernel<64>, dim3(1), dim3(64), 0, (hipStream_t)stream, keys, (uint32_t)(nkeys / 64), d, has_refresh, nchg, idx, val, out);
+    else
+        hipLaunchKernelGGL(level1_probe_kernel<32>, dim3(1), dim3(64), 0, (hipStream_t)stream, keys, (uint32_t)(nkeys / 32), d, has_refresh, nchg, idx, val, out);
+    return (int)hipGetLastError();
+}
 #endif
 
 // ------------------------------------------------------------------------------------------ launchers

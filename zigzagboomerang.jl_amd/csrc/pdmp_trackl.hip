@@ -1087,6 +1087,37 @@ struct TracklMathEval {
 int launch_math_eval_trackl(int fn, int64_t n, const double* a, const double* b, const double* c, double* out, void* stream) {
     return launch_math_eval<TracklMathEval>(fn, n, a, b, c, out, stream);
 }
+// pdmp_debug_queue_eval / pdmp_debug_state_eval: this unit's own wheel -- the quantum of a time, the place of a block's ninth bit, the images
+namespace {
+struct TracklQueueEval {
+    __device__ double operator()(int fn, double a, double b, double c, double* y1) const {
+        if (fn == PDMP_QUEUE_TL_Q) return (double)tl_q(a, b, c);
+        *y1 = (double)hb_bit((uint32_t)a);  // PDMP_QUEUE_HB
+        return (double)hb_word((uint32_t)a);
+    }
+};
+// One wavefront: clears the two planes, applies write k = img_set(idx[k], val[k]) in list order (lane k % 64 makes it: DS operations of a wave
+// execute in issue order), returns img_get of all LL::NB2 blocks.  idx[k] < LL::NB2 is the host's check (pdmp_capi_debug.hip) and is repeated here.
+__global__ __launch_bounds__(64) void wheel_probe_kernel(int64_t nchg, const uint32_t* idx, const double* val, double* out) {
+    __shared__ __align__(16) unsigned char smem[LL::BYTES];
+    const int lane = threadIdx.x;
+    for (uint32_t w = lane; w < (LL::EX - LL::IMG) / 4; w += 64) reinterpret_cast<uint32_t*>(smem + LL::IMG)[w] = 0u;  // IMG and HB are adjacent
+    PDMP_LDS_ORDER();
+    for (int64_t k = 0; k < nchg; ++k) {
+        const uint32_t b = idx[k];
+        if (lane == (int)(k & 63) && b < LL::NB2) img_set(smem, b, (uint32_t)val[k]);
+        PDMP_LDS_ORDER();
+    }
+    for (uint32_t b = lane; b < LL::NB2; b += 64) out[b] = (double)img_get(smem, b);
+}
+}  // namespace
+int launch_queue_eval_trackl(int fn, int64_t n, const double* a, const double* b, const double* c, double* out, void* stream) {
+    return launch_math_eval<TracklQueueEval>(fn, n, a, b, c, out, stream);
+}
+int launch_wheel_probe(int64_t nchg, const uint32_t* idx, const double* val, double* out, void* stream) {
+    hipLaunchKernelGGL(wheel_probe_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, nchg, idx, val, out);
+    return (int)hipGetLastError();
+}
 #endif
 
 }  // namespace pdmp

@@ -54,11 +54,12 @@ __device__ __forceinline__ uint32_t p_enc(double key, double tb, uint32_t pos) {
     const uint32_t b = __float_as_uint((float)dlt);
     return (((b >= 8u) ? b - 8u : 0u) & ~7u) | pos;
 }
-// the largest pattern a block with exact minimum <= tau can carry
+// the largest pattern a block with exact minimum <= tau can carry -- or more, never less
 __device__ __forceinline__ uint32_t p_thr(double tau, double tb) {
     double dlt = tau - tb;
     dlt = (dlt > 0.0) ? dlt : 0.0;
-    return __float_as_uint((float)dlt) + 1u;  // (one ulp above the nearest float; +Inf stays above every finite pattern)
+    const uint32_t b = __float_as_uint((float)dlt) + 1u;  // (one ulp above the nearest float; +Inf stays above every finite pattern)
+    return (b > 7u) ? b : 7u;  // (a block AT the base carries its bare position bits, whatever tau is: within 6 float quanta of the base they exceed b)
 }
 __device__ __forceinline__ double p_dec(uint32_t bits, double tb) {
     return pdmp_below(tb + (double)__uint_as_float(bits & ~7u));  // (one ulp below the rounded sum: never above the exact one)
@@ -1431,6 +1432,32 @@ struct TrackpMathEval {
 }  // namespace
 int launch_math_eval_trackp(int fn, int64_t n, const double* a, const double* b, const double* c, double* out, void* stream) {
     return launch_math_eval<TrackpMathEval>(fn, n, a, b, c, out, stream);
+}
+// pdmp_debug_wave_eval / pdmp_debug_queue_eval: this unit's own group minimum, first-level code and neighbour-id tests
+namespace {
+struct TrackpWaveEval {
+    __device__ uint64_t operator()(int, uint64_t w0, uint64_t) const { return w_grp8_min_u32((uint32_t)w0); }  // PDMP_WAVE_GRP8_MIN_U32
+};
+struct TrackpQueueEval {
+    __device__ double operator()(int fn, double a, double b, double c, double*) const {
+        const uint64_t ua = pdmp_f2u(a), ub = pdmp_f2u(b);
+        const uint4 nb = make_uint4((uint32_t)ua, (uint32_t)(ua >> 32), (uint32_t)ub, (uint32_t)(ub >> 32));
+        const uint32_t v = (uint32_t)c;
+        switch (fn) {
+        case PDMP_QUEUE_P_ENC: return (double)p_enc(a, b, v);
+        case PDMP_QUEUE_P_THR: return (double)p_thr(a, b);
+        case PDMP_QUEUE_P_DEC: return p_dec((uint32_t)a, b);
+        case PDMP_QUEUE_NB_HAS: return nb_has(nb, v | (v << 16)) ? 1.0 : 0.0;
+        default: return (double)nb_count(nb);  // PDMP_QUEUE_NB_COUNT
+        }
+    }
+};
+}  // namespace
+int launch_wave_eval_trackp(int fn, int64_t nrows, const uint64_t* in0, const uint64_t* in1, uint64_t* out, void* stream) {
+    return launch_wave_eval<TrackpWaveEval>(fn, nrows, in0, in1, out, stream);
+}
+int launch_queue_eval_trackp(int fn, int64_t n, const double* a, const double* b, const double* c, double* out, void* stream) {
+    return launch_math_eval<TrackpQueueEval>(fn, n, a, b, c, out, stream);
 }
 #endif
 
