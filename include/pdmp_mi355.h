@@ -736,6 +736,27 @@ pdmp_status pdmp_ensemble_bps_consume_pairs(pdmp_ensemble* ens, int64_t npairs, 
 pdmp_status pdmp_ensemble_bps_consume_pair_integrals(pdmp_ensemble* ens, int64_t chain_first, int64_t n, double* S, double* J, double* T_last,
                                                      void** S_dev);
 
+/* ------------------------------------------------------------------ pair integrals of arcs: covariance of a Boomerang path
+ *
+ * The same S_ij = ∫ (x_i − z_i)(x_j − z_j) dt and J_i = ∫ (x_i − z_i) dt over [t0, T_last] for the event-recorded Boomerang and the sticky
+ * Boomerang, whose pieces are arcs about the flow's μ (DESIGN.md "Pair integrals of arcs"; tests/ref/arc_pairs_ref.c states the contract
+ * sequentially and the device agrees with it bit for bit).  Plain double arithmetic, no fused multiply-add, pdmp_sincos of pdmp_detmath.h.
+ *   Per event (t_k, ...) with the cursor (t_c, x_c, θ_c, f_c) before it, τ = t_k − t_c signed; per coordinate  u = x_c − μ, p = θ_c, m = μ − z
+ *   (free) or u = 0, p = 0, m = x_c − z (not free), so that x(s) − z = u·cos s + p·sin s + m.  Once per piece:
+ *     (s, c) = pdmp_sincos(τ);  h = s·c
+ *     Icc = 0.5·(τ + h)   Iss = 0.5·(τ − h)   Isc = 0.5·(s·s)   Ic = s   Is = c > 0 ? (s·s)/(1.0 + c) : 1.0 − c
+ *     S_ij += (((ui·uj)·Icc + (pi·pj)·Iss) + (ui·pj + uj·pi)·Isc) + ((mi·(uj·Ic + pj·Is) + mj·(ui·Ic + pi·Is)) + (mi·mj)·τ)
+ *     J_i  += (u·Ic + p·Is) + m·τ
+ *   Symmetric in (i, j) bit for bit.  A τ outside pdmp_sincos's domain (|τ| > 2^30) yields NaN, as the grid rows of discretize do.  Nothing is
+ *   added behind the last event.
+ *   bps_consume_arc_pairs(npairs, pi, pj, center)   position, arguments, memory and PDMP_ERR_INVALID cases of bps_consume_pairs; center = z.
+ *     Without this call nothing changes: no allocation, no kernel.  Coexists with the mean, cummean, the grid and the sticky free-time fractions.
+ *   pdmp_ensemble_bps_consume_pair_integrals reads the result (a copy: nothing of it depends on the flow).
+ * PDMP_ERR_UNSUPPORTED: a flow that is not a Boomerang (pdmp_ensemble_bps_consume_pairs is the call for lines), the speed-recorded flow,
+ * subsample, a second pair list on one ensemble.
+ */
+pdmp_status pdmp_ensemble_bps_consume_arc_pairs(pdmp_ensemble* ens, int64_t npairs, const int64_t* pi, const int64_t* pj, const double* center);
+
 /* ------------------------------------------------------------------ marginal histograms on the device: occupation times of a sampled path
  *
  * The time each of m listed coordinates spends in each of `bins` bins of its own range [lo_s, hi_s), below the range and at or above it: the

@@ -167,6 +167,19 @@ struct Options {  // the reference's keyword arguments
     double consume_dt = 0.0;
     int64_t consume_points = 0;
     bool consume_only = false;  // ... and copy no event to the host: Result::trace.events stays empty (the Python mirror's trace=False)
+    // pdmp on a BouncyParticle (event-recorded) or a Boomerang, engine-only: with consume and a pair list -- the Python mirror's
+    // consume=dict(cov=(pi, pj), center=c) -- every slice also adds to the exact path integrals S_k = ∫ (x_i − c_i)(x_j − c_j) dt of the pairs
+    // (cov_pi[k], cov_pj[k]) and J_i = ∫ (x_i − c_i) dt (pdmp_ensemble_bps_consume_pairs; a Boomerang's pieces are arcs:
+    // pdmp_ensemble_bps_consume_arc_pairs), returned in Result::pairs.  cov_center: empty = 0
+    std::vector<int64_t> cov_pi, cov_pj;
+    std::vector<double> cov_center;
+};
+
+// What Options::consume with a pair list returns: S [npairs] in the order of the list, J [d], and the last event time T; with L = T − t0
+// cov_ij = S_ij / L − (J_i / L)(J_j / L) and mean_i = J_i / L + c_i
+struct PairIntegrals {
+    std::vector<double> S, J;
+    double T = 0.0;
 };
 
 // What the device consumers of a stickyzz run return (Options::consume): mean(Ξ) [d] and the last event time T; the rows of
@@ -215,6 +228,7 @@ struct Result {  // Ξ, (t, x, θ), (acc, num), c
     std::vector<uint8_t> frozen;
     std::vector<double> theta_saved;
     BarrierConsumed consumed;  // stickyzz with Options::consume
+    PairIntegrals pairs;       // pdmp on a BouncyParticle / Boomerang with Options::consume and cov_pi, cov_pj
 };
 
 // RAII handle on pdmp_ensemble
@@ -415,18 +429,27 @@ Result<FactTrace> factorised(int sampler, const Target& target, double t0, const
 }
 
 inline Result<PDMPTrace> not_factorised(Ensemble& e, double t0, const std::vector<double>& x0, const std::vector<double>& theta0,
-                                        double T, double c, const Options& o) {
+                                        double T, double c, const Options& o, bool arcs = false) {
     const int64_t d = (int64_t)x0.size();
     const uint64_t seed = o.seed;
     check(pdmp_ensemble_set_state_bps(e.get(), t0, x0.data(), theta0.data(), c, &seed));
+    const bool pairs = o.consume && !o.cov_pi.empty();
+    if (pairs) {
+        if (o.cov_pi.size() != o.cov_pj.size()) throw std::invalid_argument("Options::cov_pi and cov_pj have one entry per pair");
+        if (!o.cov_center.empty() && (int64_t)o.cov_center.size() != d) throw std::invalid_argument("Options::cov_center needs d entries");
+        check(pdmp_ensemble_bps_consume_begin(e.get(), 0.0, 0));
+        check((arcs ? pdmp_ensemble_bps_consume_arc_pairs : pdmp_ensemble_bps_consume_pairs)(e.get(), (int64_t)o.cov_pi.size(), o.cov_pi.data(),
+                                                                                            o.cov_pj.data(), opt(o.cov_center)));
+    }
     Result<PDMPTrace> R;
     R.trace.t0 = t0;
     R.trace.d = d;
     R.trace.x0 = x0;
     R.trace.theta0 = theta0;
     auto cnt = e.run_and_drain(T, [&](const std::vector<pdmp_chain_counters>& k) {
+        if (pairs) check(pdmp_ensemble_bps_consume(e.get()));  // (every slice, before its buffer is recycled)
         const int64_t m = (int64_t)k[0].ntrace;
-        if (m > 0) {
+        if (m > 0 && !(pairs && o.consume_only)) {
             const size_t old = R.trace.t.size();
             R.trace.t.resize(old + (size_t)m);
             R.trace.x.resize((old + (size_t)m) * (size_t)d);
@@ -443,6 +466,11 @@ inline Result<PDMPTrace> not_factorised(Ensemble& e, double t0, const std::vecto
     check(pdmp_ensemble_bps_final_state(e.get(), 0, 1, R.t.data(), R.x.data(), R.theta.data(), R.c.data()));
     R.acc.assign(1, (int64_t)cnt[0].nacc);
     R.num = (int64_t)cnt[0].num;
+    if (pairs) {
+        R.pairs.S.resize(o.cov_pi.size());
+        R.pairs.J.resize((size_t)d);
+        check(pdmp_ensemble_bps_consume_pair_integrals(e.get(), 0, 1, R.pairs.S.data(), R.pairs.J.data(), &R.pairs.T, nullptr));
+    }
     return R;
 }
 }  // namespace detail
@@ -561,7 +589,7 @@ inline Result<PDMPTrace> pdmp(const GaussianTarget& target, double t0, const std
         check(pdmp_ensemble_set_mass_cholesky(e.get(), cp.data(), rv.data(), nz.data()));
     }
     if (o.subsample) check(pdmp_ensemble_set_bps_options(e.get(), 0, 1));
-    return detail::not_factorised(e, t0, x0, theta0, T, c, o);
+    return detail::not_factorised(e, t0, x0, theta0, T, c, o, true);  // (a pair list of Options::consume integrates arcs about B.mu)
 }
 
 // pdmp(dϕ, ∇ϕ!, t0, x0, θ0, T, c::LocalBound, flow::BouncyParticle; oscn, adapt, factor=2.0)  -- src/not_fact_samplers.jl:336-384, the

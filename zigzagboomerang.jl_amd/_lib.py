@@ -58,6 +58,7 @@ EXPORTED_SYMBOLS = [
     "pdmp_ensemble_bps_consume_discretized", "pdmp_ensemble_bps_consume_cummean", "pdmp_ensemble_bps_consume_cummean_copy",
     "pdmp_ensemble_consume_condition", "pdmp_ensemble_consume_conditioned", "pdmp_ensemble_bps_consume_condition", "pdmp_ensemble_bps_consume_conditioned",
     "pdmp_ensemble_consume_pairs", "pdmp_ensemble_consume_pair_integrals", "pdmp_ensemble_bps_consume_pairs", "pdmp_ensemble_bps_consume_pair_integrals",
+    "pdmp_ensemble_bps_consume_arc_pairs",
     "pdmp_ensemble_consume_hist", "pdmp_ensemble_consume_histogram", "pdmp_ensemble_bps_consume_hist", "pdmp_ensemble_bps_consume_histogram",
     "pdmp_comm_unique_id", "pdmp_comm_init", "pdmp_comm_destroy", "pdmp_comm_info", "pdmp_comm_barrier", "pdmp_comm_allreduce",
     "pdmp_ensemble_gather_traces", "pdmp_ensemble_reduce_moments", "pdmp_comm_gathered_copy",
@@ -162,7 +163,7 @@ def load():
         getattr(L, name).argtypes = [vp, vp, vp, i64]
     for name in ("pdmp_ensemble_consume_conditioned", "pdmp_ensemble_bps_consume_conditioned"):
         getattr(L, name).argtypes = [vp, i64, i64, i64, vp, vp, C.POINTER(i64), C.POINTER(vp)]
-    for name in ("pdmp_ensemble_consume_pairs", "pdmp_ensemble_bps_consume_pairs"):
+    for name in ("pdmp_ensemble_consume_pairs", "pdmp_ensemble_bps_consume_pairs", "pdmp_ensemble_bps_consume_arc_pairs"):
         getattr(L, name).argtypes = [vp, i64, vp, vp, vp]
     for name in ("pdmp_ensemble_consume_pair_integrals", "pdmp_ensemble_bps_consume_pair_integrals"):
         getattr(L, name).argtypes = [vp, i64, i64, vp, vp, vp, C.POINTER(vp)]

@@ -123,8 +123,8 @@ pdmp_status pdmp_ensemble_bps_consume_begin(pdmp_ensemble* e, double grid_dt, in
     e->bc_cummean = false;
     e->bcn_on = e->bc_started = false;
     e->bcn_tau.release(), e->bcn_t.release(), e->bcn_x.release(), e->bcn_pn.release(), e->bcn_nh.release();
-    e->bpr_on = false;
-    e->bpr_pi.release(), e->bpr_pj.release(), e->bpr_c.release(), e->bpr_S.release(), e->bpr_J.release(), e->bpr_T.release();
+    e->bpr_on = e->bpr_arc = false;
+    e->bpr_pi.release(),e->bpr_pj.release(), e->bpr_c.release(), e->bpr_S.release(), e->bpr_J.release(), e->bpr_T.release();
     e->bhs_on = false;
     e->bhs_coords.release(), e->bhs_lo.release(), e->bhs_hi.release(), e->bhs_w.release(), e->bhs_H.release(), e->bhs_Z.release(), e->bhs_out.release();
     e->bc_dt = grid_dt;
@@ -146,7 +146,9 @@ pdmp_status pdmp_ensemble_bps_consume(pdmp_ensemble* e) {
     HIP_TRY(hipEventRecord(e->ev_c0, e->stream));
     if (e->bcn_on)  // (before the consumer: it reads the cursors and the progress the consumer is about to advance)
         LAUNCH_TRY("bps_consume_condition", pdmp::launch_bps_cond(consume_args(e), cond_args(e), e->stream));
-    if (e->bpr_on)  // (before the consumer, like the condition: it reads the cursors and the progress the consumer is about to advance)
+    if (e->bpr_on && e->bpr_arc)  // (before the consumer, like the condition: it reads the cursors and the progress the consumer is about to advance)
+        LAUNCH_TRY("bps_consume_arc_pairs", pdmp::launch_bps_arc_pairs(consume_args(e), pair_args(e), e->stream));
+    else if (e->bpr_on)
         LAUNCH_TRY("bps_consume_pairs", pdmp::launch_bps_pairs(consume_args(e), pair_args(e), e->stream));
     if (e->bhs_on)  // (before the consumer too, for the same reason)
         LAUNCH_TRY("bps_consume_hist", pdmp::launch_bps_hist(consume_args(e), hist_args(e), e->stream));
@@ -280,7 +282,8 @@ pdmp_status pdmp_ensemble_bps_consume_conditioned(pdmp_ensemble* e, int64_t chai
 pdmp_status pdmp_ensemble_bps_consume_pairs(pdmp_ensemble* e, int64_t npairs, const int64_t* pi, const int64_t* pj, const double* center) {
     PDMP_TRY(need_bps(e, __func__));
     if (e->bps.flow_kind == 1)
-        return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_pairs: on a Boomerang flow the product of two rotations is another integral than that of two lines");
+        return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_pairs: on a Boomerang flow the product of two rotations is another integral than that of two lines "
+                                          "(pdmp_ensemble_bps_consume_arc_pairs keeps that one)");
     if (e->bps.modern)
         return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_pairs: the records of the speed-recorded flow are not the corners of the path (a straight line "
                                           "between two of them is not the path)");
@@ -306,6 +309,42 @@ pdmp_status pdmp_ensemble_bps_consume_pairs(pdmp_ensemble* e, int64_t npairs, co
     HIP_TRY(hipMemsetAsync(e->bpr_J.p, 0, (size_t)(nch * d) * sizeof(double), e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->bpr_np = npairs;
+    e->bpr_on = true;
+    return PDMP_OK;
+}
+
+// the same integrals on a Boomerang flow (DESIGN.md "Pair integrals of arcs"): between two events a coordinate is an arc about μ, a pair's piece a
+// combination of five trigonometric integrals.  Same position, list and accumulators as bps_consume_pairs; bps_consume_pair_integrals reads them.
+pdmp_status pdmp_ensemble_bps_consume_arc_pairs(pdmp_ensemble* e, int64_t npairs, const int64_t* pi, const int64_t* pj, const double* center) {
+    PDMP_TRY(need_bps(e, __func__));
+    if (e->bps.modern)
+        return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_arc_pairs: the records of the speed-recorded flow are not the corners of the path");
+    if (e->bps.flow_kind != 1)
+        return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_arc_pairs: the pieces of this flow are lines, not the arcs of a Boomerang "
+                                          "(pdmp_ensemble_bps_consume_pairs keeps their integrals)");
+    if (e->bps.subsample)
+        return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_arc_pairs: with subsample the records are not the corners of the path (an arc between two of "
+                                          "them is not the path)");
+    PDMP_TRY(need_begun(e, __func__));
+    if (e->bc_started) return fail(PDMP_ERR_INVALID, "bps_consume_arc_pairs precedes the first bps_consume (its first piece starts from t0, x0, θ0)");
+    if (e->bpr_on) return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_arc_pairs: the ensemble already keeps a pair list (one list per bps_consume_begin)");
+    const int64_t d = e->cfg.d, nch = e->cfg.nchains;
+    std::vector<int32_t> vi, vj;
+    std::vector<double> c;
+    PDMP_TRY(pairs_list("bps_consume_arc_pairs", nch, d, npairs, pi, pj, center, &vi, &vj, &c));
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(device_sync(e));
+    PDMP_TRY(e->bpr_pi.upload(vi));
+    PDMP_TRY(e->bpr_pj.upload(vj));
+    PDMP_TRY(e->bpr_c.upload(c));
+    PDMP_TRY(e->bpr_S.alloc((size_t)(nch * npairs)));
+    PDMP_TRY(e->bpr_J.alloc((size_t)(nch * d)));
+    PDMP_TRY(e->bpr_T.alloc((size_t)nch));
+    HIP_TRY(hipMemsetAsync(e->bpr_S.p, 0, (size_t)(nch * npairs) * sizeof(double), e->stream));
+    HIP_TRY(hipMemsetAsync(e->bpr_J.p, 0, (size_t)(nch * d) * sizeof(double), e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->bpr_np = npairs;
+    e->bpr_arc = true;
     e->bpr_on = true;
     return PDMP_OK;
 }

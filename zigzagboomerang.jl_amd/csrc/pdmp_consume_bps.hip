@@ -399,6 +399,93 @@ int launch_bps_pairs_tlast(const BpsConsumeArgs& p, int64_t chain_first, int64_t
     return (int)hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------ pair integrals of arcs (covariance of a Boomerang's trace)
+//
+// The same S_ij and J_i over [t0, T_last] for the event-recorded Boomerang and its sticky form (DESIGN.md "Pair integrals of arcs";
+// tests/ref/arc_pairs_ref.c states the contract).  Between two events a free coordinate rotates about μ: on the piece [t_c, t_k] of an event,
+// x(s) − z = u·cos s + p·sin s + m with u = x_c − μ, p = θ_c, m = μ − z -- a coordinate that is not free: u = p = 0, m = x_c − z --, so a pair's
+// piece is a combination of the five integrals of cos², sin², sin·cos, cos and sin over [0, τ], τ = t_k − t_c signed.  τ is wave-uniform (the
+// threads of a workgroup belong to one chain): every thread evaluates pdmp_sincos(τ) and the five integrals once per event, without divergence,
+// before its pair arithmetic.  The walk, the loads and the accumulators are those of bps_pairs_kernel; runs BEFORE bps_consume_kernel of the
+// same slice and only reads what that kernel carries.
+struct ArcBasis {
+    double Icc, Iss, Isc, Ic, Is;
+};
+
+__device__ __forceinline__ ArcBasis arc_basis_of(double tau) {
+    double s, c;
+    pdmp_sincos(tau, &s, &c);
+    const double h = s * c;
+    ArcBasis b;
+    b.Icc = 0.5 * (tau + h);
+    b.Iss = 0.5 * (tau - h);
+    b.Isc = 0.5 * (s * s);
+    b.Ic = s;
+    b.Is = c > 0 ? (s * s) / (1.0 + c) : 1.0 - c;  // (1 − cos τ without its cancellation at small τ)
+    return b;
+}
+
+// symmetric in (i, j) bit for bit: every product commutes, and each sum of two products is one commutative addition
+__device__ __forceinline__ double arc_pair_piece(double ui, double pi, double mi, double uj, double pj, double mj, double tau, const ArcBasis& b) {
+    return (((ui * uj) * b.Icc + (pi * pj) * b.Iss) + (ui * pj + uj * pi) * b.Isc) +
+           ((mi * (uj * b.Ic + pj * b.Is) + mj * (ui * b.Ic + pi * b.Is)) + (mi * mj) * tau);
+}
+__device__ __forceinline__ double arc_line_piece(double u, double p, double m, double tau, const ArcBasis& b) { return (u * b.Ic + p * b.Is) + m * tau; }
+
+template <bool STICKY>
+__global__ __launch_bounds__(256) void bps_arc_pairs_kernel(BpsConsumeArgs P, BpsPairArgs Q, int64_t blocks_per_chain) {
+    const int64_t chain = (int64_t)blockIdx.x / blocks_per_chain;
+    const int64_t r = ((int64_t)blockIdx.x - chain * blocks_per_chain) * 256 + threadIdx.x;
+    const int64_t d = P.d;
+    if (r >= Q.npairs + d) return;
+    const BpsCondSlice sl = bps_cond_slice(P, chain);
+    if (sl.pos >= sl.n) return;
+    const bool is_pair = r < Q.npairs;
+    const int64_t i = is_pair ? Q.pi[r] : r - Q.npairs, j = is_pair ? Q.pj[r] : i;
+    double* const acc_at = is_pair ? Q.S + chain * Q.npairs + r : Q.J + chain * d + i;
+    const BpsConsumeMeta* const meta = static_cast<const BpsConsumeMeta*>(P.meta) + chain * P.nstrips;
+    const int64_t slot0 = chain * P.cap;
+    const double mui = P.mu[i], muj = P.mu[j], zi = Q.center[i], zj = Q.center[j];
+    double acc = *acc_at, t_cur = sl.t_cur;
+    double xi = P.cx[chain * d + i], thi = P.cth[chain * d + i], xj = P.cx[chain * d + j], thj = P.cth[chain * d + j];
+    bool fi = STICKY ? ((meta[i >> 6].free >> (i & 63)) & 1ull) != 0 : true, fj = STICKY ? ((meta[j >> 6].free >> (j & 63)) & 1ull) != 0 : true;
+
+    BpsPairEvent now[BC_AHEAD], next[BC_AHEAD];
+#pragma unroll
+    for (int q = 0; q < BC_AHEAD; ++q) now[q] = bp_load<STICKY>(P, slot0, sl.pos + q, sl.n, i, j);
+    for (uint64_t base = sl.pos; base < sl.n; base += BC_AHEAD) {
+#pragma unroll
+        for (int q = 0; q < BC_AHEAD; ++q) next[q] = bp_load<STICKY>(P, slot0, base + BC_AHEAD + q, sl.n, i, j);
+#pragma unroll
+        for (int q = 0; q < BC_AHEAD; ++q) {
+            if (base + q >= sl.n) break;
+            const double tau = now[q].t - t_cur;
+            const ArcBasis b = arc_basis_of(tau);
+            const double ui = fi ? xi - mui : 0.0, pi = fi ? thi : 0.0, mi = fi ? mui - zi : xi - zi;
+            const double uj = fj ? xj - muj : 0.0, pj = fj ? thj : 0.0, mj = fj ? muj - zj : xj - zj;
+            acc = acc + (is_pair ? arc_pair_piece(ui, pi, mi, uj, pj, mj, tau, b) : arc_line_piece(ui, pi, mi, tau, b));
+            xi = now[q].xi;
+            thi = now[q].thi;
+            xj = now[q].xj;
+            thj = now[q].thj;
+            fi = now[q].fi;
+            fj = now[q].fj;
+            t_cur = now[q].t;
+        }
+#pragma unroll
+        for (int q = 0; q < BC_AHEAD; ++q) now[q] = next[q];
+    }
+    *acc_at = acc;
+}
+
+int launch_bps_arc_pairs(const BpsConsumeArgs& p, const BpsPairArgs& q, void* stream) {
+    const int64_t bpc = (q.npairs + p.d + 255) / 256;
+    const dim3 grid((unsigned)(p.nchains * bpc)), block(256);
+    if (p.ev_f) hipLaunchKernelGGL((bps_arc_pairs_kernel<true>), grid, block, 0, (hipStream_t)stream, p, q, bpc);
+    else hipLaunchKernelGGL((bps_arc_pairs_kernel<false>), grid, block, 0, (hipStream_t)stream, p, q, bpc);
+    return (int)hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------ marginal histograms (occupation times of a PDMPTrace)
 //
 // H[s][k + 1] = the time listed coordinate s spends in the bin [e_k, e_k+1) of its own range over [t0, T_last], exactly (DESIGN.md "Marginal

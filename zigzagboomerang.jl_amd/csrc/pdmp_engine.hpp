@@ -705,6 +705,8 @@ struct BpsPairArgs {
 };
 int launch_bps_pairs(const BpsConsumeArgs& p, const BpsPairArgs& q, void* stream);
 int launch_bps_pairs_tlast(const BpsConsumeArgs& p, int64_t chain_first, int64_t n, double* T_out, void* stream);
+// ... the same integrals of a Boomerang's arcs (pdmp_ensemble_bps_consume_arc_pairs; p.mu is the flow's centre): the same arguments and accumulators
+int launch_bps_arc_pairs(const BpsConsumeArgs& p, const BpsPairArgs& q, void* stream);
 // ... the marginal histograms (pdmp_ensemble_bps_consume_hist): the listed coordinates [m] with their ranges and widths, the rows H
 // [nchains x m x (B + 2)] and the rest times Z [nchains x m]; launched before launch_bps_consume_events of the same slice
 struct BpsHistArgs {

@@ -323,6 +323,7 @@ struct pdmp_ensemble {
     DevBuf<int32_t> bpr_pi, bpr_pj;
     DevBuf<double> bpr_c, bpr_S, bpr_J, bpr_T;
     bool bpr_on = false;
+    bool bpr_arc = false;  // the list came by pdmp_ensemble_bps_consume_arc_pairs: a Boomerang's pieces are arcs
     int64_t bpr_np = 0;
 
     // pdmp_ensemble_bps_consume_hist: the listed coordinates with their ranges and widths [m], H [nchains x m x (bins + 2)], Z [nchains x m];

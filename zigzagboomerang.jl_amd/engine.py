@@ -649,6 +649,12 @@ class Ensemble:
         the first bps_consume()."""
         self._pairs(self._L.pdmp_ensemble_bps_consume_pairs, pi, pj, center)
 
+    def bps_consume_arc_pairs(self, pi, pj, center=None):
+        """bps_consume_pairs for the event-recorded Boomerang and the sticky Boomerang, whose pieces are arcs about the flow's μ: after
+        bps_consume_begin and before the first bps_consume(); bps_consume_pair_integrals reads the result (trace.arc_pair_integrals is the host
+        mirror, trace.covariance what follows)."""
+        self._pairs(self._L.pdmp_ensemble_bps_consume_arc_pairs, pi, pj, center)
+
     def bps_consume_pair_integrals(self, chain_first=0, n=None):
         """consume_pair_integrals for the Bouncy Particle family: the integrals over [t0, T_last] exactly."""
         return self._pair_integrals(self._L.pdmp_ensemble_bps_consume_pair_integrals, chain_first, n)

@@ -277,7 +277,9 @@ def _pdmp_nd(target, t0, x0, θ0, T, c, F, *, factor=1.8, adapt=False, subsample
     earlier elements are bit for bit those without the keyword.  With trace=False the events are still written to the device buffer and
     consumed, but never copied to the host; trace_capacity=0 raises.  With condition=(p, n), hits=K in the dict (event-recorded
     BouncyParticle and its sticky form) the element also holds hit_t, hit_x -- trace.conditional_trace(Ξ, p, n), at most K rows per chain --
-    and nhits, the number of hits found (above K: the later ones were dropped).
+    and nhits, the number of hits found (above K: the later ones were dropped).  With cov=P[, center=c] it holds pairs, pair_S and pair_J,
+    what trace.covariance takes: of lines on a BouncyParticle (trace.pair_integrals), of arcs about μ on a Boomerang
+    (trace.arc_pair_integrals), sticky forms included.
 
     pdmp(dϕ, ∇ϕ!, t0, x0, θ0, T, c::LocalBound, B::BouncyParticle; oscn=false, adapt=false, factor=2.0) (src/not_fact_samplers.jl:336-384),
     the speed-recorded driver: B.Γ is None (BouncyParticle(None, None, λref, ρ, L=..., U=...)), target is a GaussianTarget or a
@@ -761,8 +763,8 @@ def _bps(t0, x0, θ0, T, c, B, factor, adapt, seed, device, trace_capacity, trac
             ens.bps_consume_begin(consume.get("dt", 0.0), consume.get("points", 0))
             if _condition_of(consume) is not None:
                 ens.bps_consume_condition(*_condition_of(consume))
-            if _pairs_of(consume, ens.d) is not None:
-                ens.bps_consume_pairs(*_pairs_of(consume, ens.d))
+            if _pairs_of(consume, ens.d) is not None:  # (a Boomerang's pieces are arcs: another integral, the same accumulators)
+                (ens.bps_consume_arc_pairs if isinstance(B, Boomerang) else ens.bps_consume_pairs)(*_pairs_of(consume, ens.d))
             if _hist_of(consume, ens.d) is not None:
                 ens.bps_consume_hist(*_hist_of(consume, ens.d))
         fs_ = [[] for _ in range(nch)]

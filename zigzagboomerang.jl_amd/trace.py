@@ -604,6 +604,85 @@ def pair_integrals(tr, pi, pj, center=None):
     return _pairs_fact(tr, pi, pj, c)
 
 
+_H = float.fromhex
+_SIN_POLY = [_H(v) for v in ("-0x1.5555555555549p-3", "0x1.111111110f8a6p-7", "-0x1.a01a019c161d5p-13", "0x1.71de357b1fe7dp-19",
+                             "-0x1.ae5e68a2b9cebp-26", "0x1.5d93a5acfd57cp-33")]
+_COS_POLY = [_H(v) for v in ("0x1.555555555554cp-5", "-0x1.6c16c16c15177p-10", "0x1.a01a019cb1590p-16", "-0x1.27e4f809c52adp-22",
+                             "0x1.1ee9ebdb4b1c4p-29", "-0x1.8fae9be8838d4p-37")]
+_PIO2 = [_H(v) for v in ("0x1.921fb54400000p+0", "0x1.0b4611a600000p-34", "0x1.3198a2e000000p-69", "0x1.b839a252049c1p-104")]
+_INVPIO2 = _H("0x1.45f306dc9c883p-1")
+
+
+def _pdmp_sincos(x):
+    """(sin x, cos x) as pdmp_sincos of include/pdmp_detmath.h computes them, bit for bit (every operation below is one correctly rounded
+    double operation of that function, in its order): the Cody-Waite reduction by π/2 in three 33-bit pieces and a tail, then the two
+    polynomial kernels.  NaN beyond |x| <= 2^30 and for a non-finite x.  Vectorised over x."""
+    x = np.asarray(x, dtype=np.float64)
+    ok = np.abs(x) <= 2.0 ** 30  # (False for NaN)
+    xs = np.where(ok, x, 0.0)
+    n = np.trunc(xs * _INVPIO2 + np.where(xs < 0, -0.5, 0.5)).astype(np.int64)
+    nl = np.fmod(n, 0x100000)  # (the sign of n, as C's %)
+    fn, fnh, fnl = n.astype(np.float64), (n - nl).astype(np.float64), nl.astype(np.float64)
+    r = xs - fnh * _PIO2[0]
+    r = r - fnl * _PIO2[0]
+    r = r - fnh * _PIO2[1]
+    r = r - fnl * _PIO2[1]
+    r = r - fnh * _PIO2[2]
+    r = r - fnl * _PIO2[2]
+    r = r - fn * _PIO2[3]
+    z = r * r
+    S1, S2, S3, S4, S5, S6 = _SIN_POLY
+    sr = r + (z * r) * (S1 + z * (S2 + z * (S3 + z * (S4 + z * (S5 + z * S6)))))
+    C1, C2, C3, C4, C5, C6 = _COS_POLY
+    cr = (1.0 - 0.5 * z) + z * (z * (C1 + z * (C2 + z * (C3 + z * (C4 + z * (C5 + z * C6))))))
+    q = n & 3
+    s = np.select([q == 0, q == 1, q == 2], [sr, cr, -sr], -cr)
+    c = np.select([q == 0, q == 1, q == 2], [cr, -sr, -cr], sr)
+    return np.where(ok, s, np.nan), np.where(ok, c, np.nan)
+
+
+def _seq_sum_columns(P):
+    """_seq_sum of every column of P [m x k]"""
+    return np.cumsum(np.vstack([np.zeros((1, P.shape[1])), P]), axis=0)[-1]
+
+
+def arc_pair_integrals(tr, pi, pj, center=None):
+    """(S [npairs], J [d], T_last) as pair_integrals, for the PDMPTrace of a Boomerang, sticky or not: between two events a free coordinate
+    rotates about F.μ, x(s) − z = u·cos s + p·sin s + m with u = x_c − μ, p = θ_c, m = μ − z (a coordinate that is not free: u = p = 0,
+    m = x_c − z), and a pair's piece is a combination of the integrals of cos², sin², sin·cos, cos and sin over the piece.  The host mirror of
+    Ensemble.bps_consume_arc_pairs, bit for bit the sequential statement tests/ref/arc_pairs_ref.c (DESIGN.md "Pair integrals of arcs").  Any
+    other trace: TypeError (pair_integrals takes the straight-line flows)."""
+    if not (isinstance(tr, PDMPTrace) and isinstance(tr.F, Boomerang)):
+        raise TypeError("arc_pair_integrals: the PDMPTrace of a Boomerang (pair_integrals takes the traces of the straight-line flows)")
+    d = len(tr.x0)
+    pi, pj, z = _pair_list(d, pi, pj, center)
+    t = np.asarray(tr.t, dtype=np.float64).reshape(-1)
+    m = len(t)
+    T_last = float(t[-1]) if m else float(tr.t0)
+    mu = np.asarray(tr.F.μ, dtype=np.float64).reshape(-1)
+    tc = np.concatenate([[tr.t0], t[:-1]])[:m]
+    Xc = np.vstack([np.asarray(tr.x0, dtype=np.float64)[None], np.asarray(tr.x, dtype=np.float64).reshape(-1, d)[:-1]])[:m]
+    Pc = np.vstack([np.asarray(tr.θ0, dtype=np.float64)[None], np.asarray(tr.θ, dtype=np.float64).reshape(-1, d)[:-1]])[:m]
+    U, M = Xc - mu[None], np.broadcast_to((mu - z)[None], Xc.shape)
+    if tr.f is not None:  # a coordinate that is not free stays where it is
+        f0 = np.ones(d, dtype=bool) if tr.f0 is None else np.asarray(tr.f0, dtype=bool)
+        Fm = np.vstack([f0[None], np.asarray(tr.f, dtype=bool).reshape(-1, d)[:-1]])[:m]
+        U, Pc, M = np.where(Fm, U, 0.0), np.where(Fm, Pc, 0.0), np.where(Fm, M, Xc - z[None])
+    tau = t - tc
+    s, c = _pdmp_sincos(tau)
+    h = s * c
+    Icc, Iss, Isc, Ic = 0.5 * (tau + h), 0.5 * (tau - h), 0.5 * (s * s), s
+    with np.errstate(divide="ignore", invalid="ignore"):
+        Is = np.where(c > 0, (s * s) / (1.0 + c), 1.0 - c)
+    G = U * Ic[:, None] + Pc * Is[:, None]
+    S = np.empty(len(pi))
+    for k, (i, j) in enumerate(zip(pi, pj)):
+        S[k] = _seq_sum((((U[:, i] * U[:, j]) * Icc + (Pc[:, i] * Pc[:, j]) * Iss) + (U[:, i] * Pc[:, j] + U[:, j] * Pc[:, i]) * Isc)
+                        + ((M[:, i] * G[:, j] + M[:, j] * G[:, i]) + (M[:, i] * M[:, j]) * tau))
+    J = _seq_sum_columns(G + M * tau[:, None])
+    return S, J, T_last
+
+
 def covariance(pi, pj, S, J, L, pooled=True, center=None):
     """(cov, mean) from pair integrals: cov a symmetric scipy.sparse matrix [d x d] with S_ij / L − (J_i / L)(J_j / L) at the listed pairs, mean
     = J / L + center.  S [n x npairs], J [n x d], L [n] (the run lengths T_last − t0) of n chains -- or one chain's S [npairs], J [d], L.
