@@ -13,6 +13,7 @@
  *   pdmp_exp             exp, < 1 ulp, only + - * / on doubles (logistic targets)
  *   pdmp_sincos          sin and cos for |x| <= 2^30 (Boomerang rotations); pdmp_sincos2pi: of 2*pi*v for v in [0,1)
  *   pdmp_atan            atan for every double, < 1 ulp, only + - * / on doubles (the sticky Boomerang's freezing time)
+ *   pdmp_acos, pdmp_atan2  on pdmp_atan and sqrt: acos < 5u relative, atan2 < 10u absolute, u = 2^-53 (occupation times of a Boomerang's arcs)
  *   pdmp_randexp         -log(u)                       (replaces Random.randexp, src/poissontime.jl:77)
  *   pdmp_randn           Box-Muller normal             (replaces Random.randn,   src/dynamics.jl:115)
  *   pdmp_randn2          both Box-Muller branches of one block (the d-vector refresh of the non-factorised samplers)
@@ -345,6 +346,46 @@ PDMP_HD double pdmp_atan(double x) {
 #else
 #define PDMP_SQRT(x) __builtin_sqrt(x)
 #endif
+
+/* ---------------------------------------------------------------- acos, atan2 */
+/*
+ * The two inverse functions the occupation time of a Boomerang's arc needs (DESIGN.md "Marginal histograms of arcs"), on pdmp_atan, PDMP_SQRT
+ * and + - * / only: bit-identical on x86-64 and gfx950.  Errors below in units of u = 2^-53 (half an ulp of 1), derived from pdmp_atan's
+ * < 1 ulp (< 2u relative) and the correctly rounded operations around it.
+ *
+ * pdmp_acos(z) = 2 atan(sqrt((1 - z)/(1 + z))) for -1 < z < 1; 0 for z >= 1, pi (the double) for z <= -1; NaN -> NaN.
+ *   1 - z and 1 + z carry one rounding each (u relative; one of the two is exact where |z| >= 1/2), the quotient a third: 3u; the square
+ *   root halves that and rounds: 2.5u; atan's condition number x/((1 + x^2) atan x) is at most 1, and its own error < 2u; the factor 2 is
+ *   exact.  |pdmp_acos(z) - acos(z)| < 5u * acos(z) (second-order terms included), acos taken of the double z.  No intermediate
+ *   underflows or overflows: 2^-53 <= 1 -+ z <= 2.
+ *
+ * pdmp_atan2(y, x), THE FORM: t = pdmp_atan(y / x) -- never pi/2 - atan(x / y): pdmp_atan reduces a large argument itself, with two-part
+ * constants -- and the quadrant from the signs by comparisons (a zero's sign bit is not looked at but where x > 0, y = -0 gives -0):
+ *     x > 0:  t                          |error| < 3.5u * |atan2(y, x)|  (division u, condition <= 1; atan < 2u), or <= 2^-1074
+ *                                        absolute where y / x is subnormal or underflows
+ *     x < 0:  y >= 0:  PI_HI + (t + PI_LO);   y < 0:  -(PI_HI + (-t + PI_LO))        PI_HI + PI_LO = pi to 2^-106
+ *                                        |error| < 10u: 3u * pi/2 of t, u * pi/2 of the inner sum, u * pi of the outer one
+ *     x == 0: y > 0: pi/2, y < 0: -pi/2 (the doubles: < u), y == 0: +0.0 -- (0, 0) gives 0 whatever the signs
+ *   NaN in either -> NaN; both infinite -> NaN (inf / inf; nothing here needs it).  Everywhere |error| < 10u = 1.12e-15.
+ *   Odd in y bit for bit for every y != 0: the quotient and pdmp_atan are odd, and the two x < 0 branches mirror each other.
+ */
+PDMP_HD double pdmp_acos(double z) {
+    if (z != z) return z;
+    if (z >= 1.0) return 0.0;
+    if (z <= -1.0) return 3.14159265358979311600e+00;
+    return 2.0 * pdmp_atan(PDMP_SQRT((1.0 - z) / (1.0 + z)));
+}
+
+PDMP_HD double pdmp_atan2(double y, double x) {
+    const double pi_hi = 3.14159265358979311600e+00, pi_lo = 1.22464679914735317723e-16, pio2 = 1.57079632679489655800e+00;
+    if (y != y) return y;
+    if (x != x) return x;
+    if (x == 0.0) return y > 0.0 ? pio2 : (y < 0.0 ? -pio2 : 0.0);
+    const double t = pdmp_atan(y / x);
+    if (x > 0.0) return t;
+    if (y >= 0.0) return pi_hi + (t + pi_lo);
+    return -(pi_hi + (-t + pi_lo));
+}
 
 /* Standard normal from two uniforms (Box-Muller, cosine branch only: one normal per draw pair). */
 PDMP_HD double pdmp_randn_from_u(double u1, double u2) {

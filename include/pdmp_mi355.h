@@ -786,7 +786,7 @@ pdmp_status pdmp_ensemble_bps_consume_arc_pairs(pdmp_ensemble* ens, int64_t npai
  * PDMP_ERR_INVALID: m < 1, a NULL list, an index outside [0, d), a coordinate listed twice, lo >= hi or a non-finite bound, bins outside
  * 1..4096, rows beyond 256 GiB (refused before the lists are read), before begin, after the first consume, the other family's ensemble, a chain
  * range outside the ensemble.
- * PDMP_ERR_UNSUPPORTED: the Bouncy Particle family on a Boomerang flow (an arc is not a line), on the speed-recorded flow or with subsample
+ * PDMP_ERR_UNSUPPORTED: the Bouncy Particle family on a Boomerang flow (an arc is not a line: pdmp_ensemble_bps_consume_arc_hist), on the speed-recorded flow or with subsample
  * (their records are not the corners of the path).
  */
 pdmp_status pdmp_ensemble_consume_hist(pdmp_ensemble* ens, int64_t m, const int64_t* coords, const double* lo, const double* hi, int64_t bins);
@@ -795,6 +795,28 @@ pdmp_status pdmp_ensemble_consume_histogram(pdmp_ensemble* ens, int64_t chain_fi
 pdmp_status pdmp_ensemble_bps_consume_hist(pdmp_ensemble* ens, int64_t m, const int64_t* coords, const double* lo, const double* hi, int64_t bins);
 pdmp_status pdmp_ensemble_bps_consume_histogram(pdmp_ensemble* ens, int64_t chain_first, int64_t n, int pooled, double* H, double* Z,
                                                 double* T_last, void** H_dev);
+
+/* ------------------------------------------------------------------ marginal histograms of arcs: occupation times of a Boomerang path
+ *
+ * The same rows H and rest times Z for the event-recorded Boomerang and the sticky Boomerang, whose pieces are arcs about the flow's μ
+ * (DESIGN.md "Marginal histograms of arcs"; tests/ref/arc_hist_ref.c states the contract sequentially and the device agrees with it bit for
+ * bit).  Exact, as for lines: no grid.  Plain double arithmetic, no fused multiply-add, pdmp_acos / pdmp_atan2 of pdmp_detmath.h.  Bins, edges,
+ * slots and the pooled read are those above.
+ *   Per event (t_k, ...) with the cursor (t_c, x_c, θ_c, f_c) before it, τ = t_k − t_c; τ <= 0 adds nothing.  Per listed coordinate:
+ *     at rest -- not free, or u = x_c − μ, p = θ_c, R = sqrt(u·u + p·p) == 0: τ to the slot of x_c and to Z;
+ *     an arc otherwise: ψ0 = −pdmp_atan2(p, u), ψ1 = ψ0 + τ, and for a level y
+ *       z = (y − μ)/R;  z >= 1: below = τ;  z <= −1: below = 0.0;  else α = pdmp_acos(z), L = 2π − 2α,
+ *       W(ψ) = n·L + clamp(r − α, 0, L) with n = floor(ψ/2π), r = ψ − 2π·n (2π one double),  below(y) = W(ψ1) − W(ψ0);
+ *     the bin [e_k, e_k+1) gets max(0.0, below(e_k+1) − below(e_k)), with e_−1 = −∞ and e_bins+1 = +∞.
+ *   Nothing is added behind the last event.  Σ_k H[k] = T_last − t0 to rounding; Z <= Σ_k H[k].
+ *   bps_consume_arc_hist(m, coords, lo, hi, bins)   position, arguments, memory and PDMP_ERR_INVALID cases of bps_consume_hist, and
+ *     PDMP_ERR_INVALID where nchains x ceil(m / 4) reaches 2^24 (one wavefront per chain and listed coordinate in one launch).  Without this
+ *     call nothing changes: no allocation, no kernel.  Coexists with the mean, cummean, the grid, the free-time fractions and
+ *     bps_consume_arc_pairs.  pdmp_ensemble_bps_consume_histogram reads the result, per chain or pooled.
+ * PDMP_ERR_UNSUPPORTED: a flow that is not a Boomerang (pdmp_ensemble_bps_consume_hist is the call for lines), the speed-recorded flow,
+ * subsample, a second list on one ensemble.
+ */
+pdmp_status pdmp_ensemble_bps_consume_arc_hist(pdmp_ensemble* ens, int64_t m, const int64_t* coords, const double* lo, const double* hi, int64_t bins);
 
 /* what the ensemble was created with (any pointer may be NULL) */
 pdmp_status pdmp_ensemble_info(pdmp_ensemble* ens, int64_t* nchains, int64_t* d, int64_t* trace_capacity, int* device);

@@ -173,6 +173,36 @@ struct Options {  // the reference's keyword arguments
     // pdmp_ensemble_bps_consume_arc_pairs), returned in Result::pairs.  cov_center: empty = 0
     std::vector<int64_t> cov_pi, cov_pj;
     std::vector<double> cov_center;
+    // ... and with consume and hist_bins > 0 -- the Python mirror's consume=dict(hist=dict(coords=..., lo=..., hi=..., bins=B)) -- every slice also
+    // adds to the exact marginal histograms of the path: the time each coordinate of hist_coords (empty: all) spends in each of hist_bins bins
+    // of its own range [hist_lo, hist_hi) (one entry per listed coordinate, or one for all), returned in Result::hist
+    // (pdmp_ensemble_bps_consume_hist; a Boomerang's pieces are arcs: pdmp_ensemble_bps_consume_arc_hist)
+    std::vector<int64_t> hist_coords;
+    std::vector<double> hist_lo, hist_hi;
+    int64_t hist_bins = 0;
+};
+
+// What Options::consume with hist_bins > 0 returns: per listed coordinate s the row H [s * (bins + 2) + k] -- slot 0 the time below lo, slots
+// 1..bins the bins, slot bins + 1 the time at or above hi --, the time at rest Z [s], the edges [s * (bins + 1) + k] = e_k as the device computes
+// them, and the last event time T.  quantile(s, q): the piecewise-linear CDF of the row inverted at q, as trace.histogram_quantiles in Python
+struct Histogram {
+    std::vector<int64_t> coords;
+    std::vector<double> H, Z, edges;
+    int64_t bins = 0;
+    double T = 0.0;
+    double quantile(size_t s, double q) const {  // (NaN where the requested mass lies in an outer slot, or in a row without mass)
+        const double* row = H.data() + s * (size_t)(bins + 2);
+        const double* e = edges.data() + s * (size_t)(bins + 1);
+        std::vector<double> inner((size_t)bins + 1);  // the CDF at the edges e_0 .. e_bins, summed in slot order
+        double acc = 0.0;
+        for (int64_t k = 0; k <= bins; ++k) inner[(size_t)k] = acc = acc + row[k];
+        const double total = acc + row[bins + 1], mass = q * total;
+        const double nan = std::numeric_limits<double>::quiet_NaN();
+        if (!(total > 0.0) || !(inner[(size_t)bins] > inner[0]) || !(inner[0] <= mass && mass <= inner[(size_t)bins])) return nan;
+        size_t k = 0;
+        while (inner[k] < mass) ++k;  // the bin k − 1 with inner[k − 1] < mass <= inner[k]
+        return k == 0 ? e[0] : e[k - 1] + (e[k] - e[k - 1]) * ((mass - inner[k - 1]) / (inner[k] - inner[k - 1]));
+    }
 };
 
 // What Options::consume with a pair list returns: S [npairs] in the order of the list, J [d], and the last event time T; with L = T − t0
@@ -229,6 +259,7 @@ struct Result {  // Ξ, (t, x, θ), (acc, num), c
     std::vector<double> theta_saved;
     BarrierConsumed consumed;  // stickyzz with Options::consume
     PairIntegrals pairs;       // pdmp on a BouncyParticle / Boomerang with Options::consume and cov_pi, cov_pj
+    Histogram hist;            // ... with Options::consume and hist_bins > 0
 };
 
 // RAII handle on pdmp_ensemble
@@ -441,15 +472,40 @@ inline Result<PDMPTrace> not_factorised(Ensemble& e, double t0, const std::vecto
         check((arcs ? pdmp_ensemble_bps_consume_arc_pairs : pdmp_ensemble_bps_consume_pairs)(e.get(), (int64_t)o.cov_pi.size(), o.cov_pi.data(),
                                                                                             o.cov_pj.data(), opt(o.cov_center)));
     }
+    const bool hist = o.consume && o.hist_bins > 0;
+    Histogram hg;
+    if (hist) {
+        hg.coords = o.hist_coords;
+        if (hg.coords.empty())
+            for (int64_t k = 0; k < d; ++k) hg.coords.push_back(k);
+        const size_t m = hg.coords.size();
+        if ((o.hist_lo.size() != m && o.hist_lo.size() != 1) || (o.hist_hi.size() != m && o.hist_hi.size() != 1))
+            throw std::invalid_argument("Options::hist_lo and hist_hi have one entry per listed coordinate, or one for all");
+        std::vector<double> lo(m), hi(m);
+        for (size_t s = 0; s < m; ++s) {
+            lo[s] = o.hist_lo[o.hist_lo.size() == 1 ? 0 : s];
+            hi[s] = o.hist_hi[o.hist_hi.size() == 1 ? 0 : s];
+        }
+        if (!pairs) check(pdmp_ensemble_bps_consume_begin(e.get(), 0.0, 0));
+        check((arcs ? pdmp_ensemble_bps_consume_arc_hist : pdmp_ensemble_bps_consume_hist)(e.get(), (int64_t)m, hg.coords.data(), lo.data(), hi.data(),
+                                                                                          o.hist_bins));
+        hg.bins = o.hist_bins;
+        hg.edges.resize(m * (size_t)(o.hist_bins + 1));
+        for (size_t s = 0; s < m; ++s) {  // (the contract's edges: e_0 = lo, e_k = lo + w·k, e_bins = hi)
+            double* const ed = hg.edges.data() + s * (size_t)(o.hist_bins + 1);
+            const double w = (hi[s] - lo[s]) / (double)o.hist_bins;
+            for (int64_t k = 0; k <= o.hist_bins; ++k) ed[k] = k == 0 ? lo[s] : (k == o.hist_bins ? hi[s] : lo[s] + w * (double)k);
+        }
+    }
     Result<PDMPTrace> R;
     R.trace.t0 = t0;
     R.trace.d = d;
     R.trace.x0 = x0;
     R.trace.theta0 = theta0;
     auto cnt = e.run_and_drain(T, [&](const std::vector<pdmp_chain_counters>& k) {
-        if (pairs) check(pdmp_ensemble_bps_consume(e.get()));  // (every slice, before its buffer is recycled)
+        if (pairs || hist) check(pdmp_ensemble_bps_consume(e.get()));  // (every slice, before its buffer is recycled)
         const int64_t m = (int64_t)k[0].ntrace;
-        if (m > 0 && !(pairs && o.consume_only)) {
+        if (m > 0 && !((pairs || hist) && o.consume_only)) {
             const size_t old = R.trace.t.size();
             R.trace.t.resize(old + (size_t)m);
             R.trace.x.resize((old + (size_t)m) * (size_t)d);
@@ -470,6 +526,12 @@ inline Result<PDMPTrace> not_factorised(Ensemble& e, double t0, const std::vecto
         R.pairs.S.resize(o.cov_pi.size());
         R.pairs.J.resize((size_t)d);
         check(pdmp_ensemble_bps_consume_pair_integrals(e.get(), 0, 1, R.pairs.S.data(), R.pairs.J.data(), &R.pairs.T, nullptr));
+    }
+    if (hist) {
+        hg.H.resize(hg.coords.size() * (size_t)(hg.bins + 2));
+        hg.Z.resize(hg.coords.size());
+        check(pdmp_ensemble_bps_consume_histogram(e.get(), 0, 1, 0, hg.H.data(), hg.Z.data(), &hg.T, nullptr));
+        R.hist = std::move(hg);
     }
     return R;
 }
@@ -589,7 +651,7 @@ inline Result<PDMPTrace> pdmp(const GaussianTarget& target, double t0, const std
         check(pdmp_ensemble_set_mass_cholesky(e.get(), cp.data(), rv.data(), nz.data()));
     }
     if (o.subsample) check(pdmp_ensemble_set_bps_options(e.get(), 0, 1));
-    return detail::not_factorised(e, t0, x0, theta0, T, c, o, true);  // (a pair list of Options::consume integrates arcs about B.mu)
+    return detail::not_factorised(e, t0, x0, theta0, T, c, o, true);  // (the pair list and the histograms of Options::consume take arcs about B.mu)
 }
 
 // pdmp(dϕ, ∇ϕ!, t0, x0, θ0, T, c::LocalBound, flow::BouncyParticle; oscn, adapt, factor=2.0)  -- src/not_fact_samplers.jl:336-384, the

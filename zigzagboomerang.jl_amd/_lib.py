@@ -60,6 +60,7 @@ EXPORTED_SYMBOLS = [
     "pdmp_ensemble_consume_pairs", "pdmp_ensemble_consume_pair_integrals", "pdmp_ensemble_bps_consume_pairs", "pdmp_ensemble_bps_consume_pair_integrals",
     "pdmp_ensemble_bps_consume_arc_pairs",
     "pdmp_ensemble_consume_hist", "pdmp_ensemble_consume_histogram", "pdmp_ensemble_bps_consume_hist", "pdmp_ensemble_bps_consume_histogram",
+    "pdmp_ensemble_bps_consume_arc_hist",
     "pdmp_comm_unique_id", "pdmp_comm_init", "pdmp_comm_destroy", "pdmp_comm_info", "pdmp_comm_barrier", "pdmp_comm_allreduce",
     "pdmp_ensemble_gather_traces", "pdmp_ensemble_reduce_moments", "pdmp_comm_gathered_copy",
     "pdmp_ensemble_gather_bps_traces", "pdmp_comm_gathered_bps_copy", "pdmp_ensemble_bps_trace_dev",
@@ -167,7 +168,7 @@ def load():
         getattr(L, name).argtypes = [vp, i64, vp, vp, vp]
     for name in ("pdmp_ensemble_consume_pair_integrals", "pdmp_ensemble_bps_consume_pair_integrals"):
         getattr(L, name).argtypes = [vp, i64, i64, vp, vp, vp, C.POINTER(vp)]
-    for name in ("pdmp_ensemble_consume_hist", "pdmp_ensemble_bps_consume_hist"):
+    for name in ("pdmp_ensemble_consume_hist", "pdmp_ensemble_bps_consume_hist", "pdmp_ensemble_bps_consume_arc_hist"):
         getattr(L, name).argtypes = [vp, i64, vp, vp, vp, i64]
     for name in ("pdmp_ensemble_consume_histogram", "pdmp_ensemble_bps_consume_histogram"):
         getattr(L, name).argtypes = [vp, i64, i64, C.c_int, vp, vp, vp, C.POINTER(vp)]

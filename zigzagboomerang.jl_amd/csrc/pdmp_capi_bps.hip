@@ -267,7 +267,7 @@ pdmp_status init_state_bps(pdmp_ensemble* e, double t0, const double* x0, const 
     e->bc_on = false;
     e->bcn_on = false;
     e->bpr_on = false;
-    e->bhs_on = false;
+    e->bhs_on = e->bhs_arc = false;
     e->trace_appended = false;
     return PDMP_OK;
 }

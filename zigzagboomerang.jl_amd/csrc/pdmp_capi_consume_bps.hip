@@ -125,7 +125,7 @@ pdmp_status pdmp_ensemble_bps_consume_begin(pdmp_ensemble* e, double grid_dt, in
     e->bcn_tau.release(), e->bcn_t.release(), e->bcn_x.release(), e->bcn_pn.release(), e->bcn_nh.release();
     e->bpr_on = e->bpr_arc = false;
     e->bpr_pi.release(),e->bpr_pj.release(), e->bpr_c.release(), e->bpr_S.release(), e->bpr_J.release(), e->bpr_T.release();
-    e->bhs_on = false;
+    e->bhs_on = e->bhs_arc = false;
     e->bhs_coords.release(), e->bhs_lo.release(), e->bhs_hi.release(), e->bhs_w.release(), e->bhs_H.release(), e->bhs_Z.release(), e->bhs_out.release();
     e->bc_dt = grid_dt;
     e->bc_K = grid_points;
@@ -150,7 +150,9 @@ pdmp_status pdmp_ensemble_bps_consume(pdmp_ensemble* e) {
         LAUNCH_TRY("bps_consume_arc_pairs", pdmp::launch_bps_arc_pairs(consume_args(e), pair_args(e), e->stream));
     else if (e->bpr_on)
         LAUNCH_TRY("bps_consume_pairs", pdmp::launch_bps_pairs(consume_args(e), pair_args(e), e->stream));
-    if (e->bhs_on)  // (before the consumer too, for the same reason)
+    if (e->bhs_on && e->bhs_arc)  // (before the consumer too, for the same reason)
+        LAUNCH_TRY("bps_consume_arc_hist", pdmp::launch_bps_arc_hist(consume_args(e), hist_args(e), e->stream));
+    else if (e->bhs_on)
         LAUNCH_TRY("bps_consume_hist", pdmp::launch_bps_hist(consume_args(e), hist_args(e), e->stream));
     LAUNCH_TRY("bps_consume", pdmp::launch_bps_consume_events(consume_args(e), e->stream));
     HIP_TRY(hipEventRecord(e->ev_c1, e->stream));
@@ -373,7 +375,8 @@ pdmp_status pdmp_ensemble_bps_consume_pair_integrals(pdmp_ensemble* e, int64_t c
 pdmp_status pdmp_ensemble_bps_consume_hist(pdmp_ensemble* e, int64_t m, const int64_t* coords, const double* lo, const double* hi, int64_t bins) {
     PDMP_TRY(need_bps(e, __func__));
     if (e->bps.flow_kind == 1)
-        return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_hist: on a Boomerang flow a coordinate moves on an arc between two events, not on a line");
+        return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_hist: on a Boomerang flow a coordinate moves on an arc between two events, not on a line "
+                                          "(pdmp_ensemble_bps_consume_arc_hist keeps those histograms)");
     if (e->bps.modern)
         return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_hist: the records of the speed-recorded flow are not the corners of the path (a straight line "
                                           "between two of them is not the path)");
@@ -401,6 +404,50 @@ pdmp_status pdmp_ensemble_bps_consume_hist(pdmp_ensemble* e, int64_t m, const in
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->bhs_m = m;
     e->bhs_B = (int32_t)bins;
+    e->bhs_on = true;
+    return PDMP_OK;
+}
+
+// the same histograms on a Boomerang flow (DESIGN.md "Marginal histograms of arcs"): between two events a free coordinate is an arc about μ, and the
+// time it spends below a level is a closed form in acos and atan2.  Same position, list, rows and rest times as bps_consume_hist;
+// bps_consume_histogram reads them.
+pdmp_status pdmp_ensemble_bps_consume_arc_hist(pdmp_ensemble* e, int64_t m, const int64_t* coords, const double* lo, const double* hi, int64_t bins) {
+    PDMP_TRY(need_bps(e, __func__));
+    if (e->bps.modern)
+        return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_arc_hist: the records of the speed-recorded flow are not the corners of the path");
+    if (e->bps.flow_kind != 1)
+        return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_arc_hist: the pieces of this flow are lines, not the arcs of a Boomerang "
+                                          "(pdmp_ensemble_bps_consume_hist keeps their histograms)");
+    if (e->bps.subsample)
+        return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_arc_hist: with subsample the records are not the corners of the path (an arc between two of "
+                                          "them is not the path)");
+    PDMP_TRY(need_begun(e, __func__));
+    if (e->bc_started) return fail(PDMP_ERR_INVALID, "bps_consume_arc_hist precedes the first bps_consume (its first piece starts from t0, x0, θ0)");
+    if (e->bhs_on) return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_arc_hist: the ensemble already keeps a histogram list (one list per bps_consume_begin)");
+    const int64_t d = e->cfg.d, nch = e->cfg.nchains;
+    std::vector<int32_t> vc;
+    std::vector<double> vlo, vhi, vw;
+    // One wavefront per chain and listed coordinate, four to a workgroup of 256 threads: a launch holds fewer than 2^32 threads.  Refused before
+    // the lists are read, as hist_list refuses rows beyond 256 GiB (which stays its refusal: 2^35 doubles).
+    if (m > 0 && (double)nch * (double)((m + 3) / 4) >= 0x1.0p+24 && (double)nch * (double)m * (double)(bins + 2) <= 0x1.0p+35)
+        return fail(PDMP_ERR_INVALID, "bps_consume_arc_hist: nchains x m is beyond 2^26 wavefronts, more than one launch holds (list fewer "
+                                      "coordinates per ensemble)");
+    PDMP_TRY(hist_list("bps_consume_arc_hist", nch, d, m, coords, lo, hi, bins, &vc, &vlo, &vhi, &vw));
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(device_sync(e));
+    PDMP_TRY(e->bhs_coords.upload(vc));
+    PDMP_TRY(e->bhs_lo.upload(vlo));
+    PDMP_TRY(e->bhs_hi.upload(vhi));
+    PDMP_TRY(e->bhs_w.upload(vw));
+    PDMP_TRY(e->bhs_H.alloc((size_t)(nch * m * (bins + 2))));
+    PDMP_TRY(e->bhs_Z.alloc((size_t)(nch * m)));
+    e->bhs_out.release();
+    HIP_TRY(hipMemsetAsync(e->bhs_H.p, 0, (size_t)(nch * m * (bins + 2)) * sizeof(double), e->stream));
+    HIP_TRY(hipMemsetAsync(e->bhs_Z.p, 0, (size_t)(nch * m) * sizeof(double), e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->bhs_m = m;
+    e->bhs_B = (int32_t)bins;
+    e->bhs_arc = true;
     e->bhs_on = true;
     return PDMP_OK;
 }

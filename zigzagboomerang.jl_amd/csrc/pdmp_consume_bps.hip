@@ -583,4 +583,156 @@ int launch_bps_hist_pool(const BpsHistArgs& q, int64_t chain_first, int64_t n, d
     return (int)hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------ marginal histograms of arcs (a Boomerang's trace)
+//
+// The same rows H and rest times Z for the event-recorded Boomerang and its sticky form (DESIGN.md "Marginal histograms of arcs";
+// tests/ref/arc_hist_ref.c states the contract).  Between two events a free coordinate is x(s) = μ + R·cos(ψ0 + s) with u = x_c − μ, p = θ_c,
+// R = sqrt(u·u + p·p), ψ0 = −atan2(p, u); the time it spends below a level y is W(ψ0 + τ) − W(ψ0) with W(ψ) = n·L + clamp(r − α, 0, L),
+// α = acos((y − μ)/R), L = 2π − 2α, ψ = 2π·n + r; a bin's time the difference of its two edges' values.  A coordinate that is not free, or with
+// R == 0, is at rest and adds τ to the slot of x_c and to Z.
+//
+// One WAVEFRONT per (chain, listed coordinate), four to a workgroup: R, ψ0, ψ1 and their turns are uniform over it, the edges lie across the
+// lanes, every lane evaluates `below` at its own edge and takes its lower neighbour's value through a lane shuffle.  With bins + 2 <= 128 lane l
+// owns the slots l and l + 64 of the row IN REGISTERS for the whole slice (one load before, one store behind); a longer row is added to in
+// global memory, 64 slots at a time, slot j always by lane j & 63 (a piece at rest too: one owning lane per slot on either path), slots with
+// nothing to add skipped (x + 0.0 has the bits of x: no entry is ever −0.0).  Each slot is added
+// to in the event order of its chain from the value in memory and nothing is atomic, so the bits do not depend on the slicing.  Event loads
+// are wave-uniform; those of the next BC_AHEAD events are in flight, as in the other walkers.  Runs BEFORE bps_consume_kernel of the same
+// slice and only reads what that kernel carries.
+struct ArcPiece {
+    double tau, mu, R, n0, r0, n1, r1;
+    bool live, rest;
+    int krest;
+};
+constexpr double ARC_TWO_PI = 6.28318530717958623200e+00;  // 2π as ONE double constant
+
+__device__ __forceinline__ ArcPiece arc_piece_of(const HistBins& bn, double xc, double thc, bool is_free, double mu, double tau) {
+    ArcPiece a;
+    a.tau = tau;
+    a.mu = mu;
+    a.R = a.n0 = a.r0 = a.n1 = a.r1 = 0.0;
+    a.live = tau > 0.0;
+    a.rest = true;
+    a.krest = 0;
+    if (!a.live) return a;
+    const double u = xc - mu, p = thc;
+    a.R = is_free ? PDMP_SQRT(u * u + p * p) : 0.0;
+    if (a.R == 0.0) {
+        a.krest = hist_bin_of(bn, xc);
+        return a;
+    }
+    a.rest = false;
+    const double psi0 = -pdmp_atan2(p, u), psi1 = psi0 + tau;
+    a.n0 = floor(psi0 / ARC_TWO_PI);
+    a.r0 = psi0 - ARC_TWO_PI * a.n0;
+    a.n1 = floor(psi1 / ARC_TWO_PI);
+    a.r1 = psi1 - ARC_TWO_PI * a.n1;
+    return a;
+}
+__device__ __forceinline__ double arc_w(double n, double r, double alpha, double L) {
+    const double v = r - alpha;
+    return n * L + (v < 0.0 ? 0.0 : (v > L ? L : v));
+}
+// the time the arc spends below the level y (y = ±∞ included: 0 and τ exactly)
+__device__ __forceinline__ double arc_below(const ArcPiece& a, double y) {
+    const double z = (y - a.mu) / a.R;
+    if (z >= 1.0) return a.tau;
+    if (z <= -1.0) return 0.0;
+    const double alpha = pdmp_acos(z);
+    const double L = ARC_TWO_PI - 2.0 * alpha;
+    return arc_w(a.n1, a.r1, alpha, L) - arc_w(a.n0, a.r0, alpha, L);
+}
+// lane l's value of lane l − 1 (lane 0: of lane 63)
+__device__ __forceinline__ double arc_from_below(double v, int lane) { return __shfl(v, (lane + 63) & 63, 64); }
+
+template <bool STICKY, bool LONG_ROW>
+__global__ __launch_bounds__(256) void bps_arc_hist_kernel(BpsConsumeArgs P, BpsHistArgs Q, int64_t blocks_per_chain) {
+    const int64_t chain = (int64_t)blockIdx.x / blocks_per_chain;
+    const int lane = (int)(threadIdx.x & 63);
+    const int64_t s = ((int64_t)blockIdx.x - chain * blocks_per_chain) * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (s >= Q.m) return;
+    const BpsCondSlice sl = bps_cond_slice(P, chain);
+    if (sl.pos >= sl.n) return;
+    const int64_t d = P.d, i = Q.coords[s];
+    HistBins bn;
+    bn.lo = Q.lo[s];
+    bn.hi = Q.hi[s];
+    bn.w = Q.w[s];
+    bn.B = Q.B;
+    const int slots = Q.B + 2;
+    double* const row = Q.H + (chain * Q.m + s) * (int64_t)slots;
+    const BpsConsumeMeta* const meta = static_cast<const BpsConsumeMeta*>(P.meta) + chain * P.nstrips;
+    const int64_t slot0 = chain * P.cap;
+    const double mu = P.mu[i];
+    double Z = Q.Z[chain * Q.m + s], t_cur = sl.t_cur;
+    double x = P.cx[chain * d + i], th = P.cth[chain * d + i];
+    bool f = STICKY ? ((meta[i >> 6].free >> (i & 63)) & 1ull) != 0 : true;
+
+    // (the short row: slot j holds the time in [e_j−1, e_j); lane l owns j = l and j = l + 64 and evaluates their upper edges)
+    const bool two = !LONG_ROW && slots > 64, own0 = lane < slots, own1 = lane + 64 < slots;
+    const double y0 = hist_edge(bn, lane), y1 = hist_edge(bn, lane + 64);
+    double h0 = (!LONG_ROW && own0) ? row[lane] : 0.0, h1 = (!LONG_ROW && own1) ? row[lane + 64] : 0.0;
+
+    BpsHistEvent now[BC_AHEAD], next[BC_AHEAD];
+#pragma unroll
+    for (int q = 0; q < BC_AHEAD; ++q) now[q] = bh_load<STICKY>(P, slot0, sl.pos + q, sl.n, i);
+    for (uint64_t base = sl.pos; base < sl.n; base += BC_AHEAD) {
+#pragma unroll
+        for (int q = 0; q < BC_AHEAD; ++q) next[q] = bh_load<STICKY>(P, slot0, base + BC_AHEAD + q, sl.n, i);
+#pragma unroll
+        for (int q = 0; q < BC_AHEAD; ++q) {
+            if (base + q >= sl.n) break;
+            const ArcPiece a = arc_piece_of(bn, x, th, f, mu, now[q].t - t_cur);  // (uniform over the wavefront, and so is every branch on it)
+            if (a.live && a.rest) {
+                const int j = a.krest + 1;
+                if (LONG_ROW) {
+                    if ((j & 63) == lane) row[j] = row[j] + a.tau;  // (the lane that owns slot j in the arc walk below)
+                } else {
+                    if (j == lane) h0 = h0 + a.tau;
+                    if (j == lane + 64) h1 = h1 + a.tau;
+                }
+                Z = Z + a.tau;
+            } else if (a.live && !LONG_ROW) {
+                const double b0 = arc_below(a, y0), b1 = two ? arc_below(a, y1) : a.tau;
+                const double p0 = arc_from_below(b0, lane), p1 = arc_from_below(b1, lane);
+                const double o0 = b0 - (lane == 0 ? 0.0 : p0), o1 = b1 - (lane == 0 ? p0 : p1);
+                h0 = h0 + (o0 > 0.0 ? o0 : 0.0);
+                h1 = h1 + (o1 > 0.0 ? o1 : 0.0);
+            } else if (a.live) {
+                double carry = 0.0;  // (below e_−1 = −∞)
+                for (int j0 = 0; j0 < slots; j0 += 64) {
+                    const int j = j0 + lane;
+                    const double b = arc_below(a, hist_edge(bn, j));
+                    const double pb = arc_from_below(b, lane);
+                    const double o = b - (lane == 0 ? carry : pb);
+                    carry = __shfl(b, 63, 64);
+                    if (j < slots && o > 0.0) row[j] = row[j] + o;
+                }
+            }
+            x = now[q].x;
+            th = now[q].th;
+            f = now[q].f;
+            t_cur = now[q].t;
+        }
+#pragma unroll
+        for (int q = 0; q < BC_AHEAD; ++q) now[q] = next[q];
+    }
+    if (!LONG_ROW) {
+        if (own0) row[lane] = h0;
+        if (own1) row[lane + 64] = h1;
+    }
+    if (lane == 0) Q.Z[chain * Q.m + s] = Z;
+}
+
+int launch_bps_arc_hist(const BpsConsumeArgs& p, const BpsHistArgs& q, void* stream) {
+    const int64_t bpc = (q.m + 3) / 4;
+    const dim3 grid((unsigned)(p.nchains * bpc)), block(256);
+    const bool sticky = p.ev_f != nullptr, long_row = q.B + 2 > 128;
+    if (sticky && long_row) hipLaunchKernelGGL((bps_arc_hist_kernel<true, true>), grid, block, 0, (hipStream_t)stream, p, q, bpc);
+    else if (sticky) hipLaunchKernelGGL((bps_arc_hist_kernel<true, false>), grid, block, 0, (hipStream_t)stream, p, q, bpc);
+    else if (long_row) hipLaunchKernelGGL((bps_arc_hist_kernel<false, true>), grid, block, 0, (hipStream_t)stream, p, q, bpc);
+    else hipLaunchKernelGGL((bps_arc_hist_kernel<false, false>), grid, block, 0, (hipStream_t)stream, p, q, bpc);
+    return (int)hipGetLastError();
+}
+
 }  // namespace pdmp

@@ -719,6 +719,8 @@ struct BpsHistArgs {
 int launch_bps_hist(const BpsConsumeArgs& p, const BpsHistArgs& q, void* stream);
 // the pooled read: out_H [m x (B + 2)] and out_Z [m], the chains [chain_first, chain_first + n) summed in order
 int launch_bps_hist_pool(const BpsHistArgs& q, int64_t chain_first, int64_t n, double* out_H, double* out_Z, void* stream);
+// ... the same rows and rest times of a Boomerang's arcs (pdmp_ensemble_bps_consume_arc_hist; p.mu is the flow's centre): the same arguments
+int launch_bps_arc_hist(const BpsConsumeArgs& p, const BpsHistArgs& q, void* stream);
 
 #ifdef PDMP_EXTRA_KERNELS
 // pdmp_debug_math_eval (include/pdmp_debug.h, parity library only): a translation unit that calls the shared scalar functions of pdmp_device.hpp

@@ -331,6 +331,7 @@ struct pdmp_ensemble {
     DevBuf<int32_t> bhs_coords;
     DevBuf<double> bhs_lo, bhs_hi, bhs_w, bhs_H, bhs_Z, bhs_out;
     bool bhs_on = false;
+    bool bhs_arc = false;  // the list came by pdmp_ensemble_bps_consume_arc_hist: a Boomerang's pieces are arcs
     int64_t bhs_m = 0;
     int32_t bhs_B = 0;
 

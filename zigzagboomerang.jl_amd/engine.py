@@ -695,6 +695,12 @@ class Ensemble:
         the first bps_consume()."""
         self._hist(self._L.pdmp_ensemble_bps_consume_hist, coords, lo, hi, bins)
 
+    def bps_consume_arc_hist(self, coords, lo, hi, bins):
+        """bps_consume_hist for the event-recorded Boomerang and the sticky Boomerang, whose pieces are arcs about the flow's μ: after
+        bps_consume_begin and before the first bps_consume(); bps_consume_histogram reads the result (trace.arc_marginal_histogram is the host
+        mirror, trace.histogram_quantiles what follows)."""
+        self._hist(self._L.pdmp_ensemble_bps_consume_arc_hist, coords, lo, hi, bins)
+
     def bps_consume_histogram(self, chain_first=0, n=None, pooled=False):
         """consume_histogram for the Bouncy Particle family: the times over [t0, T_last] exactly."""
         return self._histogram(self._L.pdmp_ensemble_bps_consume_histogram, chain_first, n, pooled)

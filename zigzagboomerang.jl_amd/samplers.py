@@ -765,8 +765,8 @@ def _bps(t0, x0, θ0, T, c, B, factor, adapt, seed, device, trace_capacity, trac
                 ens.bps_consume_condition(*_condition_of(consume))
             if _pairs_of(consume, ens.d) is not None:  # (a Boomerang's pieces are arcs: another integral, the same accumulators)
                 (ens.bps_consume_arc_pairs if isinstance(B, Boomerang) else ens.bps_consume_pairs)(*_pairs_of(consume, ens.d))
-            if _hist_of(consume, ens.d) is not None:
-                ens.bps_consume_hist(*_hist_of(consume, ens.d))
+            if _hist_of(consume, ens.d) is not None:  # (likewise: the occupation time of an arc is another closed form, the rows are the same)
+                (ens.bps_consume_arc_hist if isinstance(B, Boomerang) else ens.bps_consume_hist)(*_hist_of(consume, ens.d))
         fs_ = [[] for _ in range(nch)]
         ts = [[] for _ in range(nch)]
         xs = [[] for _ in range(nch)]

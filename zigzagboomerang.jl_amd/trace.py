@@ -803,6 +803,78 @@ def marginal_histogram(tr, coords, lo, hi, bins):
     return _hist_fact(tr, coords, E)
 
 
+_TWO_PI = 6.28318530717958623200e+00  # 2π as the one double constant of the contract
+
+
+def _arc_hist_row(xc, thc, free, mu, tau, E):
+    """(H [B + 2], Z) of the pieces (x_c, θ_c, free, tau) [n] of one coordinate of a Boomerang about mu, in their order; E [B + 1] its edges.
+    The contract's piece (tests/ref/arc_hist_ref.c) with numpy's arctan2 and arccos in the place of pdmp_atan2 and pdmp_acos."""
+    B = len(E) - 1
+    keep = tau > 0.0
+    xc, thc, free, tau = xc[keep], thc[keep], free[keep], tau[keep]
+    u = xc - mu
+    R = np.where(free, np.sqrt(u * u + thc * thc), 0.0)
+    rest = R == 0.0
+    Ex = np.concatenate([[-np.inf], E, [np.inf]])
+    H = np.zeros(B + 2)
+    for s in range(0, len(xc), 1024):  # (pieces x edges at a time)
+        sl = slice(s, s + 1024)
+        Rs, ts = np.where(rest[sl], 1.0, R[sl])[:, None], tau[sl][:, None]
+        psi0 = -np.arctan2(thc[sl], u[sl])[:, None]
+        psi1 = psi0 + ts
+        n0, n1 = np.floor(psi0 / _TWO_PI), np.floor(psi1 / _TWO_PI)
+        r0, r1 = psi0 - _TWO_PI * n0, psi1 - _TWO_PI * n1
+        z = (Ex[None] - mu) / Rs
+        alpha = np.arccos(np.clip(z, -1.0, 1.0))
+        L = _TWO_PI - 2.0 * alpha
+        below = (n1 * L + np.clip(r1 - alpha, 0.0, L)) - (n0 * L + np.clip(r0 - alpha, 0.0, L))
+        below = np.where(z >= 1.0, ts, np.where(z <= -1.0, 0.0, below))
+        C = np.maximum(below[:, 1:] - below[:, :-1], 0.0)
+        at = np.searchsorted(E, xc[sl], side="right")  # slot of x_c: 0 below lo, B + 1 at or above hi
+        C[rest[sl]] = 0.0
+        C[np.flatnonzero(rest[sl]), at[rest[sl]]] = tau[sl][rest[sl]]
+        H = np.cumsum(np.vstack([H[None], C]), axis=0)[-1]
+    return H, _seq_sum(tau[rest])
+
+
+def arc_marginal_histogram(tr, coords, lo, hi, bins):
+    """(H [m x (bins + 2)], Z [m], T_last) as marginal_histogram, for the PDMPTrace of a Boomerang, sticky or not: between two events a free
+    coordinate is the arc x(s) = μ + u·cos s + p·sin s about F.μ (u = x_c − μ, p = θ_c), and the time it spends below a level is a closed form
+    in acos and atan2, so the histogram is exact as it is for lines; a coordinate that is not free, or with u = p = 0, rests (Z counts both).
+    The host mirror of Ensemble.bps_consume_arc_hist: the contract of tests/ref/arc_hist_ref.c in numpy, with numpy's arctan2 and arccos, so
+    it agrees with the device to rounding, not bit for bit (DESIGN.md "Marginal histograms of arcs").  Σ_k H[s, k] = T_last − t0 to rounding.
+    Any other trace: TypeError (marginal_histogram takes the straight-line flows)."""
+    if not (isinstance(tr, PDMPTrace) and isinstance(tr.F, Boomerang)):
+        raise TypeError("arc_marginal_histogram: the PDMPTrace of a Boomerang (marginal_histogram takes the traces of the straight-line flows)")
+    d = len(tr.x0)
+    coords = np.arange(d, dtype=np.int64) if coords is None else np.ascontiguousarray(coords, dtype=np.int64).reshape(-1)
+    bins = int(bins)
+    if coords.size < 1 or coords.min() < 0 or coords.max() >= d or len(np.unique(coords)) != coords.size:
+        raise ValueError("arc_marginal_histogram: coords lists at least one coordinate of [0, %d), each once" % d)
+    if not 1 <= bins <= 4096:
+        raise ValueError("arc_marginal_histogram: bins is in 1..4096")
+    lo = np.broadcast_to(np.asarray(lo, dtype=np.float64), coords.shape)
+    hi = np.broadcast_to(np.asarray(hi, dtype=np.float64), coords.shape)
+    if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi)) and np.all(lo < hi)):
+        raise ValueError("arc_marginal_histogram: the ranges are finite with lo < hi")
+    E = histogram_edges(lo, hi, bins)
+    t = np.asarray(tr.t, dtype=np.float64).reshape(-1)
+    m = len(t)
+    T_last = float(t[-1]) if m else float(tr.t0)
+    mu = np.broadcast_to(np.asarray(tr.F.μ, dtype=np.float64).reshape(-1), (d,))
+    tc = np.concatenate([[tr.t0], t[:-1]])[:m]
+    Xc = np.vstack([np.asarray(tr.x0, dtype=np.float64)[None], np.asarray(tr.x, dtype=np.float64).reshape(-1, d)[:-1]])[:m]
+    Pc = np.vstack([np.asarray(tr.θ0, dtype=np.float64)[None], np.asarray(tr.θ, dtype=np.float64).reshape(-1, d)[:-1]])[:m]
+    Fm = np.ones((m, d), dtype=bool)
+    if tr.f is not None:  # a coordinate that is not free stays where it is
+        f0 = np.ones(d, dtype=bool) if tr.f0 is None else np.asarray(tr.f0, dtype=bool)
+        Fm = np.vstack([f0[None], np.asarray(tr.f, dtype=bool).reshape(-1, d)[:-1]])[:m]
+    H, Z = np.empty((len(coords), bins + 2)), np.empty(len(coords))
+    for s, j in enumerate(coords):
+        H[s], Z[s] = _arc_hist_row(Xc[:, j], Pc[:, j], Fm[:, j], mu[j], t - tc, E[s])
+    return H, Z, T_last
+
+
 def histogram_quantiles(H, lo, hi, q):
     """Quantiles of marginal histograms: H [.. x m x (B + 2)] rows as marginal_histogram / Ensemble.consume_histogram return them (per chain or
     pooled), lo / hi [m] or scalars, q a probability or a list of them.  Returns [.. x m x len(q)] (the last axis dropped for a scalar q): the
