@@ -12,17 +12,17 @@ pytestmark = pytest.mark.gpu
 INF = float("inf")
 
 
-def run_pair(pkg, G, Gt, x0, th0, c, barriers, T, seed, *, mu_t=None, strong=False, adapt=False, **kw):
+def run_pair(pkg, G, Gt, x0, th0, c, barriers, T, seed, *, mu_t=None, mu_b=None, t0=0.0, strong=False, adapt=False, **kw):
     """The device run of every chain and the restatement's, compared bit for bit: events (t, i, x, θ), final (t, x, θ), (acc, num), returned c,
-    t′, frozen flags, saved speeds.  Returns (device output, list of the restatement's runs)."""
+    t′, frozen flags, saved speeds.  mu_b: the flow's mean (default 0), t0: the start time.  Returns (device output, list of the restatement's runs)."""
     d = G.shape[0]
     bl = barriers if isinstance(barriers, list) else [barriers] * d
-    out = pkg.stickyzz(pkg.GaussianTarget(Gt, mu_t), 0.0, x0, th0, T, c, pkg.ZigZag(G, np.zeros(d)), K.barriers_for(pkg, bl, d), seed=seed,
+    out = pkg.stickyzz(pkg.GaussianTarget(Gt, mu_t), t0, x0, th0, T, c, pkg.ZigZag(G, np.zeros(d) if mu_b is None else mu_b), K.barriers_for(pkg, bl, d), seed=seed,
                        strong_upperbounds=strong, adapt=adapt, details=True, **kw)
     tr, tp, (t, x, th), (acc, num), det = out
     refs = []
     for k in range(x0.shape[0]):
-        r = R.stickyzz(0.0, x0[k], th0[k], T, c, bl, gamma=G, target_gamma=Gt, target_mu=mu_t, strong_upperbounds=strong, adapt=adapt, seed=seed + k)
+        r = R.stickyzz(t0, x0[k], th0[k], T, c, bl, gamma=G, mu=mu_b, target_gamma=Gt, target_mu=mu_t, strong_upperbounds=strong, adapt=adapt, seed=seed + k)
         refs.append(r)
         assert r["status"] == R.REF_OK
         ev = tr[k].events
@@ -67,6 +67,18 @@ def test_d8(gpu_pkg, name):
     x0 = K.fit_state(x0, bar) if name != "sticky_at_0" else x0
     _, refs = run_pair(gpu_pkg, 0.9 * G, G, x0, th0, c, bar, 200.0, 7)
     assert all(r["nhit"] > 20 and r["nthaw"] > 20 and r["nrefl"] > 20 for r in refs)
+
+
+def test_d8_flow_mean_and_start_time(gpu_pkg):
+    """The mixed set through the public sampler with a flow mean that is not the target's (which has none) and t0 = 1.5: the `gx − gmu` of the
+    setup and of the re-bound, and the t0 of the first hit, reflection and thaw keys.  adapt: the bound is centred elsewhere than the target."""
+    G, x0, th0, c = problem8()
+    bar = K.mixed_barriers(8)
+    mu_b = 0.4 * np.random.default_rng(31).standard_normal(8)
+    _, refs = run_pair(gpu_pkg, 0.9 * G, G, K.fit_state(x0, bar), th0, c, bar, 101.5, 7, mu_b=mu_b, t0=1.5, adapt=True)
+    assert all(r["nhit"] > 20 and r["nthaw"] > 20 and r["nrefl"] > 20 and r["t"][0] > 1.5 for r in refs)
+    zero = R.stickyzz(1.5, K.fit_state(x0, bar)[0], th0[0], 101.5, c, bar, gamma=0.9 * G, target_gamma=G, adapt=True, seed=7)
+    assert not np.array_equal(zero["t"][:50], refs[0]["t"][:50])  # (the mean is not a no-op in this case)
 
 
 def test_d8_strong_upperbounds(gpu_pkg):
