@@ -197,6 +197,8 @@ pdmp_status pdmp_debug_wave_eval(int device, int fn, int64_t nrows, const uint64
 #define PDMP_QUEUE_HB 8     /* pdmp_trackl.hip hb_word(b = a) in row 0, hb_bit(b = a) in row 1 */
 #define PDMP_QUEUE_NB_HAS 9 /* pdmp_trackp.hip nb_has(nb = the bit images of a (x, y) and b (z, w), v = c given twice): 1 or 0 */
 #define PDMP_QUEUE_NB_COUNT 10 /* pdmp_trackp.hip nb_count(nb = the bit images of a and b) */
+/* (the selection's mask pass, same entry point, numbered on with the ids above: a whole-pass helper, not a code of the queue's tables) */
+#define PDMP_SELECT_P_MASK32 11 /* pdmp_trackp.hip p_mask32(kk, thr = a): entry j = c is b, the others 0 (odd j) and 0x7f7fffff (even j); the 32-bit mask */
 pdmp_status pdmp_debug_queue_eval(int device, int fn, int64_t n, const double* a, const double* b, const double* c, double* out);
 
 /* pdmp_debug_state_eval: the helpers that keep a state in LDS, run by ONE wavefront on a given list of nchg changes (idx[k], val[k]) applied in order.

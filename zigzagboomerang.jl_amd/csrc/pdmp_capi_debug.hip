@@ -427,7 +427,7 @@ pdmp_status pdmp_debug_queue_eval(int device, int fn, int64_t n, const double* a
     if (!a || !b || !c || !out || n <= 0 || n > ((int64_t)1 << 30)) return fail(PDMP_ERR_INVALID, "bad argument");
     decltype(&pdmp::launch_queue_eval_kernels) launch = nullptr;
     switch (fn) {
-    case PDMP_QUEUE_P_ENC: case PDMP_QUEUE_P_THR: case PDMP_QUEUE_P_DEC: case PDMP_QUEUE_NB_HAS: case PDMP_QUEUE_NB_COUNT:
+    case PDMP_QUEUE_P_ENC: case PDMP_QUEUE_P_THR: case PDMP_QUEUE_P_DEC: case PDMP_QUEUE_NB_HAS: case PDMP_QUEUE_NB_COUNT: case PDMP_SELECT_P_MASK32:
         launch = pdmp::launch_queue_eval_trackp; break;
     case PDMP_QUEUE_Q_ENC: case PDMP_QUEUE_Q_THR: case PDMP_QUEUE_Q_DEC: launch = pdmp::launch_queue_eval_exactp; break;
     case PDMP_QUEUE_TL_Q: case PDMP_QUEUE_HB: launch = pdmp::launch_queue_eval_trackl; break;

@@ -65,6 +65,19 @@ __device__ __forceinline__ double p_dec(uint32_t bits, double tb) {
     return pdmp_below(tb + (double)__uint_as_float(bits & ~7u));  // (one ulp below the rounded sum: never above the exact one)
 }
 constexpr uint32_t P_INFBITS = 0x7f7ffff8u;  // patterns from here on: the block is empty (+Inf)
+// bit j of the result: kk[j] <= thr, for thr < P_INFBITS and patterns below 2^31 (all of them are: bit patterns of non-negative floats).  Then
+// thr + 1 <= P_INFBITS < 2^31 too, kk[j] - (thr + 1) does not wrap past the sign, and its sign bit IS the comparison: one subtraction and one
+// v_alignbit per entry, which shifts the mask up and the sign bit in.  (As written in C -- m + m + (kk[j] <= thr) -- it compiled to a compare and
+// a select per entry plus a shift and a three-way OR per pair: 96 instructions for 32 entries.  thr + 1 passes through an empty asm so that the
+// compiler does not fold the subtraction back into that comparison.)
+__device__ __forceinline__ uint32_t p_mask32(const uint32_t (&kk)[32], uint32_t thr) {
+    uint32_t thr1 = thr + 1u;
+    asm volatile("" : "+v"(thr1));
+    uint32_t m_ = 0;
+#pragma unroll
+    for (int j = 31; j >= 0; --j) m_ = __builtin_amdgcn_alignbit(m_, kk[j] - thr1, 31);
+    return m_;
+}
 __device__ __forceinline__ uint32_t lbf_pos(const unsigned char* smem, uint32_t b) {  // position bits of block b's level-1 entry
     return reinterpret_cast<const uint32_t*>(smem)[b] & 7u;
 }
@@ -486,11 +499,16 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
                 const uint32_t m_ = lanemin();
                 mloc = (m_ < mloc) ? m_ : mloc;
             }
-            uint32_t mqb = wave_min_u32_dpp(mloc);
-            double mql = p_dec(mqb, tb);  // a lower bound of the next event time
+            const uint32_t mqb = wave_min_u32_dpp(mloc);
+            const double mql = p_dec(mqb, tb);  // a lower bound of the next event time
             if (mqb < P_INFBITS && (need_rebase || mql - tb > 0.25)) {
-                // move the base of the bounds up to the front (a float resolves 2^-24 of its distance from the base)
-                mloc = 0xffffffffu;
+                // move the base of the bounds up to the front (a float resolves 2^-24 of its distance from the base).  The re-basing is all this
+                // iteration does (about one in several hundred): the next one reads the new bounds back with the loads it issues anyway and
+                // selects from them.  Falling through into the selection instead joined two versions of kk[32] here, and every iteration that
+                // does not re-base paid for the join with 64 register copies.  Nothing is committed in between -- the counters, idle and seldt
+                // stand, the checks at the loop's top are the ones just passed -- and the new minimum decodes to just below the new base, so
+                // the next iteration does not come back here.  (Profiling instantiations: such an iteration passes phase mark 7 twice and never
+                // reaches 8 -- its cycles are booked to phase 7 and it is not counted in ph_iters.)
 #pragma unroll
                 for (int c = 0; c < NCH; ++c) {
                     if (NCH > 1) loadc(c);
@@ -500,14 +518,11 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
 #pragma unroll
                     for (int j = 0; j < 8; ++j)
                         reinterpret_cast<uint4*>(lbf)[512 * c + lane + 64 * j] = make_uint4(kk[4 * j + 0], kk[4 * j + 1], kk[4 * j + 2], kk[4 * j + 3]);
-                    const uint32_t m_ = lanemin();
-                    mloc = (m_ < mloc) ? m_ : mloc;
                 }
                 tb = mql;
                 need_rebase = false;
-                mqb = wave_min_u32_dpp(mloc);
-                mql = p_dec(mqb, tb);
                 PDMP_LDS_ORDER();
+                continue;
             }
             if (mqb >= P_INFBITS) {
                 stalled = true;
@@ -531,9 +546,7 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
 #pragma unroll
                     for (int c = 0; c < NCH; ++c) {
                         if (NCH > 1) loadc(c);
-                        uint32_t m_ = 0;
-#pragma unroll
-                        for (int j = 31; j >= 0; --j) m_ = m_ + m_ + ((kk[j] <= thr) ? 1u : 0u);
+                        const uint32_t m_ = p_mask32(kk, thr);
                         cm[c] = m_;
                         ncl += (uint32_t)__builtin_popcount(m_);
                     }
@@ -583,9 +596,14 @@ __device__ __forceinline__ void trackp_body(const ZzRunParams& P) {
         const uint32_t cblk = isc ? (uint32_t)TB[lane] : 0u;
         double2 q8[8];
         {
-            const double2* const bl = kp + (size_t)cblk * 8;
+            // every lane: one run of eight loads, no branch around each.  A lane without a candidate reads the line of lane 0's candidate, which
+            // is requested anyway (block 0, which every chain has, where there is no candidate at all).  Nothing of what it reads is used -- see
+            // `if (isc)` below.  (Reading block 0 in every such lane was tried first: TCC_EA0_RDREQ + 1.6 % against + 1.1 % in this form,
+            // profiles/r09_a_C3_pmc_block0.txt and profiles/HISTORY.md, r09_a)
+            const uint32_t lblk = isc ? cblk : (uint32_t)__builtin_amdgcn_readfirstlane((int)cblk);
+            const double2* const bl = kp + (size_t)lblk * 8;
 #pragma unroll
-            for (int q = 0; q < 8; ++q) q8[q] = isc ? bl[q] : make_double2(PDMP_INF, 0.0);
+            for (int q = 0; q < 8; ++q) q8[q] = bl[q];
         }
         const uint32_t cpos = isc ? (lbf[cblk] & 7u) : 0u;
         const uint32_t ci = cblk * 8u + cpos;
@@ -1448,6 +1466,12 @@ struct TrackpQueueEval {
         case PDMP_QUEUE_P_THR: return (double)p_thr(a, b);
         case PDMP_QUEUE_P_DEC: return p_dec((uint32_t)a, b);
         case PDMP_QUEUE_NB_HAS: return nb_has(nb, v | (v << 16)) ? 1.0 : 0.0;
+        case PDMP_SELECT_P_MASK32: {  // the selection's mask pass (the loop's own helper) on 32 entries: b at position c, fixed patterns around it
+            uint32_t kk[32];
+#pragma unroll
+            for (int j = 0; j < 32; ++j) kk[j] = ((uint32_t)j == v) ? (uint32_t)b : ((j & 1) ? 0u : 0x7f7fffffu);
+            return (double)p_mask32(kk, (uint32_t)a);
+        }
         default: return (double)nb_count(nb);  // PDMP_QUEUE_NB_COUNT
         }
     }
