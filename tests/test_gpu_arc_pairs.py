@@ -1,5 +1,5 @@
 """The pair integrals of a Boomerang's arcs on the device (pdmp_ensemble_bps_consume_arc_pairs, read by pdmp_ensemble_bps_consume_pair_integrals;
-bps_arc_pairs_kernel of csrc/pdmp_consume_bps.hip; -m gpu) against the sequential statement of their contract, tests/ref/arc_pairs_ref.c, BIT
+bps_pairs_kernel<ARC = true> of csrc/pdmp_consume_bps.hip; -m gpu) against the sequential statement of their contract, tests/ref/arc_pairs_ref.c, BIT
 FOR BIT (S, J and T_last):
 
   1. the hand-made traces of tests/arc_pairs_cases.py (boom and boom_sticky of tests/pdmp_consumer_cases.py among them) through

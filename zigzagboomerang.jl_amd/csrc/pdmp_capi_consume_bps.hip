@@ -101,6 +101,83 @@ static pdmp_status consume_read(pdmp_ensemble* e, int inclusion, int64_t chain_f
     return PDMP_OK;
 }
 
+// what a consumer of the path between two records refuses, in the order its callers see: the line forms the Boomerang flows first, the arc forms
+// the speed-recorded flow first; wrong_flow is the text behind "who: " where the flow's pieces are not the caller's
+static pdmp_status need_corners(const pdmp_ensemble* e, const char* who, bool arc, const char* wrong_flow) {
+    const bool boom = e->bps.flow_kind == 1;
+    if (!arc && boom) return fail(PDMP_ERR_UNSUPPORTED, "%s: %s", who, wrong_flow);
+    if (e->bps.modern)
+        return fail(PDMP_ERR_UNSUPPORTED, "%s: the records of the speed-recorded flow are not the corners of the path%s", who,
+                    arc ? "" : " (a straight line between two of them is not the path)");
+    if (arc && !boom) return fail(PDMP_ERR_UNSUPPORTED, "%s: %s", who, wrong_flow);
+    if (e->bps.subsample)
+        return fail(PDMP_ERR_UNSUPPORTED, "%s: with subsample the records are not the corners of the path (%s between two of them is not the path)", who,
+                    arc ? "an arc" : "a straight line");
+    return PDMP_OK;
+}
+
+// bps_consume_pairs / _arc_pairs behind their refusals: the list, its accumulators and the flags.  The line form may be called again before the
+// first bps_consume and replaces the list; the arc form keeps one list per bps_consume_begin.
+static pdmp_status setup_pairs(pdmp_ensemble* e, const char* who, bool arc, int64_t npairs, const int64_t* pi, const int64_t* pj, const double* center) {
+    PDMP_TRY(need_begun(e, who));
+    if (e->bc_started) return fail(PDMP_ERR_INVALID, "%s precedes the first bps_consume (its first piece starts from t0, x0, θ0)", who);
+    if (arc && e->bpr_on) return fail(PDMP_ERR_UNSUPPORTED, "%s: the ensemble already keeps a pair list (one list per bps_consume_begin)", who);
+    const int64_t d = e->cfg.d, nch = e->cfg.nchains;
+    std::vector<int32_t> vi, vj;
+    std::vector<double> c;
+    PDMP_TRY(pairs_list(who, nch, d, npairs, pi, pj, center, &vi, &vj, &c));
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(device_sync(e));
+    e->bpr_on = false;
+    PDMP_TRY(e->bpr_pi.upload(vi));
+    PDMP_TRY(e->bpr_pj.upload(vj));
+    PDMP_TRY(e->bpr_c.upload(c));
+    PDMP_TRY(e->bpr_S.alloc((size_t)(nch * npairs)));
+    PDMP_TRY(e->bpr_J.alloc((size_t)(nch * d)));
+    PDMP_TRY(e->bpr_T.alloc((size_t)nch));
+    HIP_TRY(hipMemsetAsync(e->bpr_S.p, 0, (size_t)(nch * npairs) * sizeof(double), e->stream));
+    HIP_TRY(hipMemsetAsync(e->bpr_J.p, 0, (size_t)(nch * d) * sizeof(double), e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->bpr_np = npairs;
+    e->bpr_arc = arc;  // (bps_consume_begin cleared it, and a flow serves one of the two forms)
+    e->bpr_on = true;
+    return PDMP_OK;
+}
+
+// bps_consume_hist / _arc_hist behind their refusals, in the same way
+static pdmp_status setup_hist(pdmp_ensemble* e, const char* who, bool arc, int64_t m, const int64_t* coords, const double* lo, const double* hi,
+                              int64_t bins) {
+    PDMP_TRY(need_begun(e, who));
+    if (e->bc_started) return fail(PDMP_ERR_INVALID, "%s precedes the first bps_consume (its first piece starts from t0, x0, θ0)", who);
+    if (arc && e->bhs_on) return fail(PDMP_ERR_UNSUPPORTED, "%s: the ensemble already keeps a histogram list (one list per bps_consume_begin)", who);
+    const int64_t d = e->cfg.d, nch = e->cfg.nchains;
+    std::vector<int32_t> vc;
+    std::vector<double> vlo, vhi, vw;
+    // The arc form: one wavefront per chain and listed coordinate, four to a workgroup of 256 threads: a launch holds fewer than 2^32 threads.
+    // Refused before the lists are read, as hist_list refuses rows beyond 256 GiB (which stays its refusal: 2^35 doubles).
+    if (arc && m > 0 && (double)nch * (double)((m + 3) / 4) >= 0x1.0p+24 && (double)nch * (double)m * (double)(bins + 2) <= 0x1.0p+35)
+        return fail(PDMP_ERR_INVALID, "%s: nchains x m is beyond 2^26 wavefronts, more than one launch holds (list fewer coordinates per ensemble)", who);
+    PDMP_TRY(hist_list(who, nch, d, m, coords, lo, hi, bins, &vc, &vlo, &vhi, &vw));
+    HIP_TRY(hipSetDevice(e->cfg.device));
+    HIP_TRY(device_sync(e));
+    e->bhs_on = false;
+    PDMP_TRY(e->bhs_coords.upload(vc));
+    PDMP_TRY(e->bhs_lo.upload(vlo));
+    PDMP_TRY(e->bhs_hi.upload(vhi));
+    PDMP_TRY(e->bhs_w.upload(vw));
+    PDMP_TRY(e->bhs_H.alloc((size_t)(nch * m * (bins + 2))));
+    PDMP_TRY(e->bhs_Z.alloc((size_t)(nch * m)));
+    e->bhs_out.release();
+    HIP_TRY(hipMemsetAsync(e->bhs_H.p, 0, (size_t)(nch * m * (bins + 2)) * sizeof(double), e->stream));
+    HIP_TRY(hipMemsetAsync(e->bhs_Z.p, 0, (size_t)(nch * m) * sizeof(double), e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->bhs_m = m;
+    e->bhs_B = (int32_t)bins;
+    e->bhs_arc = arc;
+    e->bhs_on = true;
+    return PDMP_OK;
+}
+
 extern "C" {
 
 pdmp_status pdmp_ensemble_bps_consume_begin(pdmp_ensemble* e, double grid_dt, int64_t grid_points) {
@@ -146,10 +223,8 @@ pdmp_status pdmp_ensemble_bps_consume(pdmp_ensemble* e) {
     HIP_TRY(hipEventRecord(e->ev_c0, e->stream));
     if (e->bcn_on)  // (before the consumer: it reads the cursors and the progress the consumer is about to advance)
         LAUNCH_TRY("bps_consume_condition", pdmp::launch_bps_cond(consume_args(e), cond_args(e), e->stream));
-    if (e->bpr_on && e->bpr_arc)  // (before the consumer, like the condition: it reads the cursors and the progress the consumer is about to advance)
-        LAUNCH_TRY("bps_consume_arc_pairs", pdmp::launch_bps_arc_pairs(consume_args(e), pair_args(e), e->stream));
-    else if (e->bpr_on)
-        LAUNCH_TRY("bps_consume_pairs", pdmp::launch_bps_pairs(consume_args(e), pair_args(e), e->stream));
+    if (e->bpr_on)  // (before the consumer, like the condition: it reads the cursors and the progress the consumer is about to advance)
+        LAUNCH_TRY(e->bpr_arc ? "bps_consume_arc_pairs" : "bps_consume_pairs", pdmp::launch_bps_pairs(consume_args(e), pair_args(e), e->bpr_arc, e->stream));
     if (e->bhs_on && e->bhs_arc)  // (before the consumer too, for the same reason)
         LAUNCH_TRY("bps_consume_arc_hist", pdmp::launch_bps_arc_hist(consume_args(e), hist_args(e), e->stream));
     else if (e->bhs_on)
@@ -182,10 +257,10 @@ pdmp_status pdmp_ensemble_bps_consume_discretized(pdmp_ensemble* e, int64_t chai
         HIP_TRY(hipMemcpy(out, e->bc_grid.p + (chain * e->bc_K + k_first) * d, (size_t)(k_count * d) * sizeof(double), hipMemcpyDeviceToHost));
     if (npoints) {
         // the number of k with t0 + k·dt < T_last, at least 1 (row 0 is x0) and NOT clamped to the grid: a value above grid_points tells the caller
-        // that the grid was too short for the run.  Strip 0's copy of the chain's progress: { t_cur, t_last, ... }
+        // that the grid was too short for the run.  T_last of strip 0's copy of the chain's progress
         double tl;
-        HIP_TRY(hipMemcpy(&tl, e->bc_meta.p + (size_t)(chain * ((d + 63) / 64)) * pdmp::bps_consume_meta_bytes() + sizeof(double), sizeof tl,
-                          hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&tl, e->bc_meta.p + (size_t)(chain * ((d + 63) / 64)) * pdmp::bps_consume_meta_bytes() + pdmp::bps_consume_meta_tlast_offset(),
+                          sizeof tl, hipMemcpyDeviceToHost));
         const double t0 = e->t0_state, dt = e->bc_dt, q = floor((tl - t0) / dt);
         if (q >= 0x1.0p+62) return fail(PDMP_ERR_INVALID, "bps_consume_discretized: (T_last - t0) / grid_dt = %g grid times do not fit an int64", q);
         int64_t np = q > 1.0 ? (int64_t)q - 1 : 0;
@@ -225,14 +300,7 @@ pdmp_status pdmp_ensemble_bps_consume_cummean_copy(pdmp_ensemble* e, int64_t cha
 // first bps_consume; from then on bps_consume also collects the hyperplane hits of every slice
 pdmp_status pdmp_ensemble_bps_consume_condition(pdmp_ensemble* e, const double* p, const double* n, int64_t max_hits) {
     PDMP_TRY(need_bps(e, __func__));
-    if (e->bps.flow_kind == 1)
-        return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_condition: the hitting time of a hyperplane has no method for the Boomerang flows (src/condition.jl:18)");
-    if (e->bps.modern)
-        return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_condition: the records of the speed-recorded flow are not the corners of the path (a straight line "
-                                          "between two of them is not the path)");
-    if (e->bps.subsample)
-        return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_condition: with subsample the records are not the corners of the path (a straight line between two of "
-                                          "them is not the path)");
+    PDMP_TRY(need_corners(e, "bps_consume_condition", false, "the hitting time of a hyperplane has no method for the Boomerang flows (src/condition.jl:18)"));
     PDMP_TRY(need_begun(e, __func__));
     if (e->bc_started) return fail(PDMP_ERR_INVALID, "bps_consume_condition precedes the first bps_consume (its first segment starts from t0, x0, θ0)");
     const int64_t d = e->cfg.d, nch = e->cfg.nchains, cap = e->cfg.trace_capacity;
@@ -283,72 +351,19 @@ pdmp_status pdmp_ensemble_bps_consume_conditioned(pdmp_ensemble* e, int64_t chai
 // and before the first bps_consume; from then on bps_consume also adds every slice's pieces
 pdmp_status pdmp_ensemble_bps_consume_pairs(pdmp_ensemble* e, int64_t npairs, const int64_t* pi, const int64_t* pj, const double* center) {
     PDMP_TRY(need_bps(e, __func__));
-    if (e->bps.flow_kind == 1)
-        return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_pairs: on a Boomerang flow the product of two rotations is another integral than that of two lines "
-                                          "(pdmp_ensemble_bps_consume_arc_pairs keeps that one)");
-    if (e->bps.modern)
-        return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_pairs: the records of the speed-recorded flow are not the corners of the path (a straight line "
-                                          "between two of them is not the path)");
-    if (e->bps.subsample)
-        return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_pairs: with subsample the records are not the corners of the path (a straight line between two of "
-                                          "them is not the path)");
-    PDMP_TRY(need_begun(e, __func__));
-    if (e->bc_started) return fail(PDMP_ERR_INVALID, "bps_consume_pairs precedes the first bps_consume (its first piece starts from t0, x0, θ0)");
-    const int64_t d = e->cfg.d, nch = e->cfg.nchains;
-    std::vector<int32_t> vi, vj;
-    std::vector<double> c;
-    PDMP_TRY(pairs_list("bps_consume_pairs", nch, d, npairs, pi, pj, center, &vi, &vj, &c));
-    HIP_TRY(hipSetDevice(e->cfg.device));
-    HIP_TRY(device_sync(e));
-    e->bpr_on = false;
-    PDMP_TRY(e->bpr_pi.upload(vi));
-    PDMP_TRY(e->bpr_pj.upload(vj));
-    PDMP_TRY(e->bpr_c.upload(c));
-    PDMP_TRY(e->bpr_S.alloc((size_t)(nch * npairs)));
-    PDMP_TRY(e->bpr_J.alloc((size_t)(nch * d)));
-    PDMP_TRY(e->bpr_T.alloc((size_t)nch));
-    HIP_TRY(hipMemsetAsync(e->bpr_S.p, 0, (size_t)(nch * npairs) * sizeof(double), e->stream));
-    HIP_TRY(hipMemsetAsync(e->bpr_J.p, 0, (size_t)(nch * d) * sizeof(double), e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->bpr_np = npairs;
-    e->bpr_on = true;
-    return PDMP_OK;
+    PDMP_TRY(need_corners(e, "bps_consume_pairs", false,
+                          "on a Boomerang flow the product of two rotations is another integral than that of two lines "
+                          "(pdmp_ensemble_bps_consume_arc_pairs keeps that one)"));
+    return setup_pairs(e, "bps_consume_pairs", false, npairs, pi, pj, center);
 }
 
 // the same integrals on a Boomerang flow (DESIGN.md "Pair integrals of arcs"): between two events a coordinate is an arc about μ, a pair's piece a
 // combination of five trigonometric integrals.  Same position, list and accumulators as bps_consume_pairs; bps_consume_pair_integrals reads them.
 pdmp_status pdmp_ensemble_bps_consume_arc_pairs(pdmp_ensemble* e, int64_t npairs, const int64_t* pi, const int64_t* pj, const double* center) {
     PDMP_TRY(need_bps(e, __func__));
-    if (e->bps.modern)
-        return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_arc_pairs: the records of the speed-recorded flow are not the corners of the path");
-    if (e->bps.flow_kind != 1)
-        return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_arc_pairs: the pieces of this flow are lines, not the arcs of a Boomerang "
-                                          "(pdmp_ensemble_bps_consume_pairs keeps their integrals)");
-    if (e->bps.subsample)
-        return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_arc_pairs: with subsample the records are not the corners of the path (an arc between two of "
-                                          "them is not the path)");
-    PDMP_TRY(need_begun(e, __func__));
-    if (e->bc_started) return fail(PDMP_ERR_INVALID, "bps_consume_arc_pairs precedes the first bps_consume (its first piece starts from t0, x0, θ0)");
-    if (e->bpr_on) return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_arc_pairs: the ensemble already keeps a pair list (one list per bps_consume_begin)");
-    const int64_t d = e->cfg.d, nch = e->cfg.nchains;
-    std::vector<int32_t> vi, vj;
-    std::vector<double> c;
-    PDMP_TRY(pairs_list("bps_consume_arc_pairs", nch, d, npairs, pi, pj, center, &vi, &vj, &c));
-    HIP_TRY(hipSetDevice(e->cfg.device));
-    HIP_TRY(device_sync(e));
-    PDMP_TRY(e->bpr_pi.upload(vi));
-    PDMP_TRY(e->bpr_pj.upload(vj));
-    PDMP_TRY(e->bpr_c.upload(c));
-    PDMP_TRY(e->bpr_S.alloc((size_t)(nch * npairs)));
-    PDMP_TRY(e->bpr_J.alloc((size_t)(nch * d)));
-    PDMP_TRY(e->bpr_T.alloc((size_t)nch));
-    HIP_TRY(hipMemsetAsync(e->bpr_S.p, 0, (size_t)(nch * npairs) * sizeof(double), e->stream));
-    HIP_TRY(hipMemsetAsync(e->bpr_J.p, 0, (size_t)(nch * d) * sizeof(double), e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->bpr_np = npairs;
-    e->bpr_arc = true;
-    e->bpr_on = true;
-    return PDMP_OK;
+    PDMP_TRY(need_corners(e, "bps_consume_arc_pairs", true,
+                          "the pieces of this flow are lines, not the arcs of a Boomerang (pdmp_ensemble_bps_consume_pairs keeps their integrals)"));
+    return setup_pairs(e, "bps_consume_arc_pairs", true, npairs, pi, pj, center);
 }
 
 pdmp_status pdmp_ensemble_bps_consume_pair_integrals(pdmp_ensemble* e, int64_t chain_first, int64_t n, double* S, double* J, double* T_last, void** S_dev) {
@@ -363,7 +378,7 @@ pdmp_status pdmp_ensemble_bps_consume_pair_integrals(pdmp_ensemble* e, int64_t c
     if (S) HIP_TRY(hipMemcpy(S, e->bpr_S.p + chain_first * np, (size_t)(n * np) * sizeof(double), hipMemcpyDeviceToHost));
     if (J) HIP_TRY(hipMemcpy(J, e->bpr_J.p + chain_first * d, (size_t)(n * d) * sizeof(double), hipMemcpyDeviceToHost));
     if (T_last) {
-        LAUNCH_TRY("bps_consume_pair_integrals", pdmp::launch_bps_pairs_tlast(consume_args(e), chain_first, n, e->bpr_T.p, e->stream));
+        LAUNCH_TRY("bps_consume_pair_integrals", pdmp::launch_bps_tlast(consume_args(e), chain_first, n, e->bpr_T.p, e->stream));
         HIP_TRY(hipStreamSynchronize(e->stream));
         HIP_TRY(hipMemcpy(T_last, e->bpr_T.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
     }
@@ -374,38 +389,10 @@ pdmp_status pdmp_ensemble_bps_consume_pair_integrals(pdmp_ensemble* e, int64_t c
 // then on bps_consume also adds every slice's pieces
 pdmp_status pdmp_ensemble_bps_consume_hist(pdmp_ensemble* e, int64_t m, const int64_t* coords, const double* lo, const double* hi, int64_t bins) {
     PDMP_TRY(need_bps(e, __func__));
-    if (e->bps.flow_kind == 1)
-        return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_hist: on a Boomerang flow a coordinate moves on an arc between two events, not on a line "
-                                          "(pdmp_ensemble_bps_consume_arc_hist keeps those histograms)");
-    if (e->bps.modern)
-        return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_hist: the records of the speed-recorded flow are not the corners of the path (a straight line "
-                                          "between two of them is not the path)");
-    if (e->bps.subsample)
-        return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_hist: with subsample the records are not the corners of the path (a straight line between two of "
-                                          "them is not the path)");
-    PDMP_TRY(need_begun(e, __func__));
-    if (e->bc_started) return fail(PDMP_ERR_INVALID, "bps_consume_hist precedes the first bps_consume (its first piece starts from t0, x0, θ0)");
-    const int64_t d = e->cfg.d, nch = e->cfg.nchains;
-    std::vector<int32_t> vc;
-    std::vector<double> vlo, vhi, vw;
-    PDMP_TRY(hist_list("bps_consume_hist", nch, d, m, coords, lo, hi, bins, &vc, &vlo, &vhi, &vw));
-    HIP_TRY(hipSetDevice(e->cfg.device));
-    HIP_TRY(device_sync(e));
-    e->bhs_on = false;
-    PDMP_TRY(e->bhs_coords.upload(vc));
-    PDMP_TRY(e->bhs_lo.upload(vlo));
-    PDMP_TRY(e->bhs_hi.upload(vhi));
-    PDMP_TRY(e->bhs_w.upload(vw));
-    PDMP_TRY(e->bhs_H.alloc((size_t)(nch * m * (bins + 2))));
-    PDMP_TRY(e->bhs_Z.alloc((size_t)(nch * m)));
-    e->bhs_out.release();
-    HIP_TRY(hipMemsetAsync(e->bhs_H.p, 0, (size_t)(nch * m * (bins + 2)) * sizeof(double), e->stream));
-    HIP_TRY(hipMemsetAsync(e->bhs_Z.p, 0, (size_t)(nch * m) * sizeof(double), e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->bhs_m = m;
-    e->bhs_B = (int32_t)bins;
-    e->bhs_on = true;
-    return PDMP_OK;
+    PDMP_TRY(need_corners(e, "bps_consume_hist", false,
+                          "on a Boomerang flow a coordinate moves on an arc between two events, not on a line "
+                          "(pdmp_ensemble_bps_consume_arc_hist keeps those histograms)"));
+    return setup_hist(e, "bps_consume_hist", false, m, coords, lo, hi, bins);
 }
 
 // the same histograms on a Boomerang flow (DESIGN.md "Marginal histograms of arcs"): between two events a free coordinate is an arc about μ, and the
@@ -413,43 +400,9 @@ pdmp_status pdmp_ensemble_bps_consume_hist(pdmp_ensemble* e, int64_t m, const in
 // bps_consume_histogram reads them.
 pdmp_status pdmp_ensemble_bps_consume_arc_hist(pdmp_ensemble* e, int64_t m, const int64_t* coords, const double* lo, const double* hi, int64_t bins) {
     PDMP_TRY(need_bps(e, __func__));
-    if (e->bps.modern)
-        return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_arc_hist: the records of the speed-recorded flow are not the corners of the path");
-    if (e->bps.flow_kind != 1)
-        return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_arc_hist: the pieces of this flow are lines, not the arcs of a Boomerang "
-                                          "(pdmp_ensemble_bps_consume_hist keeps their histograms)");
-    if (e->bps.subsample)
-        return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_arc_hist: with subsample the records are not the corners of the path (an arc between two of "
-                                          "them is not the path)");
-    PDMP_TRY(need_begun(e, __func__));
-    if (e->bc_started) return fail(PDMP_ERR_INVALID, "bps_consume_arc_hist precedes the first bps_consume (its first piece starts from t0, x0, θ0)");
-    if (e->bhs_on) return fail(PDMP_ERR_UNSUPPORTED, "bps_consume_arc_hist: the ensemble already keeps a histogram list (one list per bps_consume_begin)");
-    const int64_t d = e->cfg.d, nch = e->cfg.nchains;
-    std::vector<int32_t> vc;
-    std::vector<double> vlo, vhi, vw;
-    // One wavefront per chain and listed coordinate, four to a workgroup of 256 threads: a launch holds fewer than 2^32 threads.  Refused before
-    // the lists are read, as hist_list refuses rows beyond 256 GiB (which stays its refusal: 2^35 doubles).
-    if (m > 0 && (double)nch * (double)((m + 3) / 4) >= 0x1.0p+24 && (double)nch * (double)m * (double)(bins + 2) <= 0x1.0p+35)
-        return fail(PDMP_ERR_INVALID, "bps_consume_arc_hist: nchains x m is beyond 2^26 wavefronts, more than one launch holds (list fewer "
-                                      "coordinates per ensemble)");
-    PDMP_TRY(hist_list("bps_consume_arc_hist", nch, d, m, coords, lo, hi, bins, &vc, &vlo, &vhi, &vw));
-    HIP_TRY(hipSetDevice(e->cfg.device));
-    HIP_TRY(device_sync(e));
-    PDMP_TRY(e->bhs_coords.upload(vc));
-    PDMP_TRY(e->bhs_lo.upload(vlo));
-    PDMP_TRY(e->bhs_hi.upload(vhi));
-    PDMP_TRY(e->bhs_w.upload(vw));
-    PDMP_TRY(e->bhs_H.alloc((size_t)(nch * m * (bins + 2))));
-    PDMP_TRY(e->bhs_Z.alloc((size_t)(nch * m)));
-    e->bhs_out.release();
-    HIP_TRY(hipMemsetAsync(e->bhs_H.p, 0, (size_t)(nch * m * (bins + 2)) * sizeof(double), e->stream));
-    HIP_TRY(hipMemsetAsync(e->bhs_Z.p, 0, (size_t)(nch * m) * sizeof(double), e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->bhs_m = m;
-    e->bhs_B = (int32_t)bins;
-    e->bhs_arc = true;
-    e->bhs_on = true;
-    return PDMP_OK;
+    PDMP_TRY(need_corners(e, "bps_consume_arc_hist", true,
+                          "the pieces of this flow are lines, not the arcs of a Boomerang (pdmp_ensemble_bps_consume_hist keeps their histograms)"));
+    return setup_hist(e, "bps_consume_arc_hist", true, m, coords, lo, hi, bins);
 }
 
 pdmp_status pdmp_ensemble_bps_consume_histogram(pdmp_ensemble* e, int64_t chain_first, int64_t n, int pooled, double* H, double* Z, double* T_last,
@@ -468,7 +421,7 @@ pdmp_status pdmp_ensemble_bps_consume_histogram(pdmp_ensemble* e, int64_t chain_
     if (H_dev) *H_dev = const_cast<double*>(srcH);
     if (n == 0) return PDMP_OK;
     if (pooled && (H || Z || H_dev)) LAUNCH_TRY("bps_consume_histogram", pdmp::launch_bps_hist_pool(hist_args(e), chain_first, n, oH, oZ, e->stream));
-    if (T_last) LAUNCH_TRY("bps_consume_histogram", pdmp::launch_bps_pairs_tlast(consume_args(e), chain_first, n, oT, e->stream));
+    if (T_last) LAUNCH_TRY("bps_consume_histogram", pdmp::launch_bps_tlast(consume_args(e), chain_first, n, oT, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     const int64_t rows = pooled ? 1 : n;
     if (H) HIP_TRY(hipMemcpy(H, srcH, (size_t)(rows * len) * sizeof(double), hipMemcpyDeviceToHost));

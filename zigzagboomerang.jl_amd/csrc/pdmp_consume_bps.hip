@@ -17,9 +17,16 @@
 //      The walk stops at k = K: rows the buffer has no room for are counted by the reader (from T_last, in closed form), not by a loop here.
 //   2. sums: y += (x + x2)·(t2 − t_cur) (:241,260); cummean on: y / (2·t2) at the event's slot (:263); sticky: free_time += free ? t2 − t_cur : 0.
 //   3. cursor: x = x2, θ = θ2, free = f2, t_cur = T_last = t2.
-// The loads of the next BC_AHEAD events are issued before the arithmetic of the current ones: at small ensembles the walk is bound by latency.
+//
+// THE WALK (bps_walk), shared by this kernel and the four consumers behind it (pairs, arc pairs, histograms, arc histograms): a thread applies the
+// unconsumed slots [pos, n) of its chain's segment (bps_slice) in event order.  load(e) reads slot e < n of the segment into the consumer's event
+// record, apply(ev, e) is the consumer's own arithmetic and cursor update.  The loads of the next BC_AHEAD events are issued before the arithmetic
+// of the current ones -- at small ensembles the walk is bound by latency --; a load behind the segment reads its last event once more and is never
+// applied.  The four consumers run BEFORE bps_consume_kernel of the same slice and only read what that kernel carries (cursors, clock, free bits,
+// events consumed); their threads of a workgroup belong to one chain, so event times are wave-uniform loads.
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 
 #include "pdmp_bps_common.hpp"
@@ -37,13 +44,81 @@ struct BpsConsumeMeta {  // per (chain, strip)
     uint64_t pad;
 };
 size_t bps_consume_meta_bytes() { return sizeof(BpsConsumeMeta); }
+size_t bps_consume_meta_tlast_offset() { return offsetof(BpsConsumeMeta, t_last); }
+
+constexpr int BC_AHEAD = 4;
+#define BPS_WALK_INLINE __attribute__((always_inline))  // (on the lambdas handed to bps_walk: one copy of their code per unrolled call, no call)
+
+template <class Ev, class Load, class Apply>
+__device__ __forceinline__ void bps_walk(uint64_t pos, uint64_t n, Load load, Apply apply) {
+    Ev now[BC_AHEAD], next[BC_AHEAD];
+    const auto at = [&](uint64_t e) BPS_WALK_INLINE { return load(e < n ? e : n - 1); };
+#pragma unroll
+    for (int q = 0; q < BC_AHEAD; ++q) now[q] = at(pos + q);
+    for (uint64_t base = pos; base < n; base += BC_AHEAD) {
+#pragma unroll
+        for (int q = 0; q < BC_AHEAD; ++q) next[q] = at(base + BC_AHEAD + q);
+#pragma unroll
+        for (int q = 0; q < BC_AHEAD; ++q) {
+            if (base + q >= n) break;
+            apply(now[q], base + q);
+        }
+#pragma unroll
+        for (int q = 0; q < BC_AHEAD; ++q) now[q] = next[q];
+    }
+}
+
+// the unconsumed slots [pos, n) of a chain's segment and what the chain carries, as `strip`'s copy of its progress has it (the consumers in front
+// of bps_consume_kernel take strip 0's)
+struct BpsSlice {
+    uint64_t pos, n, nevents;
+    BpsConsumeMeta m;
+};
+__device__ __forceinline__ BpsSlice bps_slice(const BpsConsumeArgs& P, int64_t chain, int64_t strip = 0) {
+    BpsSlice s;
+    s.m = static_cast<const BpsConsumeMeta*>(P.meta)[chain * P.nstrips + strip];
+    const uint64_t ntrace = P.hdr[chain].c.ntrace;
+    s.nevents = P.hdr[chain].c.nevents;
+    s.n = ntrace < (uint64_t)P.cap ? ntrace : (uint64_t)P.cap;
+    const uint64_t first_global = s.nevents - ntrace;  // global index of buffer slot 0
+    s.pos = (s.m.consumed > first_global) ? (s.m.consumed - first_global) : 0;  // first unconsumed slot
+    return s;
+}
+
+// free bit of coordinate i in a mask of one word per strip: an event's words (ev_f + slot·BPS_STICKY_WORDS) or the carried ones (a chain's meta)
+__device__ __forceinline__ uint64_t bps_mask_word(const uint64_t* words, int64_t k) { return words[k]; }
+__device__ __forceinline__ uint64_t bps_mask_word(const BpsConsumeMeta* strips, int64_t k) { return strips[k].free; }
+template <bool STICKY, class Words>
+__device__ __forceinline__ bool bps_free_bit(const Words* words, int64_t i) {
+    return STICKY ? ((bps_mask_word(words, i >> 6) >> (i & 63)) & 1ull) != 0 : true;
+}
+
+// (x, θ, free) of column i at global slot s of the trace, or of a chain's cursor
+struct BpsColumn {
+    double x, th;
+    bool f;
+};
+template <bool STICKY>
+__device__ __forceinline__ BpsColumn bps_column(const BpsConsumeArgs& P, int64_t s, int64_t i) {
+    BpsColumn c;
+    c.x = P.ev_x[s * P.d + i];
+    c.th = P.ev_th[s * P.d + i];
+    c.f = bps_free_bit<STICKY>(P.ev_f + s * BPS_STICKY_WORDS, i);
+    return c;
+}
+template <bool STICKY>
+__device__ __forceinline__ BpsColumn bps_cursor(const BpsConsumeArgs& P, int64_t chain, int64_t i) {
+    BpsColumn c;
+    c.x = P.cx[chain * P.d + i];
+    c.th = P.cth[chain * P.d + i];
+    c.f = bps_free_bit<STICKY>(static_cast<const BpsConsumeMeta*>(P.meta) + chain * P.nstrips, i);
+    return c;
+}
 
 struct BpsConsumeEvent {
     double t, x, th;
-    uint64_t f;
+    uint64_t f;  // (the whole mask word of the strip: the meta record carries it)
 };
-
-constexpr int BC_AHEAD = 4;
 
 __global__ __launch_bounds__(256) void bps_consume_init_kernel(BpsConsumeArgs P) {
     const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -67,8 +142,7 @@ __global__ __launch_bounds__(256) void bps_consume_init_kernel(BpsConsumeArgs P)
 }
 
 template <bool STICKY>
-__device__ __forceinline__ BpsConsumeEvent bc_load(const BpsConsumeArgs& P, int64_t slot0, uint64_t e, uint64_t n, int64_t strip, int64_t ic) {
-    const int64_t s = slot0 + (int64_t)(e < n ? e : n - 1);  // (behind the segment: its last event once more, never applied)
+__device__ __forceinline__ BpsConsumeEvent bc_load(const BpsConsumeArgs& P, int64_t s, int64_t strip, int64_t ic) {
     BpsConsumeEvent ev;
     ev.t = P.ev_t[s];
     ev.x = P.ev_x[s * P.d + ic];
@@ -86,30 +160,20 @@ __global__ __launch_bounds__(256) void bps_consume_kernel(BpsConsumeArgs P) {
     const int64_t d = P.d, i = strip * 64 + lane;
     const bool live = i < d;
     const int64_t ic = live ? i : d - 1;
-    BpsConsumeMeta m = static_cast<BpsConsumeMeta*>(P.meta)[w];
-    const uint64_t ntrace = P.hdr[chain].c.ntrace, nevents = P.hdr[chain].c.nevents;
-    const uint64_t n = ntrace < (uint64_t)P.cap ? ntrace : (uint64_t)P.cap;
-    const uint64_t first_global = nevents - ntrace;  // global index of buffer slot 0
-    const uint64_t pos = (m.consumed > first_global) ? (m.consumed - first_global) : 0;  // first unconsumed slot
-    if (pos >= n) return;
+    const BpsSlice sl = bps_slice(P, chain, strip);
+    if (sl.pos >= sl.n) return;
+    BpsConsumeMeta m = sl.m;
     const int64_t slot0 = chain * P.cap, cur = chain * d + ic;
     double x = P.cx[cur], th = P.cth[cur], y = P.cy[cur];
     double ft = STICKY ? P.cft[cur] : 0.0;
     const double mu = BOOM ? P.mu[ic] : 0.0;
     double* const grid = (P.grid && P.K > 0) ? P.grid + chain * P.K * d : nullptr;
 
-    BpsConsumeEvent now[BC_AHEAD], next[BC_AHEAD];
-#pragma unroll
-    for (int q = 0; q < BC_AHEAD; ++q) now[q] = bc_load<STICKY>(P, slot0, pos + q, n, strip, ic);
-    for (uint64_t base = pos; base < n; base += BC_AHEAD) {
-#pragma unroll
-        for (int q = 0; q < BC_AHEAD; ++q) next[q] = bc_load<STICKY>(P, slot0, base + BC_AHEAD + q, n, strip, ic);
-#pragma unroll
-        for (int q = 0; q < BC_AHEAD; ++q) {
-            const uint64_t e = base + q;
-            if (e >= n) break;
-            const double t2 = now[q].t;
-            const bool free = !STICKY || ((m.free >> lane) & 1ull);
+    bps_walk<BpsConsumeEvent>(
+        sl.pos, sl.n, [&](uint64_t e) BPS_WALK_INLINE { return bc_load<STICKY>(P, slot0 + (int64_t)e, strip, ic); },
+        [&](const BpsConsumeEvent& ev, uint64_t e) BPS_WALK_INLINE {
+            const double t2 = ev.t;
+            const bool free = !STICKY || ((m.free >> lane) & 1ull);  // (bps_free_bit of the word in hand: bit `lane` of word `strip`)
             while (grid && m.k < P.K) {
                 const double g = P.t0 + (double)m.k * P.dt;
                 if (!(g < t2)) break;
@@ -127,17 +191,14 @@ __global__ __launch_bounds__(256) void bps_consume_kernel(BpsConsumeArgs P) {
                 m.k += 1;
             }
             const double dtau = t2 - m.t_cur;
-            y = y + (x + now[q].x) * dtau;
+            y = y + (x + ev.x) * dtau;
             if (P.cm && live) P.cm[(slot0 + (int64_t)e) * d + i] = y / (2.0 * t2);
             if (STICKY) ft = ft + (free ? dtau : 0.0);
-            x = now[q].x;
-            th = now[q].th;
-            m.free = now[q].f;
+            x = ev.x;
+            th = ev.th;
+            m.free = ev.f;
             m.t_cur = m.t_last = t2;
-        }
-#pragma unroll
-        for (int q = 0; q < BC_AHEAD; ++q) now[q] = next[q];
-    }
+        });
     if (live) {
         P.cx[cur] = x;
         P.cth[cur] = th;
@@ -145,7 +206,7 @@ __global__ __launch_bounds__(256) void bps_consume_kernel(BpsConsumeArgs P) {
         if (STICKY) P.cft[cur] = ft;
     }
     if (lane == 0) {
-        m.consumed = nevents;
+        m.consumed = sl.nevents;
         static_cast<BpsConsumeMeta*>(P.meta)[w] = m;
     }
 }
@@ -198,34 +259,19 @@ int launch_bps_consume_read(const BpsConsumeArgs& p, int inclusion, int64_t chai
 //                         elements l, l + 64, ..., then wave_sum_f64; τ of a hit (−1 otherwise) to the segment's slot of a [nchains x cap] array.
 //   bps_cond_rows_kernel  one workgroup per chain: chunks of 256 slots compacted in order by a block prefix count, every hit's time and row written by
 //                         the whole workgroup, four strips at a time.  The hit count is NOT clamped to max_hits; rows behind it are dropped.
-struct BpsCondSlice {
-    uint64_t pos, n;  // the unconsumed slots [pos, n) of the chain's segment
-    double t_cur;
-};
-__device__ __forceinline__ BpsCondSlice bps_cond_slice(const BpsConsumeArgs& P, int64_t chain) {
-    const BpsConsumeMeta m = static_cast<const BpsConsumeMeta*>(P.meta)[chain * P.nstrips];  // (strip 0's copy of the chain's progress)
-    const uint64_t ntrace = P.hdr[chain].c.ntrace, nevents = P.hdr[chain].c.nevents;
-    BpsCondSlice s;
-    s.n = ntrace < (uint64_t)P.cap ? ntrace : (uint64_t)P.cap;
-    const uint64_t first_global = nevents - ntrace;
-    s.pos = (m.consumed > first_global) ? (m.consumed - first_global) : 0;
-    s.t_cur = m.t_cur;
-    return s;
-}
-
 __global__ __launch_bounds__(256) void bps_cond_scan_kernel(BpsConsumeArgs P, BpsCondArgs Q) {
     const int lane = threadIdx.x & 63;
     const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (w >= P.nchains * P.cap) return;
     const int64_t chain = w / P.cap;
     const uint64_t e = (uint64_t)(w - chain * P.cap);
-    const BpsCondSlice sl = bps_cond_slice(P, chain);
+    const BpsSlice sl = bps_slice(P, chain);
     if (e < sl.pos || e >= sl.n) return;
     const int64_t d = P.d, slot0 = chain * P.cap;
     const bool first = e == sl.pos;
     const double* const xc = first ? P.cx + chain * d : P.ev_x + (slot0 + (int64_t)e - 1) * d;
     const double* const thc = first ? P.cth + chain * d : P.ev_th + (slot0 + (int64_t)e - 1) * d;
-    const double t_c = first ? sl.t_cur : P.ev_t[slot0 + (int64_t)e - 1];
+    const double t_c = first ? sl.m.t_cur : P.ev_t[slot0 + (int64_t)e - 1];
     const double t_k = P.ev_t[slot0 + (int64_t)e];
     double pg = 0.0, ph = 0.0;
     for (int64_t k = lane; k < d; k += 64) {
@@ -245,7 +291,7 @@ __global__ __launch_bounds__(256) void bps_cond_rows_kernel(BpsConsumeArgs P, Bp
     __shared__ double s_tau[256];
     const int tid = threadIdx.x;
     const int64_t chain = blockIdx.x;
-    const BpsCondSlice sl = bps_cond_slice(P, chain);
+    const BpsSlice sl = bps_slice(P, chain);
     if (sl.pos >= sl.n) return;
     const int64_t d = P.d, slot0 = chain * P.cap;
     const BpsConsumeMeta* const meta = static_cast<const BpsConsumeMeta*>(P.meta) + chain * P.nstrips;
@@ -276,14 +322,10 @@ __global__ __launch_bounds__(256) void bps_cond_rows_kernel(BpsConsumeArgs P, Bp
             const bool first = eh == sl.pos;
             const double* const xc = first ? P.cx + chain * d : P.ev_x + (slot0 + (int64_t)eh - 1) * d;
             const double* const thc = first ? P.cth + chain * d : P.ev_th + (slot0 + (int64_t)eh - 1) * d;
-            if (tid == 0) Q.hit_t[chain * Q.max_hits + (int64_t)q] = (first ? sl.t_cur : P.ev_t[slot0 + (int64_t)eh - 1]) + th;
+            if (tid == 0) Q.hit_t[chain * Q.max_hits + (int64_t)q] = (first ? sl.m.t_cur : P.ev_t[slot0 + (int64_t)eh - 1]) + th;
             double* const row = Q.hit_x + (chain * Q.max_hits + (int64_t)q) * d;
             for (int64_t j = tid; j < d; j += 256) {
-                bool free = true;
-                if (STICKY) {
-                    const uint64_t w = first ? meta[j >> 6].free : P.ev_f[(slot0 + (int64_t)eh - 1) * BPS_STICKY_WORDS + (j >> 6)];
-                    free = (w >> (j & 63)) & 1ull;
-                }
+                const bool free = first ? bps_free_bit<STICKY>(meta, j) : bps_free_bit<STICKY>(P.ev_f + (slot0 + (int64_t)eh - 1) * BPS_STICKY_WORDS, j);
                 const double x = xc[j];
                 row[j] = free ? x + thc[j] * th : x;  // smove_forward!, src/ss_not_fact.jl:78-86
             }
@@ -309,105 +351,28 @@ int launch_bps_cond(const BpsConsumeArgs& p, const BpsCondArgs& q, void* stream)
 // (DESIGN.md "Pair integrals"; tests/ref/pairs_ref.c states the contract).  An event replaces the whole state, so every pair's piece of an event
 // (t_k, ...) runs over [t_c, t_k] from the cursor before it: a = x_c,i − c_i, v_i = f_c,i ? θ_c,i : 0 (a coordinate that is not free keeps x).
 // One thread per (chain, pair) walks the chain's segment with S in a register; behind the pairs of a chain one thread per coordinate keeps J in the
-// same way (so a coordinate in no pair has its J).  The threads of a workgroup belong to one chain: the event times are wave-uniform loads, the
-// positions and velocities gathers of the pair's two columns; the loads of the next BC_AHEAD events are issued before the arithmetic of the
-// current ones, as in bps_consume_kernel.  Runs BEFORE bps_consume_kernel of the same slice and only reads what that kernel carries.
+// same way (so a coordinate in no pair has its J).  The positions and velocities are gathers of the pair's two columns.
+//
+// Pair integrals of arcs (ARC: the event-recorded Boomerang and its sticky form; DESIGN.md "Pair integrals of arcs"; tests/ref/arc_pairs_ref.c
+// states the contract): between two events a free coordinate rotates about μ: on the piece [t_c, t_k] of an event,
+// x(s) − z = u·cos s + p·sin s + m with u = x_c − μ, p = θ_c, m = μ − z -- a coordinate that is not free: u = p = 0, m = x_c − z --, so a pair's
+// piece is a combination of the five integrals of cos², sin², sin·cos, cos and sin over [0, τ], τ = t_k − t_c signed.  τ is wave-uniform:
+// every thread evaluates pdmp_sincos(τ) and the five integrals once per event, without divergence, before its pair arithmetic.
 struct BpsPairEvent {
-    double t, xi, thi, xj, thj;
-    bool fi, fj;
+    double t;
+    BpsColumn i, j;
 };
 
 template <bool STICKY>
-__device__ __forceinline__ BpsPairEvent bp_load(const BpsConsumeArgs& P, int64_t slot0, uint64_t e, uint64_t n, int64_t i, int64_t j) {
-    const int64_t s = slot0 + (int64_t)(e < n ? e : n - 1);  // (behind the segment: its last event once more, never applied)
+__device__ __forceinline__ BpsPairEvent bp_load(const BpsConsumeArgs& P, int64_t s, int64_t i, int64_t j) {
     BpsPairEvent ev;
     ev.t = P.ev_t[s];
-    ev.xi = P.ev_x[s * P.d + i];
-    ev.thi = P.ev_th[s * P.d + i];
-    ev.fi = STICKY ? ((P.ev_f[s * BPS_STICKY_WORDS + (i >> 6)] >> (i & 63)) & 1ull) != 0 : true;
-    if (j == i) {  // (a diagonal pair, or a J thread: one column)
-        ev.xj = ev.xi;
-        ev.thj = ev.thi;
-        ev.fj = ev.fi;
-        return ev;
-    }
-    ev.xj = P.ev_x[s * P.d + j];
-    ev.thj = P.ev_th[s * P.d + j];
-    ev.fj = STICKY ? ((P.ev_f[s * BPS_STICKY_WORDS + (j >> 6)] >> (j & 63)) & 1ull) != 0 : true;
+    ev.i = bps_column<STICKY>(P, s, i);
+    if (j == i) ev.j = ev.i;  // (a diagonal pair, or a J thread: one column)
+    else ev.j = bps_column<STICKY>(P, s, j);
     return ev;
 }
 
-template <bool STICKY>
-__global__ __launch_bounds__(256) void bps_pairs_kernel(BpsConsumeArgs P, BpsPairArgs Q, int64_t blocks_per_chain) {
-    const int64_t chain = (int64_t)blockIdx.x / blocks_per_chain;
-    const int64_t r = ((int64_t)blockIdx.x - chain * blocks_per_chain) * 256 + threadIdx.x;
-    const int64_t d = P.d;
-    if (r >= Q.npairs + d) return;
-    const BpsCondSlice sl = bps_cond_slice(P, chain);
-    if (sl.pos >= sl.n) return;
-    const bool is_pair = r < Q.npairs;
-    const int64_t i = is_pair ? Q.pi[r] : r - Q.npairs, j = is_pair ? Q.pj[r] : i;
-    double* const acc_at = is_pair ? Q.S + chain * Q.npairs + r : Q.J + chain * d + i;
-    const BpsConsumeMeta* const meta = static_cast<const BpsConsumeMeta*>(P.meta) + chain * P.nstrips;
-    const int64_t slot0 = chain * P.cap;
-    const double ci = Q.center[i], cj = Q.center[j];
-    double acc = *acc_at, t_cur = sl.t_cur;
-    double xi = P.cx[chain * d + i], thi = P.cth[chain * d + i], xj = P.cx[chain * d + j], thj = P.cth[chain * d + j];
-    bool fi = STICKY ? ((meta[i >> 6].free >> (i & 63)) & 1ull) != 0 : true, fj = STICKY ? ((meta[j >> 6].free >> (j & 63)) & 1ull) != 0 : true;
-
-    BpsPairEvent now[BC_AHEAD], next[BC_AHEAD];
-#pragma unroll
-    for (int q = 0; q < BC_AHEAD; ++q) now[q] = bp_load<STICKY>(P, slot0, sl.pos + q, sl.n, i, j);
-    for (uint64_t base = sl.pos; base < sl.n; base += BC_AHEAD) {
-#pragma unroll
-        for (int q = 0; q < BC_AHEAD; ++q) next[q] = bp_load<STICKY>(P, slot0, base + BC_AHEAD + q, sl.n, i, j);
-#pragma unroll
-        for (int q = 0; q < BC_AHEAD; ++q) {
-            if (base + q >= sl.n) break;
-            const double tau = now[q].t - t_cur;
-            const double vi = fi ? thi : 0.0, vj = fj ? thj : 0.0;
-            acc = acc + (is_pair ? pair_piece(xi - ci, xj - cj, vi, vj, tau) : line_piece(xi - ci, vi, tau));
-            xi = now[q].xi;
-            thi = now[q].thi;
-            xj = now[q].xj;
-            thj = now[q].thj;
-            fi = now[q].fi;
-            fj = now[q].fj;
-            t_cur = now[q].t;
-        }
-#pragma unroll
-        for (int q = 0; q < BC_AHEAD; ++q) now[q] = next[q];
-    }
-    *acc_at = acc;
-}
-
-__global__ __launch_bounds__(256) void bps_pairs_tlast_kernel(BpsConsumeArgs P, int64_t chain_first, int64_t n, double* T_out) {
-    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (q < n) T_out[q] = static_cast<const BpsConsumeMeta*>(P.meta)[(chain_first + q) * P.nstrips].t_last;
-}
-
-int launch_bps_pairs(const BpsConsumeArgs& p, const BpsPairArgs& q, void* stream) {
-    const int64_t bpc = (q.npairs + p.d + 255) / 256;
-    const dim3 grid((unsigned)(p.nchains * bpc)), block(256);
-    if (p.ev_f) hipLaunchKernelGGL((bps_pairs_kernel<true>), grid, block, 0, (hipStream_t)stream, p, q, bpc);
-    else hipLaunchKernelGGL((bps_pairs_kernel<false>), grid, block, 0, (hipStream_t)stream, p, q, bpc);
-    return (int)hipGetLastError();
-}
-
-int launch_bps_pairs_tlast(const BpsConsumeArgs& p, int64_t chain_first, int64_t n, double* T_out, void* stream) {
-    hipLaunchKernelGGL(bps_pairs_tlast_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, chain_first, n, T_out);
-    return (int)hipGetLastError();
-}
-
-// ------------------------------------------------------------------------------------------ pair integrals of arcs (covariance of a Boomerang's trace)
-//
-// The same S_ij and J_i over [t0, T_last] for the event-recorded Boomerang and its sticky form (DESIGN.md "Pair integrals of arcs";
-// tests/ref/arc_pairs_ref.c states the contract).  Between two events a free coordinate rotates about μ: on the piece [t_c, t_k] of an event,
-// x(s) − z = u·cos s + p·sin s + m with u = x_c − μ, p = θ_c, m = μ − z -- a coordinate that is not free: u = p = 0, m = x_c − z --, so a pair's
-// piece is a combination of the five integrals of cos², sin², sin·cos, cos and sin over [0, τ], τ = t_k − t_c signed.  τ is wave-uniform (the
-// threads of a workgroup belong to one chain): every thread evaluates pdmp_sincos(τ) and the five integrals once per event, without divergence,
-// before its pair arithmetic.  The walk, the loads and the accumulators are those of bps_pairs_kernel; runs BEFORE bps_consume_kernel of the
-// same slice and only reads what that kernel carries.
 struct ArcBasis {
     double Icc, Iss, Isc, Ic, Is;
 };
@@ -432,57 +397,60 @@ __device__ __forceinline__ double arc_pair_piece(double ui, double pi, double mi
 }
 __device__ __forceinline__ double arc_line_piece(double u, double p, double m, double tau, const ArcBasis& b) { return (u * b.Ic + p * b.Is) + m * tau; }
 
-template <bool STICKY>
-__global__ __launch_bounds__(256) void bps_arc_pairs_kernel(BpsConsumeArgs P, BpsPairArgs Q, int64_t blocks_per_chain) {
+template <bool ARC, bool STICKY>
+__global__ __launch_bounds__(256) void bps_pairs_kernel(BpsConsumeArgs P, BpsPairArgs Q, int64_t blocks_per_chain) {
     const int64_t chain = (int64_t)blockIdx.x / blocks_per_chain;
     const int64_t r = ((int64_t)blockIdx.x - chain * blocks_per_chain) * 256 + threadIdx.x;
     const int64_t d = P.d;
     if (r >= Q.npairs + d) return;
-    const BpsCondSlice sl = bps_cond_slice(P, chain);
+    const BpsSlice sl = bps_slice(P, chain);
     if (sl.pos >= sl.n) return;
     const bool is_pair = r < Q.npairs;
     const int64_t i = is_pair ? Q.pi[r] : r - Q.npairs, j = is_pair ? Q.pj[r] : i;
     double* const acc_at = is_pair ? Q.S + chain * Q.npairs + r : Q.J + chain * d + i;
-    const BpsConsumeMeta* const meta = static_cast<const BpsConsumeMeta*>(P.meta) + chain * P.nstrips;
     const int64_t slot0 = chain * P.cap;
-    const double mui = P.mu[i], muj = P.mu[j], zi = Q.center[i], zj = Q.center[j];
-    double acc = *acc_at, t_cur = sl.t_cur;
-    double xi = P.cx[chain * d + i], thi = P.cth[chain * d + i], xj = P.cx[chain * d + j], thj = P.cth[chain * d + j];
-    bool fi = STICKY ? ((meta[i >> 6].free >> (i & 63)) & 1ull) != 0 : true, fj = STICKY ? ((meta[j >> 6].free >> (j & 63)) & 1ull) != 0 : true;
+    const double mui = ARC ? P.mu[i] : 0.0, muj = ARC ? P.mu[j] : 0.0, ci = Q.center[i], cj = Q.center[j];
+    double acc = *acc_at, t_cur = sl.m.t_cur;
+    BpsColumn a = bps_cursor<STICKY>(P, chain, i), b = bps_cursor<STICKY>(P, chain, j);
 
-    BpsPairEvent now[BC_AHEAD], next[BC_AHEAD];
-#pragma unroll
-    for (int q = 0; q < BC_AHEAD; ++q) now[q] = bp_load<STICKY>(P, slot0, sl.pos + q, sl.n, i, j);
-    for (uint64_t base = sl.pos; base < sl.n; base += BC_AHEAD) {
-#pragma unroll
-        for (int q = 0; q < BC_AHEAD; ++q) next[q] = bp_load<STICKY>(P, slot0, base + BC_AHEAD + q, sl.n, i, j);
-#pragma unroll
-        for (int q = 0; q < BC_AHEAD; ++q) {
-            if (base + q >= sl.n) break;
-            const double tau = now[q].t - t_cur;
-            const ArcBasis b = arc_basis_of(tau);
-            const double ui = fi ? xi - mui : 0.0, pi = fi ? thi : 0.0, mi = fi ? mui - zi : xi - zi;
-            const double uj = fj ? xj - muj : 0.0, pj = fj ? thj : 0.0, mj = fj ? muj - zj : xj - zj;
-            acc = acc + (is_pair ? arc_pair_piece(ui, pi, mi, uj, pj, mj, tau, b) : arc_line_piece(ui, pi, mi, tau, b));
-            xi = now[q].xi;
-            thi = now[q].thi;
-            xj = now[q].xj;
-            thj = now[q].thj;
-            fi = now[q].fi;
-            fj = now[q].fj;
-            t_cur = now[q].t;
-        }
-#pragma unroll
-        for (int q = 0; q < BC_AHEAD; ++q) now[q] = next[q];
-    }
+    bps_walk<BpsPairEvent>(
+        sl.pos, sl.n, [&](uint64_t e) BPS_WALK_INLINE { return bp_load<STICKY>(P, slot0 + (int64_t)e, i, j); },
+        [&](const BpsPairEvent& ev, uint64_t) BPS_WALK_INLINE {
+            const double tau = ev.t - t_cur;
+            if (ARC) {
+                const ArcBasis B = arc_basis_of(tau);
+                const double ui = a.f ? a.x - mui : 0.0, pi = a.f ? a.th : 0.0, mi = a.f ? mui - ci : a.x - ci;
+                const double uj = b.f ? b.x - muj : 0.0, pj = b.f ? b.th : 0.0, mj = b.f ? muj - cj : b.x - cj;
+                acc = acc + (is_pair ? arc_pair_piece(ui, pi, mi, uj, pj, mj, tau, B) : arc_line_piece(ui, pi, mi, tau, B));
+            } else {
+                const double vi = a.f ? a.th : 0.0, vj = b.f ? b.th : 0.0;
+                acc = acc + (is_pair ? pair_piece(a.x - ci, b.x - cj, vi, vj, tau) : line_piece(a.x - ci, vi, tau));
+            }
+            a = ev.i;
+            b = ev.j;
+            t_cur = ev.t;
+        });
     *acc_at = acc;
 }
 
-int launch_bps_arc_pairs(const BpsConsumeArgs& p, const BpsPairArgs& q, void* stream) {
+__global__ __launch_bounds__(256) void bps_tlast_kernel(BpsConsumeArgs P, int64_t chain_first, int64_t n, double* T_out) {
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (q < n) T_out[q] = static_cast<const BpsConsumeMeta*>(P.meta)[(chain_first + q) * P.nstrips].t_last;
+}
+
+int launch_bps_pairs(const BpsConsumeArgs& p, const BpsPairArgs& q, bool arc, void* stream) {
     const int64_t bpc = (q.npairs + p.d + 255) / 256;
     const dim3 grid((unsigned)(p.nchains * bpc)), block(256);
-    if (p.ev_f) hipLaunchKernelGGL((bps_arc_pairs_kernel<true>), grid, block, 0, (hipStream_t)stream, p, q, bpc);
-    else hipLaunchKernelGGL((bps_arc_pairs_kernel<false>), grid, block, 0, (hipStream_t)stream, p, q, bpc);
+    const bool sticky = p.ev_f != nullptr;
+    if (arc && sticky) hipLaunchKernelGGL((bps_pairs_kernel<true, true>), grid, block, 0, (hipStream_t)stream, p, q, bpc);
+    else if (arc) hipLaunchKernelGGL((bps_pairs_kernel<true, false>), grid, block, 0, (hipStream_t)stream, p, q, bpc);
+    else if (sticky) hipLaunchKernelGGL((bps_pairs_kernel<false, true>), grid, block, 0, (hipStream_t)stream, p, q, bpc);
+    else hipLaunchKernelGGL((bps_pairs_kernel<false, false>), grid, block, 0, (hipStream_t)stream, p, q, bpc);
+    return (int)hipGetLastError();
+}
+
+int launch_bps_tlast(const BpsConsumeArgs& p, int64_t chain_first, int64_t n, double* T_out, void* stream) {
+    hipLaunchKernelGGL(bps_tlast_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, chain_first, n, T_out);
     return (int)hipGetLastError();
 }
 
@@ -493,23 +461,27 @@ int launch_bps_arc_pairs(const BpsConsumeArgs& p, const BpsPairArgs& q, void* st
 // whole state, so the piece of an event (t_k, ...) is (x_c,i, f_c,i ? θ_c,i : 0, t_k − t_c) from the cursor before it, for every listed coordinate.
 // The listed coordinates of a chain lie across the lanes: one thread per (chain, listed coordinate) walks the chain's segment in event order and
 // adds each piece to the bins it touches.  A row belongs to one thread, so lanes never share an entry and nothing is atomic; the rest time Z stays
-// in a register.  The threads of a workgroup belong to one chain: the event times are wave-uniform loads; the loads of the next BC_AHEAD events are
-// issued before the arithmetic of the current ones, as in bps_consume_kernel.  Runs BEFORE bps_consume_kernel of the same slice and only reads what
-// that kernel carries.  Nothing is open behind the last event: the rows are the result, the pooled read only adds the chains in order.
+// in a register.  Nothing is open behind the last event: the rows are the result, the pooled read only adds the chains in order.
 struct BpsHistEvent {
-    double t, x, th;
-    bool f;
+    double t;
+    BpsColumn c;
 };
 
 template <bool STICKY>
-__device__ __forceinline__ BpsHistEvent bh_load(const BpsConsumeArgs& P, int64_t slot0, uint64_t e, uint64_t n, int64_t i) {
-    const int64_t s = slot0 + (int64_t)(e < n ? e : n - 1);  // (behind the segment: its last event once more, never applied)
+__device__ __forceinline__ BpsHistEvent bh_load(const BpsConsumeArgs& P, int64_t s, int64_t i) {
     BpsHistEvent ev;
     ev.t = P.ev_t[s];
-    ev.x = P.ev_x[s * P.d + i];
-    ev.th = P.ev_th[s * P.d + i];
-    ev.f = STICKY ? ((P.ev_f[s * BPS_STICKY_WORDS + (i >> 6)] >> (i & 63)) & 1ull) != 0 : true;
+    ev.c = bps_column<STICKY>(P, s, i);
     return ev;
+}
+
+__device__ __forceinline__ HistBins bps_hist_bins(const BpsHistArgs& Q, int64_t s) {
+    HistBins bn;
+    bn.lo = Q.lo[s];
+    bn.hi = Q.hi[s];
+    bn.w = Q.w[s];
+    bn.B = Q.B;
+    return bn;
 }
 
 template <bool STICKY>
@@ -517,42 +489,25 @@ __global__ __launch_bounds__(256) void bps_hist_kernel(BpsConsumeArgs P, BpsHist
     const int64_t chain = (int64_t)blockIdx.x / blocks_per_chain;
     const int64_t s = ((int64_t)blockIdx.x - chain * blocks_per_chain) * 256 + threadIdx.x;
     if (s >= Q.m) return;
-    const BpsCondSlice sl = bps_cond_slice(P, chain);
+    const BpsSlice sl = bps_slice(P, chain);
     if (sl.pos >= sl.n) return;
-    const int64_t d = P.d, i = Q.coords[s];
-    HistBins bn;
-    bn.lo = Q.lo[s];
-    bn.hi = Q.hi[s];
-    bn.w = Q.w[s];
-    bn.B = Q.B;
+    const int64_t i = Q.coords[s];
+    const HistBins bn = bps_hist_bins(Q, s);
     double* const row = Q.H + (chain * Q.m + s) * (int64_t)(Q.B + 2);
-    const BpsConsumeMeta* const meta = static_cast<const BpsConsumeMeta*>(P.meta) + chain * P.nstrips;
     const int64_t slot0 = chain * P.cap;
-    double Z = Q.Z[chain * Q.m + s], t_cur = sl.t_cur;
-    double x = P.cx[chain * d + i], th = P.cth[chain * d + i];
-    bool f = STICKY ? ((meta[i >> 6].free >> (i & 63)) & 1ull) != 0 : true;
+    double Z = Q.Z[chain * Q.m + s], t_cur = sl.m.t_cur;
+    BpsColumn c = bps_cursor<STICKY>(P, chain, i);
 
-    BpsHistEvent now[BC_AHEAD], next[BC_AHEAD];
-#pragma unroll
-    for (int q = 0; q < BC_AHEAD; ++q) now[q] = bh_load<STICKY>(P, slot0, sl.pos + q, sl.n, i);
-    for (uint64_t base = sl.pos; base < sl.n; base += BC_AHEAD) {
-#pragma unroll
-        for (int q = 0; q < BC_AHEAD; ++q) next[q] = bh_load<STICKY>(P, slot0, base + BC_AHEAD + q, sl.n, i);
-#pragma unroll
-        for (int q = 0; q < BC_AHEAD; ++q) {
-            if (base + q >= sl.n) break;
-            const double tau = now[q].t - t_cur, v = f ? th : 0.0;
-            const HistPiece p = hist_piece_of(bn, x, v, tau);
+    bps_walk<BpsHistEvent>(
+        sl.pos, sl.n, [&](uint64_t e) BPS_WALK_INLINE { return bh_load<STICKY>(P, slot0 + (int64_t)e, i); },
+        [&](const BpsHistEvent& ev, uint64_t) BPS_WALK_INLINE {
+            const double tau = ev.t - t_cur, v = c.f ? c.th : 0.0;
+            const HistPiece p = hist_piece_of(bn, c.x, v, tau);
             for (int k = p.k0; k <= p.k1; ++k) row[k + 1] = row[k + 1] + hist_piece_at(bn, p, k);
             Z = Z + hist_piece_rest(v, tau);
-            x = now[q].x;
-            th = now[q].th;
-            f = now[q].f;
-            t_cur = now[q].t;
-        }
-#pragma unroll
-        for (int q = 0; q < BC_AHEAD; ++q) now[q] = next[q];
-    }
+            c = ev.c;
+            t_cur = ev.t;
+        });
     Q.Z[chain * Q.m + s] = Z;
 }
 
@@ -596,9 +551,8 @@ int launch_bps_hist_pool(const BpsHistArgs& q, int64_t chain_first, int64_t n, d
 // owns the slots l and l + 64 of the row IN REGISTERS for the whole slice (one load before, one store behind); a longer row is added to in
 // global memory, 64 slots at a time, slot j always by lane j & 63 (a piece at rest too: one owning lane per slot on either path), slots with
 // nothing to add skipped (x + 0.0 has the bits of x: no entry is ever −0.0).  Each slot is added
-// to in the event order of its chain from the value in memory and nothing is atomic, so the bits do not depend on the slicing.  Event loads
-// are wave-uniform; those of the next BC_AHEAD events are in flight, as in the other walkers.  Runs BEFORE bps_consume_kernel of the same
-// slice and only reads what that kernel carries.
+// to in the event order of its chain from the value in memory and nothing is atomic, so the bits do not depend on the slicing.  All of a
+// wavefront's event loads are uniform.
 struct ArcPiece {
     double tau, mu, R, n0, r0, n1, r1;
     bool live, rest;
@@ -651,38 +605,26 @@ __global__ __launch_bounds__(256) void bps_arc_hist_kernel(BpsConsumeArgs P, Bps
     const int lane = (int)(threadIdx.x & 63);
     const int64_t s = ((int64_t)blockIdx.x - chain * blocks_per_chain) * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (s >= Q.m) return;
-    const BpsCondSlice sl = bps_cond_slice(P, chain);
+    const BpsSlice sl = bps_slice(P, chain);
     if (sl.pos >= sl.n) return;
-    const int64_t d = P.d, i = Q.coords[s];
-    HistBins bn;
-    bn.lo = Q.lo[s];
-    bn.hi = Q.hi[s];
-    bn.w = Q.w[s];
-    bn.B = Q.B;
+    const int64_t i = Q.coords[s];
+    const HistBins bn = bps_hist_bins(Q, s);
     const int slots = Q.B + 2;
     double* const row = Q.H + (chain * Q.m + s) * (int64_t)slots;
-    const BpsConsumeMeta* const meta = static_cast<const BpsConsumeMeta*>(P.meta) + chain * P.nstrips;
     const int64_t slot0 = chain * P.cap;
     const double mu = P.mu[i];
-    double Z = Q.Z[chain * Q.m + s], t_cur = sl.t_cur;
-    double x = P.cx[chain * d + i], th = P.cth[chain * d + i];
-    bool f = STICKY ? ((meta[i >> 6].free >> (i & 63)) & 1ull) != 0 : true;
+    double Z = Q.Z[chain * Q.m + s], t_cur = sl.m.t_cur;
+    BpsColumn c = bps_cursor<STICKY>(P, chain, i);
 
     // (the short row: slot j holds the time in [e_j−1, e_j); lane l owns j = l and j = l + 64 and evaluates their upper edges)
     const bool two = !LONG_ROW && slots > 64, own0 = lane < slots, own1 = lane + 64 < slots;
     const double y0 = hist_edge(bn, lane), y1 = hist_edge(bn, lane + 64);
     double h0 = (!LONG_ROW && own0) ? row[lane] : 0.0, h1 = (!LONG_ROW && own1) ? row[lane + 64] : 0.0;
 
-    BpsHistEvent now[BC_AHEAD], next[BC_AHEAD];
-#pragma unroll
-    for (int q = 0; q < BC_AHEAD; ++q) now[q] = bh_load<STICKY>(P, slot0, sl.pos + q, sl.n, i);
-    for (uint64_t base = sl.pos; base < sl.n; base += BC_AHEAD) {
-#pragma unroll
-        for (int q = 0; q < BC_AHEAD; ++q) next[q] = bh_load<STICKY>(P, slot0, base + BC_AHEAD + q, sl.n, i);
-#pragma unroll
-        for (int q = 0; q < BC_AHEAD; ++q) {
-            if (base + q >= sl.n) break;
-            const ArcPiece a = arc_piece_of(bn, x, th, f, mu, now[q].t - t_cur);  // (uniform over the wavefront, and so is every branch on it)
+    bps_walk<BpsHistEvent>(
+        sl.pos, sl.n, [&](uint64_t e) BPS_WALK_INLINE { return bh_load<STICKY>(P, slot0 + (int64_t)e, i); },
+        [&](const BpsHistEvent& ev, uint64_t) BPS_WALK_INLINE {
+            const ArcPiece a = arc_piece_of(bn, c.x, c.th, c.f, mu, ev.t - t_cur);  // (uniform over the wavefront, and so is every branch on it)
             if (a.live && a.rest) {
                 const int j = a.krest + 1;
                 if (LONG_ROW) {
@@ -709,14 +651,9 @@ __global__ __launch_bounds__(256) void bps_arc_hist_kernel(BpsConsumeArgs P, Bps
                     if (j < slots && o > 0.0) row[j] = row[j] + o;
                 }
             }
-            x = now[q].x;
-            th = now[q].th;
-            f = now[q].f;
-            t_cur = now[q].t;
-        }
-#pragma unroll
-        for (int q = 0; q < BC_AHEAD; ++q) now[q] = next[q];
-    }
+            c = ev.c;
+            t_cur = ev.t;
+        });
     if (!LONG_ROW) {
         if (own0) row[lane] = h0;
         if (own1) row[lane + 64] = h1;

@@ -683,6 +683,7 @@ struct BpsConsumeArgs {
     double t0, dt;
 };
 size_t bps_consume_meta_bytes();
+size_t bps_consume_meta_tlast_offset();  // (byte offset of a chain's T_last in its progress record)
 int launch_bps_consume_init(const BpsConsumeArgs& p, void* stream);
 int launch_bps_consume_events(const BpsConsumeArgs& p, void* stream);
 int launch_bps_consume_read(const BpsConsumeArgs& p, int inclusion, int64_t chain_first, int64_t n, double* out, double* T_out, void* stream);
@@ -696,17 +697,17 @@ struct BpsCondArgs {
 };
 int launch_bps_cond(const BpsConsumeArgs& p, const BpsCondArgs& q, void* stream);
 // ... the pair integrals (pdmp_ensemble_bps_consume_pairs): the pair list, the centre [d], S [nchains x npairs] and J [nchains x d]; launched before
-// launch_bps_consume_events of the same slice
+// launch_bps_consume_events of the same slice.  arc: the same integrals of a Boomerang's arcs (pdmp_ensemble_bps_consume_arc_pairs; p.mu is the
+// flow's centre), with the same arguments and accumulators
 struct BpsPairArgs {
     const int32_t *pi, *pj;
     const double* center;
     double *S, *J;
     int64_t npairs;
 };
-int launch_bps_pairs(const BpsConsumeArgs& p, const BpsPairArgs& q, void* stream);
-int launch_bps_pairs_tlast(const BpsConsumeArgs& p, int64_t chain_first, int64_t n, double* T_out, void* stream);
-// ... the same integrals of a Boomerang's arcs (pdmp_ensemble_bps_consume_arc_pairs; p.mu is the flow's centre): the same arguments and accumulators
-int launch_bps_arc_pairs(const BpsConsumeArgs& p, const BpsPairArgs& q, void* stream);
+int launch_bps_pairs(const BpsConsumeArgs& p, const BpsPairArgs& q, bool arc, void* stream);
+// T_last of chains [chain_first, chain_first + n) to T_out [n] (the pair and the histogram reads)
+int launch_bps_tlast(const BpsConsumeArgs& p, int64_t chain_first, int64_t n, double* T_out, void* stream);
 // ... the marginal histograms (pdmp_ensemble_bps_consume_hist): the listed coordinates [m] with their ranges and widths, the rows H
 // [nchains x m x (B + 2)] and the rest times Z [nchains x m]; launched before launch_bps_consume_events of the same slice
 struct BpsHistArgs {
